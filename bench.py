@@ -11,6 +11,9 @@ map are resident in HBM before the timed region.
 
 This file holds the headline only: world, timed region (`run_steps_sync`, `timed_block`), roofline, cpu_baseline and the
 JSON line.  Everything else the line reports is a side leg under tools/benchlegs/ (one module each, `run(E)`).
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last step (--dump-outputs DIR) and prints the
+line.  --full adds four more timed blocks (median, p95), the roofline (with its self-profiling PMC passes), cpu_baseline and
+the side legs; at more than one rank the map-sharded leg runs in either mode, because `value` is its figure there.
 `value` = N / the wall time of ONE synchronous cold linearize — SURVEY.md 8(d)'s definition and what the reference's callers
 do (geometric.cpp:194-196; GTSAM re-linearizes one factor at a time): the timed region is --steps such calls made back to back
 from C through the raw C ABI (tools/micro/sync_caller.c).  `value_pipelined` = the same work with <= 64 calls of the factor in
@@ -59,6 +62,11 @@ def parse():
     ap.add_argument("--hostile-poses", type=int, default=5, help="past scans per room the hostile map is built from")
     ap.add_argument("--sharded", action="store_true", help="(kept for old command lines: the map-sharded leg runs by default)")
     ap.add_argument("--shard-block-log2", type=int, default=3, help="shard blocks of 2^n voxels per axis (3: 4 m cubes at the 0.5 m leaf)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: spread blocks, roofline (incl. PMC passes), cpu_baseline + parity, the side legs "
+                         "(tools/benchlegs) and the map-sharded leg at one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step (one float64 .npy per IcpResult field, timings and call counter left out)")
     return ap.parse_args()
 
 
@@ -184,7 +192,7 @@ def timed_block(E, k, collect=None):
 
 
 def headline(E):
-    """Warm-up, THE timed region (exactly --steps steps) + four more blocks of the same size, kernel times by HIP events."""
+    """Warm-up, THE timed region (exactly --steps steps) + with --full four more blocks of the same size, kernel times by HIP events."""
     args = E.args
     event_every = max(1, min(args.event_every, args.steps // max(len(E.factors), 1)))
     for c in E.ctxs:
@@ -213,7 +221,7 @@ def headline(E):
         E.extra_untimed += args.steps
     outs = []
     block_s = [timed_block(E, args.steps, outs)]  # the timed region of the contract
-    if not args.profile_mode:
+    if args.full and not args.profile_mode:
         for _ in range(4):
             block_s.append(timed_block(E, args.steps, outs))  # spread (median, p95) + more bracketed launches
     k3_ms = np.array([o.gpu_ms_linearize for o in outs if o.gpu_ms_linearize >= 0], dtype=np.float64)
@@ -310,6 +318,17 @@ def cpu_baseline(E, last):
     return base, parity
 
 
+DUMP_SKIP = ("linearize_count", "gpu_ms_linearize", "gpu_ms_localizability")  # call counter and timings: not results
+
+
+def dump_outputs(out_dir, last):
+    """What the caller of the timed path received from its last step: one float64 .npy per IcpResult field (a few KB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in last.items():
+        if name not in DUMP_SKIP:
+            np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(v, dtype=np.float64))
+
+
 def main():
     args = parse()
     # ONE JSON line on stdout: everything else this process and its libraries write to fd 1 (RCCL's banner) goes to stderr
@@ -319,26 +338,26 @@ def main():
     E = setup(args)
     world, rank, n = E.world, E.rank, E.n_pts
     H = headline(E)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, H["last"])
     if args.profile_mode:
         args.no_cpu_baseline, args.concurrent_streams, args.headline_only = True, 0, True
     if world > 1:
         args.no_cpu_baseline = True  # cpu_baseline and the oracle-timed legs are N = 1, rank-0 figures
-    from benchlegs import (concurrent, frontend, keyframe, latency, pcie, photometric, replay_leg, sharded, small_cloud, variants, window,
-                           worlds)
     res = E.results
-    for leg in (() if args.headline_only else (concurrent, latency, window, photometric, keyframe, frontend, replay_leg, pcie, variants, small_cloud, worlds)):
-        try:
-            res.update(leg.run(E))
-        except Exception as exc:  # noqa: BLE001 - a side leg never costs the job its line
-            res[leg.__name__.split(".")[-1] + "_error"] = f"{type(exc).__name__}: {exc}"
+    if args.full and not args.headline_only:
+        from benchlegs import concurrent, frontend, keyframe, latency, pcie, photometric, replay_leg, small_cloud, variants, window, worlds
+        for leg in (concurrent, latency, window, photometric, keyframe, frontend, replay_leg, pcie, variants, small_cloud, worlds):
+            try:
+                res.update(leg.run(E))
+            except Exception as exc:  # noqa: BLE001 - a side leg never costs the job its line
+                res[leg.__name__.split(".")[-1] + "_error"] = f"{type(exc).__name__}: {exc}"
     last, hostile = H["last"], res.get("hostile_world")
     elapsed, block_s = H["elapsed"], H["block_s"]
     line = {
         "metric": "ICP corr+residual Mpts/sec, 131k-pt scan vs 5M-pt map, 1/2/4/8 GPU",
         "value": round(n * args.steps * world / elapsed / 1e6, 3), "unit": "Mpts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-        "ms_per_step_median": round(float(np.median(block_s)) / args.steps * 1e3, 5),
-        "ms_per_step_p95": round(float(np.percentile(block_s, 95)) / args.steps * 1e3, 5),
         "ms_per_step_blocks": [round(v / args.steps * 1e3, 5) for v in block_s],
         "untimed_steps_before_the_timed_region": args.warmup + getattr(E, "extra_untimed", 0),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -356,14 +375,20 @@ def main():
                 "valid_share": round(hostile["status_hist"][8] / max(n, 1), 4), "status_hist": hostile["status_hist"],
                 "mean_candidates": hostile.get("mean_candidates"), "H_rel_vs_oracle": (hostile.get("parity_vs_oracle") or {}).get("H_rel")},
         },
-        "roofline": roofline(E, H, res.pop("small_cloud", None), res.pop("_kernel_ms_back_to_back", None)),
         "setup_s": round(E.setup_s, 2),
     }
+    if args.full:
+        line["ms_per_step_median"] = round(float(np.median(block_s)) / args.steps * 1e3, 5)
+        line["ms_per_step_p95"] = round(float(np.percentile(block_s, 95)) / args.steps * 1e3, 5)
+        line["roofline"] = roofline(E, H, res.pop("small_cloud", None), res.pop("_kernel_ms_back_to_back", None))
     line.update(res)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"], line["parity_vs_oracle"] = cpu_baseline(E, last)
-    shd = None if args.headline_only else sharded.run(E, line, real_stdout)
-    line["sharded"] = shd
+    shd = None
+    if args.full or world > 1:  # at more than one rank `value` is the map-sharded figure
+        from benchlegs import sharded
+        shd = None if args.headline_only else sharded.run(E, line, real_stdout)
+        line["sharded"] = shd
     # ---- which figure is the metric.  SURVEY 8(d) defines it as N / the wall time of ONE cold linearize — what the reference's
     # callers do, and what `value` is.  With more than one rank `value` is the MAP-SHARDED factor (north_star's multi-GPU
     # design), one synchronous protocol round at a time, and the replica figure stands next to it as value_replica.

@@ -84,6 +84,10 @@ def _run_to(cmd: list, out: str, verbose: bool = False):
 def build(force: bool = False, verbose: bool = False, timeline: bool = False) -> str:
     """timeline=True builds the diagnostic variant libmimosa_hip_timeline.so (-DMH_TIMELINE:
     per-wave s_memtime stamps + mh_icp_timeline); never loaded by the product path."""
+    _refuse_stray_defines()
+    todo, _, lib, link = _plan(force, timeline)
+    if not todo and not link:
+        return lib  # up to date: nothing is written, so no lock either (the tree may be read-only to the process using it)
     with _BuildLock():
         return _build_locked(force, verbose, timeline)
 
@@ -111,37 +115,40 @@ def _refuse_stray_defines() -> None:
             raise RuntimeError(f"{var} carries an MH_* define ({val!r}): the product build takes no kernel knobs; use tools/variant.sh")
 
 
-def _build_locked(force: bool, verbose: bool, timeline: bool) -> str:
-    from concurrent.futures import ThreadPoolExecutor
-
-    _refuse_stray_defines()
-
-    os.makedirs(LIBDIR, exist_ok=True)
+def _plan(force: bool, timeline: bool):
+    """(objects to compile as (source, extra flags, object), every object, the library, whether to link it)"""
     objdir = os.path.join(HERE, "build_timeline" if timeline else "build")
-    os.makedirs(objdir, exist_ok=True)
-    hipcc = _hipcc()
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
-    objs, jobs = [], []
+    objs, todo = [], []
     for src, extra in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
-        d = o + ".d"
         objs.append(o)
         # an object is rebuilt when one of the files the compiler actually read for it changed (its -MMD record); without
         # a record, when the source or any header of the package changed
-        deps = _deps_of(d)
+        deps = _deps_of(o + ".d")
         if deps is not None and not all(os.path.exists(x) for x in deps):
             deps = None
         if force or _stale(o, deps if deps is not None else [s] + hdrs):
-            cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-DMH_BUILDING_LIBRARY", "-MMD", "-MF", d,
-                   "-Wno-unused-parameter", *extra, *(["-DMH_TIMELINE"] if timeline else []), "-c", s, "-o", o]
-            jobs.append((cmd, o))
+            todo.append((s, extra, o))
+    lib = LIB.replace(".so", "_timeline.so") if timeline else LIB
+    return todo, objs, lib, bool(todo) or force or _stale(lib, objs)
+
+
+def _build_locked(force: bool, verbose: bool, timeline: bool) -> str:
+    from concurrent.futures import ThreadPoolExecutor
+
+    os.makedirs(LIBDIR, exist_ok=True)
+    os.makedirs(os.path.join(HERE, "build_timeline" if timeline else "build"), exist_ok=True)
+    todo, objs, lib, link = _plan(force, timeline)  # again under the lock: a builder we waited for may have done it all
+    hipcc = _hipcc()
+    jobs = [([hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-DMH_BUILDING_LIBRARY", "-MMD", "-MF", o + ".d",
+              "-Wno-unused-parameter", *extra, *(["-DMH_TIMELINE"] if timeline else []), "-c", s, "-o", o], o) for s, extra, o in todo]
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
             for f in [ex.submit(_run_to, cmd, o, verbose) for cmd, o in jobs]:
                 f.result()
-    lib = LIB.replace(".so", "_timeline.so") if timeline else LIB
-    if force or _stale(lib, objs):
+    if link:
         cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib, *objs, "-ldl"]
         _run_to(cmd, lib, verbose)
     return lib
@@ -155,6 +162,8 @@ def build_replay_native(force: bool = False) -> str:
     src = os.path.join(host, "replay_main.cpp")
     deps = [src, lib] + [os.path.join(host, "mimosa_hip", h) for h in ("replay.hpp", "sharded_replay.hpp", "sharded.hpp", "manager.hpp", "binio.hpp", "photometric.hpp", "lidar.hpp", "types.hpp")]
     deps += [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(host, "gtsam_sig")) for f in fs]
+    if not (force or _stale(exe, deps)):
+        return exe  # up to date: no lock (see build())
     with _BuildLock():
         if force or _stale(exe, deps):
             _run_to(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.dirname(HERE), "-I", host, "-I", os.path.join(host, "gtsam_sig"), src, "-o", exe,
@@ -167,7 +176,8 @@ def build_sync_caller(force: bool = False) -> str:
     leg and tools/sync_probe.py.  Measurement harness, never loaded by the product path."""
     src = os.path.join(os.path.dirname(HERE), "tools", "micro", "sync_caller.c")
     out = os.path.join(LIBDIR, "libmh_sync_caller.so")
-    os.makedirs(LIBDIR, exist_ok=True)
+    if not (force or _stale(out, [src])):
+        return out  # up to date: no lock (see build())
     with _BuildLock():
         if force or _stale(out, [src]):
             _run_to(["gcc", "-O2", "-Wall", "-Wextra", "-shared", "-fPIC", src, "-o", out], out)

@@ -206,7 +206,9 @@ def test_scan_frontend_many_distinct_timestamps_and_device_input(ctx):
     assert info["n_unique_ns"] == len(o["unique_ns"]) and info["last_point_ns"] == o["last_point_ns"] == 0xFFFFFFFF
     assert np.array_equal(sc.unique_ns(), o["unique_ns"])
     _same_points(sc.points(capi.Scan.FULL), _as_points(o["points_full"]))
-    hip = C.CDLL("libamdhip64.so")
+    # the HIP runtime the library is bound to (a symbol lookup through its handle searches its dependencies): dlopen-ing
+    # "libamdhip64.so" by name could load a second runtime, e.g. the ROCm install's beside the copy torch brought in first
+    hip = capi.load()
     d_raw = C.c_void_p()
     assert hip.hipMalloc(C.byref(d_raw), C.c_size_t(raw.nbytes)) == 0
     assert hip.hipMemcpy(d_raw, C.c_void_p(raw.ctypes.data), C.c_size_t(raw.nbytes), 1) == 0
