@@ -174,6 +174,7 @@ int mh_abi_version(void);
 /* Binds a context to HIP device `device` and creates its stream.  MH_ERR_NO_DEVICE if there is no
  * GPU: there is no CPU fallback. */
 int mh_init(int device, mh_ctx ** out);
+/* Sharded factors and communicators may outlive the context: see the teardown rule at mh_shard_icp_destroy. */
 void mh_shutdown(mh_ctx * ctx);
 /* Last error text for this context (or the calling thread when ctx == NULL). */
 const char * mh_last_error(const mh_ctx * ctx);
@@ -573,6 +574,7 @@ int mh_shard_unique_id(void * id128);
 int mh_shard_comm_init_rccl(mh_ctx * ctx, const void * id128, int world, int rank, mh_shard_comm ** out);
 /* Test transport: `world` ranks inside ONE process (one host thread per rank, all on one device); out_array[world]. */
 int mh_shard_comm_init_local(int world, mh_shard_comm ** out_array);
+/* Any time, before or after its factors and contexts: see the teardown rule at mh_shard_icp_destroy. */
 void mh_shard_comm_destroy(mh_shard_comm * comm);
 int mh_shard_comm_world(const mh_shard_comm * comm);
 int mh_shard_comm_rank(const mh_shard_comm * comm);
@@ -615,6 +617,16 @@ int mh_shard_icp_set_components(mh_shard_icp * icp, int enabled); /* as mh_icp_s
 int mh_shard_icp_get_state(mh_shard_icp * icp, uint64_t * origin, int32_t * status, double * means, double * normals,
                            size_t capacity, size_t * n_out);
 int mh_shard_icp_stats(const mh_shard_icp * icp, mh_shard_stats * out);
+/* Teardown rule.  A context (mh_shutdown), a communicator (mh_shard_comm_destroy) and a sharded factor (mh_shard_icp_destroy)
+ * may be torn down in any order.
+ * - A sharded factor whose context was shut down gave its device memory back in mh_shutdown; afterwards it can only be
+ *   destroyed and asked for mh_shard_icp_stats, every other call fails ("the factor's context was shut down").
+ * - A sharded factor whose communicator was destroyed can no longer linearize or wait ("the factor's communicator was
+ *   destroyed"); it is to be destroyed, mh_shard_icp_stats still answers.  With both gone, the context's message is the one.
+ * - A communicator whose context was shut down lets go of it; its next factor's context takes its place.
+ * - The rounds in flight of a communicator, and the calls waiting to be repeated, are dropped when the context they run on
+ *   is shut down or the communicator is destroyed: their factors' results are never filled, and the factors can only be
+ *   destroyed. */
 void mh_shard_icp_destroy(mh_shard_icp * icp);
 
 /* ---- diagnostics -------------------------------------------------------------------------------------------------------

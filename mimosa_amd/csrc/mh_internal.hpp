@@ -44,6 +44,10 @@ struct mh_ctx
   size_t d_scratch_cap = 0;
   hipStream_t copy_stream = nullptr;  // mh_scan_prefetch: uploads beside the compute stream (created on first use: an HSA queue costs ~1 ms)
   std::mutex copy_mu;
+  // what mh_shutdown takes back from the sharded handles (shard_api.hip): the sharded factors created on this context, and
+  // the communicators whose rounds run on it
+  std::vector<mh_shard_icp *> shard_factors;
+  std::vector<mh_shard_comm *> shard_comms;
 };
 
 // The stream of the context the calling thread is working for (set by mh_enter at every entry point): what the allocation
@@ -639,6 +643,6 @@ int icp_create(mh_ctx * ctx, mh_map * map, const mh_point32 * source, const mh_p
 // argument blocks of one linearize call in pending slot n_pending (claimed); no launch
 int prepare(mh_icp * icp, const double R_src[9], const double t_src[3], const double * R_tgt, const double * t_tgt, const double g_unit[3],
             mh_icp_result * out, bool want_flag, mh::IcpArgs & a, mh::LocArgs & l);
-// shard_api.hip: called by mh_shutdown(ctx) so that communicators whose rounds ran on ctx let go of it
+// shard_api.hip: called by mh_shutdown(ctx) so that the sharded handles listed on ctx let go of it
 void shard_ctx_gone(mh_ctx * ctx);
 }  // namespace mhi

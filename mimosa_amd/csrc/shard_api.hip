@@ -202,7 +202,7 @@ struct mh_shard_comm
   long long n_all_to_all = 0, n_all_reduce = 0;
   // protocol rounds in flight (FIFO: one stream, so they complete in order) and what they share: the exchange buffers are
   // reused in stream order, the publish slots form a ring in mapped pinned memory (kShardRing x ring_width entries)
-  mh_ctx * ws_ctx = nullptr;
+  mh_ctx * ws_ctx = nullptr;  // (set by comm_bind only: the context lists the communicator in shard_comms)
   std::deque<ShardRound> rounds;
   DevBuf ws_send, ws_recv, ws_ar, ws_loc;
   mh::ShardPublish * h_ring = nullptr;
@@ -215,7 +215,7 @@ struct mh_shard_comm
   std::vector<CapUpdate> cap_updates;  // in round order (rounds complete in order)
   bool repairing = false;              // run_repairs is on the stack: its own enqueues must not start another one
   std::vector<mh_shard_icp *> plain_pending;  // one rank, no protocol: the factors with mh_icp_linearize_async calls to collect
-  std::vector<mh_shard_icp *> factors;        // every live factor of this communicator (a communicator destroyed first orphans them)
+  std::vector<mh_shard_icp *> factors;        // every live factor with S->comm == this (a communicator destroyed first orphans them)
 
   int peer_missing()
   {
@@ -275,8 +275,8 @@ struct mh_shard_comm
 
 struct mh_shard_icp
 {
-  mh_ctx * ctx = nullptr;
-  mh_shard_comm * comm = nullptr;
+  mh_ctx * ctx = nullptr;          // null: mh_shutdown of the context ran first (shard_ctx_gone), the handle can only be destroyed
+  mh_shard_comm * comm = nullptr;  // set exactly while the factor is in comm->factors
   mh_icp * icp = nullptr;
   bool collective = false;
   int block_log2 = 3;
@@ -294,14 +294,19 @@ struct mh_shard_icp
   uint32_t seg_cap = 0, seg_cap_max = 0;
   uint64_t n_total = 0;
   bool broken = false;  // a collective call failed half way (records sent, slots tombstoned): the factor's state is not to be trusted
-  bool ctx_gone = false;  // mh_shutdown of the factor's context ran first (shard_ctx_gone): ctx and icp are null, the handle can only be destroyed
-  int last_linearize_count = 0;  // ... what mh_shard_icp_stats still reports then
+  int last_linearize_count = 0;  // what mh_shard_icp_stats still reports once the context is gone (icp null)
   mh_shard_stats stats{};
 };
 
 namespace
 {
 int ensure_ring(mh_ctx * ctx, mh_shard_comm * comm, size_t width);
+int fail_rounds(mh_shard_comm * comm, int rc);
+template <typename T>
+void erase_value(std::vector<T *> & v, const T * x)
+{
+  v.erase(std::remove(v.begin(), v.end(), x), v.end());
+}
 mh::ShardArrays arrays_of(mh_icp * icp, bool alt)
 {
   mh::ShardArrays a;
@@ -425,37 +430,48 @@ void global_result(mh_shard_icp * S, const mh::ShardPublish & p, const PendingCa
 }
 }  // namespace
 
-// Every live communicator, so that a context that goes away first (mh_shutdown) can take back what the communicator holds on it.
-static std::mutex g_comm_mu;
-static std::vector<mh_shard_comm *> g_comms;
-
-static void comm_register(mh_shard_comm * c)
+// The context a communicator's rounds run on (ws_ctx; null: none).  The context lists the communicator, so that its
+// mh_shutdown finds what the communicator holds on it.
+static void comm_bind(mh_shard_comm * comm, mh_ctx * ctx)
 {
-  std::lock_guard<std::mutex> g(g_comm_mu);
-  g_comms.push_back(c);
+  if (comm->ws_ctx == ctx) return;
+  if (comm->ws_ctx) erase_value(comm->ws_ctx->shard_comms, comm);
+  if (ctx) ctx->shard_comms.push_back(comm);
+  comm->ws_ctx = ctx;
 }
 
-// Detach a communicator from the context its rounds run on: rounds nobody waited for are dropped (their factors can
-// only be destroyed afterwards), the exchange buffers and the publish ring go back once the stream has drained.
+// Detach a communicator from the context its rounds run on: rounds nobody waited for and calls waiting to be repeated are
+// dropped (their factors are broken and can only be destroyed), the exchange buffers and the publish ring go back once the
+// stream has drained.
 static void comm_release_ctx(mh_shard_comm * comm)
 {
   if (!comm->ws_ctx) return;
   (void)mh_enter(comm->ws_ctx);
   (void)hipStreamSynchronize(comm->ws_ctx->stream);
-  for (ShardRound & r : comm->rounds)
-    for (ShardCall & c : r.calls)
-      if (c.S) {
-        c.S->inflight = 0;
-        c.S->broken = true;
-        c.S->comm = nullptr;
-      }
-  comm->rounds.clear();
+  fail_rounds(comm, MH_OK);
   comm->cap_updates.clear();
   for (DevBuf * b : {&comm->ws_send, &comm->ws_recv, &comm->ws_ar, &comm->ws_loc}) b->release(true);
   if (comm->h_ring) AllocCache::free_pinned(comm->h_ring, sizeof(mh::ShardPublish) * comm->ring_width * kShardRing);
   comm->h_ring = comm->d_h_ring = nullptr;
   comm->ring_width = 0;
-  comm->ws_ctx = nullptr;
+  comm_bind(comm, nullptr);
+}
+
+// Take one factor out of its communicator's queues: its part of the rounds in flight (the rounds stay, other factors'
+// results are in them), its calls waiting to be repeated, its parked capacity decisions (complete_front; they must not be
+// applied to freed memory later) and its plain calls to collect.  It stays in comm->factors.
+static void comm_detach(mh_shard_icp * S)
+{
+  mh_shard_comm * comm = S->comm;
+  if (!comm) return;
+  for (ShardRound & r : comm->rounds)
+    for (ShardCall & c : r.calls)
+      if (c.S == S) c.S = nullptr;
+  for (ShardCall & c : comm->repairs)
+    if (c.S == S) c.S = nullptr;
+  for (CapUpdate & u : comm->cap_updates)
+    if (u.S == S) u.S = nullptr;
+  erase_value(comm->plain_pending, S);
 }
 
 // Everything of a factor that lives on its context: device buffers, the inner plain factor.  The context must still be alive.
@@ -473,42 +489,31 @@ static void shard_release_device(mh_shard_icp * S)
 
 namespace mhi
 {
-// mh_shutdown(ctx), before the stream goes: communicators whose rounds ran on ctx let go of it (a later
+// mh_shutdown(ctx), before the stream goes: the communicators whose rounds run on ctx let go of it (a later
 // mh_shard_comm_destroy must not touch a dead context; a later mh_shard_icp_create may bind a new one), and the sharded
 // factors of ctx give their device memory back NOW, while the context is alive — afterwards such a handle holds no pointer
-// into the dead context (ctx, icp null; ctx_gone set): every entry point refuses it and mh_shard_icp_destroy just deletes it.
+// into the dead context (ctx, icp null): every entry point refuses it and mh_shard_icp_destroy just deletes it.  Only
+// what ctx lists is touched.
 void shard_ctx_gone(mh_ctx * ctx)
 {
-  std::lock_guard<std::mutex> g(g_comm_mu);
-  for (mh_shard_comm * c : g_comms) {
-    bool any = c->ws_ctx == ctx;
-    for (mh_shard_icp * S : c->factors) any = any || S->ctx == ctx;
-    if (!any) continue;
-    if (c->ws_ctx == ctx) comm_release_ctx(c);  // (synchronises the stream; drops the rounds)
-    for (mh_shard_icp * S : c->factors)
-      if (S->ctx == ctx) {
-        S->broken = true;
-        S->inflight = 0;
-        for (ShardCall & q : c->repairs)
-          if (q.S == S) q.S = nullptr;
-        for (CapUpdate & u : c->cap_updates)
-          if (u.S == S) u.S = nullptr;
-        auto & pend = c->plain_pending;
-        pend.erase(std::remove(pend.begin(), pend.end(), S), pend.end());
-        (void)mh_enter(ctx);
-        (void)hipStreamSynchronize(ctx->stream);
-        shard_release_device(S);
-        S->ctx = nullptr;
-        S->ctx_gone = true;
-      }
+  while (!ctx->shard_comms.empty()) comm_release_ctx(ctx->shard_comms.back());  // (each unbinds itself from ctx)
+  (void)mh_enter(ctx);
+  (void)hipStreamSynchronize(ctx->stream);
+  for (mh_shard_icp * S : ctx->shard_factors) {
+    comm_detach(S);
+    S->broken = true;
+    S->inflight = 0;
+    shard_release_device(S);
+    S->ctx = nullptr;
   }
+  ctx->shard_factors.clear();
 }
 }  // namespace mhi
 
 // every entry point but destroy: a factor whose context was shut down first
 #define MH_SHARD_ALIVE(S, who)                                                                                                      \
   do {                                                                                                                              \
-    if ((S) && (S)->ctx_gone) return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the factor's context was shut down; the handle can only be destroyed"); \
+    if ((S) && !(S)->ctx) return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the factor's context was shut down; the handle can only be destroyed"); \
   } while (0)
 
 extern "C" {
@@ -551,7 +556,6 @@ int mh_shard_comm_init_rccl(mh_ctx * ctx, const void * id128, int world, int ran
       delete c;
       return fail(ctx, MH_ERR_HIP, msg);
     }
-    comm_register(c);
     *out = c;
     return MH_OK;
   });
@@ -572,7 +576,6 @@ int mh_shard_comm_init_local(int world, mh_shard_comm ** out_array)
       c->world = world;
       c->rank = r;
       c->grp = g;
-      comm_register(c);
       out_array[r] = c;
     }
     return MH_OK;
@@ -582,10 +585,6 @@ int mh_shard_comm_init_local(int world, mh_shard_comm ** out_array)
 void mh_shard_comm_destroy(mh_shard_comm * comm)
 {
   if (!comm) return;
-  {
-    std::lock_guard<std::mutex> g(g_comm_mu);
-    g_comms.erase(std::remove(g_comms.begin(), g_comms.end(), comm), g_comms.end());
-  }
   comm_release_ctx(comm);
   for (mh_shard_icp * S : comm->factors) {  // factors that outlive their communicator can only be destroyed
     S->comm = nullptr;
@@ -627,27 +626,16 @@ int mh_shard_comm_info(const mh_shard_comm * comm, int * ranks_in_communicator, 
 void mh_shard_icp_destroy(mh_shard_icp * S)
 {
   if (!S) return;
-  if (S->ctx) {
+  if (S->comm) {
+    erase_value(S->comm->factors, S);
+    comm_detach(S);
+  }
+  if (S->ctx) {  // (a factor whose context went first gave everything back in shard_ctx_gone)
     (void)mh_enter(S->ctx);
     (void)hipStreamSynchronize(S->ctx->stream);
+    erase_value(S->ctx->shard_factors, S);
+    shard_release_device(S);
   }
-  if (S->comm) {
-    auto & all = S->comm->factors;
-    all.erase(std::remove(all.begin(), all.end(), S), all.end());
-  }
-  if (S->comm) {  // calls nobody waited for: the rounds stay (other factors' results are in them), this factor's part is dropped
-    for (ShardRound & r : S->comm->rounds)
-      for (ShardCall & c : r.calls)
-        if (c.S == S) c.S = nullptr;
-    for (ShardCall & c : S->comm->repairs)
-      if (c.S == S) c.S = nullptr;
-    // capacity decisions parked for this factor (complete_front) must not be applied to freed memory later
-    for (CapUpdate & u : S->comm->cap_updates)
-      if (u.S == S) u.S = nullptr;
-    auto & pend = S->comm->plain_pending;
-    pend.erase(std::remove(pend.begin(), pend.end(), S), pend.end());
-  }
-  if (S->ctx) shard_release_device(S);  // (a factor whose context went first gave everything back in shard_ctx_gone)
   delete S;
 }
 
@@ -663,6 +651,7 @@ static int shard_icp_create_impl(mh_ctx * ctx, mh_shard_comm * comm, mh_map * ma
   MH_HIP(ctx, mh_enter(ctx));
   mh_shard_icp * S = new mh_shard_icp;
   S->ctx = ctx;
+  ctx->shard_factors.push_back(S);
   S->comm = comm;
   comm->factors.push_back(S);
   S->block_log2 = log2;
@@ -717,7 +706,7 @@ static int shard_icp_create_impl(mh_ctx * ctx, mh_shard_comm * comm, mh_map * ma
   MH_HIP(ctx, mh::launch_shard_state_init(S->d_state, static_cast<uint32_t>(n_local), ctx->stream));
   if (!comm->rounds.empty() && comm->ws_ctx != ctx) return bail(fail(ctx, MH_ERR_INVALID_ARG, "mh_shard_icp_create: the communicator has rounds in flight on another context"));
   if (comm->rounds.empty()) {
-    comm->ws_ctx = ctx;
+    comm_bind(comm, ctx);
     rc = ensure_ring(ctx, comm, 1);
     if (rc != MH_OK) return bail(rc);
   }
@@ -751,7 +740,8 @@ uint64_t arrivals_max_idle(const mh_shard_icp * S, uint32_t world, uint32_t cap)
 {
   return std::min<uint64_t>(static_cast<uint64_t>(world - 1) * cap, S->n_total - std::min<uint64_t>(S->n_total, S->n_live));
 }
-// once a round failed nothing in flight can be trusted: every factor with a pending call is in an unknown state
+// once a round failed (or the context the rounds run on goes: comm_release_ctx) nothing in flight can be trusted: every
+// factor with a pending call is in an unknown state
 int fail_rounds(mh_shard_comm * comm, int rc)
 {
   for (ShardRound & r : comm->rounds)
@@ -987,7 +977,7 @@ int enqueue_round(const RoundSpec * spec, size_t B)
   MH_HIP(ctx, mh_enter(ctx));
   if (comm->ws_ctx && comm->ws_ctx != ctx && !comm->rounds.empty())
     return fail(ctx, MH_ERR_INVALID_ARG, "mh_shard_icp_linearize: the communicator has rounds in flight on another context");
-  comm->ws_ctx = ctx;
+  comm_bind(comm, ctx);
   const uint32_t world = static_cast<uint32_t>(comm->world), rank = static_cast<uint32_t>(comm->rank);
   const unsigned long long index = comm->n_rounds;
   const long long coll_before = comm->n_all_to_all + comm->n_all_reduce;

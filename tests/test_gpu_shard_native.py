@@ -3,6 +3,7 @@ World > 1 runs over the in-process transport (ranks = threads on the one GPU of 
 fixed-size segments, tombstones, device-side slot counts, all-reduced sums, retries on overflow, compaction — against the
 unsharded oracle.  World 1 over RCCL (the only size a one-GPU box offers to RCCL) runs in a fresh process with the full
 protocol forced."""
+import itertools
 import os
 import subprocess
 import sys
@@ -234,6 +235,61 @@ def test_sharded_factor_outlives_its_context(small_world):
         assert st["linearize_count"] >= 1
         f.destroy()
         comm.destroy()
+
+
+@pytest.mark.parametrize("collective", [True, False], ids=["collective", "plain"])
+@pytest.mark.parametrize("in_flight", [True, False], ids=["in_flight", "idle"])
+@pytest.mark.parametrize("order", list(itertools.permutations(("ctx", "factor", "comm"))), ids="-".join)
+def test_teardown_in_any_order(small_world, order, in_flight, collective):
+    """Context (raw mh_shutdown), sharded factor and communicator torn down in each of the six orders, with a call left in
+    flight or not.  A factor whose context is gone refuses linearize and reset; one whose communicator alone is gone refuses
+    linearize; stats() answers throughout; and a fresh context, communicator and factor afterwards give the same result."""
+    from mimosa_amd import capi
+    w = small_world
+    rc = capi.make_reg_config(**w["cfg"])
+
+    def life():
+        c = capi.Context(0)
+        comm = capi.ShardComm.local(1)[0]
+        vmap = capi.VoxelMap(c)
+        capi.map_insert_shard(c, vmap, w["map_xyz"], 1, 0)
+        return c, comm, vmap, capi.ShardedICPFactor(c, comm, vmap, w["pts"], rc, force_collectives=collective)
+
+    c, comm, vmap, f = life()
+    want = f.linearize(w["R"], w["t"])
+    if in_flight:
+        f.linearize_async(w["R"], w["t"])
+    vmap.release()  # (the factor holds the map; nothing of it is left to release after the raw shutdown)
+    gone = set()
+    for step in order:
+        if step == "ctx":
+            c.L.mh_shutdown(c.h)  # the raw call: the Python binding would defer the shutdown until the factor is gone
+            c.h = None
+        elif step == "factor":
+            f.destroy()
+        else:
+            comm.destroy()
+        gone.add(step)
+        if "factor" in gone:
+            continue
+        if "ctx" in gone:
+            with pytest.raises(capi.MhError, match="context was shut down"):
+                f.reset()
+            with pytest.raises(capi.MhError, match="context was shut down"):
+                f.linearize(w["R"], w["t"])
+        elif "comm" in gone:
+            with pytest.raises(capi.MhError, match="communicator was destroyed"):
+                f.linearize(w["R"], w["t"])
+        st = f.stats()
+        assert st["world"] == 1 and st["collective"] == int(collective) and st["n_live"] == len(w["pts"]) and st["linearize_count"] >= 1
+
+    c, comm, vmap, f = life()
+    got = f.linearize(w["R"], w["t"])
+    assert np.array_equal(got["H_ss"], want["H_ss"]) and np.array_equal(got["b_s"], want["b_s"]) and got["f"] == want["f"]
+    f.destroy()
+    vmap.release()
+    comm.destroy()
+    c.close()
 
 
 def test_native_world1_over_rccl_full_protocol():
