@@ -519,6 +519,107 @@ int mh_photo_factor_get_state(const mh_photo_factor * factor, int32_t * statuses
 size_t mh_photo_factor_size(const mh_photo_factor * factor);
 
 
+/* ---- radar Doppler path: radar::Manager's front end + DopplerHessianFactor (SURVEY.md component #14) --------------------
+ * replaces src/radar/manager.cpp:111-181 (Manager::preprocess), include/mimosa/radar/utils.hpp:17-69 (TargetData,
+ * decodePointType), include/mimosa/radar/point.hpp (rioPoint, mmWavePoint) and include/mimosa/radar/factor.hpp:22-188
+ * (DopplerHessianFactor).  The targets stay on the device from the raw cloud to the Hessian: mh_radar_prepare_input ->
+ * mh_radar_factor_create_from_scan -> mh_radar_factor_linearize[_async | _batch].  What the caller supplies, as the
+ * reference's constructor takes it: T_B_S (config_.base.T_B_S) and the mean gyro rate over the exposure (manager.cpp:56-75,
+ * the IMU manager's job); keys are X(0), V(0), B(0) (manager.cpp:84-86).  The static / dynamic classification is not
+ * computed: the reference never fills it (factor.hpp:135-138, :190-193 are commented out). */
+typedef struct mh_radar_scan mh_radar_scan;
+typedef struct mh_radar_factor mh_radar_factor;
+
+/* radar::ManagerConfig, include/mimosa/radar/manager.hpp:20-33: the float fields the arithmetic reads (is_exposure_compensated
+ * and frame_ms only move the timestamp, manager.cpp:34; the host mirror applies them). */
+typedef struct mh_radar_config {
+  float range_min, range_max;
+  float threshold_azimuth_deg, threshold_elevation_deg;
+  float filter_min_db;
+  float noise_sigma;
+} mh_radar_config;
+
+/* radar::PType, include/mimosa/radar/utils.hpp:45-51 (Unknown has no value here: the caller has matched the fields) */
+typedef enum mh_radar_kind {
+  MH_RADAR_RIO = 0,                     /* rioPoint: x, y, z, snr_db, noise_db, v_doppler_mps (point.hpp:17-25) */
+  MH_RADAR_MMWAVE = 1,                  /* mmWavePoint: x, y, z, intensity, velocity (point.hpp:27-32) */
+  MH_RADAR_MMWAVE_DOPPLER_RESIDUAL = 2  /* recognised, but Manager::callback throws "Unsupported point type" (manager.cpp:43-54):
+                                           MH_ERR_UNSUPPORTED */
+} mh_radar_kind;
+/* Where the fields sit in a sensor_msgs::PointCloud2 record: the radar counterpart of mh_point_layout.  Every field is a
+ * float; point_step and the offsets are multiples of 4.  RIO: off_intensity = snr_db, off_velocity = v_doppler_mps. */
+typedef struct mh_radar_layout {
+  int32_t kind; /* mh_radar_kind */
+  uint32_t point_step;
+  uint32_t off_x, off_y, off_z, off_intensity, off_velocity;
+} mh_radar_layout;
+
+/* radar::TargetData, include/mimosa/radar/utils.hpp:17-41 (same field order) */
+typedef struct mh_radar_target {
+  double x, y, z, range, azimuth, elevation, radial_speed, intensity;
+} mh_radar_target;
+
+/* RadarManagerDebug's counts (manager.cpp:135, :81) */
+typedef struct mh_radar_info {
+  uint64_t n_points_in, n_points_valid;
+} mh_radar_info;
+
+/* What gtsam::HessianFactor(X, V, B, G11, G12, G13, g1, G22, G23, g2, G33, g3, f) receives from
+ * DopplerHessianFactor::linearize (factor.hpp:185-186); blocks row-major: G11 6x6, G12 6x3, G13 6x6, G22 3x3, G23 3x6,
+ * G33 6x6.  The translation columns of X and the accelerometer columns of B are exactly 0.0. */
+typedef struct mh_radar_result {
+  double G11[36], G12[18], G13[36], G22[9], G23[18], G33[36];
+  double g1[6], g2[3], g3[6];
+  double f;
+  uint64_t n_targets;
+  float gpu_ms; /* kernel time of this call (of the whole batch for mh_radar_factor_linearize_batch), -1 unless
+                   mh_set_profiling is on */
+} mh_radar_result;
+
+/* The largest window mh_radar_factor_linearize_batch takes in one call. */
+#define MH_RADAR_MAX_BATCH 1024
+
+int mh_radar_scan_create(mh_ctx * ctx, mh_radar_scan ** out);
+void mh_radar_scan_destroy(mh_radar_scan * scan); /* waits for a call in flight on the scan */
+/* Manager::preprocess<rioPoint | mmWavePoint> (manager.cpp:111-181): raw = n host records laid out as `layout` says; the
+ * rioPoint remap (x' = y, y' = -x, intensity = snr_db, velocity = v_doppler_mps), the NaN, filter_min_db, range and angle
+ * gates and the order-preserving compaction into valid_targets_ run in one kernel, the targets stay on the device.  The
+ * arithmetic is the reference's float arithmetic (radar_kernels.hip explains the one-ulp caveat of atan2f).
+ * info (may be NULL): n_points_in, n_points_valid. */
+int mh_radar_prepare_input(mh_radar_scan * scan, const void * raw, size_t n, const mh_radar_layout * layout,
+                           const mh_radar_config * cfg, mh_radar_info * info);
+/* valid_targets_ of the last mh_radar_prepare_input; out may be NULL to ask for the count. */
+int mh_radar_get_targets(const mh_radar_scan * scan, mh_radar_target * out, size_t capacity, size_t * n_out);
+/* DopplerHessianFactor ctor (factor.hpp:54-65) from a host TargetVector: targets (copied), pose_R_B = T_B_S (R row-major, t),
+ * angular_velocity_B, noise_sigma (the manager passes its float config value, manager.cpp:84-86). */
+int mh_radar_factor_create(mh_ctx * ctx, const mh_radar_target * targets, size_t n, const double R_B_S[9], const double t_B_S[3],
+                           const double angular_velocity_B[3], double noise_sigma, mh_radar_factor ** out);
+/* The same from the scan's valid_targets_, device to device (the scan may be prepared again or destroyed afterwards). */
+int mh_radar_factor_create_from_scan(const mh_radar_scan * scan, const double R_B_S[9], const double t_B_S[3],
+                                     const double angular_velocity_B[3], double noise_sigma, mh_radar_factor ** out);
+/* clone() (factor.hpp:69-73): a copy with its own targets. */
+int mh_radar_factor_clone(const mh_radar_factor * factor, mh_radar_factor ** out);
+void mh_radar_factor_destroy(mh_radar_factor * factor); /* waits for a call in flight */
+size_t mh_radar_factor_size(const mh_radar_factor * factor); /* targets_.size() */
+/* linearize(Values) (factor.hpp:98-188): R_W_B = rotation of Values[X] (its translation is not read), v_W = Values[V],
+ * bias_gyro = Values[B].gyroscope().  Blocks until the result is on the host.  No targets: all zeros. */
+int mh_radar_factor_linearize(mh_radar_factor * factor, const double R_W_B[9], const double v_W[3], const double bias_gyro[3],
+                              mh_radar_result * out);
+/* The same enqueued on the context stream without waiting (next to mh_icp_linearize_batch / mh_photo_factor_linearize_async);
+ * mh_radar_factor_wait blocks and fills *out.  One call in flight per factor. */
+int mh_radar_factor_linearize_async(mh_radar_factor * factor, const double R_W_B[9], const double v_W[3], const double bias_gyro[3]);
+int mh_radar_factor_wait(mh_radar_factor * factor, mh_radar_result * out);
+/* Every live radar factor of the window re-linearized in ONE kernel launch (graph::Manager re-linearizes each of them per
+ * update).  All factors on one context, none with a call in flight, 1 <= n_factors <= MH_RADAR_MAX_BATCH, else
+ * MH_ERR_INVALID_ARG.  Arrays are n_factors long: R_W_B[9 n], v_W[3 n], bias_gyro[3 n], out[n].  A factor's result is
+ * bit-identical to its own mh_radar_factor_linearize.  Blocks. */
+int mh_radar_factor_linearize_batch(mh_radar_factor * const * factors, size_t n_factors, const double * R_W_B, const double * v_W,
+                                    const double * bias_gyro, mh_radar_result * out);
+/* Parity tooling: per target at the state of the last linearize, e_whitened = e / noise_sigma before the robust weight
+ * (factor.hpp:157-160) and weight (:162-164); either pointer may be NULL.  MH_ERR_INVALID_ARG before the first linearize. */
+int mh_radar_factor_get_residuals(const mh_radar_factor * factor, double * e_whitened, double * weight);
+
+
 /* ---- map sharded across GPUs (BASELINE configs[2]): what both the library's own exchange (below) and a
  * framework that owns the stream need ------------------------------------------------------------------------------------
  * No reference counterpart: the reference is single-process.  The map is partitioned into shard blocks of 2^block_log2 voxels

@@ -35,6 +35,9 @@ EXPORTS = [
     "mh_photo_create", "mh_photo_destroy", "mh_photo_preprocess", "mh_scan_keep_raw", "mh_photo_preprocess_scan", "mh_photo_preprocess_scan_begin", "mh_photo_preprocess_commit", "mh_photo_detect_prefetch", "mh_photo_get_image",
     "mh_photo_num_features", "mh_photo_get_features", "mh_photo_set_features", "mh_photo_detect_features", "mh_photo_update_map",
     "mh_photo_factor_create", "mh_photo_factor_clone", "mh_photo_factor_destroy", "mh_photo_factor_linearize", "mh_photo_factor_linearize_async", "mh_photo_factor_wait", "mh_photo_factor_get_state", "mh_photo_factor_size",
+    "mh_radar_scan_create", "mh_radar_scan_destroy", "mh_radar_prepare_input", "mh_radar_get_targets", "mh_radar_factor_create",
+    "mh_radar_factor_create_from_scan", "mh_radar_factor_clone", "mh_radar_factor_destroy", "mh_radar_factor_size", "mh_radar_factor_linearize",
+    "mh_radar_factor_linearize_async", "mh_radar_factor_wait", "mh_radar_factor_linearize_batch", "mh_radar_factor_get_residuals",
 ]
 
 
@@ -238,6 +241,61 @@ class PhotoResult(C.Structure):
         return d
 
 
+MH_RADAR_RIO, MH_RADAR_MMWAVE, MH_RADAR_MMWAVE_DOPPLER_RESIDUAL = range(3)
+MH_RADAR_MAX_BATCH = 1024
+
+
+class RadarConfig(C.Structure):
+    """radar::ManagerConfig's float fields (include/mimosa/radar/manager.hpp:20-33)"""
+    _fields_ = [(n, C.c_float) for n in ("range_min", "range_max", "threshold_azimuth_deg", "threshold_elevation_deg",
+                                          "filter_min_db", "noise_sigma")]
+
+
+class RadarLayout(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("point_step", C.c_uint32), ("off_x", C.c_uint32), ("off_y", C.c_uint32), ("off_z", C.c_uint32),
+                ("off_intensity", C.c_uint32), ("off_velocity", C.c_uint32)]
+
+
+class RadarTarget(C.Structure):
+    """radar::TargetData (include/mimosa/radar/utils.hpp:17-41)"""
+    _fields_ = [(n, C.c_double) for n in ("x", "y", "z", "range", "azimuth", "elevation", "radial_speed", "intensity")]
+
+
+RADAR_TARGET_DTYPE = np.dtype([(n, np.float64) for n, _ in RadarTarget._fields_])
+
+
+class RadarInfo(C.Structure):
+    _fields_ = [("n_points_in", C.c_uint64), ("n_points_valid", C.c_uint64)]
+
+
+class RadarResult(C.Structure):
+    _fields_ = [
+        ("G11", C.c_double * 36), ("G12", C.c_double * 18), ("G13", C.c_double * 36), ("G22", C.c_double * 9),
+        ("G23", C.c_double * 18), ("G33", C.c_double * 36), ("g1", C.c_double * 6), ("g2", C.c_double * 3), ("g3", C.c_double * 6),
+        ("f", C.c_double), ("n_targets", C.c_uint64), ("gpu_ms", C.c_float),
+    ]
+    SHAPES = {"G11": (6, 6), "G12": (6, 3), "G13": (6, 6), "G22": (3, 3), "G23": (3, 6), "G33": (6, 6)}
+
+    def as_dict(self):
+        d = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            d[name] = np.array(v) if hasattr(v, "__len__") else v
+        for k, shp in self.SHAPES.items():
+            d[k] = d[k].reshape(shp)
+        return d
+
+
+def make_radar_config(range_min=0.1, range_max=20.0, threshold_azimuth_deg=60.0, threshold_elevation_deg=60.0,
+                      filter_min_db=5.0, noise_sigma=0.1) -> RadarConfig:
+    """Defaults of radar::ManagerConfig (manager.hpp:24-32)."""
+    return RadarConfig(range_min, range_max, threshold_azimuth_deg, threshold_elevation_deg, filter_min_db, noise_sigma)
+
+
+def radar_layout(kind: int, point_step: int, off_x: int, off_y: int, off_z: int, off_intensity: int, off_velocity: int) -> RadarLayout:
+    return RadarLayout(kind, point_step, off_x, off_y, off_z, off_intensity, off_velocity)
+
+
 PHOTO_IMAGES = {"intensity": (0, np.float32, 1), "range": (1, np.float32, 1), "dx": (2, np.float32, 1), "dy": (3, np.float32, 1),
                 "mask": (4, np.uint8, 1), "idx": (5, np.int32, 1), "yaw": (6, np.float32, 1), "proj_idx": (7, np.int32, 10),
                 "grad": (8, np.uint8, 1), "detection_mask": (9, np.uint8, 1)}
@@ -426,6 +484,23 @@ def load(build_if_missing: bool = True):
     L.mh_photo_factor_get_state.argtypes = [vp, vp, vp, vp]
     L.mh_photo_factor_size.argtypes = [vp]
     L.mh_photo_factor_size.restype = sz
+    L.mh_radar_scan_create.argtypes = [vp, pvp]
+    L.mh_radar_scan_destroy.argtypes = [vp]
+    L.mh_radar_scan_destroy.restype = None
+    L.mh_radar_prepare_input.argtypes = [vp, vp, sz, C.POINTER(RadarLayout), C.POINTER(RadarConfig), C.POINTER(RadarInfo)]
+    L.mh_radar_get_targets.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    L.mh_radar_factor_create.argtypes = [vp, vp, sz, vp, vp, vp, C.c_double, pvp]
+    L.mh_radar_factor_create_from_scan.argtypes = [vp, vp, vp, vp, C.c_double, pvp]
+    L.mh_radar_factor_clone.argtypes = [vp, pvp]
+    L.mh_radar_factor_destroy.argtypes = [vp]
+    L.mh_radar_factor_destroy.restype = None
+    L.mh_radar_factor_size.argtypes = [vp]
+    L.mh_radar_factor_size.restype = sz
+    L.mh_radar_factor_linearize.argtypes = [vp, vp, vp, vp, C.POINTER(RadarResult)]
+    L.mh_radar_factor_linearize_async.argtypes = [vp, vp, vp, vp]
+    L.mh_radar_factor_wait.argtypes = [vp, C.POINTER(RadarResult)]
+    L.mh_radar_factor_linearize_batch.argtypes = [vp, sz, vp, vp, vp, vp]
+    L.mh_radar_factor_get_residuals.argtypes = [vp, vp, vp]
     _LIB = L
     return L
 
@@ -1109,3 +1184,117 @@ class PhotoFactor:
             self.destroy()
         except Exception:
             pass
+
+
+class RadarScan:
+    """radar::Manager's front end (src/radar/manager.cpp:111-181) with valid_targets_ kept on the device."""
+
+    def __init__(self, ctx: Context):
+        self.ctx, self.L = ctx, ctx.L
+        h = C.c_void_p()
+        ctx.check(self.L.mh_radar_scan_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._children += 1
+
+    def prepare_input(self, raw: np.ndarray, layout: RadarLayout, cfg: RadarConfig, n: int | None = None) -> dict:
+        """raw: the records as bytes (any numpy array, C-contiguous); n: number of records (default: raw.nbytes // point_step)."""
+        raw = np.ascontiguousarray(raw)
+        n = raw.nbytes // layout.point_step if n is None else n
+        info = RadarInfo()
+        self.ctx.check(self.L.mh_radar_prepare_input(self.h, _p(raw), n, C.byref(layout), C.byref(cfg), C.byref(info)))
+        return {"n_points_in": int(info.n_points_in), "n_points_valid": int(info.n_points_valid)}
+
+    def targets(self) -> np.ndarray:
+        n = C.c_size_t()
+        self.ctx.check(self.L.mh_radar_get_targets(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, RADAR_TARGET_DTYPE)
+        self.ctx.check(self.L.mh_radar_get_targets(self.h, _p(out), n.value, C.byref(n)))
+        return out
+
+    def destroy(self):
+        if getattr(self, "h", None):
+            self.L.mh_radar_scan_destroy(self.h)
+            self.h = None
+            self.ctx._child_released()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class RadarFactor:
+    """radar::DopplerHessianFactor counterpart (include/mimosa/radar/factor.hpp:22-188).  targets: a structured array of
+    RADAR_TARGET_DTYPE (or n x 8 doubles in TargetData's field order), or a prepared RadarScan (device to device)."""
+
+    def __init__(self, ctx: Context, targets, R_B_S, t_B_S, angular_velocity_B, noise_sigma, _clone_of=None):
+        self.ctx, self.L = ctx, ctx.L
+        h = C.c_void_p()
+        if _clone_of is not None:
+            ctx.check(self.L.mh_radar_factor_clone(_clone_of.h, C.byref(h)))
+        else:
+            R, t, w = _f64(R_B_S), _f64(t_B_S), _f64(angular_velocity_B)
+            if isinstance(targets, RadarScan):
+                ctx.check(self.L.mh_radar_factor_create_from_scan(targets.h, _p(R), _p(t), _p(w), float(noise_sigma), C.byref(h)))
+            else:
+                tg = np.ascontiguousarray(targets)
+                tg = tg.view(np.float64).reshape(-1, 8) if tg.dtype.names else np.ascontiguousarray(tg, np.float64).reshape(-1, 8)
+                ctx.check(self.L.mh_radar_factor_create(ctx.h, _p(tg), tg.shape[0], _p(R), _p(t), _p(w), float(noise_sigma), C.byref(h)))
+        self.h = h
+        self.n = int(self.L.mh_radar_factor_size(h))
+        ctx._children += 1
+
+    def linearize(self, R_W_B, v_W, bias_gyro) -> dict:
+        """linearize(Values) (:98-188): R_W_B = Values[X].rotation(), v_W = Values[V], bias_gyro = Values[B].gyroscope()."""
+        out = RadarResult()
+        R, v, b = _f64(R_W_B), _f64(v_W), _f64(bias_gyro)
+        self.ctx.check(self.L.mh_radar_factor_linearize(self.h, _p(R), _p(v), _p(b), C.byref(out)))
+        return out.as_dict()
+
+    def linearize_async(self, R_W_B, v_W, bias_gyro):
+        R, v, b = _f64(R_W_B), _f64(v_W), _f64(bias_gyro)
+        self.ctx.check(self.L.mh_radar_factor_linearize_async(self.h, _p(R), _p(v), _p(b)))
+
+    def wait(self) -> dict:
+        out = RadarResult()
+        self.ctx.check(self.L.mh_radar_factor_wait(self.h, C.byref(out)))
+        return out.as_dict()
+
+    def clone(self) -> "RadarFactor":
+        """clone() (factor.hpp:69-73)"""
+        return RadarFactor(self.ctx, None, None, None, None, None, _clone_of=self)
+
+    def residuals(self):
+        """(e_whitened before the robust weight, weight) per target at the state of the last linearize."""
+        e, w = np.empty(self.n), np.empty(self.n)
+        self.ctx.check(self.L.mh_radar_factor_get_residuals(self.h, _p(e), _p(w)))
+        return e, w
+
+    def destroy(self):
+        if getattr(self, "h", None):
+            self.L.mh_radar_factor_destroy(self.h)
+            self.h = None
+            self.ctx._child_released()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def radar_linearize_batch(factors, R_W_Bs, v_Ws, bias_gyros) -> list:
+    """Every factor re-linearized in ONE kernel launch (mh_radar_factor_linearize_batch); the factors share one context."""
+    n = len(factors)
+    L = factors[0].L if n else load()
+    hs = (C.c_void_p * max(n, 1))(*[f.h for f in factors])
+    R = _f64(R_W_Bs).reshape(-1)
+    v = _f64(v_Ws).reshape(-1)
+    b = _f64(bias_gyros).reshape(-1)
+    out = (RadarResult * max(n, 1))()
+    rc = L.mh_radar_factor_linearize_batch(hs, n, _p(R), _p(v), _p(b), out)
+    if rc != MH_OK:
+        ctx = factors[0].ctx if n else None
+        raise MhError(rc, (L.mh_last_error(ctx.h if ctx else None) or b"").decode())
+    return [out[i].as_dict() for i in range(n)]
