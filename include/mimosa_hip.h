@@ -513,6 +513,28 @@ int mh_photo_factor_linearize(mh_photo_factor * factor, const double R_b[9], con
 int mh_photo_factor_linearize_async(mh_photo_factor * factor, const double R_b[9], const double t_b[3], const double * R_a,
                                     const double * t_a);
 int mh_photo_factor_wait(mh_photo_factor * factor, mh_photo_result * out);
+/* The largest window mh_photo_factor_linearize_batch takes in one call. */
+#define MH_PHOTO_MAX_BATCH 256
+/* A window of factors linearized in ONE kernel launch (the smoother re-linearizes every live photometric factor per
+ * update, src/graph/manager.cpp:585-588).  Factor i is linearized at T_b = (R_b + 9 i, t_b + 3 i) and, if it is binary,
+ * T_a = (R_a + 9 i, t_a + 3 i); R_a / t_a may be NULL when no factor is binary.  out: n_factors results.  Blocks.
+ * - Same bits as separate calls: every factor's result (H, b, f, localizabilities, status_hist, n_exceptions) and the state
+ *   it leaves (statuses, centres, the features mh_photo_update_map reads, the rows of mh_photo_factor_get_state) are
+ *   bit-identical to its own mh_photo_factor_linearize at the same poses: the per-feature arithmetic is shared, the
+ *   feature-order fold and the unary epilogue run per factor on the host as in a single call, and each factor has its own
+ *   exception counters.
+ * - The factors come from one mh_photo (or are clones of its factors): one model, one context, one stream; their frames
+ *   may differ.  Unary and binary factors may share a call; a factor without features costs nothing.
+ * - MH_ERR_INVALID_ARG, with no factor left in flight: n_factors 0 or above MH_PHOTO_MAX_BATCH, a NULL array or factor,
+ *   factors of different mh_photo objects, the same factor twice, a factor with a call in flight, a binary factor
+ *   without R_a / t_a.
+ * - gpu_ms (profiling on) is the kernel time of the whole launch, in every factor's result. */
+int mh_photo_factor_linearize_batch(mh_photo_factor * const * factors, size_t n_factors, const double * R_b, const double * t_b,
+                                    const double * R_a, const double * t_a, mh_photo_result * out);
+/* The same enqueued without waiting; each factor is then collected with mh_photo_factor_wait, in any order.  Destroying a
+ * member while the launch is in flight waits for the launch; the other members can still be collected. */
+int mh_photo_factor_linearize_batch_async(mh_photo_factor * const * factors, size_t n_factors, const double * R_b,
+                                          const double * t_b, const double * R_a, const double * t_a);
 /* getStatuses / getFeatures().center after the last linearize; rows (optional, parity tooling): per feature and
  * patch point {whitened residual, J_b[6], valid} = 8 doubles, 64 points per feature. */
 int mh_photo_factor_get_state(const mh_photo_factor * factor, int32_t * statuses, double * centers, double * rows);

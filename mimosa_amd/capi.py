@@ -35,6 +35,7 @@ EXPORTS = [
     "mh_photo_create", "mh_photo_destroy", "mh_photo_preprocess", "mh_scan_keep_raw", "mh_photo_preprocess_scan", "mh_photo_preprocess_scan_begin", "mh_photo_preprocess_commit", "mh_photo_detect_prefetch", "mh_photo_get_image",
     "mh_photo_num_features", "mh_photo_get_features", "mh_photo_set_features", "mh_photo_detect_features", "mh_photo_update_map",
     "mh_photo_factor_create", "mh_photo_factor_clone", "mh_photo_factor_destroy", "mh_photo_factor_linearize", "mh_photo_factor_linearize_async", "mh_photo_factor_wait", "mh_photo_factor_get_state", "mh_photo_factor_size",
+    "mh_photo_factor_linearize_batch", "mh_photo_factor_linearize_batch_async",
     "mh_radar_scan_create", "mh_radar_scan_destroy", "mh_radar_prepare_input", "mh_radar_get_targets", "mh_radar_factor_create",
     "mh_radar_factor_create_from_scan", "mh_radar_factor_clone", "mh_radar_factor_destroy", "mh_radar_factor_size", "mh_radar_factor_linearize",
     "mh_radar_factor_linearize_async", "mh_radar_factor_wait", "mh_radar_factor_linearize_batch", "mh_radar_factor_get_residuals",
@@ -482,6 +483,8 @@ def load(build_if_missing: bool = True):
     L.mh_photo_factor_destroy.restype = None
     L.mh_photo_factor_linearize.argtypes = [vp, vp, vp, vp, vp, C.POINTER(PhotoResult)]
     L.mh_photo_factor_get_state.argtypes = [vp, vp, vp, vp]
+    L.mh_photo_factor_linearize_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.mh_photo_factor_linearize_batch_async.argtypes = [vp, sz, vp, vp, vp, vp]
     L.mh_photo_factor_size.argtypes = [vp]
     L.mh_photo_factor_size.restype = sz
     L.mh_radar_scan_create.argtypes = [vp, pvp]
@@ -1298,3 +1301,30 @@ def radar_linearize_batch(factors, R_W_Bs, v_Ws, bias_gyros) -> list:
         ctx = factors[0].ctx if n else None
         raise MhError(rc, (L.mh_last_error(ctx.h if ctx else None) or b"").decode())
     return [out[i].as_dict() for i in range(n)]
+
+
+def _photo_batch_call(name, factors, R_bs, t_bs, R_as, t_as, *out):
+    n = len(factors)
+    L = factors[0].L if n else load()
+    hs = (C.c_void_p * max(n, 1))(*[f.h for f in factors])
+    Rb = _f64(R_bs).reshape(-1)
+    tb = _f64(t_bs).reshape(-1)
+    Ra = _f64(R_as).reshape(-1) if R_as is not None else None
+    ta = _f64(t_as).reshape(-1) if t_as is not None else None
+    rc = getattr(L, name)(hs, n, _p(Rb), _p(tb), _p(Ra), _p(ta), *out)
+    if rc != MH_OK:
+        ctx = factors[0].ctx if n else None
+        raise MhError(rc, (L.mh_last_error(ctx.h if ctx else None) or b"").decode())
+
+
+def photo_linearize_batch(factors, R_bs, t_bs, R_as=None, t_as=None) -> list:
+    """Every photometric factor linearized at its own pose in ONE kernel launch (mh_photo_factor_linearize_batch); the
+    factors come from one Photo.  R_as / t_as: the T_a of binary factors (None when no factor is binary)."""
+    out = (PhotoResult * max(len(factors), 1))()
+    _photo_batch_call("mh_photo_factor_linearize_batch", factors, R_bs, t_bs, R_as, t_as, out)
+    return [out[i].as_dict() for i in range(len(factors))]
+
+
+def photo_linearize_batch_async(factors, R_bs, t_bs, R_as=None, t_as=None) -> None:
+    """The same enqueued without waiting: each PhotoFactor.wait() then returns its result, in any order."""
+    _photo_batch_call("mh_photo_factor_linearize_batch_async", factors, R_bs, t_bs, R_as, t_as)

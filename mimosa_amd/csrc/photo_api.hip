@@ -18,6 +18,7 @@
 #include <ctime>
 #include <new>
 #include <set>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -66,6 +67,38 @@ struct HostFeature
   std::vector<double> Le_ps, intensities, psi;
 };
 
+// One mh_photo_factor_linearize_batch launch.  Its mapped pinned block holds what the kernel reads (descriptors, block
+// prefix table) and the per-factor exception counters and completion word it writes; the factors' own outputs go to their
+// own blocks.  Released when the last member is collected or destroyed.
+constexpr size_t kBatchDescBytes = (MH_PHOTO_MAX_BATCH * sizeof(mh::PhotoFactorDesc) + 255) & ~size_t(255);
+constexpr size_t kBatchPrefixBytes = ((MH_PHOTO_MAX_BATCH + 1) * sizeof(int32_t) + 255) & ~size_t(255);
+constexpr size_t kBatchCounterBytes = MH_PHOTO_MAX_BATCH * sizeof(mh::PhotoCounters);
+constexpr size_t kBatchBytes = (kBatchDescBytes + kBatchPrefixBytes + kBatchCounterBytes + 64 + 4095) & ~size_t(4095);
+struct PhotoBatch
+{
+  int members = 0;  // factors not yet collected or destroyed
+  void * h = nullptr;
+  void * d = nullptr;  // device address of h
+  unsigned int seq = 0;  // completion number the launch publishes (0: wait on the stream)
+  bool timed = false;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  mh::PhotoFactorDesc * descs() const { return static_cast<mh::PhotoFactorDesc *>(h); }
+  int32_t * prefix() const { return reinterpret_cast<int32_t *>(static_cast<char *>(h) + kBatchDescBytes); }
+  mh::PhotoCounters * counters() const { return reinterpret_cast<mh::PhotoCounters *>(static_cast<char *>(h) + kBatchDescBytes + kBatchPrefixBytes); }
+  unsigned int * host_seq() const { return reinterpret_cast<unsigned int *>(static_cast<char *>(h) + kBatchDescBytes + kBatchPrefixBytes + kBatchCounterBytes); }
+  template <class T> T * dev(T * host_ptr) const { return reinterpret_cast<T *>(static_cast<char *>(d) + (reinterpret_cast<char *>(host_ptr) - static_cast<char *>(h))); }
+};
+
+// the stream has passed the launch (or never got it) when this is called
+void batch_release(PhotoBatch * b)
+{
+  if (!b || --b->members > 0) return;
+  if (b->h) AllocCache::free_pinned(b->h, kBatchBytes);
+  for (auto & e : b->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete b;
+}
+
 }  // namespace
 
 struct mh_photo
@@ -88,6 +121,8 @@ struct mh_photo
   // linearize between mh_photo_preprocess_scan_begin and _commit must not erase or mix into the frame's count
   mh::PhotoCounters * h_counters = nullptr;
   mh::PhotoCounters * d_counters = nullptr;
+  DevBuf d_batch_ticket;    // finished blocks of a mh_photo_factor_linearize_batch launch (the launches share the stream)
+  unsigned int batch_seq = 0;  // completion numbers of those launches
   float * h_int_out = nullptr;  // pinned staging of the corrected intensities
   size_t h_int_cap = 0;
   char * h_stage = nullptr;     // pinned staging of detectFeatures' small transfers (candidate list, gather records)
@@ -122,6 +157,8 @@ struct mh_photo_factor
   std::vector<int32_t> statuses;
   std::vector<double> centers, partials, rows;
   hipEvent_t ev[2] = {nullptr, nullptr};
+  PhotoBatch * batch = nullptr;  // the in-flight mh_photo_factor_linearize_batch[_async] this factor belongs to
+  int batch_slot = 0;            // ... its index there (its exception counters)
 };
 
 namespace
@@ -139,7 +176,7 @@ void photo_release(mh_photo * p)
   if (p->next_ev) (void)hipEventDestroy(p->next_ev);
   if (p->scan_ev) (void)hipEventDestroy(p->scan_ev);
   for (DevBuf * b : {&p->d_alt, &p->d_shift, &p->d_hp, &p->d_lp, &p->d_static, &p->d_raw_pts, &p->d_img_raw, &p->d_tmp_a, &p->d_tmp_b,
-                     &p->d_mask_raw, &p->d_yaw_valid, &p->d_int_out, &p->d_grad, &p->d_detmask, &p->d_xyz, &p->d_cand, &p->d_gather, &p->d_stamps, &p->d_proj_pre})
+                     &p->d_mask_raw, &p->d_yaw_valid, &p->d_int_out, &p->d_grad, &p->d_detmask, &p->d_xyz, &p->d_cand, &p->d_gather, &p->d_stamps, &p->d_proj_pre, &p->d_batch_ticket})
     b->release();
   if (p->h_counters) (void)hipHostFree(p->h_counters);
   if (p->h_int_out) (void)hipHostFree(p->h_int_out);
@@ -1334,6 +1371,7 @@ void mh_photo_factor_destroy(mh_photo_factor * f)
   (void)hipStreamSynchronize(ctx->stream);
   for (DevBuf * b : {&f->d_Le, &f->d_psi, &f->d_npts, &f->d_rows, &f->d_ticket}) b->release(true);
   if (f->h_out) AllocCache::free_pinned(f->h_out, f->out_bytes);
+  if (f->pending) batch_release(f->batch);  // (after the stream synchronisation above: the launch is done)
   for (auto & e : f->ev)
     if (e) (void)hipEventDestroy(e);
   frame_release(f->frame);
@@ -1343,6 +1381,77 @@ void mh_photo_factor_destroy(mh_photo_factor * f)
 
 size_t mh_photo_factor_size(const mh_photo_factor * f) { return f ? f->features.size() : 0; }
 
+// The launch-wide kernel arguments of the factors of `ph` (the completion fields are the caller's)
+static void photo_lin_launch(const mh_photo * ph, mh::PhotoLinLaunch & L)
+{
+  const mh_photo_config & c = ph->cfg;
+  L.model = ph->model;
+  std::memcpy(L.TBL_R, c.T_B_L_R, sizeof(L.TBL_R));
+  std::memcpy(L.TBL_t, c.T_B_L_t, sizeof(L.TBL_t));
+  L.sigma = c.sigma;
+  L.max_error = c.max_error;
+  L.robust_param = c.robust_cost_function_parameter;
+  L.use_robust = c.use_robust_cost_function;
+  L.robust_is_huber = c.robust_cost_function == 0;
+  L.seq = 0;
+  L.ticket = nullptr;
+  L.host_seq = nullptr;
+}
+
+// The descriptor of factor f at T_b (, T_a) (photometric_factor.hpp:141-149); the outputs are the factor's mapped block and
+// rows buffer, the exception counters the caller's
+static void photo_lin_desc(const mh_photo_factor * f, const double R_b[9], const double t_b[3], const double * R_a, const double * t_a,
+                           mh::PhotoCounters * counters, mh::PhotoFactorDesc & a)
+{
+  const mh_photo_config & c = f->photo->cfg;
+  const size_t nf = f->features.size();
+  Pose Tb, Ta, TBL;
+  std::memcpy(Tb.R, R_b, sizeof(Tb.R));
+  std::memcpy(Tb.t, t_b, sizeof(Tb.t));
+  for (int i = 0; i < 9; ++i) Ta.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  Ta.t[0] = Ta.t[1] = Ta.t[2] = 0.0;
+  if (f->binary) {
+    std::memcpy(Ta.R, R_a, sizeof(Ta.R));
+    std::memcpy(Ta.t, t_a, sizeof(Ta.t));
+  }
+  std::memcpy(TBL.R, c.T_B_L_R, sizeof(TBL.R));
+  std::memcpy(TBL.t, c.T_B_L_t, sizeof(TBL.t));
+  const Pose dBe = pose_mul(pose_inv(Tb), Ta);                     // :147
+  const Pose dLe = pose_mul(pose_mul(pose_inv(TBL), dBe), TBL);    // :148-149
+  const PhotoFrame * fr = f->frame;
+  a.frame.points = static_cast<const mh_point32 *>(fr->d_points.p);
+  a.frame.n_points = static_cast<int>(fr->n_points);
+  a.frame.intensity = static_cast<const float *>(fr->d_intensity.p);
+  a.frame.range = static_cast<const float *>(fr->d_range.p);
+  a.frame.dx = static_cast<const float *>(fr->d_dx.p);
+  a.frame.dy = static_cast<const float *>(fr->d_dy.p);
+  a.frame.mask = static_cast<const uint8_t *>(fr->d_mask.p);
+  a.frame.idx = static_cast<const int32_t *>(fr->d_idx.p);
+  a.frame.proj = static_cast<const int32_t *>(fr->d_proj.p);
+  a.frame.yaw = static_cast<const float *>(fr->d_yaw.p);
+  a.frame.pose_ns = static_cast<const uint32_t *>(fr->d_pose_ns.p);
+  a.frame.pose_Rt = reinterpret_cast<const double *>(static_cast<const char *>(fr->d_pose_ns.p) + fr->pose_rt_offset);
+  a.frame.n_poses = fr->n_poses;
+  a.Le_ps = static_cast<const double *>(f->d_Le.p);
+  a.psi_a = static_cast<const double *>(f->d_psi.p);
+  a.n_pts = static_cast<const int32_t *>(f->d_npts.p);
+  a.n_features = static_cast<int>(nf);
+  a.binary = f->binary ? 1 : 0;
+  std::memcpy(a.dLe_R, dLe.R, sizeof(a.dLe_R));
+  std::memcpy(a.dLe_t, dLe.t, sizeof(a.dLe_t));
+  std::memcpy(a.dBe_R, dBe.R, sizeof(a.dBe_R));
+  std::memcpy(a.dBe_t, dBe.t, sizeof(a.dBe_t));
+  // layout of the mapped block: centres (2 nf doubles) | partial sums (nf x kPhotoPartial doubles) | statuses (nf int32)
+  a.centers = static_cast<double *>(f->d_out);
+  a.partials = a.centers + 2 * nf;
+  a.status = reinterpret_cast<int32_t *>(a.partials + nf * mh::kPhotoPartial);
+  a.rows_out = static_cast<double *>(f->d_rows.p);
+  a.counters = counters;
+}
+
+// the completion word of a single call sits behind the statuses in the factor's mapped block (sized with 64 spare bytes)
+static size_t photo_seq_offset(size_t nf) { return ((2 * nf + nf * mh::kPhotoPartial) * sizeof(double) + nf * sizeof(int32_t) + 7) & ~size_t(7); }
+
 static int photo_linearize_enqueue(mh_photo_factor * f, const double R_b[9], const double t_b[3], const double * R_a, const double * t_a)
 {
   mh_ctx * ctx = f->photo->ctx;
@@ -1350,68 +1459,18 @@ static int photo_linearize_enqueue(mh_photo_factor * f, const double R_b[9], con
   {
     if (f->binary && (!R_a || !t_a)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_photo_factor_linearize: the binary factor needs T_a");
     MH_HIP(ctx, mh_enter(ctx));
-    const mh_photo_config & c = f->photo->cfg;
     const size_t nf = f->features.size();
-    Pose Tb, Ta, TBL;
-    std::memcpy(Tb.R, R_b, sizeof(Tb.R));
-    std::memcpy(Tb.t, t_b, sizeof(Tb.t));
-    for (int i = 0; i < 9; ++i) Ta.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    Ta.t[0] = Ta.t[1] = Ta.t[2] = 0.0;
-    if (f->binary) {
-      std::memcpy(Ta.R, R_a, sizeof(Ta.R));
-      std::memcpy(Ta.t, t_a, sizeof(Ta.t));
-    }
-    std::memcpy(TBL.R, c.T_B_L_R, sizeof(TBL.R));
-    std::memcpy(TBL.t, c.T_B_L_t, sizeof(TBL.t));
-    const Pose dBe = pose_mul(pose_inv(Tb), Ta);                     // :147
-    const Pose dLe = pose_mul(pose_mul(pose_inv(TBL), dBe), TBL);    // :148-149
     mh::PhotoLinArgs a;
-    a.model = f->photo->model;
-    PhotoFrame * fr = f->frame;
-    a.frame.points = static_cast<const mh_point32 *>(fr->d_points.p);
-    a.frame.n_points = static_cast<int>(fr->n_points);
-    a.frame.intensity = static_cast<const float *>(fr->d_intensity.p);
-    a.frame.range = static_cast<const float *>(fr->d_range.p);
-    a.frame.dx = static_cast<const float *>(fr->d_dx.p);
-    a.frame.dy = static_cast<const float *>(fr->d_dy.p);
-    a.frame.mask = static_cast<const uint8_t *>(fr->d_mask.p);
-    a.frame.idx = static_cast<const int32_t *>(fr->d_idx.p);
-    a.frame.proj = static_cast<const int32_t *>(fr->d_proj.p);
-    a.frame.yaw = static_cast<const float *>(fr->d_yaw.p);
-    a.frame.pose_ns = static_cast<const uint32_t *>(fr->d_pose_ns.p);
-    a.frame.pose_Rt = reinterpret_cast<const double *>(static_cast<const char *>(fr->d_pose_ns.p) + fr->pose_rt_offset);
-    a.frame.n_poses = fr->n_poses;
-    a.Le_ps = static_cast<const double *>(f->d_Le.p);
-    a.psi_a = static_cast<const double *>(f->d_psi.p);
-    a.n_pts = static_cast<const int32_t *>(f->d_npts.p);
-    a.n_features = static_cast<int>(nf);
-    a.binary = f->binary ? 1 : 0;
-    std::memcpy(a.dLe_R, dLe.R, sizeof(a.dLe_R));
-    std::memcpy(a.dLe_t, dLe.t, sizeof(a.dLe_t));
-    std::memcpy(a.dBe_R, dBe.R, sizeof(a.dBe_R));
-    std::memcpy(a.dBe_t, dBe.t, sizeof(a.dBe_t));
-    std::memcpy(a.TBL_R, TBL.R, sizeof(a.TBL_R));
-    std::memcpy(a.TBL_t, TBL.t, sizeof(a.TBL_t));
-    a.sigma = c.sigma;
-    a.max_error = c.max_error;
-    a.robust_param = c.robust_cost_function_parameter;
-    a.use_robust = c.use_robust_cost_function;
-    a.robust_is_huber = c.robust_cost_function == 0;
-    // layout of the mapped block: centres (2 nf doubles) | partial sums (nf x kPhotoPartial doubles) | statuses (nf int32)
-    a.centers = static_cast<double *>(f->d_out);
-    a.partials = a.centers + 2 * nf;
-    a.status = reinterpret_cast<int32_t *>(a.partials + nf * mh::kPhotoPartial);
-    a.rows_out = static_cast<double *>(f->d_rows.p);
-    a.counters = f->photo->d_counters + 1;
-    // the completion word sits behind the statuses in the mapped block (the block is sized with 64 spare bytes)
-    const size_t seq_off = ((2 * nf + nf * mh::kPhotoPartial) * sizeof(double) + nf * sizeof(int32_t) + 7) & ~size_t(7);
-    a.seq = 0;
-    a.ticket = static_cast<unsigned int *>(f->d_ticket.p);
-    a.host_seq = reinterpret_cast<unsigned int *>(static_cast<char *>(f->d_out) + seq_off);
+    photo_lin_launch(f->photo, a.launch);
+    photo_lin_desc(f, R_b, t_b, R_a, t_a, f->photo->d_counters + 1, a.factor);
+    const size_t seq_off = photo_seq_offset(nf);
+    a.launch.seq = 0;
+    a.launch.ticket = static_cast<unsigned int *>(f->d_ticket.p);
+    a.launch.host_seq = reinterpret_cast<unsigned int *>(static_cast<char *>(f->d_out) + seq_off);
     f->pending_seq = 0;
     if (!timed && nf > 0) {  // (no kernel is launched for an empty factor)
       if (++f->seq_counter == 0) ++f->seq_counter;
-      a.seq = f->pending_seq = f->seq_counter;
+      a.launch.seq = f->pending_seq = f->seq_counter;
       __atomic_store_n(reinterpret_cast<unsigned int *>(static_cast<char *>(f->h_out) + seq_off), 0u, __ATOMIC_RELEASE);  // re-arm
     }
     f->photo->h_counters[1].project_throw = f->photo->h_counters[1].pose_missing = 0;
@@ -1423,6 +1482,7 @@ static int photo_linearize_enqueue(mh_photo_factor * f, const double R_b[9], con
     MH_HIP(ctx, mh::launch_photo_linearize(a, ctx->stream));
     if (timed) MH_HIP(ctx, hipEventRecord(f->ev[1], ctx->stream));
   }
+  f->batch = nullptr;
   f->pending_timed = timed;
   f->pending = true;
   return MH_OK;
@@ -1436,14 +1496,22 @@ static int photo_linearize_finish(mh_photo_factor * f, mh_photo_result * out)
   const size_t nf = f->features.size();
   const bool timed = f->pending_timed;
   f->pending = false;
+  PhotoBatch * const batch = f->batch;  // a member of a batch launch: its completion word, counters and timing are the batch's
+  f->batch = nullptr;
+  struct BatchBack  // the member leaves the batch on every exit path
   {
-    bool need_sync = f->pending_seq == 0;
+    PhotoBatch * b;
+    ~BatchBack() { batch_release(b); }
+  } batch_back{batch};
+  {
+    const unsigned int want = batch ? batch->seq : f->pending_seq;
+    bool need_sync = want == 0;
     if (!need_sync) {  // spin on the completion number the kernel's last block publishes (mh_icp_wait does the same)
-      const size_t seq_off = ((2 * nf + nf * mh::kPhotoPartial) * sizeof(double) + nf * sizeof(int32_t) + 7) & ~size_t(7);
-      const volatile unsigned int * flag = reinterpret_cast<const volatile unsigned int *>(static_cast<const char *>(f->h_out) + seq_off);
+      const volatile unsigned int * flag =
+          batch ? batch->host_seq() : reinterpret_cast<const volatile unsigned int *>(static_cast<const char *>(f->h_out) + photo_seq_offset(nf));
       timespec t0;
       clock_gettime(CLOCK_MONOTONIC, &t0);
-      for (unsigned spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != f->pending_seq; ++spins) {
+      for (unsigned spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != want; ++spins) {
         __builtin_ia32_pause();
         if ((spins & 1023u) == 1023u) {
           timespec t1;
@@ -1461,8 +1529,9 @@ static int photo_linearize_finish(mh_photo_factor * f, mh_photo_result * out)
     std::memcpy(f->statuses.data(), new_centers + 2 * nf + nf * mh::kPhotoPartial, nf * sizeof(int32_t));
     std::memset(out, 0, sizeof(*out));
     out->gpu_ms = -1.f;
-    if (timed) (void)hipEventElapsedTime(&out->gpu_ms, f->ev[0], f->ev[1]);
-    out->n_exceptions = static_cast<int32_t>(f->photo->h_counters[1].project_throw + f->photo->h_counters[1].pose_missing);
+    if (timed) (void)hipEventElapsedTime(&out->gpu_ms, batch ? batch->ev[0] : f->ev[0], batch ? batch->ev[1] : f->ev[1]);
+    const mh::PhotoCounters & cnt = batch ? batch->counters()[f->batch_slot] : f->photo->h_counters[1];
+    out->n_exceptions = static_cast<int32_t>(cnt.project_throw + cnt.pose_missing);
     // accumulate the per-feature sums in feature order (the reference's serial loop, :157-330)
     const int NV = f->binary ? 13 : 7;
     auto ent = [NV](int r, int cc) {
@@ -1555,6 +1624,116 @@ int mh_photo_factor_wait(mh_photo_factor * f, mh_photo_result * out)
     if (!f->pending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_photo_factor_wait: no call in flight");
     return photo_linearize_finish(f, out);
   });
+}
+
+// mh_photo_factor_linearize_batch[_async]: the checks (nothing is touched when one fails), the descriptors, one launch;
+// every factor is then pending as a member of the batch and is collected by photo_linearize_finish
+static int photo_batch_enqueue(mh_photo_factor * const * factors, size_t n, const double * R_b, const double * t_b, const double * R_a,
+                               const double * t_a, const char * what)
+{
+  mh_photo * ph = factors[0]->photo;
+  mh_ctx * ctx = ph->ctx;
+  if (n > MH_PHOTO_MAX_BATCH) return fail(ctx, MH_ERR_INVALID_ARG, std::string(what) + ": more than MH_PHOTO_MAX_BATCH factors");
+  for (size_t i = 0; i < n; ++i) {
+    const mh_photo_factor * f = factors[i];
+    if (!f) return fail(ctx, MH_ERR_INVALID_ARG, std::string(what) + ": NULL factor");
+    if (f->photo != ph) return fail(ctx, MH_ERR_INVALID_ARG, std::string(what) + ": factors of different mh_photo objects");
+    if (f->pending) return fail(ctx, MH_ERR_INVALID_ARG, std::string(what) + ": a factor has a call in flight");
+    if (f->binary && (!R_a || !t_a)) return fail(ctx, MH_ERR_INVALID_ARG, std::string(what) + ": a binary factor needs T_a");
+    for (size_t j = 0; j < i; ++j)
+      if (factors[j] == f) return fail(ctx, MH_ERR_INVALID_ARG, std::string(what) + ": the same factor twice");
+  }
+  MH_HIP(ctx, mh_enter(ctx));
+  if (!ph->d_batch_ticket.p) {
+    MH_HIP(ctx, ph->d_batch_ticket.reserve(64, ctx->stream, false));
+    MH_HIP(ctx, hipMemsetAsync(ph->d_batch_ticket.p, 0, 64, ctx->stream));
+  }
+  PhotoBatch * B = new PhotoBatch;
+  B->members = 1;
+  struct Drop  // until the launch is handed to the factors: a failure frees the batch once the stream is past it
+  {
+    PhotoBatch * b;
+    hipStream_t stream;
+    ~Drop()
+    {
+      if (!b) return;
+      (void)hipStreamSynchronize(stream);
+      batch_release(b);
+    }
+  } drop{B, ctx->stream};
+  MH_HIP(ctx, AllocCache::alloc_pinned(&B->h, kBatchBytes));
+  MH_HIP(ctx, hipHostGetDevicePointer(&B->d, B->h, 0));
+  mh::PhotoFactorDesc * descs = B->descs();
+  int32_t * prefix = B->prefix();
+  mh::PhotoCounters * counters = B->counters();
+  std::memset(counters, 0, n * sizeof(mh::PhotoCounters));
+  int blocks = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const mh_photo_factor * f = factors[i];
+    photo_lin_desc(f, R_b + 9 * i, t_b + 3 * i, R_a ? R_a + 9 * i : nullptr, t_a ? t_a + 3 * i : nullptr, B->dev(&counters[i]), descs[i]);
+    prefix[i] = blocks;
+    blocks += mh::photo_linearize_blocks(static_cast<int>(f->features.size()));
+  }
+  prefix[n] = blocks;
+  mh::PhotoLinLaunch L;
+  photo_lin_launch(ph, L);
+  L.ticket = static_cast<unsigned int *>(ph->d_batch_ticket.p);
+  L.host_seq = B->dev(B->host_seq());
+  B->timed = ctx->profiling > 0;
+  if (!B->timed && blocks > 0) {
+    if (++ph->batch_seq == 0) ++ph->batch_seq;
+    B->seq = L.seq = ph->batch_seq;
+    __atomic_store_n(B->host_seq(), 0u, __ATOMIC_RELEASE);  // re-arm (the block comes from a pool)
+  }
+  if (B->timed) {
+    MH_HIP(ctx, hipEventCreate(&B->ev[0]));
+    MH_HIP(ctx, hipEventCreate(&B->ev[1]));
+    MH_HIP(ctx, hipEventRecord(B->ev[0], ctx->stream));
+  }
+  // ONE launch for the window: factor i owns the blocks [prefix[i], prefix[i + 1])
+  MH_HIP(ctx, mh::launch_photo_linearize_batch(L, B->dev(descs), B->dev(prefix), static_cast<int>(n), blocks, ctx->stream));
+  if (B->timed) MH_HIP(ctx, hipEventRecord(B->ev[1], ctx->stream));
+  B->members = static_cast<int>(n);
+  for (size_t i = 0; i < n; ++i) {
+    mh_photo_factor * f = factors[i];
+    f->batch = B;
+    f->batch_slot = static_cast<int>(i);
+    f->pending_seq = 0;
+    f->pending_timed = B->timed;
+    f->pending = true;
+  }
+  drop.b = nullptr;
+  return MH_OK;
+}
+
+int mh_photo_factor_linearize_batch(mh_photo_factor * const * factors, size_t n_factors, const double * R_b, const double * t_b,
+                                    const double * R_a, const double * t_a, mh_photo_result * out)
+{
+  if (!factors || n_factors == 0 || !factors[0] || !R_b || !t_b || !out)
+    return fail(factors && n_factors && factors[0] ? factors[0]->photo->ctx : nullptr, MH_ERR_INVALID_ARG,
+                "mh_photo_factor_linearize_batch: NULL argument or no factors");
+  mh_ctx * ctx = factors[0]->photo->ctx;
+  return guarded(ctx, "mh_photo_factor_linearize_batch", [&]() -> int {
+    const int rc = photo_batch_enqueue(factors, n_factors, R_b, t_b, R_a, t_a, "mh_photo_factor_linearize_batch");
+    if (rc != MH_OK) return rc;
+    int first = MH_OK;  // every member is collected, whatever happens to one of them
+    for (size_t i = 0; i < n_factors; ++i) {
+      const int r = photo_linearize_finish(factors[i], &out[i]);
+      if (first == MH_OK) first = r;
+    }
+    return first;
+  });
+}
+
+int mh_photo_factor_linearize_batch_async(mh_photo_factor * const * factors, size_t n_factors, const double * R_b, const double * t_b,
+                                          const double * R_a, const double * t_a)
+{
+  if (!factors || n_factors == 0 || !factors[0] || !R_b || !t_b)
+    return fail(factors && n_factors && factors[0] ? factors[0]->photo->ctx : nullptr, MH_ERR_INVALID_ARG,
+                "mh_photo_factor_linearize_batch_async: NULL argument or no factors");
+  mh_ctx * ctx = factors[0]->photo->ctx;
+  return guarded(ctx, "mh_photo_factor_linearize_batch_async",
+                 [&]() -> int { return photo_batch_enqueue(factors, n_factors, R_b, t_b, R_a, t_a, "mh_photo_factor_linearize_batch_async"); });
 }
 
 int mh_photo_factor_get_state(const mh_photo_factor * f, int32_t * statuses, double * centers, double * rows)

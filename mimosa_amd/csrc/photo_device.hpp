@@ -139,10 +139,20 @@ hipError_t launch_photo_candidates(const uint8_t * grad, const uint8_t * mask, i
 hipError_t launch_photo_gather(const int2 * uv, int n_off, int n_cand, bool per_candidate, const float * I, const int32_t * idx,
                                const mh_point32 * pts, int rows, int cols, float * win49, float4 * rec, int32_t * rec_idx, hipStream_t stream);
 
-// PhotometricFactor::linearize (photometric_factor.hpp:136-355): one wave per feature
-struct PhotoLinArgs
+// PhotometricFactor::linearize (photometric_factor.hpp:136-355): one wave per feature.  The arguments split into what a
+// launch shares (model, T_B_L, noise and robust settings, completion) and one descriptor per factor.
+struct PhotoLinLaunch
 {
   PhotoModel model;
+  double TBL_R[9], TBL_t[3];  // T_B_L
+  double sigma, max_error, robust_param;
+  int use_robust, robust_is_huber;
+  unsigned int seq;        // != 0: the last block publishes it to *host_seq (mapped pinned) after everything else
+  unsigned int * ticket;   // device counter of finished blocks
+  unsigned int * host_seq;
+};
+struct PhotoFactorDesc
+{
   PhotoFrameView frame;
   const double * Le_ps;   // n_features x kPhotoMaxPatch x 3
   const double * psi_a;   // n_features x kPhotoMaxPatch
@@ -151,19 +161,25 @@ struct PhotoLinArgs
   int binary;
   double dLe_R[9], dLe_t[3];  // delta_pose_b_a_Le
   double dBe_R[9], dBe_t[3];  // delta_pose_b_a_Be
-  double TBL_R[9], TBL_t[3];  // T_B_L
-  double sigma, max_error, robust_param;
-  int use_robust, robust_is_huber;
   // outputs
   int32_t * status;      // n_features
   double * centers;      // n_features x 2 (written for Valid features)
   double * partials;     // n_features x kPhotoPartial: upper triangle of sum v v^T, v = [J_b(6) (, J_a(6)), e]
   double * rows_out;     // optional (parity tooling): n_features x kPhotoMaxPatch x 8 = {e, J_b[6], valid}
-  PhotoCounters * counters;
-  unsigned int seq;        // != 0: the last block publishes it to *host_seq (mapped pinned) after everything else
-  unsigned int * ticket;   // device counter of finished blocks
-  unsigned int * host_seq;
+  PhotoCounters * counters;  // this factor's exceptions
+};
+// one factor, by value (photo_linearize_kernel)
+struct PhotoLinArgs
+{
+  PhotoLinLaunch launch;
+  PhotoFactorDesc factor;
 };
 hipError_t launch_photo_linearize(const PhotoLinArgs & a, hipStream_t stream);
+// blocks a factor of n_features takes (none for 0)
+int photo_linearize_blocks(int n_features);
+// N factors in one launch (photo_linearize_batch_kernel): descs / blk_start (n_factors + 1 ascending block offsets, the
+// last = n_blocks) are device-readable; the per-feature arithmetic is the single kernel's
+hipError_t launch_photo_linearize_batch(const PhotoLinLaunch & L, const PhotoFactorDesc * descs, const int32_t * blk_start, int n_factors,
+                                        int n_blocks, hipStream_t stream);
 
 }  // namespace mh

@@ -840,12 +840,12 @@ __device__ __forceinline__ void mat3_vec(const double * R, double x, double y, d
 }
 
 constexpr int kFeatPerBlock = 4;
-// one wave = one feature; returns as soon as the feature's status is known
-__device__ __forceinline__ void photo_linearize_feature(const PhotoLinArgs & a, const float * s_alt)
+// one wave = feature f of the factor `a`; returns as soon as the feature's status is known.  W: what the launch shares.
+__device__ __forceinline__ void photo_linearize_feature(const PhotoLinLaunch & W, const PhotoFactorDesc & a, const int f, const float * s_alt)
 {
-  const int lane = threadIdx.x & 63, f = blockIdx.x * kFeatPerBlock + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
   if (f >= a.n_features) return;  // whole waves
-  const PhotoModel & m = a.model;
+  const PhotoModel & m = W.model;
   const PhotoFrameView & fr = a.frame;
   if (a.rows_out) {  // rows of features that do not end Valid read as zero
     double * ro = a.rows_out + (static_cast<size_t>(f) * kPhotoMaxPatch + lane) * 8;
@@ -992,7 +992,7 @@ __device__ __forceinline__ void photo_linearize_feature(const PhotoLinArgs & a, 
   const double e0 = act ? psi - a.psi_a[static_cast<size_t>(f) * kPhotoMaxPatch + lane] : 0.0;
   const double e2 = wave_sum(e0 * e0);
   const double e_ncc = (2 - e2) / 2;
-  if (e_ncc < a.max_error) {
+  if (e_ncc < W.max_error) {
     if (lane == 0) a.status[f] = PS_MAX_ERROR;
     return;
   }
@@ -1020,10 +1020,10 @@ __device__ __forceinline__ void photo_linearize_feature(const PhotoLinArgs & a, 
     const double g0 = gx * P0 + gy * P3, g1 = gx * P1 + gy * P4, g2 = gy * P5;
     // p_Be_a = T_B_L * Le_p;  p_Be_b = delta_pose_b_a_Be * p_Be_a
     double pax, pay, paz, pbx, pby, pbz;
-    mat3_vec(a.TBL_R, ax, ay, az, pax, pay, paz);
-    pax += a.TBL_t[0];
-    pay += a.TBL_t[1];
-    paz += a.TBL_t[2];
+    mat3_vec(W.TBL_R, ax, ay, az, pax, pay, paz);
+    pax += W.TBL_t[0];
+    pay += W.TBL_t[1];
+    paz += W.TBL_t[2];
     mat3_vec(a.dBe_R, pax, pay, paz, pbx, pby, pbz);
     pbx += a.dBe_t[0];
     pby += a.dBe_t[1];
@@ -1033,7 +1033,7 @@ __device__ __forceinline__ void photo_linearize_feature(const PhotoLinArgs & a, 
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-      for (int j = 0; j < 3; ++j) Rk[3 * i + j] = TR[i] * a.TBL_R[3 * j] + (TR[3 + i] * a.TBL_R[3 * j + 1] + TR[6 + i] * a.TBL_R[3 * j + 2]);
+      for (int j = 0; j < 3; ++j) Rk[3 * i + j] = TR[i] * W.TBL_R[3 * j] + (TR[3 + i] * W.TBL_R[3 * j + 1] + TR[6 + i] * W.TBL_R[3 * j + 2]);
     const double w0 = g0 * Rk[0] + g1 * Rk[3] + g2 * Rk[6], w1 = g0 * Rk[1] + g1 * Rk[4] + g2 * Rk[7],
                  w2 = g0 * Rk[2] + g1 * Rk[5] + g2 * Rk[8];
     // w * Hat(p) = (p x w)^T ... row vector times skew: (w^T [p]x)_k = (w x p)_k with sign: w^T [p]x = (p x w)^T * (-1)?
@@ -1057,13 +1057,13 @@ __device__ __forceinline__ void photo_linearize_feature(const PhotoLinArgs & a, 
     }
   }
   // J = ((I - psi psi^T) / sigma) (I - 1 1^T / m) D   (getPsiJacobian, photometric_utils.cpp:21-27)
-  const double whitened = sqrt(e2) / a.sigma;
+  const double whitened = sqrt(e2) / W.sigma;
   double sw = 1.0;
-  if (a.use_robust) {
-    const double p = a.robust_param;
-    sw = a.robust_is_huber ? (fabs(whitened) <= p ? 1.0 : sqrt(p / fabs(whitened))) : p * p / (p * p + whitened * whitened);
+  if (W.use_robust) {
+    const double p = W.robust_param;
+    sw = W.robust_is_huber ? (fabs(whitened) <= p ? 1.0 : sqrt(p / fabs(whitened))) : p * p / (p * p + whitened * whitened);
   }
-  const double wgt = sw / a.sigma;
+  const double wgt = sw / W.sigma;
   double row[13];
   auto psi_rows = [&](const double (&D)[6], const int at) {  // six columns at a time: two 6-wide sums instead of twelve single ones
     double cm[6], dc[6], pd[6];
@@ -1124,30 +1124,56 @@ __device__ __forceinline__ void photo_linearize_feature(const PhotoLinArgs & a, 
     triangle(std::integral_constant<int, 7>{});
 }
 
-constexpr int kAltLds = 512;  // beam altitudes kept in LDS by the factor kernel (taller sensors read the table in memory)
-__global__ __launch_bounds__(64 * kFeatPerBlock) void photo_linearize_kernel(const PhotoLinArgs a)
+constexpr int kAltLds = 512;  // beam altitudes kept in LDS by the factor kernels (taller sensors read the table in memory)
+__device__ __forceinline__ const float * photo_alt_to_lds(const PhotoModel & m, float * s_alt)
 {
-  __shared__ float s_alt[kAltLds];
-  const bool alt_lds = a.model.rows <= kAltLds;
-  if (alt_lds) {
-    for (int i = threadIdx.x; i < a.model.rows; i += 64 * kFeatPerBlock) s_alt[i] = a.model.alt[i];
-    __syncthreads();
-  }
-  photo_linearize_feature(a, alt_lds ? s_alt : nullptr);
-  // Completion number for a host that spins on the mapped block instead of paying a stream synchronisation (as K4 does
-  // for the ICP factor): every block makes its host writes visible (system-scope fence), takes a ticket, the last one
-  // re-arms the ticket and publishes.
-  if (a.seq) {
+  if (m.rows > kAltLds) return nullptr;
+  for (int i = threadIdx.x; i < m.rows; i += 64 * kFeatPerBlock) s_alt[i] = m.alt[i];
+  __syncthreads();
+  return s_alt;
+}
+// Completion number for a host that spins on the mapped block instead of paying a stream synchronisation (as K4 does
+// for the ICP factor): every block makes its host writes visible (system-scope fence), takes a ticket, the last one
+// re-arms the ticket and publishes.
+__device__ __forceinline__ void photo_linearize_publish(const PhotoLinLaunch & L)
+{
+  if (L.seq) {
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) {
-      const unsigned int prev = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned int prev = __hip_atomic_fetch_add(L.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
       if (prev == gridDim.x - 1) {
-        __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(a.host_seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(L.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(L.host_seq, L.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
   }
+}
+__global__ __launch_bounds__(64 * kFeatPerBlock) void photo_linearize_kernel(const PhotoLinArgs a)
+{
+  __shared__ float s_alt[kAltLds];
+  const float * alt = photo_alt_to_lds(a.launch.model, s_alt);
+  photo_linearize_feature(a.launch, a.factor, static_cast<int>(blockIdx.x) * kFeatPerBlock + (threadIdx.x >> 6), alt);
+  photo_linearize_publish(a.launch);
+}
+// The same for a window of factors in one launch.  Factor i owns the blocks [blk_start[i], blk_start[i + 1]) (none when it
+// has no features), so a block never straddles two factors and its descriptor is the same for all of its waves.
+__global__ __launch_bounds__(64 * kFeatPerBlock) void photo_linearize_batch_kernel(const PhotoLinLaunch L, const PhotoFactorDesc * __restrict__ descs,
+                                                                                  const int32_t * __restrict__ blk_start, const int n_factors)
+{
+  __shared__ float s_alt[kAltLds];
+  // the block's factor = (factors that start at or before this block) - 1: blk_start is ascending, so one ballot per 64
+  // entries counts them, and the count is a scalar
+  const int lane = threadIdx.x & 63, blk = static_cast<int>(blockIdx.x);
+  int fi = -1;
+  for (int base = 0; base < n_factors; base += 64) {
+    const int j = base + lane;
+    fi += __popcll(__ballot(j < n_factors && blk_start[j] <= blk));
+  }
+  const float * alt = photo_alt_to_lds(L.model, s_alt);
+  const PhotoFactorDesc & d = descs[fi];
+  photo_linearize_feature(L, d, (blk - blk_start[fi]) * kFeatPerBlock + (threadIdx.x >> 6), alt);
+  photo_linearize_publish(L);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1415,9 +1441,17 @@ hipError_t launch_photo_gather(const int2 * uv, int n_off, int n_cand, bool per_
 }
 hipError_t launch_photo_linearize(const PhotoLinArgs & a, hipStream_t stream)
 {
-  if (a.n_features <= 0) return hipSuccess;
-  const int grid = (a.n_features + kFeatPerBlock - 1) / kFeatPerBlock;
+  if (a.factor.n_features <= 0) return hipSuccess;
+  const int grid = (a.factor.n_features + kFeatPerBlock - 1) / kFeatPerBlock;
   hipLaunchKernelGGL(photo_linearize_kernel, dim3(grid), dim3(64 * kFeatPerBlock), 0, stream, a);
+  return hipGetLastError();
+}
+int photo_linearize_blocks(int n_features) { return n_features > 0 ? (n_features + kFeatPerBlock - 1) / kFeatPerBlock : 0; }
+hipError_t launch_photo_linearize_batch(const PhotoLinLaunch & L, const PhotoFactorDesc * descs, const int32_t * blk_start, int n_factors,
+                                        int n_blocks, hipStream_t stream)
+{
+  if (n_blocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(photo_linearize_batch_kernel, dim3(n_blocks), dim3(64 * kFeatPerBlock), 0, stream, L, descs, blk_start, n_factors);
   return hipGetLastError();
 }
 

@@ -137,6 +137,30 @@ public:
     return toHessian(r);
   }
 
+  // Every factor of a window, each at its own keys in `c`, in ONE kernel launch (mh_photo_factor_linearize_batch): the
+  // smoother re-linearizes all of its photometric factors per update (src/graph/manager.cpp:585-588).  The factors come
+  // from one Photometric (or are clones of its factors).  Each result, lastResult() and the factor's state are
+  // bit-identical to its own linearize(); a factor whose result holds an exception throws as linearize() would.
+  static std::vector<std::shared_ptr<GaussianFactor>> linearizeBatch(const std::vector<Ptr> & factors, const Values & c)
+  {
+    std::vector<std::shared_ptr<GaussianFactor>> out;
+    if (factors.empty()) return out;
+    std::vector<mh_photo_result> r(factors.size());
+    const BatchPoses p(factors, c);
+    factors[0]->ctx_->check(mh_photo_factor_linearize_batch(p.f.data(), factors.size(), p.Rb.data(), p.tb.data(), p.Ra(), p.ta(), r.data()),
+                            "mh_photo_factor_linearize_batch");
+    for (size_t i = 0; i < factors.size(); ++i) out.push_back(factors[i]->toHessian(r[i]));
+    return out;
+  }
+  // The same enqueued without waiting (next to ICPFactor::linearizeBatch on the same stream); collect() each factor after.
+  static void linearizeBatchAsync(const std::vector<Ptr> & factors, const Values & c)
+  {
+    if (factors.empty()) return;
+    const BatchPoses p(factors, c);
+    factors[0]->ctx_->check(mh_photo_factor_linearize_batch_async(p.f.data(), factors.size(), p.Rb.data(), p.tb.data(), p.Ra(), p.ta()),
+                            "mh_photo_factor_linearize_batch_async");
+  }
+
   std::vector<RejectStatus> getStatuses() const  // :49
   {
     const size_t n = mh_photo_factor_size(f_);
@@ -165,6 +189,26 @@ public:
 
 private:
   friend class Photometric;
+  struct BatchPoses  // the C ABI's arrays of a batch: T_b = c[keys()[0]] (and T_a = c[keys()[1]]) per factor
+  {
+    std::vector<mh_photo_factor *> f;
+    std::vector<double> Rb, tb, Ra_, ta_;
+    BatchPoses(const std::vector<Ptr> & factors, const Values & c)
+    {
+      for (const Ptr & x : factors) {
+        f.push_back(x->f_);
+        const PoseRM Tb = rowMajor(c.at<Pose3>(x->keys()[0]));
+        PoseRM Ta{};
+        if (x->is_binary_) Ta = rowMajor(c.at<Pose3>(x->keys()[1]));
+        Rb.insert(Rb.end(), Tb.R.begin(), Tb.R.end());
+        tb.insert(tb.end(), Tb.t.begin(), Tb.t.end());
+        Ra_.insert(Ra_.end(), Ta.R.begin(), Ta.R.end());
+        ta_.insert(ta_.end(), Ta.t.begin(), Ta.t.end());
+      }
+    }
+    const double * Ra() const { return Ra_.data(); }
+    const double * ta() const { return ta_.data(); }
+  };
   std::shared_ptr<HessianFactor> toHessian(const mh_photo_result & r) const
   {
     if (r.n_exceptions > 0)  // project(): "invalid x coordinate" (photometric_utils.cpp:90-97) / interpolated_map_T_Le_Lt.at()

@@ -198,6 +198,10 @@ struct Config
   // device-compacted candidates, on the photometric context's own stream) run on two worker threads beside the geometric
   // path of scan k + 1.  Same calls on the same handles in the same order per handle: the trajectory does not change by a bit.
   bool pipeline = true;
+  // FixedLagReplay only: every scan's photometric factor stays in the window beside its ICP factor (on its own pose, until the
+  // pose leaves) and all of them are re-linearized per iteration in one PhotometricFactor::linearizeBatchAsync, as the
+  // reference's smoother re-linearizes its window of photometric factors.  Off: the photometric factor on the newest pose only.
+  bool photo_window = false;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
   lidar::ManagerInputConfig input = lidar::defaultManagerInputConfig();
@@ -217,6 +221,7 @@ struct Result
 {
   std::vector<RT> poses;
   std::vector<int> photo_valid;
+  std::vector<int> photo_in_window;  // photo_window: photometric factors in the window at each scan's optimisation
   std::vector<std::vector<double>> costs;
   int n_keyframes = 0;
   double seconds = 0, stage[5] = {0, 0, 0, 0, 0};  // front_end, imu, factor_create, optimise, update_map
@@ -313,6 +318,7 @@ public:
     typename FactorT::Ptr f;
     bool has_Z;
     RT Z;
+    PhotometricFactor::Ptr pf;  // photo window: this scan's photometric factor (or none), released with the pose
   };
   WindowSmootherT(int window, int update_iters, double between_sigma_rot, double between_sigma_trans)
   : window_(window), update_iters_(update_iters)
@@ -334,6 +340,14 @@ public:
   }
   const RT & newest() const { return win.back().T; }
   void clear() { win.clear(); }
+  // on: optimise() re-linearizes the photometric factors the window's entries carry (Live::pf) instead of `pf`
+  void setPhotoWindow(bool on) { photo_window_ = on; }
+  size_t photoFactorsInWindow() const
+  {
+    size_t n = 0;
+    for (const Live & lv : win) n += lv.pf ? 1 : 0;
+    return n;
+  }
   // update_iters Gauss-Newton iterations at scan k; returns the cost before each iteration
   std::vector<double> optimise(const size_t k, const PhotometricFactor::Ptr & pf)
   {
@@ -352,7 +366,21 @@ public:
           factors[i] = win[i].f;
           v.insert(X(win[i].k), toPose3(win[i].T));
         }
-        if (pf) pf->linearizeAsync(v);  // queued ahead of the window: one wait for both
+        // the photometric factors of this iteration and the window entry each one constrains
+        std::vector<PhotometricFactor::Ptr> pfs;
+        std::vector<size_t> at;
+        if (photo_window_) {
+          for (size_t i = 0; i < nW; ++i)
+            if (win[i].pf) {
+              pfs.push_back(win[i].pf);
+              at.push_back(i);
+            }
+          PhotometricFactor::linearizeBatchAsync(pfs, v);  // one launch for all of them, queued ahead of the window
+        } else if (pf) {
+          pf->linearizeAsync(v);  // queued ahead of the window: one wait for both
+          pfs.push_back(pf);
+          at.push_back(nW - 1);
+        }
         const auto lin = FactorT::linearizeBatch(factors, v);
         std::vector<double> A(dim * dim, 0.0), g(dim, 0.0);
         double cost = 0.0;
@@ -366,15 +394,16 @@ public:
           }
           cost += h.constantTerm();
         }
-        if (pf) {
-          const auto hp = std::static_pointer_cast<HessianFactor>(pf->collect());
-          bool finite = pf->lastResult().status_hist[8] > 0;
+        for (size_t j = 0; j < pfs.size(); ++j) {
+          const PhotometricFactor::Ptr & pj = pfs[j];
+          const auto hp = std::static_pointer_cast<HessianFactor>(pj->collect());
+          bool finite = pj->lastResult().status_hist[8] > 0;
           const gtsam::Matrix Gp = hp->information();
           const gtsam::Vector gp = hp->linearTerm();
           for (int q = 0; q < 36 && finite; ++q) finite = std::isfinite(Gp(q / 6, q % 6));
           for (int q = 0; q < 6 && finite; ++q) finite = std::isfinite(gp(q));
           if (finite) {
-            const size_t o = 6 * (nW - 1);
+            const size_t o = 6 * at[j];
             for (int r = 0; r < 6; ++r) {
               for (int c = 0; c < 6; ++c) A[(o + r) * dim + o + c] += Gp(r, c);
               g[o + r] += -gp(r);
@@ -436,6 +465,7 @@ private:
   double Wb_[6];
   size_t first_k_ = 0;
   bool pushed_ = false;
+  bool photo_window_ = false;
 };
 
 using WindowSmoother = WindowSmootherT<ICPFactor>;
@@ -494,6 +524,7 @@ public:
     using Smoother = WindowSmootherT<typename Geo::Factor>;
     using Live = typename Smoother::Live;
     Smoother smoother(cfg_.window, cfg_.update_iters, cfg_.between_sigma_rot, cfg_.between_sigma_trans);
+    smoother.setPhotoWindow(cfg_.photo_window);
     std::deque<Live> & win = smoother.win;
     std::vector<RT> kf_poses;
     State prev = state0;
@@ -598,7 +629,9 @@ public:
         res.detail[7] += secs(c2, clk::now());
       }
       PhotometricFactor::Ptr pf = photo_ ? photo_->factor() : nullptr;
+      if (cfg_.photo_window) lv.pf = pf;
       smoother.push(lv);
+      if (cfg_.photo_window) res.photo_in_window.push_back(static_cast<int>(smoother.photoFactorsInWindow()));
       const auto a4 = clk::now();
       const std::vector<double> fs = smoother.optimise(k, pf);
       res.costs.push_back(fs);
@@ -824,6 +857,7 @@ class ManagerReplay
 public:
   ManagerReplay(const std::shared_ptr<lidar::Context> & ctx, const Config & cfg, size_t lru_horizon = 1000) : ctx_(ctx), cfg_(cfg), imu_(cfg.gravity)
   {
+    if (cfg.photo_window) throw std::runtime_error("ManagerReplay: photo_window is not offered through lidar::Manager (FixedLagReplay only)");
     lidar::ManagerConfig mc;
     mc.range_min = cfg.input.range_min;
     mc.range_max = cfg.input.range_max;

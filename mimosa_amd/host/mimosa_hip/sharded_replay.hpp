@@ -64,6 +64,7 @@ public:
   ShardedFixedLagReplay(const lidar::ShardCommunicator::Ptr & comm, const Config & cfg, size_t lru_horizon = 1000, int block_log2 = 3, bool force_collectives = false)
   : FixedLagReplayT<ShardedGeometric>(comm->context(), cfg, std::unique_ptr<ShardedGeometric>(new ShardedGeometric(comm, cfg, lru_horizon, block_log2, force_collectives)))
   {
+    if (cfg.photo_window) throw std::runtime_error("ShardedFixedLagReplay: photo_window is not offered by the sharded replay");
   }
 };
 

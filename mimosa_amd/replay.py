@@ -13,7 +13,8 @@ What stands in for the parts that are out of scope (GTSAM / ISAM2, the IMU manag
     exactly as Manager::deskewPoints does between samples (constant acc / omega extrapolation, manager.cpp:478-489) to get
     the per-timestamp deskew poses T_Le_Lt AND the relative-pose measurement between consecutive scans;
   * smoother: a dense Gauss-Newton over the `window` most recent poses: one unary ICP Hessian factor per live scan (all of
-    them re-linearized per iteration through ONE mh_icp_linearize_batch call), the photometric factor on the newest pose,
+    them re-linearized per iteration through ONE mh_icp_linearize_batch call), the photometric factor on the newest pose
+    (photo_window: every live scan's photometric factor, on its own pose, through ONE mh_photo_factor_linearize_batch call),
     between-factors from the IMU propagation, a prior on the oldest pose (what marginalisation leaves behind).  Retraction
     T <- T Exp(xi), xi = (omega, v) in the body frame: the perturbation the reference's Jacobians are taken against
     (geometric_factor.hpp:341-355, photometric_factor.hpp:262-279).
@@ -58,6 +59,9 @@ class ReplayConfig:
     keyframe_trans_thresh: float = 1.0                # ENWIDE: map_keyframe_trans_thresh
     keyframe_rot_thresh_deg: float = 20.0
     photometric: bool = True
+    # every scan's photometric factor stays in the window on its own pose (released with the pose) and all of them are
+    # re-linearized per iteration, as the reference's smoother does; off: the photometric factor on the newest pose only
+    photo_window: bool = False
     reg: dict = field(default_factory=synth.enwide_config)
     photo: dict = None
 
@@ -228,6 +232,11 @@ class HipBackend:
         r = pf.linearize(R, t)
         return np.asarray(r["H_bb"]).reshape(6, 6), np.asarray(r["b_b"]), float(r["f"]), int(r["status_hist"][8])
 
+    def linearize_photo_window(self, pfs, poses):
+        """Every photometric factor of the window at its own pose: ONE batched call."""
+        rs = self.capi.photo_linearize_batch(pfs, [p[0] for p in poses], [p[1] for p in poses])
+        return [(np.asarray(r["H_bb"]).reshape(6, 6), np.asarray(r["b_b"]), float(r["f"]), int(r["status_hist"][8])) for r in rs]
+
     def update_map(self, R, t):
         # Geometric::updateMap: copy-then-insert (geometric.cpp:494-495), f32 world transform (:483-490) on the device
         new = self.map.copy()
@@ -262,7 +271,7 @@ def write_native_input(path, cfg: ReplayConfig, scans, rng_seed=7, mode=synth.EN
             arr = np.ascontiguousarray(arr if dtype is None else np.asarray(arr, dtype))
             f.write(struct.pack("<Q", len(arr) if arr.dtype.itemsize == 32 else arr.size))
             f.write(arr.tobytes())
-        w([cfg.window, cfg.update_iters, int(cfg.photometric), mode, 1000], np.int32)
+        w([cfg.window, cfg.update_iters, int(cfg.photometric), mode, 1000] + ([1] if cfg.photo_window else []), np.int32)
         w([cfg.between_sigma_rot, cfg.between_sigma_trans, cfg.keyframe_trans_thresh, cfg.keyframe_rot_thresh_deg, *GRAVITY], np.float64)
         w(np.frombuffer(bytes(capi.make_reg_config(**cfg.reg)), np.uint8))
         w(np.frombuffer(bytes(capi.make_input_config()), np.uint8))
@@ -340,7 +349,7 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     v_body = np.asarray(cfg.v, float)
     Wb = np.diag([1.0 / cfg.between_sigma_rot**2] * 3 + [1.0 / cfg.between_sigma_trans**2] * 3)
     win = []          # live window: dicts(k, R, t, factor, Z (relative pose to the previous scan), fresh)
-    est, kf_poses, n_kf, costs, n_photo_valid = [], [], 0, [], []
+    est, kf_poses, n_kf, costs, n_photo_valid, n_photo_window = [], [], 0, [], [], []
     R_prev = t_prev = vel_prev = None
     t0 = time.perf_counter()
     for k, sc in enumerate(scans):
@@ -362,9 +371,14 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         f = backend.make_factor()
         pf = backend.make_photo_factor() if cfg.photometric else None
         Z = _between(R_start, p_start, R_pred, p_pred) if R_prev is not None else None
-        win.append(dict(k=k, R=R_pred, t=p_pred, f=f, Z=Z))
+        win.append(dict(k=k, R=R_pred, t=p_pred, f=f, Z=Z, pf=pf if cfg.photo_window else None))
         if len(win) > cfg.window:
-            backend.release(win.pop(0)["f"])
+            old = win.pop(0)
+            backend.release(old["f"])
+            if old["pf"] is not None:
+                backend.release(old["pf"])
+        if cfg.photo_window:
+            n_photo_window.append(sum(w["pf"] is not None for w in win))
         a4 = time.perf_counter()
         # ---- smoother update: every live factor re-linearized per iteration -------------------------------------
         nW = len(win)
@@ -378,11 +392,22 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
                 A[6 * i:6 * i + 6, 6 * i:6 * i + 6] += H
                 g[6 * i:6 * i + 6] += b
                 cost += fv
-            if pf is not None:
-                Hp, bp, fp, nv = backend.linearize_photo(pf, win[-1]["R"], win[-1]["t"])
+            if cfg.photo_window:
+                at = [i for i, w in enumerate(win) if w["pf"] is not None]
+                pfs, poses = [win[i]["pf"] for i in at], [(win[i]["R"], win[i]["t"]) for i in at]
+                if not at:
+                    plin = []
+                elif hasattr(backend, "linearize_photo_window"):
+                    plin = backend.linearize_photo_window(pfs, poses)
+                else:
+                    plin = [backend.linearize_photo(p, R_, t_) for p, (R_, t_) in zip(pfs, poses)]
+            else:
+                at = [nW - 1] if pf is not None else []
+                plin = [backend.linearize_photo(pf, win[-1]["R"], win[-1]["t"])] if pf is not None else []
+            for i, (Hp, bp, fp, nv) in zip(at, plin):
                 if nv and np.all(np.isfinite(Hp)) and np.all(np.isfinite(bp)):
-                    A[-6:, -6:] += Hp
-                    g[-6:] += bp
+                    A[6 * i:6 * i + 6, 6 * i:6 * i + 6] += Hp
+                    g[6 * i:6 * i + 6] += bp
                     cost += fp
             for i in range(1, nW):
                 if win[i]["Z"] is None:
@@ -427,7 +452,7 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
             if pf is not None:
                 n_photo_valid.append(int(pf.linearize(R, t)["status_hist"][8]))
             backend.photo_update_map(pf, R, t)
-            if pf is not None:
+            if pf is not None and not cfg.photo_window:
                 backend.release(pf)
         a6 = time.perf_counter()
         stage["front_end"] += (a1 - a0) + (a3 - a2)
@@ -440,8 +465,11 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         R_prev, t_prev, vel_prev = R, t, R @ (R_pred.T @ vel_pred)
     for w in win:
         backend.release(w["f"])
+        if w["pf"] is not None:
+            backend.release(w["pf"])
     total = time.perf_counter() - t0
     terr = [float(np.linalg.norm(te - s["t_gt"])) for (_, te), s in zip(est, scans)]
     rerr = [float(np.rad2deg(np.linalg.norm(_so3_log(Re.T @ s["R_gt"])))) for (Re, _), s in zip(est, scans)]
     return {"poses_est": est, "trans_err": terr, "rot_err_deg": rerr, "n_keyframes": n_kf, "seconds": total,
-            "scans_per_s": len(scans) / total, "stage_s": stage, "costs": costs, "photo_valid": n_photo_valid}
+            "scans_per_s": len(scans) / total, "stage_s": stage, "costs": costs, "photo_valid": n_photo_valid,
+            "photo_in_window": n_photo_window}
