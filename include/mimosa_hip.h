@@ -347,6 +347,33 @@ int mh_scan_get_unique_ns(const mh_scan * scan, uint32_t * out, size_t capacity,
  * Rt12[g] = pose (row-major R, then t, float) of the group with timestamp unique_ns[g].  Rt12 is read before the call returns;
  * the kernel itself is only ENQUEUED (every later call on the handle is ordered behind it on the context's stream). */
 int mh_scan_deskew(mh_scan * scan, const float * Rt12, size_t n_groups);
+/* Manager::deskewPoints with its pose part (lidar/manager.cpp:455-499) on the device as well: the caller hands over the IMU
+ * intervals the reference's loop walks, the device computes T_Le_Lt for every distinct timestamp (R = R_c Exp(omega dt),
+ * p = p_c + v_c dt + 1/2 R_c acc dt^2 + 1/2 g dt^2, :478-489; T_Le_W * T_W_Bt * T_B_S, :493-499), casts it to float (:504-505)
+ * and runs mh_scan_deskew's per-point kernel with it.  No timestamp comes back to the host, no pose table goes up. */
+#define MH_MAX_IMU_SEGMENTS 64    /* a 10 Hz scan at 400 Hz IMU has 40 */
+typedef struct mh_imu_segment {   /* one IMU interval (t0, t1] of manager.cpp:459-492 */
+  double t0, t1;                  /* curr_itr->first, next_itr->first (global seconds) */
+  double R[9], p[3], v[3];        /* curr_state: pose (R row-major) and velocity at t0 */
+  double acc[3], omega[3];        /* bias-corrected measurement of curr_itr (:479-480) */
+} mh_imu_segment;
+/* Interval rule of the reference's while loop (:469-476): ts = header_ts + ns * 1e-9 belongs to the FIRST segment with
+ * ts <= t1, dt = ts - t0 (negative before the first sample: extrapolated backwards, as there).  gravity = unit vector * |g|;
+ * T_Le_W = (T_W_Be * T_B_S)^-1 (:492-496).  n_seg == 0 is the first, uninitialised cloud (:399-408): identity for every group,
+ * the cloud is left as it is.  More than MH_MAX_IMU_SEGMENTS segments: MH_ERR_UNSUPPORTED.  The arguments are read before the
+ * call returns; the kernels are only ENQUEUED on the context's stream, as with mh_scan_deskew.
+ * A timestamp later than the last segment's t1 has no pose in the reference (its flat_map ends there; the host mirror throws
+ * "IMU samples end before the last point of the cloud").  The device cannot throw: the pose kernel raises a flag and writes
+ * identity for every group, so no point of that cloud is moved (the per-point kernel still runs, with identity: a finite
+ * coordinate keeps its value, -0.0 becomes +0.0), and the next call on the scan that waits for the device anyway
+ * (mh_scan_preprocess_geometric, mh_scan_get_points, mh_scan_get_deskew_poses, mh_photo_preprocess_commit,
+ * mh_photo_preprocess_scan_resident) returns MH_ERR_INVALID_ARG with that message.  The flag belongs to the prepared cloud:
+ * it stays up — also across another mh_scan_deskew_imu with a longer buffer — until the next mh_scan_prepare_input*. */
+int mh_scan_deskew_imu(mh_scan * scan, const mh_imu_segment * seg, size_t n_seg, double header_ts, const double gravity[3],
+                       const double R_Le_W[9], const double t_Le_W[3], const double R_B_S[9], const double t_B_S[3]);
+/* interpolated_map_T_Le_Lt_ (lidar/manager.cpp:390-405, :501-503) as mh_scan_deskew_imu left it on the device: 12 doubles per
+ * distinct timestamp (R row-major, then t), in the order of mh_scan_get_unique_ns.  T_Le_Lt == NULL: only *n_out. */
+int mh_scan_get_deskew_poses(const mh_scan * scan, double * T_Le_Lt, size_t capacity, size_t * n_out);
 /* Geometric::preprocess (geometric.cpp:128-183): Be_cloud_ = R_B_L * points_full_[geometric idx] + t_B_L
  * (f32), then Geometric::downsample (geometric.cpp:55-126) into sm_Be_cloud_ds_.  max_points_per_voxel <= 20
  * (the reference passes the literal 20). */
@@ -470,6 +497,14 @@ int mh_photo_preprocess_scan(mh_photo * photo, mh_scan * scan, const double * T_
  * mh_photo_destroy. */
 int mh_photo_preprocess_scan_begin(mh_photo * photo, mh_scan * scan, const double * T_Le_Lt, size_t n_groups);
 int mh_photo_preprocess_commit(mh_photo * photo);
+/* mh_photo_preprocess_scan / _begin with interpolated_map_T_Le_Lt_ (lidar/manager.cpp:501-503) read from the table
+ * mh_scan_deskew_imu left on the device: no pose table crosses PCIe.  MH_ERR_INVALID_ARG on a scan whose current cloud was not
+ * deskewed by mh_scan_deskew_imu.  _begin_resident is followed by mh_photo_preprocess_commit as _begin is.  When the scan's
+ * IMU buffer ended too early (see mh_scan_deskew_imu) both forms return MH_ERR_INVALID_ARG and drop the frame; the current
+ * frame stays what it was.  (The blocking form has by then written corrected intensities into the scan's cloud, which every
+ * waiting call on that scan reports as failed until it is prepared again.) */
+int mh_photo_preprocess_scan_resident(mh_photo * photo, mh_scan * scan);
+int mh_photo_preprocess_scan_begin_resident(mh_photo * photo, mh_scan * scan);
 /* One image of the current frame, rows * cols elements.  which: 0 img_intensity (float), 1 img_range (float),
  * 2 img_dx (float), 3 img_dy (float), 4 img_mask (uint8), 5 img_deskewed_cloud_idx (int32), 6 yaw_angles (float),
  * 7 proj_idx (int32, x 10 per pixel), 8 gradient magnitude (uint8, photometric.cpp:536-540), 9 detection mask

@@ -26,6 +26,7 @@ EXPORTS = [
     "mh_icp_wait", "mh_icp_linearize_batch", "mh_icp_get_state", "mh_icp_reset", "mh_icp_set_components", "mh_icp_size",
     "mh_deskew", "mh_transform_f32",
     "mh_scan_create", "mh_scan_destroy", "mh_scan_prepare_input", "mh_scan_prepare_input_device", "mh_scan_prefetch", "mh_scan_prepare_input_prefetched", "mh_scan_prepare_input_layout", "mh_scan_get_unique_ns", "mh_scan_deskew",
+    "mh_scan_deskew_imu", "mh_scan_get_deskew_poses", "mh_photo_preprocess_scan_resident", "mh_photo_preprocess_scan_begin_resident",
     "mh_scan_preprocess_geometric", "mh_scan_get_points", "mh_scan_get_indices", "mh_icp_create_from_scan",
     "mh_init_on_stream", "mh_map_insert_shard", "mh_icp_create_from_device", 
     "mh_shard_unique_id", "mh_shard_comm_init_rccl", "mh_shard_comm_init_local", "mh_shard_comm_destroy", "mh_shard_comm_world", "mh_shard_comm_rank",
@@ -262,6 +263,24 @@ class RadarTarget(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("x", "y", "z", "range", "azimuth", "elevation", "radial_speed", "intensity")]
 
 
+MH_MAX_IMU_SEGMENTS = 64
+# mh_imu_segment: one IMU interval (t0, t1] of Manager::deskewPoints (src/lidar/manager.cpp:459-492)
+IMU_SEGMENT_DTYPE = np.dtype([("t0", np.float64), ("t1", np.float64), ("R", np.float64, (9,)), ("p", np.float64, (3,)), ("v", np.float64, (3,)),
+                              ("acc", np.float64, (3,)), ("omega", np.float64, (3,))])
+
+
+def imu_segments(imu_t, imu_acc, imu_gyro, nav_R, nav_p, nav_v, bias_acc=(0, 0, 0), bias_gyro=(0, 0, 0)):
+    """The segments mh_scan_deskew_imu takes, from what Manager::deskewPoints has in hand: sample times, raw measurements, the
+    state at each sample time and the bias (interval c: state and bias-corrected measurement of sample c, manager.cpp:459-492)."""
+    m = len(imu_t)
+    seg = np.zeros(max(m - 1, 0), IMU_SEGMENT_DTYPE)
+    for c in range(m - 1):
+        seg[c] = (imu_t[c], imu_t[c + 1], np.asarray(nav_R[c], np.float64).ravel(), nav_p[c], nav_v[c],
+                  np.asarray(imu_acc[c], np.float64) - np.asarray(bias_acc, np.float64),
+                  np.asarray(imu_gyro[c], np.float64) - np.asarray(bias_gyro, np.float64))
+    return seg
+
+
 RADAR_TARGET_DTYPE = np.dtype([(n, np.float64) for n, _ in RadarTarget._fields_])
 
 
@@ -428,6 +447,8 @@ def load(build_if_missing: bool = True):
     L.mh_scan_prepare_input_prefetched.argtypes = [vp, C.POINTER(InputConfig), C.POINTER(ScanInfo)]
     L.mh_scan_get_unique_ns.argtypes = [vp, vp, sz, C.POINTER(sz)]
     L.mh_scan_deskew.argtypes = [vp, vp, sz]
+    L.mh_scan_deskew_imu.argtypes = [vp, vp, sz, C.c_double, vp, vp, vp, vp, vp]
+    L.mh_scan_get_deskew_poses.argtypes = [vp, vp, sz, C.POINTER(sz)]
     L.mh_scan_preprocess_geometric.argtypes = [vp, vp, vp, C.c_double, i32, C.c_double, C.POINTER(ScanInfo)]
     L.mh_scan_get_points.argtypes = [vp, i32, vp, sz, C.POINTER(sz)]
     L.mh_scan_get_indices.argtypes = [vp, i32, vp, sz, C.POINTER(sz)]
@@ -468,6 +489,8 @@ def load(build_if_missing: bool = True):
     L.mh_photo_preprocess_scan.argtypes = [vp, vp, vp, sz]
     L.mh_photo_preprocess_scan_begin.argtypes = [vp, vp, vp, sz]
     L.mh_photo_preprocess_commit.argtypes = [vp]
+    L.mh_photo_preprocess_scan_resident.argtypes = [vp, vp]
+    L.mh_photo_preprocess_scan_begin_resident.argtypes = [vp, vp]
     L.mh_photo_detect_prefetch.argtypes = [vp]
     L.mh_photo_get_image.argtypes = [vp, i32, vp, sz]
     L.mh_photo_num_features.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
@@ -699,6 +722,23 @@ class Scan:
     def deskew(self, Rt12):
         P = np.ascontiguousarray(Rt12, dtype=np.float32).reshape(-1, 12)
         self.ctx.check(self.L.mh_scan_deskew(self.h, _p(P), len(P)))
+
+    def deskew_imu(self, segments, header_ts, gravity, T_Le_W, T_B_S):
+        """Manager::deskewPoints with the per-timestamp poses computed on the device (src/lidar/manager.cpp:455-509).
+        segments: IMU_SEGMENT_DTYPE records (imu_segments builds them); gravity = unit vector * |g|; T_* = (R 3x3, t 3)."""
+        seg = np.ascontiguousarray(segments, dtype=IMU_SEGMENT_DTYPE)
+        d = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        g, Rl, tl, Rb, tb = d(gravity), d(T_Le_W[0]), d(T_Le_W[1]), d(T_B_S[0]), d(T_B_S[1])
+        self.ctx.check(self.L.mh_scan_deskew_imu(self.h, _p(seg) if len(seg) else None, len(seg), float(header_ts), _p(g), _p(Rl), _p(tl),
+                                                 _p(Rb), _p(tb)))
+
+    def deskew_poses(self):
+        """T_Le_Lt per distinct timestamp as mh_scan_deskew_imu left it on the device: (n, 12) doubles, R row-major then t."""
+        n = C.c_size_t()
+        self.ctx.check(self.L.mh_scan_get_deskew_poses(self.h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 12), np.float64)
+        self.ctx.check(self.L.mh_scan_get_deskew_poses(self.h, _p(out), n.value, C.byref(n)))
+        return out
 
     def preprocess_geometric(self, R_B_L, t_B_L, leaf=0.5, max_pts=20, min_dist=0.15) -> dict:
         R = np.ascontiguousarray(R_B_L, dtype=np.float32)
@@ -1087,6 +1127,13 @@ class Photo(_PhotoBase):
 
     def preprocess_commit(self):
         self.ctx.check(self.L.mh_photo_preprocess_commit(self.h))
+
+    def preprocess_scan_resident(self, scan):
+        """preprocess_scan with T_Le_Lt read from the table Scan.deskew_imu left on the device."""
+        self.ctx.check(self.L.mh_photo_preprocess_scan_resident(self.h, scan.h))
+
+    def preprocess_scan_begin_resident(self, scan):
+        self.ctx.check(self.L.mh_photo_preprocess_scan_begin_resident(self.h, scan.h))
 
     def detect_prefetch(self):
         self.ctx.check(self.L.mh_photo_detect_prefetch(self.h))

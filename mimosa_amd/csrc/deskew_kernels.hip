@@ -1,4 +1,5 @@
-// HIP kernels for the f32 rigid transforms of the scan (kernels K1 / K2 of SURVEY.md §2.3).
+// HIP kernels for the f32 rigid transforms of the scan (kernels K1 / K2 of SURVEY.md §2.3), and K0: the fp64 per-timestamp pose
+// table K1 reads, from the IMU intervals (Manager::deskewPoints' pose part, src/lidar/manager.cpp:455-499; mh_scan_deskew_imu).
 //
 // Reference: Manager::deskewPoints hot loop src/lidar/manager.cpp:496-509 (per-timestamp-group
 // pose, p <- R p + t in float), Geometric::preprocess body transform src/lidar/geometric.cpp:154-161,
@@ -14,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "icp_device.hpp"
+#include "scan_device.hpp"
 
 namespace mh
 {
@@ -89,6 +91,107 @@ __global__ __launch_bounds__(256) void copy16_kernel(const uint4 * __restrict__ 
   const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n16; i += stride) dst[i] = src[i];
 }
+
+// ---- K0: the per-timestamp pose table (Manager::deskewPoints' pose part, lidar/manager.cpp:455-499) ---------------------------
+// One lane per distinct timestamp, fp64, in the reference's operation order (no FMA: this file is built with -ffp-contract=off).
+// A latency-bound launch of a few waves (1024 timestamps = 4 workgroups): what matters is that it needs no host round trip.
+constexpr int kPoseThreads = 256;
+
+__device__ __forceinline__ void mat3_mul(const double * a, const double * b, double * c)
+{
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+}
+__device__ __forceinline__ void mat3_vec(const double * a, const double * v, double * o)
+{
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = a[3 * i] * v[0] + a[3 * i + 1] * v[1] + a[3 * i + 2] * v[2];
+}
+// gtsam::Rot3::Expmap (Rodrigues) with the small-angle branch of the host mirror's so3Expmap
+__device__ __forceinline__ void so3_expmap(const double wx, const double wy, const double wz, double * R)
+{
+  const double th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
+  const double K[9] = {0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0};
+  double A, B;
+  if (th < 1e-10) {
+    A = 1.0 - th2 / 6.0;
+    B = 0.5 - th2 / 24.0;
+  } else {
+    A = sin(th) / th;
+    B = (1.0 - cos(th)) / th2;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      double kk = 0.0;
+#pragma unroll
+      for (int m = 0; m < 3; ++m) kk += K[3 * i + m] * K[3 * m + j];
+      R[3 * i + j] = (i == j ? 1.0 : 0.0) + (A * K[3 * i + j] + B * kk);
+    }
+}
+
+__global__ __launch_bounds__(kPoseThreads) void deskew_pose_kernel(const uint32_t * __restrict__ unique_ns, const int n_groups,
+                                                                   const double * __restrict__ block, const int n_seg,
+                                                                   uint32_t * __restrict__ table_ns, double * __restrict__ T64,
+                                                                   float * __restrict__ T32, uint32_t * flag)
+{
+  // the fixed part and the intervals in LDS (at most 12 016 bytes): every lane of a wave reads the same one or two intervals
+  __shared__ double s_blk[sizeof(DeskewImuBlock) / sizeof(double)];
+  const int n_words = n_seg > 0 ? static_cast<int>((offsetof(DeskewImuBlock, seg) + n_seg * sizeof(mh_imu_segment)) / sizeof(double)) : 0;
+  for (int i = threadIdx.x; i < n_words; i += kPoseThreads) s_blk[i] = block[i];
+  __syncthreads();
+  const int g = blockIdx.x * kPoseThreads + threadIdx.x;
+  if (g >= n_groups) return;
+  const DeskewImuBlock & B = *reinterpret_cast<const DeskewImuBlock *>(s_blk);
+  const uint32_t ns = unique_ns[g];
+  double T[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+  // the timestamps ascend: if any of them lies behind the last interval, the last one does — every lane sees the same answer,
+  // so the whole table stays identity (no point is moved with a made-up pose) and the host learns of it at its next wait
+  const bool past_end = n_seg > 0 && B.header_ts + unique_ns[n_groups - 1] * 1.0e-9 > B.seg[n_seg - 1].t1;
+  if (past_end && g == 0) *flag = 1u;
+  if (n_seg > 0 && !past_end) {
+    const double ts = B.header_ts + ns * 1.0e-9;  // globalTs, manager.hpp:94
+    // the first interval with ts <= t1 (:469-476): found once for the wave's first timestamp (the same search in every lane:
+    // LDS broadcasts), then a forward scan of usually zero or one step
+    const double ts0 = B.header_ts + unique_ns[g & ~63] * 1.0e-9;
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (ts0 > B.seg[mid].t1)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    int c = lo;
+    while (c < n_seg - 1 && ts > B.seg[c].t1) ++c;
+    const mh_imu_segment & S = B.seg[c];
+    const double dt = ts - S.t0;
+    // :478-489  R = R_c Exp(omega dt),  p = p_c + v_c dt + 1/2 R_c acc dt^2 + 1/2 g dt^2
+    double E[9], R[9], Ra[3], p[3];
+    so3_expmap(S.omega[0] * dt, S.omega[1] * dt, S.omega[2] * dt, E);
+    mat3_mul(S.R, E, R);
+    mat3_vec(S.R, S.acc, Ra);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p[i] = S.p[i] + S.v[i] * dt + 0.5 * Ra[i] * dt * dt + 0.5 * B.gravity[i] * dt * dt;
+    // :493-499  T_Le_W * T_W_Bt * T_B_S  (Pose3 product: R1 R2, t1 + R1 t2)
+    double R1[9], t1[3], t2[3];
+    mat3_mul(B.R_Le_W, R, R1);
+    mat3_vec(B.R_Le_W, p, t1);
+    mat3_mul(R1, B.R_B_S, T);
+    mat3_vec(R1, B.t_B_S, t2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) T[9 + i] = (B.t_Le_W[i] + t1[i]) + t2[i];
+  }
+  table_ns[g] = ns;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    T64[12 * static_cast<size_t>(g) + i] = T[i];
+    T32[12 * static_cast<size_t>(g) + i] = static_cast<float>(T[i]);  // :504-505 cast<float>()
+  }
+}
 }  // namespace
 
 hipError_t launch_copy16(const void * src, void * dst, size_t bytes, hipStream_t stream)
@@ -106,6 +209,17 @@ hipError_t launch_deskew(mh_point32 * pts, int n, const uint32_t * unique_ns, co
 {
   hipLaunchKernelGGL(deskew_kernel, dim3(grid_for(n)), dim3(kThreads), 0, stream, reinterpret_cast<float4 *>(pts), n,
                      unique_ns, Rt12, n_groups, body_Rt12, n_groups <= kMaxGroupsLds ? 1 : 0);
+  return hipGetLastError();
+}
+hipError_t launch_deskew_poses(const uint32_t * unique_ns, int n_groups, const DeskewImuBlock * block, int n_seg, void * table,
+                               float * Rt12_f32, uint32_t * flag, hipStream_t stream)
+{
+  if (n_groups <= 0) return hipSuccess;
+  if (n_seg < 0 || n_seg > kMaxImuSegments) return hipErrorInvalidValue;
+  auto * ns = static_cast<uint32_t *>(table);
+  auto * T64 = reinterpret_cast<double *>(static_cast<char *>(table) + pose_table_ns_bytes(static_cast<size_t>(n_groups)));
+  hipLaunchKernelGGL(deskew_pose_kernel, dim3((n_groups + kPoseThreads - 1) / kPoseThreads), dim3(kPoseThreads), 0, stream, unique_ns,
+                     n_groups, reinterpret_cast<const double *>(block), n_seg, ns, T64, Rt12_f32, flag);
   return hipGetLastError();
 }
 hipError_t launch_transform(mh_point32 * pts, int n, const float * Rt12, hipStream_t stream)

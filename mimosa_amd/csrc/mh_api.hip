@@ -1247,7 +1247,7 @@ int mh_transform_f32(mh_ctx * ctx, mh_point32 * pts, size_t n, const float R[9],
 
 namespace
 {
-// pinned landing block of a scan: [ScanCounters | kUniqueCached timestamps | one flag word]
+// pinned landing block of a scan: [ScanCounters | kUniqueCached timestamps | two flag words (mh_internal.hpp: scan_pinned_flag), padded to 16 bytes]
 constexpr size_t kScanPinnedBytes = sizeof(mh::ScanCounters) + mh_scan::kUniqueCached * sizeof(uint32_t) + 16;
 int scan_ensure_pinned(mh_scan * s)
 {
@@ -1257,10 +1257,6 @@ int scan_ensure_pinned(mh_scan * s)
     s->h_c = static_cast<mh::ScanCounters *>(p);
   }
   return MH_OK;
-}
-uint32_t * scan_pinned_flag(mh_scan * s)
-{
-  return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(s->h_c) + sizeof(mh::ScanCounters) + mh_scan::kUniqueCached * sizeof(uint32_t));
 }
 int scan_fetch_counters(mh_scan * s, bool with_unique = false)
 {
@@ -1320,9 +1316,9 @@ void mh_scan_destroy(mh_scan * s)
   if (s->copy_done) (void)hipEventSynchronize(s->copy_done);
   s->d_full_raw.release(true);
   for (DevBuf * b : {&s->d_raw, &s->d_full, &s->d_geo_idx, &s->d_unique, &s->d_body, &s->d_ds, &s->d_kept_idx, &s->d_counters,
-                     &s->d_rt, &s->d_prep, &s->d_vox, &s->d_sensor})
+                     &s->d_rt, &s->d_prep, &s->d_vox, &s->d_sensor, &s->d_imu, &s->d_pose})
     b->release(true);
-  AllocCache::free_pinned(s->h_c, sizeof(mh::ScanCounters) + mh_scan::kUniqueCached * sizeof(uint32_t));
+  if (s->h_c) AllocCache::free_pinned(s->h_c, kScanPinnedBytes);  // the size it was taken with (flag words included)
   if (s->copy_done) (void)hipEventDestroy(s->copy_done);
   if (s->compute_mark) (void)hipEventDestroy(s->compute_mark);
   if (s->h_stage) AllocCache::free_pinned(s->h_stage, s->h_stage_cap);
@@ -1343,7 +1339,7 @@ static int scan_prepare_common(mh_scan * s, const mh_ouster_point * raw, bool ra
   if (cfg->point_skip_divisor < 1 || cfg->ring_skip_divisor < 1)
     return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": skip divisors must be >= 1");
   MH_HIP(ctx, mh_enter(ctx));
-  s->prepared = s->preprocessed = s->raw_valid = false;
+  s->prepared = s->preprocessed = s->raw_valid = s->imu_deskewed = false;
   s->n_unique_cached = 0;
   s->n_in = n;
   s->n_body = 0;
@@ -1372,6 +1368,7 @@ static int scan_prepare_common(mh_scan * s, const mh_ouster_point * raw, bool ra
                                        ctx->stream, canonical, ring_filter));
   const int rc = scan_fetch_counters(s, true);
   if (rc != MH_OK) return rc;
+  scan_pinned_flag(s)[1] = 0u;  // the stream has been waited for: no pose kernel of the previous cloud is left to raise it
   s->prepared = true;
   scan_fill_info(s, info);
   return MH_OK;
@@ -1535,6 +1532,7 @@ static int mh_scan_deskew_impl(mh_scan * s, const float * Rt12, size_t n_groups)
   mh_ctx * ctx = s->ctx;
   if (!s->prepared) return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_deskew: no mh_scan_prepare_input before");
   if (n_groups != s->c.n_unique_ns) return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_deskew: one pose per unique timestamp");
+  s->imu_deskewed = false;  // the device table (if any) no longer describes this cloud
   if (s->c.n_full == 0) return MH_OK;
   MH_HIP(ctx, mh_enter(ctx));
   if (s->keep_raw && !s->raw_valid) {  // points_raw_ = points_full_ before deskewing (lidar/manager.cpp:376-380)
@@ -1576,6 +1574,110 @@ int mh_scan_deskew(mh_scan * s, const float * Rt12, size_t n_groups)
   return guarded(s ? s->ctx : nullptr, "mh_scan_deskew", [&]() -> int { return mh_scan_deskew_impl(s, Rt12, n_groups); });
 }
 
+// the scan's pinned transfer block (h_rt), at least `bytes` large and no longer read by an earlier call's copy kernel
+static int scan_rt_block(mh_scan * s, size_t bytes)
+{
+  mh_ctx * ctx = s->ctx;
+  if (s->rt_done) MH_HIP(ctx, hipEventSynchronize(s->rt_done));  // the previous call's copy out of the block (long done)
+  if (bytes > s->h_rt_cap) {
+    size_t cap = size_t(64) << 10;
+    while (cap < bytes) cap <<= 1;
+    if (s->h_rt) AllocCache::free_pinned(s->h_rt, s->h_rt_cap);
+    s->h_rt = nullptr;
+    s->h_rt_cap = 0;
+    MH_HIP(ctx, AllocCache::alloc_pinned(&s->h_rt, cap));
+    s->h_rt_cap = cap;
+  }
+  if (!s->rt_done) MH_HIP(ctx, hipEventCreateWithFlags(&s->rt_done, hipEventDisableTiming));
+  return MH_OK;
+}
+
+static int mh_scan_deskew_imu_impl(mh_scan * s, const mh_imu_segment * seg, size_t n_seg, double header_ts, const double gravity[3],
+                                   const double R_Le_W[9], const double t_Le_W[3], const double R_B_S[9], const double t_B_S[3])
+{
+  const mh_ctx * ectx = s ? s->ctx : nullptr;
+  if (n_seg > MH_MAX_IMU_SEGMENTS) return fail(ectx, MH_ERR_UNSUPPORTED, "mh_scan_deskew_imu: more than MH_MAX_IMU_SEGMENTS (64) IMU segments");
+  if (!s || (n_seg && (!seg || !gravity || !R_Le_W || !t_Le_W || !R_B_S || !t_B_S)))
+    return fail(ectx, MH_ERR_INVALID_ARG, "mh_scan_deskew_imu: NULL argument");
+  mh_ctx * ctx = s->ctx;
+  if (!s->prepared) return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_deskew_imu: no mh_scan_prepare_input before");
+  const size_t n_groups = s->c.n_unique_ns;
+  MH_HIP(ctx, mh_enter(ctx));
+  if (s->keep_raw && !s->raw_valid && s->c.n_full) {  // points_raw_ = points_full_ before deskewing (lidar/manager.cpp:376-380)
+    MH_HIP(ctx, s->d_full_raw.reserve(s->c.n_full * sizeof(mh_point32), ctx->stream, false));
+    MH_HIP(ctx, mh::launch_copy16(s->d_full.p, s->d_full_raw.p, s->c.n_full * sizeof(mh_point32), ctx->stream));
+    s->raw_valid = true;
+  }
+  MH_HIP(ctx, s->d_rt.reserve((n_groups + 1) * 12 * sizeof(float) + 16, ctx->stream, false));
+  MH_HIP(ctx, s->d_pose.reserve(mh::pose_table_ns_bytes(n_groups) + n_groups * 12 * sizeof(double) + 32, ctx->stream, false));
+  MH_HIP(ctx, s->d_imu.reserve(sizeof(mh::DeskewImuBlock), ctx->stream, false));
+  const int rcp = scan_ensure_pinned(s);
+  if (rcp != MH_OK) return rcp;
+  if (n_seg) {
+    // the intervals leave the caller's buffer here, on the host: pinned block -> device by a copy kernel in stream order (12 KB at
+    // most; mh_scan_deskew has the measurement behind "a kernel, not hipMemcpyAsync").  A small DEVICE block rather than the
+    // mapped block itself under the kernel: every workgroup stages all of it, 512 times for a cloud with per-point timestamps
+    const int rcb = scan_rt_block(s, sizeof(mh::DeskewImuBlock));
+    if (rcb != MH_OK) return rcb;
+    auto * b = static_cast<mh::DeskewImuBlock *>(s->h_rt);
+    b->header_ts = header_ts;
+    std::memcpy(b->gravity, gravity, sizeof(b->gravity));
+    std::memcpy(b->R_Le_W, R_Le_W, sizeof(b->R_Le_W));
+    std::memcpy(b->t_Le_W, t_Le_W, sizeof(b->t_Le_W));
+    std::memcpy(b->R_B_S, R_B_S, sizeof(b->R_B_S));
+    std::memcpy(b->t_B_S, t_B_S, sizeof(b->t_B_S));
+    b->pad[0] = b->pad[1] = 0.0;
+    std::memcpy(b->seg, seg, n_seg * sizeof(mh_imu_segment));
+    const size_t bytes = (offsetof(mh::DeskewImuBlock, seg) + n_seg * sizeof(mh_imu_segment) + 15) & ~size_t(15);
+    void * d_src = nullptr;
+    MH_HIP(ctx, hipHostGetDevicePointer(&d_src, s->h_rt, 0));
+    MH_HIP(ctx, mh::launch_copy16(d_src, s->d_imu.p, bytes, ctx->stream));
+    MH_HIP(ctx, hipEventRecord(s->rt_done, ctx->stream));
+  }
+  void * d_flag = nullptr;
+  MH_HIP(ctx, hipHostGetDevicePointer(&d_flag, scan_pinned_flag(s), 0));
+  MH_HIP(ctx, mh::launch_deskew_poses(static_cast<const uint32_t *>(s->d_unique.p), static_cast<int>(n_groups),
+                                      static_cast<const mh::DeskewImuBlock *>(s->d_imu.p), static_cast<int>(n_seg), s->d_pose.p,
+                                      static_cast<float *>(s->d_rt.p), static_cast<uint32_t *>(d_flag) + 1, ctx->stream));
+  // K1 unchanged behind it on the same stream; the first cloud (no segments, identity poses) is left untouched as in :399-408.
+  // When the pose kernel finds the IMU buffer too short K1 still runs, over an identity table (the host cannot know without a
+  // wait): x = (1 x + (0 y + 0 z)) + 0 leaves every finite coordinate as it is, up to -0.0 becoming +0.0.  The flag stays up
+  // until the next prepare_input — clearing it here would race with a pose kernel still in flight
+  if (n_seg && s->c.n_full)
+    MH_HIP(ctx, mh::launch_deskew(static_cast<mh_point32 *>(s->d_full.p), static_cast<int>(s->c.n_full),
+                                  static_cast<const uint32_t *>(s->d_unique.p), static_cast<const float *>(s->d_rt.p),
+                                  static_cast<int>(n_groups), nullptr, ctx->stream));
+  s->imu_deskewed = true;
+  s->preprocessed = false;
+  return MH_OK;
+}
+int mh_scan_deskew_imu(mh_scan * s, const mh_imu_segment * seg, size_t n_seg, double header_ts, const double gravity[3],
+                       const double R_Le_W[9], const double t_Le_W[3], const double R_B_S[9], const double t_B_S[3])
+{
+  return guarded(s ? s->ctx : nullptr, "mh_scan_deskew_imu",
+                 [&]() -> int { return mh_scan_deskew_imu_impl(s, seg, n_seg, header_ts, gravity, R_Le_W, t_Le_W, R_B_S, t_B_S); });
+}
+
+static int mh_scan_get_deskew_poses_impl(const mh_scan * s, double * T_Le_Lt, size_t capacity, size_t * n_out)
+{
+  if (!s || !n_out) return fail(s ? s->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_scan_get_deskew_poses: NULL argument");
+  mh_ctx * ctx = s->ctx;
+  if (!s->prepared || !s->imu_deskewed) return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_get_deskew_poses: no mh_scan_deskew_imu on this cloud");
+  *n_out = s->c.n_unique_ns;
+  if (!T_Le_Lt) return MH_OK;
+  if (capacity < *n_out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_get_deskew_poses: buffer too small");
+  MH_HIP(ctx, mh_enter(ctx));
+  if (*n_out)
+    MH_HIP(ctx, hipMemcpyAsync(T_Le_Lt, static_cast<const char *>(s->d_pose.p) + mh::pose_table_ns_bytes(*n_out), *n_out * 12 * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return scan_imu_error(s, ctx, "mh_scan_get_deskew_poses");
+}
+int mh_scan_get_deskew_poses(const mh_scan * s, double * T_Le_Lt, size_t capacity, size_t * n_out)
+{
+  return guarded(s ? s->ctx : nullptr, "mh_scan_get_deskew_poses", [&]() -> int { return mh_scan_get_deskew_poses_impl(s, T_Le_Lt, capacity, n_out); });
+}
+
 static int mh_scan_preprocess_geometric_impl(mh_scan * s, const float R_B_L[9], const float t_B_L[3], double leaf_size,
                                  int max_points_per_voxel, double min_dist_in_voxel, mh_scan_info * info)
 {
@@ -1602,6 +1704,8 @@ static int mh_scan_preprocess_geometric_impl(mh_scan * s, const float R_B_L[9], 
                                     static_cast<uint32_t *>(s->d_kept_idx.p), static_cast<mh_point32 *>(s->d_ds.p), cnt, ctx->stream));
   const int rc = scan_fetch_counters(s);
   if (rc != MH_OK) return rc;
+  const int rci = scan_imu_error(s, ctx, "mh_scan_preprocess_geometric");
+  if (rci != MH_OK) return rci;
   if (n == 0) s->c.n_downsampled = s->c.bad_coord = 0;
   if (s->c.bad_coord) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_scan_preprocess_geometric: a voxel coordinate exceeds +-2^20");
   s->preprocessed = true;
@@ -1627,7 +1731,7 @@ static int mh_scan_get_points_impl(const mh_scan * s, int which, mh_point32 * ou
   MH_HIP(ctx, mh_enter(ctx));
   if (*n_out) MH_HIP(ctx, hipMemcpyAsync(out, b.p, *n_out * sizeof(mh_point32), hipMemcpyDeviceToHost, ctx->stream));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MH_OK;
+  return scan_imu_error(s, ctx, "mh_scan_get_points");
 }
 int mh_scan_get_points(const mh_scan * s, int which, mh_point32 * out, size_t capacity, size_t * n_out)
 {

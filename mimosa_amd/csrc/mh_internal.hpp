@@ -505,7 +505,25 @@ struct mh_scan
   void * h_rt = nullptr;
   size_t h_rt_cap = 0;
   hipEvent_t rt_done = nullptr;
+  // mh_scan_deskew_imu: the IMU intervals travel the same way (h_rt -> d_imu); d_pose = [timestamps | double[12] per group], the
+  // table the photometric frame and mh_scan_get_deskew_poses read; the float cast goes into d_rt, where K1 reads it
+  DevBuf d_imu, d_pose;
+  bool imu_deskewed = false;  // the current cloud was deskewed by mh_scan_deskew_imu: d_pose is its table
 };
+// the two flag words behind a scan's pinned landing block [ScanCounters | kUniqueCached timestamps | flags]: [0] a ring number
+// >= 128 (mh_scan_prepare_input_layout), [1] deskew_pose_kernel met a timestamp behind the last IMU interval
+inline uint32_t * scan_pinned_flag(const mh_scan * s)
+{
+  return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(s->h_c) + sizeof(mh::ScanCounters) + mh_scan::kUniqueCached * sizeof(uint32_t));
+}
+// for the calls that have just waited for the device: what the pose kernel could not report by throwing (lidar/manager.cpp:469-476
+// runs off the end of the IMU buffer there)
+inline int scan_imu_error(const mh_scan * s, const mh_ctx * ctx, const char * who)
+{
+  if (s && s->imu_deskewed && s->h_c && scan_pinned_flag(s)[1])
+    return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": deskewPoints: IMU samples end before the last point of the cloud");
+  return MH_OK;
+}
 
 // IncrementalVoxelMapPCL counterpart: the device-resident voxel map (map_device.hpp / map_kernels.hip).  The device
 // arrays ARE the map; the host keeps counters only (refreshed from the mapped state after every mutation).

@@ -359,7 +359,8 @@ int upload_pinned(mh_ctx * ctx, DevBuf & b, const void * pinned_src, size_t byte
 // scan_writeback: the corrected intensities also go straight into scan_cloud (a committing mh_photo_preprocess_scan).
 // *folded says whether both were done inside the chain's launches (else the caller copies first / writes back afterwards).
 int preprocess_device(mh_photo * ph, PhotoFrame * fr, const mh_point32 * d_raw, size_t n, const uint32_t * unique_ns,
-                      const double * T_Le_Lt, size_t n_groups, mh_point32 * scan_cloud = nullptr, bool scan_writeback = false, bool * folded = nullptr)
+                      const double * T_Le_Lt, size_t n_groups, mh_point32 * scan_cloud = nullptr, bool scan_writeback = false, bool * folded = nullptr,
+                      const void * d_pose_table = nullptr)
 {
   if (folded) *folded = false;
   mh_ctx * ctx = ph->ctx;
@@ -376,7 +377,15 @@ int preprocess_device(mh_photo * ph, PhotoFrame * fr, const mh_point32 * d_raw, 
   MH_HIP(ctx, ph->d_int_out.reserve((n ? n : 1) * sizeof(float), ctx->stream, false));
   const void * pose_src = nullptr;
   size_t pose_bytes = 0;
-  {
+  if (d_pose_table) {
+    // the scan's own table (mh_scan_deskew_imu), already [timestamps | poses] in device memory: the frame-reset launch copies
+    // from there instead of from a mapped pinned block
+    const size_t b_ns = mh::pose_table_ns_bytes(n_groups), b_rt = n_groups * 12 * sizeof(double);
+    MH_HIP(ctx, fr->d_pose_ns.reserve(b_ns + b_rt + 32, ctx->stream, false));
+    fr->pose_rt_offset = b_ns;
+    pose_src = d_pose_table;
+    pose_bytes = n_groups ? b_ns + ((b_rt + 15) & ~size_t(15)) : 0;
+  } else {
     const size_t b_ns = (n_groups * sizeof(uint32_t) + 255) & ~size_t(255), b_rt = n_groups * 12 * sizeof(double);
     size_t cap = size_t(64) << 10;
     while (cap < b_ns + b_rt) cap <<= 1;
@@ -946,7 +955,10 @@ int mh_scan_keep_raw(mh_scan * scan, int keep)
   return MH_OK;
 }
 
-static int photo_finish_preprocess(mh_photo * photo, PhotoFrame * fr, mh_point32 * host_desk, size_t n, bool commit = true)
+// imu_scan: the scan whose device pose table the frame was built from (the _resident form) — what its pose kernel could not throw
+// is reported here, after the wait and before the frame becomes current, as mh_photo_preprocess_commit does
+static int photo_finish_preprocess(mh_photo * photo, PhotoFrame * fr, mh_point32 * host_desk, size_t n, bool commit = true,
+                                   const mh_scan * imu_scan = nullptr)
 {
   mh_ctx * ctx = photo->ctx;
   // corrected intensities back into the caller's cloud (:307-314)
@@ -961,6 +973,14 @@ static int photo_finish_preprocess(mh_photo * photo, PhotoFrame * fr, mh_point32
     MH_HIP(ctx, hipMemcpyAsync(photo->h_int_out, photo->d_int_out.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  {
+    // it comes first: a cloud left undeskewed may well fail project() too
+    const int rci = scan_imu_error(imu_scan, ctx, "mh_photo_preprocess_scan_resident");
+    if (rci != MH_OK) {
+      frame_release(fr);
+      return rci;
+    }
+  }
   if (photo->h_counters->project_throw) {
     frame_release(fr);
     return fail(ctx, MH_ERR_INVALID_ARG,
@@ -1031,12 +1051,17 @@ static int photo_writeback_scan(mh_photo * photo, PhotoFrame * fr, mh_scan * sca
   return MH_OK;
 }
 
-static int photo_preprocess_scan(mh_photo * photo, mh_scan * scan, const double * T_Le_Lt, size_t n_groups, bool commit)
+static int photo_preprocess_scan(mh_photo * photo, mh_scan * scan, const double * T_Le_Lt, size_t n_groups, bool commit, bool resident = false)
 {
-  if (!photo || !scan || (n_groups && !T_Le_Lt))
+  if (!photo || !scan || (!resident && n_groups && !T_Le_Lt))
     return fail(photo ? photo->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_photo_preprocess_scan: NULL argument");
   mh_ctx * ctx = photo->ctx;
   return guarded(ctx, "mh_photo_preprocess_scan", [&]() -> int {
+    if (resident) {
+      if (!scan->prepared || !scan->imu_deskewed)
+        return fail(ctx, MH_ERR_INVALID_ARG, "mh_photo_preprocess_scan_resident: the scan's cloud was not deskewed by mh_scan_deskew_imu");
+      n_groups = scan->c.n_unique_ns;
+    }
     if (scan->ctx->device != ctx->device) return fail(ctx, MH_ERR_INVALID_ARG, "mh_photo_preprocess_scan: scan lives on another device");
     if (!scan->prepared) return fail(ctx, MH_ERR_INVALID_ARG, "mh_photo_preprocess_scan: no mh_scan_prepare_input before");
     if (!scan->raw_valid) return fail(ctx, MH_ERR_INVALID_ARG, "mh_photo_preprocess_scan: call mh_scan_keep_raw(scan, 1) before mh_scan_deskew");
@@ -1057,8 +1082,10 @@ static int photo_preprocess_scan(mh_photo * photo, mh_scan * scan, const double 
       frame_release(fr);
       return hip_fail(ctx, e, "mh_photo_preprocess_scan: frame cloud");
     }
-    std::vector<uint32_t> uns(n_groups);
-    if (n_groups && scan->n_unique_cached == n_groups) {  // the host copy that came back with mh_scan_prepare_input's counters
+    std::vector<uint32_t> uns(resident ? 0 : n_groups);
+    if (resident) {
+      // nothing to fetch: the timestamps sit in front of the poses in the scan's table
+    } else if (n_groups && scan->n_unique_cached == n_groups) {  // the host copy that came back with mh_scan_prepare_input's counters
       std::memcpy(uns.data(), scan->h_c + 1, n_groups * sizeof(uint32_t));
     } else {
       if (n_groups) MH_HIP(ctx, hipMemcpyAsync(uns.data(), scan->d_unique.p, n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1068,7 +1095,7 @@ static int photo_preprocess_scan(mh_photo * photo, mh_scan * scan, const double 
     // intensities into the scan by its last (six launches -> four)
     bool folded = false;
     int rc = preprocess_device(photo, fr, static_cast<const mh_point32 *>(scan->d_full_raw.p), n, uns.data(), T_Le_Lt, n_groups,
-                               static_cast<mh_point32 *>(scan->d_full.p), commit, &folded);
+                               static_cast<mh_point32 *>(scan->d_full.p), commit, &folded, resident ? scan->d_pose.p : nullptr);
     if (rc != MH_OK) {
       frame_release(fr);
       return rc;
@@ -1087,9 +1114,11 @@ static int photo_preprocess_scan(mh_photo * photo, mh_scan * scan, const double 
       frame_release(fr);
       return rc;
     }
-    return photo_finish_preprocess(photo, fr, nullptr, n, true);
+    return photo_finish_preprocess(photo, fr, nullptr, n, true, resident ? scan : nullptr);
   });
 }
+int mh_photo_preprocess_scan_resident(mh_photo * photo, mh_scan * scan) { return photo_preprocess_scan(photo, scan, nullptr, 0, true, true); }
+int mh_photo_preprocess_scan_begin_resident(mh_photo * photo, mh_scan * scan) { return photo_preprocess_scan(photo, scan, nullptr, 0, false, true); }
 int mh_photo_preprocess_scan(mh_photo * photo, mh_scan * scan, const double * T_Le_Lt, size_t n_groups)
 {
   return photo_preprocess_scan(photo, scan, T_Le_Lt, n_groups, true);
@@ -1108,6 +1137,11 @@ int mh_photo_preprocess_commit(mh_photo * photo)
     MH_HIP(ctx, hipEventSynchronize(photo->next_ev));  // the frame's kernels (normally long done: they ran beside the caller's work)
     PhotoFrame * fr = photo->next_frame;
     photo->next_frame = nullptr;
+    if (scan_imu_error(photo->next_scan, ctx, "mh_photo_preprocess_commit") != MH_OK) {  // of mh_scan_deskew_imu, behind which _begin queued
+      frame_release(fr);
+      photo->next_scan = nullptr;
+      return MH_ERR_INVALID_ARG;
+    }
     if (photo->h_counters->project_throw) {
       frame_release(fr);
       return fail(ctx, MH_ERR_INVALID_ARG,

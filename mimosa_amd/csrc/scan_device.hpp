@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/mimosa_hip.h"
@@ -26,6 +27,23 @@ struct Rt12  // row-major R, then t; passed to kernels by value
 {
   float v[12];
 };
+
+// What mh_scan_deskew_imu hands to deskew_pose_kernel: the fixed part, then n_seg IMU intervals.  Filled in the scan's pinned
+// block, copied to the device by launch_copy16 (16-byte words: the size is a multiple of 16), staged in LDS per workgroup.
+constexpr int kMaxImuSegments = 64;
+struct DeskewImuBlock
+{
+  double header_ts;
+  double gravity[3];
+  double R_Le_W[9], t_Le_W[3];
+  double R_B_S[9], t_B_S[3];
+  double pad[2];
+  mh_imu_segment seg[kMaxImuSegments];
+};
+static_assert(sizeof(mh_imu_segment) == 184 && offsetof(DeskewImuBlock, seg) == 240 && sizeof(DeskewImuBlock) % 16 == 0,
+              "DeskewImuBlock is copied as 16-byte words and read as doubles");
+// the scan's pose table on the device, laid out as a photometric frame keeps it: [timestamps, padded to 256 B | double[12] per group]
+inline size_t pose_table_ns_bytes(size_t n_groups) { return (n_groups * sizeof(uint32_t) + 255) & ~size_t(255); }
 
 struct PrepareLayout
 {
@@ -58,5 +76,11 @@ hipError_t launch_decode_points(const void * raw, uint32_t n, const mh_point_lay
 hipError_t launch_preprocess(const mh_point32 * points_full, const uint32_t * geo_idx, uint32_t n, const Rt12 & body_from_lidar,
                              double leaf, uint32_t max_pts, double min_dist, void * scratch, mh_point32 * body,
                              uint32_t * kept_idx, mh_point32 * out, ScanCounters * counters, hipStream_t stream);
+
+// Manager::deskewPoints' pose part (lidar/manager.cpp:455-499) for every distinct timestamp: T_Le_Lt as double[12] behind a copy
+// of the timestamps in `table` (pose_table_ns_bytes) and as float[12] in Rt12_f32 (what launch_deskew reads).  n_seg == 0:
+// identity.  A timestamp behind the last interval: identity for the whole scan and *flag = 1 (flag: mapped host word).
+hipError_t launch_deskew_poses(const uint32_t * unique_ns, int n_groups, const DeskewImuBlock * block, int n_seg, void * table,
+                               float * Rt12_f32, uint32_t * flag, hipStream_t stream);
 
 }  // namespace mh

@@ -334,9 +334,7 @@ public:
   {
     ctx_->check(mh_scan_prepare_input(scan_, raw, n, &cfg, &info_), "mh_scan_prepare_input");
     corrected_ts_ = header_ts + info_.last_point_ns * 1.0e-9;
-    unique_ns_.resize(info_.n_unique_ns);
-    size_t m = 0;
-    ctx_->check(mh_scan_get_unique_ns(scan_, unique_ns_.data(), unique_ns_.size(), &m), "mh_scan_get_unique_ns");
+    fetchUniqueNs();
   }
   // Pipelined input: prefetch() stages the NEXT cloud (pinned copy + host-to-device copy on this front end's own copy stream)
   // while another ScanFrontEnd is being processed — it may run on another host thread; prepareInputPrefetched() is
@@ -346,9 +344,7 @@ public:
   {
     ctx_->check(mh_scan_prepare_input_prefetched(scan_, &cfg, &info_), "mh_scan_prepare_input_prefetched");
     corrected_ts_ = header_ts + info_.last_point_ns * 1.0e-9;
-    unique_ns_.resize(info_.n_unique_ns);
-    size_t m = 0;
-    ctx_->check(mh_scan_get_unique_ns(scan_, unique_ns_.data(), unique_ns_.size(), &m), "mh_scan_get_unique_ns");
+    fetchUniqueNs();
   }
   // Manager::prepareInput<PointT> for any of the reference's point types (the sensor's own records go to the device).
   // transpose_pointcloud is honoured for PointRslidar / PointVelodyneAnybotics only, as in the reference (:177-203).
@@ -362,14 +358,15 @@ public:
                                              order.organize_pointcloud_by_ring ? 1 : 0, header_ts, &cfg, &info_),
                 "mh_scan_prepare_input_layout");
     corrected_ts_ = header_ts + info_.last_point_ns * 1.0e-9;
-    unique_ns_.resize(info_.n_unique_ns);
-    size_t m = 0;
-    ctx_->check(mh_scan_get_unique_ns(scan_, unique_ns_.data(), unique_ns_.size(), &m), "mh_scan_get_unique_ns");
+    fetchUniqueNs();
   }
   // points_raw_ (manager.cpp:376-380): keep a copy of points_full_ as it was before deskewPoints — Photometric::preprocess
   // reads it (call before deskewPoints)
   void keepRaw(bool keep) { ctx_->check(mh_scan_keep_raw(scan_, keep ? 1 : 0), "mh_scan_keep_raw"); }
   const std::vector<uint32_t> & uniqueNs() const { return unique_ns_; }  // the IMU propagation runs over these
+  // A caller that deskews with deskewPointsFromImu needs no timestamp on the host: with `keep` false prepareInput* leaves
+  // uniqueNs() empty and skips mh_scan_get_unique_ns (a stream wait and a copy for a cloud with per-point times)
+  void keepUniqueNsOnHost(bool keep) { unique_ns_on_host_ = keep; }
   double correctedTs() const { return corrected_ts_; }
   const mh_scan_info & info() const { return info_; }
 
@@ -390,6 +387,28 @@ public:
     for (size_t i = 0; i < 12 * n; ++i) f[i] = static_cast<float>(Rt12[i]);
     ctx_->check(mh_scan_deskew(scan_, f.data(), n), "mh_scan_deskew");
   }
+  // Manager::deskewPoints with the pose part (manager.cpp:455-499) on the device too: `segments` from imuSegments() below,
+  // gravity = unit vector * |g|, T_W_Be = propagated_state_.pose() (:492-493).  No segment: the first, uninitialised cloud
+  // (:399-408).  An IMU buffer that ends before the last point is reported by the next call that waits for the device.
+  void deskewPointsFromImu(const std::vector<mh_imu_segment> & segments, const double header_ts, const V3D & gravity, const Pose3 & T_W_Be,
+                           const Pose3 & T_B_S)
+  {
+    const PoseRM le_w = rowMajor(T_B_S.inverse() * T_W_Be.inverse()), b_s = rowMajor(T_B_S);  // T_Le_W (:496)
+    const double g[3] = {gravity(0), gravity(1), gravity(2)};
+    ctx_->check(mh_scan_deskew_imu(scan_, segments.data(), segments.size(), header_ts, g, le_w.R.data(), le_w.t.data(), b_s.R.data(), b_s.t.data()),
+                "mh_scan_deskew_imu");
+  }
+  // interpolated_map_T_Le_Lt_'s poses as deskewPointsFromImu left them on the device, for a caller that still wants them
+  std::vector<Pose3> deskewPoses() const
+  {
+    size_t n = 0;
+    ctx_->check(mh_scan_get_deskew_poses(scan_, nullptr, 0, &n), "mh_scan_get_deskew_poses");
+    std::vector<double> T(12 * n);
+    ctx_->check(mh_scan_get_deskew_poses(scan_, T.data(), n, &n), "mh_scan_get_deskew_poses");
+    std::vector<Pose3> out(n);
+    for (size_t g = 0; g < n; ++g) out[g] = pose3(&T[12 * g], &T[12 * g + 9]);
+    return out;
+  }
   // which: 0 points_full_, 1 Be_cloud_, 2 sm_Be_cloud_ds_
   PointCloud download(int which) const
   {
@@ -404,10 +423,18 @@ public:
   mh_scan_info & mutableInfo() { return info_; }
 
 private:
+  void fetchUniqueNs()
+  {
+    unique_ns_.resize(unique_ns_on_host_ ? info_.n_unique_ns : 0);
+    if (!unique_ns_on_host_) return;
+    size_t m = 0;
+    ctx_->check(mh_scan_get_unique_ns(scan_, unique_ns_.data(), unique_ns_.size(), &m), "mh_scan_get_unique_ns");
+  }
   std::shared_ptr<Context> ctx_;
   mh_scan * scan_ = nullptr;
   mh_scan_info info_{};
   std::vector<uint32_t> unique_ns_;
+  bool unique_ns_on_host_ = true;
   double corrected_ts_ = 0;
 };
 
@@ -872,6 +899,34 @@ inline std::vector<Pose3> computeDeskewPoses(const std::vector<double> & imu_t, 
   out.reserve(T_W_Bts.size());
   for (const Pose3 & T : T_W_Bts) out.push_back(T_Le_W * T * T_B_S);
   return out;
+}
+
+// The IMU intervals mh_scan_deskew_imu / ScanFrontEnd::deskewPointsFromImu take, from the same inputs as computeDeskewPoses:
+// interval c = (imu_t[c], imu_t[c + 1]] with the state at imu_t[c] and the bias-corrected measurement of sample c (:459-492).
+// The per-timestamp half of computeDeskewPoses then runs on the device.
+inline std::vector<mh_imu_segment> imuSegments(const std::vector<double> & imu_t, const std::vector<V3D> & imu_acc, const std::vector<V3D> & imu_gyro,
+                                               const std::vector<NavState> & nav, const V3D & bias_acc, const V3D & bias_gyro)
+{
+  if (imu_t.size() < 2) throw std::runtime_error("Preintegration not possible as there are less than 2 measurements P1");  // :442-446
+  if (imu_acc.size() != imu_t.size() || imu_gyro.size() != imu_t.size() || nav.size() != imu_t.size())
+    throw std::runtime_error("imuSegments: one measurement and one state per IMU sample");
+  if (imu_t.size() - 1 > MH_MAX_IMU_SEGMENTS) throw std::runtime_error("imuSegments: more than MH_MAX_IMU_SEGMENTS IMU intervals in one scan");
+  std::vector<mh_imu_segment> seg(imu_t.size() - 1);
+  for (size_t c = 0; c + 1 < imu_t.size(); ++c) {
+    mh_imu_segment & s = seg[c];
+    s.t0 = imu_t[c];
+    s.t1 = imu_t[c + 1];
+    const A9 R = rowMajor(nav[c].pose().rotation().matrix());
+    const A3 p = toArray(nav[c].pose().translation()), v = toArray(nav[c].velocity());
+    for (int i = 0; i < 9; ++i) s.R[i] = R[static_cast<size_t>(i)];
+    for (int i = 0; i < 3; ++i) {
+      s.p[i] = p[static_cast<size_t>(i)];
+      s.v[i] = v[static_cast<size_t>(i)];
+      s.acc[i] = imu_acc[c](i) - bias_acc(i);      // ConstantBias::correctAccelerometer (:479)
+      s.omega[i] = imu_gyro[c](i) - bias_gyro(i);  // ::correctGyroscope (:480)
+    }
+  }
+  return seg;
 }
 
 // Manager::deskewPoints' per-point part (manager.cpp:496-509).  T_Le_Lt[g] is the pose of the sensor at

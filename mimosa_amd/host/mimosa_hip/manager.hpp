@@ -185,6 +185,12 @@ public:
   Photometric & photometric() { return *photometric_; }
   ScanFrontEnd & scan() { return scan_; }
   const gtsam::NavState & propagatedState() const { return propagated_state_; }
+  // Opt-in: deskewPoints' per-timestamp poses (manager.cpp:468-499) are computed on the device (mh_scan_deskew_imu) and the
+  // photometric frame reads them there; no pose table comes into being on the host.  The distinct timestamps are still
+  // fetched (the cached copy that came back with prepareInput's counters for up to 4096 of them): :421-433 moves the state
+  // back to the FIRST one.  Off by default.
+  void setDevicePoses(bool on) { device_poses_ = on; }
+  bool posesOnDevice() const { return poses_on_device_; }  // the last callback's cloud took its poses from the device
 
 private:
   using clk = std::chrono::steady_clock;
@@ -229,6 +235,7 @@ private:
     const auto t0 = now();
     const std::vector<uint32_t> & unique_ns = scan_.uniqueNs();
     T_Le_Lt_.clear();
+    poses_on_device_ = false;
     if (!initialized_) {  // :399-408 — the first cloud is not deskewed
       T_Le_Lt_.assign(unique_ns.size(), Pose3());
       scan_.deskewPoints(T_Le_Lt_);  // identity per timestamp: points_full_ = points_raw_
@@ -262,6 +269,17 @@ private:
       }
     }
     // :468-499 — constant-acceleration / constant-rate extrapolation to every distinct timestamp, then T_Le_W T_W_Bt T_B_S
+    if (device_poses_) {
+      // the same extrapolation by mh_scan_deskew_imu: the interval states go down, no pose table comes into being on the host
+      // (unique_ns is still read above: :421-433 needs the first timestamp).  An IMU buffer that ends too early is reported
+      // by the next call that waits for the device — Geometric::preprocess, a few lines on
+      const V3D g = state.gravity().unitVector() * imu_manager_.gravityNorm();
+      scan_.deskewPointsFromImu(imuSegments(imu_t, imu_acc, imu_gyro, nav, state.biasAcc(), state.biasGyro()), header_ts_, g, propagated_state_.pose(),
+                                config_.T_B_S);
+      poses_on_device_ = true;
+      debug_.t_deskew = ms(t0);
+      return;
+    }
     T_Le_Lt_ = computeDeskewPoses(imu_t, imu_acc, imu_gyro, nav, state.biasAcc(), state.biasGyro(), state.gravity().unitVector(), imu_manager_.gravityNorm(),
                                   unique_ns, header_ts_, config_.T_B_S);
     if (T_Le_Lt_.size() != unique_ns.size()) throw std::runtime_error("deskewPoints: IMU samples end before the last point of the cloud");
@@ -273,7 +291,10 @@ private:
   void preprocess(const Key key)
   {
     const auto t0 = now();
-    photometric_->preprocess(scan_, T_Le_Lt_, corrected_ts_, key);
+    if (poses_on_device_)
+      photometric_->preprocessResident(scan_, corrected_ts_, key);
+    else
+      photometric_->preprocess(scan_, T_Le_Lt_, corrected_ts_, key);
     geometric_->preprocess(scan_, corrected_ts_);
     debug_.t_preprocess_geo_photo = ms(t0);
   }
@@ -332,6 +353,7 @@ private:
   double header_ts_ = 0, corrected_ts_ = 0;
   size_t new_key_ = 0;
   bool first_ = true, initialized_ = false;
+  bool device_poses_ = false, poses_on_device_ = false;  // setDevicePoses; this cloud's table is the device's
   ManagerDebug debug_;
 };
 

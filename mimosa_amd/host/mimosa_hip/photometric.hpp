@@ -360,6 +360,20 @@ public:
     if (!config.enabled) return;
     ctx_->check(mh_photo_preprocess_scan_begin(photo_, scan.underlying(), Rt12, n), "mh_photo_preprocess_scan_begin");
   }
+  // The same with interpolated_map_T_Le_Lt_ read from the table ScanFrontEnd::deskewPointsFromImu left on the device (no pose
+  // table crosses PCIe); preprocessBeginResident is followed by preprocessCommit as preprocessBegin is.
+  void preprocessResident(ScanFrontEnd & scan, const double ts, const Key key)
+  {
+    if (!config.enabled) return;
+    ctx_->check(mh_photo_preprocess_scan_resident(photo_, scan.underlying()), "mh_photo_preprocess_scan_resident");
+    ts_ = ts;
+    key_ = key;
+  }
+  void preprocessBeginResident(ScanFrontEnd & scan)
+  {
+    if (!config.enabled) return;
+    ctx_->check(mh_photo_preprocess_scan_begin_resident(photo_, scan.underlying()), "mh_photo_preprocess_scan_begin_resident");
+  }
   void preprocessCommit(const double ts, const Key key)
   {
     if (!config.enabled) return;

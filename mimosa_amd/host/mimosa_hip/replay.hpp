@@ -16,6 +16,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <thread>
 
@@ -186,6 +187,39 @@ inline std::vector<RT> propagate(const State & s0, const ImuSamples & imu, const
   return out;
 }
 
+// propagate()'s sample-to-sample half alone, as the IMU intervals mh_scan_deskew_imu takes (same arithmetic, same order).  Like
+// propagate(), the last interval also serves the timestamps behind the last sample (t1 = +inf).
+inline std::vector<mh_imu_segment> imuSegments(const State & s0, const ImuSamples & imu, const A3 & gravity, State & last)
+{
+  const size_t m = imu.ts.size();
+  if (m < 2) throw std::runtime_error("Preintegration not possible as there are less than 2 measurements P1");  // :442-446
+  if (m - 1 > MH_MAX_IMU_SEGMENTS) throw std::runtime_error("imuSegments: more than MH_MAX_IMU_SEGMENTS IMU intervals in one scan");
+  std::vector<mh_imu_segment> seg(m - 1);
+  State st = s0;
+  for (size_t c = 0; c + 1 < m; ++c) {
+    mh_imu_segment & g = seg[c];
+    g.t0 = imu.ts[c];
+    g.t1 = c + 2 < m ? imu.ts[c + 1] : std::numeric_limits<double>::infinity();
+    std::memcpy(g.R, st.T.R.data(), sizeof(g.R));
+    std::memcpy(g.p, st.T.t.data(), sizeof(g.p));
+    std::memcpy(g.v, st.vel.data(), sizeof(g.v));
+    std::memcpy(g.acc, imu.acc[c].data(), sizeof(g.acc));
+    std::memcpy(g.omega, imu.gyro[c].data(), sizeof(g.omega));
+    const double d = imu.ts[c + 1] - imu.ts[c];
+    const A3 Ra = matvec(st.T.R, imu.acc[c]);
+    const A3 aw{Ra[0] + gravity[0], Ra[1] + gravity[1], Ra[2] + gravity[2]};
+    State nx;
+    nx.T.R = matmul(st.T.R, so3Expmap({imu.gyro[c][0] * d, imu.gyro[c][1] * d, imu.gyro[c][2] * d}));
+    for (int i = 0; i < 3; ++i) {
+      nx.T.t[i] = st.T.t[i] + st.vel[i] * d + 0.5 * aw[i] * d * d;
+      nx.vel[i] = st.vel[i] + aw[i] * d;
+    }
+    st = nx;
+  }
+  last = st;
+  return seg;
+}
+
 struct Config
 {
   int window = 5;
@@ -202,6 +236,11 @@ struct Config
   // pose leaves) and all of them are re-linearized per iteration in one PhotometricFactor::linearizeBatchAsync, as the
   // reference's smoother re-linearizes its window of photometric factors.  Off: the photometric factor on the newest pose only.
   bool photo_window = false;
+  // The per-timestamp poses of Manager::deskewPoints (manager.cpp:468-499) are computed on the device (mh_scan_deskew_imu): the
+  // scan loop neither reads the distinct timestamps back nor runs propagate()'s per-timestamp half, and the photometric frame
+  // reads the scan's device table.  The device's sin / cos are not the host's: poses agree to ~1e-15, not bit for bit.
+  // ManagerReplay hands it to lidar::Manager::setDevicePoses (the Manager still reads the timestamps: it needs the first one).
+  bool device_poses = false;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
   lidar::ManagerInputConfig input = lidar::defaultManagerInputConfig();
@@ -224,6 +263,7 @@ struct Result
   std::vector<int> photo_in_window;  // photo_window: photometric factors in the window at each scan's optimisation
   std::vector<std::vector<double>> costs;
   int n_keyframes = 0;
+  int device_pose_scans = 0;  // scans whose deskew poses were computed on the device (Config::device_poses)
   double seconds = 0, stage[5] = {0, 0, 0, 0, 0};  // front_end, imu, factor_create, optimise, update_map
   // finer split of the main thread's time: stage_wait, prepare, deskew, geo_preprocess, icp_create, photo_wait, photo_preprocess,
   // photo_factor, optimise, keyframe_map, photo_final_linearize, photo_update_or_submit
@@ -512,6 +552,10 @@ public:
       scan_.keepRaw(true);
       scan_b_.keepRaw(true);
     }
+    if (cfg_.device_poses) {  // no timestamp comes back to the host
+      scan_.keepUniqueNsOnHost(false);
+      scan_b_.keepUniqueNsOnHost(false);
+    }
   }
   void seedMap(const float * xyz, size_t n) { geo_->seed(xyz, n); }
 
@@ -566,7 +610,12 @@ public:
       }
       const auto a1 = clk::now();
       State pred;
-      const std::vector<RT> T_W_Bt = propagate(prev, sc.imu, sc.header_ts, scan_.uniqueNs(), cfg_.gravity, pred);
+      std::vector<RT> T_W_Bt;
+      std::vector<mh_imu_segment> segments;
+      if (cfg_.device_poses)
+        segments = imuSegments(prev, sc.imu, cfg_.gravity, pred);  // the sequential half; the per-timestamp half runs on the device
+      else
+        T_W_Bt = propagate(prev, sc.imu, sc.header_ts, scan_.uniqueNs(), cfg_.gravity, pred);
       // pose of every column in the scan-end frame, laid out as the C ABI takes poses (R row-major, t): the deskew and the
       // photometric frame read the same 12 doubles a Pose3 would hand back
       std::vector<double> T_Le_Lt12(12 * T_W_Bt.size());
@@ -580,7 +629,12 @@ public:
         }
       }
       const auto a2 = clk::now();
-      scan_.deskewPoints(T_Le_Lt12.data(), T_W_Bt.size());
+      if (cfg_.device_poses) {
+        scan_.deskewPointsFromImu(segments, sc.header_ts, V3D(cfg_.gravity[0], cfg_.gravity[1], cfg_.gravity[2]), toPose3(pred.T), Pose3());
+        ++res.device_pose_scans;
+      } else {
+        scan_.deskewPoints(T_Le_Lt12.data(), T_W_Bt.size());
+      }
       const auto b0 = clk::now();
       res.detail[2] += secs(a2, b0);
       const Key Xk = X(k);
@@ -588,14 +642,18 @@ public:
       // and runs beside the down-sampler and the ICP factor below, while the worker may still be inside updateMap of scan k - 1
       // (it reads the frame and the tracked features of k - 1; building touches neither); it becomes current — and the scan's
       // cloud receives the corrected intensities — at the commit, once that update has returned.
-      if (photo_ && !cfg_.pipeline) {
+      if (photo_ && !cfg_.pipeline && cfg_.device_poses) photo_->preprocessResident(scan_, sc.header_ts, Xk);
+      if (photo_ && !cfg_.pipeline && !cfg_.device_poses) {
         std::vector<Pose3> T_Le_Lt(T_W_Bt.size());
         for (size_t g = 0; g < T_W_Bt.size(); ++g) T_Le_Lt[g] = pose3(&T_Le_Lt12[12 * g], &T_Le_Lt12[12 * g + 9]);
         photo_->preprocess(scan_, T_Le_Lt, sc.header_ts, Xk);
       }
       if (photo_ && cfg_.pipeline) {
         const auto c0 = clk::now();
-        photo_->preprocessBegin(scan_, T_Le_Lt12.data(), T_W_Bt.size());
+        if (cfg_.device_poses)
+          photo_->preprocessBeginResident(scan_);
+        else
+          photo_->preprocessBegin(scan_, T_Le_Lt12.data(), T_W_Bt.size());
         res.detail[6] += secs(c0, clk::now());
       }
       const auto b0g = clk::now();
@@ -884,6 +942,7 @@ public:
     using clk = std::chrono::steady_clock;
     WindowGraph graph(cfg_, imu_, state0);
     lidar::Manager manager(ctx_, mc_, gc_, pc_, graph, imu_, photo_ctx_);
+    manager.setDevicePoses(cfg_.device_poses);
     if (n_seed) manager.geometric().map()->insert(seed_xyz, n_seed);
     Result res;
     const auto t0 = clk::now();
@@ -898,6 +957,7 @@ public:
       T.t = p.t;
       res.poses.push_back(T);
       res.n_keyframes += manager.geometric().debug().map_updated ? 1 : 0;
+      res.device_pose_scans += manager.posesOnDevice() ? 1 : 0;
       if (manager.photometric().debug().n_features_in_factor) res.photo_valid.push_back(manager.photometric().debug().n_status[8]);
       res.stage[0] += (manager.debug().t_deskew + manager.debug().t_preprocess_geo_photo) * 1e-3;
       res.stage[2] += manager.debug().t_factor_prep * 1e-3;

@@ -1,6 +1,7 @@
 // Native sequence replay: drives mimosa_hip::replay::FixedLagReplay (host/mimosa_hip/replay.hpp) on an input file written
 // by mimosa_amd/replay.py:write_native_input and prints one JSON object (estimated poses, per-stage seconds, scans/s).
-//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl]
+//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-poses]
+//     device-poses (last word): replay::Config::device_poses — the per-timestamp deskew poses are computed on the device
 //     repeats > 1: the whole sequence again, timing of the last pass is reported
 //     sharded <world>: the map sharded over <world> ranks INSIDE this process (one host thread and one context each, in-process
 //       transport: what a one-GPU box can run); sharded-rccl: this process is one rank of a torch.distributed.run-style launch
@@ -19,9 +20,11 @@ using binio::read_vec;
 int main(int argc, char ** argv)
 {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential]\n");
+    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-poses]\n");
     return 2;
   }
+  const bool device_poses = argc > 2 && std::string(argv[argc - 1]) == "device-poses";
+  if (device_poses) --argc;
   const int repeats = argc > 2 ? std::atoi(argv[2]) : 1;
   const bool through_manager = argc > 3 && std::string(argv[3]) == "manager";  // the same sequence through lidar::Manager::callback
   const bool sequential = argc > 3 && std::string(argv[3]) == "sequential";   // FixedLagReplay without the cross-scan overlap
@@ -52,6 +55,7 @@ int main(int argc, char ** argv)
     std::memcpy(&cfg.input, inpb.data(), sizeof(cfg.input));
     if (cfg.photometric) cfg.photo = binio::read_photo_config(f);
     cfg.pipeline = !sequential;
+    cfg.device_poses = device_poses;
     const auto bias = read_vec<double>(f);
     for (size_t i = 0; i + 2 < bias.size(); i += 3) cfg.bias_directions.push_back(V3D(bias[i], bias[i + 1], bias[i + 2]));
     const auto seed = read_vec<float>(f);
@@ -124,8 +128,8 @@ int main(int argc, char ** argv)
         r = run.run(scans, st0);
       }
     }
-    std::printf("{\"scans\": %zu, \"seconds\": %.9f, \"scans_per_s\": %.3f, \"n_keyframes\": %d, \"n_ranks\": %d, \"max_rank_deviation_m\": %.3e,\n", scans.size(),
-                r.seconds, static_cast<double>(scans.size()) / r.seconds, r.n_keyframes, n_ranks, max_dev);
+    std::printf("{\"scans\": %zu, \"seconds\": %.9f, \"scans_per_s\": %.3f, \"n_keyframes\": %d, \"n_ranks\": %d, \"max_rank_deviation_m\": %.3e, \"device_pose_scans\": %d,\n", scans.size(),
+                r.seconds, static_cast<double>(scans.size()) / r.seconds, r.n_keyframes, n_ranks, max_dev, r.device_pose_scans);
     std::printf("\"stage_s\": {\"front_end\": %.9f, \"imu\": %.9f, \"factor_create\": %.9f, \"optimise\": %.9f, \"update_map\": %.9f},\n",
                 r.stage[0], r.stage[1], r.stage[2], r.stage[3], r.stage[4]);
     {

@@ -62,6 +62,10 @@ class ReplayConfig:
     # every scan's photometric factor stays in the window on its own pose (released with the pose) and all of them are
     # re-linearized per iteration, as the reference's smoother does; off: the photometric factor on the newest pose only
     photo_window: bool = False
+    # the per-timestamp deskew poses (src/lidar/manager.cpp:468-499) are computed on the device (mh_scan_deskew_imu): no
+    # timestamp is read back, no pose table uploaded, the photometric frame reads the scan's device table.  HIP backend and the
+    # native replay only (the CPU backend has no device to keep a table on)
+    device_poses: bool = False
     reg: dict = field(default_factory=synth.enwide_config)
     photo: dict = None
 
@@ -181,6 +185,22 @@ def propagate(R, p, vel, imu, header_ts, unique_ns):
     return out, states[-1]
 
 
+def imu_segments(R, p, vel, imu):
+    """propagate()'s sample-to-sample half alone, as the IMU intervals mh_scan_deskew_imu takes; like propagate(), the last
+    interval also serves timestamps behind the last sample.  Returns (segments, state at the last sample)."""
+    from . import capi
+    ts, gyro, acc = imu
+    states = [(R, p, vel)]
+    for c in range(len(ts) - 1):
+        Rc, pc, vc = states[-1]
+        d = ts[c + 1] - ts[c]
+        aw = Rc @ acc[c] + GRAVITY
+        states.append((Rc @ synth.so3_exp(gyro[c] * d), pc + vc * d + 0.5 * aw * d * d, vc + aw * d))
+    seg = capi.imu_segments(ts, acc, gyro, [s_[0] for s_ in states], [s_[1] for s_ in states], [s_[2] for s_ in states])
+    seg["t1"][-1] = np.inf
+    return seg, states[-1]
+
+
 class HipBackend:
     """The C ABI: device-resident front end, voxel map, ICP factors (batched re-linearization), photometric path."""
 
@@ -211,6 +231,18 @@ class HipBackend:
         self.scan.deskew(T_Le_Lt.astype(np.float32))
         if self.photo is not None:
             self.photo.preprocess_scan(self.scan, T_Le_Lt)
+        info = self.scan.preprocess_geometric(self.I3, self.z3, self.regd["source_voxel_grid_filter_leaf_size"], 20,
+                                              self.regd["source_voxel_grid_min_dist_in_voxel"])
+        return info["n_downsampled"]
+
+    def prepare_resident(self, raw):
+        self.scan.prepare_input(raw, self.icfg)     # the distinct timestamps stay on the device
+
+    def deskew_imu_and_preprocess(self, segments, header_ts, R_end, p_end):
+        """deskew_and_preprocess with the poses computed on the device from the IMU intervals (body = sensor frame here)."""
+        self.scan.deskew_imu(segments, header_ts, GRAVITY, (R_end.T, -R_end.T @ p_end), (np.eye(3), np.zeros(3)))
+        if self.photo is not None:
+            self.photo.preprocess_scan_resident(self.scan)
         info = self.scan.preprocess_geometric(self.I3, self.z3, self.regd["source_voxel_grid_filter_leaf_size"], 20,
                                               self.regd["source_voxel_grid_min_dist_in_voxel"])
         return info["n_downsampled"]
@@ -330,6 +362,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
         mode = ["sharded", str(sharded_world)]
     if sharded_rccl:
         mode = ["sharded-rccl"]
+    if cfg.device_poses:
+        mode = mode + ["device-poses"]
     out = subprocess.run([exe, path, str(repeats)] + mode, capture_output=True, text=True, timeout=timeout, env=env)
     os.remove(path)
     if out.returncode != 0:
@@ -344,6 +378,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
 def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     """Replay: returns dict(poses_est, errors, keyframes, per-stage seconds, ...)."""
     scans = scans if scans is not None else make_scans(cfg)
+    if cfg.device_poses and not hasattr(backend, "deskew_imu_and_preprocess"):
+        raise ValueError("device_poses needs a backend that keeps the pose table on the device (HipBackend)")
     backend.seed_map(synth.make_room(synth.BASE_SEED, 0, 0, room=np.asarray(cfg.room)))
     stage = {"front_end": 0.0, "imu": 0.0, "factor_create": 0.0, "optimise": 0.0, "update_map": 0.0}
     v_body = np.asarray(cfg.v, float)
@@ -354,19 +390,28 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     t0 = time.perf_counter()
     for k, sc in enumerate(scans):
         a0 = time.perf_counter()
-        uns = backend.prepare(sc["raw"])
+        if cfg.device_poses:
+            backend.prepare_resident(sc["raw"])
+            uns = np.zeros(0, np.uint32)
+        else:
+            uns = backend.prepare(sc["raw"])
         a1 = time.perf_counter()
         # IMU propagation from the previous scan's estimate (first scan: ground truth + the prior error)
         if R_prev is None:
             R_start, p_start, vel_start = first_state(cfg, sc, rng_seed)   # state at the first IMU sample of this sweep
         else:
             R_start, p_start, vel_start = R_prev, t_prev, vel_prev
-        T_W_Bt, (R_pred, p_pred, vel_pred) = propagate(R_start, p_start, vel_start, sc["imu"], sc["header_ts"], uns)
-        T_Le_Lt = np.empty_like(T_W_Bt)
-        T_Le_Lt[:, :9] = (R_pred.T @ T_W_Bt[:, :9].reshape(-1, 3, 3)).reshape(-1, 9)
-        T_Le_Lt[:, 9:] = (T_W_Bt[:, 9:] - p_pred) @ R_pred
-        a2 = time.perf_counter()
-        backend.deskew_and_preprocess(T_Le_Lt)
+        if cfg.device_poses:
+            segments, (R_pred, p_pred, vel_pred) = imu_segments(R_start, p_start, vel_start, sc["imu"])
+            a2 = time.perf_counter()
+            backend.deskew_imu_and_preprocess(segments, sc["header_ts"], R_pred, p_pred)
+        else:
+            T_W_Bt, (R_pred, p_pred, vel_pred) = propagate(R_start, p_start, vel_start, sc["imu"], sc["header_ts"], uns)
+            T_Le_Lt = np.empty_like(T_W_Bt)
+            T_Le_Lt[:, :9] = (R_pred.T @ T_W_Bt[:, :9].reshape(-1, 3, 3)).reshape(-1, 9)
+            T_Le_Lt[:, 9:] = (T_W_Bt[:, 9:] - p_pred) @ R_pred
+            a2 = time.perf_counter()
+            backend.deskew_and_preprocess(T_Le_Lt)
         a3 = time.perf_counter()
         f = backend.make_factor()
         pf = backend.make_photo_factor() if cfg.photometric else None
