@@ -274,6 +274,51 @@ int mh_icp_reset(mh_icp * icp);
 int mh_icp_set_components(mh_icp * icp, int enabled);
 size_t mh_icp_size(const mh_icp * icp);
 
+/* ---- scan-to-map alignment: a Gauss-Newton loop on the device ----------------------------------
+ * One scan, one map, a rough pose in; the aligned pose out.  What a caller otherwise writes around mh_icp_linearize — one
+ * blocking call, a 6 x 6 solve on the host, a retraction, again — runs as ONE chain of launches on the context's stream: K3
+ * (component pass off), a one-wave step kernel that does the host epilogue's part of the work, solves
+ * (H_ss + diag(prior) + damping I) xi = -b_s, retracts (R <- R Exp(xi_r), t <- t + R xi_t) and writes the pose into the
+ * argument block of the next K3, and so on; the host waits once (or once per `check_every` iterations).  The step is taken
+ * with exactly the H_ss, b_s that mh_icp_linearize returns at that pose, the reference's degeneracy quirk included: an
+ * iteration with a degenerate direction (project_on_degneneracy) has H = b = 0 and moves by prior / damping only, i.e. not
+ * at all.  A system without a positive pivot (a degenerate iteration without prior and damping) takes no step and ends the
+ * call: MH_OK, converged = 0, the pose of that iteration unchanged, bit 4 in the trace row.
+ * Unary, unsharded, non-empty factors without a call in flight.  The per-point association state evolves as under repeated
+ * mh_icp_linearize calls and is left as the last EVALUATED pose left it (iterations queued behind the stop evaluate nothing);
+ * the linearize count advances by `iters`. */
+typedef struct mh_icp_align_config {
+  int32_t max_iters;           /* 1 .. 64 (the factor's ring holds 64 calls) */
+  double eps_rot, eps_trans;   /* rad, m: stop when both step norms fall below (0 = never) */
+  double damping;              /* >= 0, added to the diagonal */
+  double prior_sigma_rot, prior_sigma_trans; /* 0 = no prior; else 1 / sigma^2 on the diagonal, pulling towards the step's own pose */
+  int32_t check_every;         /* launches queued per host look at the stop flag; 0 = all max_iters at once.  The result does
+                                  not depend on it (mh_icp_align_async always queues everything) */
+} mh_icp_align_config;
+
+typedef struct mh_icp_align_trace {
+  double f;                    /* cost at the pose the iteration evaluated */
+  double step_rot, step_trans; /* |xi_r|, |xi_t| of its step */
+  double R[9], t[3];           /* the pose after the step */
+  int64_t n_knn;               /* queries that ran k-NN in this iteration (the rest hit the association cache) */
+  int32_t degenerate;          /* 1: a rotation direction below its threshold, 2: a translation direction, 4: singular system */
+  int32_t reserved;
+} mh_icp_align_trace;
+
+typedef struct mh_icp_align_result {
+  double R[9], t[3];
+  int32_t iters, converged;
+  mh_icp_align_trace trace[64]; /* one row per executed iteration */
+  mh_icp_result first, last;    /* what mh_icp_linearize (components off) returns at the initial and at the last evaluated pose */
+} mh_icp_align_result;
+
+int mh_icp_align(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3],
+                 const mh_icp_align_config * cfg, mh_icp_align_result * out);
+/* The same without waiting: *out (which must stay valid) is filled when mh_icp_wait returns.  No other call on the
+ * factor until then. */
+int mh_icp_align_async(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3],
+                       const mh_icp_align_config * cfg, mh_icp_align_result * out);
+
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals
  * unique_ns[g] gets p <- R_g p + t_g in float (no FMA, Eigen's evaluation order).  Rt12 = n_groups x

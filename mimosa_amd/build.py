@@ -32,8 +32,9 @@ SOURCES = [
     ("photo_api.hip", []),
     ("radar_kernels.hip", ["-ffp-contract=off"]),
     ("radar_api.hip", []),
+    ("align_kernels.hip", ["-ffp-contract=off"]),  # the host build of align_device.hpp (tests/cpp/align_step.cpp) gives the same digits
 ]
-HEADERS = ["icp_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
+HEADERS = ["icp_device.hpp", "align_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
 
 
 def _hipcc() -> str:
@@ -170,6 +171,26 @@ def build_replay_native(force: bool = False) -> str:
         if force or _stale(exe, deps):
             _run_to(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.dirname(HERE), "-I", host, "-I", os.path.join(host, "gtsam_sig"), src, "-o", exe,
                      "-L", LIBDIR, "-lmimosa_hip", "-lpthread", "-Wl,-rpath,$ORIGIN"], exe)
+    return exe
+
+
+# Host tests of headers the device code shares (plain g++, link nothing): name -> (source under tests/cpp, headers it reads)
+HOST_TESTS = {
+    "align_step": ("align_step.cpp", ["align_device.hpp", "math3.hpp"]),
+}
+
+
+def build_host_test(name: str, force: bool = False) -> str:
+    """tests/cpp/<name>.cpp over a csrc header compiled for the CPU, without floating-point contraction like the device build."""
+    src_name, hdrs = HOST_TESTS[name]
+    src = os.path.join(os.path.dirname(HERE), "tests", "cpp", src_name)
+    exe = os.path.join(LIBDIR, name)
+    deps = [src] + [os.path.join(CSRC, h) for h in hdrs]
+    if not (force or _stale(exe, deps)):
+        return exe
+    with _BuildLock():
+        if force or _stale(exe, deps):
+            _run_to(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas", "-I", CSRC, src, "-o", exe], exe)
     return exe
 
 

@@ -24,6 +24,7 @@ EXPORTS = [
     "mh_map_get_cloud", "mh_map_knn",
     "mh_icp_create", "mh_icp_clone", "mh_icp_destroy", "mh_icp_linearize", "mh_icp_linearize_async",
     "mh_icp_wait", "mh_icp_linearize_batch", "mh_icp_get_state", "mh_icp_reset", "mh_icp_set_components", "mh_icp_size",
+    "mh_icp_align", "mh_icp_align_async",
     "mh_deskew", "mh_transform_f32",
     "mh_scan_create", "mh_scan_destroy", "mh_scan_prepare_input", "mh_scan_prepare_input_device", "mh_scan_prefetch", "mh_scan_prepare_input_prefetched", "mh_scan_prepare_input_layout", "mh_scan_get_unique_ns", "mh_scan_deskew",
     "mh_scan_deskew_imu", "mh_scan_get_deskew_poses", "mh_photo_preprocess_scan_resident", "mh_photo_preprocess_scan_begin_resident",
@@ -105,6 +106,39 @@ class IcpResult(C.Structure):
         for k in ("eigvec_trans", "eigvec_rot", "degen_eigvec_rot", "degen_eigvec_trans"):
             d[k] = d[k].reshape(3, 3)
         return d
+
+
+class AlignConfig(C.Structure):
+    """mh_icp_align_config"""
+    _fields_ = [("max_iters", C.c_int32), ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("damping", C.c_double),
+                ("prior_sigma_rot", C.c_double), ("prior_sigma_trans", C.c_double), ("check_every", C.c_int32)]
+
+
+class AlignTrace(C.Structure):
+    """mh_icp_align_trace"""
+    _fields_ = [("f", C.c_double), ("step_rot", C.c_double), ("step_trans", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("n_knn", C.c_int64), ("degenerate", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AlignResult(C.Structure):
+    """mh_icp_align_result"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("iters", C.c_int32), ("converged", C.c_int32),
+                ("trace", AlignTrace * 64), ("first", IcpResult), ("last", IcpResult)]
+
+    def as_dict(self):
+        n = int(self.iters)
+        tr = [self.trace[i] for i in range(n)]
+        return {
+            "R": np.array(self.R).reshape(3, 3), "t": np.array(self.t), "iters": n, "converged": int(self.converged),
+            "trace": [{"f": r.f, "step_rot": r.step_rot, "step_trans": r.step_trans, "R": np.array(r.R).reshape(3, 3), "t": np.array(r.t),
+                       "n_knn": int(r.n_knn), "degenerate": int(r.degenerate)} for r in tr],
+            "first": self.first.as_dict(), "last": self.last.as_dict(),
+        }
+
+
+def make_align_config(max_iters=10, eps_rot=1e-6, eps_trans=1e-6, damping=0.0, prior_sigma_rot=0.0, prior_sigma_trans=0.0,
+                      check_every=0) -> AlignConfig:
+    return AlignConfig(max_iters, eps_rot, eps_trans, damping, prior_sigma_rot, prior_sigma_trans, check_every)
 
 
 class ShardConfig(C.Structure):
@@ -433,6 +467,8 @@ def load(build_if_missing: bool = True):
     L.mh_icp_reset.argtypes = [vp]
     L.mh_icp_set_components.argtypes = [vp, C.c_int]
     L.mh_icp_size.argtypes = [vp]
+    L.mh_icp_align.argtypes = [vp, vp, vp, vp, C.POINTER(AlignConfig), C.POINTER(AlignResult)]
+    L.mh_icp_align_async.argtypes = [vp, vp, vp, vp, C.POINTER(AlignConfig), C.POINTER(AlignResult)]
     L.mh_icp_size.restype = sz
     L.mh_deskew.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
     L.mh_transform_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -843,6 +879,21 @@ class ICPFactor:
 
     def reset(self):
         self.ctx.check(self.L.mh_icp_reset(self.h))
+
+    def align(self, R0, t0, cfg: AlignConfig, g_unit=(0.0, 0.0, -1.0)) -> dict:
+        """mh_icp_align: the Gauss-Newton loop from (R0, t0) as one chain of launches; pose, trace, first / last results."""
+        out = AlignResult()
+        R, t, g = _f64(R0), _f64(t0), _f64(g_unit)
+        self.ctx.check(self.L.mh_icp_align(self.h, _p(R), _p(t), _p(g), C.byref(cfg), C.byref(out)))
+        return out.as_dict()
+
+    def align_async(self, R0, t0, cfg: AlignConfig, g_unit=(0.0, 0.0, -1.0)) -> AlignResult:
+        """mh_icp_align_async: collected by wait(); the returned struct is filled then (as_dict())."""
+        out = AlignResult()
+        R, t, g = _f64(R0), _f64(t0), _f64(g_unit)
+        self._keep.append((out, R, t, g, cfg))
+        self.ctx.check(self.L.mh_icp_align_async(self.h, _p(R), _p(t), _p(g), C.byref(cfg), C.byref(out)))
+        return out
 
     def set_components(self, enabled: bool):
         """component localizabilities + status histogram (K4) on / off for the following linearize calls"""

@@ -1659,6 +1659,19 @@ __global__ __launch_bounds__(TPB) void icp_linearize_batch_kernel(const IcpArgs 
   icp_linearize_body<K, BINARY, NOFF, TPB, false>(a, b - s0, s1 - s0);
 }
 
+// The staged form in the several-lanes-per-point classes of a plain unary k = 5 factor (QL = 2 / 4): what a chain of launches
+// whose argument blocks are rewritten on the device between two of them (align_kernels.hip) runs for a small cloud, so that its
+// sums are those of the factor's own single-call class.  Same body, same rows, same fold.
+template <int NOFF, int QL>
+__global__ __launch_bounds__(256) void icp_linearize_batch_ql_kernel(const IcpArgs * args, const int * start, int n_factors)
+{
+  const int b = static_cast<int>(blockIdx.x);
+  const int f = batch_factor_of(start, n_factors, b);
+  const int s0 = __builtin_amdgcn_readfirstlane(start[f]), s1 = __builtin_amdgcn_readfirstlane(start[f + 1]);
+  const IcpArgs a = load_uniform(args + f);
+  icp_linearize_body<5, false, NOFF, 256, false, QL>(a, b - s0, s1 - s0);
+}
+
 // The same with the argument blocks inside the kernel-argument segment.  They are read through the segment pointer:
 // indexing the by-value parameter itself with a runtime index makes the compiler copy the whole struct to scratch.
 template <int K, bool BINARY, int NOFF, int TPB, bool SHARD, int QL = 1>
@@ -2140,7 +2153,8 @@ static void launch_linearize_batch_nt(const IcpArgs * d_args, const int * d_star
   }
 }
 
-// (windows of more than kBatchInline factors: the one-lane-per-point classes only — batch_class never hands them another)
+// (windows of more than kBatchInline factors: the one-lane-per-point classes only — batch_class never hands them another; the
+// two- and four-lane classes are there for the single-factor chains of mh_icp_align)
 hipError_t launch_linearize_batch(const IcpArgs * d_args, const int * d_start, int n_factors, int total_grid, int ppw, int k,
                                   int n_off, bool binary, hipStream_t stream)
 {
@@ -2151,6 +2165,23 @@ hipError_t launch_linearize_batch(const IcpArgs * d_args, const int * d_start, i
     else                                                                                                    \
       launch_linearize_batch_nt<NOFF, kThreads>(d_args, d_start, n_factors, total_grid, k, binary, stream); \
   } while (0)
+#define MH_BATCH_QL(NOFF)                                                                                                                            \
+  do {                                                                                                                                               \
+    if (ppw == 128)                                                                                                                                  \
+      hipLaunchKernelGGL((icp_linearize_batch_ql_kernel<NOFF, 2>), dim3(total_grid), dim3(256), 0, stream, d_args, d_start, n_factors);             \
+    else                                                                                                                                             \
+      hipLaunchKernelGGL((icp_linearize_batch_ql_kernel<NOFF, 4>), dim3(total_grid), dim3(256), 0, stream, d_args, d_start, n_factors);             \
+  } while (0)
+  if ((ppw == 128 || ppw == 64) && k == 5 && !binary) {  // (the classes linearize_class hands a plain unary k = 5 factor only)
+    if (n_off <= 7)
+      MH_BATCH_QL(7);
+    else if (n_off == 19)
+      MH_BATCH_QL(19);
+    else
+      MH_BATCH_QL(27);
+    return hipGetLastError();
+  }
+#undef MH_BATCH_QL
   if (ppw != 256 && ppw != kThreads) return hipErrorInvalidValue;
   if (n_off <= 7)
     MH_BATCH_TPB(7);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/mimosa_hip.h"
+#include "align_device.hpp"
 #include "icp_device.hpp"
 #include "math3.hpp"
 #include "mh_internal.hpp"
@@ -324,6 +325,16 @@ int mh_timer_end(mh_ctx * ctx, float * ms)
 
 }  // extern "C"
 
+// mh_icp_align's block of device memory (mh_icp::d_align) and the pinned staging of its first part (h_align):
+// [grid prefix, 64 B | AlignState, 192 B | 64 argument blocks | 256 B that load_uniform may read past the last block |
+//  64 landing slots of 32 flagged words for K3's sums and counters]
+constexpr size_t kAlignBlocksAt = 256;
+constexpr size_t kAlignStageBytes = kAlignBlocksAt + sizeof(mh::IcpArgs) * kMaxPending;
+constexpr size_t kAlignLlAt = (kAlignStageBytes + 256 + 255) & ~size_t(255);
+constexpr size_t kAlignLlWords = 32;
+constexpr size_t kAlignBytes = kAlignLlAt + kAlignLlWords * sizeof(uint4) * kMaxPending;
+static_assert(sizeof(mh::AlignState) <= 192 && mh::kRowWords <= mh::kLlEig, "mh_icp_align layout");
+
 extern "C" {
 // ---- factor ------------------------------------------------------------------------------------
 static int icp_alloc(mh_icp * icp)
@@ -543,6 +554,8 @@ void mh_icp_destroy(mh_icp * icp)
   if (icp->h_counts) (void)hipHostFree(icp->h_counts);
   if (icp->h_results) AllocCache::free_pinned(icp->h_results, sizeof(mh::DeviceResult) * kMaxPending);
   if (icp->h_ll) AllocCache::free_pinned(icp->h_ll, icp->ll_words * sizeof(uint4) * kMaxPending);
+  icp->d_align.release(true);
+  if (icp->h_align) AllocCache::free_pinned(icp->h_align, kAlignStageBytes);
   if (icp->events_ready)
     for (auto & ev : icp->events)
       for (auto & e : ev) (void)hipEventDestroy(e);
@@ -574,6 +587,7 @@ int mh_icp_timeline(mh_icp * icp, unsigned long long * out, size_t capacity_word
 static int mh_icp_reset_impl(mh_icp * icp)
 {
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_reset: icp is NULL");
+  if (icp->align.active) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: an alignment is in flight");  // (its books would overwrite the reset)
   icp->cold = true;  // the next linearize treats the cached state as all-zero (no memset needed)
   return MH_OK;
 }
@@ -892,10 +906,13 @@ static bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, l
   return true;
 }
 
+static int align_wait(mh_icp * icp);  // (below: mh_icp_align)
+
 static int mh_icp_wait_impl(mh_icp * icp)
 {
   const double tw_enter = g_wt.on ? WaitTrace::now() : 0.0;
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_wait: icp is NULL");
+  if (icp->align.active) return align_wait(icp);
   mh_ctx * ctx = icp->ctx;
   MH_HIP(ctx, mh_enter(ctx));
   // Every value a call produces arrives in mapped pinned memory tagged with the call's sequence number: the host polls the
@@ -1136,6 +1153,268 @@ int mh_icp_linearize_batch(mh_icp * const * icps, size_t n_factors, const double
                            const double * R_tgt, const double * t_tgt, const double * g_unit, mh_icp_result * out)
 {
   return guarded((icps && n_factors && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_linearize_batch", [&]() -> int { return mh_icp_linearize_batch_impl(icps, n_factors, R_src, t_src, R_tgt, t_tgt, g_unit, out); });
+}
+
+// ---- scan-to-map alignment: K3, step, K3, step ... on the context's stream, one wait ---------------------------------------
+// The argument blocks of every iteration sit in device memory (d_align), filled here except R, t of the iterations after the
+// first, which the step kernel in front of each writes (align_kernels.hip).  K3 runs in the staged batch form with one factor
+// and the class a call of its own would get, tail = 1, its flagged words landing in a device slot; the step forwards them and
+// its own row to the iteration's slot of the factor's pinned ring.
+static bool align_read_row(const mh_icp * icp, int i, long spin_ns, double * row)
+{
+  const uint4 * base = icp->h_ll + static_cast<size_t>(i) * icp->ll_words + mh::kLlSums;
+  timespec t0;
+  clock_gettime(CLOCK_MONOTONIC, &t0);
+  unsigned spins = 0;
+  for (int w = mh::kRowWords - 1; w >= 0; --w) {
+    while (!ll_read(base + w, icp->align.seq[i], row[w])) {
+      if (spin_ns <= 0) return false;
+      __builtin_ia32_pause();
+      if ((++spins & 1023u) == 0u) {
+        timespec t1;
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        if ((t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec) > spin_ns) return false;
+      }
+    }
+  }
+  return true;
+}
+
+// wait for the row of iteration i (the last one queued so far): the values themselves, the stream behind them
+static int align_wait_row(mh_icp * icp, int i, double * row)
+{
+  mh_ctx * ctx = icp->ctx;
+  if (align_read_row(icp, i, 50000000L, row)) return MH_OK;  // 50 ms: 64 iterations of a large cloud are a few
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (align_read_row(icp, i, 2000000L, row)) return MH_OK;
+  return fail(ctx, MH_ERR_HIP, "mh_icp_align: the stream drained without the chain's results");
+}
+
+static void align_abandon(mh_icp * icp)
+{
+  (void)hipStreamSynchronize(icp->ctx->stream);
+  icp->align.active = false;
+  icp->n_pending = 0;
+}
+
+static int align_begin(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
+                       mh_icp_align_result * out)
+{
+  if (!icp || !R0 || !t0 || !g_unit || !cfg || !out) return fail(icp ? icp->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_align: NULL argument");
+  mh_ctx * ctx = icp->ctx;
+  if (icp->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align: unary factors only");
+  if (icp->n_pending || icp->align.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: the factor has calls in flight");
+  if (cfg->max_iters < 1 || cfg->max_iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: max_iters must be in 1..64");
+  if (!(cfg->eps_rot >= 0.0) || !(cfg->eps_trans >= 0.0) || !(cfg->damping >= 0.0) || !(cfg->prior_sigma_rot >= 0.0) ||
+      !(cfg->prior_sigma_trans >= 0.0) || cfg->check_every < 0)
+    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: eps, damping, prior sigmas and check_every must be >= 0");
+  if (icp->no_order || icp->cap_n > icp->n) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align: not for the factors of the map-sharded path");
+  if (icp->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: the factor has no points");
+  MH_HIP(ctx, mh_enter(ctx));
+  MH_HIP(ctx, icp->d_align.reserve(kAlignBytes, ctx->stream, false));
+  if (!icp->h_align) MH_HIP(ctx, AllocCache::alloc_pinned(&icp->h_align, kAlignStageBytes));
+
+  // the argument block of a components-off linearize at (R0, t0); what linearize_prepare changes on the handle is put back —
+  // the chain keeps its own books
+  mh::IcpArgs a;
+  {
+    mh::LocArgs l;
+    bool timed = false;
+    mh_icp_result scratch;
+    LinearizeTxn txn(icp);
+    const int rc = linearize_prepare(icp, R0, t0, nullptr, nullptr, g_unit, &scratch, false, false, a, l, timed);
+    if (rc != MH_OK) return rc;
+  }
+  a.rec = nullptr;
+  a.rec_n = 0;
+  a.tail = 1;
+  a.host_result = nullptr;
+
+  mh_icp::AlignCall & c = icp->align;
+  c.cfg = *cfg;
+  c.out = out;
+  std::memcpy(c.R0, R0, sizeof(c.R0));
+  for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
+  c.queued = 0;
+  c.count0 = icp->linearize_count;
+  c.cold0 = icp->cold;
+  mh::AlignParams & p = c.p;
+  for (int i = 0; i < 3; ++i) p.gz[i] = c.gz[i];
+  p.eps_rot = cfg->eps_rot;
+  p.eps_trans = cfg->eps_trans;
+  p.damping = cfg->damping;
+  p.prior_rot = cfg->prior_sigma_rot > 0.0 ? 1.0 / (cfg->prior_sigma_rot * cfg->prior_sigma_rot) : 0.0;
+  p.prior_trans = cfg->prior_sigma_trans > 0.0 ? 1.0 / (cfg->prior_sigma_trans * cfg->prior_sigma_trans) : 0.0;
+  p.thresh_rot = icp->cfg.degen_thresh_rot;
+  p.thresh_trans = icp->cfg.degen_thresh_trans;
+  p.reg_4_dof = icp->cfg.reg_4_dof;
+  p.project_on_degeneracy = icp->cfg.project_on_degneneracy;
+
+  char * h = static_cast<char *>(icp->h_align);
+  char * d = static_cast<char *>(icp->d_align.p);
+  const int ppw = mh::linearize_class(a.n, a.k, false);
+  int * start = reinterpret_cast<int *>(h);
+  start[0] = 0;
+  start[1] = mh::class_grid(a.n, ppw);
+  mh::AlignState st;
+  std::memset(&st, 0, sizeof(st));
+  std::memcpy(st.R, a.R, sizeof(st.R));
+  std::memcpy(st.t, a.t, sizeof(st.t));
+  std::memcpy(h + 64, &st, sizeof(st));
+  auto * blocks = reinterpret_cast<mh::IcpArgs *>(h + kAlignBlocksAt);
+  for (int i = 0; i < cfg->max_iters; ++i) {
+    mh::IcpArgs b = a;
+    b.cold = (i == 0 && c.cold0) ? 1 : 0;
+    b.seq = c.seq[i] = next_call_seq();
+    b.ll = reinterpret_cast<uint4 *>(d + kAlignLlAt) + static_cast<size_t>(i) * kAlignLlWords;
+    blocks[i] = b;
+  }
+  MH_HIP(ctx, hipMemcpyAsync(d, h, kAlignBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(cfg->max_iters), hipMemcpyHostToDevice, ctx->stream));
+  c.active = true;
+  icp->n_pending = kMaxPending;  // the chain holds the whole ring
+  return MH_OK;
+}
+
+// iterations [queued, upto) onto the stream
+static int align_enqueue(mh_icp * icp, int upto)
+{
+  mh_ctx * ctx = icp->ctx;
+  mh_icp::AlignCall & c = icp->align;
+  char * d = static_cast<char *>(icp->d_align.p);
+  auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + kAlignBlocksAt);
+  const int n = static_cast<int>(icp->n), k = static_cast<int>(icp->cfg.num_corres_points);
+  const int ppw = mh::linearize_class(n, k, false), grid = mh::class_grid(n, ppw);
+  for (int i = c.queued; i < upto; ++i) {
+    hipError_t e = mh::launch_linearize_batch(blocks + i, reinterpret_cast<const int *>(d), 1, grid, ppw, k == 5 ? 5 : 8, icp->map->n_off, false, ctx->stream);
+    if (e == hipSuccess) {
+      mh::AlignStepArgs s;
+      s.ll_dev = reinterpret_cast<const uint4 *>(d + kAlignLlAt) + static_cast<size_t>(i) * kAlignLlWords;
+      s.ll_host = icp->d_h_ll + static_cast<size_t>(i) * icp->ll_words;
+      s.next = i + 1 < c.cfg.max_iters ? blocks + i + 1 : nullptr;
+      s.state = reinterpret_cast<mh::AlignState *>(d + 64);
+      s.p = c.p;
+      s.seq = c.seq[i];
+      e = mh::launch_align_step(s, ctx->stream);
+    }
+    if (e != hipSuccess) {
+      align_abandon(icp);
+      return hip_fail(ctx, e, "mh_icp_align: launch");
+    }
+    c.queued = i + 1;
+  }
+  return MH_OK;
+}
+
+// every queued iteration has run (the caller waited for the last row): the result, and the handle's books
+static int align_finish(mh_icp * icp)
+{
+  mh_ctx * ctx = icp->ctx;
+  mh_icp::AlignCall & c = icp->align;
+  mh_icp_align_result * out = c.out;
+  std::memset(static_cast<void *>(out), 0, sizeof(*out));
+  int iters = 0, converged = 0;
+  for (int i = 0; i < c.queued; ++i) {
+    double row[mh::kRowWords];
+    const int rc = align_wait_row(icp, i, row);
+    if (rc != MH_OK) {
+      align_abandon(icp);
+      return rc;
+    }
+    const int flags = static_cast<int>(row[mh::kRowFlags]);
+    if (flags & 4) break;  // queued behind the stop: nothing was evaluated, here or later
+    mh_icp_align_trace & tr = out->trace[iters++];
+    tr.f = row[mh::kRowF];
+    tr.step_rot = row[mh::kRowStepRot];
+    tr.step_trans = row[mh::kRowStepTrans];
+    tr.n_knn = static_cast<int64_t>(row[mh::kRowKnn]);
+    tr.degenerate = static_cast<int32_t>(row[mh::kRowBits]);
+    std::memcpy(tr.R, row + mh::kRowR, sizeof(tr.R));
+    std::memcpy(tr.t, row + mh::kRowT, sizeof(tr.t));
+    converged = (flags & 2) ? 1 : 0;
+  }
+  if (iters == 0) {  // (the first queued iteration is always evaluated: its row never carries the flag)
+    align_abandon(icp);
+    return fail(ctx, MH_ERR_HIP, "mh_icp_align: no iteration was evaluated");
+  }
+  int rc_all = MH_OK;
+  if (out->trace[iters - 1].degenerate & 8) rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_align: a step did not find its K3's sums");
+  out->iters = iters;
+  out->converged = converged;
+  std::memcpy(out->R, out->trace[iters - 1].R, sizeof(out->R));
+  std::memcpy(out->t, out->trace[iters - 1].t, sizeof(out->t));
+  // first / last: the host epilogue of linearize() on the sums K3 folded at the initial and at the last evaluated pose
+  for (int which = 0; which < 2 && rc_all == MH_OK; ++which) {
+    const int i = which == 0 ? 0 : iters - 1;
+    PendingCall pc{};
+    pc.out = nullptr;
+    std::memcpy(pc.R, i == 0 ? c.R0 : out->trace[i - 1].R, sizeof(pc.R));
+    std::memcpy(pc.gz, c.gz, sizeof(pc.gz));
+    pc.linearize_count = c.count0 + i + 1;
+    pc.seq = c.seq[i];
+    pc.components = false;
+    pc.ev[0] = pc.ev[1] = pc.ev[2] = nullptr;
+    mh::DeviceResult dres;
+    if (!collect_call(icp, i, pc, 2000000L, dres)) {
+      rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_align: an iteration's sums did not arrive");
+      break;
+    }
+    mh_icp_result * r = which == 0 ? &out->first : &out->last;
+    finish_result(icp, dres, pc, r);
+    r->gpu_ms_linearize = r->gpu_ms_localizability = -1.0f;
+  }
+  icp->linearize_count = c.count0 + iters;
+  icp->cold = false;
+  icp->n_pending = 0;
+  c.active = false;
+  return rc_all;
+}
+
+static int align_wait(mh_icp * icp)
+{
+  mh_ctx * ctx = icp->ctx;
+  MH_HIP(ctx, mh_enter(ctx));
+  if (icp->align.queued > 0) {
+    double row[mh::kRowWords];
+    const int rc = align_wait_row(icp, icp->align.queued - 1, row);
+    if (rc != MH_OK) {
+      align_abandon(icp);
+      return rc;
+    }
+  }
+  return align_finish(icp);
+}
+
+static int mh_icp_align_impl(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
+                             mh_icp_align_result * out, bool blocking)
+{
+  int rc = align_begin(icp, R0, t0, g_unit, cfg, out);
+  if (rc != MH_OK) return rc;
+  const int max_iters = cfg->max_iters;
+  const int chunk = (blocking && cfg->check_every > 0) ? cfg->check_every : max_iters;
+  while (icp->align.queued < max_iters) {
+    const int upto = std::min(icp->align.queued + chunk, max_iters);
+    rc = align_enqueue(icp, upto);
+    if (rc != MH_OK) return rc;
+    if (!blocking) return MH_OK;  // (everything is queued: chunk == max_iters)
+    double row[mh::kRowWords];
+    rc = align_wait_row(icp, upto - 1, row);
+    if (rc != MH_OK) {
+      align_abandon(icp);
+      return rc;
+    }
+    if (static_cast<int>(row[mh::kRowFlags]) & 1) break;  // stopped: nothing more to queue
+  }
+  return align_finish(icp);
+}
+int mh_icp_align(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
+                 mh_icp_align_result * out)
+{
+  return guarded(icp ? icp->ctx : nullptr, "mh_icp_align", [&]() -> int { return mh_icp_align_impl(icp, R0, t0, g_unit, cfg, out, true); });
+}
+int mh_icp_align_async(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
+                       mh_icp_align_result * out)
+{
+  return guarded(icp ? icp->ctx : nullptr, "mh_icp_align_async", [&]() -> int { return mh_icp_align_impl(icp, R0, t0, g_unit, cfg, out, false); });
 }
 
 static int mh_icp_get_state_impl(const mh_icp * icp, int32_t * status, double * means, double * normals)

@@ -21,6 +21,7 @@
 #include "../../include/mimosa_hip.h"
 #include <atomic>
 
+#include "align_device.hpp"
 #include "icp_device.hpp"
 #include "map_device.hpp"
 #include "scan_device.hpp"
@@ -649,6 +650,22 @@ struct mh_icp
   uint32_t * h_counts = nullptr;  // pinned
   bool origin_ready = false, plan_open = false;
   uint32_t n_movers = 0;
+  // mh_icp_align: the chain's argument blocks, grid prefix, state and K3's landing slots in device memory the factor owns
+  // (d_align), their pinned staging (h_align), and the call in flight.  While one is, it holds the whole ring (n_pending ==
+  // kMaxPending): every other entry point refuses the factor as it refuses one with 64 calls in flight.
+  DevBuf d_align;
+  void * h_align = nullptr;
+  struct AlignCall
+  {
+    bool active = false;
+    mh_icp_align_config cfg{};
+    mh_icp_align_result * out = nullptr;
+    double R0[9], gz[3];
+    int queued = 0, count0 = 0;
+    bool cold0 = true;
+    unsigned int seq[kMaxPending];
+    mh::AlignParams p;
+  } align;
 };
 
 // mh_api.hip internals used by shard_api.hip

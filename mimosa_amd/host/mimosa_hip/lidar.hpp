@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <unordered_map>
 
 #include "../../../include/mimosa_hip.h"
@@ -550,6 +551,44 @@ public:
       factors[i]->last_ = r[i];
       out.push_back(factors[i]->toHessian(r[i]));
     }
+    return out;
+  }
+
+  // Scan-to-map alignment from a rough pose (no counterpart in the reference, which leaves the loop to GTSAM): the whole
+  // Gauss-Newton loop — linearize, 6 x 6 solve, retract — as one chain of launches on the device, one wait (mh_icp_align).
+  struct AlignConfig
+  {
+    int max_iters = 10;
+    double eps_rot = 1e-6, eps_trans = 1e-6, damping = 0.0, prior_sigma_rot = 0.0, prior_sigma_trans = 0.0;
+    int check_every = 0;
+  };
+  struct AlignResult
+  {
+    Pose3 pose;
+    int iters = 0;
+    bool converged = false;
+    std::vector<mh_icp_align_trace> trace;  // one row per executed iteration
+  };
+  AlignResult align(const Pose3 & T0, const Unit3 & g, const AlignConfig & config)
+  {
+    const PoseRM T = rowMajor(T0);
+    const A3 gu = toArray(g.unitVector());
+    mh_icp_align_config c;
+    c.max_iters = config.max_iters;
+    c.eps_rot = config.eps_rot;
+    c.eps_trans = config.eps_trans;
+    c.damping = config.damping;
+    c.prior_sigma_rot = config.prior_sigma_rot;
+    c.prior_sigma_trans = config.prior_sigma_trans;
+    c.check_every = config.check_every;
+    std::unique_ptr<mh_icp_align_result> r(new mh_icp_align_result);
+    ctx().check(mh_icp_align(icp_, T.R.data(), T.t.data(), gu.data(), &c, r.get()), "mh_icp_align");
+    last_ = r->last;
+    AlignResult out;
+    out.pose = pose3(r->R, r->t);
+    out.iters = r->iters;
+    out.converged = r->converged != 0;
+    out.trace.assign(r->trace, r->trace + r->iters);
     return out;
   }
 

@@ -19,6 +19,7 @@
 #include <limits>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 
 #include "manager.hpp"
 
@@ -241,6 +242,10 @@ struct Config
   // reads the scan's device table.  The device's sin / cos are not the host's: poses agree to ~1e-15, not bit for bit.
   // ManagerReplay hands it to lidar::Manager::setDevicePoses (the Manager still reads the timestamps: it needs the first one).
   bool device_poses = false;
+  // FixedLagReplay only: the first scan after seedMap is aligned to the map (ICPFactor::align: the Gauss-Newton loop on the
+  // device, from the propagated first guess) before its factor goes to the smoother.
+  bool init_align = false;
+  int init_align_iters = 10;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
   lidar::ManagerInputConfig input = lidar::defaultManagerInputConfig();
@@ -263,6 +268,7 @@ struct Result
   std::vector<int> photo_in_window;  // photo_window: photometric factors in the window at each scan's optimisation
   std::vector<std::vector<double>> costs;
   int n_keyframes = 0;
+  int init_align_iters = 0;   // Config::init_align: iterations the first scan's alignment executed
   int device_pose_scans = 0;  // scans whose deskew poses were computed on the device (Config::device_poses)
   double seconds = 0, stage[5] = {0, 0, 0, 0, 0};  // front_end, imu, factor_create, optimise, update_map
   // finer split of the main thread's time: stage_wait, prepare, deskew, geo_preprocess, icp_create, photo_wait, photo_preprocess,
@@ -667,6 +673,21 @@ public:
       lv.T = pred.T;
       lv.f = geo_->makeFactor(Xk, scan_, cfg_.reg);
       lv.f->computeComponents(false);  // the loop below only takes H, b, f
+      if (cfg_.init_align && k == 0) {
+        if constexpr (std::is_same<typename Geo::Factor, ICPFactor>::value) {
+          ICPFactor::AlignConfig ac;
+          ac.max_iters = cfg_.init_align_iters;
+          ac.eps_rot = ac.eps_trans = 1e-6;
+          ac.damping = 1e-9;
+          const ICPFactor::AlignResult ar = lv.f->align(toPose3(lv.T), Unit3(0.0, 0.0, -1.0), ac);
+          const PoseRM Ta = rowMajor(ar.pose);
+          lv.T.R = Ta.R;
+          lv.T.t = Ta.t;
+          res.init_align_iters = ar.iters;
+        } else {
+          throw std::runtime_error("replay: init_align is offered by FixedLagReplay only");
+        }
+      }
       const auto b1 = clk::now();
       res.detail[4] += secs(a3, b1);
       lv.has_Z = have_prev;
@@ -682,7 +703,7 @@ public:
           res.detail[5] += secs(c1, clk::now());
         }
         const auto c2 = clk::now();
-        values.insert(Xk, toPose3(pred.T));
+        values.insert(Xk, toPose3(lv.T));
         photo_->getFactors(values, photo_graph);  // no factor while nothing is tracked (photometric.cpp:381)
         res.detail[7] += secs(c2, clk::now());
       }
@@ -916,6 +937,7 @@ public:
   ManagerReplay(const std::shared_ptr<lidar::Context> & ctx, const Config & cfg, size_t lru_horizon = 1000) : ctx_(ctx), cfg_(cfg), imu_(cfg.gravity)
   {
     if (cfg.photo_window) throw std::runtime_error("ManagerReplay: photo_window is not offered through lidar::Manager (FixedLagReplay only)");
+    if (cfg.init_align) throw std::runtime_error("ManagerReplay: init_align is not offered through lidar::Manager (FixedLagReplay only)");
     lidar::ManagerConfig mc;
     mc.range_min = cfg.input.range_min;
     mc.range_max = cfg.input.range_max;

@@ -34,17 +34,19 @@ int main(int argc, char ** argv)
   try {
     std::ifstream f(argv[1], std::ios::binary);
     if (!f) throw std::runtime_error("cannot open the input file");
-    const auto I = read_vec<int32_t>(f);   // window, update_iters, photometric, neighbour mode, lru_horizon[, photo_window]
+    const auto I = read_vec<int32_t>(f);   // window, update_iters, photometric, neighbour mode, lru_horizon[, photo_window[, init_align iterations]]
     const auto D = read_vec<double>(f);    // between sigmas (rot, trans), keyframe thresholds (trans, rot deg), gravity xyz
     const auto regb = read_vec<uint8_t>(f);
     const auto inpb = read_vec<uint8_t>(f);
-    if ((I.size() != 5 && I.size() != 6) || D.size() != 7 || regb.size() != sizeof(mh_reg_config) || inpb.size() != sizeof(mh_input_config))
+    if ((I.size() != 5 && I.size() != 6 && I.size() != 7) || D.size() != 7 || regb.size() != sizeof(mh_reg_config) || inpb.size() != sizeof(mh_input_config))
       throw std::runtime_error("configuration block has the wrong shape");
     replay::Config cfg;
     cfg.window = I[0];
     cfg.update_iters = I[1];
     cfg.photometric = I[2] != 0;
     cfg.photo_window = (I.size() > 5 ? I[5] : 0) != 0;
+    cfg.init_align = I.size() > 6 && I[6] > 0;  // (the seventh word: init_align's iteration limit)
+    if (cfg.init_align) cfg.init_align_iters = I[6];
     cfg.neighbor_voxel_mode = static_cast<size_t>(I[3]);
     cfg.between_sigma_rot = D[0];
     cfg.between_sigma_trans = D[1];
@@ -144,7 +146,7 @@ int main(int argc, char ** argv)
     for (size_t i = 0; i < r.photo_valid.size(); ++i) std::printf("%d%s", r.photo_valid[i], i + 1 < r.photo_valid.size() ? ", " : "");
     std::printf("],\n\"photo_in_window\": [");
     for (size_t i = 0; i < r.photo_in_window.size(); ++i) std::printf("%d%s", r.photo_in_window[i], i + 1 < r.photo_in_window.size() ? ", " : "");
-    std::printf("],\n\"first_costs\": [");
+    std::printf("],\n\"init_align_iters\": %d,\n\"first_costs\": [", r.init_align_iters);
     for (size_t i = 0; !r.costs.empty() && i < r.costs.at(0).size(); ++i) std::printf("%.17g%s", r.costs[0][i], i + 1 < r.costs[0].size() ? ", " : "");
     std::printf("],\n\"poses\": [");
     for (size_t k = 0; k < r.poses.size(); ++k) {

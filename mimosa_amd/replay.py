@@ -66,6 +66,10 @@ class ReplayConfig:
     # timestamp is read back, no pose table uploaded, the photometric frame reads the scan's device table.  HIP backend and the
     # native replay only (the CPU backend has no device to keep a table on)
     device_poses: bool = False
+    # the first scan after the map is seeded is aligned to the map (mh_icp_align: the Gauss-Newton loop on the device, from the
+    # propagated first guess) before its factor goes to the smoother.  HIP backend and the native FixedLagReplay only
+    init_align: bool = False
+    init_align_iters: int = 10
     reg: dict = field(default_factory=synth.enwide_config)
     photo: dict = None
 
@@ -252,6 +256,11 @@ class HipBackend:
         f.set_components(False)  # the loop takes H, b, f only (mh_icp_set_components)
         return f
 
+    def align_first(self, f, R, t, max_iters):
+        """init_align: the factor's scan aligned to the map from (R, t); the association state the loop leaves stays with f"""
+        r = f.align(R, t, self.capi.make_align_config(max_iters=max_iters, eps_rot=1e-6, eps_trans=1e-6, damping=1e-9))
+        return r["R"], r["t"]
+
     def make_photo_factor(self):
         return self.photo.make_factor() if self.photo is not None and self.photo.features() else None
 
@@ -303,7 +312,8 @@ def write_native_input(path, cfg: ReplayConfig, scans, rng_seed=7, mode=synth.EN
             arr = np.ascontiguousarray(arr if dtype is None else np.asarray(arr, dtype))
             f.write(struct.pack("<Q", len(arr) if arr.dtype.itemsize == 32 else arr.size))
             f.write(arr.tobytes())
-        w([cfg.window, cfg.update_iters, int(cfg.photometric), mode, 1000] + ([1] if cfg.photo_window else []), np.int32)
+        w([cfg.window, cfg.update_iters, int(cfg.photometric), mode, 1000] + ([1] if cfg.photo_window and not cfg.init_align else [])
+          + ([int(cfg.photo_window), cfg.init_align_iters] if cfg.init_align else []), np.int32)
         w([cfg.between_sigma_rot, cfg.between_sigma_trans, cfg.keyframe_trans_thresh, cfg.keyframe_rot_thresh_deg, *GRAVITY], np.float64)
         w(np.frombuffer(bytes(capi.make_reg_config(**cfg.reg)), np.uint8))
         w(np.frombuffer(bytes(capi.make_input_config()), np.uint8))
@@ -380,6 +390,8 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     scans = scans if scans is not None else make_scans(cfg)
     if cfg.device_poses and not hasattr(backend, "deskew_imu_and_preprocess"):
         raise ValueError("device_poses needs a backend that keeps the pose table on the device (HipBackend)")
+    if cfg.init_align and not hasattr(backend, "align_first"):
+        raise ValueError("init_align needs a backend with mh_icp_align (HipBackend)")
     backend.seed_map(synth.make_room(synth.BASE_SEED, 0, 0, room=np.asarray(cfg.room)))
     stage = {"front_end": 0.0, "imu": 0.0, "factor_create": 0.0, "optimise": 0.0, "update_map": 0.0}
     v_body = np.asarray(cfg.v, float)
@@ -416,7 +428,10 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         f = backend.make_factor()
         pf = backend.make_photo_factor() if cfg.photometric else None
         Z = _between(R_start, p_start, R_pred, p_pred) if R_prev is not None else None
-        win.append(dict(k=k, R=R_pred, t=p_pred, f=f, Z=Z, pf=pf if cfg.photo_window else None))
+        R_w, t_w = R_pred, p_pred
+        if cfg.init_align and R_prev is None:
+            R_w, t_w = backend.align_first(f, R_pred, p_pred, cfg.init_align_iters)
+        win.append(dict(k=k, R=R_w, t=t_w, f=f, Z=Z, pf=pf if cfg.photo_window else None))
         if len(win) > cfg.window:
             old = win.pop(0)
             backend.release(old["f"])
