@@ -34,7 +34,7 @@ SOURCES = [
     ("radar_api.hip", []),
     ("align_kernels.hip", ["-ffp-contract=off"]),  # the host build of align_device.hpp (tests/cpp/align_step.cpp) gives the same digits
 ]
-HEADERS = ["icp_device.hpp", "align_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
+HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
 
 
 def _hipcc() -> str:
@@ -177,6 +177,7 @@ def build_replay_native(force: bool = False) -> str:
 # Host tests of headers the device code shares (plain g++, link nothing): name -> (source under tests/cpp, headers it reads)
 HOST_TESTS = {
     "align_step": ("align_step.cpp", ["align_device.hpp", "math3.hpp"]),
+    "flagged_word": ("flagged_word.cpp", ["flagged_word.hpp"]),
 }
 
 

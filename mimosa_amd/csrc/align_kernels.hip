@@ -14,15 +14,6 @@
 
 namespace mh
 {
-namespace
-{
-__device__ __forceinline__ void ll_put(uint4 * p, double v, unsigned int seq)
-{
-  const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
-  *p = make_uint4(static_cast<unsigned int>(b), seq, static_cast<unsigned int>(b >> 32), seq);
-}
-}  // namespace
-
 __global__ __launch_bounds__(64) void icp_align_step_kernel(const AlignStepArgs a)
 {
   __shared__ double s_sum[32];
@@ -60,8 +51,8 @@ __global__ __launch_bounds__(64) void icp_align_step_kernel(const AlignStepArgs 
     if (lane == 32 && s_stop) a.next->n = 0;
   }
   // to the host: the sums + counters of an evaluated iteration, then the row
-  if (lane < 32 && !frozen && !missing) ll_put(a.ll_host + lane, s_sum[lane], a.seq);
-  if (lane < kRowWords) ll_put(a.ll_host + kLlSums + lane, s_row[lane], a.seq);
+  if (lane < 32 && !frozen && !missing) ll_store(a.ll_host + lane, s_sum[lane], a.seq);
+  if (lane < kRowWords) ll_store(a.ll_host + kLlSums + lane, s_row[lane], a.seq);
 }
 
 hipError_t launch_align_step(const AlignStepArgs & a, hipStream_t stream)

@@ -1,10 +1,12 @@
-// Kernel argument / device-result structs shared by the HIP kernels and the C-ABI implementation.
+// Kernel argument structs and the flagged-word slot layout shared by the HIP kernels and the C-ABI implementation.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 
+#include "flagged_word.hpp"
 #include "voxel_map.hpp"
 
 namespace mh
@@ -26,15 +28,16 @@ struct MapView
                  // kernarg block to scratch and serialise every access behind s_waitcnt vmcnt(0).
 };
 
-// Everything linearize() returns from the device in one small D2H copy.
+// Host-side staging of what one linearize() call's kernels produced: assembled from the call's flagged words (plain factors)
+// or from the all-reduced vectors a sharded round published, then turned into the caller's mh_icp_result by the host epilogue.
+// No kernel reads or writes it.
 struct DeviceResult
 {
   double sums[kPartialStride];  // upper triangle of sum v v^T, v = [J_s(6) (,J_t(6)), e]
-  double loc_rot_final[3], eig_rot[9], loc_trans_final[3], eig_trans[9];
+  double eig_rot[9], eig_trans[9];  // the eigenbases K4 projected on (plain factors whose K4 ran)
   double loc_comp[6];     // trans xyz, rot xyz
   unsigned long long n_knn, n_cand, n_fallback, n_scanned;
   unsigned int status_hist[9];
-  unsigned int seq;  // host slot only: written LAST by K4 (system-scope release) = the call's sequence number
 };
 
 // Results of a plain (unsharded) factor reach the host as "flagged words": every double travels as ONE 16-byte store
@@ -67,8 +70,6 @@ struct IcpArgs
   int32_t * status;
   double * partials;
   unsigned int * ticket;
-  DeviceResult * result;
-  DeviceResult * host_result;  // mapped pinned host slot (may be null): the last block writes its part there too
   unsigned int seq;          // the call's sequence number (tags every flagged word of the call)
   int tail;                  // plain factors: 1 = no K4 follows (components switched off) — ticket, fold by the last block, sums + counters
                              // published as flagged words; 0 = K4 follows and folds the per-block rows itself: this kernel ends at its row
@@ -79,7 +80,7 @@ struct IcpArgs
   // kernel of the same stream, the host only knows an upper bound `n` that sizes the grid); slots whose status carries
   // kShardSkip (points that left for another rank, or could not be sent yet) are passed over untouched
   const uint32_t * n_dev = nullptr;    // null: n is exact
-  double * shard_out = nullptr;        // non-null: the last block also writes the NENT sums + 4 counters here (all-reduce input)
+  double * shard_out = nullptr;        // map-sharded factors (always set there): the last block writes the NENT sums + 4 counters here (all-reduce input)
   // plain factors whose K4 follows: what K4 needs of every point, written HERE into the factor's record (6 arrays of rec_n
   // doubles: the unwhitened, normalised Jacobian directions jr[3], jt[3] — zero unless the point is Valid — then rec_n
   // status words).  K4 follows on the same stream and reads nothing of the factor's association state.
@@ -91,10 +92,8 @@ constexpr int32_t kShardSkip = 0x100;  // status flag bit: not this rank's point
 
 struct LocArgs
 {
-  DeviceResult * host_result;  // mapped pinned host slot: the last block writes loc_comp / status_hist there (no D2H copy node)
-  unsigned int seq;            // published to host_result->seq after everything else: the host may spin on it
-  const double * eig;          // 18 doubles: eig_rot (9) then eig_trans (9); null = derive them from result->sums (K3's Hessian sums)
-  int nv;                      // 7 (unary) or 13 (binary): row length of the v v^T triangle in result->sums
+  unsigned int seq;            // the call's sequence number (tags every flagged word of the call)
+  int nv;                      // 7 (unary) or 13 (binary): row length of the v v^T triangle of the Hessian sums
   const float4 * src;
   int n;
   int chunks_per_block;  // set by the launcher
@@ -106,9 +105,8 @@ struct LocArgs
   const int32_t * status;
   double * partials;
   unsigned int * ticket;
-  DeviceResult * result;
   const uint32_t * n_dev = nullptr;  // as IcpArgs::n_dev
-  const double * sums = nullptr;     // null: result->sums; map-sharded factors: the all-reduced (global) Hessian sums
+  const double * sums = nullptr;     // map-sharded factors (always set there): the all-reduced (global) Hessian sums
   double * shard_out = nullptr;      // non-null: the last block also writes 6 component sums + 9 histogram counts here (16 doubles)
   const double * rec = nullptr;      // plain factors: the call's record written by K3 (IcpArgs::rec); src / normal / status are not read
   int rec_n = 0;
@@ -141,6 +139,22 @@ struct BatchInline
   int n;
   char pad[256];  // load_uniform reads whole 256-byte chunks: keep the last block's read inside the segment
 };
+// One launch's block from n <= kBatchInline members: arg_at(i) is member i's argument block, grid_at(i) its grid.  Fills a[], the
+// exclusive prefix start[], n and the zeroed pad; returns the total grid.
+template <typename A, typename ArgAt, typename GridAt>
+inline int fill_batch_inline(BatchInline<A> & blk, int n, ArgAt && arg_at, GridAt && grid_at)
+{
+  std::memset(static_cast<void *>(&blk), 0, sizeof(blk));
+  int acc = 0;
+  for (int i = 0; i < n; ++i) {
+    blk.a[i] = arg_at(i);
+    blk.start[i] = acc;
+    acc += grid_at(i);
+  }
+  blk.start[n] = acc;
+  blk.n = n;
+  return acc;
+}
 // shard: every factor of the launch is a map-sharded factor's (IcpArgs::n_dev / LocArgs::n_dev set) — the SHARD instantiation.
 hipError_t launch_linearize_batch_inline(const BatchInline<IcpArgs> & blk, int total_grid, int tpb, int k, int n_off, bool binary,
                                          hipStream_t stream, bool shard = false);
@@ -154,7 +168,7 @@ hipError_t launch_spatial_order(const float4 * xyz_in, int n, float cell, uint32
                                 size_t temp_bytes, uint32_t * perm, float4 * xyz_out, hipStream_t stream);
 size_t source_order_scratch_bytes(int n);
 hipError_t launch_source_order(const mh_point32 * d_pts, int n, float cell, void * scratch, uint32_t * perm, float4 * xyz_out,
-                               uint32_t * zero_a, int n_zero_a, uint32_t * zero_b, int n_zero_b, hipStream_t stream);
+                               uint32_t * zero, int n_zero, hipStream_t stream);
 hipError_t launch_unpermute_state(const uint32_t * perm, int n, const int32_t * st_in, const double * mean_in,
                                   const double * nrm_in, int32_t * st_out, double * mean_out, double * nrm_out,
                                   hipStream_t stream);

@@ -1031,13 +1031,6 @@ __device__ __forceinline__ double load_partial(const double * p)
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// One double as a flagged word (icp_device.hpp): a single 16-byte store into mapped pinned memory.
-__device__ __forceinline__ void ll_store(uint4 * p, double v, unsigned int seq)
-{
-  const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
-  *p = make_uint4(static_cast<unsigned int>(b), seq, static_cast<unsigned int>(b >> 32), seq);
-}
-
 __device__ __forceinline__ bool arrive_is_last(unsigned int * ticket, unsigned int n_blocks, bool * s_last)
 {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave drains its own write-through stores
@@ -1098,7 +1091,7 @@ __device__ __forceinline__ void fold_rows(const double * partials, int n_blocks,
 // Unwhitened, normalised Jacobian directions of one point, as the component localizabilities project them
 // (geometric_factor.hpp:343-352, :434-457): n_s = R^T n, jr = (n_s x p) normalised (Eigen normalized(): unchanged when the
 // squared norm is zero), jt = -n_s.  One body for K3 (plain factors: it writes them into the call's record) and K4 (map-sharded
-// and two-phase callers: from the stored normals), so both produce the same bits.
+// factors: from the stored normals), so both produce the same bits.
 template <typename A>
 __device__ __forceinline__ void loc_directions(const A & a, const double nx, const double ny, const double nz, const double px,
                                                const double py, const double pz, double (&jr)[3], double (&jt)[3])
@@ -1584,19 +1577,8 @@ __device__ __forceinline__ void icp_linearize_body(const IcpArgs & a, const int 
   double * s_sum = s_aux + (TPB / EW) * EW;
   fold_rows<EW, TPB>(a.partials, n_blocks, NENT + 4, s_aux, s_sum);
   if constexpr (SHARD) {
-    // Results go to the device struct (the caller-driven two-phase form reads them there) and, when given, to a mapped host slot
-#define MH_PUT(field, val)                          \
-  do {                                              \
-    a.result->field = (val);                        \
-    if (a.host_result) a.host_result->field = (val); \
-  } while (0)
-    if (threadIdx.x < NENT) MH_PUT(sums[threadIdx.x], s_sum[threadIdx.x]);
-    if (threadIdx.x == NENT) MH_PUT(n_knn, static_cast<unsigned long long>(s_sum[NENT]));
-    if (threadIdx.x == NENT + 1) MH_PUT(n_cand, static_cast<unsigned long long>(s_sum[NENT + 1]));
-    if (threadIdx.x == NENT + 2) MH_PUT(n_fallback, static_cast<unsigned long long>(s_sum[NENT + 2]));
-    if (threadIdx.x == NENT + 3) MH_PUT(n_scanned, static_cast<unsigned long long>(s_sum[NENT + 3]));
-#undef MH_PUT
-    if (a.shard_out && threadIdx.x < NENT + 4) a.shard_out[threadIdx.x] = s_sum[threadIdx.x];  // what the shards all-reduce
+    // precondition of the SHARD instantiation: shard_out is set (both sharded launch sites do) — what the shards all-reduce
+    if (threadIdx.x < NENT + 4) a.shard_out[threadIdx.x] = s_sum[threadIdx.x];
   } else {
     // this kernel is the whole call: sums + counters straight to the host as flagged words (computeLocalizability of the
     // rot / trans blocks, :405-411, is the host epilogue's: finish_result)
@@ -1717,7 +1699,6 @@ __device__ __forceinline__ void icp_localizability_body(const LocArgs & a, const
   const bool worker = !XW || threadIdx.x < static_cast<unsigned int>(TPB);  // (wave-uniform)
   __shared__ double s_w[NW][16];
   __shared__ double s_seg[TPB + 96 + 96];  // fold scratch: (TPB / EW) * EW segment sums + EW totals, EW = 32 or 96
-  __shared__ bool s_last;
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   MH_STAMP4(a.dbg, 0);
@@ -1778,7 +1759,7 @@ __device__ __forceinline__ void icp_localizability_body(const LocArgs & a, const
   const double * sums = nullptr;
   double * s_h = s_seg + TPB;  // folded sums + counters (plain factors)
   if constexpr (SHARD) {
-    sums = a.sums ? a.sums : a.result->sums;
+    sums = a.sums;
   } else {
     const int n_ent = a.nv * (a.nv + 1) / 2 + 4;
     constexpr int FB = 32;  // rows in flight per thread: 256 rows over 8 segments in one round trip
@@ -1790,12 +1771,10 @@ __device__ __forceinline__ void icp_localizability_body(const LocArgs & a, const
   }
   load_all();
   MH_STAMP4(a.dbg, 2);
-  // The two eigenbases: given (two-phase callers), or derived here — one lane per 3 x 3 block (computeLocalizability,
-  // utils.hpp:308-313), every workgroup for itself, on the LAST two waves (the others go on to their points).
+  // The two eigenbases, derived here — one lane per 3 x 3 block (computeLocalizability, utils.hpp:308-313), every workgroup
+  // for itself, on the LAST two waves (the others go on to their points).
   __shared__ double s_E[18];
-  if (a.eig) {
-    if (threadIdx.x < 18) s_E[threadIdx.x] = a.eig[threadIdx.x];
-  } else if (XW ? (threadIdx.x == TPB || threadIdx.x == TPB + 1) : (threadIdx.x == TPB - 64 || threadIdx.x == TPB - 128)) {
+  if (XW ? (threadIdx.x == TPB || threadIdx.x == TPB + 1) : (threadIdx.x == TPB - 64 || threadIdx.x == TPB - 128)) {
     const int NV = a.nv, o = (XW ? threadIdx.x == TPB + 1 : threadIdx.x == TPB - 64) ? 3 : 0;
     double Hb[9];
     for (int r = 0; r < 3; ++r)
@@ -1808,7 +1787,7 @@ __device__ __forceinline__ void icp_localizability_body(const LocArgs & a, const
     for (int q = 0; q < 9; ++q) s_E[(o ? 9 : 0) + q] = E[q];
   }
   MH_STAMP4(a.dbg, 3);
-  // Jacobian directions of this thread's points (independent of the eigenbases): map-sharded / two-phase callers work them
+  // Jacobian directions of this thread's points (independent of the eigenbases): map-sharded factors work them
   // out here from the stored normals, plain factors loaded them above
   if constexpr (SHARD) {
 #pragma unroll
@@ -1883,48 +1862,32 @@ __device__ __forceinline__ void icp_localizability_body(const LocArgs & a, const
         for (int w2 = 0; w2 < NW; ++w2) c += static_cast<unsigned int>(s_w[w2][6 + h0 + h]);
         pk |= static_cast<unsigned long long>(c) << (12 * h);
       }
-      ll_rows[threadIdx.x] = make_uint4(static_cast<unsigned int>(pk), a.seq, static_cast<unsigned int>(pk >> 32), a.seq);
+      ll_store_bits(ll_rows + threadIdx.x, pk, a.seq);
     }
     if (block_id == 0) {
       const int n_ent = a.nv * (a.nv + 1) / 2 + 4;
       if (threadIdx.x >= 64 && static_cast<int>(threadIdx.x) < 64 + n_ent) ll_store(a.ll + (threadIdx.x - 64), s_h[threadIdx.x - 64], a.seq);
       if (threadIdx.x >= 192 && threadIdx.x < 192 + 18) ll_store(a.ll + kLlSums + (threadIdx.x - 192), s_E[threadIdx.x - 192], a.seq);
     }
-    (void)n_blocks;
-    (void)s_last;
 #ifdef MH_TIMELINE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the flagged words have left (acknowledged) by this stamp
 #endif
     MH_STAMP4(a.dbg, 9);
     return;
   } else {
-  if (threadIdx.x < 15) {
-    double s = 0.0;
-    for (int w2 = 0; w2 < NW; ++w2) s += s_w[w2][threadIdx.x];
-    store_partial(&a.partials[static_cast<size_t>(block_id) * kPartialStride + threadIdx.x], s);
-  }
-  if (!arrive_is_last(a.ticket, static_cast<unsigned int>(n_blocks), &s_last)) return;
-  double * s_sum = s_seg + (TPB / 32) * 32;
-  fold_rows<32, TPB>(a.partials, n_blocks, 15, s_seg, s_sum);
-  if (threadIdx.x < 6) a.result->loc_comp[threadIdx.x] = s_sum[threadIdx.x];
-  if (threadIdx.x >= 6 && threadIdx.x < 15)
-    a.result->status_hist[threadIdx.x - 6] = static_cast<unsigned int>(s_sum[threadIdx.x]);
-  if (a.shard_out && threadIdx.x < 16) a.shard_out[threadIdx.x] = threadIdx.x < 15 ? s_sum[threadIdx.x] : 0.0;
-  // the eigenbases THIS pass projected on are what the caller is told (the host's own decomposition of the same sums may
-  // pick another basis of a clustered eigenspace: no FMA there, other branches of sym_eigen3)
-  if (threadIdx.x >= 32 && threadIdx.x < 50) {
-    const int q = threadIdx.x - 32;
-    double * dst = q < 9 ? &a.result->eig_rot[q] : &a.result->eig_trans[q - 9];
-    *dst = s_E[q];
-    if (a.host_result) *(q < 9 ? &a.host_result->eig_rot[q] : &a.host_result->eig_trans[q - 9]) = s_E[q];
-  }
-  // two-phase callers (mh_icp_linearize_finish): this kernel's outputs also go to a mapped pinned host slot; the end of the
-  // kernel makes them visible to the host (they synchronise the stream)
-  if (a.host_result) {
-    if (threadIdx.x < 6) a.host_result->loc_comp[threadIdx.x] = s_sum[threadIdx.x];
-    if (threadIdx.x >= 6 && threadIdx.x < 15)
-      a.host_result->status_hist[threadIdx.x - 6] = static_cast<unsigned int>(s_sum[threadIdx.x]);
-  }
+    // Map-sharded factor: per-workgroup rows, ticket, fold by the last block; its 6 component sums + 9 histogram counts are
+    // this rank's input to the all-reduce (shard_out, set by both sharded launch sites).  The eigenbases the caller is told
+    // come from the host's decomposition of the all-reduced sums.
+    __shared__ bool s_last;
+    if (threadIdx.x < 15) {
+      double s = 0.0;
+      for (int w2 = 0; w2 < NW; ++w2) s += s_w[w2][threadIdx.x];
+      store_partial(&a.partials[static_cast<size_t>(block_id) * kPartialStride + threadIdx.x], s);
+    }
+    if (!arrive_is_last(a.ticket, static_cast<unsigned int>(n_blocks), &s_last)) return;
+    double * s_sum = s_seg + (TPB / 32) * 32;
+    fold_rows<32, TPB>(a.partials, n_blocks, 15, s_seg, s_sum);
+    if (a.shard_out && threadIdx.x < 16) a.shard_out[threadIdx.x] = threadIdx.x < 15 ? s_sum[threadIdx.x] : 0.0;
   }
 }
 

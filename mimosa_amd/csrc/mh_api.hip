@@ -349,14 +349,11 @@ static int icp_alloc(mh_icp * icp)
   MH_HIP(ctx, icp->d_status.reserve(n * sizeof(int32_t), ctx->stream, false));
   const size_t max_grid = static_cast<size_t>(mh::linearize_grid_max(static_cast<int>(n)));
   MH_HIP(ctx, icp->d_partials.reserve(max_grid * mh::kPartialStride * sizeof(double), ctx->stream, false));
-  MH_HIP(ctx, icp->d_ticket.reserve(4 * sizeof(unsigned int), ctx->stream, false));  // K3's ticket, K4's ticket, the point count of the two-phase forms
-  MH_HIP(ctx, icp->d_result.reserve(sizeof(mh::DeviceResult), ctx->stream, false));
+  MH_HIP(ctx, icp->d_ticket.reserve(2 * sizeof(unsigned int), ctx->stream, false));  // K3's ticket, K4's ticket
 #ifdef MH_TIMELINE
   MH_HIP(ctx, icp->d_dbg.reserve(2 * max_grid * 8 * 16 * sizeof(unsigned long long), ctx->stream, false));  // K3's waves, then K4's
   MH_HIP(ctx, hipMemsetAsync(icp->d_dbg.p, 0, icp->d_dbg.cap, ctx->stream));
 #endif
-  MH_HIP(ctx, AllocCache::alloc_pinned(reinterpret_cast<void **>(&icp->h_results), sizeof(mh::DeviceResult) * kMaxPending));
-  MH_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&icp->d_h_results), icp->h_results, 0));
   // flagged-word slots: a recycled pinned block may hold another factor's words — harmless, sequence numbers are drawn from
   // one process-wide counter (next_call_seq), so nothing stale ever carries the number of a call of this factor
   // (row capacity in steps of 16 workgroups: factors of similar size — a scan's down-sampled cloud from one keyframe to the
@@ -380,8 +377,6 @@ static int icp_init_source(mh_icp * icp, const mh_point32 * source, const mh_poi
 {
   mh_ctx * ctx = icp->ctx;
   const size_t n = icp->n;
-  auto * zero_a = static_cast<uint32_t *>(icp->d_ticket.p);
-  auto * zero_b = static_cast<uint32_t *>(icp->d_result.p);
   if (n) {
     const char * ns = std::getenv("MH_NO_SORT");  // MH_NO_SORT=1 keeps input order (diagnostics)
     const bool order = !(ns && ns[0] == '1') && !icp->no_order;
@@ -407,16 +402,14 @@ static int icp_init_source(mh_icp * icp, const mh_point32 * source, const mh_poi
       float cell = 0.25f;
       if (const char * cs = std::getenv("MH_SORT_CELL")) cell = static_cast<float>(std::atof(cs));
       MH_HIP(ctx, mh::launch_source_order(d_pts, ni, cell, sc + up, static_cast<uint32_t *>(icp->d_perm.p), static_cast<float4 *>(icp->d_src.p),
-                                          zero_a, 2, zero_b, static_cast<int>(sizeof(mh::DeviceResult) / 4), ctx->stream));
+                                          static_cast<uint32_t *>(icp->d_ticket.p), 2, ctx->stream));
       icp->ordered = true;
     } else {
       MH_HIP(ctx, mh::launch_pack_xyz(d_pts, ni, static_cast<float4 *>(icp->d_src.p), ctx->stream));
       MH_HIP(ctx, hipMemsetAsync(icp->d_ticket.p, 0, 2 * sizeof(unsigned int), ctx->stream));
-      MH_HIP(ctx, hipMemsetAsync(icp->d_result.p, 0, sizeof(mh::DeviceResult), ctx->stream));
     }
   } else {
     MH_HIP(ctx, hipMemsetAsync(icp->d_ticket.p, 0, 2 * sizeof(unsigned int), ctx->stream));
-    MH_HIP(ctx, hipMemsetAsync(icp->d_result.p, 0, sizeof(mh::DeviceResult), ctx->stream));
   }
   // commonConstructor(): all per-point state zero (geometric_factor.hpp:144-156).  A cold factor's state is never read
   // (the first linearize treats it as zero without touching memory, the getters answer zeros while `cold`); only a
@@ -512,7 +505,6 @@ static int mh_icp_clone_impl(const mh_icp * src, mh_icp ** out)
   MH_HIP(ctx, cp(src->d_mean, icp->d_mean, n * 3 * sizeof(double)));
   MH_HIP(ctx, cp(src->d_normal, icp->d_normal, n * 3 * sizeof(double)));
   MH_HIP(ctx, cp(src->d_status, icp->d_status, n * sizeof(int32_t)));
-  MH_HIP(ctx, cp(src->d_result, icp->d_result, sizeof(mh::DeviceResult)));
   if (src->ordered) {
     MH_HIP(ctx, icp->d_perm.reserve(n * sizeof(uint32_t), ctx->stream, false));
     MH_HIP(ctx, cp(src->d_perm, icp->d_perm, n * sizeof(uint32_t)));
@@ -544,15 +536,12 @@ void mh_icp_destroy(mh_icp * icp)
   icp->d_status.release(true);
   icp->d_partials.release(true);
   icp->d_ticket.release(true);
-  icp->d_result.release(true);
   icp->d_dbg.release(true);
   icp->d_perm.release(true);
-  icp->d_eig.release(true);
   for (DevBuf * b : {&icp->d_origin, &icp->x_src, &icp->x_qda, &icp->x_mean, &icp->x_normal, &icp->x_status, &icp->x_origin, &icp->s_keys_a,
                      &icp->s_keys_b, &icp->s_idx_a, &icp->s_idx_b, &icp->s_counts, &icp->s_temp, &icp->d_sums})
     b->release(true);
   if (icp->h_counts) (void)hipHostFree(icp->h_counts);
-  if (icp->h_results) AllocCache::free_pinned(icp->h_results, sizeof(mh::DeviceResult) * kMaxPending);
   if (icp->h_ll) AllocCache::free_pinned(icp->h_ll, icp->ll_words * sizeof(uint4) * kMaxPending);
   icp->d_align.release(true);
   if (icp->h_align) AllocCache::free_pinned(icp->h_align, kAlignStageBytes);
@@ -648,11 +637,9 @@ static unsigned int next_call_seq()
 }
 
 // Argument blocks of one linearize call of `icp` in pending slot n_pending (which it claims): everything of
-// linearize_enqueue except the launches.  want_flag: the last kernel publishes a completion sequence number to the
-// host slot (mh_icp_wait then spins on it instead of synchronising the stream).  Worth it for one synchronous call,
-// not for a pipelined batch: the system-scope fence it needs lengthens every K4 by ~2 us.
+// linearize_enqueue except the launches.
 static int linearize_prepare(mh_icp * icp, const double R_src[9], const double t_src[3], const double * R_tgt,
-                             const double * t_tgt, const double g_unit[3], mh_icp_result * out, bool want_flag, bool allow_timing,
+                             const double * t_tgt, const double g_unit[3], mh_icp_result * out, bool allow_timing,
                              mh::IcpArgs & a, mh::LocArgs & l, bool & timed)
 {
   if (!icp || !R_src || !t_src || !g_unit || !out)
@@ -698,8 +685,6 @@ static int linearize_prepare(mh_icp * icp, const double R_src[9], const double t
   a.status = static_cast<int32_t *>(icp->d_status.p);
   a.partials = static_cast<double *>(icp->d_partials.p);
   a.ticket = static_cast<unsigned int *>(icp->d_ticket.p);
-  a.result = static_cast<mh::DeviceResult *>(icp->d_result.p);
-  a.host_result = nullptr;  // set below once the slot is known
   a.dbg = static_cast<unsigned long long *>(icp->d_dbg.p);
   a.reps = 1;
 #ifdef MH_TIMELINE
@@ -707,9 +692,7 @@ static int linearize_prepare(mh_icp * icp, const double R_src[9], const double t
 #endif
 
   l.src = a.src;
-  l.host_result = nullptr;  // set below once the slot is known
   l.seq = 0;
-  l.eig = nullptr;
   l.nv = icp->binary ? 13 : 7;
   l.n = a.n;
   l.k = a.k;
@@ -719,7 +702,6 @@ static int linearize_prepare(mh_icp * icp, const double R_src[9], const double t
   l.status = a.status;
   l.partials = a.partials;
   l.ticket = a.ticket + 1;
-  l.result = a.result;
   l.rec = a.rec;
   l.rec_n = a.rec_n;
 #ifdef MH_TIMELINE
@@ -749,9 +731,8 @@ static int linearize_prepare(mh_icp * icp, const double R_src[9], const double t
   a.ll = l.ll = nullptr;
   const int ppw = mh::linearize_class(a.n, a.k, false);  // (a call of its own; a window batch and the sharded path set their own)
   l.k3_blocks = mh::class_grid(a.n, ppw);
-  (void)want_flag;  // every call is collected through its flagged words now: no completion flag to ask for
   if (a.n > 0) {
-    // plain factors publish flagged words into the call's slot; the two-phase and sharded callers overwrite what they need
+    // plain factors publish flagged words into the call's slot; the sharded callers overwrite what they need
     pc.seq = a.seq = l.seq = next_call_seq();
     a.ll = l.ll = icp->d_h_ll + static_cast<size_t>(slot) * icp->ll_words;
     pc.loc_blocks = mh::class_loc_grid(a.n, ppw);
@@ -762,13 +743,13 @@ static int linearize_prepare(mh_icp * icp, const double R_src[9], const double t
 }
 
 static int linearize_enqueue(mh_icp * icp, const double R_src[9], const double t_src[3], const double * R_tgt,
-                             const double * t_tgt, const double g_unit[3], mh_icp_result * out, bool want_flag)
+                             const double * t_tgt, const double g_unit[3], mh_icp_result * out)
 {
   mh::IcpArgs a;
   mh::LocArgs l;
   bool timed = false;
   LinearizeTxn txn(icp);
-  const int rc = linearize_prepare(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out, want_flag, true, a, l, timed);
+  const int rc = linearize_prepare(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out, true, a, l, timed);
   if (rc != MH_OK) return rc;
   mh_ctx * ctx = icp->ctx;
   const int slot = icp->n_pending - 1;
@@ -805,29 +786,12 @@ static int linearize_enqueue(mh_icp * icp, const double R_src[9], const double t
 static int mh_icp_linearize_async_impl(mh_icp * icp, const double R_src[9], const double t_src[3], const double * R_tgt,
                            const double * t_tgt, const double g_unit[3], mh_icp_result * out)
 {
-  return linearize_enqueue(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out, false);
+  return linearize_enqueue(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out);
 }
 int mh_icp_linearize_async(mh_icp * icp, const double R_src[9], const double t_src[3], const double * R_tgt,
                            const double * t_tgt, const double g_unit[3], mh_icp_result * out)
 {
   return guarded(icp ? icp->ctx : nullptr, "mh_icp_linearize_async", [&]() -> int { return mh_icp_linearize_async_impl(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out); });
-}
-
-// One flagged word (icp_device.hpp): two self-validating 8-byte halves {lo | seq << 32, hi | seq << 32}.
-static inline bool ll_read_bits(const uint4 * p, unsigned int seq, unsigned long long & bits)
-{
-  const auto * q = reinterpret_cast<const unsigned long long *>(p);
-  const unsigned long long a = __atomic_load_n(q, __ATOMIC_ACQUIRE), b = __atomic_load_n(q + 1, __ATOMIC_ACQUIRE);
-  if (static_cast<unsigned int>(a >> 32) != seq || static_cast<unsigned int>(b >> 32) != seq) return false;
-  bits = (a & 0xffffffffull) | (b << 32);
-  return true;
-}
-static inline bool ll_read(const uint4 * p, unsigned int seq, double & v)
-{
-  unsigned long long bits;
-  if (!ll_read_bits(p, seq, bits)) return false;
-  std::memcpy(&v, &bits, sizeof(v));
-  return true;
 }
 
 // Assemble a call's DeviceResult from its flagged words: sums + counters (from K4's workgroup 0, or from K3's last block when
@@ -838,21 +802,8 @@ static bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, l
   std::memset(&d, 0, sizeof(d));
   if (pc.seq == 0) return true;  // nothing was launched (empty cloud)
   const uint4 * base = icp->h_ll + static_cast<size_t>(slot) * icp->ll_words;
-  timespec t0;
-  clock_gettime(CLOCK_MONOTONIC, &t0);
-  unsigned spins = 0;
-  auto get = [&](const uint4 * p, double & v) {
-    while (!ll_read(p, pc.seq, v)) {
-      if (spin_ns <= 0) return false;
-      __builtin_ia32_pause();
-      if ((++spins & 1023u) == 0u) {
-        timespec t1;
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        if ((t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec) > spin_ns) return false;
-      }
-    }
-    return true;
-  };
+  mh::SpinBudget spin(spin_ns);  // one budget for the whole call
+  auto get = [&](const uint4 * p, double & v) { return spin.until([&] { return mh::ll_read(reinterpret_cast<const uint64_t *>(p), pc.seq, v); }); };
   const int nent = icp->binary ? 91 : 28;
   double c4[4];
   // the words that are written LAST first (K4's rows, when it ran): once they are here the rest usually is
@@ -962,7 +913,7 @@ static int mh_icp_linearize_impl(mh_icp * icp, const double R_src[9], const doub
                      const double * t_tgt, const double g_unit[3], mh_icp_result * out)
 {
   const double t0 = g_wt.on ? WaitTrace::now() : 0.0;
-  const int rc = linearize_enqueue(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out, icp && icp->n_pending == 0);
+  const int rc = linearize_enqueue(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out);
   if (rc != MH_OK) return rc;
   if (g_wt.on) g_wt.enq += WaitTrace::now() - t0;
   return mh_icp_wait(icp);
@@ -1001,14 +952,7 @@ static int mh_icp_linearize_batch_impl(mh_icp * const * icps, size_t n_factors, 
   // above: so every factor reduces in exactly the order of a separate call), k == 5 or the generic k <= 8 path, neighbour
   // mode, unary / binary.  One K3b (+ one K4b) launch per non-empty group; a window of like factors — the usual case — is
   // one group.  Staging: [IcpArgs x 64 | LocArgs x 64 | grid prefixes], host-pinned + a device copy the kernels read.
-  struct Group
-  {
-    int tpb, k, n_off;
-    bool binary;
-    std::vector<size_t> members;
-    int first = 0, grid = 0, grid4 = 0;
-  };
-  std::vector<Group> groups;
+  std::vector<LaunchGroup> groups;
   long long total_points = 0;  // the class of a small cloud depends on how full the machine is: the whole window's points
   for (size_t f = 0; f < n_factors; ++f) total_points += static_cast<long long>(icps[f]->n);
   // (more factors than ride in the kernel-argument segment: the staged launch form has the one-lane-per-point classes only)
@@ -1019,11 +963,11 @@ static int mh_icp_linearize_batch_impl(mh_icp * const * icps, size_t n_factors, 
     const int k = c->cfg.num_corres_points == 5 ? 5 : 8, n_off = c->map->n_off;
     int tpb = mh::linearize_class(static_cast<int>(c->n), static_cast<int>(c->cfg.num_corres_points), false, total_points);
     if (maybe_staged && tpb < 256) tpb = 256;
-    Group * g = nullptr;
-    for (Group & q : groups)
+    LaunchGroup * g = nullptr;
+    for (LaunchGroup & q : groups)
       if (q.tpb == tpb && q.k == k && q.n_off == n_off && q.binary == c->binary) g = &q;
     if (!g) {
-      groups.push_back(Group{tpb, k, n_off, c->binary, {}, 0, 0, 0});
+      groups.push_back(LaunchGroup{tpb, k, n_off, c->binary, {}});
       g = &groups.back();
     }
     g->members.push_back(f);
@@ -1038,7 +982,7 @@ static int mh_icp_linearize_batch_impl(mh_icp * const * icps, size_t n_factors, 
   size_t slot_of[kMaxBatch];
   {
     int pos = 0;
-    for (Group & g : groups) {
+    for (LaunchGroup & g : groups) {
       g.first = pos;
       for (size_t f : g.members) slot_of[f] = static_cast<size_t>(pos++);
     }
@@ -1051,7 +995,7 @@ static int mh_icp_linearize_batch_impl(mh_icp * const * icps, size_t n_factors, 
     mh::LocArgs l;
     txns.emplace_back(icps[f]);
     const int rc = linearize_prepare(icps[f], R_src + 9 * f, t_src + 3 * f, R_tgt ? R_tgt + 9 * f : nullptr,
-                                     t_tgt ? t_tgt + 3 * f : nullptr, g_unit + 3 * f, out + f, true, false, a, l, timed);
+                                     t_tgt ? t_tgt + 3 * f : nullptr, g_unit + 3 * f, out + f, false, a, l, timed);
     if (rc != MH_OK) return rc;
     if (icps[f]->n == 0) continue;  // (pc.seq == 0: an all-zero result is assembled at the wait)
     h_a[slot_of[f]] = a;
@@ -1066,7 +1010,7 @@ static int mh_icp_linearize_batch_impl(mh_icp * const * icps, size_t n_factors, 
   bool inline_args = true;
   int * h_s4 = h_s + 2 * (kMaxBatch + 1);  // the same prefixes for K4b's (smaller) per-factor grids
   for (size_t gi = 0; gi < groups.size(); ++gi) {
-    Group & g = groups[gi];
+    LaunchGroup & g = groups[gi];
     int * start = h_s + g.first + static_cast<int>(gi);  // prefix of the group's grids, in slot order
     int * start4 = h_s4 + g.first + static_cast<int>(gi);
     int acc = 0, acc4 = 0;
@@ -1091,36 +1035,30 @@ static int mh_icp_linearize_batch_impl(mh_icp * const * icps, size_t n_factors, 
     if (inline_args) {
       // small window: the argument blocks ride in the kernel-argument segment, nothing is copied before the launches
       for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group & g = groups[gi];
+        const LaunchGroup & g = groups[gi];
         const int * start = h_s + g.first + static_cast<int>(gi);
         mh::BatchInline<mh::IcpArgs> blk;
-        std::memset(static_cast<void *>(&blk), 0, sizeof(blk));
-        for (size_t i = 0; i < g.members.size(); ++i) blk.a[i] = h_a[g.first + static_cast<int>(i)];
-        for (size_t i = 0; i <= g.members.size(); ++i) blk.start[i] = start[i];
-        blk.n = static_cast<int>(g.members.size());
+        mh::fill_batch_inline(blk, static_cast<int>(g.members.size()), [&](int i) -> const mh::IcpArgs & { return h_a[g.first + i]; }, [&](int i) { return start[i + 1] - start[i]; });
         MH_HIP(ctx, mh::launch_linearize_batch_inline(blk, g.grid, g.tpb, g.k, g.n_off, g.binary, ctx->stream));
       }
       for (size_t gi = 0; gi < groups.size() && any_components; ++gi) {
-        const Group & g = groups[gi];
+        const LaunchGroup & g = groups[gi];
         const int * start4 = h_s4 + g.first + static_cast<int>(gi);
         mh::BatchInline<mh::LocArgs> blk;
-        std::memset(static_cast<void *>(&blk), 0, sizeof(blk));
-        for (size_t i = 0; i < g.members.size(); ++i) blk.a[i] = h_l[g.first + static_cast<int>(i)];
-        for (size_t i = 0; i <= g.members.size(); ++i) blk.start[i] = start4[i];
-        blk.n = static_cast<int>(g.members.size());
+        mh::fill_batch_inline(blk, static_cast<int>(g.members.size()), [&](int i) -> const mh::LocArgs & { return h_l[g.first + i]; }, [&](int i) { return start4[i + 1] - start4[i]; });
         MH_HIP(ctx, mh::launch_localizability_batch_inline(blk, g.grid4, g.tpb, ctx->stream));
       }
     } else {
       char * d = static_cast<char *>(ctx->d_batch);
       MH_HIP(ctx, hipMemcpyAsync(d, ctx->h_batch, ab + lb + sb, hipMemcpyHostToDevice, ctx->stream));
       for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group & g = groups[gi];
+        const LaunchGroup & g = groups[gi];
         const auto * da = reinterpret_cast<const mh::IcpArgs *>(d) + g.first;
         const int * ds = reinterpret_cast<const int *>(d + ab + lb) + g.first + static_cast<int>(gi);
         MH_HIP(ctx, mh::launch_linearize_batch(da, ds, static_cast<int>(g.members.size()), g.grid, g.tpb, g.k, g.n_off, g.binary, ctx->stream));
       }
       for (size_t gi = 0; gi < groups.size() && any_components; ++gi) {
-        const Group & g = groups[gi];
+        const LaunchGroup & g = groups[gi];
         const auto * dl = reinterpret_cast<const mh::LocArgs *>(d + ab) + g.first;
         const int * ds4 = reinterpret_cast<const int *>(d + ab + lb) + 2 * (kMaxBatch + 1) + g.first + static_cast<int>(gi);
         MH_HIP(ctx, mh::launch_localizability_batch(dl, ds4, static_cast<int>(g.members.size()), g.grid4, g.tpb, ctx->stream));
@@ -1163,20 +1101,9 @@ int mh_icp_linearize_batch(mh_icp * const * icps, size_t n_factors, const double
 static bool align_read_row(const mh_icp * icp, int i, long spin_ns, double * row)
 {
   const uint4 * base = icp->h_ll + static_cast<size_t>(i) * icp->ll_words + mh::kLlSums;
-  timespec t0;
-  clock_gettime(CLOCK_MONOTONIC, &t0);
-  unsigned spins = 0;
-  for (int w = mh::kRowWords - 1; w >= 0; --w) {
-    while (!ll_read(base + w, icp->align.seq[i], row[w])) {
-      if (spin_ns <= 0) return false;
-      __builtin_ia32_pause();
-      if ((++spins & 1023u) == 0u) {
-        timespec t1;
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        if ((t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec) > spin_ns) return false;
-      }
-    }
-  }
+  mh::SpinBudget spin(spin_ns);  // one budget for the whole row
+  for (int w = mh::kRowWords - 1; w >= 0; --w)
+    if (!spin.until([&] { return mh::ll_read(reinterpret_cast<const uint64_t *>(base + w), icp->align.seq[i], row[w]); })) return false;
   return true;
 }
 
@@ -1222,13 +1149,12 @@ static int align_begin(mh_icp * icp, const double R0[9], const double t0[3], con
     bool timed = false;
     mh_icp_result scratch;
     LinearizeTxn txn(icp);
-    const int rc = linearize_prepare(icp, R0, t0, nullptr, nullptr, g_unit, &scratch, false, false, a, l, timed);
+    const int rc = linearize_prepare(icp, R0, t0, nullptr, nullptr, g_unit, &scratch, false, a, l, timed);
     if (rc != MH_OK) return rc;
   }
   a.rec = nullptr;
   a.rec_n = 0;
   a.tail = 1;
-  a.host_result = nullptr;
 
   mh_icp::AlignCall & c = icp->align;
   c.cfg = *cfg;
@@ -2149,9 +2075,9 @@ int icp_create(mh_ctx * ctx, mh_map * map, const mh_point32 * source, const mh_p
   return icp_create_common(ctx, map, source, d_source, n, cfg, is_binary, out, no_order, capacity);
 }
 int prepare(mh_icp * icp, const double R_src[9], const double t_src[3], const double * R_tgt, const double * t_tgt, const double g_unit[3],
-            mh_icp_result * out, bool want_flag, mh::IcpArgs & a, mh::LocArgs & l)
+            mh_icp_result * out, mh::IcpArgs & a, mh::LocArgs & l)
 {
   bool timed = false;
-  return linearize_prepare(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out, want_flag, false, a, l, timed);
+  return linearize_prepare(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out, false, a, l, timed);
 }
 }  // namespace mhi

@@ -608,9 +608,9 @@ struct PendingCall
   double gz[3];    // global_z = -g_unit
   int parity;
   int linearize_count;
-  unsigned int seq;  // what the call's last kernel publishes to the host slot when it is complete (0: nothing was launched)
+  unsigned int seq;  // the call's sequence number: tags every flagged word its kernels publish (0: nothing was launched)
   bool components;   // K4 ran for this call: loc_*_comp / status_hist are meaningful
-  bool seq_has_basis = false;  // ... and wrote the eigenbases it projected on into the call's result slot
+  bool seq_has_basis = false;  // ... and published the eigenbases it projected on among the call's flagged words
   int loc_blocks = 0;          // plain factors: K4's workgroups of this call = rows of flagged words the host folds
   bool launched_k4 = false;    // plain factors: the call's sums come from K4's workgroup 0 (else from K3's last block)
   hipEvent_t ev[3];
@@ -623,13 +623,11 @@ struct mh_icp
   size_t n;
   mh_reg_config cfg;
   bool binary;
-  DevBuf d_src, d_qda, d_mean, d_normal, d_status, d_partials, d_ticket, d_result, d_dbg, d_perm, d_eig;
+  DevBuf d_src, d_qda, d_mean, d_normal, d_status, d_partials, d_ticket, d_dbg, d_perm;
   // plain factors: what K4 reads of a call is the record K3 wrote for it (icp_device.hpp: IcpArgs::rec) and K3's partial rows;
   // K4 follows its K3 on the context's stream, so one of each serves every call of the factor
   DevBuf d_rec;
   bool ordered = false;  // d_src / per-point state are in Morton order, d_perm maps back
-  mh::DeviceResult * h_results = nullptr;    // pinned, mapped ring: the device writes results here directly (two-phase callers)
-  mh::DeviceResult * d_h_results = nullptr;  // its device-side address
   uint4 * h_ll = nullptr;     // pinned, mapped ring of flagged-word slots (icp_device.hpp): what a plain call's kernels publish
   uint4 * d_h_ll = nullptr;   // its device-side address
   size_t ll_words = 0;        // 16-byte words per slot
@@ -668,6 +666,16 @@ struct mh_icp
   } align;
 };
 
+// The factors of a window that share a kernel instantiation — launch class, k == 5 or the generic k <= 8 path, neighbour mode,
+// unary / binary: one batched K3 (+ one K4) launch (mh_icp_linearize_batch, mh_shard_icp_linearize_batch).
+struct LaunchGroup
+{
+  int tpb, k, n_off;
+  bool binary;
+  std::vector<size_t> members;        // indices into the call's factor list
+  int first = 0, grid = 0, grid4 = 0;  // plain path: the group's first staging slot, its K3 and K4 grids
+};
+
 // mh_api.hip internals used by shard_api.hip
 namespace mhi
 {
@@ -677,7 +685,7 @@ int icp_create(mh_ctx * ctx, mh_map * map, const mh_point32 * source, const mh_p
                const mh_reg_config * cfg, int is_binary, mh_icp ** out, bool no_order);
 // argument blocks of one linearize call in pending slot n_pending (claimed); no launch
 int prepare(mh_icp * icp, const double R_src[9], const double t_src[3], const double * R_tgt, const double * t_tgt, const double g_unit[3],
-            mh_icp_result * out, bool want_flag, mh::IcpArgs & a, mh::LocArgs & l);
+            mh_icp_result * out, mh::IcpArgs & a, mh::LocArgs & l);
 // shard_api.hip: called by mh_shutdown(ctx) so that the sharded handles listed on ctx let go of it
 void shard_ctx_gone(mh_ctx * ctx);
 }  // namespace mhi

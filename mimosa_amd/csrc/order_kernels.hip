@@ -46,12 +46,10 @@ __global__ __launch_bounds__(kThreads) void morton_keys_kernel(const float4 * xy
 
 // the same from the 32-byte point records (two float4 each): packs xyz on the way
 __global__ __launch_bounds__(kThreads) void pack_morton_kernel(const float4 * pts2, int n, float inv_cell, float4 * xyz, uint32_t * keys,
-                                                               uint32_t * vals, uint32_t * zero_a, int n_zero_a, uint32_t * zero_b, int n_zero_b)
+                                                               uint32_t * vals, uint32_t * zero, int n_zero)
 {
-  if (blockIdx.x == 0) {  // the factor's ticket / result block start at zero
-    for (int i = threadIdx.x; i < n_zero_a; i += kThreads) zero_a[i] = 0u;
-    for (int i = threadIdx.x; i < n_zero_b; i += kThreads) zero_b[i] = 0u;
-  }
+  if (blockIdx.x == 0)  // the factor's tickets start at zero
+    for (int i = threadIdx.x; i < n_zero; i += kThreads) zero[i] = 0u;
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
     const float4 p = pts2[2 * i];
     xyz[i] = p;
@@ -115,14 +113,14 @@ hipError_t launch_spatial_order(const float4 * xyz_in, int n, float cell, uint32
 }
 
 // Factor creation: d_pts (n 32-byte records, device) -> perm (sorted position -> original index) and xyz_out (packed,
-// sorted).  scratch: source_order_scratch_bytes(n) bytes, stream-ordered.  zero_a / zero_b: dword ranges cleared on the way.
+// sorted).  scratch: source_order_scratch_bytes(n) bytes, stream-ordered.  zero: n_zero dwords cleared on the way.
 size_t source_order_scratch_bytes(int n)
 {
   const size_t m = static_cast<size_t>(n);
   return ((m * sizeof(float4) + 255) & ~size_t(255)) + ((3 * m * sizeof(uint32_t) + 255) & ~size_t(255)) + order_temp_bytes(n) + 256;
 }
 hipError_t launch_source_order(const mh_point32 * d_pts, int n, float cell, void * scratch, uint32_t * perm, float4 * xyz_out,
-                               uint32_t * zero_a, int n_zero_a, uint32_t * zero_b, int n_zero_b, hipStream_t stream)
+                               uint32_t * zero, int n_zero, hipStream_t stream)
 {
   const size_t m = static_cast<size_t>(n);
   char * sc = static_cast<char *>(scratch);
@@ -132,7 +130,7 @@ hipError_t launch_source_order(const mh_point32 * d_pts, int n, float cell, void
   sc += (3 * m * sizeof(uint32_t) + 255) & ~size_t(255);
   size_t tb = order_temp_bytes(n);
   hipLaunchKernelGGL(pack_morton_kernel, dim3(grid_for(n)), dim3(kThreads), 0, stream, reinterpret_cast<const float4 *>(d_pts), n,
-                     1.0f / cell, xyz_tmp, keys2, vals, zero_a, n_zero_a, zero_b, n_zero_b);
+                     1.0f / cell, xyz_tmp, keys2, vals, zero, n_zero);
   hipError_t e = rocprim::radix_sort_pairs(sc, tb, keys2, keys2 + m, vals, perm, m, 0, 30, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(gather_xyz_kernel, dim3(grid_for(n)), dim3(kThreads), 0, stream, xyz_tmp, perm, n, xyz_out);

@@ -1543,19 +1543,7 @@ static int photo_linearize_finish(mh_photo_factor * f, mh_photo_result * out)
     if (!need_sync) {  // spin on the completion number the kernel's last block publishes (mh_icp_wait does the same)
       const volatile unsigned int * flag =
           batch ? batch->host_seq() : reinterpret_cast<const volatile unsigned int *>(static_cast<const char *>(f->h_out) + photo_seq_offset(nf));
-      timespec t0;
-      clock_gettime(CLOCK_MONOTONIC, &t0);
-      for (unsigned spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != want; ++spins) {
-        __builtin_ia32_pause();
-        if ((spins & 1023u) == 1023u) {
-          timespec t1;
-          clock_gettime(CLOCK_MONOTONIC, &t1);
-          if ((t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec) > 20000000L) {  // 20 ms: fall back
-            need_sync = true;
-            break;
-          }
-        }
-      }
+      need_sync = !mh::spin_until([&] { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == want; }, 20000000L);  // 20 ms: fall back
     }
     if (need_sync) MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the end of the kernel makes its host writes visible
     const double * new_centers = static_cast<const double *>(f->h_out);

@@ -345,10 +345,7 @@ int wait_publish(mh_ctx * ctx, mh_shard_comm * comm, const unsigned int * flag_w
     clock_gettime(CLOCK_MONOTONIC, &t1);
     return (t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec);
   };
-  for (unsigned spins = 0; __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq; ++spins) {
-    __builtin_ia32_pause();
-    if ((spins & 1023u) != 1023u) continue;
-    if (elapsed_ns() < 50000000L) continue;
+  if (!mh::spin_until([&] { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq; }, 50000000L)) {
     // 50 ms: something is slow (a first call's channel set-up) or wrong (a peer is gone).  Stop burning the core; poll the
     // stream and, over RCCL, the communicator's asynchronous error state
     for (;;) {
@@ -373,7 +370,6 @@ int wait_publish(mh_ctx * ctx, mh_shard_comm * comm, const unsigned int * flag_w
       g_mh_err = comm->err;
       return MH_ERR_HIP;
     }
-    break;
   }
   return MH_OK;
 }
@@ -1115,7 +1111,7 @@ int enqueue_round(const RoundSpec * spec, size_t B)
     ShardCall & c = round.calls[f];
     const uint32_t bound = static_cast<uint32_t>(std::min<uint64_t>(S->slot_capacity, static_cast<uint64_t>(S->slots_bound) + c.arrivals_bound));
     icp->n = bound ? bound : 1;
-    rc = mhi::prepare(icp, c.R_src, c.t_src, c.has_tgt ? c.R_tgt : nullptr, c.has_tgt ? c.t_tgt : nullptr, c.g_unit, &scratch, false, ia[f], la[f]);
+    rc = mhi::prepare(icp, c.R_src, c.t_src, c.has_tgt ? c.R_tgt : nullptr, c.has_tgt ? c.t_tgt : nullptr, c.g_unit, &scratch, ia[f], la[f]);
     if (rc != MH_OK) return rc;
     c.pc = icp->pending[0];
     icp->n_pending = 0;  // the pending slot is not used: the call lives in the round
@@ -1125,10 +1121,8 @@ int enqueue_round(const RoundSpec * spec, size_t B)
     a.cold = S->cold_pending ? 1 : 0;  // (K3 still reads the status words: tombstones and held-back movers are marked there)
     round.calls[f].cold = S->cold_pending;
     S->cold_pending = false;
-    a.host_result = nullptr;
     a.seq = 0;
     a.shard_out = ar + f * mh::kShardArLen;
-    l.host_result = nullptr;
     l.seq = 0;
     l.sums = ar + f * mh::kShardArLen;  // the eigenbases of the GLOBAL H_rr / H_tt
     l.shard_out = loc + f * 16;
@@ -1136,43 +1130,31 @@ int enqueue_round(const RoundSpec * spec, size_t B)
   }
   // launch groups of the batched form: the factors that share a kernel instantiation (as mh_icp_linearize_batch), at most
   // kBatchInline per launch — the argument blocks ride in the kernel-argument segment, nothing is staged
-  struct Group
-  {
-    int tpb, k, n_off;
-    bool binary;
-    std::vector<size_t> members;
-  };
-  std::vector<Group> groups;
+  std::vector<LaunchGroup> groups;
   if (B > 1) {
     for (size_t f = 0; f < B; ++f) {
       const mh_icp * icp = spec[f].S->icp;
       const int tpb = mh::linearize_class(ia[f].n, ia[f].k, true), k = icp->cfg.num_corres_points == 5 ? 5 : 8, n_off = icp->map->n_off;
-      Group * g = nullptr;
-      for (Group & q : groups)
+      LaunchGroup * g = nullptr;
+      for (LaunchGroup & q : groups)
         if (q.tpb == tpb && q.k == k && q.n_off == n_off && q.binary == icp->binary && static_cast<int>(q.members.size()) < mh::kBatchInline) g = &q;
       if (!g) {
-        groups.push_back(Group{tpb, k, n_off, icp->binary, {}});
+        groups.push_back(LaunchGroup{tpb, k, n_off, icp->binary, {}});
         g = &groups.back();
       }
       g->members.push_back(f);
     }
   }
+  // (a map-sharded factor's K4 takes one chunk per workgroup: K3's grid serves both kernels)
+  auto grid_of = [&](const LaunchGroup & g) { return [&ia, &g](int i) { return mh::class_grid(ia[g.members[i]].n, g.tpb); }; };
   if (B == 1) {
     const hipError_t e = mh::launch_linearize(ia[0], spec[0].S->icp->binary, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch_linearize");
   } else {
-    for (const Group & g : groups) {
+    for (const LaunchGroup & g : groups) {
       mh::BatchInline<mh::IcpArgs> blk;
-      std::memset(static_cast<void *>(&blk), 0, sizeof(blk));
-      int acc = 0;
-      for (size_t i = 0; i < g.members.size(); ++i) {
-        blk.a[i] = ia[g.members[i]];
-        blk.start[i] = acc;
-        acc += mh::class_grid(ia[g.members[i]].n, g.tpb);
-      }
-      blk.start[g.members.size()] = acc;
-      blk.n = static_cast<int>(g.members.size());
-      const hipError_t e = mh::launch_linearize_batch_inline(blk, acc, g.tpb, g.k, g.n_off, g.binary, ctx->stream, true);
+      const int grid = mh::fill_batch_inline(blk, static_cast<int>(g.members.size()), [&](int i) -> const mh::IcpArgs & { return ia[g.members[i]]; }, grid_of(g));
+      const hipError_t e = mh::launch_linearize_batch_inline(blk, grid, g.tpb, g.k, g.n_off, g.binary, ctx->stream, true);
       if (e != hipSuccess) return hip_fail(ctx, e, "launch_linearize_batch_inline");
     }
   }
@@ -1183,18 +1165,10 @@ int enqueue_round(const RoundSpec * spec, size_t B)
       const hipError_t e = mh::launch_localizability(la[0], ctx->stream);
       if (e != hipSuccess) return hip_fail(ctx, e, "launch_localizability");
     } else {
-      for (const Group & g : groups) {
+      for (const LaunchGroup & g : groups) {
         mh::BatchInline<mh::LocArgs> blk;
-        std::memset(static_cast<void *>(&blk), 0, sizeof(blk));
-        int acc = 0;
-        for (size_t i = 0; i < g.members.size(); ++i) {
-          blk.a[i] = la[g.members[i]];
-          blk.start[i] = acc;
-          acc += mh::class_grid(ia[g.members[i]].n, g.tpb);
-        }
-        blk.start[g.members.size()] = acc;
-        blk.n = static_cast<int>(g.members.size());
-        const hipError_t e = mh::launch_localizability_batch_inline(blk, acc, g.tpb, ctx->stream, true);
+        const int grid = mh::fill_batch_inline(blk, static_cast<int>(g.members.size()), [&](int i) -> const mh::LocArgs & { return la[g.members[i]]; }, grid_of(g));
+        const hipError_t e = mh::launch_localizability_batch_inline(blk, grid, g.tpb, ctx->stream, true);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_localizability_batch_inline");
       }
     }
