@@ -319,6 +319,68 @@ int mh_icp_align(mh_icp * icp, const double R0[9], const double t0[3], const dou
 int mh_icp_align_async(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3],
                        const mh_icp_align_config * cfg, mh_icp_align_result * out);
 
+/* ---- fixed-lag window: the smoother's Gauss-Newton loop on the device ---------------------------
+ * W unary factors, one pose each, tied by between factors and a prior on the oldest pose: what a caller otherwise writes
+ * around mh_icp_linearize_batch — one blocking batch call, a 6W x 6W system assembled and solved on the host, W retractions,
+ * again — runs as ONE chain of launches on the context's stream.  Per iteration: the window's K3 batch launches (component
+ * pass off; launch groups and launch classes chosen as mh_icp_linearize_batch chooses them for the same window) and a
+ * one-workgroup step kernel, which does the host epilogue's part of the work for every factor, assembles
+ *   A = blockdiag(H_ss,i) + sum_i J_i^T diag(between_info) J_i + diag(prior_info) on pose 0 + damping I,   g likewise,
+ * with the between factor Z_i of poses i - 1, i (where has_Z[i] != 0; has_Z[0] is ignored): residual
+ * [Log(Z.R^T R_ab), Z.R^T (t_ab - Z.t)], T_ab = T_{i-1}^-1 T_i, J_a = -Ad(T_ab^-1), J_b = I; solves A xi = -g (block
+ * tridiagonal L D L^T with residual refinement), retracts every pose (R <- R Exp(xi_r), t <- t + R xi_t) and writes the poses
+ * into the argument blocks of the next iteration's launches.  The host waits once (or once per `check_every` iterations).
+ * Every factor's step uses exactly the H_ss, b_s that mh_icp_linearize returns at its pose (4-DoF projection and the
+ * degeneracy quirk included).  A system without a positive pivot takes no step and ends the call: MH_OK, converged = 0, the
+ * poses of that iteration unchanged, bit 4 in the trace row.
+ * Factors: 1 .. MH_WINDOW_MAX, unary, unsharded, of one context, each at most once, none with a call in flight; an empty
+ * factor is allowed and contributes nothing.  One window call per context at a time.  The per-point association state
+ * evolves as under repeated mh_icp_linearize_batch calls and is left as the last EVALUATED poses left it; every factor's
+ * linearize count advances by `iters` (the executed ones).  Until the call has been waited for, mh_icp_reset, mh_icp_linearize*,
+ * mh_icp_align* and mh_icp_wait refuse its factors.  Bad arguments: MH_ERR_INVALID_ARG / MH_ERR_UNSUPPORTED, nothing
+ * enqueued, the handles unchanged. */
+#define MH_WINDOW_MAX 16
+
+typedef struct mh_icp_window_config {
+  int32_t iters;               /* 1 .. 64 iterations queued */
+  int32_t check_every;         /* iterations queued per host look at the stop flag; 0 = all at once.  The result does not
+                                  depend on it (mh_icp_window_optimise_async always queues everything) */
+  double between_info[6];      /* diagonal weights of every between factor, (rotation, translation) order: 1 / sigma^2 */
+  double prior_info[6];        /* on the diagonal of the oldest pose (0 = none), pulling towards the step's own pose */
+  double damping;              /* >= 0, added to every diagonal entry */
+  double eps_rot, eps_trans;   /* rad, m: stop when EVERY pose's step norms fall below (0 = never: a fixed iteration count) */
+} mh_icp_window_config;
+
+typedef struct mh_icp_window_trace {
+  double f;                    /* cost at the poses the iteration evaluated: the factors' f plus the between terms */
+  double step_rot, step_trans; /* max over the poses of |xi_r|, |xi_t| */
+  int32_t flags;               /* 4: singular system (no step; the call ends here) */
+  uint32_t degenerate;         /* 2 bits per pose: 1 a rotation direction of its factor below the threshold, 2 a translation one */
+} mh_icp_window_trace;
+
+typedef struct mh_icp_window_result {
+  double R[MH_WINDOW_MAX * 9], t[MH_WINDOW_MAX * 3]; /* the final poses, W used */
+  int32_t iters, converged;
+  int32_t n_poses, reserved;
+  mh_icp_window_trace trace[64];     /* one row per executed iteration */
+  mh_icp_result first[MH_WINDOW_MAX], last[MH_WINDOW_MAX]; /* per factor: what mh_icp_linearize (components off) returns at the
+                                        initial and at the last evaluated pose */
+} mh_icp_window_result;
+
+/* R[9 W], t[3 W]: the initial poses, oldest first; has_Z[W], Z_R[9 W], Z_t[3 W]: the between measurements (entry i ties poses
+ * i - 1 and i; Z_R / Z_t may be NULL when no has_Z is set); g_unit[3]: the gravity direction every factor reads.
+ * trace_poses: NULL, or cfg->iters x W x 12 doubles the caller owns — the poses (R row-major, then t) after every executed
+ * step; rows of iterations that were not executed are left untouched.  Blocks until the result is on the host. */
+int mh_icp_window_optimise(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                           const double * Z_R, const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg,
+                           mh_icp_window_result * out, double * trace_poses);
+/* The same without waiting: *out and trace_poses (which must stay valid) are filled when mh_icp_window_wait(ctx) returns, ctx
+ * being the factors' context.  No other call on the factors until then. */
+int mh_icp_window_optimise_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                 const double * Z_R, const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg,
+                                 mh_icp_window_result * out, double * trace_poses);
+int mh_icp_window_wait(mh_ctx * ctx);
+
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals
  * unique_ns[g] gets p <- R_g p + t_g in float (no FMA, Eigen's evaluation order).  Rt12 = n_groups x

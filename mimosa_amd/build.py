@@ -33,8 +33,9 @@ SOURCES = [
     ("radar_kernels.hip", ["-ffp-contract=off"]),
     ("radar_api.hip", []),
     ("align_kernels.hip", ["-ffp-contract=off"]),  # the host build of align_device.hpp (tests/cpp/align_step.cpp) gives the same digits
+    ("window_kernels.hip", ["-ffp-contract=off"]),  # likewise window_device.hpp (tests/cpp/window_step.cpp)
 ]
-HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
+HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "window_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
 
 
 def _hipcc() -> str:
@@ -178,6 +179,7 @@ def build_replay_native(force: bool = False) -> str:
 HOST_TESTS = {
     "align_step": ("align_step.cpp", ["align_device.hpp", "math3.hpp"]),
     "flagged_word": ("flagged_word.cpp", ["flagged_word.hpp"]),
+    "window_step": ("window_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
 }
 
 

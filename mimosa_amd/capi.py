@@ -25,6 +25,7 @@ EXPORTS = [
     "mh_icp_create", "mh_icp_clone", "mh_icp_destroy", "mh_icp_linearize", "mh_icp_linearize_async",
     "mh_icp_wait", "mh_icp_linearize_batch", "mh_icp_get_state", "mh_icp_reset", "mh_icp_set_components", "mh_icp_size",
     "mh_icp_align", "mh_icp_align_async",
+    "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
     "mh_deskew", "mh_transform_f32",
     "mh_scan_create", "mh_scan_destroy", "mh_scan_prepare_input", "mh_scan_prepare_input_device", "mh_scan_prefetch", "mh_scan_prepare_input_prefetched", "mh_scan_prepare_input_layout", "mh_scan_get_unique_ns", "mh_scan_deskew",
     "mh_scan_deskew_imu", "mh_scan_get_deskew_poses", "mh_photo_preprocess_scan_resident", "mh_photo_preprocess_scan_begin_resident",
@@ -139,6 +140,46 @@ class AlignResult(C.Structure):
 def make_align_config(max_iters=10, eps_rot=1e-6, eps_trans=1e-6, damping=0.0, prior_sigma_rot=0.0, prior_sigma_trans=0.0,
                       check_every=0) -> AlignConfig:
     return AlignConfig(max_iters, eps_rot, eps_trans, damping, prior_sigma_rot, prior_sigma_trans, check_every)
+
+
+MH_WINDOW_MAX = 16
+
+
+class WindowConfig(C.Structure):
+    """mh_icp_window_config"""
+    _fields_ = [("iters", C.c_int32), ("check_every", C.c_int32), ("between_info", C.c_double * 6), ("prior_info", C.c_double * 6),
+                ("damping", C.c_double), ("eps_rot", C.c_double), ("eps_trans", C.c_double)]
+
+
+class WindowTrace(C.Structure):
+    """mh_icp_window_trace"""
+    _fields_ = [("f", C.c_double), ("step_rot", C.c_double), ("step_trans", C.c_double), ("flags", C.c_int32), ("degenerate", C.c_uint32)]
+
+
+class WindowResult(C.Structure):
+    """mh_icp_window_result"""
+    _fields_ = [("R", C.c_double * (9 * MH_WINDOW_MAX)), ("t", C.c_double * (3 * MH_WINDOW_MAX)), ("iters", C.c_int32), ("converged", C.c_int32),
+                ("n_poses", C.c_int32), ("reserved", C.c_int32), ("trace", WindowTrace * 64), ("first", IcpResult * MH_WINDOW_MAX),
+                ("last", IcpResult * MH_WINDOW_MAX)]
+
+    def as_dict(self):
+        n, W = int(self.iters), int(self.n_poses)
+        return {
+            "R": np.array(self.R).reshape(MH_WINDOW_MAX, 3, 3)[:W], "t": np.array(self.t).reshape(MH_WINDOW_MAX, 3)[:W], "iters": n,
+            "converged": int(self.converged),
+            "trace": [{"f": r.f, "step_rot": r.step_rot, "step_trans": r.step_trans, "flags": int(r.flags), "degenerate": int(r.degenerate)}
+                      for r in (self.trace[i] for i in range(n))],
+            "first": [self.first[i].as_dict() for i in range(W)], "last": [self.last[i].as_dict() for i in range(W)],
+        }
+
+
+def make_window_config(iters=6, between_sigma_rot=2e-3, between_sigma_trans=1e-2, prior_sigma_rot=1e-4, prior_sigma_trans=1e-4, damping=1e-9,
+                       eps_rot=0.0, eps_trans=0.0, check_every=0, between_info=None, prior_info=None) -> WindowConfig:
+    """the defaults are the replay's smoother: six fixed iterations, its between sigmas, the tight prior marginalisation leaves"""
+    bi = [1.0 / between_sigma_rot ** 2] * 3 + [1.0 / between_sigma_trans ** 2] * 3 if between_info is None else list(between_info)
+    pi = ([1.0 / prior_sigma_rot ** 2 if prior_sigma_rot > 0 else 0.0] * 3 + [1.0 / prior_sigma_trans ** 2 if prior_sigma_trans > 0 else 0.0] * 3
+          if prior_info is None else list(prior_info))
+    return WindowConfig(iters, check_every, (C.c_double * 6)(*bi), (C.c_double * 6)(*pi), damping, eps_rot, eps_trans)
 
 
 class ShardConfig(C.Structure):
@@ -469,6 +510,9 @@ def load(build_if_missing: bool = True):
     L.mh_icp_size.argtypes = [vp]
     L.mh_icp_align.argtypes = [vp, vp, vp, vp, C.POINTER(AlignConfig), C.POINTER(AlignResult)]
     L.mh_icp_align_async.argtypes = [vp, vp, vp, vp, C.POINTER(AlignConfig), C.POINTER(AlignResult)]
+    L.mh_icp_window_optimise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
+    L.mh_icp_window_optimise_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
+    L.mh_icp_window_wait.argtypes = [vp]
     L.mh_icp_size.restype = sz
     L.mh_deskew.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
     L.mh_transform_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -833,6 +877,50 @@ def linearize_batch(factors, Rs, ts, g_units=None, R_tgts=None, t_tgts=None) -> 
     out = (IcpResult * n)()
     ctx.check(ctx.L.mh_icp_linearize_batch(handles, n, _p(R), _p(t), _p(Rt), _p(tt), _p(g), out))
     return [out[i].as_dict() for i in range(n)]
+
+
+class WindowCall:
+    """an mh_icp_window_optimise_async call in flight: wait() collects it and returns the result"""
+
+    def __init__(self, ctx, keep, out, trace):
+        self.ctx, self._keep, self.out, self.trace = ctx, keep, out, trace
+
+    def wait(self) -> dict:
+        self.ctx.check(self.ctx.L.mh_icp_window_wait(self.ctx.h))
+        d = self.out.as_dict()
+        if self.trace is not None:
+            d["poses"] = self.trace[:d["iters"]]
+        self._keep = None
+        return d
+
+
+def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), trace_poses=False, wait=True):
+    """mh_icp_window_optimise: the fixed-lag Gauss-Newton loop over `factors` (oldest first) as one chain of launches.
+    poses: (R, t) per factor; Z: (R, t) per factor, entry i the measured T_{i-1}^-1 T_i where has_Z[i] (entry 0 unused).
+    trace_poses: also return "poses", (iters, W, 12) — R row-major then t after every executed step.
+    wait=False: mh_icp_window_optimise_async; returns a WindowCall whose wait() gives the same dict."""
+    W = len(factors)
+    ctx = factors[0].ctx
+    R = np.ascontiguousarray(np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses]))
+    t = np.ascontiguousarray(np.array([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
+    hz = np.zeros(W, np.int32) if has_Z is None else np.ascontiguousarray(np.asarray(has_Z).astype(np.int32))
+    ZR = Zt = None
+    if Z is not None:
+        ZR = np.ascontiguousarray(np.array([np.asarray(z[0], np.float64).reshape(9) for z in Z]))
+        Zt = np.ascontiguousarray(np.array([np.asarray(z[1], np.float64).reshape(3) for z in Z]))
+    g = _f64(g_unit)
+    handles = (C.c_void_p * W)(*[f.h for f in factors])
+    out = WindowResult()
+    trace = np.full((int(cfg.iters), W, 12), np.nan) if trace_poses else None
+    args = (handles, W, _p(R), _p(t), _p(hz), _p(ZR), _p(Zt), _p(g), C.byref(cfg), C.byref(out), _p(trace))
+    if not wait:
+        ctx.check(ctx.L.mh_icp_window_optimise_async(*args))
+        return WindowCall(ctx, (handles, R, t, hz, ZR, Zt, g, cfg), out, trace)
+    ctx.check(ctx.L.mh_icp_window_optimise(*args))
+    d = out.as_dict()
+    if trace is not None:
+        d["poses"] = trace[:d["iters"]]
+    return d
 
 
 class ICPFactor:

@@ -22,6 +22,7 @@
 #include <atomic>
 
 #include "align_device.hpp"
+#include "window_device.hpp"
 #include "icp_device.hpp"
 #include "map_device.hpp"
 #include "scan_device.hpp"
@@ -30,6 +31,29 @@
 inline thread_local std::string g_mh_err;
 constexpr int kMaxPending = 64;
 constexpr int kMaxBatch = 64;  // factors per mh_icp_linearize_batch call
+
+// mh_icp_window_optimise: the call in flight on a context (at most one).  Its argument blocks, grid prefixes, state and K3's
+// landing slots live in device memory the context owns (d_window), their pinned staging in h_window, the rows the step
+// kernel publishes in mapped pinned memory (h_window_rows).
+struct WindowLaunch
+{
+  int tpb, k, n_off, first, n, grid;  // one staged K3 launch per iteration: class, kernel path, its first slot and members, its grid
+};
+struct WindowCall
+{
+  bool active = false;
+  int W = 0, iters = 0, queued = 0, n_slots = 0;
+  mh_icp * icps[mh::kWindowMax];
+  int slot[mh::kWindowMax];  // pose i's argument block within an iteration (-1: empty factor)
+  int count0[mh::kWindowMax];
+  double R0[mh::kWindowMax][9];
+  double gz[3];
+  unsigned int seq[64];
+  mh::WindowParams p;
+  std::vector<WindowLaunch> launches;
+  mh_icp_window_result * out = nullptr;
+  double * trace_poses = nullptr;
+};
 
 struct mh_ctx
 {
@@ -43,6 +67,11 @@ struct mh_ctx
   void * d_batch = nullptr;  // ... and the device copy the batched kernels read
   void * d_scratch = nullptr;  // stream-ordered scratch of factor creation (source ordering): reused, never freed per call
   size_t d_scratch_cap = 0;
+  void * h_window = nullptr;       // mh_icp_window_optimise: pinned staging of the chain's block
+  void * d_window = nullptr;       // ... the block itself
+  uint4 * h_window_rows = nullptr; // ... the rows of its iterations (mapped pinned), and their device-side address
+  uint4 * d_window_rows = nullptr;
+  WindowCall window;
   hipStream_t copy_stream = nullptr;  // mh_scan_prefetch: uploads beside the compute stream (created on first use: an HSA queue costs ~1 ms)
   std::mutex copy_mu;
   // what mh_shutdown takes back from the sharded handles (shard_api.hip): the sharded factors created on this context, and
@@ -664,7 +693,19 @@ struct mh_icp
     unsigned int seq[kMaxPending];
     mh::AlignParams p;
   } align;
+  bool in_window = false;  // held by the mh_icp_window_optimise call in flight on its context (which also holds the whole ring)
 };
+
+// The window call on ctx is over (collected, or abandoned behind a drained stream): its factors are free again.
+inline void window_release(mh_ctx * ctx)
+{
+  WindowCall & c = ctx->window;
+  for (int i = 0; i < c.W; ++i) {
+    c.icps[i]->in_window = false;
+    c.icps[i]->n_pending = 0;
+  }
+  c.active = false;
+}
 
 // The factors of a window that share a kernel instantiation — launch class, k == 5 or the generic k <= 8 path, neighbour mode,
 // unary / binary: one batched K3 (+ one K4) launch (mh_icp_linearize_batch, mh_shard_icp_linearize_batch).

@@ -592,6 +592,71 @@ public:
     return out;
   }
 
+  // The smoother's loop over a window of unary factors (no counterpart in the reference, which leaves it to ISAM2): linearize
+  // every factor, assemble the block-tridiagonal system of the factors, the between factors and the prior on the oldest pose,
+  // solve, retract every pose — as one chain of launches on the device, one wait (mh_icp_window_optimise).
+  struct WindowConfig
+  {
+    int iters = 6;
+    double between_info[6] = {0, 0, 0, 0, 0, 0}, prior_info[6] = {0, 0, 0, 0, 0, 0};
+    double damping = 1e-9, eps_rot = 0.0, eps_trans = 0.0;
+    int check_every = 0;
+  };
+  struct WindowBetween
+  {
+    bool present = false;
+    Pose3 Z;  // the measured T_{i-1}^-1 T_i
+  };
+  struct WindowResult
+  {
+    std::vector<Pose3> poses;
+    int iters = 0;
+    bool converged = false;
+    std::vector<mh_icp_window_trace> trace;  // one row per executed iteration
+  };
+  // a call in flight (optimiseWindowAsync): wait() collects it
+  class WindowCall
+  {
+  public:
+    WindowResult wait()
+    {
+      factors_[0]->ctx().check(mh_icp_window_wait(factors_[0]->ctx().get()), "mh_icp_window_wait");
+      return finish();
+    }
+
+  private:
+    friend class ICPFactor;
+    WindowResult finish()
+    {
+      WindowResult out;
+      out.iters = r_->iters;
+      out.converged = r_->converged != 0;
+      out.trace.assign(r_->trace, r_->trace + r_->iters);
+      for (size_t i = 0; i < factors_.size(); ++i) {
+        out.poses.push_back(pose3(r_->R + 9 * i, r_->t + 3 * i));
+        factors_[i]->last_ = r_->last[i];
+      }
+      return out;
+    }
+    std::vector<Ptr> factors_;
+    std::vector<mh_icp *> h_;
+    std::vector<double> R_, t_, ZR_, Zt_;
+    std::vector<int32_t> has_Z_;
+    A3 g_{};
+    mh_icp_window_config c_{};
+    std::unique_ptr<mh_icp_window_result> r_;
+  };
+  static WindowResult optimiseWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
+                                     const Unit3 & g, const WindowConfig & config)
+  {
+    return startWindow(factors, poses, between, g, config, true)->finish();
+  }
+  static std::unique_ptr<WindowCall> optimiseWindowAsync(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses,
+                                                         const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config)
+  {
+    return startWindow(factors, poses, between, g, config, false);
+  }
+
   // getters, :48-72
   std::vector<RejectStatus> getStatuses() const
   {
@@ -658,6 +723,46 @@ private:
                 "mh_icp_create");
   }
   const Context & ctx() const { return *ivox_target_->context(); }
+  static std::unique_ptr<WindowCall> startWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
+                                                 const Unit3 & g, const WindowConfig & config, bool blocking)
+  {
+    const size_t n = factors.size();
+    if (!n || poses.size() != n || between.size() != n) throw std::runtime_error("ICPFactor::optimiseWindow: one pose and one between entry per factor");
+    std::unique_ptr<WindowCall> w(new WindowCall);
+    w->factors_ = factors;
+    w->h_.resize(n);
+    w->R_.resize(9 * n);
+    w->t_.resize(3 * n);
+    w->ZR_.assign(9 * n, 0.0);
+    w->Zt_.assign(3 * n, 0.0);
+    w->has_Z_.assign(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+      if (factors[i]->is_binary_) throw std::runtime_error("ICPFactor::optimiseWindow: unary factors only");
+      w->h_[i] = factors[i]->icp_;
+      const PoseRM T = rowMajor(poses[i]);
+      std::memcpy(&w->R_[9 * i], T.R.data(), 72);
+      std::memcpy(&w->t_[3 * i], T.t.data(), 24);
+      if (i && between[i].present) {
+        const PoseRM Z = rowMajor(between[i].Z);
+        std::memcpy(&w->ZR_[9 * i], Z.R.data(), 72);
+        std::memcpy(&w->Zt_[3 * i], Z.t.data(), 24);
+        w->has_Z_[i] = 1;
+      }
+    }
+    w->g_ = toArray(g.unitVector());
+    w->c_.iters = config.iters;
+    w->c_.check_every = config.check_every;
+    std::memcpy(w->c_.between_info, config.between_info, sizeof(config.between_info));
+    std::memcpy(w->c_.prior_info, config.prior_info, sizeof(config.prior_info));
+    w->c_.damping = config.damping;
+    w->c_.eps_rot = config.eps_rot;
+    w->c_.eps_trans = config.eps_trans;
+    w->r_.reset(new mh_icp_window_result);
+    const auto fn = blocking ? mh_icp_window_optimise : mh_icp_window_optimise_async;
+    factors[0]->ctx().check(fn(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_, w->r_.get(), nullptr),
+                            blocking ? "mh_icp_window_optimise" : "mh_icp_window_optimise_async");
+    return w;
+  }
 
   const bool is_binary_;
   IncrementalVoxelMapPCL::Ptr ivox_target_;

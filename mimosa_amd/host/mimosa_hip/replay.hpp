@@ -246,6 +246,11 @@ struct Config
   // device, from the propagated first guess) before its factor goes to the smoother.
   bool init_align = false;
   int init_align_iters = 10;
+  // FixedLagReplay without the photometric factor only: the smoother's update_iters Gauss-Newton iterations run as ONE chain of
+  // launches on the device (ICPFactor::optimiseWindow: linearize, assembly, block-tridiagonal solve, retraction) instead of one
+  // blocking linearizeBatch, a dense host solve and the retractions per iteration.  The device's solve is refined, the host's is
+  // a plain elimination, and acos / sin are the device's: the trajectory agrees to ~1e-10 m, not bit for bit.
+  bool device_window = false;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
   lidar::ManagerInputConfig input = lidar::defaultManagerInputConfig();
@@ -388,6 +393,8 @@ public:
   void clear() { win.clear(); }
   // on: optimise() re-linearizes the photometric factors the window's entries carry (Live::pf) instead of `pf`
   void setPhotoWindow(bool on) { photo_window_ = on; }
+  // on: optimise() hands the whole loop to the device (FactorT::optimiseWindow); no photometric factor may be in play
+  void setDeviceWindow(bool on) { device_window_ = on; }
   size_t photoFactorsInWindow() const
   {
     size_t n = 0;
@@ -404,6 +411,7 @@ public:
     } cfg_{window_, update_iters_};
       const size_t nW = win.size(), dim = 6 * nW;
       std::vector<double> fs;
+      if (device_window_) return optimiseOnDevice(k, pf);
       for (int it = 0; it < cfg_.update_iters; ++it) {
         std::vector<typename FactorT::Ptr> factors(nW);
         Values v;
@@ -507,6 +515,49 @@ public:
   std::deque<Live> win;
 
 private:
+  // optimise() as one call: the same factors, between factors, prior and damping, a fixed update_iters iterations
+  std::vector<double> optimiseOnDevice(const size_t k, const PhotometricFactor::Ptr & pf)
+  {
+    if constexpr (std::is_same<FactorT, ICPFactor>::value) {
+      if (pf || (photo_window_ && photoFactorsInWindow())) throw std::runtime_error("replay: device_window takes no photometric factor");
+      const size_t nW = win.size();
+      std::vector<typename FactorT::Ptr> factors(nW);
+      std::vector<Pose3> poses(nW);
+      std::vector<ICPFactor::WindowBetween> between(nW);
+      for (size_t i = 0; i < nW; ++i) {
+        factors[i] = win[i].f;
+        poses[i] = toPose3(win[i].T);
+        between[i].present = i > 0 && win[i].has_Z;
+        if (between[i].present) between[i].Z = toPose3(win[i].Z);
+      }
+      ICPFactor::WindowConfig wc;
+      wc.iters = update_iters_;
+      const bool loose = win[0].k == first_k_ && static_cast<int>(k - first_k_) < window_;
+      const double sr = loose ? 0.017453292519943295 : 1e-4, st = loose ? 0.1 : 1e-4;
+      for (int p = 0; p < 3; ++p) {
+        wc.between_info[p] = Wb_[p];
+        wc.between_info[3 + p] = Wb_[3 + p];
+        wc.prior_info[p] = 1.0 / (sr * sr);
+        wc.prior_info[3 + p] = 1.0 / (st * st);
+      }
+      wc.damping = 1e-9;
+      const ICPFactor::WindowResult r = ICPFactor::optimiseWindow(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc);
+      if (r.iters != update_iters_) throw std::runtime_error("replay::solve: singular system");
+      std::vector<double> fs;
+      for (size_t i = 0; i < nW; ++i) {
+        const PoseRM T = rowMajor(r.poses[i]);
+        win[i].T.R = T.R;
+        win[i].T.t = T.t;
+      }
+      for (const mh_icp_window_trace & tr : r.trace) fs.push_back(tr.f);
+      return fs;
+    } else {
+      (void)k;
+      (void)pf;
+      throw std::runtime_error("replay: device_window is offered for lidar::ICPFactor only");
+    }
+  }
+  bool device_window_ = false;
   int window_, update_iters_;
   double Wb_[6];
   size_t first_k_ = 0;
@@ -575,6 +626,8 @@ public:
     using Live = typename Smoother::Live;
     Smoother smoother(cfg_.window, cfg_.update_iters, cfg_.between_sigma_rot, cfg_.between_sigma_trans);
     smoother.setPhotoWindow(cfg_.photo_window);
+    if (cfg_.device_window && cfg_.photometric) throw std::runtime_error("replay: device_window is not offered with the photometric factor enabled");
+    smoother.setDeviceWindow(cfg_.device_window);
     std::deque<Live> & win = smoother.win;
     std::vector<RT> kf_poses;
     State prev = state0;
@@ -937,6 +990,7 @@ public:
   ManagerReplay(const std::shared_ptr<lidar::Context> & ctx, const Config & cfg, size_t lru_horizon = 1000) : ctx_(ctx), cfg_(cfg), imu_(cfg.gravity)
   {
     if (cfg.photo_window) throw std::runtime_error("ManagerReplay: photo_window is not offered through lidar::Manager (FixedLagReplay only)");
+    if (cfg.device_window) throw std::runtime_error("ManagerReplay: device_window is not offered through lidar::Manager (FixedLagReplay only)");
     if (cfg.init_align) throw std::runtime_error("ManagerReplay: init_align is not offered through lidar::Manager (FixedLagReplay only)");
     lidar::ManagerConfig mc;
     mc.range_min = cfg.input.range_min;

@@ -65,6 +65,7 @@ public:
   : FixedLagReplayT<ShardedGeometric>(comm->context(), cfg, std::unique_ptr<ShardedGeometric>(new ShardedGeometric(comm, cfg, lru_horizon, block_log2, force_collectives)))
   {
     if (cfg.photo_window) throw std::runtime_error("ShardedFixedLagReplay: photo_window is not offered by the sharded replay");
+    if (cfg.device_window) throw std::runtime_error("ShardedFixedLagReplay: device_window is not offered by the sharded replay");
   }
 };
 

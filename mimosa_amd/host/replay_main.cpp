@@ -1,7 +1,9 @@
 // Native sequence replay: drives mimosa_hip::replay::FixedLagReplay (host/mimosa_hip/replay.hpp) on an input file written
 // by mimosa_amd/replay.py:write_native_input and prints one JSON object (estimated poses, per-stage seconds, scans/s).
-//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-poses]
+//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window] [device-poses]
 //     device-poses (last word): replay::Config::device_poses — the per-timestamp deskew poses are computed on the device
+//     device-window (in front of it): replay::Config::device_window — the smoother's iterations run as one chain of launches on
+//       the device (FixedLagReplay without the photometric factor; refused elsewhere)
 //     repeats > 1: the whole sequence again, timing of the last pass is reported
 //     sharded <world>: the map sharded over <world> ranks INSIDE this process (one host thread and one context each, in-process
 //       transport: what a one-GPU box can run); sharded-rccl: this process is one rank of a torch.distributed.run-style launch
@@ -20,11 +22,13 @@ using binio::read_vec;
 int main(int argc, char ** argv)
 {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-poses]\n");
+    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window] [device-poses]\n");
     return 2;
   }
   const bool device_poses = argc > 2 && std::string(argv[argc - 1]) == "device-poses";
   if (device_poses) --argc;
+  const bool device_window = argc > 2 && std::string(argv[argc - 1]) == "device-window";
+  if (device_window) --argc;
   const int repeats = argc > 2 ? std::atoi(argv[2]) : 1;
   const bool through_manager = argc > 3 && std::string(argv[3]) == "manager";  // the same sequence through lidar::Manager::callback
   const bool sequential = argc > 3 && std::string(argv[3]) == "sequential";   // FixedLagReplay without the cross-scan overlap
@@ -58,6 +62,7 @@ int main(int argc, char ** argv)
     if (cfg.photometric) cfg.photo = binio::read_photo_config(f);
     cfg.pipeline = !sequential;
     cfg.device_poses = device_poses;
+    cfg.device_window = device_window;
     const auto bias = read_vec<double>(f);
     for (size_t i = 0; i + 2 < bias.size(); i += 3) cfg.bias_directions.push_back(V3D(bias[i], bias[i + 1], bias[i + 2]));
     const auto seed = read_vec<float>(f);

@@ -70,6 +70,10 @@ class ReplayConfig:
     # propagated first guess) before its factor goes to the smoother.  HIP backend and the native FixedLagReplay only
     init_align: bool = False
     init_align_iters: int = 10
+    # the smoother's update_iters iterations run as ONE chain of launches on the device (mh_icp_window_optimise: linearize,
+    # assembly, block-tridiagonal solve, retraction) instead of a batched linearize, a numpy solve and the retractions per
+    # iteration.  Without the photometric factor only; HIP backend and the native FixedLagReplay
+    device_window: bool = False
     reg: dict = field(default_factory=synth.enwide_config)
     photo: dict = None
 
@@ -269,6 +273,15 @@ class HipBackend:
         rs = self.capi.linearize_batch(factors, [p[0] for p in poses], [p[1] for p in poses])
         return [(np.asarray(r["H_ss"]).reshape(6, 6), np.asarray(r["b_s"]), float(r["f"])) for r in rs]
 
+    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping):
+        """device_window: the smoother's loop over the window as one call; the poses after it and the cost before each iteration"""
+        cfg = self.capi.make_window_config(iters=iters, between_info=between_info, prior_info=prior_info, damping=damping)
+        I3, z3 = np.eye(3), np.zeros(3)
+        r = self.capi.optimise_window(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs])
+        if r["iters"] != iters:
+            raise np.linalg.LinAlgError("Singular matrix")
+        return [(r["R"][i], r["t"][i]) for i in range(len(factors))], [row["f"] for row in r["trace"]]
+
     def linearize_photo(self, pf, R, t):
         r = pf.linearize(R, t)
         return np.asarray(r["H_bb"]).reshape(6, 6), np.asarray(r["b_b"]), float(r["f"]), int(r["status_hist"][8])
@@ -372,6 +385,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
         mode = ["sharded", str(sharded_world)]
     if sharded_rccl:
         mode = ["sharded-rccl"]
+    if cfg.device_window:
+        mode = mode + ["device-window"]
     if cfg.device_poses:
         mode = mode + ["device-poses"]
     out = subprocess.run([exe, path, str(repeats)] + mode, capture_output=True, text=True, timeout=timeout, env=env)
@@ -390,6 +405,10 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     scans = scans if scans is not None else make_scans(cfg)
     if cfg.device_poses and not hasattr(backend, "deskew_imu_and_preprocess"):
         raise ValueError("device_poses needs a backend that keeps the pose table on the device (HipBackend)")
+    if cfg.device_window and cfg.photometric:
+        raise ValueError("device_window is not offered with the photometric factor enabled")
+    if cfg.device_window and not hasattr(backend, "optimise_window"):
+        raise ValueError("device_window needs a backend with mh_icp_window_optimise (HipBackend)")
     if cfg.init_align and not hasattr(backend, "align_first"):
         raise ValueError("init_align needs a backend with mh_icp_align (HipBackend)")
     backend.seed_map(synth.make_room(synth.BASE_SEED, 0, 0, room=np.asarray(cfg.room)))
@@ -443,55 +462,63 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         # ---- smoother update: every live factor re-linearized per iteration -------------------------------------
         nW = len(win)
         fs = []
-        for it in range(cfg.update_iters):
-            lin = backend.linearize_window([w["f"] for w in win], [(w["R"], w["t"]) for w in win])
-            A = np.zeros((6 * nW, 6 * nW))
-            g = np.zeros(6 * nW)
-            cost = 0.0
-            for i, (H, b, fv) in enumerate(lin):
-                A[6 * i:6 * i + 6, 6 * i:6 * i + 6] += H
-                g[6 * i:6 * i + 6] += b
-                cost += fv
-            if cfg.photo_window:
-                at = [i for i, w in enumerate(win) if w["pf"] is not None]
-                pfs, poses = [win[i]["pf"] for i in at], [(win[i]["R"], win[i]["t"]) for i in at]
-                if not at:
-                    plin = []
-                elif hasattr(backend, "linearize_photo_window"):
-                    plin = backend.linearize_photo_window(pfs, poses)
-                else:
-                    plin = [backend.linearize_photo(p, R_, t_) for p, (R_, t_) in zip(pfs, poses)]
-            else:
-                at = [nW - 1] if pf is not None else []
-                plin = [backend.linearize_photo(pf, win[-1]["R"], win[-1]["t"])] if pf is not None else []
-            for i, (Hp, bp, fp, nv) in zip(at, plin):
-                if nv and np.all(np.isfinite(Hp)) and np.all(np.isfinite(bp)):
-                    A[6 * i:6 * i + 6, 6 * i:6 * i + 6] += Hp
-                    g[6 * i:6 * i + 6] += bp
-                    cost += fp
-            for i in range(1, nW):
-                if win[i]["Z"] is None:
-                    continue
-                Rz, tz = win[i]["Z"]
-                Rab, tab = _between(win[i - 1]["R"], win[i - 1]["t"], win[i]["R"], win[i]["t"])
-                Re, te = Rz.T @ Rab, Rz.T @ (tab - tz)                     # Z^-1 * between(X_{i-1}, X_i)
-                r = np.concatenate([_so3_log(Re), te])
-                Jb = np.eye(6)
-                Ja = -_adjoint(Rab.T, -Rab.T @ tab)                         # -Ad(between^-1)
-                J = np.zeros((6, 6 * nW))
-                J[:, 6 * (i - 1):6 * i] = Ja
-                J[:, 6 * i:6 * i + 6] = Jb
-                A += J.T @ Wb @ J
-                g += J.T @ Wb @ r
-                cost += float(r @ Wb @ r)
-            # what marginalisation leaves on the oldest pose; loose while that pose has never been optimised
+        if cfg.device_window:
             loose = win[0]["k"] == 0 and k < cfg.window
             sr, st = (np.deg2rad(1.0), 0.1) if loose else (1e-4, 1e-4)
-            A[:6, :6] += np.diag([1.0 / sr**2] * 3 + [1.0 / st**2] * 3)
-            xi = np.linalg.solve(A + 1e-9 * np.eye(6 * nW), -g)
-            for i, w in enumerate(win):
-                w["R"], w["t"] = _retract(w["R"], w["t"], xi[6 * i:6 * i + 6])
-            fs.append(cost)
+            new_poses, fs = backend.optimise_window([w["f"] for w in win], [(w["R"], w["t"]) for w in win], [None] + [w["Z"] for w in win[1:]],
+                                                    cfg.update_iters, list(np.diag(Wb)), [1.0 / sr**2] * 3 + [1.0 / st**2] * 3, 1e-9)
+            for w, (R_n, t_n) in zip(win, new_poses):
+                w["R"], w["t"] = R_n, t_n
+        else:
+            for it in range(cfg.update_iters):
+                lin = backend.linearize_window([w["f"] for w in win], [(w["R"], w["t"]) for w in win])
+                A = np.zeros((6 * nW, 6 * nW))
+                g = np.zeros(6 * nW)
+                cost = 0.0
+                for i, (H, b, fv) in enumerate(lin):
+                    A[6 * i:6 * i + 6, 6 * i:6 * i + 6] += H
+                    g[6 * i:6 * i + 6] += b
+                    cost += fv
+                if cfg.photo_window:
+                    at = [i for i, w in enumerate(win) if w["pf"] is not None]
+                    pfs, poses = [win[i]["pf"] for i in at], [(win[i]["R"], win[i]["t"]) for i in at]
+                    if not at:
+                        plin = []
+                    elif hasattr(backend, "linearize_photo_window"):
+                        plin = backend.linearize_photo_window(pfs, poses)
+                    else:
+                        plin = [backend.linearize_photo(p, R_, t_) for p, (R_, t_) in zip(pfs, poses)]
+                else:
+                    at = [nW - 1] if pf is not None else []
+                    plin = [backend.linearize_photo(pf, win[-1]["R"], win[-1]["t"])] if pf is not None else []
+                for i, (Hp, bp, fp, nv) in zip(at, plin):
+                    if nv and np.all(np.isfinite(Hp)) and np.all(np.isfinite(bp)):
+                        A[6 * i:6 * i + 6, 6 * i:6 * i + 6] += Hp
+                        g[6 * i:6 * i + 6] += bp
+                        cost += fp
+                for i in range(1, nW):
+                    if win[i]["Z"] is None:
+                        continue
+                    Rz, tz = win[i]["Z"]
+                    Rab, tab = _between(win[i - 1]["R"], win[i - 1]["t"], win[i]["R"], win[i]["t"])
+                    Re, te = Rz.T @ Rab, Rz.T @ (tab - tz)                     # Z^-1 * between(X_{i-1}, X_i)
+                    r = np.concatenate([_so3_log(Re), te])
+                    Jb = np.eye(6)
+                    Ja = -_adjoint(Rab.T, -Rab.T @ tab)                         # -Ad(between^-1)
+                    J = np.zeros((6, 6 * nW))
+                    J[:, 6 * (i - 1):6 * i] = Ja
+                    J[:, 6 * i:6 * i + 6] = Jb
+                    A += J.T @ Wb @ J
+                    g += J.T @ Wb @ r
+                    cost += float(r @ Wb @ r)
+                # what marginalisation leaves on the oldest pose; loose while that pose has never been optimised
+                loose = win[0]["k"] == 0 and k < cfg.window
+                sr, st = (np.deg2rad(1.0), 0.1) if loose else (1e-4, 1e-4)
+                A[:6, :6] += np.diag([1.0 / sr**2] * 3 + [1.0 / st**2] * 3)
+                xi = np.linalg.solve(A + 1e-9 * np.eye(6 * nW), -g)
+                for i, w in enumerate(win):
+                    w["R"], w["t"] = _retract(w["R"], w["t"], xi[6 * i:6 * i + 6])
+                fs.append(cost)
         costs.append(fs)
         a5 = time.perf_counter()
         R, t = win[-1]["R"], win[-1]["t"]
