@@ -381,6 +381,35 @@ int mh_icp_window_optimise_async(mh_icp * const * icps, size_t W, const double *
                                  mh_icp_window_result * out, double * trace_poses);
 int mh_icp_window_wait(mh_ctx * ctx);
 
+/* The same chain with ISAM2's per-variable relinearization thresholds: a factor is evaluated again (K3 at the current pose)
+ * only once its pose has left the neighbourhood of the pose L_i of its last evaluation.  At the start of an iteration, with
+ * d_r = Log(L_i.R^T R_i), d_t = L_i.R^T (t_i - L_i.t): factor i is evaluated in iteration 0, and whenever any |d_r[k]| > relin_rot
+ * or any |d_t[k]| > relin_trans (component-wise and strict: exactly at a threshold keeps).  Otherwise its K3 launch touches
+ * none of its points and the step uses the H_ss, b_s, f of the evaluation at L_i, carried to the current pose to first order
+ * under the chain's retraction: with M = blockdiag(Jr^-1(d_r), Exp(d_r)) and d = [d_r, d_t] the factor contributes M^T H M,
+ * M^T (b + H d) and the cost f + 2 b^T d + d^T H d (at d = 0 the stored H, b, f as they are).  The step in front of an iteration
+ * takes the decision on the device; between factors, prior, damping, solve, retraction and stopping are those of
+ * mh_icp_window_optimise, at the current poses.  With both thresholds 0 every non-empty factor whose pose moved at all is
+ * evaluated and the call computes, bit for bit, what mh_icp_window_optimise computes.
+ * Per-point association state: as the factor's own last evaluation left it.  Linearize count: advances by the number of the
+ * factor's evaluations (an empty factor's by the executed iterations, as above).  first / last in the result: the factor's
+ * first and last evaluation.  trace[].degenerate carries a kept factor's bits of its last evaluation.
+ * evaluated_mask: NULL, or cfg->iters words the caller owns — bit i of word j: factor i ran K3 in iteration j; words of
+ * iterations that were not executed are left untouched.  Every restriction and error rule of mh_icp_window_optimise applies;
+ * thresholds that are negative or not finite: MH_ERR_INVALID_ARG, nothing enqueued.  mh_icp_window_wait collects the _async
+ * form as well (evaluated_mask must stay valid until then). */
+typedef struct mh_icp_window_relin {
+  double relin_rot, relin_trans;  /* rad, m; >= 0 */
+} mh_icp_window_relin;
+int mh_icp_window_optimise_relin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                 const double * Z_R, const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg,
+                                 const mh_icp_window_relin * relin, mh_icp_window_result * out, double * trace_poses,
+                                 uint32_t * evaluated_mask);
+int mh_icp_window_optimise_relin_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                       const double * Z_R, const double * Z_t, const double g_unit[3],
+                                       const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                       mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask);
+
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals
  * unique_ns[g] gets p <- R_g p + t_g in float (no FMA, Eigen's evaluation order).  Rt12 = n_groups x

@@ -26,6 +26,7 @@ EXPORTS = [
     "mh_icp_wait", "mh_icp_linearize_batch", "mh_icp_get_state", "mh_icp_reset", "mh_icp_set_components", "mh_icp_size",
     "mh_icp_align", "mh_icp_align_async",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
+    "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
     "mh_deskew", "mh_transform_f32",
     "mh_scan_create", "mh_scan_destroy", "mh_scan_prepare_input", "mh_scan_prepare_input_device", "mh_scan_prefetch", "mh_scan_prepare_input_prefetched", "mh_scan_prepare_input_layout", "mh_scan_get_unique_ns", "mh_scan_deskew",
     "mh_scan_deskew_imu", "mh_scan_get_deskew_poses", "mh_photo_preprocess_scan_resident", "mh_photo_preprocess_scan_begin_resident",
@@ -171,6 +172,11 @@ class WindowResult(C.Structure):
                       for r in (self.trace[i] for i in range(n))],
             "first": [self.first[i].as_dict() for i in range(W)], "last": [self.last[i].as_dict() for i in range(W)],
         }
+
+
+class WindowRelin(C.Structure):
+    """mh_icp_window_relin"""
+    _fields_ = [("relin_rot", C.c_double), ("relin_trans", C.c_double)]
 
 
 def make_window_config(iters=6, between_sigma_rot=2e-3, between_sigma_trans=1e-2, prior_sigma_rot=1e-4, prior_sigma_trans=1e-4, damping=1e-9,
@@ -513,6 +519,8 @@ def load(build_if_missing: bool = True):
     L.mh_icp_window_optimise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_optimise_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_wait.argtypes = [vp]
+    L.mh_icp_window_optimise_relin.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowRelin), C.POINTER(WindowResult), vp, vp]
+    L.mh_icp_window_optimise_relin_async.argtypes = L.mh_icp_window_optimise_relin.argtypes
     L.mh_icp_size.restype = sz
     L.mh_deskew.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
     L.mh_transform_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -882,23 +890,28 @@ def linearize_batch(factors, Rs, ts, g_units=None, R_tgts=None, t_tgts=None) -> 
 class WindowCall:
     """an mh_icp_window_optimise_async call in flight: wait() collects it and returns the result"""
 
-    def __init__(self, ctx, keep, out, trace):
-        self.ctx, self._keep, self.out, self.trace = ctx, keep, out, trace
+    def __init__(self, ctx, keep, out, trace, masks=None):
+        self.ctx, self._keep, self.out, self.trace, self.masks = ctx, keep, out, trace, masks
 
     def wait(self) -> dict:
         self.ctx.check(self.ctx.L.mh_icp_window_wait(self.ctx.h))
         d = self.out.as_dict()
         if self.trace is not None:
             d["poses"] = self.trace[:d["iters"]]
+        if self.masks is not None:
+            d["evaluated"] = self.masks[:d["iters"]].copy()
         self._keep = None
         return d
 
 
-def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), trace_poses=False, wait=True):
+def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), trace_poses=False, wait=True, relin=None):
     """mh_icp_window_optimise: the fixed-lag Gauss-Newton loop over `factors` (oldest first) as one chain of launches.
     poses: (R, t) per factor; Z: (R, t) per factor, entry i the measured T_{i-1}^-1 T_i where has_Z[i] (entry 0 unused).
     trace_poses: also return "poses", (iters, W, 12) — R row-major then t after every executed step.
-    wait=False: mh_icp_window_optimise_async; returns a WindowCall whose wait() gives the same dict."""
+    wait=False: mh_icp_window_optimise_async; returns a WindowCall whose wait() gives the same dict.
+    relin=(rot, trans): mh_icp_window_optimise_relin — a factor is evaluated again only once its pose has moved past these
+    thresholds (rad, m) from the pose of its last evaluation; also returns "evaluated", per executed iteration the mask of the
+    factors that ran K3."""
     W = len(factors)
     ctx = factors[0].ctx
     R = np.ascontiguousarray(np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses]))
@@ -912,6 +925,19 @@ def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_uni
     handles = (C.c_void_p * W)(*[f.h for f in factors])
     out = WindowResult()
     trace = np.full((int(cfg.iters), W, 12), np.nan) if trace_poses else None
+    if relin is not None:
+        rl = WindowRelin(float(relin[0]), float(relin[1]))
+        masks = np.zeros(max(int(cfg.iters), 1), np.uint32)  # (a bad iters is the library's to refuse)
+        args = (handles, W, _p(R), _p(t), _p(hz), _p(ZR), _p(Zt), _p(g), C.byref(cfg), C.byref(rl), C.byref(out), _p(trace), _p(masks))
+        if not wait:
+            ctx.check(ctx.L.mh_icp_window_optimise_relin_async(*args))
+            return WindowCall(ctx, (handles, R, t, hz, ZR, Zt, g, cfg, rl), out, trace, masks)
+        ctx.check(ctx.L.mh_icp_window_optimise_relin(*args))
+        d = out.as_dict()
+        if trace is not None:
+            d["poses"] = trace[:d["iters"]]
+        d["evaluated"] = masks[:d["iters"]].copy()
+        return d
     args = (handles, W, _p(R), _p(t), _p(hz), _p(ZR), _p(Zt), _p(g), C.byref(cfg), C.byref(out), _p(trace))
     if not wait:
         ctx.check(ctx.L.mh_icp_window_optimise_async(*args))

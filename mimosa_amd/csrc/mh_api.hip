@@ -341,13 +341,17 @@ static_assert(sizeof(mh::AlignState) <= 192 && mh::kRowWords <= mh::kLlEig, "mh_
 
 // mh_icp_window_optimise's block of device memory (mh_ctx::d_window) and the pinned staging of its first part (h_window):
 // [grid prefixes, 256 B | WindowState | iters x n_slots argument blocks | 256 B that load_uniform may read past the last block |
-//  one landing slot of 32 flagged words per pose for K3's sums and counters (every iteration's words carry its own number)]
+//  one landing slot of 32 flagged words per pose for K3's sums and counters (every iteration's words carry its own number) |
+//  WindowRelin, which the steps of an mh_icp_window_optimise_relin chain keep among themselves]
 constexpr size_t kWinStateAt = 256;
 constexpr size_t kWinBlocksAt = 3584;
 constexpr size_t kWinStageBytes = kWinBlocksAt + sizeof(mh::IcpArgs) * mh::kWindowMax * kMaxPending;
 constexpr size_t kWinLlAt = (kWinStageBytes + 256 + 255) & ~size_t(255);
-constexpr size_t kWinBytes = kWinLlAt + 32 * sizeof(uint4) * mh::kWindowMax;
+constexpr size_t kWinRelinAt = kWinLlAt + 32 * sizeof(uint4) * mh::kWindowMax;
+constexpr size_t kWinBytes = kWinRelinAt + ((sizeof(mh::WindowRelin) + 255) & ~size_t(255));
 constexpr size_t kWinRowWords = 256;  // flagged words per iteration's row in h_window_rows
+constexpr size_t kWinMaskWord = kWinRowWords - 1;  // of which the last: the evaluated mask of an mh_icp_window_optimise_relin iteration
+static_assert(mh::kWRowPose + 12 * mh::kWindowMax <= static_cast<int>(kWinMaskWord) && kWinRelinAt % 16 == 0, "mh_icp_window_optimise_relin layout");
 static_assert(kWinStateAt + sizeof(mh::WindowState) <= kWinBlocksAt && mh::kWRowPose + 12 * mh::kWindowMax <= static_cast<int>(kWinRowWords) &&
                 MH_WINDOW_MAX == mh::kWindowMax, "mh_icp_window_optimise layout");
 
@@ -1404,7 +1408,8 @@ static void window_abandon(mh_ctx * ctx)
 }
 
 static int window_begin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses)
+                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses,
+                        const mh_icp_window_relin * relin, uint32_t * evaluated_mask)
 {
   mh_ctx * ctx = (icps && W && icps[0]) ? icps[0]->ctx : nullptr;  // (where the message goes: mh_last_error(ctx) as well as mh_last_error(NULL))
   if (!icps || !R || !t || !has_Z || !g_unit || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
@@ -1427,6 +1432,9 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   bool ok = cfg->damping >= 0.0 && cfg->eps_rot >= 0.0 && cfg->eps_trans >= 0.0 && cfg->check_every >= 0;
   for (int i = 0; i < 6; ++i) ok = ok && cfg->between_info[i] >= 0.0 && cfg->prior_info[i] >= 0.0;
   if (!ok) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: eps, damping, between_info, prior_info and check_every must be >= 0");
+  if (relin && !(relin->relin_rot >= 0.0 && relin->relin_rot <= std::numeric_limits<double>::max() && relin->relin_trans >= 0.0 &&
+                 relin->relin_trans <= std::numeric_limits<double>::max()))
+    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: relin_rot and relin_trans must be finite and >= 0");
   unsigned int zmask = 0;
   for (size_t f = 1; f < W; ++f)
     if (has_Z[f]) zmask |= 1u << f;
@@ -1446,6 +1454,10 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   c.queued = 0;
   c.out = out;
   c.trace_poses = trace_poses;
+  c.relin = relin != nullptr;
+  c.relin_rot = relin ? relin->relin_rot : 0.0;
+  c.relin_trans = relin ? relin->relin_trans : 0.0;
+  c.evaluated_mask = evaluated_mask;
   for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
   // launch groups in slot order, as mh_icp_linearize_batch lays the same window out
   const std::vector<LaunchGroup> groups = window_launch_groups(icps, W);
@@ -1574,7 +1586,19 @@ static int window_enqueue(mh_ctx * ctx, int upto)
       s.state = reinterpret_cast<mh::WindowState *>(d + kWinStateAt);
       s.p = c.p;
       s.seq = c.seq[it];
-      e = mh::launch_window_step(s, ctx->stream);
+      if (c.relin) {
+        mh::WindowRelinStepArgs ra;
+        std::memset(static_cast<void *>(&ra), 0, sizeof(ra));
+        ra.s = s;
+        ra.relin = reinterpret_cast<mh::WindowRelin *>(d + kWinRelinAt);
+        ra.mask_host = s.row_host + kWinMaskWord;
+        ra.rp.relin_rot = c.relin_rot;
+        ra.rp.relin_trans = c.relin_trans;
+        ra.rp.first = it == 0 ? 1 : 0;
+        e = mh::launch_window_relin_step(ra, ctx->stream);
+      } else {
+        e = mh::launch_window_step(s, ctx->stream);
+      }
     }
     if (e != hipSuccess) {
       window_abandon(ctx);
@@ -1628,16 +1652,41 @@ static int window_finish(mh_ctx * ctx)
     std::memcpy(out->R + 9 * i, last_row + mh::kWRowPose + 12 * i, sizeof(double) * 9);
     std::memcpy(out->t + 3 * i, last_row + mh::kWRowPose + 12 * i + 9, sizeof(double) * 3);
   }
+  // which factors ran K3 in which iteration: all of them, unless the chain's steps decided (the word behind each row).  An
+  // empty factor has no evaluation; its books move with the iterations, as they always did.
+  uint32_t masks[kMaxPending];
+  for (int it = 0; it < iters; ++it) masks[it] = c.p.have;
+  for (int it = 0; it < iters && c.relin && rc_all == MH_OK; ++it) {
+    double m = 0.0;
+    const uint4 * word = ctx->h_window_rows + static_cast<size_t>(it) * kWinRowWords + kWinMaskWord;
+    mh::SpinBudget spin(2000000L);
+    if (!spin.until([&] { return mh::ll_read(reinterpret_cast<const uint64_t *>(word), c.seq[it], m); })) {
+      rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_window_optimise_relin: an iteration's evaluated mask did not arrive");
+      break;
+    }
+    masks[it] = static_cast<uint32_t>(m);
+    if (c.evaluated_mask) c.evaluated_mask[it] = masks[it];
+  }
+  int last_it[mh::kWindowMax], n_eval[mh::kWindowMax];
+  for (int i = 0; i < W; ++i) {
+    last_it[i] = c.icps[i]->n ? 0 : iters - 1;
+    n_eval[i] = c.icps[i]->n ? 0 : iters;
+    for (int it = 0; it < iters && c.icps[i]->n; ++it)
+      if ((masks[it] >> i) & 1u) {
+        last_it[i] = it;
+        n_eval[i] += 1;
+      }
+  }
   // first / last: the host epilogue of linearize() on the sums K3 folded at the initial and at the last evaluated poses
   for (int i = 0; i < W && rc_all == MH_OK; ++i) {
     mh_icp * icp = c.icps[i];
     for (int which = 0; which < 2; ++which) {
-      const int it = which == 0 ? 0 : iters - 1;
+      const int it = which == 0 ? 0 : last_it[i];
       PendingCall pc{};
       pc.out = nullptr;
       std::memcpy(pc.R, it == 0 ? c.R0[i] : rows.data() + static_cast<size_t>(it - 1) * words + mh::kWRowPose + 12 * i, sizeof(pc.R));
       std::memcpy(pc.gz, c.gz, sizeof(pc.gz));
-      pc.linearize_count = c.count0[i] + it + 1;
+      pc.linearize_count = c.count0[i] + (which == 0 ? 1 : n_eval[i]);
       pc.seq = icp->n ? c.seq[it] : 0;
       pc.components = false;
       pc.ev[0] = pc.ev[1] = pc.ev[2] = nullptr;
@@ -1652,7 +1701,7 @@ static int window_finish(mh_ctx * ctx)
     }
   }
   for (int i = 0; i < W; ++i) {
-    c.icps[i]->linearize_count = c.count0[i] + iters;
+    c.icps[i]->linearize_count = c.count0[i] + n_eval[i];
     c.icps[i]->cold = false;
   }
   window_release(ctx);
@@ -1677,9 +1726,9 @@ static int mh_icp_window_wait_impl(mh_ctx * ctx)
 
 static int mh_icp_window_optimise_impl(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out,
-                                       double * trace_poses, bool blocking)
+                                       double * trace_poses, bool blocking, const mh_icp_window_relin * relin = nullptr, uint32_t * evaluated_mask = nullptr)
 {
-  int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses);
+  int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask);
   if (rc != MH_OK) return rc;
   mh_ctx * ctx = icps[0]->ctx;
   const int iters = cfg->iters;
@@ -1710,6 +1759,24 @@ int mh_icp_window_optimise_async(mh_icp * const * icps, size_t W, const double *
 {
   return guarded((icps && W && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_window_optimise_async",
                  [&]() -> int { return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false); });
+}
+int mh_icp_window_optimise_relin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                 const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                 mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
+{
+  return guarded((icps && W && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_window_optimise_relin", [&]() -> int {
+    if (!relin) return fail((icps && W && icps[0]) ? icps[0]->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: NULL argument");
+    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, relin, evaluated_mask);
+  });
+}
+int mh_icp_window_optimise_relin_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                       const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                       mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
+{
+  return guarded((icps && W && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_window_optimise_relin_async", [&]() -> int {
+    if (!relin) return fail((icps && W && icps[0]) ? icps[0]->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: NULL argument");
+    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, relin, evaluated_mask);
+  });
 }
 int mh_icp_window_wait(mh_ctx * ctx)
 {

@@ -53,6 +53,9 @@ struct WindowCall
   std::vector<WindowLaunch> launches;
   mh_icp_window_result * out = nullptr;
   double * trace_poses = nullptr;
+  bool relin = false;  // mh_icp_window_optimise_relin: the step kernel chooses per factor and iteration whether K3 runs
+  double relin_rot = 0.0, relin_trans = 0.0;
+  uint32_t * evaluated_mask = nullptr;
 };
 
 struct mh_ctx

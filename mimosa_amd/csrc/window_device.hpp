@@ -44,6 +44,24 @@ struct WindowState
   int stopped, converged, iters, pad;
 };
 
+// mh_icp_window_optimise_relin: per pose the linearization pose L_i of its factor's last evaluation and the factor's H_ss, b_s, f
+// (after the 4-DoF projection and the degeneracy quirk) as evaluated there.  A factor whose pose stays within the thresholds of
+// L_i (component-wise in L_i's tangent, strict) is not evaluated again: its quadratic model is carried to the current pose.
+struct WindowRelin
+{
+  double LR[kWindowMax][9], Lt[kWindowMax][3];
+  double H[kWindowMax][36], b[kWindowMax][6], f[kWindowMax];
+  double d[kWindowMax][6];      // the current pose in L_i's tangent: [Log(L.R^T R), L.R^T (t - L.t)], as the last step left it
+  int degen[2 * kWindowMax];    // the degeneracy bits of the last evaluation (reported while the factor is kept)
+  int next[kWindowMax];         // the decision of the step in flight, per pose
+  unsigned int eval, pad;       // bit i: factor i is evaluated in the iteration queued behind the last step
+};
+struct WindowRelinParams
+{
+  double relin_rot, relin_trans;  // rad, m
+  int first, pad;                 // the call's first iteration: every non-empty factor is evaluated, nothing is read from WindowRelin
+};
+
 // One row per queued iteration, published as flagged words.
 enum WindowRow
 {
@@ -181,22 +199,112 @@ MH_HD void window_solve6(const double L[36], const double D[6], const double * r
   }
 }
 
-// w.A, w.E, w.rhs, w.cost from the factors' sums at the poses of `st`
-template <typename Par>
-MH_HD void window_assemble(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, Par & par)
+// ---- relinearization past a pose threshold (mh_icp_window_optimise_relin) ------------------------------------------------------
+// the pose (R, t) in the tangent of (LR, Lt) under the chain's retraction R <- R Exp(xi_r), t <- t + R xi_t
+MH_HD void window_local(const double LR[9], const double Lt[3], const double R[9], const double t[3], double d[6])
+{
+  double Lrt[9], Rel[9];
+  win_tr(LR, Lrt);
+  win_mm(Lrt, R, Rel);
+  window_so3log(Rel, d);
+  const double dt[3] = {t[0] - Lt[0], t[1] - Lt[1], t[2] - Lt[2]};
+  win_mv(Lrt, dt, d + 3);
+}
+// the inverse right Jacobian of SO(3): I + 1/2 [phi]x + c [phi]x^2, c = 1 / th^2 - (1 + cos th) / (2 th sin th) (its series
+// 1/12 + th^2 / 720 + th^4 / 30240 below 1e-2 rad, where the closed form has lost five digits and the series' next term is 1e-18)
+MH_HD void window_jrinv(const double phi[3], double J[9])
+{
+  const double th2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2], th = sqrt(th2);
+  const double K[9] = {0, -phi[2], phi[1], phi[2], 0, -phi[0], -phi[1], phi[0], 0};
+  const double c = th < 1e-2 ? 1.0 / 12.0 + th2 / 720.0 + th2 * th2 / 30240.0 : 1.0 / th2 - (1.0 + cos(th)) / (2.0 * th * sin(th));
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double kk = 0;
+      for (int m = 0; m < 3; ++m) kk += K[3 * i + m] * K[3 * m + j];
+      J[3 * i + j] = (i == j ? 1.0 : 0.0) + 0.5 * K[3 * i + j] + c * kk;
+    }
+}
+// The model f + 2 b^T x + x^T H x of a factor around L, seen from the pose at offset d: a step xi there is x = d + M xi to
+// first order, M = blockdiag(Jr^-1(d_r), Exp(d_r)).  Ho = M^T H M, bo = M^T (b + H d), fo = f + 2 b^T d + d^T H d; at d = 0 the
+// model itself, untouched.  tmp: 36 doubles of the caller's (H M).
+MH_HD void window_transport(const double H[36], const double b[6], double f, const double d[6], double Ho[36], double bo[6], double & fo, double * tmp)
+{
+  if (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0 && d[3] == 0.0 && d[4] == 0.0 && d[5] == 0.0) {
+    for (int q = 0; q < 36; ++q) Ho[q] = H[q];
+    for (int q = 0; q < 6; ++q) bo[q] = b[q];
+    fo = f;
+    return;
+  }
+  double M[18];  // Jr^-1(d_r), then Exp(d_r)
+  window_jrinv(d, M);
+  align_expmap(d, M + 9);
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) {
+      const double * blk = M + (c < 3 ? 0 : 9);
+      const int h0 = c < 3 ? 0 : 3, cc = c - h0;
+      tmp[6 * r + c] = H[6 * r + h0] * blk[cc] + H[6 * r + h0 + 1] * blk[3 + cc] + H[6 * r + h0 + 2] * blk[6 + cc];
+    }
+  double bd = 0.0, dHd = 0.0;
+  for (int r = 0; r < 6; ++r) {
+    const double * blk = M + (r < 3 ? 0 : 9);
+    const int h0 = r < 3 ? 0 : 3, rr = r - h0;
+    for (int c = 0; c < 6; ++c) Ho[6 * r + c] = blk[rr] * tmp[6 * h0 + c] + blk[3 + rr] * tmp[6 * (h0 + 1) + c] + blk[6 + rr] * tmp[6 * (h0 + 2) + c];
+    double hd = 0.0;
+    for (int m = 0; m < 6; ++m) hd += H[6 * r + m] * d[m];
+    bd += b[r] * d[r];
+    dHd += d[r] * hd;
+  }
+  for (int r = 0; r < 6; ++r) {
+    const double * blk = M + (r < 3 ? 0 : 9);
+    const int h0 = r < 3 ? 0 : 3, rr = r - h0;
+    double g = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      double v = b[h0 + k];
+      for (int m = 0; m < 6; ++m) v += H[6 * (h0 + k) + m] * d[m];
+      g += blk[3 * k + rr] * v;
+    }
+    bo[r] = g;
+  }
+  fo = f + 2.0 * bd + dHd;
+}
+// ISAM2's vector thresholds: component-wise, strict
+MH_HD bool window_relin_decide(const double d[6], double relin_rot, double relin_trans)
+{
+  return fabs(d[0]) > relin_rot || fabs(d[1]) > relin_rot || fabs(d[2]) > relin_rot || fabs(d[3]) > relin_trans || fabs(d[4]) > relin_trans ||
+         fabs(d[5]) > relin_trans;
+}
+
+// w.A, w.E, w.rhs, w.cost from the factors' sums at the poses of `st`.  RELIN: the factors of `eval` from their sums (and into
+// rl, with the pose), the other non-empty ones from rl
+template <bool RELIN, typename Par>
+MH_HD void window_assemble_impl(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, WindowRelin * rl, unsigned int eval, Par & par)
 {
   const int W = p.W;
   par.each(2 * W, [&](int l) {
     const int i = l >> 1, blk = l & 1;
+    if (RELIN && ((p.have >> i) & 1u) && !((eval >> i) & 1u)) {
+      w.degen[l] = rl->degen[l];
+      return;
+    }
     w.degen[l] = ((p.have >> i) & 1u) && align_block_degenerate(sums + 32 * i, blk, blk ? p.thresh_trans[i] : p.thresh_rot[i]) ? 1 : 0;
+    if (RELIN) rl->degen[l] = w.degen[l];
   });
   par.each(W, [&](int i) {
-    if ((p.have >> i) & 1u) {
+    if (RELIN && ((p.have >> i) & 1u) && !((eval >> i) & 1u)) {
+      window_transport(rl->H[i], rl->b[i], rl->f[i], rl->d[i], w.H[i], w.b[i], w.f[i], w.A[i]);
+    } else if ((p.have >> i) & 1u) {
       AlignParams ap{};
       for (int q = 0; q < 3; ++q) ap.gz[q] = p.gz[q];
       ap.reg_4_dof = static_cast<int>((p.reg_4_dof >> i) & 1u);
       ap.project_on_degeneracy = static_cast<int>((p.project_on_degeneracy >> i) & 1u);
       align_hessian(sums + 32 * i, st.R[i], ap, w.degen[2 * i] != 0, w.degen[2 * i + 1] != 0, w.H[i], w.b[i], w.f[i]);
+      if (RELIN) {
+        for (int q = 0; q < 36; ++q) rl->H[i][q] = w.H[i][q];
+        for (int q = 0; q < 6; ++q) rl->b[i][q] = w.b[i][q];
+        rl->f[i] = w.f[i];
+        for (int q = 0; q < 9; ++q) rl->LR[i][q] = st.R[i][q];
+        for (int q = 0; q < 3; ++q) rl->Lt[i][q] = st.t[i][q];
+      }
     } else {
       for (int q = 0; q < 36; ++q) w.H[i][q] = 0.0;
       for (int q = 0; q < 6; ++q) w.b[i][q] = 0.0;
@@ -234,6 +342,11 @@ MH_HD void window_assemble(const double * sums, const WindowState & st, const Wi
       w.cost = cost;
     }
   });
+}
+template <typename Par>
+MH_HD void window_assemble(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, Par & par)
+{
+  window_assemble_impl<false>(sums, st, p, w, nullptr, 0u, par);
 }
 
 // the block sweep: S_i = L_i D_i L_i^T and G_{i+1} for every block.  false (w.ok == 0): a pivot is not positive
@@ -336,15 +449,20 @@ MH_HD bool window_solve(int W, WindowWork & w, Par & par)
 // One queued iteration: the chain's state in, the state and the iteration's row out.  sums: 32 doubles per pose (28 sums +
 // 4 counters; ignored where p.have has no bit).  arrived: the words of every factor carry the call's number (they always do; a
 // chain that finds otherwise stops).  Returns the row's flags.  Once st.stopped is set the poses are passed on unchanged.
-template <typename Par>
-MH_HD int window_advance(WindowState & st, const double * sums, bool arrived, const WindowParams & p, WindowWork & w, double * row, Par & par)
+// RELIN: `arrived` speaks of the factors this iteration evaluates (window_relin_mask); behind the step, rl holds every pose's
+// offset from its linearization pose and the factors the next iteration evaluates.
+template <bool RELIN, typename Par>
+MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrived, const WindowParams & p, WindowWork & w, double * row, WindowRelin * rl,
+                              const WindowRelinParams * rp, Par & par)
 {
   const int W = p.W;
   const bool frozen = st.stopped != 0;
+  unsigned int eval = 0u;
+  if (RELIN) eval = rp->first ? p.have : rl->eval;
   par.sync();  // (every index has read the state before index 0 changes it)
   bool stepped = false;
   if (!frozen && arrived) {
-    window_assemble(sums, st, p, w, par);
+    window_assemble_impl<RELIN>(sums, st, p, w, rl, eval, par);
     stepped = window_solve(W, w, par);
     par.each(W, [&](int i) {
       if (stepped) {
@@ -365,6 +483,14 @@ MH_HD int window_advance(WindowState & st, const double * sums, bool arrived, co
       else
         st.t[i][q - 9] = w.tn[i][q - 9];
     });
+    if (RELIN)
+      par.each(W, [&](int i) {
+        rl->next[i] = 0;
+        if ((p.have >> i) & 1u) {
+          window_local(rl->LR[i], rl->Lt[i], st.R[i], st.t[i], rl->d[i]);
+          rl->next[i] = window_relin_decide(rl->d[i], rp->relin_rot, rp->relin_trans) ? 1 : 0;
+        }
+      });
   }
   par.each(12 * W, [&](int l) {
     const int i = l / 12, q = l % 12;
@@ -399,11 +525,29 @@ MH_HD int window_advance(WindowState & st, const double * sums, bool arrived, co
       row[kWRowBits] = stepped ? 0.0 : static_cast<double>(kAlignSingular);
       row[kWRowDegen] = dg;
       flags = st.stopped | (conv ? 2 : 0);
+      if (RELIN) {
+        unsigned int m = 0u;
+        for (int i = 0; i < W; ++i) m |= rl->next[i] ? 1u << i : 0u;
+        rl->eval = m;
+      }
     }
     row[kWRowFlags] = static_cast<double>(flags);
     row[kWRowIters] = static_cast<double>(st.iters);
   });
   return static_cast<int>(row[kWRowFlags]);
+}
+template <typename Par>
+MH_HD int window_advance(WindowState & st, const double * sums, bool arrived, const WindowParams & p, WindowWork & w, double * row, Par & par)
+{
+  return window_advance_impl<false>(st, sums, arrived, p, w, row, nullptr, nullptr, par);
+}
+// the factors the iteration about to run evaluates (read before window_advance_relin changes rl)
+MH_HD unsigned int window_relin_mask(const WindowRelin & rl, const WindowParams & p, const WindowRelinParams & rp) { return rp.first ? p.have : rl.eval; }
+template <typename Par>
+MH_HD int window_advance_relin(WindowState & st, WindowRelin & rl, const double * sums, bool arrived, const WindowParams & p, const WindowRelinParams & rp,
+                               WindowWork & w, double * row, Par & par)
+{
+  return window_advance_impl<true>(st, sums, arrived, p, w, row, &rl, &rp, par);
 }
 
 }  // namespace mh
@@ -429,5 +573,17 @@ struct WindowStepArgs
   unsigned int seq;              // tags K3's words of this iteration and everything this step publishes
 };
 hipError_t launch_window_step(const WindowStepArgs & a, hipStream_t stream);
+
+// One step of an mh_icp_window_optimise_relin chain: as above, and the step decides per factor whether the iteration queued
+// behind it evaluates it (n left alone in its argument block) or keeps its linearization (n = 0); it expects K3's words of the
+// factors the step in front of it chose, forwards those alone, and publishes the iteration's evaluated mask behind the row.
+struct WindowRelinStepArgs
+{
+  WindowStepArgs s;
+  WindowRelin * relin;  // device memory the context owns; needs no initialisation (rp.first)
+  uint4 * mask_host;    // the iteration's evaluated mask as one flagged word in mapped pinned memory
+  WindowRelinParams rp;
+};
+hipError_t launch_window_relin_step(const WindowRelinStepArgs & a, hipStream_t stream);
 }  // namespace mh
 #endif

@@ -613,6 +613,13 @@ public:
     int iters = 0;
     bool converged = false;
     std::vector<mh_icp_window_trace> trace;  // one row per executed iteration
+    std::vector<uint32_t> evaluated;         // optimiseWindowRelin: per executed iteration, bit i: factor i ran K3
+  };
+  // ISAM2's per-variable relinearization thresholds (graph/manager.cpp:51-73): a factor is evaluated again only once its pose
+  // has moved past them from the pose of its last evaluation (mh_icp_window_optimise_relin)
+  struct WindowRelin
+  {
+    double rot = 1.75e-2, trans = 5.0e-3;  // rad, m: config/enwide/params.yaml:32-33
   };
   // a call in flight (optimiseWindowAsync): wait() collects it
   class WindowCall
@@ -632,6 +639,7 @@ public:
       out.iters = r_->iters;
       out.converged = r_->converged != 0;
       out.trace.assign(r_->trace, r_->trace + r_->iters);
+      if (relin_on_) out.evaluated.assign(masks_.begin(), masks_.begin() + r_->iters);
       for (size_t i = 0; i < factors_.size(); ++i) {
         out.poses.push_back(pose3(r_->R + 9 * i, r_->t + 3 * i));
         factors_[i]->last_ = r_->last[i];
@@ -645,6 +653,9 @@ public:
     A3 g_{};
     mh_icp_window_config c_{};
     std::unique_ptr<mh_icp_window_result> r_;
+    bool relin_on_ = false;
+    mh_icp_window_relin relin_{};
+    std::vector<uint32_t> masks_;
   };
   static WindowResult optimiseWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
                                      const Unit3 & g, const WindowConfig & config)
@@ -655,6 +666,17 @@ public:
                                                          const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config)
   {
     return startWindow(factors, poses, between, g, config, false);
+  }
+  static WindowResult optimiseWindowRelin(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
+                                          const Unit3 & g, const WindowConfig & config, const WindowRelin & relin)
+  {
+    return startWindow(factors, poses, between, g, config, true, &relin)->finish();
+  }
+  static std::unique_ptr<WindowCall> optimiseWindowRelinAsync(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses,
+                                                              const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config,
+                                                              const WindowRelin & relin)
+  {
+    return startWindow(factors, poses, between, g, config, false, &relin);
   }
 
   // getters, :48-72
@@ -724,7 +746,7 @@ private:
   }
   const Context & ctx() const { return *ivox_target_->context(); }
   static std::unique_ptr<WindowCall> startWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
-                                                 const Unit3 & g, const WindowConfig & config, bool blocking)
+                                                 const Unit3 & g, const WindowConfig & config, bool blocking, const WindowRelin * relin = nullptr)
   {
     const size_t n = factors.size();
     if (!n || poses.size() != n || between.size() != n) throw std::runtime_error("ICPFactor::optimiseWindow: one pose and one between entry per factor");
@@ -758,6 +780,17 @@ private:
     w->c_.eps_rot = config.eps_rot;
     w->c_.eps_trans = config.eps_trans;
     w->r_.reset(new mh_icp_window_result);
+    if (relin) {
+      w->relin_on_ = true;
+      w->relin_.relin_rot = relin->rot;
+      w->relin_.relin_trans = relin->trans;
+      w->masks_.assign(static_cast<size_t>(config.iters > 0 ? config.iters : 0), 0u);
+      const auto fr = blocking ? mh_icp_window_optimise_relin : mh_icp_window_optimise_relin_async;
+      factors[0]->ctx().check(fr(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_, &w->relin_,
+                                 w->r_.get(), nullptr, w->masks_.data()),
+                              blocking ? "mh_icp_window_optimise_relin" : "mh_icp_window_optimise_relin_async");
+      return w;
+    }
     const auto fn = blocking ? mh_icp_window_optimise : mh_icp_window_optimise_async;
     factors[0]->ctx().check(fn(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_, w->r_.get(), nullptr),
                             blocking ? "mh_icp_window_optimise" : "mh_icp_window_optimise_async");

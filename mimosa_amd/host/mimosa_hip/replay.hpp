@@ -251,6 +251,10 @@ struct Config
   // blocking linearizeBatch, a dense host solve and the retractions per iteration.  The device's solve is refined, the host's is
   // a plain elimination, and acos / sin are the device's: the trajectory agrees to ~1e-10 m, not bit for bit.
   bool device_window = false;
+  // with device_window: a factor of the window is evaluated again only once its pose has moved past these thresholds (rad, m)
+  // from the pose of its last evaluation within the call (ICPFactor::optimiseWindowRelin).  Refused without device_window
+  bool window_relin = false;
+  double window_relin_rot = 1.75e-2, window_relin_trans = 5.0e-3;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
   lidar::ManagerInputConfig input = lidar::defaultManagerInputConfig();
@@ -395,6 +399,12 @@ public:
   void setPhotoWindow(bool on) { photo_window_ = on; }
   // on: optimise() hands the whole loop to the device (FactorT::optimiseWindow); no photometric factor may be in play
   void setDeviceWindow(bool on) { device_window_ = on; }
+  void setWindowRelin(bool on, double rot, double trans)
+  {
+    window_relin_ = on;
+    relin_rot_ = rot;
+    relin_trans_ = trans;
+  }
   size_t photoFactorsInWindow() const
   {
     size_t n = 0;
@@ -541,7 +551,11 @@ private:
         wc.prior_info[3 + p] = 1.0 / (st * st);
       }
       wc.damping = 1e-9;
-      const ICPFactor::WindowResult r = ICPFactor::optimiseWindow(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc);
+      ICPFactor::WindowRelin rl;
+      rl.rot = relin_rot_;
+      rl.trans = relin_trans_;
+      const ICPFactor::WindowResult r = window_relin_ ? ICPFactor::optimiseWindowRelin(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc, rl)
+                                                      : ICPFactor::optimiseWindow(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc);
       if (r.iters != update_iters_) throw std::runtime_error("replay::solve: singular system");
       std::vector<double> fs;
       for (size_t i = 0; i < nW; ++i) {
@@ -557,7 +571,8 @@ private:
       throw std::runtime_error("replay: device_window is offered for lidar::ICPFactor only");
     }
   }
-  bool device_window_ = false;
+  bool device_window_ = false, window_relin_ = false;
+  double relin_rot_ = 0.0, relin_trans_ = 0.0;
   int window_, update_iters_;
   double Wb_[6];
   size_t first_k_ = 0;
@@ -627,7 +642,9 @@ public:
     Smoother smoother(cfg_.window, cfg_.update_iters, cfg_.between_sigma_rot, cfg_.between_sigma_trans);
     smoother.setPhotoWindow(cfg_.photo_window);
     if (cfg_.device_window && cfg_.photometric) throw std::runtime_error("replay: device_window is not offered with the photometric factor enabled");
+    if (cfg_.window_relin && !cfg_.device_window) throw std::runtime_error("replay: window_relin is only offered with device_window");
     smoother.setDeviceWindow(cfg_.device_window);
+    smoother.setWindowRelin(cfg_.window_relin, cfg_.window_relin_rot, cfg_.window_relin_trans);
     std::deque<Live> & win = smoother.win;
     std::vector<RT> kf_poses;
     State prev = state0;

@@ -74,6 +74,10 @@ class ReplayConfig:
     # assembly, block-tridiagonal solve, retraction) instead of a batched linearize, a numpy solve and the retractions per
     # iteration.  Without the photometric factor only; HIP backend and the native FixedLagReplay
     device_window: bool = False
+    # with device_window: (rot, trans) in rad and m — a factor of the window is evaluated again only once its pose has moved past
+    # these thresholds from the pose of its last evaluation within the call (mh_icp_window_optimise_relin; the reference's ISAM2
+    # runs with 1.75e-2, 5e-3).  None: every factor every iteration.  Refused without device_window
+    window_relin: tuple = None
     reg: dict = field(default_factory=synth.enwide_config)
     photo: dict = None
 
@@ -273,11 +277,12 @@ class HipBackend:
         rs = self.capi.linearize_batch(factors, [p[0] for p in poses], [p[1] for p in poses])
         return [(np.asarray(r["H_ss"]).reshape(6, 6), np.asarray(r["b_s"]), float(r["f"])) for r in rs]
 
-    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping):
+    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping, relin=None):
         """device_window: the smoother's loop over the window as one call; the poses after it and the cost before each iteration"""
         cfg = self.capi.make_window_config(iters=iters, between_info=between_info, prior_info=prior_info, damping=damping)
         I3, z3 = np.eye(3), np.zeros(3)
-        r = self.capi.optimise_window(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs])
+        kw = {} if relin is None else dict(relin=relin)
+        r = self.capi.optimise_window(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs], **kw)
         if r["iters"] != iters:
             raise np.linalg.LinAlgError("Singular matrix")
         return [(r["R"][i], r["t"][i]) for i in range(len(factors))], [row["f"] for row in r["trace"]]
@@ -374,6 +379,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
     import subprocess
     import sys
     from . import build
+    if cfg.window_relin is not None and not cfg.device_window:
+        raise RuntimeError("window_relin is only offered with device_window")
     exe = build.build_replay_native()
     path = os.path.join(workdir, "replay_input.bin")
     write_native_input(path, cfg, scans, rng_seed)
@@ -386,7 +393,7 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
     if sharded_rccl:
         mode = ["sharded-rccl"]
     if cfg.device_window:
-        mode = mode + ["device-window"]
+        mode = mode + ["device-window" if cfg.window_relin is None else "device-window-relin=%r,%r" % (float(cfg.window_relin[0]), float(cfg.window_relin[1]))]
     if cfg.device_poses:
         mode = mode + ["device-poses"]
     out = subprocess.run([exe, path, str(repeats)] + mode, capture_output=True, text=True, timeout=timeout, env=env)
@@ -405,6 +412,8 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     scans = scans if scans is not None else make_scans(cfg)
     if cfg.device_poses and not hasattr(backend, "deskew_imu_and_preprocess"):
         raise ValueError("device_poses needs a backend that keeps the pose table on the device (HipBackend)")
+    if cfg.window_relin is not None and not cfg.device_window:
+        raise ValueError("window_relin is only offered with device_window")
     if cfg.device_window and cfg.photometric:
         raise ValueError("device_window is not offered with the photometric factor enabled")
     if cfg.device_window and not hasattr(backend, "optimise_window"):
@@ -466,7 +475,8 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
             loose = win[0]["k"] == 0 and k < cfg.window
             sr, st = (np.deg2rad(1.0), 0.1) if loose else (1e-4, 1e-4)
             new_poses, fs = backend.optimise_window([w["f"] for w in win], [(w["R"], w["t"]) for w in win], [None] + [w["Z"] for w in win[1:]],
-                                                    cfg.update_iters, list(np.diag(Wb)), [1.0 / sr**2] * 3 + [1.0 / st**2] * 3, 1e-9)
+                                                    cfg.update_iters, list(np.diag(Wb)), [1.0 / sr**2] * 3 + [1.0 / st**2] * 3, 1e-9,
+                                                    **({} if cfg.window_relin is None else dict(relin=tuple(cfg.window_relin))))
             for w, (R_n, t_n) in zip(win, new_poses):
                 w["R"], w["t"] = R_n, t_n
         else:
