@@ -24,6 +24,7 @@ SOURCES = [
     ("order_kernels.hip", []),
     ("scan_kernels.hip", ["-ffp-contract=off"]),
     ("mh_api.hip", []),
+    ("chain_api.hip", []),
     ("map_kernels.hip", ["-ffp-contract=off"]),
     ("map_api.hip", []),
     ("shard_kernels.hip", []),

@@ -1,5 +1,5 @@
 // One Gauss-Newton step of a scan-to-map alignment (mh_icp_align): from the 28 Hessian sums K3 folded for a unary factor to
-// the next pose.  Plain fp64 functions for the device (align_kernels.hip: icp_align_step_kernel) and the host (mh_api.hip's
+// the next pose.  Plain fp64 functions for the device (align_kernels.hip: icp_align_step_kernel) and the host (chain_api.hip's
 // argument checks, tests/cpp/align_step.cpp under g++); both are compiled without floating-point contraction.
 //
 // What is repeated here of the host epilogue of linearize() (mh_api.hip: finish_result) is exactly what decides the step:

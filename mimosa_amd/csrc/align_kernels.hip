@@ -1,4 +1,4 @@
-// icp_align_step_kernel: the link between two K3 launches of an mh_icp_align chain (mh_api.hip).  One workgroup of one wave,
+// icp_align_step_kernel: the link between two K3 launches of an mh_icp_align chain (chain_api.hip).  One workgroup of one wave,
 // launched behind each K3 (batch form, tail = 1: its last workgroup folds the rows and publishes the 28 sums + 4 counters as
 // flagged words — here into a device-resident slot).  The step turns the sums into the next pose (align_device.hpp), writes it
 // into the argument block of the K3 launch queued behind it, and publishes the iteration's sums and its trace row to the

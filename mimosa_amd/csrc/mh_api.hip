@@ -19,7 +19,6 @@
 #include <vector>
 
 #include "../../include/mimosa_hip.h"
-#include "align_device.hpp"
 #include "icp_device.hpp"
 #include "math3.hpp"
 #include "mh_internal.hpp"
@@ -327,35 +326,6 @@ int mh_timer_end(mh_ctx * ctx, float * ms)
   return guarded(ctx, "mh_timer_end", [&]() -> int { return mh_timer_end_impl(ctx, ms); });
 }
 
-}  // extern "C"
-
-// mh_icp_align's block of device memory (mh_icp::d_align) and the pinned staging of its first part (h_align):
-// [grid prefix, 64 B | AlignState, 192 B | 64 argument blocks | 256 B that load_uniform may read past the last block |
-//  64 landing slots of 32 flagged words for K3's sums and counters]
-constexpr size_t kAlignBlocksAt = 256;
-constexpr size_t kAlignStageBytes = kAlignBlocksAt + sizeof(mh::IcpArgs) * kMaxPending;
-constexpr size_t kAlignLlAt = (kAlignStageBytes + 256 + 255) & ~size_t(255);
-constexpr size_t kAlignLlWords = 32;
-constexpr size_t kAlignBytes = kAlignLlAt + kAlignLlWords * sizeof(uint4) * kMaxPending;
-static_assert(sizeof(mh::AlignState) <= 192 && mh::kRowWords <= mh::kLlEig, "mh_icp_align layout");
-
-// mh_icp_window_optimise's block of device memory (mh_ctx::d_window) and the pinned staging of its first part (h_window):
-// [grid prefixes, 256 B | WindowState | iters x n_slots argument blocks | 256 B that load_uniform may read past the last block |
-//  one landing slot of 32 flagged words per pose for K3's sums and counters (every iteration's words carry its own number) |
-//  WindowRelin, which the steps of an mh_icp_window_optimise_relin chain keep among themselves]
-constexpr size_t kWinStateAt = 256;
-constexpr size_t kWinBlocksAt = 3584;
-constexpr size_t kWinStageBytes = kWinBlocksAt + sizeof(mh::IcpArgs) * mh::kWindowMax * kMaxPending;
-constexpr size_t kWinLlAt = (kWinStageBytes + 256 + 255) & ~size_t(255);
-constexpr size_t kWinRelinAt = kWinLlAt + 32 * sizeof(uint4) * mh::kWindowMax;
-constexpr size_t kWinBytes = kWinRelinAt + ((sizeof(mh::WindowRelin) + 255) & ~size_t(255));
-constexpr size_t kWinRowWords = 256;  // flagged words per iteration's row in h_window_rows
-constexpr size_t kWinMaskWord = kWinRowWords - 1;  // of which the last: the evaluated mask of an mh_icp_window_optimise_relin iteration
-static_assert(mh::kWRowPose + 12 * mh::kWindowMax <= static_cast<int>(kWinMaskWord) && kWinRelinAt % 16 == 0, "mh_icp_window_optimise_relin layout");
-static_assert(kWinStateAt + sizeof(mh::WindowState) <= kWinBlocksAt && mh::kWRowPose + 12 * mh::kWindowMax <= static_cast<int>(kWinRowWords) &&
-                MH_WINDOW_MAX == mh::kWindowMax, "mh_icp_window_optimise layout");
-
-extern "C" {
 // ---- factor ------------------------------------------------------------------------------------
 static int icp_alloc(mh_icp * icp)
 {
@@ -881,14 +851,12 @@ static bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, l
   return true;
 }
 
-static int align_wait(mh_icp * icp);  // (below: mh_icp_align)
-
 static int mh_icp_wait_impl(mh_icp * icp)
 {
   const double tw_enter = g_wt.on ? WaitTrace::now() : 0.0;
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_wait: icp is NULL");
   if (icp->in_window) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_wait: the factor is in a window call: mh_icp_window_wait collects it");
-  if (icp->align.active) return align_wait(icp);
+  if (icp->align.active) return mhi::align_wait(icp);
   mh_ctx * ctx = icp->ctx;
   MH_HIP(ctx, mh_enter(ctx));
   // Every value a call produces arrives in mapped pinned memory tagged with the call's sequence number: the host polls the
@@ -949,35 +917,6 @@ int mh_icp_linearize(mh_icp * icp, const double R_src[9], const double t_src[3],
   return guarded(icp ? icp->ctx : nullptr, "mh_icp_linearize", [&]() -> int { return mh_icp_linearize_impl(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out); });
 }
 
-// Launch groups of a window: the factors that share a kernel instantiation — workgroup size (256 threads up to 65 536 points,
-// 512 above: so every factor reduces in exactly the order of a separate call), k == 5 or the generic k <= 8 path, neighbour
-// mode, unary / binary.  Shared by mh_icp_linearize_batch and mh_icp_window_optimise, which therefore run a window's factors
-// in the same classes.
-static std::vector<LaunchGroup> window_launch_groups(mh_icp * const * icps, size_t n_factors)
-{
-  std::vector<LaunchGroup> groups;
-  long long total_points = 0;  // the class of a small cloud depends on how full the machine is: the whole window's points
-  for (size_t f = 0; f < n_factors; ++f) total_points += static_cast<long long>(icps[f]->n);
-  // (more factors than ride in the kernel-argument segment: the staged launch form has the one-lane-per-point classes only)
-  const bool maybe_staged = n_factors > static_cast<size_t>(mh::kBatchInline);
-  for (size_t f = 0; f < n_factors; ++f) {
-    const mh_icp * c = icps[f];
-    if (c->n == 0) continue;
-    const int k = c->cfg.num_corres_points == 5 ? 5 : 8, n_off = c->map->n_off;
-    int tpb = mh::linearize_class(static_cast<int>(c->n), static_cast<int>(c->cfg.num_corres_points), false, total_points);
-    if (maybe_staged && tpb < 256) tpb = 256;
-    LaunchGroup * g = nullptr;
-    for (LaunchGroup & q : groups)
-      if (q.tpb == tpb && q.k == k && q.n_off == n_off && q.binary == c->binary) g = &q;
-    if (!g) {
-      groups.push_back(LaunchGroup{tpb, k, n_off, c->binary, {}});
-      g = &groups.back();
-    }
-    g->members.push_back(f);
-  }
-  return groups;
-}
-
 // ---- all live factors of the sliding window in two launches ------------------------------------------------
 // graph::Manager::defineNoLock (src/graph/manager.cpp:585-588): smoother_->update() + additional_update_iterations
 // re-linearize EVERY live ICPFactor whose pose moved; GTSAM calls them one after the other.  Here one K3 grid
@@ -1006,7 +945,7 @@ static int mh_icp_linearize_batch_impl(mh_icp * const * icps, size_t n_factors, 
   // above: so every factor reduces in exactly the order of a separate call), k == 5 or the generic k <= 8 path, neighbour
   // mode, unary / binary.  One K3b (+ one K4b) launch per non-empty group; a window of like factors — the usual case — is
   // one group.  Staging: [IcpArgs x 64 | LocArgs x 64 | grid prefixes], host-pinned + a device copy the kernels read.
-  std::vector<LaunchGroup> groups = window_launch_groups(icps, n_factors);
+  std::vector<LaunchGroup> groups = mhi::window_launch_groups(icps, n_factors);
   const size_t ab = sizeof(mh::IcpArgs) * kMaxBatch, lb = sizeof(mh::LocArgs) * kMaxBatch, sb = sizeof(int) * 4 * (kMaxBatch + 1);  // two prefix tables (K3b, K4b), each up to factors + groups entries
   const size_t total = ((ab + lb + sb + 255) & ~size_t(255)) + 256;
   if (!ctx->h_batch) MH_HIP(ctx, hipHostMalloc(&ctx->h_batch, total, hipHostMallocDefault));
@@ -1126,661 +1065,6 @@ int mh_icp_linearize_batch(mh_icp * const * icps, size_t n_factors, const double
                            const double * R_tgt, const double * t_tgt, const double * g_unit, mh_icp_result * out)
 {
   return guarded((icps && n_factors && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_linearize_batch", [&]() -> int { return mh_icp_linearize_batch_impl(icps, n_factors, R_src, t_src, R_tgt, t_tgt, g_unit, out); });
-}
-
-// ---- scan-to-map alignment: K3, step, K3, step ... on the context's stream, one wait ---------------------------------------
-// The argument blocks of every iteration sit in device memory (d_align), filled here except R, t of the iterations after the
-// first, which the step kernel in front of each writes (align_kernels.hip).  K3 runs in the staged batch form with one factor
-// and the class a call of its own would get, tail = 1, its flagged words landing in a device slot; the step forwards them and
-// its own row to the iteration's slot of the factor's pinned ring.
-static bool align_read_row(const mh_icp * icp, int i, long spin_ns, double * row)
-{
-  const uint4 * base = icp->h_ll + static_cast<size_t>(i) * icp->ll_words + mh::kLlSums;
-  mh::SpinBudget spin(spin_ns);  // one budget for the whole row
-  for (int w = mh::kRowWords - 1; w >= 0; --w)
-    if (!spin.until([&] { return mh::ll_read(reinterpret_cast<const uint64_t *>(base + w), icp->align.seq[i], row[w]); })) return false;
-  return true;
-}
-
-// wait for the row of iteration i (the last one queued so far): the values themselves, the stream behind them
-static int align_wait_row(mh_icp * icp, int i, double * row)
-{
-  mh_ctx * ctx = icp->ctx;
-  if (align_read_row(icp, i, 50000000L, row)) return MH_OK;  // 50 ms: 64 iterations of a large cloud are a few
-  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (align_read_row(icp, i, 2000000L, row)) return MH_OK;
-  return fail(ctx, MH_ERR_HIP, "mh_icp_align: the stream drained without the chain's results");
-}
-
-static void align_abandon(mh_icp * icp)
-{
-  (void)hipStreamSynchronize(icp->ctx->stream);
-  icp->align.active = false;
-  icp->n_pending = 0;
-}
-
-static int align_begin(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
-                       mh_icp_align_result * out)
-{
-  if (!icp || !R0 || !t0 || !g_unit || !cfg || !out) return fail(icp ? icp->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_align: NULL argument");
-  mh_ctx * ctx = icp->ctx;
-  if (icp->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align: unary factors only");
-  if (icp->n_pending || icp->align.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: the factor has calls in flight");
-  if (cfg->max_iters < 1 || cfg->max_iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: max_iters must be in 1..64");
-  if (!(cfg->eps_rot >= 0.0) || !(cfg->eps_trans >= 0.0) || !(cfg->damping >= 0.0) || !(cfg->prior_sigma_rot >= 0.0) ||
-      !(cfg->prior_sigma_trans >= 0.0) || cfg->check_every < 0)
-    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: eps, damping, prior sigmas and check_every must be >= 0");
-  if (icp->no_order || icp->cap_n > icp->n) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align: not for the factors of the map-sharded path");
-  if (icp->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: the factor has no points");
-  MH_HIP(ctx, mh_enter(ctx));
-  MH_HIP(ctx, icp->d_align.reserve(kAlignBytes, ctx->stream, false));
-  if (!icp->h_align) MH_HIP(ctx, AllocCache::alloc_pinned(&icp->h_align, kAlignStageBytes));
-
-  // the argument block of a components-off linearize at (R0, t0); what linearize_prepare changes on the handle is put back —
-  // the chain keeps its own books
-  mh::IcpArgs a;
-  {
-    mh::LocArgs l;
-    bool timed = false;
-    mh_icp_result scratch;
-    LinearizeTxn txn(icp);
-    const int rc = linearize_prepare(icp, R0, t0, nullptr, nullptr, g_unit, &scratch, false, a, l, timed);
-    if (rc != MH_OK) return rc;
-  }
-  a.rec = nullptr;
-  a.rec_n = 0;
-  a.tail = 1;
-
-  mh_icp::AlignCall & c = icp->align;
-  c.cfg = *cfg;
-  c.out = out;
-  std::memcpy(c.R0, R0, sizeof(c.R0));
-  for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
-  c.queued = 0;
-  c.count0 = icp->linearize_count;
-  c.cold0 = icp->cold;
-  mh::AlignParams & p = c.p;
-  for (int i = 0; i < 3; ++i) p.gz[i] = c.gz[i];
-  p.eps_rot = cfg->eps_rot;
-  p.eps_trans = cfg->eps_trans;
-  p.damping = cfg->damping;
-  p.prior_rot = cfg->prior_sigma_rot > 0.0 ? 1.0 / (cfg->prior_sigma_rot * cfg->prior_sigma_rot) : 0.0;
-  p.prior_trans = cfg->prior_sigma_trans > 0.0 ? 1.0 / (cfg->prior_sigma_trans * cfg->prior_sigma_trans) : 0.0;
-  p.thresh_rot = icp->cfg.degen_thresh_rot;
-  p.thresh_trans = icp->cfg.degen_thresh_trans;
-  p.reg_4_dof = icp->cfg.reg_4_dof;
-  p.project_on_degeneracy = icp->cfg.project_on_degneneracy;
-
-  char * h = static_cast<char *>(icp->h_align);
-  char * d = static_cast<char *>(icp->d_align.p);
-  const int ppw = mh::linearize_class(a.n, a.k, false);
-  int * start = reinterpret_cast<int *>(h);
-  start[0] = 0;
-  start[1] = mh::class_grid(a.n, ppw);
-  mh::AlignState st;
-  std::memset(&st, 0, sizeof(st));
-  std::memcpy(st.R, a.R, sizeof(st.R));
-  std::memcpy(st.t, a.t, sizeof(st.t));
-  std::memcpy(h + 64, &st, sizeof(st));
-  auto * blocks = reinterpret_cast<mh::IcpArgs *>(h + kAlignBlocksAt);
-  for (int i = 0; i < cfg->max_iters; ++i) {
-    mh::IcpArgs b = a;
-    b.cold = (i == 0 && c.cold0) ? 1 : 0;
-    b.seq = c.seq[i] = next_call_seq();
-    b.ll = reinterpret_cast<uint4 *>(d + kAlignLlAt) + static_cast<size_t>(i) * kAlignLlWords;
-    blocks[i] = b;
-  }
-  MH_HIP(ctx, hipMemcpyAsync(d, h, kAlignBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(cfg->max_iters), hipMemcpyHostToDevice, ctx->stream));
-  c.active = true;
-  icp->n_pending = kMaxPending;  // the chain holds the whole ring
-  return MH_OK;
-}
-
-// iterations [queued, upto) onto the stream
-static int align_enqueue(mh_icp * icp, int upto)
-{
-  mh_ctx * ctx = icp->ctx;
-  mh_icp::AlignCall & c = icp->align;
-  char * d = static_cast<char *>(icp->d_align.p);
-  auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + kAlignBlocksAt);
-  const int n = static_cast<int>(icp->n), k = static_cast<int>(icp->cfg.num_corres_points);
-  const int ppw = mh::linearize_class(n, k, false), grid = mh::class_grid(n, ppw);
-  for (int i = c.queued; i < upto; ++i) {
-    hipError_t e = mh::launch_linearize_batch(blocks + i, reinterpret_cast<const int *>(d), 1, grid, ppw, k == 5 ? 5 : 8, icp->map->n_off, false, ctx->stream);
-    if (e == hipSuccess) {
-      mh::AlignStepArgs s;
-      s.ll_dev = reinterpret_cast<const uint4 *>(d + kAlignLlAt) + static_cast<size_t>(i) * kAlignLlWords;
-      s.ll_host = icp->d_h_ll + static_cast<size_t>(i) * icp->ll_words;
-      s.next = i + 1 < c.cfg.max_iters ? blocks + i + 1 : nullptr;
-      s.state = reinterpret_cast<mh::AlignState *>(d + 64);
-      s.p = c.p;
-      s.seq = c.seq[i];
-      e = mh::launch_align_step(s, ctx->stream);
-    }
-    if (e != hipSuccess) {
-      align_abandon(icp);
-      return hip_fail(ctx, e, "mh_icp_align: launch");
-    }
-    c.queued = i + 1;
-  }
-  return MH_OK;
-}
-
-// every queued iteration has run (the caller waited for the last row): the result, and the handle's books
-static int align_finish(mh_icp * icp)
-{
-  mh_ctx * ctx = icp->ctx;
-  mh_icp::AlignCall & c = icp->align;
-  mh_icp_align_result * out = c.out;
-  std::memset(static_cast<void *>(out), 0, sizeof(*out));
-  int iters = 0, converged = 0;
-  for (int i = 0; i < c.queued; ++i) {
-    double row[mh::kRowWords];
-    const int rc = align_wait_row(icp, i, row);
-    if (rc != MH_OK) {
-      align_abandon(icp);
-      return rc;
-    }
-    const int flags = static_cast<int>(row[mh::kRowFlags]);
-    if (flags & 4) break;  // queued behind the stop: nothing was evaluated, here or later
-    mh_icp_align_trace & tr = out->trace[iters++];
-    tr.f = row[mh::kRowF];
-    tr.step_rot = row[mh::kRowStepRot];
-    tr.step_trans = row[mh::kRowStepTrans];
-    tr.n_knn = static_cast<int64_t>(row[mh::kRowKnn]);
-    tr.degenerate = static_cast<int32_t>(row[mh::kRowBits]);
-    std::memcpy(tr.R, row + mh::kRowR, sizeof(tr.R));
-    std::memcpy(tr.t, row + mh::kRowT, sizeof(tr.t));
-    converged = (flags & 2) ? 1 : 0;
-  }
-  if (iters == 0) {  // (the first queued iteration is always evaluated: its row never carries the flag)
-    align_abandon(icp);
-    return fail(ctx, MH_ERR_HIP, "mh_icp_align: no iteration was evaluated");
-  }
-  int rc_all = MH_OK;
-  if (out->trace[iters - 1].degenerate & 8) rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_align: a step did not find its K3's sums");
-  out->iters = iters;
-  out->converged = converged;
-  std::memcpy(out->R, out->trace[iters - 1].R, sizeof(out->R));
-  std::memcpy(out->t, out->trace[iters - 1].t, sizeof(out->t));
-  // first / last: the host epilogue of linearize() on the sums K3 folded at the initial and at the last evaluated pose
-  for (int which = 0; which < 2 && rc_all == MH_OK; ++which) {
-    const int i = which == 0 ? 0 : iters - 1;
-    PendingCall pc{};
-    pc.out = nullptr;
-    std::memcpy(pc.R, i == 0 ? c.R0 : out->trace[i - 1].R, sizeof(pc.R));
-    std::memcpy(pc.gz, c.gz, sizeof(pc.gz));
-    pc.linearize_count = c.count0 + i + 1;
-    pc.seq = c.seq[i];
-    pc.components = false;
-    pc.ev[0] = pc.ev[1] = pc.ev[2] = nullptr;
-    mh::DeviceResult dres;
-    if (!collect_call(icp, i, pc, 2000000L, dres)) {
-      rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_align: an iteration's sums did not arrive");
-      break;
-    }
-    mh_icp_result * r = which == 0 ? &out->first : &out->last;
-    finish_result(icp, dres, pc, r);
-    r->gpu_ms_linearize = r->gpu_ms_localizability = -1.0f;
-  }
-  icp->linearize_count = c.count0 + iters;
-  icp->cold = false;
-  icp->n_pending = 0;
-  c.active = false;
-  return rc_all;
-}
-
-static int align_wait(mh_icp * icp)
-{
-  mh_ctx * ctx = icp->ctx;
-  MH_HIP(ctx, mh_enter(ctx));
-  if (icp->align.queued > 0) {
-    double row[mh::kRowWords];
-    const int rc = align_wait_row(icp, icp->align.queued - 1, row);
-    if (rc != MH_OK) {
-      align_abandon(icp);
-      return rc;
-    }
-  }
-  return align_finish(icp);
-}
-
-static int mh_icp_align_impl(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
-                             mh_icp_align_result * out, bool blocking)
-{
-  int rc = align_begin(icp, R0, t0, g_unit, cfg, out);
-  if (rc != MH_OK) return rc;
-  const int max_iters = cfg->max_iters;
-  const int chunk = (blocking && cfg->check_every > 0) ? cfg->check_every : max_iters;
-  while (icp->align.queued < max_iters) {
-    const int upto = std::min(icp->align.queued + chunk, max_iters);
-    rc = align_enqueue(icp, upto);
-    if (rc != MH_OK) return rc;
-    if (!blocking) return MH_OK;  // (everything is queued: chunk == max_iters)
-    double row[mh::kRowWords];
-    rc = align_wait_row(icp, upto - 1, row);
-    if (rc != MH_OK) {
-      align_abandon(icp);
-      return rc;
-    }
-    if (static_cast<int>(row[mh::kRowFlags]) & 1) break;  // stopped: nothing more to queue
-  }
-  return align_finish(icp);
-}
-int mh_icp_align(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
-                 mh_icp_align_result * out)
-{
-  return guarded(icp ? icp->ctx : nullptr, "mh_icp_align", [&]() -> int { return mh_icp_align_impl(icp, R0, t0, g_unit, cfg, out, true); });
-}
-int mh_icp_align_async(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
-                       mh_icp_align_result * out)
-{
-  return guarded(icp ? icp->ctx : nullptr, "mh_icp_align_async", [&]() -> int { return mh_icp_align_impl(icp, R0, t0, g_unit, cfg, out, false); });
-}
-
-// ---- fixed-lag window: [K3 batch launches, step] x iters on the context's stream, one wait --------------------------------
-// The argument blocks of every iteration sit in device memory the context owns (d_window), filled here except R, t of the
-// iterations after the first, which the step kernel in front of each writes (window_kernels.hip).  K3 runs in the staged batch
-// form, one launch per launch group, tail = 1, its flagged words landing in a device slot per pose; the step forwards them to
-// the iteration's slot of each factor's pinned ring and publishes its own row to the context's rows.
-static bool window_read_row(const mh_ctx * ctx, int it, long spin_ns, double * row)
-{
-  const WindowCall & c = ctx->window;
-  const uint4 * base = ctx->h_window_rows + static_cast<size_t>(it) * kWinRowWords;
-  mh::SpinBudget spin(spin_ns);  // one budget for the whole row
-  for (int w = mh::window_row_words(c.W) - 1; w >= 0; --w)
-    if (!spin.until([&] { return mh::ll_read(reinterpret_cast<const uint64_t *>(base + w), c.seq[it], row[w]); })) return false;
-  return true;
-}
-
-static int window_wait_row(mh_ctx * ctx, int it, double * row)
-{
-  if (window_read_row(ctx, it, 50000000L, row)) return MH_OK;
-  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (window_read_row(ctx, it, 2000000L, row)) return MH_OK;
-  return fail(ctx, MH_ERR_HIP, "mh_icp_window_optimise: the stream drained without the chain's results");
-}
-
-static void window_abandon(mh_ctx * ctx)
-{
-  (void)hipStreamSynchronize(ctx->stream);
-  window_release(ctx);
-}
-
-static int window_begin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses,
-                        const mh_icp_window_relin * relin, uint32_t * evaluated_mask)
-{
-  mh_ctx * ctx = (icps && W && icps[0]) ? icps[0]->ctx : nullptr;  // (where the message goes: mh_last_error(ctx) as well as mh_last_error(NULL))
-  if (!icps || !R || !t || !has_Z || !g_unit || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
-  if (W < 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the window has no pose");
-  if (W > static_cast<size_t>(mh::kWindowMax)) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: at most 16 poses per call");
-  for (size_t f = 0; f < W; ++f)
-    if (!icps[f]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL factor");
-  ctx = icps[0]->ctx;
-  if (ctx->window.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the context has a window call in flight");
-  for (size_t f = 0; f < W; ++f) {
-    const mh_icp * c = icps[f];
-    if (c->ctx != ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: factors of different contexts");
-    if (c->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: unary factors only");
-    if (c->no_order || c->cap_n > c->n) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: not for the factors of the map-sharded path");
-    if (c->n_pending || c->align.active || c->in_window) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: a factor has calls in flight");
-    for (size_t g = 0; g < f; ++g)
-      if (icps[g] == c) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the same factor twice");
-  }
-  if (cfg->iters < 1 || cfg->iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: iters must be in 1..64");
-  bool ok = cfg->damping >= 0.0 && cfg->eps_rot >= 0.0 && cfg->eps_trans >= 0.0 && cfg->check_every >= 0;
-  for (int i = 0; i < 6; ++i) ok = ok && cfg->between_info[i] >= 0.0 && cfg->prior_info[i] >= 0.0;
-  if (!ok) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: eps, damping, between_info, prior_info and check_every must be >= 0");
-  if (relin && !(relin->relin_rot >= 0.0 && relin->relin_rot <= std::numeric_limits<double>::max() && relin->relin_trans >= 0.0 &&
-                 relin->relin_trans <= std::numeric_limits<double>::max()))
-    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: relin_rot and relin_trans must be finite and >= 0");
-  unsigned int zmask = 0;
-  for (size_t f = 1; f < W; ++f)
-    if (has_Z[f]) zmask |= 1u << f;
-  if (zmask && (!Z_R || !Z_t)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL between measurements");
-  MH_HIP(ctx, mh_enter(ctx));
-  if (!ctx->h_window) MH_HIP(ctx, hipHostMalloc(&ctx->h_window, kWinStageBytes, hipHostMallocDefault));
-  if (!ctx->d_window) MH_HIP(ctx, hipMalloc(&ctx->d_window, kWinBytes));
-  if (!ctx->h_window_rows) {
-    MH_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_window_rows), kWinRowWords * sizeof(uint4) * kMaxPending, hipHostMallocMapped));
-    std::memset(ctx->h_window_rows, 0, kWinRowWords * sizeof(uint4) * kMaxPending);
-    MH_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->d_window_rows), ctx->h_window_rows, 0));
-  }
-
-  WindowCall & c = ctx->window;
-  c.W = static_cast<int>(W);
-  c.iters = cfg->iters;
-  c.queued = 0;
-  c.out = out;
-  c.trace_poses = trace_poses;
-  c.relin = relin != nullptr;
-  c.relin_rot = relin ? relin->relin_rot : 0.0;
-  c.relin_trans = relin ? relin->relin_trans : 0.0;
-  c.evaluated_mask = evaluated_mask;
-  for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
-  // launch groups in slot order, as mh_icp_linearize_batch lays the same window out
-  const std::vector<LaunchGroup> groups = window_launch_groups(icps, W);
-  c.launches.clear();
-  c.n_slots = 0;
-  for (size_t f = 0; f < W; ++f) c.slot[f] = -1;
-  for (const LaunchGroup & g : groups) {
-    WindowLaunch wl{g.tpb, g.k, g.n_off, c.n_slots, static_cast<int>(g.members.size()), 0};
-    for (size_t f : g.members) c.slot[f] = c.n_slots++;
-    c.launches.push_back(wl);
-  }
-
-  char * h = static_cast<char *>(ctx->h_window);
-  char * d = static_cast<char *>(ctx->d_window);
-  auto * blocks = reinterpret_cast<mh::IcpArgs *>(h + kWinBlocksAt);
-  mh::WindowState st;
-  std::memset(&st, 0, sizeof(st));
-  for (int it = 0; it < cfg->iters; ++it) c.seq[it] = next_call_seq();
-  // per factor the argument block of a components-off linearize at its pose; what linearize_prepare changes on the handle is
-  // put back — the chain keeps its own books.  (linearize_prepare follows the factor's components setting and may reserve the
-  // record of a K4 pass the chain never runs: a.rec is cleared below.  c.R0 keeps the caller's R for the epilogue of `first`;
-  // the chain starts from a.R, which for a unary factor is the same matrix.)
-  for (size_t f = 0; f < W; ++f) {
-    mh_icp * icp = icps[f];
-    c.icps[f] = icp;
-    c.count0[f] = icp->linearize_count;
-    std::memcpy(c.R0[f], R + 9 * f, sizeof(c.R0[f]));
-    std::memcpy(st.R[f], R + 9 * f, sizeof(st.R[f]));
-    std::memcpy(st.t[f], t + 3 * f, sizeof(st.t[f]));
-    if ((zmask >> f) & 1u) {
-      std::memcpy(st.ZR[f], Z_R + 9 * f, sizeof(st.ZR[f]));
-      std::memcpy(st.Zt[f], Z_t + 3 * f, sizeof(st.Zt[f]));
-    }
-    if (icp->n == 0) continue;
-    mh::IcpArgs a;
-    const bool cold0 = icp->cold;
-    {
-      mh::LocArgs l;
-      bool timed = false;
-      mh_icp_result scratch;
-      LinearizeTxn txn(icp);
-      const int rc = linearize_prepare(icp, R + 9 * f, t + 3 * f, nullptr, nullptr, g_unit, &scratch, false, a, l, timed);
-      if (rc != MH_OK) return rc;
-    }
-    a.rec = nullptr;
-    a.rec_n = 0;
-    a.tail = 1;
-    a.ll = reinterpret_cast<uint4 *>(d + kWinLlAt) + 32 * f;
-    std::memcpy(st.R[f], a.R, sizeof(st.R[f]));
-    std::memcpy(st.t[f], a.t, sizeof(st.t[f]));
-    for (int it = 0; it < cfg->iters; ++it) {
-      mh::IcpArgs b = a;
-      b.cold = (it == 0 && cold0) ? 1 : 0;
-      b.seq = c.seq[it];
-      blocks[static_cast<size_t>(it) * c.n_slots + c.slot[f]] = b;
-    }
-  }
-  int * prefix = reinterpret_cast<int *>(h);
-  for (size_t gi = 0; gi < c.launches.size(); ++gi) {
-    WindowLaunch & wl = c.launches[gi];
-    int * start = prefix + wl.first + static_cast<int>(gi);
-    int acc = 0;
-    for (int i = 0; i < wl.n; ++i) {
-      start[i] = acc;
-      acc += mh::class_grid(blocks[wl.first + i].n, wl.tpb);
-    }
-    start[wl.n] = acc;
-    wl.grid = acc;
-  }
-  std::memcpy(h + kWinStateAt, &st, sizeof(st));
-
-  mh::WindowParams & p = c.p;
-  std::memset(&p, 0, sizeof(p));
-  p.W = c.W;
-  p.has_Z = zmask;
-  for (size_t f = 0; f < W; ++f) {
-    const mh_icp * icp = icps[f];
-    if (icp->n) p.have |= 1u << f;
-    if (icp->cfg.reg_4_dof) p.reg_4_dof |= 1u << f;
-    if (icp->cfg.project_on_degneneracy) p.project_on_degeneracy |= 1u << f;
-    p.thresh_rot[f] = icp->cfg.degen_thresh_rot;
-    p.thresh_trans[f] = icp->cfg.degen_thresh_trans;
-  }
-  for (int i = 0; i < 3; ++i) p.gz[i] = c.gz[i];
-  for (int i = 0; i < 6; ++i) {
-    p.Wb[i] = cfg->between_info[i];
-    p.prior[i] = cfg->prior_info[i];
-  }
-  p.damping = cfg->damping;
-  p.eps_rot = cfg->eps_rot;
-  p.eps_trans = cfg->eps_trans;
-
-  MH_HIP(ctx, hipMemcpyAsync(d, h, kWinBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(cfg->iters), hipMemcpyHostToDevice, ctx->stream));
-  c.active = true;
-  for (size_t f = 0; f < W; ++f) {
-    icps[f]->in_window = true;
-    icps[f]->n_pending = kMaxPending;  // the chain holds the whole ring
-  }
-  return MH_OK;
-}
-
-// iterations [queued, upto) onto the stream
-static int window_enqueue(mh_ctx * ctx, int upto)
-{
-  WindowCall & c = ctx->window;
-  char * d = static_cast<char *>(ctx->d_window);
-  auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + kWinBlocksAt);
-  const int * prefix = reinterpret_cast<const int *>(d);
-  for (int it = c.queued; it < upto; ++it) {
-    hipError_t e = hipSuccess;
-    for (size_t gi = 0; gi < c.launches.size() && e == hipSuccess; ++gi) {
-      const WindowLaunch & wl = c.launches[gi];
-      e = mh::launch_linearize_batch(blocks + static_cast<size_t>(it) * c.n_slots + wl.first, prefix + wl.first + static_cast<int>(gi), wl.n, wl.grid, wl.tpb, wl.k,
-                                     wl.n_off, false, ctx->stream);
-    }
-    if (e == hipSuccess) {
-      mh::WindowStepArgs s;
-      std::memset(static_cast<void *>(&s), 0, sizeof(s));
-      s.ll_dev = reinterpret_cast<const uint4 *>(d + kWinLlAt);
-      for (int i = 0; i < c.W; ++i) {
-        s.ll_host[i] = c.icps[i]->n ? c.icps[i]->d_h_ll + static_cast<size_t>(it) * c.icps[i]->ll_words : nullptr;
-        s.slot[i] = static_cast<signed char>(c.slot[i]);
-      }
-      s.row_host = ctx->d_window_rows + static_cast<size_t>(it) * kWinRowWords;
-      s.next = it + 1 < c.iters ? blocks + static_cast<size_t>(it + 1) * c.n_slots : nullptr;
-      s.state = reinterpret_cast<mh::WindowState *>(d + kWinStateAt);
-      s.p = c.p;
-      s.seq = c.seq[it];
-      if (c.relin) {
-        mh::WindowRelinStepArgs ra;
-        std::memset(static_cast<void *>(&ra), 0, sizeof(ra));
-        ra.s = s;
-        ra.relin = reinterpret_cast<mh::WindowRelin *>(d + kWinRelinAt);
-        ra.mask_host = s.row_host + kWinMaskWord;
-        ra.rp.relin_rot = c.relin_rot;
-        ra.rp.relin_trans = c.relin_trans;
-        ra.rp.first = it == 0 ? 1 : 0;
-        e = mh::launch_window_relin_step(ra, ctx->stream);
-      } else {
-        e = mh::launch_window_step(s, ctx->stream);
-      }
-    }
-    if (e != hipSuccess) {
-      window_abandon(ctx);
-      return hip_fail(ctx, e, "mh_icp_window_optimise: launch");
-    }
-    c.queued = it + 1;
-  }
-  return MH_OK;
-}
-
-// every queued iteration has run (the caller waited for the last row): the result, and the handles' books
-static int window_finish(mh_ctx * ctx)
-{
-  WindowCall & c = ctx->window;
-  mh_icp_window_result * out = c.out;
-  std::memset(static_cast<void *>(out), 0, sizeof(*out));
-  const int W = c.W, words = mh::window_row_words(W);
-  std::vector<double> rows(static_cast<size_t>(c.queued) * words);
-  int iters = 0, converged = 0;
-  bool lost = false;
-  for (int it = 0; it < c.queued; ++it) {
-    double * row = rows.data() + static_cast<size_t>(it) * words;
-    const int rc = window_wait_row(ctx, it, row);
-    if (rc != MH_OK) {
-      window_abandon(ctx);
-      return rc;
-    }
-    const int flags = static_cast<int>(row[mh::kWRowFlags]);
-    if (flags & 4) break;  // queued behind the stop: nothing was evaluated, here or later
-    mh_icp_window_trace & tr = out->trace[iters++];
-    tr.f = row[mh::kWRowF];
-    tr.step_rot = row[mh::kWRowStepRot];
-    tr.step_trans = row[mh::kWRowStepTrans];
-    tr.flags = static_cast<int32_t>(row[mh::kWRowBits]) & mh::kAlignSingular;
-    tr.degenerate = static_cast<uint32_t>(row[mh::kWRowDegen]);
-    lost = lost || (static_cast<int>(row[mh::kWRowBits]) & 8);
-    if (c.trace_poses) std::memcpy(c.trace_poses + static_cast<size_t>(it) * W * 12, row + mh::kWRowPose, sizeof(double) * 12 * W);
-    converged = (flags & 2) ? 1 : 0;
-  }
-  if (iters == 0) {  // (the first queued iteration is always evaluated: its row never carries the flag)
-    window_abandon(ctx);
-    return fail(ctx, MH_ERR_HIP, "mh_icp_window_optimise: no iteration was evaluated");
-  }
-  int rc_all = MH_OK;
-  if (lost) rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_window_optimise: a step did not find its K3's sums");
-  out->iters = iters;
-  out->converged = converged;
-  out->n_poses = W;
-  const double * last_row = rows.data() + static_cast<size_t>(iters - 1) * words;
-  for (int i = 0; i < W; ++i) {
-    std::memcpy(out->R + 9 * i, last_row + mh::kWRowPose + 12 * i, sizeof(double) * 9);
-    std::memcpy(out->t + 3 * i, last_row + mh::kWRowPose + 12 * i + 9, sizeof(double) * 3);
-  }
-  // which factors ran K3 in which iteration: all of them, unless the chain's steps decided (the word behind each row).  An
-  // empty factor has no evaluation; its books move with the iterations, as they always did.
-  uint32_t masks[kMaxPending];
-  for (int it = 0; it < iters; ++it) masks[it] = c.p.have;
-  for (int it = 0; it < iters && c.relin && rc_all == MH_OK; ++it) {
-    double m = 0.0;
-    const uint4 * word = ctx->h_window_rows + static_cast<size_t>(it) * kWinRowWords + kWinMaskWord;
-    mh::SpinBudget spin(2000000L);
-    if (!spin.until([&] { return mh::ll_read(reinterpret_cast<const uint64_t *>(word), c.seq[it], m); })) {
-      rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_window_optimise_relin: an iteration's evaluated mask did not arrive");
-      break;
-    }
-    masks[it] = static_cast<uint32_t>(m);
-    if (c.evaluated_mask) c.evaluated_mask[it] = masks[it];
-  }
-  int last_it[mh::kWindowMax], n_eval[mh::kWindowMax];
-  for (int i = 0; i < W; ++i) {
-    last_it[i] = c.icps[i]->n ? 0 : iters - 1;
-    n_eval[i] = c.icps[i]->n ? 0 : iters;
-    for (int it = 0; it < iters && c.icps[i]->n; ++it)
-      if ((masks[it] >> i) & 1u) {
-        last_it[i] = it;
-        n_eval[i] += 1;
-      }
-  }
-  // first / last: the host epilogue of linearize() on the sums K3 folded at the initial and at the last evaluated poses
-  for (int i = 0; i < W && rc_all == MH_OK; ++i) {
-    mh_icp * icp = c.icps[i];
-    for (int which = 0; which < 2; ++which) {
-      const int it = which == 0 ? 0 : last_it[i];
-      PendingCall pc{};
-      pc.out = nullptr;
-      std::memcpy(pc.R, it == 0 ? c.R0[i] : rows.data() + static_cast<size_t>(it - 1) * words + mh::kWRowPose + 12 * i, sizeof(pc.R));
-      std::memcpy(pc.gz, c.gz, sizeof(pc.gz));
-      pc.linearize_count = c.count0[i] + (which == 0 ? 1 : n_eval[i]);
-      pc.seq = icp->n ? c.seq[it] : 0;
-      pc.components = false;
-      pc.ev[0] = pc.ev[1] = pc.ev[2] = nullptr;
-      mh::DeviceResult dres;
-      if (!collect_call(icp, it, pc, 2000000L, dres)) {
-        rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_window_optimise: an iteration's sums did not arrive");
-        break;
-      }
-      mh_icp_result * r = which == 0 ? &out->first[i] : &out->last[i];
-      finish_result(icp, dres, pc, r);
-      r->gpu_ms_linearize = r->gpu_ms_localizability = -1.0f;
-    }
-  }
-  for (int i = 0; i < W; ++i) {
-    c.icps[i]->linearize_count = c.count0[i] + n_eval[i];
-    c.icps[i]->cold = false;
-  }
-  window_release(ctx);
-  return rc_all;
-}
-
-static int mh_icp_window_wait_impl(mh_ctx * ctx)
-{
-  if (!ctx) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_window_wait: ctx is NULL");
-  if (!ctx->window.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_wait: no window call in flight");
-  MH_HIP(ctx, mh_enter(ctx));
-  if (ctx->window.queued > 0) {
-    std::vector<double> row(static_cast<size_t>(mh::window_row_words(ctx->window.W)));
-    const int rc = window_wait_row(ctx, ctx->window.queued - 1, row.data());
-    if (rc != MH_OK) {
-      window_abandon(ctx);
-      return rc;
-    }
-  }
-  return window_finish(ctx);
-}
-
-static int mh_icp_window_optimise_impl(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                                       const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out,
-                                       double * trace_poses, bool blocking, const mh_icp_window_relin * relin = nullptr, uint32_t * evaluated_mask = nullptr)
-{
-  int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask);
-  if (rc != MH_OK) return rc;
-  mh_ctx * ctx = icps[0]->ctx;
-  const int iters = cfg->iters;
-  const int chunk = (blocking && cfg->check_every > 0) ? cfg->check_every : iters;
-  std::vector<double> row(static_cast<size_t>(mh::window_row_words(static_cast<int>(W))));
-  while (ctx->window.queued < iters) {
-    const int upto = std::min(ctx->window.queued + chunk, iters);
-    rc = window_enqueue(ctx, upto);
-    if (rc != MH_OK) return rc;
-    if (!blocking) return MH_OK;  // (everything is queued: chunk == iters)
-    rc = window_wait_row(ctx, upto - 1, row.data());
-    if (rc != MH_OK) {
-      window_abandon(ctx);
-      return rc;
-    }
-    if (static_cast<int>(row[mh::kWRowFlags]) & 1) break;  // stopped: nothing more to queue
-  }
-  return window_finish(ctx);
-}
-int mh_icp_window_optimise(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                           const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses)
-{
-  return guarded((icps && W && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_window_optimise",
-                 [&]() -> int { return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true); });
-}
-int mh_icp_window_optimise_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                                 const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses)
-{
-  return guarded((icps && W && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_window_optimise_async",
-                 [&]() -> int { return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false); });
-}
-int mh_icp_window_optimise_relin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                                 const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
-                                 mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
-{
-  return guarded((icps && W && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_window_optimise_relin", [&]() -> int {
-    if (!relin) return fail((icps && W && icps[0]) ? icps[0]->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: NULL argument");
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, relin, evaluated_mask);
-  });
-}
-int mh_icp_window_optimise_relin_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                                       const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
-                                       mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
-{
-  return guarded((icps && W && icps[0]) ? icps[0]->ctx : nullptr, "mh_icp_window_optimise_relin_async", [&]() -> int {
-    if (!relin) return fail((icps && W && icps[0]) ? icps[0]->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: NULL argument");
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, relin, evaluated_mask);
-  });
-}
-int mh_icp_window_wait(mh_ctx * ctx)
-{
-  return guarded(ctx, "mh_icp_window_wait", [&]() -> int { return mh_icp_window_wait_impl(ctx); });
 }
 
 static int mh_icp_get_state_impl(const mh_icp * icp, int32_t * status, double * means, double * normals)
@@ -2468,7 +1752,7 @@ int mh_icp_create_from_device(mh_ctx * ctx, mh_map * map, const mh_point32 * d_p
 
 }  // extern "C"
 
-// ---- internals shared with shard_api.hip (declared in mh_internal.hpp) ---------------------------------------------
+// ---- internals shared with shard_api.hip and chain_api.hip (declared in mh_internal.hpp) ---------------------------------------------
 // MH_ALLOC_CHECK (mh_internal.hpp): words of a re-used cached block that are not the poison pattern any more
 namespace mh
 {
@@ -2520,4 +1804,21 @@ int prepare(mh_icp * icp, const double R_src[9], const double t_src[3], const do
   bool timed = false;
   return linearize_prepare(icp, R_src, t_src, R_tgt, t_tgt, g_unit, out, false, a, l, timed);
 }
+int chain_k3_block(mh_icp * icp, const double R[9], const double t[3], const double g_unit[3], mh::IcpArgs & a)
+{
+  // what linearize_prepare changes on the handle is put back — the chain keeps its own books.  (linearize_prepare follows the
+  // factor's components setting and may reserve the record of a K4 pass the chain never runs: a.rec is cleared.)
+  mh::LocArgs l;
+  bool timed = false;
+  mh_icp_result scratch;
+  LinearizeTxn txn(icp);
+  const int rc = linearize_prepare(icp, R, t, nullptr, nullptr, g_unit, &scratch, false, a, l, timed);
+  if (rc != MH_OK) return rc;
+  a.rec = nullptr;
+  a.rec_n = 0;
+  a.tail = 1;
+  return MH_OK;
+}
+bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, long spin_ns, mh::DeviceResult & d) { return ::collect_call(icp, slot, pc, spin_ns, d); }
+unsigned int next_call_seq() { return ::next_call_seq(); }
 }  // namespace mhi

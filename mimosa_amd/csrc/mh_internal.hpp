@@ -1,4 +1,4 @@
-// Internals shared by the translation units that implement the C ABI (mh_api.hip, photo_api.hip): the context,
+// Internals shared by the translation units that implement the C ABI (mh_api.hip, chain_api.hip, photo_api.hip, ...): the context,
 // error plumbing, the device / pinned allocation cache and the growable device buffer.  Not installed, not part of
 // the boundary.
 #pragma once
@@ -32,7 +32,7 @@ inline thread_local std::string g_mh_err;
 constexpr int kMaxPending = 64;
 constexpr int kMaxBatch = 64;  // factors per mh_icp_linearize_batch call
 
-// mh_icp_window_optimise: the call in flight on a context (at most one).  Its argument blocks, grid prefixes, state and K3's
+// mh_icp_window_optimise (chain_api.hip): the call in flight on a context (at most one).  Its argument blocks, grid prefixes, state and K3's
 // landing slots live in device memory the context owns (d_window), their pinned staging in h_window, the rows the step
 // kernel publishes in mapped pinned memory (h_window_rows).
 struct WindowLaunch
@@ -632,7 +632,12 @@ inline mh::MapView map_view(const mh_map * m)
   return v;
 }
 
-// ---- ICP factor handle (mh_api.hip; shared with shard_api.hip) --------------------------------------------------
+// ---- ICP factor handle (mh_api.hip; shared with shard_api.hip and chain_api.hip) ----------------------------------
+// mh_icp::h_align, which mh_icp_destroy gives back: [grid prefix and AlignState, 256 B | 64 argument blocks] (chain_api.hip has
+// the whole layout)
+constexpr size_t kAlignBlocksAt = 256;
+constexpr size_t kAlignStageBytes = kAlignBlocksAt + sizeof(mh::IcpArgs) * kMaxPending;
+
 struct PendingCall
 {
   mh_icp_result * out;
@@ -680,7 +685,7 @@ struct mh_icp
   uint32_t * h_counts = nullptr;  // pinned
   bool origin_ready = false, plan_open = false;
   uint32_t n_movers = 0;
-  // mh_icp_align: the chain's argument blocks, grid prefix, state and K3's landing slots in device memory the factor owns
+  // mh_icp_align (chain_api.hip): the chain's argument blocks, grid prefix, state and K3's landing slots in device memory the factor owns
   // (d_align), their pinned staging (h_align), and the call in flight.  While one is, it holds the whole ring (n_pending ==
   // kMaxPending): every other entry point refuses the factor as it refuses one with 64 calls in flight.
   DevBuf d_align;
@@ -720,7 +725,7 @@ struct LaunchGroup
   int first = 0, grid = 0, grid4 = 0;  // plain path: the group's first staging slot, its K3 and K4 grids
 };
 
-// mh_api.hip internals used by shard_api.hip
+// mh_api.hip internals used by shard_api.hip and chain_api.hip
 namespace mhi
 {
 void pose_delta(const double * Rs, const double * ts, const double * Rt, const double * tt, double * R, double * t);
@@ -732,4 +737,17 @@ int prepare(mh_icp * icp, const double R_src[9], const double t_src[3], const do
             mh_icp_result * out, mh::IcpArgs & a, mh::LocArgs & l);
 // shard_api.hip: called by mh_shutdown(ctx) so that the sharded handles listed on ctx let go of it
 void shard_ctx_gone(mh_ctx * ctx);
+// a call's DeviceResult from its flagged words in pending slot `slot` (spin_ns > 0: wait up to that long for words that have
+// not arrived); false = something is still missing
+bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, long spin_ns, mh::DeviceResult & d);
+// sequence numbers of calls: process-wide, never 0
+unsigned int next_call_seq();
+// the K3 argument block of a components-off linearize of a unary factor at (R, t), for a chain that launches K3 itself: rec =
+// nullptr, rec_n = 0, tail = 1; ll and seq are the chain's to set.  The handle's books (cold, linearize_count, n_pending) are
+// on return what they were.
+int chain_k3_block(mh_icp * icp, const double R[9], const double t[3], const double g_unit[3], mh::IcpArgs & a);
+// chain_api.hip: the launch groups of a window (also mh_icp_linearize_batch's), and mh_icp_wait on a factor whose alignment
+// is in flight
+std::vector<LaunchGroup> window_launch_groups(mh_icp * const * icps, size_t n_factors);
+int align_wait(mh_icp * icp);
 }  // namespace mhi

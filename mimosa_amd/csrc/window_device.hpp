@@ -1,4 +1,4 @@
-// One Gauss-Newton iteration over a fixed-lag window of poses (mh_icp_window_optimise): from the 28 Hessian sums K3 folded for
+// One Gauss-Newton iteration over a fixed-lag window of poses (mh_icp_window_optimise, chain_api.hip): from the 28 Hessian sums K3 folded for
 // each of the window's unary factors to the next W poses.  It restates one iteration of WindowSmootherT::optimise
 // (host/mimosa_hip/replay.hpp) without the photometric terms, in that function's sign conventions: per pose the H_ss, b_s, f
 // of the factor at its own rotation (align_device.hpp: align_hessian, with the 4-DoF projection and the degeneracy quirk),

@@ -1,4 +1,4 @@
-// icp_window_step_kernel: the link between two iterations of an mh_icp_window_optimise chain (mh_api.hip).  One workgroup of
+// icp_window_step_kernel: the link between two iterations of an mh_icp_window_optimise chain (chain_api.hip).  One workgroup of
 // one wave, launched behind the staged K3 batch launches of an iteration (tail = 1: each factor's last workgroup folds its rows
 // and publishes the 28 sums + 4 counters as flagged words — here into device-resident slots, 32 words per pose).  The step
 // turns the sums into the next W poses (window_device.hpp), writes them into the argument blocks of the launches queued behind

@@ -1,4 +1,4 @@
-// icp_window_relin_step_kernel: the step of an mh_icp_window_optimise_relin chain (mh_api.hip) — icp_window_step_kernel
+// icp_window_relin_step_kernel: the step of an mh_icp_window_optimise_relin chain (chain_api.hip) — icp_window_step_kernel
 // (window_kernels.hip) with a decision per factor: one workgroup of one wave behind the staged K3 batch launches of an iteration,
 // window_device.hpp's phases one index per lane with a barrier behind each, everything fp64, compiled without floating-point
 // contraction so that the host build of the header gives the same digits.  A translation unit of its own, so that the plain

@@ -18,7 +18,8 @@ Scene: that of tests/test_gpu_icp_window.py (synth.small_world(): a map of ~5 k 
     on eps.
 3.  Thresholds of 1e9: only iteration 0 evaluates — counts advance by 1, the per-point state is that of one
     mh_icp_linearize_batch at the start poses, last == first.
-4.  Bad arguments and the in-flight refusals through the new entry points; the handles stay usable."""
+4.  Bad arguments and the in-flight refusals through the new entry points; the handles stay usable.
+5.  The reference's thresholds, blocking with check_every 0 and 1 and async + wait: the same bits in every field."""
 import numpy as np
 import pytest
 
@@ -239,6 +240,46 @@ def test_thresholds_zero_with_an_empty_factor(world):
     assert list(got["evaluated"]) == [0b1011] * got["iters"]
     for f in a + b:
         f.destroy()
+
+
+# ---- how the host drives the chain does not show in the result ------------------------------------------------------------------
+def same_bits(a, b, where="result"):
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), where
+        for k in a:
+            same_bits(a[k], b[k], f"{where}.{k}")
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), where
+        for i, (x, y) in enumerate(zip(a, b)):
+            same_bits(x, y, f"{where}[{i}]")
+    else:
+        x, y = np.asarray(a), np.asarray(b)
+        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), where
+
+
+def test_check_every_and_async_do_not_change_the_relin_result(world, optima):
+    """The reference's thresholds on the smallest scenario (one_off), W = 3 with an empty factor, 6 iterations: blocking with
+    check_every 0 and 1 and _async + mh_icp_window_wait give the same bits in every field — poses, trace, first, last, masks —
+    and leave every factor's linearize_count the same."""
+    capi = world.capi
+    W, empty_at = 3, 1
+    mk = lambda i: (world.base(5, empty=True) if i == empty_at else world.base(5)).clone()  # noqa: E731
+    poses = one_off(optima[0][:W], 0, who=2)
+    Z, has_Z = [(np.eye(3), np.zeros(3)) for _ in range(W)], [0] + [1] * (W - 1)
+    runs, counts = [], []
+    for ce, wait in ((0, True), (1, True), (0, False)):
+        fs = [mk(i) for i in range(W)]
+        got = capi.optimise_window(fs, poses, base.window_cfg(True, iters=6, check_every=ce, **FIXED), has_Z=has_Z, Z=Z, trace_poses=True, relin=RELIN, wait=wait)
+        runs.append(got if wait else got.wait())
+        counts.append([f.linearize(*poses[i], G)["linearize_count"] - 1 for i, f in enumerate(fs)])  # (the next call's number, less one)
+        for f in fs:
+            f.destroy()
+    print("masks", [bin(int(m)) for m in runs[0]["evaluated"]], "counts", counts[0])
+    assert runs[0]["iters"] == 6 and len(runs[0]["evaluated"]) == 6 and runs[0]["poses"].shape == (6, W, 12)
+    assert all(not (int(m) >> empty_at) & 1 for m in runs[0]["evaluated"])
+    for r, c in zip(runs[1:], counts[1:]):
+        same_bits(r, runs[0])
+        assert c == counts[0]
 
 
 # ---- thresholds nothing reaches ------------------------------------------------------------------------------------------------
