@@ -410,6 +410,40 @@ int mh_icp_window_optimise_relin_async(mh_icp * const * icps, size_t W, const do
                                        const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
                                        mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask);
 
+/* Either chain with Hessian factors the host linearized ONCE: whatever else a fixed-lag smoother puts on a pose (a photometric
+ * factor, a marginal prior with its own linearization point and a dense information matrix, a radar or odometry term), each
+ * on one pose of the window.  Factor j is the quadratic model f + 2 b^T x + x^T H x in the tangent of its linearization pose
+ * L (R <- R Exp(x_r), t <- t + R x_t): the convention of mh_icp_result.H_ss / b_s / f and mh_photo_result.H_bb / b_b / f, what
+ * HessianFactor(key, H, -b, f) receives.  Every iteration carries it from L to the current pose T of its variable as the
+ * relin chain carries a kept ICP factor: d = [Log(L.R^T T.R), L.R^T (T.t - L.t)], M = blockdiag(Jr^-1(d_r), Exp(d_r)); the
+ * factor contributes M^T H M, M^T (b + H d) and the cost f + 2 b^T d + d^T H d (at d = 0 the stored H, b, f as they are) — how
+ * ISAM2 treats a factor whose variable stays inside its relinearization threshold.  Per entry the system adds the pose's ICP
+ * factor, then its linear factors in list order, then between terms, prior and damping; trace[].f adds the ICP factors' f,
+ * the linear factors' in list order, then the between terms.  H is read as given, all 36 entries.  A pose whose ICP factor
+ * is empty may carry linear factors.
+ * relin: NULL (every non-empty ICP factor is evaluated in every iteration: first / last, linearize counts and association
+ * state as under mh_icp_window_optimise; evaluated_mask is not written) or the thresholds of mh_icp_window_optimise_relin
+ * (all of that as there).  With n_lin == 0 the call computes, bit for bit, what the respective call computes.
+ * Every restriction and error rule of mh_icp_window_optimise applies; n_lin > MH_WINDOW_LINEAR_MAX, lin == NULL with
+ * n_lin > 0, a pose outside 0 .. W - 1, an entry of L_R, L_t, H, b or f that is not finite: MH_ERR_INVALID_ARG, nothing
+ * enqueued, the handles unchanged.  lin is copied before the call returns.  mh_icp_window_wait collects the _async form. */
+#define MH_WINDOW_LINEAR_MAX 32
+typedef struct mh_window_linear_factor {
+  int32_t pose, reserved;          /* 0 .. W-1 */
+  double L_R[9], L_t[3];           /* where H, b, f were evaluated */
+  double H[36], b[6], f;
+} mh_window_linear_factor;
+int mh_icp_window_optimise_lin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                               const double * Z_R, const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg,
+                               const mh_icp_window_relin * relin /* NULL: evaluate every factor */,
+                               const mh_window_linear_factor * lin, size_t n_lin, mh_icp_window_result * out,
+                               double * trace_poses, uint32_t * evaluated_mask);
+int mh_icp_window_optimise_lin_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                     const double * Z_R, const double * Z_t, const double g_unit[3],
+                                     const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                     const mh_window_linear_factor * lin, size_t n_lin, mh_icp_window_result * out,
+                                     double * trace_poses, uint32_t * evaluated_mask);
+
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals
  * unique_ns[g] gets p <- R_g p + t_g in float (no FMA, Eigen's evaluation order).  Rt12 = n_groups x

@@ -36,6 +36,7 @@ SOURCES = [
     ("align_kernels.hip", ["-ffp-contract=off"]),  # the host build of align_device.hpp (tests/cpp/align_step.cpp) gives the same digits
     ("window_kernels.hip", ["-ffp-contract=off"]),  # likewise window_device.hpp (tests/cpp/window_step.cpp)
     ("window_relin_kernels.hip", ["-ffp-contract=off"]),  # (tests/cpp/window_relin_step.cpp)
+    ("window_lin_kernels.hip", ["-ffp-contract=off"]),  # (tests/cpp/window_lin_step.cpp)
 ]
 HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "window_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
 
@@ -183,6 +184,7 @@ HOST_TESTS = {
     "flagged_word": ("flagged_word.cpp", ["flagged_word.hpp"]),
     "window_step": ("window_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "window_relin_step": ("window_relin_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
+    "window_lin_step": ("window_lin_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
 }
 
 

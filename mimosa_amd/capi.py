@@ -27,6 +27,7 @@ EXPORTS = [
     "mh_icp_align", "mh_icp_align_async",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
     "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
+    "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
     "mh_deskew", "mh_transform_f32",
     "mh_scan_create", "mh_scan_destroy", "mh_scan_prepare_input", "mh_scan_prepare_input_device", "mh_scan_prefetch", "mh_scan_prepare_input_prefetched", "mh_scan_prepare_input_layout", "mh_scan_get_unique_ns", "mh_scan_deskew",
     "mh_scan_deskew_imu", "mh_scan_get_deskew_poses", "mh_photo_preprocess_scan_resident", "mh_photo_preprocess_scan_begin_resident",
@@ -177,6 +178,28 @@ class WindowResult(C.Structure):
 class WindowRelin(C.Structure):
     """mh_icp_window_relin"""
     _fields_ = [("relin_rot", C.c_double), ("relin_trans", C.c_double)]
+
+
+MH_WINDOW_LINEAR_MAX = 32
+
+
+class WindowLinearFactor(C.Structure):
+    """mh_window_linear_factor"""
+    _fields_ = [("pose", C.c_int32), ("reserved", C.c_int32), ("L_R", C.c_double * 9), ("L_t", C.c_double * 3), ("H", C.c_double * 36), ("b", C.c_double * 6),
+                ("f", C.c_double)]
+
+
+def make_window_linear(linear):
+    """an array of mh_window_linear_factor from dicts {"pose": i, "at": (R, t), "H": 6 x 6, "b": 6, "f": float}"""
+    arr = (WindowLinearFactor * max(len(linear), 1))()
+    for q, l in zip(arr, linear):
+        q.pose = int(l["pose"])
+        q.L_R[:] = [float(v) for v in np.asarray(l["at"][0], np.float64).reshape(9)]
+        q.L_t[:] = [float(v) for v in np.asarray(l["at"][1], np.float64).reshape(3)]
+        q.H[:] = [float(v) for v in np.asarray(l["H"], np.float64).reshape(36)]
+        q.b[:] = [float(v) for v in np.asarray(l["b"], np.float64).reshape(6)]
+        q.f = float(l["f"])
+    return arr
 
 
 def make_window_config(iters=6, between_sigma_rot=2e-3, between_sigma_trans=1e-2, prior_sigma_rot=1e-4, prior_sigma_trans=1e-4, damping=1e-9,
@@ -521,6 +544,9 @@ def load(build_if_missing: bool = True):
     L.mh_icp_window_wait.argtypes = [vp]
     L.mh_icp_window_optimise_relin.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowRelin), C.POINTER(WindowResult), vp, vp]
     L.mh_icp_window_optimise_relin_async.argtypes = L.mh_icp_window_optimise_relin.argtypes
+    L.mh_icp_window_optimise_lin.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowRelin), C.POINTER(WindowLinearFactor), sz,
+                                             C.POINTER(WindowResult), vp, vp]
+    L.mh_icp_window_optimise_lin_async.argtypes = L.mh_icp_window_optimise_lin.argtypes
     L.mh_icp_size.restype = sz
     L.mh_deskew.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
     L.mh_transform_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -904,14 +930,17 @@ class WindowCall:
         return d
 
 
-def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), trace_poses=False, wait=True, relin=None):
+def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), trace_poses=False, wait=True, relin=None, linear=None):
     """mh_icp_window_optimise: the fixed-lag Gauss-Newton loop over `factors` (oldest first) as one chain of launches.
     poses: (R, t) per factor; Z: (R, t) per factor, entry i the measured T_{i-1}^-1 T_i where has_Z[i] (entry 0 unused).
     trace_poses: also return "poses", (iters, W, 12) — R row-major then t after every executed step.
     wait=False: mh_icp_window_optimise_async; returns a WindowCall whose wait() gives the same dict.
     relin=(rot, trans): mh_icp_window_optimise_relin — a factor is evaluated again only once its pose has moved past these
     thresholds (rad, m) from the pose of its last evaluation; also returns "evaluated", per executed iteration the mask of the
-    factors that ran K3."""
+    factors that ran K3.
+    linear=[...]: mh_icp_window_optimise_lin (with or without relin) — Hessian factors the host linearized once, each a dict
+    {"pose": index, "at": (R, t) of its linearization, "H": 6 x 6, "b": 6, "f": float} (make_window_linear); an empty list takes
+    the same entry point with no factor."""
     W = len(factors)
     ctx = factors[0].ctx
     R = np.ascontiguousarray(np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses]))
@@ -925,6 +954,22 @@ def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_uni
     handles = (C.c_void_p * W)(*[f.h for f in factors])
     out = WindowResult()
     trace = np.full((int(cfg.iters), W, 12), np.nan) if trace_poses else None
+    if linear is not None:
+        rl = None if relin is None else WindowRelin(float(relin[0]), float(relin[1]))
+        masks = None if relin is None else np.zeros(max(int(cfg.iters), 1), np.uint32)
+        lin = make_window_linear(linear)
+        args = (handles, W, _p(R), _p(t), _p(hz), _p(ZR), _p(Zt), _p(g), C.byref(cfg), None if rl is None else C.byref(rl), lin, len(linear), C.byref(out),
+                _p(trace), _p(masks))
+        if not wait:
+            ctx.check(ctx.L.mh_icp_window_optimise_lin_async(*args))
+            return WindowCall(ctx, (handles, R, t, hz, ZR, Zt, g, cfg, rl, lin), out, trace, masks)
+        ctx.check(ctx.L.mh_icp_window_optimise_lin(*args))
+        d = out.as_dict()
+        if trace is not None:
+            d["poses"] = trace[:d["iters"]]
+        if masks is not None:
+            d["evaluated"] = masks[:d["iters"]].copy()
+        return d
     if relin is not None:
         rl = WindowRelin(float(relin[0]), float(relin[1]))
         masks = np.zeros(max(int(cfg.iters), 1), np.uint32)  # (a bad iters is the library's to refuse)

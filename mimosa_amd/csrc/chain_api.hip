@@ -1,12 +1,14 @@
 // The device-chain drivers of the C ABI (include/mimosa_hip.h): mh_icp_align[_async], mh_icp_window_optimise[_async],
-// mh_icp_window_optimise_relin[_async] and mh_icp_window_wait.  A chain is K3 (icp_kernels.hip), a step kernel
-// (align_kernels.hip, window_kernels.hip, window_relin_kernels.hip), K3, step ... on the context's stream with one wait at its
+// mh_icp_window_optimise_relin[_async], mh_icp_window_optimise_lin[_async] and mh_icp_window_wait.  A chain is K3
+// (icp_kernels.hip), a step kernel (align_kernels.hip, window_kernels.hip, window_relin_kernels.hip, window_lin_kernels.hip),
+// K3, step ... on the context's stream with one wait at its
 // end; every step publishes a row of flagged words the host reads.  What the two families share is written once at the top;
 // argument checks, staging layout, the step launch and the decoding of a row are each family's own.  The factor handle,
 // linearize and the flagged words of a call live in mh_api.hip (mh_internal.hpp: mhi).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <limits>
 
 #include "mh_internal.hpp"
@@ -23,13 +25,16 @@ static_assert(sizeof(mh::AlignState) <= 192 && mh::kRowWords <= mh::kLlEig, "mh_
 // mh_icp_window_optimise's block of device memory (mh_ctx::d_window) and the pinned staging of its first part (h_window):
 // [grid prefixes, 256 B | WindowState | iters x n_slots argument blocks | 256 B that load_uniform may read past the last block |
 //  one landing slot of 32 flagged words per pose for K3's sums and counters (every iteration's words carry its own number) |
-//  WindowRelin, which the steps of an mh_icp_window_optimise_relin chain keep among themselves]
+//  WindowRelin, which the steps of an mh_icp_window_optimise_relin chain keep among themselves |
+//  WindowLinear, the linear factors of an mh_icp_window_optimise_lin call (staged behind the first part in h_window)]
 constexpr size_t kWinStateAt = 256;
 constexpr size_t kWinBlocksAt = 3584;
 constexpr size_t kWinStageBytes = kWinBlocksAt + sizeof(mh::IcpArgs) * mh::kWindowMax * kMaxPending;
 constexpr size_t kWinLlAt = (kWinStageBytes + 256 + 255) & ~size_t(255);
 constexpr size_t kWinRelinAt = kWinLlAt + 32 * sizeof(uint4) * mh::kWindowMax;
-constexpr size_t kWinBytes = kWinRelinAt + ((sizeof(mh::WindowRelin) + 255) & ~size_t(255));
+constexpr size_t kWinLinAt = kWinRelinAt + ((sizeof(mh::WindowRelin) + 255) & ~size_t(255));
+constexpr size_t kWinBytes = kWinLinAt + ((sizeof(mh::WindowLinear) + 255) & ~size_t(255));
+static_assert(MH_WINDOW_LINEAR_MAX == mh::kWindowLinMax && kWinLinAt % 16 == 0, "mh_icp_window_optimise_lin layout");
 constexpr size_t kWinRowWords = 256;  // flagged words per iteration's row in h_window_rows
 constexpr size_t kWinMaskWord = kWinRowWords - 1;  // of which the last: the evaluated mask of an mh_icp_window_optimise_relin iteration
 static_assert(mh::kWRowPose + 12 * mh::kWindowMax <= static_cast<int>(kWinMaskWord) && kWinRelinAt % 16 == 0, "mh_icp_window_optimise_relin layout");
@@ -356,7 +361,7 @@ static void window_abandon(mh_ctx * ctx)
 
 static int window_begin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                         const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses,
-                        const mh_icp_window_relin * relin, uint32_t * evaluated_mask)
+                        const mh_icp_window_relin * relin, uint32_t * evaluated_mask, bool lin_call, const mh_window_linear_factor * lin, size_t n_lin)
 {
   mh_ctx * ctx = window_ctx(icps, W);
   if (!icps || !R || !t || !has_Z || !g_unit || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
@@ -382,12 +387,26 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   if (relin && !(relin->relin_rot >= 0.0 && relin->relin_rot <= std::numeric_limits<double>::max() && relin->relin_trans >= 0.0 &&
                  relin->relin_trans <= std::numeric_limits<double>::max()))
     return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: relin_rot and relin_trans must be finite and >= 0");
+  if (lin_call) {
+    if (n_lin > static_cast<size_t>(MH_WINDOW_LINEAR_MAX)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_lin: at most 32 linear factors per call");
+    if (n_lin && !lin) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_lin: NULL linear factors");
+    for (size_t j = 0; j < n_lin; ++j) {
+      const mh_window_linear_factor & q = lin[j];
+      if (q.pose < 0 || static_cast<size_t>(q.pose) >= W) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_lin: a linear factor's pose is outside the window");
+      bool fin = std::isfinite(q.f);
+      for (double v : q.L_R) fin = fin && std::isfinite(v);
+      for (double v : q.L_t) fin = fin && std::isfinite(v);
+      for (double v : q.H) fin = fin && std::isfinite(v);
+      for (double v : q.b) fin = fin && std::isfinite(v);
+      if (!fin) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_lin: a linear factor has an entry that is not finite");
+    }
+  }
   unsigned int zmask = 0;
   for (size_t f = 1; f < W; ++f)
     if (has_Z[f]) zmask |= 1u << f;
   if (zmask && (!Z_R || !Z_t)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL between measurements");
   MH_HIP(ctx, mh_enter(ctx));
-  if (!ctx->h_window) MH_HIP(ctx, hipHostMalloc(&ctx->h_window, kWinStageBytes, hipHostMallocDefault));
+  if (!ctx->h_window) MH_HIP(ctx, hipHostMalloc(&ctx->h_window, kWinStageBytes + sizeof(mh::WindowLinear), hipHostMallocDefault));
   if (!ctx->d_window) MH_HIP(ctx, hipMalloc(&ctx->d_window, kWinBytes));
   if (!ctx->h_window_rows) {
     MH_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_window_rows), kWinRowWords * sizeof(uint4) * kMaxPending, hipHostMallocMapped));
@@ -405,6 +424,7 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   c.relin_rot = relin ? relin->relin_rot : 0.0;
   c.relin_trans = relin ? relin->relin_trans : 0.0;
   c.evaluated_mask = evaluated_mask;
+  c.lin = lin_call;
   for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
   // launch groups in slot order, as mh_icp_linearize_batch lays the same window out
   const std::vector<LaunchGroup> groups = mhi::window_launch_groups(icps, W);
@@ -481,6 +501,21 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   p.eps_trans = cfg->eps_trans;
 
   MH_HIP(ctx, hipMemcpyAsync(d, h, kWinBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(cfg->iters), hipMemcpyHostToDevice, ctx->stream));
+  if (lin_call) {
+    // the linear factors, once per call: the header and the factors in use
+    auto * wl = reinterpret_cast<mh::WindowLinear *>(h + kWinStageBytes);
+    wl->n = static_cast<int>(n_lin);
+    wl->pad = 0;
+    for (size_t j = 0; j < static_cast<size_t>(mh::kWindowLinMax); ++j) wl->pose[j] = j < n_lin ? lin[j].pose : 0;
+    for (size_t j = 0; j < n_lin; ++j) {
+      std::memcpy(wl->LR[j], lin[j].L_R, sizeof(wl->LR[j]));
+      std::memcpy(wl->Lt[j], lin[j].L_t, sizeof(wl->Lt[j]));
+      std::memcpy(wl->H[j], lin[j].H, sizeof(wl->H[j]));
+      std::memcpy(wl->b[j], lin[j].b, sizeof(wl->b[j]));
+      wl->f[j] = lin[j].f;
+    }
+    MH_HIP(ctx, hipMemcpyAsync(d + kWinLinAt, wl, sizeof(mh::WindowLinear), hipMemcpyHostToDevice, ctx->stream));
+  }
   c.active = true;
   for (size_t f = 0; f < W; ++f) {
     icps[f]->in_window = true;
@@ -516,16 +551,20 @@ static int window_enqueue(mh_ctx * ctx, int upto)
       s.state = reinterpret_cast<mh::WindowState *>(d + kWinStateAt);
       s.p = c.p;
       s.seq = c.seq[it];
-      if (c.relin) {
-        mh::WindowRelinStepArgs ra;
-        std::memset(static_cast<void *>(&ra), 0, sizeof(ra));
+      if (c.relin || c.lin) {
+        mh::WindowLinStepArgs la;
+        std::memset(static_cast<void *>(&la), 0, sizeof(la));
+        mh::WindowRelinStepArgs & ra = la.r;
         ra.s = s;
-        ra.relin = reinterpret_cast<mh::WindowRelin *>(d + kWinRelinAt);
-        ra.mask_host = s.row_host + kWinMaskWord;
-        ra.rp.relin_rot = c.relin_rot;
-        ra.rp.relin_trans = c.relin_trans;
-        ra.rp.first = it == 0 ? 1 : 0;
-        e = mh::launch_window_relin_step(ra, ctx->stream);
+        if (c.relin) {
+          ra.relin = reinterpret_cast<mh::WindowRelin *>(d + kWinRelinAt);
+          ra.mask_host = s.row_host + kWinMaskWord;
+          ra.rp.relin_rot = c.relin_rot;
+          ra.rp.relin_trans = c.relin_trans;
+          ra.rp.first = it == 0 ? 1 : 0;
+        }
+        la.lin = reinterpret_cast<const mh::WindowLinear *>(d + kWinLinAt);
+        e = c.lin ? mh::launch_window_lin_step(la, c.relin, ctx->stream) : mh::launch_window_relin_step(ra, ctx->stream);
       } else {
         e = mh::launch_window_step(s, ctx->stream);
       }
@@ -635,10 +674,11 @@ static int mh_icp_window_wait_impl(mh_ctx * ctx)
 // relin_call: through mh_icp_window_optimise_relin[_async], whose thresholds are not optional
 static int mh_icp_window_optimise_impl(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out,
-                                       double * trace_poses, bool blocking, bool relin_call, const mh_icp_window_relin * relin, uint32_t * evaluated_mask)
+                                       double * trace_poses, bool blocking, bool relin_call, const mh_icp_window_relin * relin, uint32_t * evaluated_mask,
+                                       bool lin_call = false, const mh_window_linear_factor * lin = nullptr, size_t n_lin = 0)
 {
   if (relin_call && !relin) return fail(window_ctx(icps, W), MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: NULL argument");
-  const int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask);
+  const int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask, lin_call, lin, n_lin);
   if (rc != MH_OK) return rc;
   if (!blocking) return window_enqueue(icps[0]->ctx, cfg->iters);
   return window_run(icps[0]->ctx, cfg->check_every > 0 ? cfg->check_every : cfg->iters);
@@ -683,6 +723,23 @@ int mh_icp_window_optimise_relin_async(mh_icp * const * icps, size_t W, const do
 {
   return guarded(window_ctx(icps, W), "mh_icp_window_optimise_relin_async", [&]() -> int {
     return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, true, relin, evaluated_mask);
+  });
+}
+int mh_icp_window_optimise_lin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                               const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                               const mh_window_linear_factor * lin, size_t n_lin, mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_lin", [&]() -> int {
+    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, false, relin, evaluated_mask, true, lin, n_lin);
+  });
+}
+int mh_icp_window_optimise_lin_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                     const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                     const mh_window_linear_factor * lin, size_t n_lin, mh_icp_window_result * out, double * trace_poses,
+                                     uint32_t * evaluated_mask)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_lin_async", [&]() -> int {
+    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, relin, evaluated_mask, true, lin, n_lin);
   });
 }
 int mh_icp_window_wait(mh_ctx * ctx)

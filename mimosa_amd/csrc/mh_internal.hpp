@@ -56,6 +56,7 @@ struct WindowCall
   bool relin = false;  // mh_icp_window_optimise_relin: the step kernel chooses per factor and iteration whether K3 runs
   double relin_rot = 0.0, relin_trans = 0.0;
   uint32_t * evaluated_mask = nullptr;
+  bool lin = false;    // mh_icp_window_optimise_lin: the step kernel also carries the call's linear factors
 };
 
 struct mh_ctx

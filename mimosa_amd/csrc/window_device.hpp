@@ -62,6 +62,23 @@ struct WindowRelinParams
   int first, pad;                 // the call's first iteration: every non-empty factor is evaluated, nothing is read from WindowRelin
 };
 
+// mh_icp_window_optimise_lin: Hessian factors the host linearized once, each on one pose, in the convention of the ICP factor's
+// H_ss, b_s, f (the model f + 2 b^T x + x^T H x in the tangent of its linearization pose L).  Read-only to the chain: every
+// iteration carries each of them from L to the current pose of its variable (window_transport) into WindowLinWork.
+constexpr int kWindowLinMax = 32;
+struct WindowLinear
+{
+  int n, pad;
+  int pose[kWindowLinMax];  // 0 .. W - 1
+  double LR[kWindowLinMax][9], Lt[kWindowLinMax][3];
+  double H[kWindowLinMax][36], b[kWindowLinMax][6], f[kWindowLinMax];
+};
+struct WindowLinWork
+{
+  double H[kWindowLinMax][36], b[kWindowLinMax][6], f[kWindowLinMax];  // factor j at the current pose of its variable
+  double tmp[kWindowLinMax][36];
+};
+
 // One row per queued iteration, published as flagged words.
 enum WindowRow
 {
@@ -275,11 +292,13 @@ MH_HD bool window_relin_decide(const double d[6], double relin_rot, double relin
 }
 
 // w.A, w.E, w.rhs, w.cost from the factors' sums at the poses of `st`.  RELIN: the factors of `eval` from their sums (and into
-// rl, with the pose), the other non-empty ones from rl
-template <bool RELIN, typename Par>
-MH_HD void window_assemble_impl(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, WindowRelin * rl, unsigned int eval, Par & par)
+// rl, with the pose), the other non-empty ones from rl.  LIN: the linear factors of `lin` as well, carried to the poses of `st`
+template <bool RELIN, bool LIN, typename Par>
+MH_HD void window_assemble_impl(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, WindowRelin * rl, unsigned int eval,
+                                const WindowLinear * lin, WindowLinWork * lw, Par & par)
 {
   const int W = p.W;
+  const int n_lin = LIN ? lin->n : 0;
   par.each(2 * W, [&](int l) {
     const int i = l >> 1, blk = l & 1;
     if (RELIN && ((p.have >> i) & 1u) && !((eval >> i) & 1u)) {
@@ -316,11 +335,22 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
       for (int q = 0; q < 36; ++q) w.E[i][q] = 0.0;
     }
   });
-  // per entry in the order optimise() adds: the factor, the between factors in window order, the prior, the damping
+  if (LIN)
+    par.each(n_lin, [&](int j) {
+      const int i = lin->pose[j];
+      double d[6];
+      window_local(lin->LR[j], lin->Lt[j], st.R[i], st.t[i], d);
+      window_transport(lin->H[j], lin->b[j], lin->f[j], d, lw->H[j], lw->b[j], lw->f[j], lw->tmp[j]);
+    });
+  // per entry in the order optimise() adds: the factor, (the linear factors on its pose in list order,) the between factors in
+  // window order, the prior, the damping
   par.each(36 * W + 6 * W + 1, [&](int l) {
     if (l < 36 * W) {
       const int i = l / 36, e = l % 36, r = e / 6, c = e % 6;
       double a = w.H[i][e];
+      if (LIN)
+        for (int j = 0; j < n_lin; ++j)
+          if (lin->pose[j] == i) a += lw->H[j][e];
       if (r == c && ((p.has_Z >> i) & 1u)) a += p.Wb[r];
       if (i + 1 < W && ((p.has_Z >> (i + 1)) & 1u)) a += w.Baa[i + 1][e];
       if (r == c) {
@@ -331,12 +361,17 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
     } else if (l < 42 * W) {
       const int q = l - 36 * W, i = q / 6, r = q % 6;
       double g = w.b[i][r];
+      if (LIN)
+        for (int j = 0; j < n_lin; ++j)
+          if (lin->pose[j] == i) g += lw->b[j][r];
       if ((p.has_Z >> i) & 1u) g += w.gb[i][r];
       if (i + 1 < W && ((p.has_Z >> (i + 1)) & 1u)) g += w.ga[i + 1][r];
       w.rhs[q] = -g;
     } else {
       double cost = 0.0;
       for (int i = 0; i < W; ++i) cost += w.f[i];
+      if (LIN)
+        for (int j = 0; j < n_lin; ++j) cost += lw->f[j];
       for (int i = 1; i < W; ++i)
         if ((p.has_Z >> i) & 1u) cost += w.cz[i];
       w.cost = cost;
@@ -346,7 +381,7 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
 template <typename Par>
 MH_HD void window_assemble(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, Par & par)
 {
-  window_assemble_impl<false>(sums, st, p, w, nullptr, 0u, par);
+  window_assemble_impl<false, false>(sums, st, p, w, nullptr, 0u, nullptr, nullptr, par);
 }
 
 // the block sweep: S_i = L_i D_i L_i^T and G_{i+1} for every block.  false (w.ok == 0): a pivot is not positive
@@ -451,9 +486,10 @@ MH_HD bool window_solve(int W, WindowWork & w, Par & par)
 // chain that finds otherwise stops).  Returns the row's flags.  Once st.stopped is set the poses are passed on unchanged.
 // RELIN: `arrived` speaks of the factors this iteration evaluates (window_relin_mask); behind the step, rl holds every pose's
 // offset from its linearization pose and the factors the next iteration evaluates.
-template <bool RELIN, typename Par>
+// LIN: the system and the cost also hold the linear factors of `lin` (lw: their work arrays); nothing else changes.
+template <bool RELIN, bool LIN, typename Par>
 MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrived, const WindowParams & p, WindowWork & w, double * row, WindowRelin * rl,
-                              const WindowRelinParams * rp, Par & par)
+                              const WindowRelinParams * rp, const WindowLinear * lin, WindowLinWork * lw, Par & par)
 {
   const int W = p.W;
   const bool frozen = st.stopped != 0;
@@ -462,7 +498,7 @@ MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrive
   par.sync();  // (every index has read the state before index 0 changes it)
   bool stepped = false;
   if (!frozen && arrived) {
-    window_assemble_impl<RELIN>(sums, st, p, w, rl, eval, par);
+    window_assemble_impl<RELIN, LIN>(sums, st, p, w, rl, eval, lin, lw, par);
     stepped = window_solve(W, w, par);
     par.each(W, [&](int i) {
       if (stepped) {
@@ -539,7 +575,7 @@ MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrive
 template <typename Par>
 MH_HD int window_advance(WindowState & st, const double * sums, bool arrived, const WindowParams & p, WindowWork & w, double * row, Par & par)
 {
-  return window_advance_impl<false>(st, sums, arrived, p, w, row, nullptr, nullptr, par);
+  return window_advance_impl<false, false>(st, sums, arrived, p, w, row, nullptr, nullptr, nullptr, nullptr, par);
 }
 // the factors the iteration about to run evaluates (read before window_advance_relin changes rl)
 MH_HD unsigned int window_relin_mask(const WindowRelin & rl, const WindowParams & p, const WindowRelinParams & rp) { return rp.first ? p.have : rl.eval; }
@@ -547,7 +583,15 @@ template <typename Par>
 MH_HD int window_advance_relin(WindowState & st, WindowRelin & rl, const double * sums, bool arrived, const WindowParams & p, const WindowRelinParams & rp,
                                WindowWork & w, double * row, Par & par)
 {
-  return window_advance_impl<true>(st, sums, arrived, p, w, row, &rl, &rp, par);
+  return window_advance_impl<true, false>(st, sums, arrived, p, w, row, &rl, &rp, nullptr, nullptr, par);
+}
+// mh_icp_window_optimise_lin: either chain with the linear factors of `lin`.  rl, rp: null for the plain chain
+template <typename Par>
+MH_HD int window_advance_lin(WindowState & st, WindowRelin * rl, const double * sums, bool arrived, const WindowParams & p, const WindowRelinParams * rp,
+                             const WindowLinear & lin, WindowLinWork & lw, WindowWork & w, double * row, Par & par)
+{
+  if (rl) return window_advance_impl<true, true>(st, sums, arrived, p, w, row, rl, rp, &lin, &lw, par);
+  return window_advance_impl<false, true>(st, sums, arrived, p, w, row, nullptr, nullptr, &lin, &lw, par);
 }
 
 }  // namespace mh
@@ -585,5 +629,14 @@ struct WindowRelinStepArgs
   WindowRelinParams rp;
 };
 hipError_t launch_window_relin_step(const WindowRelinStepArgs & a, hipStream_t stream);
+
+// One step of an mh_icp_window_optimise_lin chain (window_lin_kernels.hip): either of the above (relin: with the decisions),
+// with the linear factors of `lin`, which the host wrote once per call.
+struct WindowLinStepArgs
+{
+  WindowRelinStepArgs r;     // relin == false: r.relin, r.mask_host, r.rp unused
+  const WindowLinear * lin;  // device memory the context owns
+};
+hipError_t launch_window_lin_step(const WindowLinStepArgs & a, bool relin, hipStream_t stream);
 }  // namespace mh
 #endif

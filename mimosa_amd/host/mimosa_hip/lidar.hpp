@@ -621,6 +621,33 @@ public:
   {
     double rot = 1.75e-2, trans = 5.0e-3;  // rad, m: config/enwide/params.yaml:32-33
   };
+  // A Hessian factor the host linearized once, on one pose of the window (mh_icp_window_optimise_lin): the model
+  // f + 2 b^T x + x^T H x in the tangent of `at`, the convention of mh_icp_result.H_ss / b_s / f — what
+  // HessianFactor(key, H, -b, f) receives.  The chain carries it to the current pose of its variable in every iteration.
+  struct WindowLinear
+  {
+    size_t pose = 0;  // index into the window
+    Pose3 at;         // where H, b, f were evaluated
+    M66 H;
+    V6D b;
+    double f = 0.0;
+  };
+  // from the unary HessianFactor a linearize() returned (which carries -b) and the pose it was linearized at
+  static WindowLinear windowLinearFrom(const HessianFactor & h, size_t pose, const Pose3 & at)
+  {
+    WindowLinear l;
+    l.pose = pose;
+    l.at = at;
+    const gtsam::Matrix G = h.information();
+    const gtsam::Vector g = h.linearTerm();
+    if (G.rows() != 6 || G.cols() != 6 || g.size() != 6) throw std::runtime_error("ICPFactor::windowLinearFrom: a factor over one pose only");
+    for (int r = 0; r < 6; ++r) {
+      for (int c = 0; c < 6; ++c) l.H(r, c) = G(r, c);
+      l.b(r) = -g(r);
+    }
+    l.f = h.constantTerm();
+    return l;
+  }
   // a call in flight (optimiseWindowAsync): wait() collects it
   class WindowCall
   {
@@ -656,6 +683,7 @@ public:
     bool relin_on_ = false;
     mh_icp_window_relin relin_{};
     std::vector<uint32_t> masks_;
+    std::vector<mh_window_linear_factor> lin_;
   };
   static WindowResult optimiseWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
                                      const Unit3 & g, const WindowConfig & config)
@@ -677,6 +705,18 @@ public:
                                                               const WindowRelin & relin)
   {
     return startWindow(factors, poses, between, g, config, false, &relin);
+  }
+  // either of the above (relin == nullptr: every factor is evaluated in every iteration) with linear factors on the poses
+  static WindowResult optimiseWindowLin(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
+                                        const Unit3 & g, const WindowConfig & config, const std::vector<WindowLinear> & linear, const WindowRelin * relin = nullptr)
+  {
+    return startWindow(factors, poses, between, g, config, true, relin, &linear)->finish();
+  }
+  static std::unique_ptr<WindowCall> optimiseWindowLinAsync(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses,
+                                                            const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config,
+                                                            const std::vector<WindowLinear> & linear, const WindowRelin * relin = nullptr)
+  {
+    return startWindow(factors, poses, between, g, config, false, relin, &linear);
   }
 
   // getters, :48-72
@@ -746,7 +786,8 @@ private:
   }
   const Context & ctx() const { return *ivox_target_->context(); }
   static std::unique_ptr<WindowCall> startWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
-                                                 const Unit3 & g, const WindowConfig & config, bool blocking, const WindowRelin * relin = nullptr)
+                                                 const Unit3 & g, const WindowConfig & config, bool blocking, const WindowRelin * relin = nullptr,
+                                                 const std::vector<WindowLinear> * linear = nullptr)
   {
     const size_t n = factors.size();
     if (!n || poses.size() != n || between.size() != n) throw std::runtime_error("ICPFactor::optimiseWindow: one pose and one between entry per factor");
@@ -780,6 +821,33 @@ private:
     w->c_.eps_rot = config.eps_rot;
     w->c_.eps_trans = config.eps_trans;
     w->r_.reset(new mh_icp_window_result);
+    if (linear) {
+      for (const WindowLinear & l : *linear) {
+        mh_window_linear_factor q;
+        std::memset(&q, 0, sizeof(q));
+        q.pose = l.pose < n ? static_cast<int32_t>(l.pose) : -1;  // (out of range: the library's to refuse)
+        const PoseRM L = rowMajor(l.at);
+        std::memcpy(q.L_R, L.R.data(), 72);
+        std::memcpy(q.L_t, L.t.data(), 24);
+        for (int r = 0; r < 6; ++r) {
+          for (int c = 0; c < 6; ++c) q.H[6 * r + c] = l.H(r, c);
+          q.b[r] = l.b(r);
+        }
+        q.f = l.f;
+        w->lin_.push_back(q);
+      }
+      if (relin) {
+        w->relin_on_ = true;
+        w->relin_.relin_rot = relin->rot;
+        w->relin_.relin_trans = relin->trans;
+        w->masks_.assign(static_cast<size_t>(config.iters > 0 ? config.iters : 0), 0u);
+      }
+      const auto fl = blocking ? mh_icp_window_optimise_lin : mh_icp_window_optimise_lin_async;
+      factors[0]->ctx().check(fl(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_,
+                                 relin ? &w->relin_ : nullptr, w->lin_.data(), w->lin_.size(), w->r_.get(), nullptr, relin ? w->masks_.data() : nullptr),
+                              blocking ? "mh_icp_window_optimise_lin" : "mh_icp_window_optimise_lin_async");
+      return w;
+    }
     if (relin) {
       w->relin_on_ = true;
       w->relin_.relin_rot = relin->rot;

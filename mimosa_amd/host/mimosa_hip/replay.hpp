@@ -255,6 +255,10 @@ struct Config
   // from the pose of its last evaluation within the call (ICPFactor::optimiseWindowRelin).  Refused without device_window
   bool window_relin = false;
   double window_relin_rot = 1.75e-2, window_relin_trans = 5.0e-3;
+  // with device_window: the photometric factor is accepted — before each window call the host linearizes it once at the call's
+  // initial poses (photo_window: every live one, in one batch call) and hands the results to the chain as linear factors on their
+  // poses (ICPFactor::optimiseWindowLin), which carries them along instead of evaluating them again.  Refused without device_window
+  bool window_photo_linear = false;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
   lidar::ManagerInputConfig input = lidar::defaultManagerInputConfig();
@@ -399,6 +403,8 @@ public:
   void setPhotoWindow(bool on) { photo_window_ = on; }
   // on: optimise() hands the whole loop to the device (FactorT::optimiseWindow); no photometric factor may be in play
   void setDeviceWindow(bool on) { device_window_ = on; }
+  // on (with the device window): photometric factors are linearized once per call and carried by the chain as linear factors
+  void setWindowPhotoLinear(bool on) { window_photo_linear_ = on; }
   void setWindowRelin(bool on, double rot, double trans)
   {
     window_relin_ = on;
@@ -529,7 +535,8 @@ private:
   std::vector<double> optimiseOnDevice(const size_t k, const PhotometricFactor::Ptr & pf)
   {
     if constexpr (std::is_same<FactorT, ICPFactor>::value) {
-      if (pf || (photo_window_ && photoFactorsInWindow())) throw std::runtime_error("replay: device_window takes no photometric factor");
+      if (!window_photo_linear_ && (pf || (photo_window_ && photoFactorsInWindow())))
+        throw std::runtime_error("replay: device_window takes no photometric factor");
       const size_t nW = win.size();
       std::vector<typename FactorT::Ptr> factors(nW);
       std::vector<Pose3> poses(nW);
@@ -554,8 +561,40 @@ private:
       ICPFactor::WindowRelin rl;
       rl.rot = relin_rot_;
       rl.trans = relin_trans_;
-      const ICPFactor::WindowResult r = window_relin_ ? ICPFactor::optimiseWindowRelin(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc, rl)
-                                                      : ICPFactor::optimiseWindow(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc);
+      // window_photo_linear: the photometric factors of this call (as optimise() chooses them), linearized once at the call's
+      // initial poses; one without valid features or with a non-finite entry is skipped, as optimise() skips it
+      std::vector<ICPFactor::WindowLinear> linear;
+      if (window_photo_linear_) {
+        Values v;
+        for (size_t i = 0; i < nW; ++i) v.insert(X(win[i].k), poses[i]);
+        std::vector<PhotometricFactor::Ptr> pfs;
+        std::vector<size_t> at;
+        if (photo_window_) {
+          for (size_t i = 0; i < nW; ++i)
+            if (win[i].pf) {
+              pfs.push_back(win[i].pf);
+              at.push_back(i);
+            }
+          if (!pfs.empty()) PhotometricFactor::linearizeBatchAsync(pfs, v);
+        } else if (pf) {
+          pf->linearizeAsync(v);
+          pfs.push_back(pf);
+          at.push_back(nW - 1);
+        }
+        for (size_t j = 0; j < pfs.size(); ++j) {
+          const auto hp = std::static_pointer_cast<HessianFactor>(pfs[j]->collect());
+          bool finite = pfs[j]->lastResult().status_hist[8] > 0 && std::isfinite(hp->constantTerm());
+          const gtsam::Matrix Gp = hp->information();
+          const gtsam::Vector gp = hp->linearTerm();
+          for (int q = 0; q < 36 && finite; ++q) finite = std::isfinite(Gp(q / 6, q % 6));
+          for (int q = 0; q < 6 && finite; ++q) finite = std::isfinite(gp(q));
+          if (finite) linear.push_back(ICPFactor::windowLinearFrom(*hp, at[j], poses[at[j]]));
+        }
+      }
+      const Unit3 down(0.0, 0.0, -1.0);
+      const ICPFactor::WindowResult r = window_photo_linear_ ? ICPFactor::optimiseWindowLin(factors, poses, between, down, wc, linear, window_relin_ ? &rl : nullptr)
+                                        : window_relin_      ? ICPFactor::optimiseWindowRelin(factors, poses, between, down, wc, rl)
+                                                             : ICPFactor::optimiseWindow(factors, poses, between, down, wc);
       if (r.iters != update_iters_) throw std::runtime_error("replay::solve: singular system");
       std::vector<double> fs;
       for (size_t i = 0; i < nW; ++i) {
@@ -571,7 +610,7 @@ private:
       throw std::runtime_error("replay: device_window is offered for lidar::ICPFactor only");
     }
   }
-  bool device_window_ = false, window_relin_ = false;
+  bool device_window_ = false, window_relin_ = false, window_photo_linear_ = false;
   double relin_rot_ = 0.0, relin_trans_ = 0.0;
   int window_, update_iters_;
   double Wb_[6];
@@ -641,9 +680,12 @@ public:
     using Live = typename Smoother::Live;
     Smoother smoother(cfg_.window, cfg_.update_iters, cfg_.between_sigma_rot, cfg_.between_sigma_trans);
     smoother.setPhotoWindow(cfg_.photo_window);
-    if (cfg_.device_window && cfg_.photometric) throw std::runtime_error("replay: device_window is not offered with the photometric factor enabled");
+    if (cfg_.window_photo_linear && !cfg_.device_window) throw std::runtime_error("replay: window_photo_linear is only offered with device_window");
+    if (cfg_.device_window && cfg_.photometric && !cfg_.window_photo_linear)
+      throw std::runtime_error("replay: device_window is not offered with the photometric factor enabled");
     if (cfg_.window_relin && !cfg_.device_window) throw std::runtime_error("replay: window_relin is only offered with device_window");
     smoother.setDeviceWindow(cfg_.device_window);
+    smoother.setWindowPhotoLinear(cfg_.window_photo_linear);
     smoother.setWindowRelin(cfg_.window_relin, cfg_.window_relin_rot, cfg_.window_relin_trans);
     std::deque<Live> & win = smoother.win;
     std::vector<RT> kf_poses;

@@ -1,9 +1,11 @@
 // Native sequence replay: drives mimosa_hip::replay::FixedLagReplay (host/mimosa_hip/replay.hpp) on an input file written
 // by mimosa_amd/replay.py:write_native_input and prints one JSON object (estimated poses, per-stage seconds, scans/s).
-//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window | device-window-relin=<rot>,<trans>] [device-poses]
+//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear] | device-window-relin=<rot>,<trans>[+photo-linear]] [device-poses]
 //     device-poses (last word): replay::Config::device_poses — the per-timestamp deskew poses are computed on the device
 //     device-window (in front of it): replay::Config::device_window — the smoother's iterations run as one chain of launches on
-//       the device (FixedLagReplay without the photometric factor; refused elsewhere)
+//       the device (FixedLagReplay without the photometric factor; refused elsewhere).  +photo-linear behind either form:
+//       replay::Config::window_photo_linear — the photometric factor is accepted, linearized once per window call on the host
+//       and carried by the chain as a linear factor
 //     repeats > 1: the whole sequence again, timing of the last pass is reported
 //     sharded <world>: the map sharded over <world> ranks INSIDE this process (one host thread and one context each, in-process
 //       transport: what a one-GPU box can run); sharded-rccl: this process is one rank of a torch.distributed.run-style launch
@@ -22,16 +24,20 @@ using binio::read_vec;
 int main(int argc, char ** argv)
 {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window | device-window-relin=<rot>,<trans>] [device-poses]\n");
+    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear] | device-window-relin=<rot>,<trans>[+photo-linear]] [device-poses]\n");
     return 2;
   }
   const bool device_poses = argc > 2 && std::string(argv[argc - 1]) == "device-poses";
   if (device_poses) --argc;
   // device-window-relin=<rot>,<trans>: device-window with replay::Config::window_relin (relinearization thresholds, rad and m)
-  bool device_window = argc > 2 && std::string(argv[argc - 1]) == "device-window";
+  std::string window_word = argc > 2 ? argv[argc - 1] : "";
+  const std::string photo_suffix = "+photo-linear";
+  const bool window_photo_linear = window_word.size() > photo_suffix.size() && window_word.compare(window_word.size() - photo_suffix.size(), photo_suffix.size(), photo_suffix) == 0;
+  if (window_photo_linear) window_word.resize(window_word.size() - photo_suffix.size());
+  bool device_window = window_word == "device-window";
   bool window_relin = false;
   double relin_rot = 0.0, relin_trans = 0.0;
-  if (!device_window && argc > 2 && std::sscanf(argv[argc - 1], "device-window-relin=%lf,%lf", &relin_rot, &relin_trans) == 2) device_window = window_relin = true;
+  if (!device_window && std::sscanf(window_word.c_str(), "device-window-relin=%lf,%lf", &relin_rot, &relin_trans) == 2) device_window = window_relin = true;
   if (device_window) --argc;
   const int repeats = argc > 2 ? std::atoi(argv[2]) : 1;
   const bool through_manager = argc > 3 && std::string(argv[3]) == "manager";  // the same sequence through lidar::Manager::callback
@@ -70,6 +76,7 @@ int main(int argc, char ** argv)
     cfg.window_relin = window_relin;
     cfg.window_relin_rot = relin_rot;
     cfg.window_relin_trans = relin_trans;
+    cfg.window_photo_linear = device_window && window_photo_linear;
     const auto bias = read_vec<double>(f);
     for (size_t i = 0; i + 2 < bias.size(); i += 3) cfg.bias_directions.push_back(V3D(bias[i], bias[i + 1], bias[i + 2]));
     const auto seed = read_vec<float>(f);

@@ -78,6 +78,10 @@ class ReplayConfig:
     # these thresholds from the pose of its last evaluation within the call (mh_icp_window_optimise_relin; the reference's ISAM2
     # runs with 1.75e-2, 5e-3).  None: every factor every iteration.  Refused without device_window
     window_relin: tuple = None
+    # with device_window: the photometric factor is accepted — before each window call the host linearizes it once at the call's
+    # initial poses (photo_window: every live one, through the batch call) and passes the results as linear factors on their poses
+    # (mh_icp_window_optimise_lin), which the chain carries along instead of evaluating them again.  Refused without device_window
+    window_photo_linear: bool = False
     reg: dict = field(default_factory=synth.enwide_config)
     photo: dict = None
 
@@ -277,11 +281,14 @@ class HipBackend:
         rs = self.capi.linearize_batch(factors, [p[0] for p in poses], [p[1] for p in poses])
         return [(np.asarray(r["H_ss"]).reshape(6, 6), np.asarray(r["b_s"]), float(r["f"])) for r in rs]
 
-    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping, relin=None):
-        """device_window: the smoother's loop over the window as one call; the poses after it and the cost before each iteration"""
+    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping, relin=None, linear=None):
+        """device_window: the smoother's loop over the window as one call; the poses after it and the cost before each iteration.
+        linear: host-linearized Hessian factors on poses of the window (capi.optimise_window)"""
         cfg = self.capi.make_window_config(iters=iters, between_info=between_info, prior_info=prior_info, damping=damping)
         I3, z3 = np.eye(3), np.zeros(3)
         kw = {} if relin is None else dict(relin=relin)
+        if linear is not None:
+            kw["linear"] = linear
         r = self.capi.optimise_window(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs], **kw)
         if r["iters"] != iters:
             raise np.linalg.LinAlgError("Singular matrix")
@@ -381,6 +388,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
     from . import build
     if cfg.window_relin is not None and not cfg.device_window:
         raise RuntimeError("window_relin is only offered with device_window")
+    if cfg.window_photo_linear and not cfg.device_window:
+        raise RuntimeError("window_photo_linear is only offered with device_window")
     exe = build.build_replay_native()
     path = os.path.join(workdir, "replay_input.bin")
     write_native_input(path, cfg, scans, rng_seed)
@@ -393,7 +402,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
     if sharded_rccl:
         mode = ["sharded-rccl"]
     if cfg.device_window:
-        mode = mode + ["device-window" if cfg.window_relin is None else "device-window-relin=%r,%r" % (float(cfg.window_relin[0]), float(cfg.window_relin[1]))]
+        word = "device-window" if cfg.window_relin is None else "device-window-relin=%r,%r" % (float(cfg.window_relin[0]), float(cfg.window_relin[1]))
+        mode = mode + [word + ("+photo-linear" if cfg.window_photo_linear else "")]
     if cfg.device_poses:
         mode = mode + ["device-poses"]
     out = subprocess.run([exe, path, str(repeats)] + mode, capture_output=True, text=True, timeout=timeout, env=env)
@@ -414,7 +424,9 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         raise ValueError("device_poses needs a backend that keeps the pose table on the device (HipBackend)")
     if cfg.window_relin is not None and not cfg.device_window:
         raise ValueError("window_relin is only offered with device_window")
-    if cfg.device_window and cfg.photometric:
+    if cfg.window_photo_linear and not cfg.device_window:
+        raise ValueError("window_photo_linear is only offered with device_window")
+    if cfg.device_window and cfg.photometric and not cfg.window_photo_linear:
         raise ValueError("device_window is not offered with the photometric factor enabled")
     if cfg.device_window and not hasattr(backend, "optimise_window"):
         raise ValueError("device_window needs a backend with mh_icp_window_optimise (HipBackend)")
@@ -474,9 +486,24 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         if cfg.device_window:
             loose = win[0]["k"] == 0 and k < cfg.window
             sr, st = (np.deg2rad(1.0), 0.1) if loose else (1e-4, 1e-4)
+            kw = {} if cfg.window_relin is None else dict(relin=tuple(cfg.window_relin))
+            if cfg.window_photo_linear:
+                # the photometric factors of this call (as the host loop below chooses them), linearized once at the call's initial
+                # poses; one without valid features or with a non-finite entry is skipped, as that loop skips it
+                if cfg.photo_window:
+                    at = [i for i, w in enumerate(win) if w["pf"] is not None]
+                else:
+                    at = [nW - 1] if pf is not None else []
+                pfs = [win[i]["pf"] if cfg.photo_window else pf for i in at]
+                poses = [(win[i]["R"], win[i]["t"]) for i in at]
+                if len(at) > 1 or (at and cfg.photo_window):
+                    plin = backend.linearize_photo_window(pfs, poses)
+                else:
+                    plin = [backend.linearize_photo(p, R_, t_) for p, (R_, t_) in zip(pfs, poses)]
+                kw["linear"] = [dict(pose=i, at=T, H=Hp, b=bp, f=fp) for i, T, (Hp, bp, fp, nv) in zip(at, poses, plin)
+                                if nv and np.all(np.isfinite(Hp)) and np.all(np.isfinite(bp)) and np.isfinite(fp)]
             new_poses, fs = backend.optimise_window([w["f"] for w in win], [(w["R"], w["t"]) for w in win], [None] + [w["Z"] for w in win[1:]],
-                                                    cfg.update_iters, list(np.diag(Wb)), [1.0 / sr**2] * 3 + [1.0 / st**2] * 3, 1e-9,
-                                                    **({} if cfg.window_relin is None else dict(relin=tuple(cfg.window_relin))))
+                                                    cfg.update_iters, list(np.diag(Wb)), [1.0 / sr**2] * 3 + [1.0 / st**2] * 3, 1e-9, **kw)
             for w, (R_n, t_n) in zip(win, new_poses):
                 w["R"], w["t"] = R_n, t_n
         else:
