@@ -444,6 +444,44 @@ int mh_icp_window_optimise_lin_async(mh_icp * const * icps, size_t W, const doub
                                      const mh_window_linear_factor * lin, size_t n_lin, mh_icp_window_result * out,
                                      double * trace_poses, uint32_t * evaluated_mask);
 
+/* mh_icp_window_optimise_lin (relin NULL or set, n_lin 0 .. 32; has_Z / Z / cfg->between_info exactly as there) with between
+ * factors on ANY pair of poses, each with its own measurement and a dense information matrix: the odometry manager's
+ * BetweenFactor<Pose3> beside the IMU tie, a tie across several poses, a second tie on one pair.  Every iteration evaluates
+ * edge e of the poses a < b at the current poses as the has_Z factor is evaluated: with T_ab = T_a^-1 T_b the residual
+ * r = [Log(Z.R^T R_ab), Z.R^T (t_ab - Z.t)], J_a = -Ad(T_ab^-1), J_b = I; with Om = info it adds J_a^T Om J_a to the diagonal
+ * block of a, Om J_a to the block in block row b, block column a (its transpose above the diagonal), Om to the diagonal
+ * block of b, J_a^T Om r and Om r to the gradients of a and b, r^T Om r to the cost.  info is read as given, all 36 entries.
+ * Per entry the system adds the pose's ICP factor, its linear factors in list order, the has_Z between terms in window
+ * order, the edges in list order, the prior, the damping; trace[].f adds the edges' terms behind the has_Z terms, in list
+ * order.  Several edges may share a pair; an edge may lie parallel to a has_Z tie, span a has_Z gap, or end on a pose whose
+ * ICP factor is empty.  The system is then not block-tridiagonal: it is solved by a block L D L^T over its row profile
+ * (fill stays between a row's first block and the diagonal), every pivot block factorised and tested as in the other chains,
+ * followed by the same two refinement steps.  Retraction, stopping, relin decisions, masks, first / last, linearize counts and
+ * association state are those of the underlying chain; a system without a positive pivot takes no step and ends the call
+ * (trace[].flags bit 4).  With n_edges == 0 the call computes, bit for bit, what mh_icp_window_optimise_lin computes.
+ * Everything mh_icp_window_optimise_lin refuses is refused; n_edges > MH_WINDOW_EDGE_MAX, edges == NULL with n_edges > 0,
+ * pose_a < 0, pose_b >= W, pose_a >= pose_b, an entry of Z_R, Z_t or info that is not finite, info[6 r + c] != info[6 c + r]:
+ * MH_ERR_INVALID_ARG, nothing enqueued, the handles unchanged.  The edge arguments are checked first, before icps and W: a call
+ * with several things wrong reports the edges' error.  edges is copied before the call returns.
+ * mh_icp_window_wait collects the _async form. */
+#define MH_WINDOW_EDGE_MAX 32
+typedef struct mh_window_edge {
+  int32_t pose_a, pose_b;          /* 0 <= pose_a < pose_b <= W - 1, any distance apart */
+  double Z_R[9], Z_t[3];           /* the measured T_a^-1 T_b */
+  double info[36];                 /* information matrix, (rotation, translation) order, row-major, symmetric */
+} mh_window_edge;
+int mh_icp_window_optimise_edges(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                 const double * Z_R, const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg,
+                                 const mh_icp_window_relin * relin /* NULL: evaluate every factor */,
+                                 const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges,
+                                 mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask);
+int mh_icp_window_optimise_edges_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                       const double * Z_R, const double * Z_t, const double g_unit[3],
+                                       const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                       const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges,
+                                       size_t n_edges, mh_icp_window_result * out, double * trace_poses,
+                                       uint32_t * evaluated_mask);
+
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals
  * unique_ns[g] gets p <- R_g p + t_g in float (no FMA, Eigen's evaluation order).  Rt12 = n_groups x

@@ -37,6 +37,7 @@ SOURCES = [
     ("window_kernels.hip", ["-ffp-contract=off"]),  # likewise window_device.hpp (tests/cpp/window_step.cpp)
     ("window_relin_kernels.hip", ["-ffp-contract=off"]),  # (tests/cpp/window_relin_step.cpp)
     ("window_lin_kernels.hip", ["-ffp-contract=off"]),  # (tests/cpp/window_lin_step.cpp)
+    ("window_edge_kernels.hip", ["-ffp-contract=off"]),  # (tests/cpp/window_edge_step.cpp)
 ]
 HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "window_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
 
@@ -167,13 +168,30 @@ def build_replay_native(force: bool = False) -> str:
     exe = os.path.join(LIBDIR, "replay_native")
     host = os.path.join(HERE, "host")
     src = os.path.join(host, "replay_main.cpp")
-    deps = [src, lib] + [os.path.join(host, "mimosa_hip", h) for h in ("replay.hpp", "sharded_replay.hpp", "sharded.hpp", "manager.hpp", "binio.hpp", "photometric.hpp", "lidar.hpp", "types.hpp")]
+    deps = [src, lib] + [os.path.join(host, "mimosa_hip", h) for h in ("replay.hpp", "sharded_replay.hpp", "sharded.hpp", "manager.hpp", "binio.hpp", "photometric.hpp", "lidar.hpp", "types.hpp", "odometry.hpp")]
     deps += [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(host, "gtsam_sig")) for f in fs]
     if not (force or _stale(exe, deps)):
         return exe  # up to date: no lock (see build())
     with _BuildLock():
         if force or _stale(exe, deps):
             _run_to(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.dirname(HERE), "-I", host, "-I", os.path.join(host, "gtsam_sig"), src, "-o", exe,
+                     "-L", LIBDIR, "-lmimosa_hip", "-lpthread", "-Wl,-rpath,$ORIGIN"], exe)
+    return exe
+
+
+def build_odometry_test(force: bool = False) -> str:
+    """tests/cpp/odometry_manager.cpp over host/mimosa_hip/odometry.hpp (plain g++, links the library, as the replay driver does)."""
+    lib = build()
+    exe = os.path.join(LIBDIR, "odometry_manager")
+    host = os.path.join(HERE, "host")
+    src = os.path.join(os.path.dirname(HERE), "tests", "cpp", "odometry_manager.cpp")
+    deps = [src, lib] + [os.path.join(host, "mimosa_hip", h) for h in ("odometry.hpp", "lidar.hpp", "types.hpp")]
+    deps += [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(host, "gtsam_sig")) for f in fs]
+    if not (force or _stale(exe, deps)):
+        return exe  # up to date: no lock (see build())
+    with _BuildLock():
+        if force or _stale(exe, deps):
+            _run_to(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.dirname(HERE), "-I", os.path.join(host, "gtsam_sig"), src, "-o", exe,
                      "-L", LIBDIR, "-lmimosa_hip", "-lpthread", "-Wl,-rpath,$ORIGIN"], exe)
     return exe
 
@@ -185,6 +203,7 @@ HOST_TESTS = {
     "window_step": ("window_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "window_relin_step": ("window_relin_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "window_lin_step": ("window_lin_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
+    "window_edge_step": ("window_edge_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
 }
 
 

@@ -28,6 +28,7 @@ EXPORTS = [
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
     "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
     "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
+    "mh_icp_window_optimise_edges", "mh_icp_window_optimise_edges_async",
     "mh_deskew", "mh_transform_f32",
     "mh_scan_create", "mh_scan_destroy", "mh_scan_prepare_input", "mh_scan_prepare_input_device", "mh_scan_prefetch", "mh_scan_prepare_input_prefetched", "mh_scan_prepare_input_layout", "mh_scan_get_unique_ns", "mh_scan_deskew",
     "mh_scan_deskew_imu", "mh_scan_get_deskew_poses", "mh_photo_preprocess_scan_resident", "mh_photo_preprocess_scan_begin_resident",
@@ -199,6 +200,25 @@ def make_window_linear(linear):
         q.H[:] = [float(v) for v in np.asarray(l["H"], np.float64).reshape(36)]
         q.b[:] = [float(v) for v in np.asarray(l["b"], np.float64).reshape(6)]
         q.f = float(l["f"])
+    return arr
+
+
+MH_WINDOW_EDGE_MAX = 32
+
+
+class WindowEdge(C.Structure):
+    """mh_window_edge"""
+    _fields_ = [("pose_a", C.c_int32), ("pose_b", C.c_int32), ("Z_R", C.c_double * 9), ("Z_t", C.c_double * 3), ("info", C.c_double * 36)]
+
+
+def make_window_edge(edges):
+    """an array of mh_window_edge from dicts {"a": i, "b": j, "Z": (R, t) the measured T_a^-1 T_b, "info": 6 x 6}"""
+    arr = (WindowEdge * max(len(edges), 1))()
+    for q, e in zip(arr, edges):
+        q.pose_a, q.pose_b = int(e["a"]), int(e["b"])
+        q.Z_R[:] = [float(v) for v in np.asarray(e["Z"][0], np.float64).reshape(9)]
+        q.Z_t[:] = [float(v) for v in np.asarray(e["Z"][1], np.float64).reshape(3)]
+        q.info[:] = [float(v) for v in np.asarray(e["info"], np.float64).reshape(36)]
     return arr
 
 
@@ -547,6 +567,9 @@ def load(build_if_missing: bool = True):
     L.mh_icp_window_optimise_lin.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowRelin), C.POINTER(WindowLinearFactor), sz,
                                              C.POINTER(WindowResult), vp, vp]
     L.mh_icp_window_optimise_lin_async.argtypes = L.mh_icp_window_optimise_lin.argtypes
+    L.mh_icp_window_optimise_edges.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowRelin), C.POINTER(WindowLinearFactor), sz,
+                                               C.POINTER(WindowEdge), sz, C.POINTER(WindowResult), vp, vp]
+    L.mh_icp_window_optimise_edges_async.argtypes = L.mh_icp_window_optimise_edges.argtypes
     L.mh_icp_size.restype = sz
     L.mh_deskew.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
     L.mh_transform_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -930,7 +953,8 @@ class WindowCall:
         return d
 
 
-def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), trace_poses=False, wait=True, relin=None, linear=None):
+def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), trace_poses=False, wait=True, relin=None, linear=None,
+                    edges=None):
     """mh_icp_window_optimise: the fixed-lag Gauss-Newton loop over `factors` (oldest first) as one chain of launches.
     poses: (R, t) per factor; Z: (R, t) per factor, entry i the measured T_{i-1}^-1 T_i where has_Z[i] (entry 0 unused).
     trace_poses: also return "poses", (iters, W, 12) — R row-major then t after every executed step.
@@ -940,7 +964,10 @@ def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_uni
     factors that ran K3.
     linear=[...]: mh_icp_window_optimise_lin (with or without relin) — Hessian factors the host linearized once, each a dict
     {"pose": index, "at": (R, t) of its linearization, "H": 6 x 6, "b": 6, "f": float} (make_window_linear); an empty list takes
-    the same entry point with no factor."""
+    the same entry point with no factor.
+    edges=[...]: mh_icp_window_optimise_edges (with or without relin and linear) — between factors on any pair of poses, each a
+    dict {"a": i, "b": j, "Z": (R, t) the measured T_a^-1 T_b, "info": 6 x 6} (make_window_edge); an empty list takes the same
+    entry point with no edge.  None: the dispatch above, untouched."""
     W = len(factors)
     ctx = factors[0].ctx
     R = np.ascontiguousarray(np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses]))
@@ -954,6 +981,23 @@ def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_uni
     handles = (C.c_void_p * W)(*[f.h for f in factors])
     out = WindowResult()
     trace = np.full((int(cfg.iters), W, 12), np.nan) if trace_poses else None
+    if edges is not None:
+        rl = None if relin is None else WindowRelin(float(relin[0]), float(relin[1]))
+        masks = None if relin is None else np.zeros(max(int(cfg.iters), 1), np.uint32)
+        lin = make_window_linear(linear or [])
+        ed = make_window_edge(edges)
+        args = (handles, W, _p(R), _p(t), _p(hz), _p(ZR), _p(Zt), _p(g), C.byref(cfg), None if rl is None else C.byref(rl), lin, len(linear or []), ed, len(edges),
+                C.byref(out), _p(trace), _p(masks))
+        if not wait:
+            ctx.check(ctx.L.mh_icp_window_optimise_edges_async(*args))
+            return WindowCall(ctx, (handles, R, t, hz, ZR, Zt, g, cfg, rl, lin, ed), out, trace, masks)
+        ctx.check(ctx.L.mh_icp_window_optimise_edges(*args))
+        d = out.as_dict()
+        if trace is not None:
+            d["poses"] = trace[:d["iters"]]
+        if masks is not None:
+            d["evaluated"] = masks[:d["iters"]].copy()
+        return d
     if linear is not None:
         rl = None if relin is None else WindowRelin(float(relin[0]), float(relin[1]))
         masks = None if relin is None else np.zeros(max(int(cfg.iters), 1), np.uint32)

@@ -1,6 +1,7 @@
 // The device-chain drivers of the C ABI (include/mimosa_hip.h): mh_icp_align[_async], mh_icp_window_optimise[_async],
-// mh_icp_window_optimise_relin[_async], mh_icp_window_optimise_lin[_async] and mh_icp_window_wait.  A chain is K3
-// (icp_kernels.hip), a step kernel (align_kernels.hip, window_kernels.hip, window_relin_kernels.hip, window_lin_kernels.hip),
+// mh_icp_window_optimise_relin[_async], mh_icp_window_optimise_lin[_async], mh_icp_window_optimise_edges[_async] and
+// mh_icp_window_wait.  A chain is K3 (icp_kernels.hip), a step kernel (align_kernels.hip, window_kernels.hip,
+// window_relin_kernels.hip, window_lin_kernels.hip, window_edge_kernels.hip),
 // K3, step ... on the context's stream with one wait at its
 // end; every step publishes a row of flagged words the host reads.  What the two families share is written once at the top;
 // argument checks, staging layout, the step launch and the decoding of a row are each family's own.  The factor handle,
@@ -26,14 +27,18 @@ static_assert(sizeof(mh::AlignState) <= 192 && mh::kRowWords <= mh::kLlEig, "mh_
 // [grid prefixes, 256 B | WindowState | iters x n_slots argument blocks | 256 B that load_uniform may read past the last block |
 //  one landing slot of 32 flagged words per pose for K3's sums and counters (every iteration's words carry its own number) |
 //  WindowRelin, which the steps of an mh_icp_window_optimise_relin chain keep among themselves |
-//  WindowLinear, the linear factors of an mh_icp_window_optimise_lin call (staged behind the first part in h_window)]
+//  WindowLinear, the linear factors of an mh_icp_window_optimise_lin call (staged behind the first part in h_window) |
+//  WindowEdges, the edges of an mh_icp_window_optimise_edges call (staged behind WindowLinear)]
 constexpr size_t kWinStateAt = 256;
 constexpr size_t kWinBlocksAt = 3584;
 constexpr size_t kWinStageBytes = kWinBlocksAt + sizeof(mh::IcpArgs) * mh::kWindowMax * kMaxPending;
 constexpr size_t kWinLlAt = (kWinStageBytes + 256 + 255) & ~size_t(255);
 constexpr size_t kWinRelinAt = kWinLlAt + 32 * sizeof(uint4) * mh::kWindowMax;
 constexpr size_t kWinLinAt = kWinRelinAt + ((sizeof(mh::WindowRelin) + 255) & ~size_t(255));
-constexpr size_t kWinBytes = kWinLinAt + ((sizeof(mh::WindowLinear) + 255) & ~size_t(255));
+constexpr size_t kWinEdgeAt = kWinLinAt + ((sizeof(mh::WindowLinear) + 255) & ~size_t(255));
+constexpr size_t kWinBytes = kWinEdgeAt + ((sizeof(mh::WindowEdges) + 255) & ~size_t(255));
+constexpr size_t kWinStageEdgeAt = kWinStageBytes + ((sizeof(mh::WindowLinear) + 255) & ~size_t(255));  // in h_window
+static_assert(MH_WINDOW_EDGE_MAX == mh::kWindowEdgeMax && kWinEdgeAt % 16 == 0 && kWinStageEdgeAt % 16 == 0, "mh_icp_window_optimise_edges layout");
 static_assert(MH_WINDOW_LINEAR_MAX == mh::kWindowLinMax && kWinLinAt % 16 == 0, "mh_icp_window_optimise_lin layout");
 constexpr size_t kWinRowWords = 256;  // flagged words per iteration's row in h_window_rows
 constexpr size_t kWinMaskWord = kWinRowWords - 1;  // of which the last: the evaluated mask of an mh_icp_window_optimise_relin iteration
@@ -361,9 +366,26 @@ static void window_abandon(mh_ctx * ctx)
 
 static int window_begin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                         const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses,
-                        const mh_icp_window_relin * relin, uint32_t * evaluated_mask, bool lin_call, const mh_window_linear_factor * lin, size_t n_lin)
+                        const mh_icp_window_relin * relin, uint32_t * evaluated_mask, bool lin_call, const mh_window_linear_factor * lin, size_t n_lin,
+                        const mh_window_edge * edges, size_t n_edges)
 {
   mh_ctx * ctx = window_ctx(icps, W);
+  // the edges first: what is wrong with them is told apart without a factor
+  if (n_edges > static_cast<size_t>(MH_WINDOW_EDGE_MAX)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: at most 32 edges per call");
+  if (n_edges && !edges) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: NULL edges");
+  for (size_t e = 0; e < n_edges; ++e) {
+    const mh_window_edge & q = edges[e];
+    if (q.pose_a < 0 || static_cast<size_t>(q.pose_b) >= W || q.pose_b < 0 || q.pose_a >= q.pose_b)
+      return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: an edge needs 0 <= pose_a < pose_b <= W - 1");
+    bool fin = true;
+    for (double v : q.Z_R) fin = fin && std::isfinite(v);
+    for (double v : q.Z_t) fin = fin && std::isfinite(v);
+    for (double v : q.info) fin = fin && std::isfinite(v);
+    if (!fin) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: an edge has an entry that is not finite");
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < r; ++c)
+        if (q.info[6 * r + c] != q.info[6 * c + r]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: an edge's info is not symmetric");
+  }
   if (!icps || !R || !t || !has_Z || !g_unit || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
   if (W < 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the window has no pose");
   if (W > static_cast<size_t>(mh::kWindowMax)) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: at most 16 poses per call");
@@ -406,7 +428,7 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
     if (has_Z[f]) zmask |= 1u << f;
   if (zmask && (!Z_R || !Z_t)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL between measurements");
   MH_HIP(ctx, mh_enter(ctx));
-  if (!ctx->h_window) MH_HIP(ctx, hipHostMalloc(&ctx->h_window, kWinStageBytes + sizeof(mh::WindowLinear), hipHostMallocDefault));
+  if (!ctx->h_window) MH_HIP(ctx, hipHostMalloc(&ctx->h_window, kWinStageEdgeAt + sizeof(mh::WindowEdges), hipHostMallocDefault));
   if (!ctx->d_window) MH_HIP(ctx, hipMalloc(&ctx->d_window, kWinBytes));
   if (!ctx->h_window_rows) {
     MH_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_window_rows), kWinRowWords * sizeof(uint4) * kMaxPending, hipHostMallocMapped));
@@ -425,6 +447,7 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   c.relin_trans = relin ? relin->relin_trans : 0.0;
   c.evaluated_mask = evaluated_mask;
   c.lin = lin_call;
+  c.edges = n_edges > 0;
   for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
   // launch groups in slot order, as mh_icp_linearize_batch lays the same window out
   const std::vector<LaunchGroup> groups = mhi::window_launch_groups(icps, W);
@@ -516,6 +539,20 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
     }
     MH_HIP(ctx, hipMemcpyAsync(d + kWinLinAt, wl, sizeof(mh::WindowLinear), hipMemcpyHostToDevice, ctx->stream));
   }
+  if (n_edges) {
+    // the edges, once per call; the slots behind the last keep a valid pair, which nothing reads
+    auto * we = reinterpret_cast<mh::WindowEdges *>(h + kWinStageEdgeAt);
+    std::memset(static_cast<void *>(we), 0, sizeof(*we));
+    we->n = static_cast<int>(n_edges);
+    for (size_t e = 0; e < n_edges; ++e) {
+      we->a[e] = edges[e].pose_a;
+      we->b[e] = edges[e].pose_b;
+      std::memcpy(we->ZR[e], edges[e].Z_R, sizeof(we->ZR[e]));
+      std::memcpy(we->Zt[e], edges[e].Z_t, sizeof(we->Zt[e]));
+      std::memcpy(we->Om[e], edges[e].info, sizeof(we->Om[e]));
+    }
+    MH_HIP(ctx, hipMemcpyAsync(d + kWinEdgeAt, we, sizeof(mh::WindowEdges), hipMemcpyHostToDevice, ctx->stream));
+  }
   c.active = true;
   for (size_t f = 0; f < W; ++f) {
     icps[f]->in_window = true;
@@ -564,7 +601,15 @@ static int window_enqueue(mh_ctx * ctx, int upto)
           ra.rp.first = it == 0 ? 1 : 0;
         }
         la.lin = reinterpret_cast<const mh::WindowLinear *>(d + kWinLinAt);
-        e = c.lin ? mh::launch_window_lin_step(la, c.relin, ctx->stream) : mh::launch_window_relin_step(ra, ctx->stream);
+        if (c.edges) {
+          mh::WindowEdgeStepArgs ea;
+          std::memset(static_cast<void *>(&ea), 0, sizeof(ea));
+          ea.l = la;
+          ea.edges = reinterpret_cast<const mh::WindowEdges *>(d + kWinEdgeAt);
+          e = mh::launch_window_edge_step(ea, c.relin, ctx->stream);
+        } else {
+          e = c.lin ? mh::launch_window_lin_step(la, c.relin, ctx->stream) : mh::launch_window_relin_step(ra, ctx->stream);
+        }
       } else {
         e = mh::launch_window_step(s, ctx->stream);
       }
@@ -675,10 +720,11 @@ static int mh_icp_window_wait_impl(mh_ctx * ctx)
 static int mh_icp_window_optimise_impl(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out,
                                        double * trace_poses, bool blocking, bool relin_call, const mh_icp_window_relin * relin, uint32_t * evaluated_mask,
-                                       bool lin_call = false, const mh_window_linear_factor * lin = nullptr, size_t n_lin = 0)
+                                       bool lin_call = false, const mh_window_linear_factor * lin = nullptr, size_t n_lin = 0,
+                                       const mh_window_edge * edges = nullptr, size_t n_edges = 0)
 {
   if (relin_call && !relin) return fail(window_ctx(icps, W), MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: NULL argument");
-  const int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask, lin_call, lin, n_lin);
+  const int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask, lin_call, lin, n_lin, edges, n_edges);
   if (rc != MH_OK) return rc;
   if (!blocking) return window_enqueue(icps[0]->ctx, cfg->iters);
   return window_run(icps[0]->ctx, cfg->check_every > 0 ? cfg->check_every : cfg->iters);
@@ -740,6 +786,27 @@ int mh_icp_window_optimise_lin_async(mh_icp * const * icps, size_t W, const doub
 {
   return guarded(window_ctx(icps, W), "mh_icp_window_optimise_lin_async", [&]() -> int {
     return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, relin, evaluated_mask, true, lin, n_lin);
+  });
+}
+// n_edges == 0: the lin call's own step kernels
+int mh_icp_window_optimise_edges(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                 const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                 const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_icp_window_result * out,
+                                 double * trace_poses, uint32_t * evaluated_mask)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_edges", [&]() -> int {
+    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, false, relin, evaluated_mask, true, lin, n_lin, edges,
+                                       n_edges);
+  });
+}
+int mh_icp_window_optimise_edges_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                       const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                       const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges,
+                                       mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_edges_async", [&]() -> int {
+    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, relin, evaluated_mask, true, lin, n_lin, edges,
+                                       n_edges);
   });
 }
 int mh_icp_window_wait(mh_ctx * ctx)

@@ -57,6 +57,7 @@ struct WindowCall
   double relin_rot = 0.0, relin_trans = 0.0;
   uint32_t * evaluated_mask = nullptr;
   bool lin = false;    // mh_icp_window_optimise_lin: the step kernel also carries the call's linear factors
+  bool edges = false;  // mh_icp_window_optimise_edges with n_edges > 0: ... and the call's edges, solved over the row profile
 };
 
 struct mh_ctx

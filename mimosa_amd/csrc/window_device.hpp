@@ -9,6 +9,8 @@
 // (S_0 = A_00, G_i = S_{i-1}^-1 E_i^T, S_i = A_ii - E_i G_i; every S_i factorised as align_solve6 factorises its matrix), forward
 // over the W blocks and back, followed by two refinement steps whose residual is accumulated in twice the working precision.
 // A window of one pose without a between factor goes through exactly the operations of align_step, in the same order.
+// With edges (mh_icp_window_optimise_edges: between factors on any pair of poses) the system has blocks away from the
+// sub-diagonal; it is then solved by the same block L D L^T over its row profile, with fill (window_factor_profile below).
 //
 // Plain fp64 for the device (window_kernels.hip: icp_window_step_kernel) and the host (tests/cpp/window_step.cpp under g++),
 // both compiled without floating-point contraction.  The work is written as PHASES: in one phase every index of a range
@@ -77,6 +79,29 @@ struct WindowLinWork
 {
   double H[kWindowLinMax][36], b[kWindowLinMax][6], f[kWindowLinMax];  // factor j at the current pose of its variable
   double tmp[kWindowLinMax][36];
+};
+
+// mh_icp_window_optimise_edges: between factors on any pair of poses a < b, each with its own measurement and a dense 6 x 6
+// information matrix.  Read-only to the chain: every iteration evaluates each of them at the current poses
+// (window_between_dense) into WindowEdgeWork.  With them the system is no longer block-tridiagonal: its strictly lower blocks
+// (i, k), k < i, are kept packed, block (i, k) at window_pair(i, k), and solved over the row profile lo (window_factor_profile).
+constexpr int kWindowEdgeMax = 32;
+constexpr int kWindowPairs = kWindowMax * (kWindowMax - 1) / 2;
+MH_HD int window_pair(int i, int k) { return i * (i - 1) / 2 + k; }
+struct WindowEdges
+{
+  int n, pad;
+  int a[kWindowEdgeMax], b[kWindowEdgeMax];  // 0 <= a < b <= W - 1
+  double ZR[kWindowEdgeMax][9], Zt[kWindowEdgeMax][3];  // the measured T_a^-1 T_b
+  double Om[kWindowEdgeMax][36];
+};
+struct WindowEdgeWork
+{
+  double Baa[kWindowEdgeMax][36], Eba[kWindowEdgeMax][36];  // edge e: J_a^T Om J_a, Om J_a (block row b, block column a)
+  double ga[kWindowEdgeMax][6], gb[kWindowEdgeMax][6], cz[kWindowEdgeMax];  // J_a^T Om r, Om r, r^T Om r
+  double B[kWindowPairs][36];  // the system's block (i, k); during window_factor_profile the updated block T_ik
+  double G[kWindowPairs][36];  // G_ik = S_k^-1 T_ik^T
+  int lo[kWindowMax];          // the smallest block column with a nonzero in block row i (i: none)
 };
 
 // One row per queued iteration, published as flagged words.
@@ -200,6 +225,53 @@ MH_HD void window_between(const double Ra[9], const double ta[3], const double R
   }
 }
 
+// window_between with a dense information matrix Om (row-major, read as given): the same residual and J_a = -Ad(between^-1),
+// J_b = I; Baa = J_a^T Om J_a, Eba = Om J_a, ga = J_a^T Om r, gb = Om r, cost = r^T Om r  (J_b^T Om J_b = Om is added by the
+// assembly).  Eba and gb are read back while Baa, ga and the cost are formed: they must not alias the other outputs.
+MH_HD void window_between_dense(const double Ra[9], const double ta[3], const double Rb[9], const double tb[3], const double ZR[9], const double Zt[3],
+                                const double Om[36], double Baa[36], double Eba[36], double ga[6], double gb[6], double & cost)
+{
+  double Rat[9], abR[9], abt[3];
+  win_tr(Ra, Rat);
+  win_mm(Rat, Rb, abR);
+  const double dt[3] = {tb[0] - ta[0], tb[1] - ta[1], tb[2] - ta[2]};
+  win_mv(Rat, dt, abt);
+  double Rzt[9], Re[9], te[3], lr[3];
+  win_tr(ZR, Rzt);
+  win_mm(Rzt, abR, Re);
+  const double de[3] = {abt[0] - Zt[0], abt[1] - Zt[1], abt[2] - Zt[2]};
+  win_mv(Rzt, de, te);  // Z^-1 * between
+  window_so3log(Re, lr);
+  const double r[6] = {lr[0], lr[1], lr[2], te[0], te[1], te[2]};
+  double Rabt[9], tinv[3], Ad[36];
+  win_tr(abR, Rabt);
+  const double nt[3] = {-abt[0], -abt[1], -abt[2]};
+  win_mv(Rabt, nt, tinv);
+  window_adjoint(Rabt, tinv, Ad);  // J_a = -Ad(between^-1), J_b = I
+  for (int p = 0; p < 6; ++p) {
+    for (int q = 0; q < 6; ++q) {
+      double s = 0;
+      for (int m = 0; m < 6; ++m) s += Om[6 * p + m] * -Ad[6 * m + q];
+      Eba[6 * p + q] = s;
+    }
+    double g = 0;
+    for (int m = 0; m < 6; ++m) g += Om[6 * p + m] * r[m];
+    gb[p] = g;
+  }
+  cost = 0.0;
+  for (int p = 0; p < 6; ++p) {
+    for (int q = 0; q < 6; ++q) {
+      double aa = 0;
+      for (int m = 0; m < 6; ++m) aa += -Ad[6 * m + p] * Eba[6 * m + q];
+      Baa[6 * p + q] = aa;
+    }
+    double g = 0;
+    for (int m = 0; m < 6; ++m) g += -Ad[6 * m + p] * gb[m];
+    ga[p] = g;
+    cost += r[p] * gb[p];
+  }
+}
+
 // L D L^T y = r for one factorised 6 x 6 block: the three sweeps of align_solve6
 MH_HD void window_solve6(const double L[36], const double D[6], const double * r, double * y)
 {
@@ -291,12 +363,33 @@ MH_HD bool window_relin_decide(const double d[6], double relin_rot, double relin
          fabs(d[5]) > relin_trans;
 }
 
-// w.A, w.E, w.rhs, w.cost from the factors' sums at the poses of `st`.  RELIN: the factors of `eval` from their sums (and into
-// rl, with the pose), the other non-empty ones from rl.  LIN: the linear factors of `lin` as well, carried to the poses of `st`
-template <bool RELIN, bool LIN, typename Par>
-MH_HD void window_assemble_impl(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, WindowRelin * rl, unsigned int eval,
-                                const WindowLinear * lin, WindowLinWork * lw, Par & par)
+// ew.B over the profile: block (i, k), lo(i) <= k < i, is the has_Z term of the pair (k = i - 1), then its edges in list order;
+// a block of the profile that has neither is fill: zero.  A phase of its own: window_solve_profile runs it again behind the
+// factorisation, which leaves its updated blocks in ew.B.
+template <typename Par>
+MH_HD void window_assemble_blocks(int W, const WindowParams & p, const WindowWork & w, const WindowEdges & ed, WindowEdgeWork & ew, Par & par)
 {
+  par.each(36 * (W * (W - 1) / 2), [&](int l) {
+    const int q = l / 36, e = l % 36;
+    int i = 1;
+    while (window_pair(i + 1, 0) <= q) ++i;
+    const int k = q - window_pair(i, 0);
+    if (k < ew.lo[i]) return;
+    double a = (k == i - 1 && ((p.has_Z >> i) & 1u)) ? w.E[i][e] : 0.0;
+    for (int j = 0; j < ed.n; ++j)
+      if (ed.b[j] == i && ed.a[j] == k) a += ew.Eba[j][e];
+    ew.B[q][e] = a;
+  });
+}
+
+// w.A, w.E, w.rhs, w.cost from the factors' sums at the poses of `st`.  RELIN: the factors of `eval` from their sums (and into
+// rl, with the pose), the other non-empty ones from rl.  LIN: the linear factors of `lin` as well, carried to the poses of `st`.
+// EDGE: the edges of `ed` as well, and every block below the diagonal into ew->B over the profile ew->lo (w.E keeps the has_Z terms)
+template <bool RELIN, bool LIN, bool EDGE, typename Par>
+MH_HD void window_assemble_impl(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, WindowRelin * rl, unsigned int eval,
+                                const WindowLinear * lin, WindowLinWork * lw, const WindowEdges * ed, WindowEdgeWork * ew, Par & par)
+{
+  const int n_edge = EDGE ? ed->n : 0;
   const int W = p.W;
   const int n_lin = LIN ? lin->n : 0;
   par.each(2 * W, [&](int l) {
@@ -342,8 +435,21 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
       window_local(lin->LR[j], lin->Lt[j], st.R[i], st.t[i], d);
       window_transport(lin->H[j], lin->b[j], lin->f[j], d, lw->H[j], lw->b[j], lw->f[j], lw->tmp[j]);
     });
+  if (EDGE)
+    par.each(n_edge + W, [&](int l) {
+      if (l < n_edge) {
+        const int a = ed->a[l], b = ed->b[l];
+        window_between_dense(st.R[a], st.t[a], st.R[b], st.t[b], ed->ZR[l], ed->Zt[l], ed->Om[l], ew->Baa[l], ew->Eba[l], ew->ga[l], ew->gb[l], ew->cz[l]);
+      } else {
+        const int i = l - n_edge;
+        int lo = ((p.has_Z >> i) & 1u) ? i - 1 : i;
+        for (int e = 0; e < n_edge; ++e)
+          if (ed->b[e] == i && ed->a[e] < lo) lo = ed->a[e];
+        ew->lo[i] = lo;
+      }
+    });
   // per entry in the order optimise() adds: the factor, (the linear factors on its pose in list order,) the between factors in
-  // window order, the prior, the damping
+  // window order, (the edges in list order,) the prior, the damping
   par.each(36 * W + 6 * W + 1, [&](int l) {
     if (l < 36 * W) {
       const int i = l / 36, e = l % 36, r = e / 6, c = e % 6;
@@ -353,6 +459,11 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
           if (lin->pose[j] == i) a += lw->H[j][e];
       if (r == c && ((p.has_Z >> i) & 1u)) a += p.Wb[r];
       if (i + 1 < W && ((p.has_Z >> (i + 1)) & 1u)) a += w.Baa[i + 1][e];
+      if (EDGE)
+        for (int j = 0; j < n_edge; ++j) {
+          if (ed->b[j] == i) a += ed->Om[j][e];
+          if (ed->a[j] == i) a += ew->Baa[j][e];
+        }
       if (r == c) {
         if (i == 0) a += p.prior[r];
         a += p.damping;
@@ -366,6 +477,11 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
           if (lin->pose[j] == i) g += lw->b[j][r];
       if ((p.has_Z >> i) & 1u) g += w.gb[i][r];
       if (i + 1 < W && ((p.has_Z >> (i + 1)) & 1u)) g += w.ga[i + 1][r];
+      if (EDGE)
+        for (int j = 0; j < n_edge; ++j) {
+          if (ed->b[j] == i) g += ew->gb[j][r];
+          if (ed->a[j] == i) g += ew->ga[j][r];
+        }
       w.rhs[q] = -g;
     } else {
       double cost = 0.0;
@@ -374,14 +490,17 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
         for (int j = 0; j < n_lin; ++j) cost += lw->f[j];
       for (int i = 1; i < W; ++i)
         if ((p.has_Z >> i) & 1u) cost += w.cz[i];
+      if (EDGE)
+        for (int j = 0; j < n_edge; ++j) cost += ew->cz[j];
       w.cost = cost;
     }
   });
+  if (EDGE) window_assemble_blocks(W, p, w, *ed, *ew, par);
 }
 template <typename Par>
 MH_HD void window_assemble(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, Par & par)
 {
-  window_assemble_impl<false, false>(sums, st, p, w, nullptr, 0u, nullptr, nullptr, par);
+  window_assemble_impl<false, false, false>(sums, st, p, w, nullptr, 0u, nullptr, nullptr, nullptr, nullptr, par);
 }
 
 // the block sweep: S_i = L_i D_i L_i^T and G_{i+1} for every block.  false (w.ok == 0): a pivot is not positive
@@ -481,15 +600,140 @@ MH_HD bool window_solve(int W, WindowWork & w, Par & par)
   return w.ok != 0;
 }
 
+// ---- the solve over a row profile (mh_icp_window_optimise_edges) ----------------------------------------------------------------
+// Block L D L^T of the system whose block row i holds blocks in the columns lo(i) .. i: with T_ik = L_ik S_k (the updated
+// off-diagonal block) and G_ik = S_k^-1 T_ik^T = L_ik^T,
+//   S_k = A_kk - sum_j T_kj G_kj,  T_ik = B_ik - sum_j T_ij G_kj  (j from max(lo(i), lo(k)) to k - 1),
+// column by column: S_k is factorised as window_factor factorises it, then every row below with lo(i) <= k takes its T_ik (in
+// place, in ew.B) and G_ik.  Fill stays inside [lo(i), i]; rows whose profile starts behind k are not touched.  A tridiagonal
+// system goes through the operations of window_factor, in its order.  false (w.ok == 0): a pivot is not positive
+template <typename Par>
+MH_HD bool window_factor_profile(int W, WindowWork & w, WindowEdgeWork & ew, Par & par)
+{
+  par.each(1, [&](int) { w.ok = 1; });
+  for (int k = 0; k < W; ++k) {
+    par.each(36, [&](int l) {
+      const int r = l / 6, c = l % 6;
+      double s = w.A[k][l];
+      for (int j = ew.lo[k]; j < k; ++j) {
+        const double *T = ew.B[window_pair(k, j)], *G = ew.G[window_pair(k, j)];
+        for (int m = 0; m < 6; ++m) s -= T[6 * r + m] * G[6 * m + c];
+      }
+      w.S[l] = s;
+    });
+    for (int j = 0; j < 6; ++j) {
+      par.each(6 - j, [&](int l) {
+        double d = w.S[7 * j];
+        for (int q = 0; q < j; ++q) d -= w.L[k][6 * j + q] * w.L[k][6 * j + q] * w.Dv[k][q];
+        if (l == 0) {
+          w.Dv[k][j] = d;
+          if (!(d > 0.0) || !(d < 1e300)) w.ok = 0;
+        } else {
+          const int row = j + l;
+          double s = w.S[6 * row + j];
+          for (int q = 0; q < j; ++q) s -= w.L[k][6 * row + q] * w.L[k][6 * j + q] * w.Dv[k][q];
+          w.L[k][6 * row + j] = s / d;
+        }
+      });
+      if (!w.ok) return false;
+    }
+    par.each(36 * (W - 1 - k), [&](int l) {
+      const int i = k + 1 + l / 36, e = l % 36, r = e / 6, c = e % 6;
+      if (ew.lo[i] > k) return;
+      double s = ew.B[window_pair(i, k)][e];
+      for (int j = ew.lo[i] > ew.lo[k] ? ew.lo[i] : ew.lo[k]; j < k; ++j) {
+        const double *T = ew.B[window_pair(i, j)], *G = ew.G[window_pair(k, j)];
+        for (int m = 0; m < 6; ++m) s -= T[6 * r + m] * G[6 * m + c];
+      }
+      ew.B[window_pair(i, k)][e] = s;
+    });
+    par.each(6 * (W - 1 - k), [&](int l) {
+      const int i = k + 1 + l / 6, c = l % 6;
+      if (ew.lo[i] > k) return;
+      double col[6];
+      window_solve6(w.L[k], w.Dv[k], &ew.B[window_pair(i, k)][6 * c], col);  // column c of T^T = row c of T
+      for (int m = 0; m < 6; ++m) ew.G[window_pair(i, k)][6 * m + c] = col[m];
+    });
+  }
+  return true;
+}
+
+// A out = v with the factors of window_factor_profile
+template <typename Par>
+MH_HD void window_sweep_profile(int W, WindowWork & w, const WindowEdgeWork & ew, const double * v, double * out, Par & par)
+{
+  for (int i = 0; i < W; ++i) {
+    par.each(6, [&](int r) {
+      double s = v[6 * i + r];
+      for (int k = ew.lo[i]; k < i; ++k) {
+        const double * G = ew.G[window_pair(i, k)];
+        for (int m = 0; m < 6; ++m) s -= G[6 * m + r] * w.y[6 * k + m];
+      }
+      w.y[6 * i + r] = s;
+    });
+  }
+  for (int i = W - 1; i >= 0; --i) {
+    par.each(1, [&](int) { window_solve6(w.L[i], w.Dv[i], &w.y[6 * i], w.z); });
+    par.each(6, [&](int r) {
+      double s = w.z[r];
+      for (int j = i + 1; j < W; ++j) {
+        if (ew.lo[j] > i) continue;
+        const double * G = ew.G[window_pair(j, i)];
+        for (int m = 0; m < 6; ++m) s -= G[6 * r + m] * out[6 * j + m];
+      }
+      out[6 * i + r] = s;
+    });
+  }
+}
+
+// window_solve over the profile: w.x from w.A, ew.B, w.rhs.  The factorisation leaves its updated blocks in ew.B, so the
+// blocks are assembled again behind it (the same phase, the same digits; a third set of 120 blocks would not fit the LDS a
+// workgroup may declare): the refinement's residual is taken with every block of the system as assembled.
+template <typename Par>
+MH_HD bool window_solve_profile(int W, const WindowParams & p, WindowWork & w, const WindowEdges & ed, WindowEdgeWork & ew, Par & par)
+{
+  if (!window_factor_profile(W, w, ew, par)) return false;
+  window_assemble_blocks(W, p, w, ed, ew, par);
+  window_sweep_profile(W, w, ew, w.rhs, w.x, par);
+  for (int it = 0; it < 2; ++it) {
+    par.each(6 * W, [&](int row) {
+      const int i = row / 6, r = row % 6;
+      double hi = w.rhs[row], lo = 0.0;
+      auto term = [&](double a, double xj) {
+        const double pr = a * xj, pe = fma(a, xj, -pr);  // a x = pr + pe exactly
+        const double s = hi - pr, bv = s - hi;
+        lo += ((hi - (s - bv)) + (-pr - bv)) - pe;  // two-sum of hi and -pr
+        hi = s;
+      };
+      for (int k = ew.lo[i]; k < i; ++k)
+        for (int m = 0; m < 6; ++m) term(ew.B[window_pair(i, k)][6 * r + m], w.x[6 * k + m]);
+      for (int m = 0; m < 6; ++m) term(w.A[i][6 * r + m], w.x[6 * i + m]);
+      for (int j = i + 1; j < W; ++j) {
+        if (ew.lo[j] > i) continue;
+        for (int m = 0; m < 6; ++m) term(ew.B[window_pair(j, i)][6 * m + r], w.x[6 * j + m]);
+      }
+      w.r[row] = hi + lo;
+    });
+    window_sweep_profile(W, w, ew, w.r, w.d, par);
+    par.each(6 * W, [&](int row) { w.x[row] += w.d[row]; });
+  }
+  par.each(1, [&](int) {
+    for (int q = 0; q < 6 * W; ++q)
+      if (!(fabs(w.x[q]) < 1e300)) w.ok = 0;
+  });
+  return w.ok != 0;
+}
+
 // One queued iteration: the chain's state in, the state and the iteration's row out.  sums: 32 doubles per pose (28 sums +
 // 4 counters; ignored where p.have has no bit).  arrived: the words of every factor carry the call's number (they always do; a
 // chain that finds otherwise stops).  Returns the row's flags.  Once st.stopped is set the poses are passed on unchanged.
 // RELIN: `arrived` speaks of the factors this iteration evaluates (window_relin_mask); behind the step, rl holds every pose's
 // offset from its linearization pose and the factors the next iteration evaluates.
 // LIN: the system and the cost also hold the linear factors of `lin` (lw: their work arrays); nothing else changes.
-template <bool RELIN, bool LIN, typename Par>
+// EDGE: ... and the edges of `ed` (ew: their work arrays and the profile); the system is solved by window_solve_profile.
+template <bool RELIN, bool LIN, bool EDGE, typename Par>
 MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrived, const WindowParams & p, WindowWork & w, double * row, WindowRelin * rl,
-                              const WindowRelinParams * rp, const WindowLinear * lin, WindowLinWork * lw, Par & par)
+                              const WindowRelinParams * rp, const WindowLinear * lin, WindowLinWork * lw, const WindowEdges * ed, WindowEdgeWork * ew, Par & par)
 {
   const int W = p.W;
   const bool frozen = st.stopped != 0;
@@ -498,8 +742,11 @@ MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrive
   par.sync();  // (every index has read the state before index 0 changes it)
   bool stepped = false;
   if (!frozen && arrived) {
-    window_assemble_impl<RELIN, LIN>(sums, st, p, w, rl, eval, lin, lw, par);
-    stepped = window_solve(W, w, par);
+    window_assemble_impl<RELIN, LIN, EDGE>(sums, st, p, w, rl, eval, lin, lw, ed, ew, par);
+    if (EDGE)
+      stepped = window_solve_profile(W, p, w, *ed, *ew, par);
+    else
+      stepped = window_solve(W, w, par);
     par.each(W, [&](int i) {
       if (stepped) {
         const double * xi = &w.x[6 * i];
@@ -575,7 +822,7 @@ MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrive
 template <typename Par>
 MH_HD int window_advance(WindowState & st, const double * sums, bool arrived, const WindowParams & p, WindowWork & w, double * row, Par & par)
 {
-  return window_advance_impl<false, false>(st, sums, arrived, p, w, row, nullptr, nullptr, nullptr, nullptr, par);
+  return window_advance_impl<false, false, false>(st, sums, arrived, p, w, row, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, par);
 }
 // the factors the iteration about to run evaluates (read before window_advance_relin changes rl)
 MH_HD unsigned int window_relin_mask(const WindowRelin & rl, const WindowParams & p, const WindowRelinParams & rp) { return rp.first ? p.have : rl.eval; }
@@ -583,15 +830,23 @@ template <typename Par>
 MH_HD int window_advance_relin(WindowState & st, WindowRelin & rl, const double * sums, bool arrived, const WindowParams & p, const WindowRelinParams & rp,
                                WindowWork & w, double * row, Par & par)
 {
-  return window_advance_impl<true, false>(st, sums, arrived, p, w, row, &rl, &rp, nullptr, nullptr, par);
+  return window_advance_impl<true, false, false>(st, sums, arrived, p, w, row, &rl, &rp, nullptr, nullptr, nullptr, nullptr, par);
 }
 // mh_icp_window_optimise_lin: either chain with the linear factors of `lin`.  rl, rp: null for the plain chain
 template <typename Par>
 MH_HD int window_advance_lin(WindowState & st, WindowRelin * rl, const double * sums, bool arrived, const WindowParams & p, const WindowRelinParams * rp,
                              const WindowLinear & lin, WindowLinWork & lw, WindowWork & w, double * row, Par & par)
 {
-  if (rl) return window_advance_impl<true, true>(st, sums, arrived, p, w, row, rl, rp, &lin, &lw, par);
-  return window_advance_impl<false, true>(st, sums, arrived, p, w, row, nullptr, nullptr, &lin, &lw, par);
+  if (rl) return window_advance_impl<true, true, false>(st, sums, arrived, p, w, row, rl, rp, &lin, &lw, nullptr, nullptr, par);
+  return window_advance_impl<false, true, false>(st, sums, arrived, p, w, row, nullptr, nullptr, &lin, &lw, nullptr, nullptr, par);
+}
+// mh_icp_window_optimise_edges: window_advance_lin with the edges of `ed` (ed.n may be 0: the same system through the profile solve)
+template <typename Par>
+MH_HD int window_advance_edges(WindowState & st, WindowRelin * rl, const double * sums, bool arrived, const WindowParams & p, const WindowRelinParams * rp,
+                               const WindowLinear & lin, WindowLinWork & lw, const WindowEdges & ed, WindowEdgeWork & ew, WindowWork & w, double * row, Par & par)
+{
+  if (rl) return window_advance_impl<true, true, true>(st, sums, arrived, p, w, row, rl, rp, &lin, &lw, &ed, &ew, par);
+  return window_advance_impl<false, true, true>(st, sums, arrived, p, w, row, nullptr, nullptr, &lin, &lw, &ed, &ew, par);
 }
 
 }  // namespace mh
@@ -638,5 +893,14 @@ struct WindowLinStepArgs
   const WindowLinear * lin;  // device memory the context owns
 };
 hipError_t launch_window_lin_step(const WindowLinStepArgs & a, bool relin, hipStream_t stream);
+
+// One step of an mh_icp_window_optimise_edges chain (window_edge_kernels.hip): the lin step with the edges of `edges`, which
+// the host wrote once per call, solved over the row profile.
+struct WindowEdgeStepArgs
+{
+  WindowLinStepArgs l;
+  const WindowEdges * edges;  // device memory the context owns
+};
+hipError_t launch_window_edge_step(const WindowEdgeStepArgs & a, bool relin, hipStream_t stream);
 }  // namespace mh
 #endif

@@ -1,11 +1,13 @@
-// icp_window_lin_step_kernel: the step of an mh_icp_window_optimise_lin chain (chain_api.hip) — icp_window_step_kernel
-// (window_kernels.hip) or, with RELIN, icp_window_relin_step_kernel (window_relin_kernels.hip), whose system also holds Hessian
-// factors the host linearized once: one more phase per iteration carries each of them from its linearization pose to the
-// current pose of its variable (window_device.hpp: window_transport), one index per factor, into LDS; the assembly adds them
-// behind the pose's own factor.  The factors themselves sit in the context's device block, written once per call and only
-// read here.  One workgroup of one wave, a barrier behind each phase, everything fp64, compiled without floating-point
-// contraction so that the host build of the header gives the same digits.  A translation unit of its own, so that the other
-// two step kernels are compiled exactly as they were.
+// icp_window_edge_step_kernel: the step of an mh_icp_window_optimise_edges chain (chain_api.hip) — icp_window_lin_step_kernel
+// (window_lin_kernels.hip) whose system also holds between factors on any pair of poses, each with a dense information matrix:
+// one more phase per iteration evaluates each of them at the current poses (window_device.hpp: window_between_dense), one
+// index per edge, into LDS; the assembly adds them behind the has_Z terms.  The system is then no longer block-tridiagonal
+// and is solved over its row profile (window_factor_profile): the off-diagonal blocks and the factor's S_k^-1 T^T, up to 120
+// blocks of 6 x 6 each, sit in LDS as well — 153 960 B in all, under the 160 KiB one workgroup of gfx950 may declare; one
+// workgroup per launch, so occupancy is not a concern.  The edges themselves sit in the context's device block, written once
+// per call and only read here.  One workgroup of one wave, a barrier behind each phase, everything fp64, compiled without
+// floating-point contraction so that the host build of the header gives the same digits.  A translation unit of its own, so
+// that the other step kernels are compiled exactly as they were.
 #include <hip/hip_runtime.h>
 
 #include "icp_device.hpp"
@@ -31,13 +33,15 @@ struct WindowWave
 }  // namespace
 
 template <bool RELIN>
-__global__ __launch_bounds__(kWindowLanes) void icp_window_lin_step_kernel(const WindowLinStepArgs la)
+__global__ __launch_bounds__(kWindowLanes) void icp_window_edge_step_kernel(const WindowEdgeStepArgs ea)
 {
   __shared__ WindowWork s_w;
   __shared__ WindowLinWork s_lw;
+  __shared__ WindowEdgeWork s_ew;
   __shared__ double s_sum[32 * kWindowMax];
   __shared__ double s_row[kWRowPose + 12 * kWindowMax];
   __shared__ int s_missing;
+  const WindowLinStepArgs & la = ea.l;
   const WindowRelinStepArgs & ra = la.r;
   const WindowStepArgs & a = ra.s;
   const int lane = static_cast<int>(threadIdx.x);
@@ -63,8 +67,8 @@ __global__ __launch_bounds__(kWindowLanes) void icp_window_lin_step_kernel(const
   const bool missing = s_missing != 0;
 
   WindowWave par{lane};
-  const int flags = window_advance_impl<RELIN, true, false>(*a.state, s_sum, !missing, a.p, s_w, s_row, RELIN ? ra.relin : nullptr, RELIN ? &ra.rp : nullptr,
-                                                            la.lin, &s_lw, nullptr, nullptr, par);
+  const int flags = window_advance_impl<RELIN, true, true>(*a.state, s_sum, !missing, a.p, s_w, s_row, RELIN ? ra.relin : nullptr, RELIN ? &ra.rp : nullptr,
+                                                           la.lin, &s_lw, ea.edges, &s_ew, par);
 
   // the launches queued behind this step: the new poses, and n = 0 once the chain has stopped or (RELIN) for a factor that
   // keeps its linearization
@@ -93,13 +97,13 @@ __global__ __launch_bounds__(kWindowLanes) void icp_window_lin_step_kernel(const
   for (int l = lane; l < kWRowPose + 12 * W; l += kWindowLanes) ll_store(a.row_host + l, s_row[l], a.seq);
 }
 
-hipError_t launch_window_lin_step(const WindowLinStepArgs & a, bool relin, hipStream_t stream)
+hipError_t launch_window_edge_step(const WindowEdgeStepArgs & a, bool relin, hipStream_t stream)
 {
-  if (a.r.s.p.W < 1 || a.r.s.p.W > kWindowMax || !a.lin) return hipErrorInvalidValue;
+  if (a.l.r.s.p.W < 1 || a.l.r.s.p.W > kWindowMax || !a.l.lin || !a.edges) return hipErrorInvalidValue;
   if (relin)
-    hipLaunchKernelGGL(icp_window_lin_step_kernel<true>, dim3(1), dim3(kWindowLanes), 0, stream, a);
+    hipLaunchKernelGGL(icp_window_edge_step_kernel<true>, dim3(1), dim3(kWindowLanes), 0, stream, a);
   else
-    hipLaunchKernelGGL(icp_window_lin_step_kernel<false>, dim3(1), dim3(kWindowLanes), 0, stream, a);
+    hipLaunchKernelGGL(icp_window_edge_step_kernel<false>, dim3(1), dim3(kWindowLanes), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -648,6 +648,25 @@ public:
     l.f = h.constantTerm();
     return l;
   }
+  // A between factor on any pair of poses a < b of the window, with its own measurement and a dense information matrix in
+  // (rotation, translation) order (mh_icp_window_optimise_edges): what BetweenFactor<Pose3>(X(a), X(b), Z, model) is to ISAM2.
+  struct WindowEdge
+  {
+    size_t a = 0, b = 0;  // indices into the window
+    Pose3 Z;              // the measured T_a^-1 T_b
+    M66 info;
+  };
+  // from diagonal sigmas (rotation rad x 3, translation m x 3), the order of noiseModel::Diagonal::Sigmas on a Pose3
+  static WindowEdge windowEdgeFromSigmas(size_t a, size_t b, const Pose3 & Z, const V6D & sigmas)
+  {
+    WindowEdge e;
+    e.a = a;
+    e.b = b;
+    e.Z = Z;
+    e.info = M66::Zero();
+    for (int r = 0; r < 6; ++r) e.info(r, r) = 1.0 / (sigmas(r) * sigmas(r));
+    return e;
+  }
   // a call in flight (optimiseWindowAsync): wait() collects it
   class WindowCall
   {
@@ -684,6 +703,7 @@ public:
     mh_icp_window_relin relin_{};
     std::vector<uint32_t> masks_;
     std::vector<mh_window_linear_factor> lin_;
+    std::vector<mh_window_edge> edges_;
   };
   static WindowResult optimiseWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
                                      const Unit3 & g, const WindowConfig & config)
@@ -717,6 +737,21 @@ public:
                                                             const std::vector<WindowLinear> & linear, const WindowRelin * relin = nullptr)
   {
     return startWindow(factors, poses, between, g, config, false, relin, &linear);
+  }
+
+  // ... and with edges on any pair of poses; an empty `edges` takes the same entry point with no edge
+  static WindowResult optimiseWindowEdges(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
+                                          const Unit3 & g, const WindowConfig & config, const std::vector<WindowLinear> & linear,
+                                          const std::vector<WindowEdge> & edges, const WindowRelin * relin = nullptr)
+  {
+    return startWindow(factors, poses, between, g, config, true, relin, &linear, &edges)->finish();
+  }
+  static std::unique_ptr<WindowCall> optimiseWindowEdgesAsync(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses,
+                                                              const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config,
+                                                              const std::vector<WindowLinear> & linear, const std::vector<WindowEdge> & edges,
+                                                              const WindowRelin * relin = nullptr)
+  {
+    return startWindow(factors, poses, between, g, config, false, relin, &linear, &edges);
   }
 
   // getters, :48-72
@@ -787,7 +822,7 @@ private:
   const Context & ctx() const { return *ivox_target_->context(); }
   static std::unique_ptr<WindowCall> startWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
                                                  const Unit3 & g, const WindowConfig & config, bool blocking, const WindowRelin * relin = nullptr,
-                                                 const std::vector<WindowLinear> * linear = nullptr)
+                                                 const std::vector<WindowLinear> * linear = nullptr, const std::vector<WindowEdge> * edges = nullptr)
   {
     const size_t n = factors.size();
     if (!n || poses.size() != n || between.size() != n) throw std::runtime_error("ICPFactor::optimiseWindow: one pose and one between entry per factor");
@@ -841,6 +876,26 @@ private:
         w->relin_.relin_rot = relin->rot;
         w->relin_.relin_trans = relin->trans;
         w->masks_.assign(static_cast<size_t>(config.iters > 0 ? config.iters : 0), 0u);
+      }
+      if (edges) {
+        for (const WindowEdge & e : *edges) {
+          mh_window_edge q;
+          std::memset(&q, 0, sizeof(q));
+          q.pose_a = e.a < n ? static_cast<int32_t>(e.a) : -1;  // (out of range: the library's to refuse)
+          q.pose_b = e.b < n ? static_cast<int32_t>(e.b) : -1;
+          const PoseRM Z = rowMajor(e.Z);
+          std::memcpy(q.Z_R, Z.R.data(), 72);
+          std::memcpy(q.Z_t, Z.t.data(), 24);
+          for (int r = 0; r < 6; ++r)
+            for (int c = 0; c < 6; ++c) q.info[6 * r + c] = e.info(r, c);
+          w->edges_.push_back(q);
+        }
+        const auto fe = blocking ? mh_icp_window_optimise_edges : mh_icp_window_optimise_edges_async;
+        factors[0]->ctx().check(fe(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_,
+                                   relin ? &w->relin_ : nullptr, w->lin_.data(), w->lin_.size(), w->edges_.data(), w->edges_.size(), w->r_.get(), nullptr,
+                                   relin ? w->masks_.data() : nullptr),
+                                blocking ? "mh_icp_window_optimise_edges" : "mh_icp_window_optimise_edges_async");
+        return w;
       }
       const auto fl = blocking ? mh_icp_window_optimise_lin : mh_icp_window_optimise_lin_async;
       factors[0]->ctx().check(fl(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_,

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "manager.hpp"
+#include "odometry.hpp"
 
 namespace mimosa_hip
 {
@@ -259,6 +260,12 @@ struct Config
   // initial poses (photo_window: every live one, in one batch call) and hands the results to the chain as linear factors on their
   // poses (ICPFactor::optimiseWindowLin), which carries them along instead of evaluating them again.  Refused without device_window
   bool window_photo_linear = false;
+  // > 0: the scans carry the messages of an external odometry source (ScanInput::has_odometry, at every odometry_every-th scan);
+  // each goes through odometry::Manager and becomes a between factor with these sigmas on the window poses of scans
+  // k - odometry_every and k, beside the IMU ties, dropped once its older pose has left the window.  With device_window the edges
+  // go to ICPFactor::optimiseWindowEdges.  Unlike the reference's source, this one reports at scan times.  FixedLagReplay only
+  int odometry_every = 0;
+  double odometry_sigma_rot_deg = 1.0, odometry_sigma_trans_m = 0.5;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
   lidar::ManagerInputConfig input = lidar::defaultManagerInputConfig();
@@ -272,6 +279,9 @@ struct ScanInput
   std::vector<lidar::PointOuster> raw;
   ImuSamples imu;
   double header_ts = 0;
+  bool has_odometry = false;  // Config::odometry_every: the external odometry's pose of this scan and its covariance (row-major)
+  RT odometry_T;
+  double odometry_cov[36] = {};
 };
 
 struct Result
@@ -396,7 +406,32 @@ public:
     }
     win.push_back(lv);
     if (static_cast<int>(win.size()) > window_) win.pop_front();
+    expireEdges();
   }
+  // A between factor on the poses of scans ka < kb with its own dense information matrix (the odometry manager's), beside the
+  // has_Z ties; it is dropped once the pose of ka has left the window
+  struct Edge
+  {
+    size_t ka, kb;
+    RT Z;
+    double info[36];
+  };
+  // on: optimise() on the device goes through FactorT::optimiseWindowEdges, also while no edge is live
+  void setEdges(bool on) { edges_on_ = on; }
+  void addEdge(size_t ka, size_t kb, const ICPFactor::WindowEdge & e)
+  {
+    Edge q;
+    q.ka = ka;
+    q.kb = kb;
+    const PoseRM Z = rowMajor(e.Z);
+    q.Z.R = Z.R;
+    q.Z.t = Z.t;
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) q.info[6 * r + c] = e.info(r, c);
+    edges_.push_back(q);
+    expireEdges();
+  }
+  size_t liveEdges() const { return edges_.size(); }
   const RT & newest() const { return win.back().T; }
   void clear() { win.clear(); }
   // on: optimise() re-linearizes the photometric factors the window's entries carry (Live::pf) instead of `pf`
@@ -511,6 +546,45 @@ public:
             cost += r[p] * Wb[p] * r[p];
           }
         }
+        for (const Edge & e : edges_) {  // the edges, behind the has_Z ties: the same residual and Jacobians, a dense weight
+          const size_t ia = e.ka - win[0].k, ib = e.kb - win[0].k;
+          const RT ab = between(win[ia].T, win[ib].T);
+          const A9 Rzt = transpose(e.Z.R);
+          const A9 Re = matmul(Rzt, ab.R);
+          const A3 te = matvec(Rzt, {ab.t[0] - e.Z.t[0], ab.t[1] - e.Z.t[1], ab.t[2] - e.Z.t[2]});
+          const A3 lr = so3Log(Re);
+          const double r[6] = {lr[0], lr[1], lr[2], te[0], te[1], te[2]};
+          const A9 Rabt = transpose(ab.R);
+          const A3 tinv = matvec(Rabt, {-ab.t[0], -ab.t[1], -ab.t[2]});
+          const A36 Ad = adjoint(Rabt, tinv);  // J_a = -Ad(between^-1), J_b = I
+          double OJ[36], Or[6];                // Om J_a, Om r
+          for (int p = 0; p < 6; ++p) {
+            for (int q = 0; q < 6; ++q) {
+              double sum = 0;
+              for (int m = 0; m < 6; ++m) sum += e.info[6 * p + m] * -Ad[6 * m + q];
+              OJ[6 * p + q] = sum;
+            }
+            double sum = 0;
+            for (int m = 0; m < 6; ++m) sum += e.info[6 * p + m] * r[m];
+            Or[p] = sum;
+          }
+          const size_t oa = 6 * ia, ob = 6 * ib;
+          for (int p = 0; p < 6; ++p) {
+            for (int q = 0; q < 6; ++q) {
+              double aa = 0;
+              for (int m = 0; m < 6; ++m) aa += -Ad[6 * m + p] * OJ[6 * m + q];
+              A[(oa + p) * dim + oa + q] += aa;
+              A[(oa + p) * dim + ob + q] += OJ[6 * q + p];
+              A[(ob + p) * dim + oa + q] += OJ[6 * p + q];
+              A[(ob + p) * dim + ob + q] += e.info[6 * p + q];
+            }
+            double ga = 0;
+            for (int m = 0; m < 6; ++m) ga += -Ad[6 * m + p] * Or[m];
+            g[oa + p] += ga;
+            g[ob + p] += Or[p];
+            cost += r[p] * Or[p];
+          }
+        }
         // what marginalisation leaves on the oldest pose; loose while that pose has never been optimised
         const bool loose = win[0].k == first_k_ && static_cast<int>(k - first_k_) < cfg_.window;
         const double sr = loose ? 0.017453292519943295 : 1e-4, st = loose ? 0.1 : 1e-4;
@@ -592,7 +666,17 @@ private:
         }
       }
       const Unit3 down(0.0, 0.0, -1.0);
-      const ICPFactor::WindowResult r = window_photo_linear_ ? ICPFactor::optimiseWindowLin(factors, poses, between, down, wc, linear, window_relin_ ? &rl : nullptr)
+      std::vector<ICPFactor::WindowEdge> edges;
+      for (const Edge & e : edges_) {
+        ICPFactor::WindowEdge q;
+        q.a = e.ka - win[0].k;
+        q.b = e.kb - win[0].k;
+        q.Z = toPose3(e.Z);
+        q.info = matrix6(e.info);
+        edges.push_back(q);
+      }
+      const ICPFactor::WindowResult r = edges_on_ ? ICPFactor::optimiseWindowEdges(factors, poses, between, down, wc, linear, edges, window_relin_ ? &rl : nullptr)
+                                        : window_photo_linear_ ? ICPFactor::optimiseWindowLin(factors, poses, between, down, wc, linear, window_relin_ ? &rl : nullptr)
                                         : window_relin_      ? ICPFactor::optimiseWindowRelin(factors, poses, between, down, wc, rl)
                                                              : ICPFactor::optimiseWindow(factors, poses, between, down, wc);
       if (r.iters != update_iters_) throw std::runtime_error("replay::solve: singular system");
@@ -610,6 +694,16 @@ private:
       throw std::runtime_error("replay: device_window is offered for lidar::ICPFactor only");
     }
   }
+  void expireEdges()
+  {
+    for (size_t j = 0; j < edges_.size();)
+      if (win.empty() || edges_[j].ka < win.front().k)
+        edges_.erase(edges_.begin() + static_cast<std::ptrdiff_t>(j));
+      else
+        ++j;
+  }
+  std::vector<Edge> edges_;
+  bool edges_on_ = false;
   bool device_window_ = false, window_relin_ = false, window_photo_linear_ = false;
   double relin_rot_ = 0.0, relin_trans_ = 0.0;
   int window_, update_iters_;
@@ -687,6 +781,15 @@ public:
     smoother.setDeviceWindow(cfg_.device_window);
     smoother.setWindowPhotoLinear(cfg_.window_photo_linear);
     smoother.setWindowRelin(cfg_.window_relin, cfg_.window_relin_rot, cfg_.window_relin_trans);
+    std::unique_ptr<odometry::Manager> odo;
+    if (cfg_.odometry_every > 0) {
+      if constexpr (!std::is_same<typename Geo::Factor, ICPFactor>::value) throw std::runtime_error("replay: odometry_every is offered by FixedLagReplay only");
+      odometry::ManagerConfig oc;  // T_B_S = identity: the source reports the pose the window estimates
+      oc.sigma_rot_deg = static_cast<float>(cfg_.odometry_sigma_rot_deg);
+      oc.sigma_trans_m = static_cast<float>(cfg_.odometry_sigma_trans_m);
+      odo.reset(new odometry::Manager(oc));
+      smoother.setEdges(true);
+    }
     std::deque<Live> & win = smoother.win;
     std::vector<RT> kf_poses;
     State prev = state0;
@@ -822,6 +925,11 @@ public:
       PhotometricFactor::Ptr pf = photo_ ? photo_->factor() : nullptr;
       if (cfg_.photo_window) lv.pf = pf;
       smoother.push(lv);
+      if (odo && sc.has_odometry) {
+        odometry::Manager::Measurement m;
+        if (odo->callback(toPose3(sc.odometry_T), sc.odometry_cov, k, m) == odometry::Manager::Outcome::Factor)
+          smoother.addEdge(static_cast<size_t>(m.prev_key), k, odometry::Manager::windowEdge(m, 0, 1));
+      }
       if (cfg_.photo_window) res.photo_in_window.push_back(static_cast<int>(smoother.photoFactorsInWindow()));
       const auto a4 = clk::now();
       const std::vector<double> fs = smoother.optimise(k, pf);
@@ -1050,6 +1158,7 @@ public:
   {
     if (cfg.photo_window) throw std::runtime_error("ManagerReplay: photo_window is not offered through lidar::Manager (FixedLagReplay only)");
     if (cfg.device_window) throw std::runtime_error("ManagerReplay: device_window is not offered through lidar::Manager (FixedLagReplay only)");
+    if (cfg.odometry_every > 0) throw std::runtime_error("ManagerReplay: odometry_every is not offered through lidar::Manager (FixedLagReplay only)");
     if (cfg.init_align) throw std::runtime_error("ManagerReplay: init_align is not offered through lidar::Manager (FixedLagReplay only)");
     lidar::ManagerConfig mc;
     mc.range_min = cfg.input.range_min;

@@ -66,6 +66,7 @@ public:
   {
     if (cfg.photo_window) throw std::runtime_error("ShardedFixedLagReplay: photo_window is not offered by the sharded replay");
     if (cfg.device_window) throw std::runtime_error("ShardedFixedLagReplay: device_window is not offered by the sharded replay");
+    if (cfg.odometry_every > 0) throw std::runtime_error("ShardedFixedLagReplay: odometry_every is not offered by the sharded replay");
   }
 };
 

@@ -1,11 +1,14 @@
 // Native sequence replay: drives mimosa_hip::replay::FixedLagReplay (host/mimosa_hip/replay.hpp) on an input file written
 // by mimosa_amd/replay.py:write_native_input and prints one JSON object (estimated poses, per-stage seconds, scans/s).
-//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear] | device-window-relin=<rot>,<trans>[+photo-linear]] [device-poses]
+//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear] | device-window-relin=<rot>,<trans>[+photo-linear]] [odometry] [device-poses]
 //     device-poses (last word): replay::Config::device_poses — the per-timestamp deskew poses are computed on the device
 //     device-window (in front of it): replay::Config::device_window — the smoother's iterations run as one chain of launches on
 //       the device (FixedLagReplay without the photometric factor; refused elsewhere).  +photo-linear behind either form:
 //       replay::Config::window_photo_linear — the photometric factor is accepted, linearized once per window call on the host
 //       and carried by the chain as a linear factor
+//     odometry (in front of device-poses, behind the window word): replay::Config::odometry_every — the input file ends with the
+//       external odometry section (odometry_every; sigma_rot_deg, sigma_trans_m; per message scan index, pose, covariance); each
+//       message goes through odometry::Manager and ties the window poses of two scans (FixedLagReplay; refused elsewhere)
 //     repeats > 1: the whole sequence again, timing of the last pass is reported
 //     sharded <world>: the map sharded over <world> ranks INSIDE this process (one host thread and one context each, in-process
 //       transport: what a one-GPU box can run); sharded-rccl: this process is one rank of a torch.distributed.run-style launch
@@ -24,11 +27,14 @@ using binio::read_vec;
 int main(int argc, char ** argv)
 {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear] | device-window-relin=<rot>,<trans>[+photo-linear]] [device-poses]\n");
+    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear] | device-window-relin=<rot>,<trans>[+photo-linear]] [odometry] [device-poses]\n");
     return 2;
   }
   const bool device_poses = argc > 2 && std::string(argv[argc - 1]) == "device-poses";
   if (device_poses) --argc;
+  // odometry: the input file ends with the external odometry section (replay::Config::odometry_every, the sigmas, the messages)
+  const bool odometry = argc > 2 && std::string(argv[argc - 1]) == "odometry";
+  if (odometry) --argc;
   // device-window-relin=<rot>,<trans>: device-window with replay::Config::window_relin (relinearization thresholds, rad and m)
   std::string window_word = argc > 2 ? argv[argc - 1] : "";
   const std::string photo_suffix = "+photo-linear";
@@ -92,6 +98,23 @@ int main(int argc, char ** argv)
         sc.imu.acc.push_back({ac[3 * j], ac[3 * j + 1], ac[3 * j + 2]});
       }
       sc.header_ts = read_vec<double>(f).at(0);
+    }
+    if (odometry) {
+      const auto oe = read_vec<int32_t>(f);  // odometry_every
+      const auto os = read_vec<double>(f);   // sigma_rot_deg, sigma_trans_m
+      const auto om = read_vec<double>(f);   // per message: scan index, R (9), t (3), covariance (36, row-major)
+      if (!f || oe.size() != 1 || oe[0] < 1 || os.size() != 2 || om.size() % 49) throw std::runtime_error("odometry: the input file has no odometry section");
+      cfg.odometry_every = oe[0];
+      cfg.odometry_sigma_rot_deg = os[0];
+      cfg.odometry_sigma_trans_m = os[1];
+      for (size_t j = 0; j < om.size() / 49; ++j) {
+        const double * q = &om[49 * j];
+        replay::ScanInput & sc = scans.at(static_cast<size_t>(q[0]));
+        sc.has_odometry = true;
+        for (int i = 0; i < 9; ++i) sc.odometry_T.R[i] = q[1 + i];
+        for (int i = 0; i < 3; ++i) sc.odometry_T.t[i] = q[10 + i];
+        for (int i = 0; i < 36; ++i) sc.odometry_cov[i] = q[13 + i];
+      }
     }
     replay::State st0;
     if (s0.size() < 15) throw std::runtime_error("the initial state needs 15 doubles");

@@ -82,12 +82,61 @@ class ReplayConfig:
     # initial poses (photo_window: every live one, through the batch call) and passes the results as linear factors on their poses
     # (mh_icp_window_optimise_lin), which the chain carries along instead of evaluating them again.  Refused without device_window
     window_photo_linear: bool = False
+    # > 0: a synthetic external odometry source delivers, at every odometry_every-th scan, the true pose with noise from a fixed
+    # seed and a covariance; the message goes through the odometry manager's rules (OdometryManager; the reference:
+    # src/odometry/manager.cpp:22-67) and becomes a between factor with these sigmas on the window poses of scans
+    # k - odometry_every and k, beside the IMU ties; it is dropped once its older pose has left the window.  With device_window
+    # the edges go to mh_icp_window_optimise_edges.  Unlike the reference's source, this one reports at scan times.  0: off
+    odometry_every: int = 0
+    odometry_sigma_rot_deg: float = 1.0
+    odometry_sigma_trans_m: float = 0.5
     reg: dict = field(default_factory=synth.enwide_config)
     photo: dict = None
 
     def __post_init__(self):
         if self.photo is None:
             self.photo = _photo_cfg(self.rows, self.cols)
+
+
+# ---- external odometry (ReplayConfig.odometry_every) ---------------------------------------------------------------------
+ODOMETRY_SEED = 11
+ODOMETRY_NOISE = (1e-3, 5e-3)  # rad, m: the synthetic source's own error, which its covariance states
+
+
+def odometry_messages(cfg, scans):
+    """[(k, R, t, covariance 6 x 6)]: at every odometry_every-th scan the true pose with noise from a fixed seed"""
+    if cfg.odometry_every <= 0:
+        return []
+    rng = np.random.default_rng(ODOMETRY_SEED)
+    cov = np.diag([ODOMETRY_NOISE[0] ** 2] * 3 + [ODOMETRY_NOISE[1] ** 2] * 3)
+    out = []
+    for k in range(0, len(scans), cfg.odometry_every):
+        R = scans[k]["R_gt"] @ synth.so3_exp(ODOMETRY_NOISE[0] * rng.standard_normal(3))
+        out.append((k, R, scans[k]["t_gt"] + ODOMETRY_NOISE[1] * rng.standard_normal(3), cov))
+    return out
+
+
+class OdometryManager:
+    """odometry::Manager::callback (src/odometry/manager.cpp:22-67) without ROS, T_B_S = identity: the D-optimality gate
+    (utils.hpp:21 as written; a negative determinant gives NaN, which passes), the first accepted message only initialises, every
+    later one gives (previous key, Z = T_km1^-1 T_k, information matrix from the configured sigmas)."""
+
+    def __init__(self, sigma_rot_deg, sigma_trans_m, d_opt_thresh=1.0):
+        sr = float(sigma_rot_deg) * np.pi / 180.0
+        self.info = np.diag([1.0 / (sr * sr)] * 3 + [1.0 / (float(sigma_trans_m) * float(sigma_trans_m))] * 3)
+        self.thresh, self.prev = d_opt_thresh, None
+
+    def callback(self, key, R, t, cov):
+        with np.errstate(invalid="ignore"):
+            d_opt = np.exp(np.log(np.power(np.float64(np.linalg.det(np.asarray(cov, float))), 1.0 / 6.0)))
+        if d_opt > self.thresh:
+            return None
+        out = None
+        if self.prev is not None:
+            pk, Rp, tp = self.prev
+            out = (pk, _between(Rp, tp, R, t), self.info)
+        self.prev = (key, R, t)
+        return out
 
 
 # ---- SE(3) helpers (Pose3 tangent order: rotation first) ---------------------------------------------------------
@@ -281,7 +330,7 @@ class HipBackend:
         rs = self.capi.linearize_batch(factors, [p[0] for p in poses], [p[1] for p in poses])
         return [(np.asarray(r["H_ss"]).reshape(6, 6), np.asarray(r["b_s"]), float(r["f"])) for r in rs]
 
-    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping, relin=None, linear=None):
+    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping, relin=None, linear=None, edges=None):
         """device_window: the smoother's loop over the window as one call; the poses after it and the cost before each iteration.
         linear: host-linearized Hessian factors on poses of the window (capi.optimise_window)"""
         cfg = self.capi.make_window_config(iters=iters, between_info=between_info, prior_info=prior_info, damping=damping)
@@ -289,6 +338,8 @@ class HipBackend:
         kw = {} if relin is None else dict(relin=relin)
         if linear is not None:
             kw["linear"] = linear
+        if edges is not None:  # mh_icp_window_optimise_edges, also with an empty list
+            kw["edges"] = edges
         r = self.capi.optimise_window(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs], **kw)
         if r["iters"] != iters:
             raise np.linalg.LinAlgError("Singular matrix")
@@ -370,6 +421,11 @@ def write_native_input(path, cfg: ReplayConfig, scans, rng_seed=7, mode=synth.EN
             w(np.asarray(gyro, np.float64).ravel())
             w(np.asarray(acc, np.float64).ravel())
             w([sc["header_ts"]], np.float64)
+        if cfg.odometry_every > 0:  # the trailing section the driver reads behind its `odometry` word
+            w([cfg.odometry_every], np.int32)
+            w([cfg.odometry_sigma_rot_deg, cfg.odometry_sigma_trans_m], np.float64)
+            msgs = odometry_messages(cfg, scans)
+            w(np.concatenate([np.concatenate([[float(k)], R.ravel(), t, cov.ravel()]) for k, R, t, cov in msgs]) if msgs else np.zeros(0), np.float64)
 
 
 def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible_device=None, through_manager=False, sequential=False,
@@ -404,6 +460,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
     if cfg.device_window:
         word = "device-window" if cfg.window_relin is None else "device-window-relin=%r,%r" % (float(cfg.window_relin[0]), float(cfg.window_relin[1]))
         mode = mode + [word + ("+photo-linear" if cfg.window_photo_linear else "")]
+    if cfg.odometry_every > 0:
+        mode = mode + ["odometry"]
     if cfg.device_poses:
         mode = mode + ["device-poses"]
     out = subprocess.run([exe, path, str(repeats)] + mode, capture_output=True, text=True, timeout=timeout, env=env)
@@ -436,6 +494,9 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     stage = {"front_end": 0.0, "imu": 0.0, "factor_create": 0.0, "optimise": 0.0, "update_map": 0.0}
     v_body = np.asarray(cfg.v, float)
     Wb = np.diag([1.0 / cfg.between_sigma_rot**2] * 3 + [1.0 / cfg.between_sigma_trans**2] * 3)
+    odo = OdometryManager(cfg.odometry_sigma_rot_deg, cfg.odometry_sigma_trans_m) if cfg.odometry_every > 0 else None
+    odo_msgs = {m[0]: m for m in odometry_messages(cfg, scans)}
+    edges = []        # live odometry edges: dicts(ka, kb, Z, info), ka < kb scan indices
     win = []          # live window: dicts(k, R, t, factor, Z (relative pose to the previous scan), fresh)
     est, kf_poses, n_kf, costs, n_photo_valid, n_photo_window = [], [], 0, [], [], []
     R_prev = t_prev = vel_prev = None
@@ -477,6 +538,12 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
             backend.release(old["f"])
             if old["pf"] is not None:
                 backend.release(old["pf"])
+        if odo is not None:
+            if k in odo_msgs:
+                got = odo.callback(k, *odo_msgs[k][1:])
+                if got is not None:
+                    edges.append(dict(ka=got[0], kb=k, Z=got[1], info=got[2]))
+            edges = [e for e in edges if e["ka"] >= win[0]["k"]]  # dropped once the older pose has left the window
         if cfg.photo_window:
             n_photo_window.append(sum(w["pf"] is not None for w in win))
         a4 = time.perf_counter()
@@ -502,6 +569,8 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
                     plin = [backend.linearize_photo(p, R_, t_) for p, (R_, t_) in zip(pfs, poses)]
                 kw["linear"] = [dict(pose=i, at=T, H=Hp, b=bp, f=fp) for i, T, (Hp, bp, fp, nv) in zip(at, poses, plin)
                                 if nv and np.all(np.isfinite(Hp)) and np.all(np.isfinite(bp)) and np.isfinite(fp)]
+            if odo is not None:
+                kw["edges"] = [dict(a=e["ka"] - win[0]["k"], b=e["kb"] - win[0]["k"], Z=e["Z"], info=e["info"]) for e in edges]
             new_poses, fs = backend.optimise_window([w["f"] for w in win], [(w["R"], w["t"]) for w in win], [None] + [w["Z"] for w in win[1:]],
                                                     cfg.update_iters, list(np.diag(Wb)), [1.0 / sr**2] * 3 + [1.0 / st**2] * 3, 1e-9, **kw)
             for w, (R_n, t_n) in zip(win, new_poses):
@@ -548,6 +617,17 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
                     A += J.T @ Wb @ J
                     g += J.T @ Wb @ r
                     cost += float(r @ Wb @ r)
+                for e in edges:  # the odometry edges, behind the IMU ties
+                    ia, ib = e["ka"] - win[0]["k"], e["kb"] - win[0]["k"]
+                    Rz, tz = e["Z"]
+                    Rab, tab = _between(win[ia]["R"], win[ia]["t"], win[ib]["R"], win[ib]["t"])
+                    r = np.concatenate([_so3_log(Rz.T @ Rab), Rz.T @ (tab - tz)])
+                    J = np.zeros((6, 6 * nW))
+                    J[:, 6 * ia:6 * ia + 6] = -_adjoint(Rab.T, -Rab.T @ tab)
+                    J[:, 6 * ib:6 * ib + 6] = np.eye(6)
+                    A += J.T @ e["info"] @ J
+                    g += J.T @ e["info"] @ r
+                    cost += float(r @ e["info"] @ r)
                 # what marginalisation leaves on the oldest pose; loose while that pose has never been optimised
                 loose = win[0]["k"] == 0 and k < cfg.window
                 sr, st = (np.deg2rad(1.0), 0.1) if loose else (1e-4, 1e-4)
