@@ -482,6 +482,43 @@ int mh_icp_window_optimise_edges_async(mh_icp * const * icps, size_t W, const do
                                        size_t n_edges, mh_icp_window_result * out, double * trace_poses,
                                        uint32_t * evaluated_mask);
 
+/* What a fixed-lag smoother leaves behind when the oldest pose drops out of the window: the marginal of pose 0, as ONE dense
+ * Gaussian on pose 1, in the shape mh_icp_window_optimise_lin takes.  Nothing is iterated: the poses are the caller's.  The
+ * call evaluates every term that touches pose 0 at R / t, in the chains' own per-entry order — the ICP factor icps[0] (one
+ * K3 launch, component pass off, the launch class mh_icp_linearize chooses for that factor alone; H_ss, b_s, f after the
+ * 4-DoF projection and the degeneracy quirk; nothing if the factor is empty), the linear factors with pose == 0 in list order,
+ * each carried from its L to T_0 as the lin chain carries it, the has_Z[1] tie with diag(cfg->between_info), the edges with
+ * (pose_a, pose_b) == (0, 1) in list order, diag(cfg->prior_info) and cfg->damping on the block of pose 0 — accumulates
+ *   A00 = H_u + sum J_a^T Om J_a + prior + damping,  g0 = b_u + sum J_a^T Om r,  A10 = sum Om J_a,  A11' = sum Om,
+ *   g1' = sum Om r,  c = f_u + sum r^T Om r
+ * and eliminates pose 0 in a one-workgroup kernel: A00 is factorised as the chains factorise a pivot block, then
+ *   H_m = A11' - A10 A00^-1 A10^T (exactly symmetric),  b_m = g1' - A10 A00^-1 g0,  f_m = c - g0^T A00^-1 g0,
+ * the model f + 2 b^T x + x^T H x in the tangent of L = pose 1 as given.  Linear factors on other poses, has_Z ties and edges
+ * that do not touch pose 0 and the other ICP factors contribute nothing: they stay in the window.  Of cfg the call reads
+ * between_info, prior_info and damping (iters, check_every and the eps are ignored, but checked).  A00 without a positive
+ * pivot: MH_OK, valid = 0, prior.H / b / f zero.
+ * The caller passes the arrays it holds for mh_icp_window_optimise_edges; every argument is checked as there, the edges first.
+ * Further: an edge with pose_a == 0 and pose_b > 1 (the marginal would be a joint factor on several poses): MH_ERR_UNSUPPORTED,
+ * reported with the edges' errors; W < 2: MH_ERR_INVALID_ARG.  Nothing is enqueued then, the handles unchanged.
+ * Only icps[0] runs K3: its association state and linearize count advance as under one mh_icp_linearize; the other factors'
+ * state and counts are untouched (they are held, like the factors of any window call, until the call has been waited for).
+ * The call counts as the context's one window call in flight; mh_icp_window_wait collects the _async form (*out must stay
+ * valid until then). */
+typedef struct mh_window_marginal {
+  mh_window_linear_factor prior;   /* pose = 1 (index in THIS window), L = pose 1 as given, H_m, b_m, f_m */
+  int32_t valid;                   /* 0: A00 had no positive pivot; prior.H / b / f are zero */
+  int32_t n_ties;                  /* has_Z[1] plus the edges on (0, 1) */
+  mh_icp_result oldest;            /* what mh_icp_linearize (components off) returns for icps[0] at pose 0 */
+} mh_window_marginal;
+int mh_icp_window_marginalise(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                              const double * Z_R, const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg,
+                              const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges,
+                              mh_window_marginal * out);
+int mh_icp_window_marginalise_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                    const double * Z_R, const double * Z_t, const double g_unit[3],
+                                    const mh_icp_window_config * cfg, const mh_window_linear_factor * lin, size_t n_lin,
+                                    const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out);
+
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals
  * unique_ns[g] gets p <- R_g p + t_g in float (no FMA, Eigen's evaluation order).  Rt12 = n_groups x

@@ -29,6 +29,7 @@ EXPORTS = [
     "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
     "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
     "mh_icp_window_optimise_edges", "mh_icp_window_optimise_edges_async",
+    "mh_icp_window_marginalise", "mh_icp_window_marginalise_async",
     "mh_deskew", "mh_transform_f32",
     "mh_scan_create", "mh_scan_destroy", "mh_scan_prepare_input", "mh_scan_prepare_input_device", "mh_scan_prefetch", "mh_scan_prepare_input_prefetched", "mh_scan_prepare_input_layout", "mh_scan_get_unique_ns", "mh_scan_deskew",
     "mh_scan_deskew_imu", "mh_scan_get_deskew_poses", "mh_photo_preprocess_scan_resident", "mh_photo_preprocess_scan_begin_resident",
@@ -220,6 +221,18 @@ def make_window_edge(edges):
         q.Z_t[:] = [float(v) for v in np.asarray(e["Z"][1], np.float64).reshape(3)]
         q.info[:] = [float(v) for v in np.asarray(e["info"], np.float64).reshape(36)]
     return arr
+
+
+class WindowMarginal(C.Structure):
+    """mh_window_marginal"""
+    _fields_ = [("prior", WindowLinearFactor), ("valid", C.c_int32), ("n_ties", C.c_int32), ("oldest", IcpResult)]
+
+    def as_dict(self):
+        """"linear": the marginal as optimise_window(linear=[...]) takes it, on pose 0 of the window without its oldest pose"""
+        q = self.prior
+        lin = {"pose": int(q.pose) - 1, "at": (np.array(q.L_R).reshape(3, 3), np.array(q.L_t)), "H": np.array(q.H).reshape(6, 6), "b": np.array(q.b),
+               "f": float(q.f)}
+        return {"valid": int(self.valid), "n_ties": int(self.n_ties), "oldest": self.oldest.as_dict(), "linear": lin}
 
 
 def make_window_config(iters=6, between_sigma_rot=2e-3, between_sigma_trans=1e-2, prior_sigma_rot=1e-4, prior_sigma_trans=1e-4, damping=1e-9,
@@ -570,6 +583,9 @@ def load(build_if_missing: bool = True):
     L.mh_icp_window_optimise_edges.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowRelin), C.POINTER(WindowLinearFactor), sz,
                                                C.POINTER(WindowEdge), sz, C.POINTER(WindowResult), vp, vp]
     L.mh_icp_window_optimise_edges_async.argtypes = L.mh_icp_window_optimise_edges.argtypes
+    L.mh_icp_window_marginalise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowLinearFactor), sz, C.POINTER(WindowEdge), sz,
+                                            C.POINTER(WindowMarginal)]
+    L.mh_icp_window_marginalise_async.argtypes = L.mh_icp_window_marginalise.argtypes
     L.mh_icp_size.restype = sz
     L.mh_deskew.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
     L.mh_transform_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -1036,6 +1052,33 @@ def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_uni
     if trace is not None:
         d["poses"] = trace[:d["iters"]]
     return d
+
+
+def marginalise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), linear=None, edges=None, wait=True):
+    """mh_icp_window_marginalise: what eliminating the oldest pose of the window leaves on pose 1, at `poses` (nothing is
+    iterated).  The arguments are optimise_window's (of cfg: between_info, prior_info, damping).  Returns {"valid", "n_ties",
+    "oldest": the oldest factor linearized at pose 0, "linear": the marginal as optimise_window(linear=[...]) takes it, its
+    pose rebased to 0 for the window without its oldest pose}.  wait=False: mh_icp_window_marginalise_async; returns a
+    WindowCall whose wait() gives the same dict."""
+    W = len(factors)
+    ctx = factors[0].ctx
+    R = np.ascontiguousarray(np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses]))
+    t = np.ascontiguousarray(np.array([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
+    hz = np.zeros(W, np.int32) if has_Z is None else np.ascontiguousarray(np.asarray(has_Z).astype(np.int32))
+    ZR = Zt = None
+    if Z is not None:
+        ZR = np.ascontiguousarray(np.array([np.asarray(z[0], np.float64).reshape(9) for z in Z]))
+        Zt = np.ascontiguousarray(np.array([np.asarray(z[1], np.float64).reshape(3) for z in Z]))
+    g = _f64(g_unit)
+    handles = (C.c_void_p * W)(*[f.h for f in factors])
+    out = WindowMarginal()
+    lin, ed = make_window_linear(linear or []), make_window_edge(edges or [])
+    args = (handles, W, _p(R), _p(t), _p(hz), _p(ZR), _p(Zt), _p(g), C.byref(cfg), lin, len(linear or []), ed, len(edges or []), C.byref(out))
+    if not wait:
+        ctx.check(ctx.L.mh_icp_window_marginalise_async(*args))
+        return WindowCall(ctx, (handles, R, t, hz, ZR, Zt, g, cfg, lin, ed), out, None)
+    ctx.check(ctx.L.mh_icp_window_marginalise(*args))
+    return out.as_dict()
 
 
 class ICPFactor:

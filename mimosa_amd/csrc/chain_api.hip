@@ -1,7 +1,7 @@
 // The device-chain drivers of the C ABI (include/mimosa_hip.h): mh_icp_align[_async], mh_icp_window_optimise[_async],
-// mh_icp_window_optimise_relin[_async], mh_icp_window_optimise_lin[_async], mh_icp_window_optimise_edges[_async] and
-// mh_icp_window_wait.  A chain is K3 (icp_kernels.hip), a step kernel (align_kernels.hip, window_kernels.hip,
-// window_relin_kernels.hip, window_lin_kernels.hip, window_edge_kernels.hip),
+// mh_icp_window_optimise_relin[_async], mh_icp_window_optimise_lin[_async], mh_icp_window_optimise_edges[_async],
+// mh_icp_window_marginalise[_async] and mh_icp_window_wait.  A chain is K3 (icp_kernels.hip), a step kernel (align_kernels.hip, window_kernels.hip,
+// window_relin_kernels.hip, window_lin_kernels.hip, window_edge_kernels.hip; window_marginal_kernels.hip for the marginal),
 // K3, step ... on the context's stream with one wait at its
 // end; every step publishes a row of flagged words the host reads.  What the two families share is written once at the top;
 // argument checks, staging layout, the step launch and the decoding of a row are each family's own.  The factor handle,
@@ -367,8 +367,10 @@ static void window_abandon(mh_ctx * ctx)
 static int window_begin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                         const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses,
                         const mh_icp_window_relin * relin, uint32_t * evaluated_mask, bool lin_call, const mh_window_linear_factor * lin, size_t n_lin,
-                        const mh_window_edge * edges, size_t n_edges)
+                        const mh_window_edge * edges, size_t n_edges, bool mcall = false, mh_window_marginal * marg = nullptr)
 {
+  // mcall: mh_icp_window_marginalise — the same checks, staging and books for ONE queued "iteration" in which only icps[0] runs K3
+  // (a launch of its own class, as mh_icp_align runs it) and the marginal kernel stands in for the step
   mh_ctx * ctx = window_ctx(icps, W);
   // the edges first: what is wrong with them is told apart without a factor
   if (n_edges > static_cast<size_t>(MH_WINDOW_EDGE_MAX)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: at most 32 edges per call");
@@ -386,8 +388,12 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
       for (int c = 0; c < r; ++c)
         if (q.info[6 * r + c] != q.info[6 * c + r]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: an edge's info is not symmetric");
   }
-  if (!icps || !R || !t || !has_Z || !g_unit || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
+  for (size_t e = 0; mcall && e < n_edges; ++e)
+    if (edges[e].pose_a == 0 && edges[e].pose_b > 1)
+      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_marginalise: an edge from pose 0 beyond pose 1 makes the marginal a joint factor on several poses");
+  if (!icps || !R || !t || !has_Z || !g_unit || !cfg || (mcall ? !marg : !out)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
   if (W < 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the window has no pose");
+  if (mcall && W < 2) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_marginalise: the window needs a pose behind the oldest");
   if (W > static_cast<size_t>(mh::kWindowMax)) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: at most 16 poses per call");
   for (size_t f = 0; f < W; ++f)
     if (!icps[f]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL factor");
@@ -437,8 +443,15 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   }
 
   WindowCall & c = ctx->window;
+  const int iters = mcall ? 1 : cfg->iters;
   c.W = static_cast<int>(W);
-  c.iters = cfg->iters;
+  c.iters = iters;
+  c.marginal = mcall;
+  c.mout = marg;
+  if (mcall) {
+    std::memcpy(c.L1R, R + 9, sizeof(c.L1R));
+    std::memcpy(c.L1t, t + 3, sizeof(c.L1t));
+  }
   c.queued = 0;
   c.out = out;
   c.trace_poses = trace_poses;
@@ -450,7 +463,12 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   c.edges = n_edges > 0;
   for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
   // launch groups in slot order, as mh_icp_linearize_batch lays the same window out
-  const std::vector<LaunchGroup> groups = mhi::window_launch_groups(icps, W);
+  std::vector<LaunchGroup> groups;
+  if (!mcall)
+    groups = mhi::window_launch_groups(icps, W);
+  else if (icps[0]->n)  // the oldest factor alone, in the class of a call of its own
+    groups.push_back(LaunchGroup{mh::linearize_class(static_cast<int>(icps[0]->n), static_cast<int>(icps[0]->cfg.num_corres_points), false),
+                                 icps[0]->cfg.num_corres_points == 5 ? 5 : 8, icps[0]->map->n_off, false, {0}});
   c.launches.clear();
   c.n_slots = 0;
   for (size_t f = 0; f < W; ++f) c.slot[f] = -1;
@@ -465,7 +483,7 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   auto * blocks = reinterpret_cast<mh::IcpArgs *>(h + kWinBlocksAt);
   mh::WindowState st;
   std::memset(&st, 0, sizeof(st));
-  for (int it = 0; it < cfg->iters; ++it) c.seq[it] = mhi::next_call_seq();
+  for (int it = 0; it < iters; ++it) c.seq[it] = mhi::next_call_seq();
   // per factor the argument block of a components-off linearize at its pose.  c.R0 keeps the caller's R for the epilogue of
   // `first`; the chain starts from a.R, which for a unary factor is the same matrix.
   for (size_t f = 0; f < W; ++f) {
@@ -479,14 +497,14 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
       std::memcpy(st.ZR[f], Z_R + 9 * f, sizeof(st.ZR[f]));
       std::memcpy(st.Zt[f], Z_t + 3 * f, sizeof(st.Zt[f]));
     }
-    if (icp->n == 0) continue;
+    if (icp->n == 0 || (mcall && f > 0)) continue;
     mh::IcpArgs a;
     const int rc = mhi::chain_k3_block(icp, R + 9 * f, t + 3 * f, g_unit, a);
     if (rc != MH_OK) return rc;
     a.ll = reinterpret_cast<uint4 *>(d + kWinLlAt) + 32 * f;
     std::memcpy(st.R[f], a.R, sizeof(st.R[f]));
     std::memcpy(st.t[f], a.t, sizeof(st.t[f]));
-    chain_fill_blocks(a, icp->cold, cfg->iters, c.seq, blocks + c.slot[f], static_cast<size_t>(c.n_slots), 0);
+    chain_fill_blocks(a, icp->cold, iters, c.seq, blocks + c.slot[f], static_cast<size_t>(c.n_slots), 0);
   }
   int * prefix = reinterpret_cast<int *>(h);
   for (size_t gi = 0; gi < c.launches.size(); ++gi) {
@@ -523,7 +541,7 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   p.eps_rot = cfg->eps_rot;
   p.eps_trans = cfg->eps_trans;
 
-  MH_HIP(ctx, hipMemcpyAsync(d, h, kWinBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(cfg->iters), hipMemcpyHostToDevice, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(d, h, kWinBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(iters), hipMemcpyHostToDevice, ctx->stream));
   if (lin_call) {
     // the linear factors, once per call: the header and the factors in use
     auto * wl = reinterpret_cast<mh::WindowLinear *>(h + kWinStageBytes);
@@ -539,8 +557,8 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
     }
     MH_HIP(ctx, hipMemcpyAsync(d + kWinLinAt, wl, sizeof(mh::WindowLinear), hipMemcpyHostToDevice, ctx->stream));
   }
-  if (n_edges) {
-    // the edges, once per call; the slots behind the last keep a valid pair, which nothing reads
+  if (n_edges || mcall) {
+    // the edges, once per call (the marginal kernel reads the header of an empty list); the slots behind the last keep a valid pair, which nothing reads
     auto * we = reinterpret_cast<mh::WindowEdges *>(h + kWinStageEdgeAt);
     std::memset(static_cast<void *>(we), 0, sizeof(*we));
     we->n = static_cast<int>(n_edges);
@@ -708,12 +726,92 @@ static int window_run(mh_ctx * ctx, int chunk)
                      [ctx] { window_abandon(ctx); }, [ctx] { return window_finish(ctx); });
 }
 
+// ---- the marginal prior of the oldest pose: K3 of icps[0], the marginal kernel, one wait ------------------------------------------
+// window_begin staged the call as a window call of one queued iteration whose only argument block is the oldest factor's.
+static int marginal_enqueue(mh_ctx * ctx)
+{
+  WindowCall & c = ctx->window;
+  char * d = static_cast<char *>(ctx->d_window);
+  hipError_t e = hipSuccess;
+  for (size_t gi = 0; gi < c.launches.size() && e == hipSuccess; ++gi) {
+    const WindowLaunch & wl = c.launches[gi];
+    e = mh::launch_linearize_batch(reinterpret_cast<mh::IcpArgs *>(d + kWinBlocksAt) + wl.first, reinterpret_cast<const int *>(d) + wl.first + static_cast<int>(gi), wl.n,
+                                   wl.grid, wl.tpb, wl.k, wl.n_off, false, ctx->stream);
+  }
+  if (e == hipSuccess) {
+    mh::WindowMarginalArgs a;
+    std::memset(static_cast<void *>(&a), 0, sizeof(a));
+    a.ll_dev = reinterpret_cast<const uint4 *>(d + kWinLlAt);
+    a.ll_host = c.icps[0]->n ? c.icps[0]->d_h_ll : nullptr;
+    a.row_host = ctx->d_window_rows;
+    a.state = reinterpret_cast<const mh::WindowState *>(d + kWinStateAt);
+    a.lin = reinterpret_cast<const mh::WindowLinear *>(d + kWinLinAt);
+    a.edges = reinterpret_cast<const mh::WindowEdges *>(d + kWinEdgeAt);
+    a.p = c.p;
+    a.seq = c.seq[0];
+    e = mh::launch_window_marginal(a, ctx->stream);
+  }
+  if (e != hipSuccess) {
+    window_abandon(ctx);
+    return hip_fail(ctx, e, "mh_icp_window_marginalise: launch");
+  }
+  c.queued = 1;
+  return MH_OK;
+}
+
+// wait for the kernel's row, then the result and the oldest factor's books
+static int marginal_finish(mh_ctx * ctx)
+{
+  static_assert(mh::kWMargWords <= static_cast<int>(kWinRowWords) && mh::kWMargH + 36 == mh::kWMargWords, "mh_icp_window_marginalise layout");
+  WindowCall & c = ctx->window;
+  mh_window_marginal * out = c.mout;
+  double row[mh::kWMargWords];
+  const ChainRows rows{ctx->h_window_rows, kWinRowWords, mh::kWMargWords, c.seq};
+  const int rc = chain_wait_row(ctx, rows, 0, row, "mh_icp_window_marginalise");
+  if (rc != MH_OK) {
+    window_abandon(ctx);
+    return rc;
+  }
+  std::memset(static_cast<void *>(out), 0, sizeof(*out));
+  int rc_all = MH_OK;
+  if (static_cast<int>(row[mh::kWMargBits]) & 8) rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_window_marginalise: the kernel did not find its K3's sums");
+  mh_icp * icp = c.icps[0];
+  if (rc_all == MH_OK) {
+    out->prior.pose = 1;
+    std::memcpy(out->prior.L_R, c.L1R, sizeof(c.L1R));
+    std::memcpy(out->prior.L_t, c.L1t, sizeof(c.L1t));
+    std::memcpy(out->prior.H, row + mh::kWMargH, sizeof(out->prior.H));
+    std::memcpy(out->prior.b, row + mh::kWMargB, sizeof(out->prior.b));
+    out->prior.f = row[mh::kWMargF];
+    out->valid = static_cast<int32_t>(row[mh::kWMargValid]);
+    out->n_ties = static_cast<int32_t>(row[mh::kWMargTies]);
+    if (!chain_epilogue(icp, 0, c.R0[0], c.gz, c.count0[0] + 1, icp->n ? c.seq[0] : 0, &out->oldest))
+      rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_window_marginalise: the oldest factor's sums did not arrive");
+  }
+  icp->linearize_count = c.count0[0] + 1;
+  icp->cold = false;
+  window_release(ctx);
+  return rc_all;
+}
+
 static int mh_icp_window_wait_impl(mh_ctx * ctx)
 {
   if (!ctx) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_window_wait: ctx is NULL");
   if (!ctx->window.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_wait: no window call in flight");
   MH_HIP(ctx, mh_enter(ctx));
+  if (ctx->window.marginal) return marginal_finish(ctx);
   return window_run(ctx, 0);
+}
+
+static int mh_icp_window_marginalise_impl(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                          const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
+                                          size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out, bool blocking)
+{
+  int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, nullptr, nullptr, nullptr, nullptr, true, lin, n_lin, edges, n_edges, true, out);
+  if (rc != MH_OK) return rc;
+  rc = marginal_enqueue(icps[0]->ctx);
+  if (rc != MH_OK || !blocking) return rc;
+  return marginal_finish(icps[0]->ctx);
 }
 
 // relin_call: through mh_icp_window_optimise_relin[_async], whose thresholds are not optional
@@ -807,6 +905,22 @@ int mh_icp_window_optimise_edges_async(mh_icp * const * icps, size_t W, const do
   return guarded(window_ctx(icps, W), "mh_icp_window_optimise_edges_async", [&]() -> int {
     return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, relin, evaluated_mask, true, lin, n_lin, edges,
                                        n_edges);
+  });
+}
+int mh_icp_window_marginalise(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                              const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin, size_t n_lin,
+                              const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise", [&]() -> int {
+    return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, out, true);
+  });
+}
+int mh_icp_window_marginalise_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                    const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
+                                    size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_async", [&]() -> int {
+    return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, out, false);
   });
 }
 int mh_icp_window_wait(mh_ctx * ctx)

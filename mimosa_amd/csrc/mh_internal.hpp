@@ -58,6 +58,9 @@ struct WindowCall
   uint32_t * evaluated_mask = nullptr;
   bool lin = false;    // mh_icp_window_optimise_lin: the step kernel also carries the call's linear factors
   bool edges = false;  // mh_icp_window_optimise_edges with n_edges > 0: ... and the call's edges, solved over the row profile
+  bool marginal = false;  // mh_icp_window_marginalise: one K3 launch of icps[0] and the marginal kernel; the result goes to mout
+  mh_window_marginal * mout = nullptr;
+  double L1R[9], L1t[3];  // ... pose 1 as the caller gave it
 };
 
 struct mh_ctx

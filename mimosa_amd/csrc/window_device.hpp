@@ -849,6 +849,186 @@ MH_HD int window_advance_edges(WindowState & st, WindowRelin * rl, const double 
   return window_advance_impl<false, true, true>(st, sums, arrived, p, w, row, nullptr, nullptr, &lin, &lw, &ed, &ew, par);
 }
 
+// ---- the marginal prior of the oldest pose (mh_icp_window_marginalise) ------------------------------------------------------------
+// What eliminating pose 0 leaves on pose 1: every term that touches pose 0, at the poses given (nothing is iterated), in the
+// assembly's own per-entry order — the ICP factor at T_0, the linear factors on pose 0 in list order carried to T_0, the has_Z[1]
+// tie, the edges on (0, 1) in list order, the prior, the damping — accumulated into
+//   A00 = H_u + sum Baa + prior + damping,  g0 = b_u + sum ga,  A10 = sum E,  A11' = sum Omega,  g1' = sum gb,  c = f_u + sum cz
+// and eliminated: A00 = L D L^T as window_factor factorises a pivot block, with its pivot test, then
+//   H_m = A11' - A10 A00^-1 A10^T,  b_m = g1' - A10 A00^-1 g0,  f_m = c - g0^T A00^-1 g0,
+// the model f + 2 b^T x + x^T H x in the tangent of L = T_1.  Factors on pose 1 alone, ties and edges that do not touch pose 0
+// contribute nothing: they stay in the window.  An edge (0, b), b > 1, is the caller's to refuse.
+constexpr int kWindowTieMax = kWindowEdgeMax + 1;  // the has_Z[1] tie (slot 0), then edge e in slot 1 + e
+struct WindowMarginalWork
+{
+  double H[36], b[6], f;  // the ICP factor of pose 0: H_ss, b_s, f
+  double Baa[kWindowTieMax][36], E[kWindowTieMax][36], ga[kWindowTieMax][6], gb[kWindowTieMax][6], cz[kWindowTieMax];
+  double A00[36], A10[36], A11[36], g0[6], g1[6], c;
+  double L[36], Dv[6];  // A00 = L D L^T (unit lower triangle, strictly lower part stored)
+  double X[7][6];       // A00^-1 times column c of A10^T (c < 6), times g0 (c == 6)
+  int degen[2];
+  int ok, pad;
+};
+struct WindowMarginalOut
+{
+  double H[36], b[6], f;
+  int valid, n_ties;
+  int degen[2];  // the degeneracy bits of pose 0's factor
+};
+
+// sums: the 32 words of factor 0 at T_0 (ignored without bit 0 of p.have).  Of p: has_Z bit 1, have / reg_4_dof /
+// project_on_degeneracy bit 0, thresh_*[0], gz, Wb, prior, damping.  Of st: R, t of poses 0 and 1, ZR[1], Zt[1].
+template <typename Par>
+MH_HD void window_marginal_impl(const double * sums, const WindowState & st, const WindowParams & p, const WindowLinear & lin, WindowLinWork & lw,
+                                const WindowEdges & ed, WindowMarginalWork & w, WindowMarginalOut & out, Par & par)
+{
+  const int n_lin = lin.n, n_edge = ed.n;
+  const bool have = (p.have & 1u) != 0, tie = ((p.has_Z >> 1) & 1u) != 0;
+  auto on01 = [&](int e) { return ed.a[e] == 0 && ed.b[e] == 1; };
+  par.each(2, [&](int blk) { w.degen[blk] = have && align_block_degenerate(sums, blk, blk ? p.thresh_trans[0] : p.thresh_rot[0]) ? 1 : 0; });
+  par.each(1 + n_lin + kWindowTieMax, [&](int l) {
+    if (l == 0) {
+      if (have) {
+        AlignParams ap{};
+        for (int q = 0; q < 3; ++q) ap.gz[q] = p.gz[q];
+        ap.reg_4_dof = static_cast<int>(p.reg_4_dof & 1u);
+        ap.project_on_degeneracy = static_cast<int>(p.project_on_degeneracy & 1u);
+        align_hessian(sums, st.R[0], ap, w.degen[0] != 0, w.degen[1] != 0, w.H, w.b, w.f);
+      } else {
+        for (int q = 0; q < 36; ++q) w.H[q] = 0.0;
+        for (int q = 0; q < 6; ++q) w.b[q] = 0.0;
+        w.f = 0.0;
+      }
+    } else if (l <= n_lin) {
+      const int j = l - 1;
+      if (lin.pose[j] != 0) return;
+      double d[6];
+      window_local(lin.LR[j], lin.Lt[j], st.R[0], st.t[0], d);
+      window_transport(lin.H[j], lin.b[j], lin.f[j], d, lw.H[j], lw.b[j], lw.f[j], lw.tmp[j]);
+    } else if (l == n_lin + 1) {
+      if (tie) window_between(st.R[0], st.t[0], st.R[1], st.t[1], st.ZR[1], st.Zt[1], p.Wb, w.Baa[0], w.E[0], w.ga[0], w.gb[0], w.cz[0]);
+    } else {
+      const int e = l - n_lin - 2;
+      if (e < n_edge && on01(e))
+        window_between_dense(st.R[0], st.t[0], st.R[1], st.t[1], ed.ZR[e], ed.Zt[e], ed.Om[e], w.Baa[1 + e], w.E[1 + e], w.ga[1 + e], w.gb[1 + e], w.cz[1 + e]);
+    }
+  });
+  par.each(36 * 3 + 6 * 2 + 1, [&](int l) {
+    if (l < 36) {
+      const int r = l / 6, c = l % 6;
+      double a = w.H[l];
+      for (int j = 0; j < n_lin; ++j)
+        if (lin.pose[j] == 0) a += lw.H[j][l];
+      if (tie) a += w.Baa[0][l];
+      for (int e = 0; e < n_edge; ++e)
+        if (on01(e)) a += w.Baa[1 + e][l];
+      if (r == c) {
+        a += p.prior[r];
+        a += p.damping;
+      }
+      w.A00[l] = a;
+    } else if (l < 72) {
+      const int q = l - 36;
+      double a = tie ? w.E[0][q] : 0.0;
+      for (int e = 0; e < n_edge; ++e)
+        if (on01(e)) a += w.E[1 + e][q];
+      w.A10[q] = a;
+    } else if (l < 108) {
+      const int q = l - 72;
+      double a = (tie && q / 6 == q % 6) ? p.Wb[q / 6] : 0.0;
+      for (int e = 0; e < n_edge; ++e)
+        if (on01(e)) a += ed.Om[e][q];
+      w.A11[q] = a;
+    } else if (l < 114) {
+      const int r = l - 108;
+      double g = w.b[r];
+      for (int j = 0; j < n_lin; ++j)
+        if (lin.pose[j] == 0) g += lw.b[j][r];
+      if (tie) g += w.ga[0][r];
+      for (int e = 0; e < n_edge; ++e)
+        if (on01(e)) g += w.ga[1 + e][r];
+      w.g0[r] = g;
+    } else if (l < 120) {
+      const int r = l - 114;
+      double g = tie ? w.gb[0][r] : 0.0;
+      for (int e = 0; e < n_edge; ++e)
+        if (on01(e)) g += w.gb[1 + e][r];
+      w.g1[r] = g;
+    } else {
+      double c = w.f;
+      for (int j = 0; j < n_lin; ++j)
+        if (lin.pose[j] == 0) c += lw.f[j];
+      if (tie) c += w.cz[0];
+      int n = tie ? 1 : 0;
+      for (int e = 0; e < n_edge; ++e)
+        if (on01(e)) {
+          c += w.cz[1 + e];
+          n += 1;
+        }
+      w.c = c;
+      w.ok = 1;
+      out.n_ties = n;
+      out.degen[0] = w.degen[0];
+      out.degen[1] = w.degen[1];
+    }
+  });
+  // A00 = L D L^T: the columns of window_factor, its pivot test
+  for (int j = 0; j < 6 && w.ok; ++j) {
+    par.each(6 - j, [&](int l) {
+      double d = w.A00[7 * j];
+      for (int k = 0; k < j; ++k) d -= w.L[6 * j + k] * w.L[6 * j + k] * w.Dv[k];
+      if (l == 0) {
+        w.Dv[j] = d;
+        if (!(d > 0.0) || !(d < 1e300)) w.ok = 0;
+      } else {
+        const int row = j + l;
+        double s = w.A00[6 * row + j];
+        for (int k = 0; k < j; ++k) s -= w.L[6 * row + k] * w.L[6 * j + k] * w.Dv[k];
+        w.L[6 * row + j] = s / d;
+      }
+    });
+  }
+  if (!w.ok) {
+    par.each(36 + 6 + 1, [&](int l) {
+      if (l < 36)
+        out.H[l] = 0.0;
+      else if (l < 42)
+        out.b[l - 36] = 0.0;
+      else {
+        out.f = 0.0;
+        out.valid = 0;
+      }
+    });
+    return;
+  }
+  par.each(7, [&](int c) { window_solve6(w.L, w.Dv, c < 6 ? &w.A10[6 * c] : w.g0, w.X[c]); });  // column c of A10^T = row c of A10
+  // the upper triangle of H_m, mirrored
+  par.each(21 + 6 + 1, [&](int l) {
+    if (l < 21) {
+      int r = 0, q = l;
+      while (q >= 6 - r) {
+        q -= 6 - r;
+        ++r;
+      }
+      const int c = r + q;
+      double s = w.A11[6 * r + c];
+      for (int m = 0; m < 6; ++m) s -= w.A10[6 * r + m] * w.X[c][m];
+      out.H[6 * r + c] = s;
+      out.H[6 * c + r] = s;
+    } else if (l < 27) {
+      const int r = l - 21;
+      double s = w.g1[r];
+      for (int m = 0; m < 6; ++m) s -= w.A10[6 * r + m] * w.X[6][m];
+      out.b[r] = s;
+    } else {
+      double s = w.c;
+      for (int m = 0; m < 6; ++m) s -= w.g0[m] * w.X[6][m];
+      out.f = s;
+      out.valid = 1;
+    }
+  });
+}
+
 }  // namespace mh
 
 #if defined(__HIPCC__)
@@ -902,5 +1082,31 @@ struct WindowEdgeStepArgs
   const WindowEdges * edges;  // device memory the context owns
 };
 hipError_t launch_window_edge_step(const WindowEdgeStepArgs & a, bool relin, hipStream_t stream);
+
+// mh_icp_window_marginalise (window_marginal_kernels.hip): launched behind the one staged K3 launch (tail = 1) of the oldest
+// factor, whose flagged words landed in ll_dev (32 words; none when the factor is empty).  The kernel forwards them to ll_host,
+// runs window_marginal_impl at the poses of `state` and publishes one row of kWMargWords flagged words.
+enum WindowMarginalRow
+{
+  kWMargValid = 0,
+  kWMargTies,
+  kWMargF,
+  kWMargBits,  // 8: the factor's sums were missing (nothing was computed)
+  kWMargB = 4,
+  kWMargH = 10,
+  kWMargWords = 46,
+};
+struct WindowMarginalArgs
+{
+  const uint4 * ll_dev;
+  uint4 * ll_host;   // slot 0 of the factor's pinned ring (null: empty factor)
+  uint4 * row_host;  // the row in mapped pinned memory
+  const WindowState * state;
+  const WindowLinear * lin;
+  const WindowEdges * edges;
+  WindowParams p;
+  unsigned int seq;
+};
+hipError_t launch_window_marginal(const WindowMarginalArgs & a, hipStream_t stream);
 }  // namespace mh
 #endif

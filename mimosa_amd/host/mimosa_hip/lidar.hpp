@@ -667,7 +667,16 @@ public:
     for (int r = 0; r < 6; ++r) e.info(r, r) = 1.0 / (sigmas(r) * sigmas(r));
     return e;
   }
-  // a call in flight (optimiseWindowAsync): wait() collects it
+  // What eliminating the oldest pose of the window leaves on the pose behind it (mh_icp_window_marginalise): `prior` is a linear
+  // factor on pose 0 of the window WITHOUT its oldest pose, linearized at that pose as given — what optimiseWindowLin /
+  // optimiseWindowEdges take.  valid == false: the oldest pose's block had no positive pivot; prior.H, b, f are zero.
+  struct WindowMarginal
+  {
+    bool valid = false;
+    int n_ties = 0;  // the between entry of pose 1 plus the edges on (0, 1)
+    WindowLinear prior;
+  };
+  // a call in flight (optimiseWindowAsync, marginaliseWindowAsync): wait() / waitMarginal() collects it
   class WindowCall
   {
   public:
@@ -676,9 +685,28 @@ public:
       factors_[0]->ctx().check(mh_icp_window_wait(factors_[0]->ctx().get()), "mh_icp_window_wait");
       return finish();
     }
+    WindowMarginal waitMarginal()
+    {
+      factors_[0]->ctx().check(mh_icp_window_wait(factors_[0]->ctx().get()), "mh_icp_window_wait");
+      return finishMarginal();
+    }
 
   private:
     friend class ICPFactor;
+    WindowMarginal finishMarginal()
+    {
+      WindowMarginal out;
+      out.valid = m_->valid != 0;
+      out.n_ties = m_->n_ties;
+      out.prior.pose = static_cast<size_t>(m_->prior.pose - 1);
+      out.prior.at = pose3(m_->prior.L_R, m_->prior.L_t);
+      out.prior.H = matrix6(m_->prior.H);
+      for (int r = 0; r < 6; ++r) out.prior.b(r) = m_->prior.b[r];
+      out.prior.f = m_->prior.f;
+      factors_[0]->last_ = m_->oldest;
+      return out;
+    }
+    std::unique_ptr<mh_window_marginal> m_;  // set: the call is mh_icp_window_marginalise
     WindowResult finish()
     {
       WindowResult out;
@@ -754,6 +782,21 @@ public:
     return startWindow(factors, poses, between, g, config, false, relin, &linear, &edges);
   }
 
+  // The marginal prior of the oldest pose at `poses` (nothing is iterated): of `config` between_info, prior_info and damping are
+  // used; linear factors and edges as optimiseWindowEdges takes them.  Only factors[0] is linearized (once).
+  static WindowMarginal marginaliseWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
+                                          const Unit3 & g, const WindowConfig & config, const std::vector<WindowLinear> & linear,
+                                          const std::vector<WindowEdge> & edges)
+  {
+    return startWindow(factors, poses, between, g, config, true, nullptr, &linear, &edges, true)->finishMarginal();
+  }
+  static std::unique_ptr<WindowCall> marginaliseWindowAsync(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses,
+                                                            const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config,
+                                                            const std::vector<WindowLinear> & linear, const std::vector<WindowEdge> & edges)
+  {
+    return startWindow(factors, poses, between, g, config, false, nullptr, &linear, &edges, true);
+  }
+
   // getters, :48-72
   std::vector<RejectStatus> getStatuses() const
   {
@@ -822,7 +865,8 @@ private:
   const Context & ctx() const { return *ivox_target_->context(); }
   static std::unique_ptr<WindowCall> startWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
                                                  const Unit3 & g, const WindowConfig & config, bool blocking, const WindowRelin * relin = nullptr,
-                                                 const std::vector<WindowLinear> * linear = nullptr, const std::vector<WindowEdge> * edges = nullptr)
+                                                 const std::vector<WindowLinear> * linear = nullptr, const std::vector<WindowEdge> * edges = nullptr,
+                                                 bool marginal = false)
   {
     const size_t n = factors.size();
     if (!n || poses.size() != n || between.size() != n) throw std::runtime_error("ICPFactor::optimiseWindow: one pose and one between entry per factor");
@@ -889,6 +933,14 @@ private:
           for (int r = 0; r < 6; ++r)
             for (int c = 0; c < 6; ++c) q.info[6 * r + c] = e.info(r, c);
           w->edges_.push_back(q);
+        }
+        if (marginal) {
+          w->m_.reset(new mh_window_marginal);
+          const auto fm = blocking ? mh_icp_window_marginalise : mh_icp_window_marginalise_async;
+          factors[0]->ctx().check(fm(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_,
+                                     w->lin_.data(), w->lin_.size(), w->edges_.data(), w->edges_.size(), w->m_.get()),
+                                  blocking ? "mh_icp_window_marginalise" : "mh_icp_window_marginalise_async");
+          return w;
         }
         const auto fe = blocking ? mh_icp_window_optimise_edges : mh_icp_window_optimise_edges_async;
         factors[0]->ctx().check(fe(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_,

@@ -265,6 +265,11 @@ struct Config
   // k - odometry_every and k, beside the IMU ties, dropped once its older pose has left the window.  With device_window the edges
   // go to ICPFactor::optimiseWindowEdges.  Unlike the reference's source, this one reports at scan times.  FixedLagReplay only
   int odometry_every = 0;
+  // with device_window: when a scan's arrival pushes the oldest pose out of the window, that pose is marginalised on the device
+  // (ICPFactor::marginaliseWindow, at the current poses, before it is dropped) and the dense Gaussian this leaves on the next pose
+  // is carried as a linear factor on the window's pose 0 instead of the 1e-4 rad / 1e-4 m pin; a marginal that is not valid falls
+  // back to the pin for that window.  Refused without device_window and with odometry_every > 1
+  bool window_marginal = false;
   double odometry_sigma_rot_deg = 1.0, odometry_sigma_trans_m = 0.5;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
@@ -288,6 +293,7 @@ struct Result
 {
   std::vector<RT> poses;
   std::vector<int> photo_valid;
+  std::vector<int> marginal_valid;   // window_marginal: the valid flag of every marginal computed
   std::vector<int> photo_in_window;  // photo_window: photometric factors in the window at each scan's optimisation
   std::vector<std::vector<double>> costs;
   int n_keyframes = 0;
@@ -405,7 +411,10 @@ public:
       pushed_ = true;
     }
     win.push_back(lv);
-    if (static_cast<int>(win.size()) > window_) win.pop_front();
+    if (static_cast<int>(win.size()) > window_) {
+      if (window_marginal_) marginaliseOldest();
+      win.pop_front();
+    }
     expireEdges();
   }
   // A between factor on the poses of scans ka < kb with its own dense information matrix (the odometry manager's), beside the
@@ -440,6 +449,9 @@ public:
   void setDeviceWindow(bool on) { device_window_ = on; }
   // on (with the device window): photometric factors are linearized once per call and carried by the chain as linear factors
   void setWindowPhotoLinear(bool on) { window_photo_linear_ = on; }
+  // on (with the device window): the pose that leaves the window is marginalised and its marginal carried as the prior
+  void setWindowMarginal(bool on) { window_marginal_ = on; }
+  const std::vector<int> & marginalValid() const { return marginal_valid_; }
   void setWindowRelin(bool on, double rot, double trans)
   {
     window_relin_ = on;
@@ -665,6 +677,10 @@ private:
           if (finite) linear.push_back(ICPFactor::windowLinearFrom(*hp, at[j], poses[at[j]]));
         }
       }
+      if (has_carried_) {  // the marginal prior stands in for the pin
+        linear.push_back(carried_);
+        for (double & v : wc.prior_info) v = 0.0;
+      }
       const Unit3 down(0.0, 0.0, -1.0);
       std::vector<ICPFactor::WindowEdge> edges;
       for (const Edge & e : edges_) {
@@ -676,7 +692,7 @@ private:
         edges.push_back(q);
       }
       const ICPFactor::WindowResult r = edges_on_ ? ICPFactor::optimiseWindowEdges(factors, poses, between, down, wc, linear, edges, window_relin_ ? &rl : nullptr)
-                                        : window_photo_linear_ ? ICPFactor::optimiseWindowLin(factors, poses, between, down, wc, linear, window_relin_ ? &rl : nullptr)
+                                        : (window_photo_linear_ || has_carried_) ? ICPFactor::optimiseWindowLin(factors, poses, between, down, wc, linear, window_relin_ ? &rl : nullptr)
                                         : window_relin_      ? ICPFactor::optimiseWindowRelin(factors, poses, between, down, wc, rl)
                                                              : ICPFactor::optimiseWindow(factors, poses, between, down, wc);
       if (r.iters != update_iters_) throw std::runtime_error("replay::solve: singular system");
@@ -694,6 +710,64 @@ private:
       throw std::runtime_error("replay: device_window is offered for lidar::ICPFactor only");
     }
   }
+  // window_marginal: the window as it was optimised (without the scan that just arrived), at its current poses, with the carried
+  // prior and, where the window call passes it, the oldest pose's photometric factor as linear factors on pose 0
+  void marginaliseOldest()
+  {
+    if constexpr (std::is_same<FactorT, ICPFactor>::value) {
+      const size_t nW = win.size() - 1;
+      std::vector<typename FactorT::Ptr> factors(nW);
+      std::vector<Pose3> poses(nW);
+      std::vector<ICPFactor::WindowBetween> between(nW);
+      for (size_t i = 0; i < nW; ++i) {
+        factors[i] = win[i].f;
+        poses[i] = toPose3(win[i].T);
+        between[i].present = i > 0 && win[i].has_Z;
+        if (between[i].present) between[i].Z = toPose3(win[i].Z);
+      }
+      std::vector<ICPFactor::WindowLinear> linear;
+      if (has_carried_) linear.push_back(carried_);
+      if (window_photo_linear_ && photo_window_ && win[0].pf) {
+        Values v;
+        v.insert(X(win[0].k), poses[0]);
+        const std::vector<PhotometricFactor::Ptr> pfs{win[0].pf};
+        PhotometricFactor::linearizeBatchAsync(pfs, v);
+        const auto hp = std::static_pointer_cast<HessianFactor>(pfs[0]->collect());
+        bool finite = pfs[0]->lastResult().status_hist[8] > 0 && std::isfinite(hp->constantTerm());
+        const gtsam::Matrix Gp = hp->information();
+        const gtsam::Vector gp = hp->linearTerm();
+        for (int q = 0; q < 36 && finite; ++q) finite = std::isfinite(Gp(q / 6, q % 6));
+        for (int q = 0; q < 6 && finite; ++q) finite = std::isfinite(gp(q));
+        if (finite) linear.push_back(ICPFactor::windowLinearFrom(*hp, 0, poses[0]));
+      }
+      std::vector<ICPFactor::WindowEdge> edges;
+      for (const Edge & e : edges_) {
+        ICPFactor::WindowEdge q;
+        q.a = e.ka - win[0].k;
+        q.b = e.kb - win[0].k;
+        q.Z = toPose3(e.Z);
+        q.info = matrix6(e.info);
+        edges.push_back(q);
+      }
+      ICPFactor::WindowConfig wc;
+      wc.iters = 1;
+      const bool loose = win[0].k == first_k_;
+      const double sr = loose ? 0.017453292519943295 : 1e-4, st = loose ? 0.1 : 1e-4;
+      for (int p = 0; p < 3; ++p) {
+        wc.between_info[p] = Wb_[p];
+        wc.between_info[3 + p] = Wb_[3 + p];
+        wc.prior_info[p] = has_carried_ ? 0.0 : 1.0 / (sr * sr);
+        wc.prior_info[3 + p] = has_carried_ ? 0.0 : 1.0 / (st * st);
+      }
+      wc.damping = 1e-9;
+      const ICPFactor::WindowMarginal m = ICPFactor::marginaliseWindow(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc, linear, edges);
+      marginal_valid_.push_back(m.valid ? 1 : 0);
+      has_carried_ = m.valid;
+      carried_ = m.prior;
+    } else {
+      throw std::runtime_error("replay: window_marginal is offered for lidar::ICPFactor only");
+    }
+  }
   void expireEdges()
   {
     for (size_t j = 0; j < edges_.size();)
@@ -704,7 +778,10 @@ private:
   }
   std::vector<Edge> edges_;
   bool edges_on_ = false;
-  bool device_window_ = false, window_relin_ = false, window_photo_linear_ = false;
+  bool device_window_ = false, window_relin_ = false, window_photo_linear_ = false, window_marginal_ = false;
+  bool has_carried_ = false;          // window_marginal: a marginal prior sits on the window's pose 0 (false: the pin)
+  ICPFactor::WindowLinear carried_;
+  std::vector<int> marginal_valid_;
   double relin_rot_ = 0.0, relin_trans_ = 0.0;
   int window_, update_iters_;
   double Wb_[6];
@@ -778,6 +855,11 @@ public:
     if (cfg_.device_window && cfg_.photometric && !cfg_.window_photo_linear)
       throw std::runtime_error("replay: device_window is not offered with the photometric factor enabled");
     if (cfg_.window_relin && !cfg_.device_window) throw std::runtime_error("replay: window_relin is only offered with device_window");
+    if (cfg_.window_marginal && !cfg_.device_window) throw std::runtime_error("replay: window_marginal is only offered with device_window");
+    if (cfg_.window_marginal && cfg_.odometry_every > 1)
+      throw std::runtime_error("replay: window_marginal is not offered with odometry_every > 1: an odometry edge would reach from pose 0 beyond pose 1");
+    if (cfg_.window_marginal && cfg_.window < 2) throw std::runtime_error("replay: window_marginal needs a window of at least two poses");
+    smoother.setWindowMarginal(cfg_.window_marginal);
     smoother.setDeviceWindow(cfg_.device_window);
     smoother.setWindowPhotoLinear(cfg_.window_photo_linear);
     smoother.setWindowRelin(cfg_.window_relin, cfg_.window_relin_rot, cfg_.window_relin_trans);
@@ -1001,6 +1083,7 @@ public:
     }
     if (photo_worker) photo_worker->wait();
     win.clear();
+    res.marginal_valid = smoother.marginalValid();
     res.seconds = secs(t_begin, clk::now());
     return res;
   }

@@ -88,6 +88,12 @@ class ReplayConfig:
     # k - odometry_every and k, beside the IMU ties; it is dropped once its older pose has left the window.  With device_window
     # the edges go to mh_icp_window_optimise_edges.  Unlike the reference's source, this one reports at scan times.  0: off
     odometry_every: int = 0
+    # with device_window: when a scan's arrival pushes the oldest pose out of the window, that pose is marginalised on the device
+    # (mh_icp_window_marginalise, at the current poses, before it is dropped) and the dense Gaussian this leaves on the next pose
+    # is carried as a linear factor on the window's pose 0 instead of the 1e-4 rad / 1e-4 m pin; a marginal that is not valid
+    # falls back to the pin for that window.  Refused without device_window, and with odometry_every > 1 (an odometry edge would
+    # reach from pose 0 beyond pose 1: the marginal would be a joint factor on several poses)
+    window_marginal: bool = False
     odometry_sigma_rot_deg: float = 1.0
     odometry_sigma_trans_m: float = 0.5
     reg: dict = field(default_factory=synth.enwide_config)
@@ -345,6 +351,13 @@ class HipBackend:
             raise np.linalg.LinAlgError("Singular matrix")
         return [(r["R"][i], r["t"][i]) for i in range(len(factors))], [row["f"] for row in r["trace"]]
 
+    def marginalise_window(self, factors, poses, Zs, between_info, prior_info, damping, linear, edges):
+        """window_marginal: what eliminating the oldest pose leaves on the next one (capi.marginalise_window's dict)"""
+        cfg = self.capi.make_window_config(iters=1, between_info=between_info, prior_info=prior_info, damping=damping)
+        I3, z3 = np.eye(3), np.zeros(3)
+        return self.capi.marginalise_window(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs],
+                                            linear=linear, edges=edges)
+
     def linearize_photo(self, pf, R, t):
         r = pf.linearize(R, t)
         return np.asarray(r["H_bb"]).reshape(6, 6), np.asarray(r["b_b"]), float(r["f"]), int(r["status_hist"][8])
@@ -428,6 +441,17 @@ def write_native_input(path, cfg: ReplayConfig, scans, rng_seed=7, mode=synth.EN
             w(np.concatenate([np.concatenate([[float(k)], R.ravel(), t, cov.ravel()]) for k, R, t, cov in msgs]) if msgs else np.zeros(0), np.float64)
 
 
+def _check_window_marginal(cfg, error):
+    if not cfg.window_marginal:
+        return
+    if not cfg.device_window:
+        raise error("window_marginal is only offered with device_window")
+    if cfg.odometry_every > 1:
+        raise error("window_marginal is not offered with odometry_every > 1: an odometry edge would reach from pose 0 beyond pose 1")
+    if cfg.window < 2:
+        raise error("window_marginal needs a window of at least two poses")
+
+
 def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible_device=None, through_manager=False, sequential=False,
                sharded_world=0, sharded_rccl=False, timeout=900):
     """The same replay through the C++ host mirror (host/mimosa_hip/replay.hpp): no Python between the library calls.
@@ -446,6 +470,7 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
         raise RuntimeError("window_relin is only offered with device_window")
     if cfg.window_photo_linear and not cfg.device_window:
         raise RuntimeError("window_photo_linear is only offered with device_window")
+    _check_window_marginal(cfg, RuntimeError)
     exe = build.build_replay_native()
     path = os.path.join(workdir, "replay_input.bin")
     write_native_input(path, cfg, scans, rng_seed)
@@ -459,7 +484,7 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
         mode = ["sharded-rccl"]
     if cfg.device_window:
         word = "device-window" if cfg.window_relin is None else "device-window-relin=%r,%r" % (float(cfg.window_relin[0]), float(cfg.window_relin[1]))
-        mode = mode + [word + ("+photo-linear" if cfg.window_photo_linear else "")]
+        mode = mode + [word + ("+photo-linear" if cfg.window_photo_linear else "") + ("+marginal" if cfg.window_marginal else "")]
     if cfg.odometry_every > 0:
         mode = mode + ["odometry"]
     if cfg.device_poses:
@@ -484,6 +509,7 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         raise ValueError("window_relin is only offered with device_window")
     if cfg.window_photo_linear and not cfg.device_window:
         raise ValueError("window_photo_linear is only offered with device_window")
+    _check_window_marginal(cfg, ValueError)
     if cfg.device_window and cfg.photometric and not cfg.window_photo_linear:
         raise ValueError("device_window is not offered with the photometric factor enabled")
     if cfg.device_window and not hasattr(backend, "optimise_window"):
@@ -499,6 +525,9 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     edges = []        # live odometry edges: dicts(ka, kb, Z, info), ka < kb scan indices
     win = []          # live window: dicts(k, R, t, factor, Z (relative pose to the previous scan), fresh)
     est, kf_poses, n_kf, costs, n_photo_valid, n_photo_window = [], [], 0, [], [], []
+    carried, marginal_valid = None, []  # window_marginal: the marginal prior on the window's pose 0 (None: the pin), every marginal's valid flag
+    pin = [1.0 / 1e-4**2] * 6
+    loose_info = [1.0 / np.deg2rad(1.0)**2] * 3 + [1.0 / 0.1**2] * 3
     R_prev = t_prev = vel_prev = None
     t0 = time.perf_counter()
     for k, sc in enumerate(scans):
@@ -534,6 +563,22 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
             R_w, t_w = backend.align_first(f, R_pred, p_pred, cfg.init_align_iters)
         win.append(dict(k=k, R=R_w, t=t_w, f=f, Z=Z, pf=pf if cfg.photo_window else None))
         if len(win) > cfg.window:
+            if cfg.window_marginal:
+                # the window as it was optimised (without the scan that just arrived), at its current poses, with the carried
+                # prior and, where the window call passes it, the oldest pose's photometric factor as linear factors on pose 0
+                live = win[:-1]
+                mlin = [] if carried is None else [carried]
+                if cfg.window_photo_linear and cfg.photo_window and live[0]["pf"] is not None:
+                    T0 = (live[0]["R"], live[0]["t"])
+                    Hp, bp, fp, nv = backend.linearize_photo_window([live[0]["pf"]], [T0])[0]
+                    if nv and np.all(np.isfinite(Hp)) and np.all(np.isfinite(bp)) and np.isfinite(fp):
+                        mlin.append(dict(pose=0, at=T0, H=Hp, b=bp, f=fp))
+                medges = [dict(a=e["ka"] - live[0]["k"], b=e["kb"] - live[0]["k"], Z=e["Z"], info=e["info"]) for e in edges]
+                prior = [0.0] * 6 if carried is not None else (loose_info if live[0]["k"] == 0 else pin)
+                m = backend.marginalise_window([w["f"] for w in live], [(w["R"], w["t"]) for w in live], [None] + [w["Z"] for w in live[1:]],
+                                               list(np.diag(Wb)), prior, 1e-9, mlin, medges)
+                marginal_valid.append(int(m["valid"]))
+                carried = m["linear"] if m["valid"] else None
             old = win.pop(0)
             backend.release(old["f"])
             if old["pf"] is not None:
@@ -571,8 +616,12 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
                                 if nv and np.all(np.isfinite(Hp)) and np.all(np.isfinite(bp)) and np.isfinite(fp)]
             if odo is not None:
                 kw["edges"] = [dict(a=e["ka"] - win[0]["k"], b=e["kb"] - win[0]["k"], Z=e["Z"], info=e["info"]) for e in edges]
+            prior = [1.0 / sr**2] * 3 + [1.0 / st**2] * 3
+            if carried is not None:  # the marginal prior stands in for the pin
+                kw["linear"] = kw.get("linear", []) + [carried]
+                prior = [0.0] * 6
             new_poses, fs = backend.optimise_window([w["f"] for w in win], [(w["R"], w["t"]) for w in win], [None] + [w["Z"] for w in win[1:]],
-                                                    cfg.update_iters, list(np.diag(Wb)), [1.0 / sr**2] * 3 + [1.0 / st**2] * 3, 1e-9, **kw)
+                                                    cfg.update_iters, list(np.diag(Wb)), prior, 1e-9, **kw)
             for w, (R_n, t_n) in zip(win, new_poses):
                 w["R"], w["t"] = R_n, t_n
         else:
@@ -676,4 +725,4 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     rerr = [float(np.rad2deg(np.linalg.norm(_so3_log(Re.T @ s["R_gt"])))) for (Re, _), s in zip(est, scans)]
     return {"poses_est": est, "trans_err": terr, "rot_err_deg": rerr, "n_keyframes": n_kf, "seconds": total,
             "scans_per_s": len(scans) / total, "stage_s": stage, "costs": costs, "photo_valid": n_photo_valid,
-            "photo_in_window": n_photo_window}
+            "photo_in_window": n_photo_window, "marginal_valid": marginal_valid}
