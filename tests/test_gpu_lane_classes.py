@@ -2,7 +2,8 @@
 one-lane-per-point class on the same clouds: the per-point results — status, mean, normal of every point, cold and after a pose
 step that re-associates part of them — must be IDENTICAL to the bit (the k-NN answer is exact in every class and the plane fit
 sums in an order that does not depend on which lane scanned what), the k-NN counters equal, and the sums equal up to the order
-in which the classes add their rows.  The class is chosen per process (environment), so each class runs in a worker."""
+in which the classes add their rows.  The class is chosen per process (environment), so each class runs in a worker.
+This compares HIP with HIP: it shows that the classes agree with each other, and is no parity evidence for any of them."""
 import os
 import subprocess
 import sys
