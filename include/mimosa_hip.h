@@ -519,6 +519,75 @@ int mh_icp_window_marginalise_async(mh_icp * const * icps, size_t W, const doubl
                                     const mh_icp_window_config * cfg, const mh_window_linear_factor * lin, size_t n_lin,
                                     const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out);
 
+/* ONE dense Gaussian on up to four poses of the window: what eliminating the oldest pose leaves when something ties it to
+ * poses beyond pose 1 (an odometry edge (0, b), b > 1, or an earlier joint marginal).  The model is f + 2 b^T x + x^T H x,
+ * x the stacked tangents of the member poses at their linearization poses L, in the convention of mh_window_linear_factor
+ * (rotation first, R <- R Exp(x_r), t <- t + R x_t); member m owns rows / columns 6 m .. 6 m + 5 of H (row stride 24) and b.
+ *
+ * mh_icp_window_optimise_joint: mh_icp_window_optimise_edges (every argument as there) with one joint factor, or none
+ * (joint == NULL: the call IS mh_icp_window_optimise_edges, the same kernels, bit for bit).  Every iteration carries the joint
+ * factor to the current poses as a linear factor is carried, member by member: d_i = [Log(L_i.R^T T_i.R), L_i.R^T (T_i.t - L_i.t)],
+ * M_i = blockdiag(Jr^-1(d_i,r), Exp(d_i,r)); with M = blockdiag(M_i) and d stacked it contributes M^T H M, M^T (b + H d) and the
+ * cost f + 2 b^T d + d^T H d (every d zero: H, b, f as they are).  Per entry the system adds the pose's ICP factor, its linear
+ * factors in list order, the joint factor's block, the has_Z terms, the edges, the prior, the damping; trace[].f adds the joint
+ * factor's cost behind the linear factors' costs.  The blocks between two member poses lie off the diagonal, anywhere in the
+ * window: they enter the row profile of the edges call's solve.  Solve, refinement, retraction, stopping, relin decisions,
+ * masks, first / last, counts and the singular path are those of mh_icp_window_optimise_edges.  With n_poses == 1 the call
+ * computes, bit for bit, what mh_icp_window_optimise_edges computes with the same L, H, b, f appended as the last linear factor.
+ * Refused with MH_ERR_INVALID_ARG, nothing enqueued, the handles unchanged: n_poses outside 1 .. MH_WINDOW_JOINT_POSES, poses
+ * not strictly ascending or outside 0 .. W - 1, a used entry of L_R, L_t, H, b or f that is not finite, used H not symmetric.
+ * The joint factor is checked behind the edges and before icps and W.  joint is copied before the call returns;
+ * mh_icp_window_wait collects the _async form. */
+#define MH_WINDOW_JOINT_POSES 4
+typedef struct mh_window_joint_factor {
+  int32_t n_poses, reserved;                 /* 1 .. MH_WINDOW_JOINT_POSES */
+  int32_t pose[MH_WINDOW_JOINT_POSES];       /* strictly ascending, 0 .. W-1; entries >= n_poses ignored */
+  double L_R[MH_WINDOW_JOINT_POSES * 9], L_t[MH_WINDOW_JOINT_POSES * 3];   /* linearization pose of each member */
+  double H[24 * 24], b[24], f;               /* leading 6 n_poses rows/cols used, row stride 24; rest ignored on input, zero on output */
+} mh_window_joint_factor;
+int mh_icp_window_optimise_joint(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                 const double * Z_R, const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg,
+                                 const mh_icp_window_relin * relin /* NULL: evaluate every factor */,
+                                 const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges,
+                                 mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask,
+                                 const mh_window_joint_factor * joint /* NULL: none */);
+int mh_icp_window_optimise_joint_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                       const double * Z_R, const double * Z_t, const double g_unit[3],
+                                       const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                       const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges,
+                                       size_t n_edges, mh_icp_window_result * out, double * trace_poses,
+                                       uint32_t * evaluated_mask, const mh_window_joint_factor * joint);
+
+/* mh_icp_window_marginalise for a pose 0 that is tied beyond pose 1: the marginal as one joint factor on the separator
+ * S = {1} + {b of every edge (0, b)} + (the poses of `joint` other than 0), sorted; pose 1 is always a member, also without a
+ * tie.  Every term on pose 0 is evaluated as mh_icp_window_marginalise evaluates it, in the same order, and additionally every
+ * edge (0, b) at the poses 0 and b, and the joint factor (if given: it must contain pose 0), carried to the current poses, in
+ * the chains' per-entry order (behind the linear factors, in front of the has_Z tie).  With A the accumulated system over
+ * {0} + S, g its gradient and c its constant:
+ *   H_m = A_SS' - A_S0 A00^-1 A_S0^T (exactly symmetric),  b_m = g_S' - A_S0 A00^-1 g0,  f_m = c - g0^T A00^-1 g0,
+ * in the tangents of the separator poses as given.  A00 is factorised and tested as in mh_icp_window_marginalise; without a
+ * positive pivot: MH_OK, valid = 0, prior.H / b / f zero — prior.n_poses, prior.pose and prior.L_R / L_t report the separator
+ * and its poses as given also then (as mh_icp_window_marginalise reports pose and L).  With no edge beyond pose 1 and joint == NULL the leading 6 x 6 / 6 / f, valid, n_ties
+ * and oldest are mh_icp_window_marginalise's, bit for bit.  Every argument is checked as in mh_icp_window_optimise_joint; a
+ * separator of more than MH_WINDOW_JOINT_POSES poses, and a joint factor that does not contain pose 0 (it would have to stay in
+ * the window as a second joint factor, which no chain takes): MH_ERR_UNSUPPORTED; W < 2: MH_ERR_INVALID_ARG.  Only icps[0] runs
+ * K3, as in mh_icp_window_marginalise; mh_icp_window_wait collects the _async form (*out must stay valid until then). */
+typedef struct mh_window_joint_marginal {
+  mh_window_joint_factor prior;  /* poses as indices in THIS window, L = those poses as given */
+  int32_t valid, n_ties;         /* n_ties: has_Z[1] plus every edge with pose_a == 0 */
+  mh_icp_result oldest;
+} mh_window_joint_marginal;
+int mh_icp_window_marginalise_joint(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z,
+                                    const double * Z_R, const double * Z_t, const double g_unit[3],
+                                    const mh_icp_window_config * cfg, const mh_window_linear_factor * lin, size_t n_lin,
+                                    const mh_window_edge * edges, size_t n_edges, const mh_window_joint_factor * joint,
+                                    mh_window_joint_marginal * out);
+int mh_icp_window_marginalise_joint_async(mh_icp * const * icps, size_t W, const double * R, const double * t,
+                                          const int32_t * has_Z, const double * Z_R, const double * Z_t, const double g_unit[3],
+                                          const mh_icp_window_config * cfg, const mh_window_linear_factor * lin, size_t n_lin,
+                                          const mh_window_edge * edges, size_t n_edges, const mh_window_joint_factor * joint,
+                                          mh_window_joint_marginal * out);
+
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals
  * unique_ns[g] gets p <- R_g p + t_g in float (no FMA, Eigen's evaluation order).  Rt12 = n_groups x

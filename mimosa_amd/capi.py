@@ -30,6 +30,7 @@ EXPORTS = [
     "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
     "mh_icp_window_optimise_edges", "mh_icp_window_optimise_edges_async",
     "mh_icp_window_marginalise", "mh_icp_window_marginalise_async",
+    "mh_icp_window_optimise_joint", "mh_icp_window_optimise_joint_async", "mh_icp_window_marginalise_joint", "mh_icp_window_marginalise_joint_async",
     "mh_deskew", "mh_transform_f32",
     "mh_scan_create", "mh_scan_destroy", "mh_scan_prepare_input", "mh_scan_prepare_input_device", "mh_scan_prefetch", "mh_scan_prepare_input_prefetched", "mh_scan_prepare_input_layout", "mh_scan_get_unique_ns", "mh_scan_deskew",
     "mh_scan_deskew_imu", "mh_scan_get_deskew_poses", "mh_photo_preprocess_scan_resident", "mh_photo_preprocess_scan_begin_resident",
@@ -233,6 +234,53 @@ class WindowMarginal(C.Structure):
         lin = {"pose": int(q.pose) - 1, "at": (np.array(q.L_R).reshape(3, 3), np.array(q.L_t)), "H": np.array(q.H).reshape(6, 6), "b": np.array(q.b),
                "f": float(q.f)}
         return {"valid": int(self.valid), "n_ties": int(self.n_ties), "oldest": self.oldest.as_dict(), "linear": lin}
+
+
+MH_WINDOW_JOINT_POSES = 4
+
+
+class WindowJointFactor(C.Structure):
+    """mh_window_joint_factor"""
+    _fields_ = [("n_poses", C.c_int32), ("reserved", C.c_int32), ("pose", C.c_int32 * MH_WINDOW_JOINT_POSES), ("L_R", C.c_double * (9 * MH_WINDOW_JOINT_POSES)),
+                ("L_t", C.c_double * (3 * MH_WINDOW_JOINT_POSES)), ("H", C.c_double * (24 * 24)), ("b", C.c_double * 24), ("f", C.c_double)]
+
+    def as_dict(self, shift=0):
+        """{"poses": [...], "at": [(R, t)] per member, "H": 6n x 6n, "b": 6n, "f"}; shift is subtracted from every pose index"""
+        n = int(self.n_poses)
+        LR, Lt = np.array(self.L_R).reshape(MH_WINDOW_JOINT_POSES, 3, 3), np.array(self.L_t).reshape(MH_WINDOW_JOINT_POSES, 3)
+        return {"poses": [int(self.pose[m]) - shift for m in range(n)], "at": [(LR[m].copy(), Lt[m].copy()) for m in range(n)],
+                "H": np.array(self.H).reshape(24, 24)[:6 * n, :6 * n].copy(), "b": np.array(self.b)[:6 * n].copy(), "f": float(self.f)}
+
+
+def make_window_joint(joint) -> WindowJointFactor:
+    """mh_window_joint_factor from a dict {"poses": ascending indices, "at": [(R, t)] per member, "H": 6n x 6n, "b": 6n, "f": float}"""
+    q = WindowJointFactor()
+    n = len(joint["poses"])
+    q.n_poses = n
+    m = min(n, MH_WINDOW_JOINT_POSES)  # (a bad n_poses is the library's to refuse)
+    H = np.zeros((24, 24))
+    H[:6 * m, :6 * m] = np.asarray(joint["H"], np.float64).reshape(6 * n, 6 * n)[:6 * m, :6 * m]
+    b = np.zeros(24)
+    b[:6 * m] = np.asarray(joint["b"], np.float64).reshape(6 * n)[:6 * m]
+    for k in range(m):
+        q.pose[k] = int(joint["poses"][k])
+        q.L_R[9 * k:9 * k + 9] = [float(v) for v in np.asarray(joint["at"][k][0], np.float64).reshape(9)]
+        q.L_t[3 * k:3 * k + 3] = [float(v) for v in np.asarray(joint["at"][k][1], np.float64).reshape(3)]
+    q.H[:] = [float(v) for v in H.reshape(-1)]
+    q.b[:] = [float(v) for v in b]
+    q.f = float(joint["f"])
+    return q
+
+
+class WindowJointMarginal(C.Structure):
+    """mh_window_joint_marginal"""
+    _fields_ = [("prior", WindowJointFactor), ("valid", C.c_int32), ("n_ties", C.c_int32), ("oldest", IcpResult)]
+
+    def as_dict(self):
+        """"joint_here": the marginal with the pose indices of the window it was computed in; "joint": rebased to the window
+        without its oldest pose (every index minus one), as optimise_window(joint=...) takes it there"""
+        return {"valid": int(self.valid), "n_ties": int(self.n_ties), "oldest": self.oldest.as_dict(), "joint_here": self.prior.as_dict(0),
+                "joint": self.prior.as_dict(1)}
 
 
 def make_window_config(iters=6, between_sigma_rot=2e-3, between_sigma_trans=1e-2, prior_sigma_rot=1e-4, prior_sigma_trans=1e-4, damping=1e-9,
@@ -586,6 +634,10 @@ def load(build_if_missing: bool = True):
     L.mh_icp_window_marginalise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowLinearFactor), sz, C.POINTER(WindowEdge), sz,
                                             C.POINTER(WindowMarginal)]
     L.mh_icp_window_marginalise_async.argtypes = L.mh_icp_window_marginalise.argtypes
+    L.mh_icp_window_optimise_joint.argtypes = L.mh_icp_window_optimise_edges.argtypes + [C.POINTER(WindowJointFactor)]
+    L.mh_icp_window_optimise_joint_async.argtypes = L.mh_icp_window_optimise_joint.argtypes
+    L.mh_icp_window_marginalise_joint.argtypes = L.mh_icp_window_marginalise.argtypes[:-1] + [C.POINTER(WindowJointFactor), C.POINTER(WindowJointMarginal)]
+    L.mh_icp_window_marginalise_joint_async.argtypes = L.mh_icp_window_marginalise_joint.argtypes
     L.mh_icp_size.restype = sz
     L.mh_deskew.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
     L.mh_transform_f32.argtypes = [vp, vp, sz, vp, vp]
@@ -970,7 +1022,7 @@ class WindowCall:
 
 
 def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), trace_poses=False, wait=True, relin=None, linear=None,
-                    edges=None):
+                    edges=None, joint=None):
     """mh_icp_window_optimise: the fixed-lag Gauss-Newton loop over `factors` (oldest first) as one chain of launches.
     poses: (R, t) per factor; Z: (R, t) per factor, entry i the measured T_{i-1}^-1 T_i where has_Z[i] (entry 0 unused).
     trace_poses: also return "poses", (iters, W, 12) — R row-major then t after every executed step.
@@ -983,7 +1035,10 @@ def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_uni
     the same entry point with no factor.
     edges=[...]: mh_icp_window_optimise_edges (with or without relin and linear) — between factors on any pair of poses, each a
     dict {"a": i, "b": j, "Z": (R, t) the measured T_a^-1 T_b, "info": 6 x 6} (make_window_edge); an empty list takes the same
-    entry point with no edge.  None: the dispatch above, untouched."""
+    entry point with no edge.  None: the dispatch above, untouched.
+    joint={...}: mh_icp_window_optimise_joint (with or without relin, linear and edges) — one dense factor on up to four poses, a
+    dict {"poses": ascending indices, "at": [(R, t)] per member, "H": 6n x 6n, "b": 6n, "f": float} (make_window_joint), what
+    marginalise_window_joint returns as "joint".  None: the dispatch above, untouched."""
     W = len(factors)
     ctx = factors[0].ctx
     R = np.ascontiguousarray(np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses]))
@@ -997,6 +1052,22 @@ def optimise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_uni
     handles = (C.c_void_p * W)(*[f.h for f in factors])
     out = WindowResult()
     trace = np.full((int(cfg.iters), W, 12), np.nan) if trace_poses else None
+    if joint is not None:
+        rl = None if relin is None else WindowRelin(float(relin[0]), float(relin[1]))
+        masks = None if relin is None else np.zeros(max(int(cfg.iters), 1), np.uint32)
+        lin, ed, jt = make_window_linear(linear or []), make_window_edge(edges or []), make_window_joint(joint)
+        args = (handles, W, _p(R), _p(t), _p(hz), _p(ZR), _p(Zt), _p(g), C.byref(cfg), None if rl is None else C.byref(rl), lin, len(linear or []), ed,
+                len(edges or []), C.byref(out), _p(trace), _p(masks), C.byref(jt))
+        if not wait:
+            ctx.check(ctx.L.mh_icp_window_optimise_joint_async(*args))
+            return WindowCall(ctx, (handles, R, t, hz, ZR, Zt, g, cfg, rl, lin, ed, jt), out, trace, masks)
+        ctx.check(ctx.L.mh_icp_window_optimise_joint(*args))
+        d = out.as_dict()
+        if trace is not None:
+            d["poses"] = trace[:d["iters"]]
+        if masks is not None:
+            d["evaluated"] = masks[:d["iters"]].copy()
+        return d
     if edges is not None:
         rl = None if relin is None else WindowRelin(float(relin[0]), float(relin[1]))
         masks = None if relin is None else np.zeros(max(int(cfg.iters), 1), np.uint32)
@@ -1078,6 +1149,34 @@ def marginalise_window(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_
         ctx.check(ctx.L.mh_icp_window_marginalise_async(*args))
         return WindowCall(ctx, (handles, R, t, hz, ZR, Zt, g, cfg, lin, ed), out, None)
     ctx.check(ctx.L.mh_icp_window_marginalise(*args))
+    return out.as_dict()
+
+
+def marginalise_window_joint(factors, poses, cfg: WindowConfig, has_Z=None, Z=None, g_unit=(0.0, 0.0, -1.0), linear=None, edges=None, joint=None, wait=True):
+    """mh_icp_window_marginalise_joint: marginalise_window for an oldest pose that is tied beyond pose 1 — by edges (0, b) or by
+    the carried joint factor `joint` (a dict as optimise_window(joint=...) takes it; it must contain pose 0).  Returns {"valid",
+    "n_ties", "oldest", "joint_here": the marginal on its separator with this window's pose indices, "joint": the same rebased to
+    the window without its oldest pose, every index minus one}.  wait=False: the _async form; returns a WindowCall."""
+    W = len(factors)
+    ctx = factors[0].ctx
+    R = np.ascontiguousarray(np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses]))
+    t = np.ascontiguousarray(np.array([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
+    hz = np.zeros(W, np.int32) if has_Z is None else np.ascontiguousarray(np.asarray(has_Z).astype(np.int32))
+    ZR = Zt = None
+    if Z is not None:
+        ZR = np.ascontiguousarray(np.array([np.asarray(z[0], np.float64).reshape(9) for z in Z]))
+        Zt = np.ascontiguousarray(np.array([np.asarray(z[1], np.float64).reshape(3) for z in Z]))
+    g = _f64(g_unit)
+    handles = (C.c_void_p * W)(*[f.h for f in factors])
+    out = WindowJointMarginal()
+    lin, ed = make_window_linear(linear or []), make_window_edge(edges or [])
+    jt = None if joint is None else make_window_joint(joint)
+    args = (handles, W, _p(R), _p(t), _p(hz), _p(ZR), _p(Zt), _p(g), C.byref(cfg), lin, len(linear or []), ed, len(edges or []),
+            None if jt is None else C.byref(jt), C.byref(out))
+    if not wait:
+        ctx.check(ctx.L.mh_icp_window_marginalise_joint_async(*args))
+        return WindowCall(ctx, (handles, R, t, hz, ZR, Zt, g, cfg, lin, ed, jt), out, None)
+    ctx.check(ctx.L.mh_icp_window_marginalise_joint(*args))
     return out.as_dict()
 
 

@@ -1,7 +1,7 @@
 // The device-chain drivers of the C ABI (include/mimosa_hip.h): mh_icp_align[_async], mh_icp_window_optimise[_async],
 // mh_icp_window_optimise_relin[_async], mh_icp_window_optimise_lin[_async], mh_icp_window_optimise_edges[_async],
-// mh_icp_window_marginalise[_async] and mh_icp_window_wait.  A chain is K3 (icp_kernels.hip), a step kernel (align_kernels.hip, window_kernels.hip,
-// window_relin_kernels.hip, window_lin_kernels.hip, window_edge_kernels.hip; window_marginal_kernels.hip for the marginal),
+// mh_icp_window_marginalise[_async], mh_icp_window_optimise_joint[_async], mh_icp_window_marginalise_joint[_async] and mh_icp_window_wait.  A chain is K3 (icp_kernels.hip), a step kernel (align_kernels.hip, window_kernels.hip,
+// window_relin_kernels.hip, window_lin_kernels.hip, window_edge_kernels.hip, window_joint_kernels.hip; window_marginal_kernels.hip and window_joint_kernels.hip for the marginals),
 // K3, step ... on the context's stream with one wait at its
 // end; every step publishes a row of flagged words the host reads.  What the two families share is written once at the top;
 // argument checks, staging layout, the step launch and the decoding of a row are each family's own.  The factor handle,
@@ -28,7 +28,8 @@ static_assert(sizeof(mh::AlignState) <= 192 && mh::kRowWords <= mh::kLlEig, "mh_
 //  one landing slot of 32 flagged words per pose for K3's sums and counters (every iteration's words carry its own number) |
 //  WindowRelin, which the steps of an mh_icp_window_optimise_relin chain keep among themselves |
 //  WindowLinear, the linear factors of an mh_icp_window_optimise_lin call (staged behind the first part in h_window) |
-//  WindowEdges, the edges of an mh_icp_window_optimise_edges call (staged behind WindowLinear)]
+//  WindowEdges, the edges of an mh_icp_window_optimise_edges call (staged behind WindowLinear) |
+//  WindowJoint, the joint factor of an mh_icp_window_optimise_joint / mh_icp_window_marginalise_joint call (staged behind WindowEdges)]
 constexpr size_t kWinStateAt = 256;
 constexpr size_t kWinBlocksAt = 3584;
 constexpr size_t kWinStageBytes = kWinBlocksAt + sizeof(mh::IcpArgs) * mh::kWindowMax * kMaxPending;
@@ -36,8 +37,12 @@ constexpr size_t kWinLlAt = (kWinStageBytes + 256 + 255) & ~size_t(255);
 constexpr size_t kWinRelinAt = kWinLlAt + 32 * sizeof(uint4) * mh::kWindowMax;
 constexpr size_t kWinLinAt = kWinRelinAt + ((sizeof(mh::WindowRelin) + 255) & ~size_t(255));
 constexpr size_t kWinEdgeAt = kWinLinAt + ((sizeof(mh::WindowLinear) + 255) & ~size_t(255));
-constexpr size_t kWinBytes = kWinEdgeAt + ((sizeof(mh::WindowEdges) + 255) & ~size_t(255));
+constexpr size_t kWinJointAt = kWinEdgeAt + ((sizeof(mh::WindowEdges) + 255) & ~size_t(255));
+constexpr size_t kWinBytes = kWinJointAt + ((sizeof(mh::WindowJoint) + 255) & ~size_t(255));
 constexpr size_t kWinStageEdgeAt = kWinStageBytes + ((sizeof(mh::WindowLinear) + 255) & ~size_t(255));  // in h_window
+constexpr size_t kWinStageJointAt = kWinStageEdgeAt + ((sizeof(mh::WindowEdges) + 255) & ~size_t(255));
+static_assert(MH_WINDOW_JOINT_POSES == mh::kWindowJointMax && kWinJointAt % 16 == 0 && kWinStageJointAt % 16 == 0 &&
+                mh::kWJMargWords <= static_cast<int>(256 * kMaxPending), "mh_icp_window_optimise_joint layout");
 static_assert(MH_WINDOW_EDGE_MAX == mh::kWindowEdgeMax && kWinEdgeAt % 16 == 0 && kWinStageEdgeAt % 16 == 0, "mh_icp_window_optimise_edges layout");
 static_assert(MH_WINDOW_LINEAR_MAX == mh::kWindowLinMax && kWinLinAt % 16 == 0, "mh_icp_window_optimise_lin layout");
 constexpr size_t kWinRowWords = 256;  // flagged words per iteration's row in h_window_rows
@@ -367,8 +372,10 @@ static void window_abandon(mh_ctx * ctx)
 static int window_begin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                         const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses,
                         const mh_icp_window_relin * relin, uint32_t * evaluated_mask, bool lin_call, const mh_window_linear_factor * lin, size_t n_lin,
-                        const mh_window_edge * edges, size_t n_edges, bool mcall = false, mh_window_marginal * marg = nullptr)
+                        const mh_window_edge * edges, size_t n_edges, bool mcall = false, mh_window_marginal * marg = nullptr,
+                        const mh_window_joint_factor * joint = nullptr, mh_window_joint_marginal * jmarg = nullptr, bool jmcall = false)
 {
+  // jmcall: mh_icp_window_marginalise_joint — mcall (set as well) whose edges may reach beyond pose 1 and whose result goes to jmarg
   // mcall: mh_icp_window_marginalise — the same checks, staging and books for ONE queued "iteration" in which only icps[0] runs K3
   // (a launch of its own class, as mh_icp_align runs it) and the marginal kernel stands in for the step
   mh_ctx * ctx = window_ctx(icps, W);
@@ -388,10 +395,46 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
       for (int c = 0; c < r; ++c)
         if (q.info[6 * r + c] != q.info[6 * c + r]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: an edge's info is not symmetric");
   }
-  for (size_t e = 0; mcall && e < n_edges; ++e)
+  for (size_t e = 0; mcall && !jmcall && e < n_edges; ++e)
     if (edges[e].pose_a == 0 && edges[e].pose_b > 1)
       return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_marginalise: an edge from pose 0 beyond pose 1 makes the marginal a joint factor on several poses");
-  if (!icps || !R || !t || !has_Z || !g_unit || !cfg || (mcall ? !marg : !out)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
+  // the joint factor: behind the edges, before the factors and W
+  if (joint) {
+    const mh_window_joint_factor & q = *joint;
+    if (q.n_poses < 1 || q.n_poses > MH_WINDOW_JOINT_POSES) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_joint: n_poses must be in 1..4");
+    const int n = q.n_poses;
+    for (int m = 0; m < n; ++m)
+      if (q.pose[m] < 0 || static_cast<size_t>(q.pose[m]) >= W || (m > 0 && q.pose[m] <= q.pose[m - 1]))
+        return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_joint: the poses must be strictly ascending in 0 .. W - 1");
+    bool fin = std::isfinite(q.f);
+    for (int k = 0; k < 9 * n; ++k) fin = fin && std::isfinite(q.L_R[k]);
+    for (int k = 0; k < 3 * n; ++k) fin = fin && std::isfinite(q.L_t[k]);
+    for (int r = 0; r < 6 * n; ++r) {
+      fin = fin && std::isfinite(q.b[r]);
+      for (int c = 0; c < 6 * n; ++c) fin = fin && std::isfinite(q.H[24 * r + c]);
+    }
+    if (!fin) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_joint: the joint factor has an entry that is not finite");
+    for (int r = 0; r < 6 * n; ++r)
+      for (int c = 0; c < r; ++c)
+        if (q.H[24 * r + c] != q.H[24 * c + r]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_joint: the joint factor's H is not symmetric");
+  }
+  int sep[MH_WINDOW_JOINT_POSES] = {0, 0, 0, 0}, n_sep = 0;
+  if (jmcall) {
+    if (joint && joint->pose[0] != 0)
+      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_marginalise_joint: a joint factor without pose 0 would stay in the window as a second joint factor");
+    unsigned int smask = 2u;
+    for (size_t e = 0; e < n_edges; ++e)
+      if (edges[e].pose_a == 0) smask |= 1u << std::min(edges[e].pose_b, 31);  // (a window of more than 16 poses is refused below)
+    for (int m = 1; joint && m < joint->n_poses; ++m) smask |= 1u << std::min(joint->pose[m], 31);
+    for (int i = 1; i < 32; ++i)
+      if ((smask >> i) & 1u) {
+        if (n_sep < MH_WINDOW_JOINT_POSES) sep[n_sep] = i;
+        ++n_sep;
+      }
+    if (n_sep > MH_WINDOW_JOINT_POSES)
+      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_marginalise_joint: the separator of pose 0 has more than 4 poses");
+  }
+  if (!icps || !R || !t || !has_Z || !g_unit || !cfg || (jmcall ? !jmarg : mcall ? !marg : !out)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
   if (W < 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the window has no pose");
   if (mcall && W < 2) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_marginalise: the window needs a pose behind the oldest");
   if (W > static_cast<size_t>(mh::kWindowMax)) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: at most 16 poses per call");
@@ -434,7 +477,7 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
     if (has_Z[f]) zmask |= 1u << f;
   if (zmask && (!Z_R || !Z_t)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL between measurements");
   MH_HIP(ctx, mh_enter(ctx));
-  if (!ctx->h_window) MH_HIP(ctx, hipHostMalloc(&ctx->h_window, kWinStageEdgeAt + sizeof(mh::WindowEdges), hipHostMallocDefault));
+  if (!ctx->h_window) MH_HIP(ctx, hipHostMalloc(&ctx->h_window, kWinStageJointAt + sizeof(mh::WindowJoint), hipHostMallocDefault));
   if (!ctx->d_window) MH_HIP(ctx, hipMalloc(&ctx->d_window, kWinBytes));
   if (!ctx->h_window_rows) {
     MH_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_window_rows), kWinRowWords * sizeof(uint4) * kMaxPending, hipHostMallocMapped));
@@ -451,6 +494,18 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
   if (mcall) {
     std::memcpy(c.L1R, R + 9, sizeof(c.L1R));
     std::memcpy(c.L1t, t + 3, sizeof(c.L1t));
+  }
+  c.joint = joint != nullptr && !mcall;
+  c.jmarginal = jmcall;
+  c.jm_joint = jmcall && joint != nullptr;
+  c.jmout = jmarg;
+  c.n_sep = n_sep;
+  for (int k = 0; k < MH_WINDOW_JOINT_POSES; ++k) {
+    c.sep[k] = sep[k];
+    if (k < n_sep) {  // (W >= 2 and every separator pose inside the window: the edges' and the joint factor's checks)
+      std::memcpy(c.LSR[k], R + 9 * sep[k], sizeof(c.LSR[k]));
+      std::memcpy(c.LSt[k], t + 3 * sep[k], sizeof(c.LSt[k]));
+    }
   }
   c.queued = 0;
   c.out = out;
@@ -557,8 +612,8 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
     }
     MH_HIP(ctx, hipMemcpyAsync(d + kWinLinAt, wl, sizeof(mh::WindowLinear), hipMemcpyHostToDevice, ctx->stream));
   }
-  if (n_edges || mcall) {
-    // the edges, once per call (the marginal kernel reads the header of an empty list); the slots behind the last keep a valid pair, which nothing reads
+  if (n_edges || mcall || joint) {
+    // the edges, once per call (the marginal kernels and the joint step read the header of an empty list); the slots behind the last keep a valid pair, which nothing reads
     auto * we = reinterpret_cast<mh::WindowEdges *>(h + kWinStageEdgeAt);
     std::memset(static_cast<void *>(we), 0, sizeof(*we));
     we->n = static_cast<int>(n_edges);
@@ -570,6 +625,24 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
       std::memcpy(we->Om[e], edges[e].info, sizeof(we->Om[e]));
     }
     MH_HIP(ctx, hipMemcpyAsync(d + kWinEdgeAt, we, sizeof(mh::WindowEdges), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (joint) {
+    // the joint factor, once per call: the members in use, everything behind them zero
+    auto * wj = reinterpret_cast<mh::WindowJoint *>(h + kWinStageJointAt);
+    std::memset(static_cast<void *>(wj), 0, sizeof(*wj));
+    const int n = joint->n_poses;
+    wj->n = n;
+    for (int m = 0; m < n; ++m) {
+      wj->pose[m] = joint->pose[m];
+      std::memcpy(wj->LR[m], joint->L_R + 9 * m, sizeof(wj->LR[m]));
+      std::memcpy(wj->Lt[m], joint->L_t + 3 * m, sizeof(wj->Lt[m]));
+    }
+    for (int r = 0; r < 6 * n; ++r) {
+      std::memcpy(wj->H + mh::kWindowJointDim * r, joint->H + 24 * r, sizeof(double) * 6 * n);
+      wj->b[r] = joint->b[r];
+    }
+    wj->f = joint->f;
+    MH_HIP(ctx, hipMemcpyAsync(d + kWinJointAt, wj, sizeof(mh::WindowJoint), hipMemcpyHostToDevice, ctx->stream));
   }
   c.active = true;
   for (size_t f = 0; f < W; ++f) {
@@ -619,7 +692,14 @@ static int window_enqueue(mh_ctx * ctx, int upto)
           ra.rp.first = it == 0 ? 1 : 0;
         }
         la.lin = reinterpret_cast<const mh::WindowLinear *>(d + kWinLinAt);
-        if (c.edges) {
+        if (c.joint) {
+          mh::WindowJointStepArgs ja;
+          std::memset(static_cast<void *>(&ja), 0, sizeof(ja));
+          ja.e.l = la;
+          ja.e.edges = reinterpret_cast<const mh::WindowEdges *>(d + kWinEdgeAt);
+          ja.joint = reinterpret_cast<const mh::WindowJoint *>(d + kWinJointAt);
+          e = mh::launch_window_joint_step(ja, c.relin, ctx->stream);
+        } else if (c.edges) {
           mh::WindowEdgeStepArgs ea;
           std::memset(static_cast<void *>(&ea), 0, sizeof(ea));
           ea.l = la;
@@ -749,7 +829,17 @@ static int marginal_enqueue(mh_ctx * ctx)
     a.edges = reinterpret_cast<const mh::WindowEdges *>(d + kWinEdgeAt);
     a.p = c.p;
     a.seq = c.seq[0];
-    e = mh::launch_window_marginal(a, ctx->stream);
+    if (c.jmarginal) {
+      mh::WindowMarginalJointArgs ja;
+      std::memset(static_cast<void *>(&ja), 0, sizeof(ja));
+      ja.m = a;
+      ja.joint = c.jm_joint ? reinterpret_cast<const mh::WindowJoint *>(d + kWinJointAt) : nullptr;
+      ja.n_sep = c.n_sep;
+      for (int k = 0; k < MH_WINDOW_JOINT_POSES; ++k) ja.sep[k] = c.sep[k];
+      e = mh::launch_window_marginal_joint(ja, ctx->stream);
+    } else {
+      e = mh::launch_window_marginal(a, ctx->stream);
+    }
   }
   if (e != hipSuccess) {
     window_abandon(ctx);
@@ -759,24 +849,63 @@ static int marginal_enqueue(mh_ctx * ctx)
   return MH_OK;
 }
 
+// What the two marginal calls share behind their kernel's row: wait for the row (`words` flagged words, the bits word at
+// `bits_word`), clear *out, let `decode` take the row unless the kernel reports missing sums, `oldest` from the host epilogue of icps[0]'s K3, the
+// oldest factor's books and the release of the window.
+template <typename Decode>
+static int marginal_collect(mh_ctx * ctx, int words, int bits_word, const char * what, void * out, size_t out_bytes, mh_icp_result * oldest, Decode decode)
+{
+  WindowCall & c = ctx->window;
+  std::vector<double> row(static_cast<size_t>(words));
+  const ChainRows rows{ctx->h_window_rows, kWinRowWords, words, c.seq};
+  const int rc = chain_wait_row(ctx, rows, 0, row.data(), what);
+  if (rc != MH_OK) {
+    window_abandon(ctx);
+    return rc;
+  }
+  std::memset(out, 0, out_bytes);
+  int rc_all = MH_OK;
+  if (static_cast<int>(row[bits_word]) & 8) rc_all = fail(ctx, MH_ERR_HIP, std::string(what) + ": the kernel did not find its K3's sums");
+  mh_icp * icp = c.icps[0];
+  if (rc_all == MH_OK) {
+    decode(row.data());
+    if (!chain_epilogue(icp, 0, c.R0[0], c.gz, c.count0[0] + 1, icp->n ? c.seq[0] : 0, oldest))
+      rc_all = fail(ctx, MH_ERR_HIP, std::string(what) + ": the oldest factor's sums did not arrive");
+  }
+  icp->linearize_count = c.count0[0] + 1;
+  icp->cold = false;
+  window_release(ctx);
+  return rc_all;
+}
+
+// mh_icp_window_marginalise_joint: the wide row
+static int marginal_joint_finish(mh_ctx * ctx)
+{
+  WindowCall & c = ctx->window;
+  mh_window_joint_marginal * out = c.jmout;
+  return marginal_collect(ctx, mh::kWJMargWords, mh::kWJMargBits, "mh_icp_window_marginalise_joint", out, sizeof(*out), &out->oldest, [&](const double * row) {
+    out->prior.n_poses = c.n_sep;  // the separator and its poses are reported whether or not A00 had a positive pivot
+    for (int k = 0; k < c.n_sep; ++k) {
+      out->prior.pose[k] = c.sep[k];
+      std::memcpy(out->prior.L_R + 9 * k, c.LSR[k], sizeof(c.LSR[k]));
+      std::memcpy(out->prior.L_t + 3 * k, c.LSt[k], sizeof(c.LSt[k]));
+    }
+    std::memcpy(out->prior.H, row + mh::kWJMargH, sizeof(out->prior.H));
+    std::memcpy(out->prior.b, row + mh::kWJMargB, sizeof(out->prior.b));
+    out->prior.f = row[mh::kWJMargF];
+    out->valid = static_cast<int32_t>(row[mh::kWJMargValid]);
+    out->n_ties = static_cast<int32_t>(row[mh::kWJMargTies]);
+  });
+}
+
 // wait for the kernel's row, then the result and the oldest factor's books
 static int marginal_finish(mh_ctx * ctx)
 {
   static_assert(mh::kWMargWords <= static_cast<int>(kWinRowWords) && mh::kWMargH + 36 == mh::kWMargWords, "mh_icp_window_marginalise layout");
   WindowCall & c = ctx->window;
+  if (c.jmarginal) return marginal_joint_finish(ctx);
   mh_window_marginal * out = c.mout;
-  double row[mh::kWMargWords];
-  const ChainRows rows{ctx->h_window_rows, kWinRowWords, mh::kWMargWords, c.seq};
-  const int rc = chain_wait_row(ctx, rows, 0, row, "mh_icp_window_marginalise");
-  if (rc != MH_OK) {
-    window_abandon(ctx);
-    return rc;
-  }
-  std::memset(static_cast<void *>(out), 0, sizeof(*out));
-  int rc_all = MH_OK;
-  if (static_cast<int>(row[mh::kWMargBits]) & 8) rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_window_marginalise: the kernel did not find its K3's sums");
-  mh_icp * icp = c.icps[0];
-  if (rc_all == MH_OK) {
+  return marginal_collect(ctx, mh::kWMargWords, mh::kWMargBits, "mh_icp_window_marginalise", out, sizeof(*out), &out->oldest, [&](const double * row) {
     out->prior.pose = 1;
     std::memcpy(out->prior.L_R, c.L1R, sizeof(c.L1R));
     std::memcpy(out->prior.L_t, c.L1t, sizeof(c.L1t));
@@ -785,13 +914,7 @@ static int marginal_finish(mh_ctx * ctx)
     out->prior.f = row[mh::kWMargF];
     out->valid = static_cast<int32_t>(row[mh::kWMargValid]);
     out->n_ties = static_cast<int32_t>(row[mh::kWMargTies]);
-    if (!chain_epilogue(icp, 0, c.R0[0], c.gz, c.count0[0] + 1, icp->n ? c.seq[0] : 0, &out->oldest))
-      rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_window_marginalise: the oldest factor's sums did not arrive");
-  }
-  icp->linearize_count = c.count0[0] + 1;
-  icp->cold = false;
-  window_release(ctx);
-  return rc_all;
+  });
 }
 
 static int mh_icp_window_wait_impl(mh_ctx * ctx)
@@ -805,9 +928,11 @@ static int mh_icp_window_wait_impl(mh_ctx * ctx)
 
 static int mh_icp_window_marginalise_impl(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                           const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
-                                          size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out, bool blocking)
+                                          size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out, bool blocking,
+                                          bool jmcall = false, const mh_window_joint_factor * joint = nullptr, mh_window_joint_marginal * jout = nullptr)
 {
-  int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, nullptr, nullptr, nullptr, nullptr, true, lin, n_lin, edges, n_edges, true, out);
+  int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, nullptr, nullptr, nullptr, nullptr, true, lin, n_lin, edges, n_edges, true, out, joint, jout,
+                        jmcall);
   if (rc != MH_OK) return rc;
   rc = marginal_enqueue(icps[0]->ctx);
   if (rc != MH_OK || !blocking) return rc;
@@ -819,10 +944,11 @@ static int mh_icp_window_optimise_impl(mh_icp * const * icps, size_t W, const do
                                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out,
                                        double * trace_poses, bool blocking, bool relin_call, const mh_icp_window_relin * relin, uint32_t * evaluated_mask,
                                        bool lin_call = false, const mh_window_linear_factor * lin = nullptr, size_t n_lin = 0,
-                                       const mh_window_edge * edges = nullptr, size_t n_edges = 0)
+                                       const mh_window_edge * edges = nullptr, size_t n_edges = 0, const mh_window_joint_factor * joint = nullptr)
 {
   if (relin_call && !relin) return fail(window_ctx(icps, W), MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: NULL argument");
-  const int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask, lin_call, lin, n_lin, edges, n_edges);
+  const int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask, lin_call, lin, n_lin, edges, n_edges, false,
+                              nullptr, joint);
   if (rc != MH_OK) return rc;
   if (!blocking) return window_enqueue(icps[0]->ctx, cfg->iters);
   return window_run(icps[0]->ctx, cfg->check_every > 0 ? cfg->check_every : cfg->iters);
@@ -921,6 +1047,45 @@ int mh_icp_window_marginalise_async(mh_icp * const * icps, size_t W, const doubl
 {
   return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_async", [&]() -> int {
     return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, out, false);
+  });
+}
+// joint == NULL: mh_icp_window_optimise_edges, its kernels
+int mh_icp_window_optimise_joint(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                 const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                 const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_icp_window_result * out,
+                                 double * trace_poses, uint32_t * evaluated_mask, const mh_window_joint_factor * joint)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_joint", [&]() -> int {
+    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, false, relin, evaluated_mask, true, lin, n_lin, edges,
+                                       n_edges, joint);
+  });
+}
+int mh_icp_window_optimise_joint_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                       const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
+                                       const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges,
+                                       mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask, const mh_window_joint_factor * joint)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_joint_async", [&]() -> int {
+    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, relin, evaluated_mask, true, lin, n_lin, edges,
+                                       n_edges, joint);
+  });
+}
+int mh_icp_window_marginalise_joint(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                    const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
+                                    size_t n_lin, const mh_window_edge * edges, size_t n_edges, const mh_window_joint_factor * joint,
+                                    mh_window_joint_marginal * out)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_joint", [&]() -> int {
+    return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, nullptr, true, true, joint, out);
+  });
+}
+int mh_icp_window_marginalise_joint_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
+                                          const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
+                                          size_t n_lin, const mh_window_edge * edges, size_t n_edges, const mh_window_joint_factor * joint,
+                                          mh_window_joint_marginal * out)
+{
+  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_joint_async", [&]() -> int {
+    return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, nullptr, false, true, joint, out);
   });
 }
 int mh_icp_window_wait(mh_ctx * ctx)

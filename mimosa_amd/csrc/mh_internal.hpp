@@ -61,6 +61,12 @@ struct WindowCall
   bool marginal = false;  // mh_icp_window_marginalise: one K3 launch of icps[0] and the marginal kernel; the result goes to mout
   mh_window_marginal * mout = nullptr;
   double L1R[9], L1t[3];  // ... pose 1 as the caller gave it
+  bool joint = false;     // mh_icp_window_optimise_joint with a joint factor: the joint step kernel
+  bool jmarginal = false; // mh_icp_window_marginalise_joint (marginal is set as well): the joint marginal kernel; the result goes to jmout
+  bool jm_joint = false;  // ... with a joint factor
+  mh_window_joint_marginal * jmout = nullptr;
+  int n_sep = 0, sep[MH_WINDOW_JOINT_POSES];                                   // ... its separator
+  double LSR[MH_WINDOW_JOINT_POSES][9], LSt[MH_WINDOW_JOINT_POSES][3];         // ... and those poses as the caller gave them
 };
 
 struct mh_ctx

@@ -104,6 +104,33 @@ struct WindowEdgeWork
   int lo[kWindowMax];          // the smallest block column with a nonzero in block row i (i: none)
 };
 
+// mh_icp_window_optimise_joint: ONE dense factor on up to four poses of the window (ascending), the model f + 2 b^T x + x^T H x
+// in the stacked tangents of its members at their linearization poses L; member m owns rows / columns 6 m .. 6 m + 5 of H (row
+// stride kWindowJointDim) and b.  Read-only to the chain: every iteration carries it to the current poses of its members
+// (window_joint_transport) into WindowJointWork.  Its blocks between two members lie off the diagonal: they go into ew.B and
+// the profile.
+constexpr int kWindowJointMax = 4;
+constexpr int kWindowJointDim = 6 * kWindowJointMax;
+struct WindowJoint
+{
+  int n, pad;
+  int pose[kWindowJointMax];
+  double LR[kWindowJointMax][9], Lt[kWindowJointMax][3];
+  double H[kWindowJointDim * kWindowJointDim], b[kWindowJointDim], f;
+};
+struct WindowJointWork
+{
+  double H[kWindowJointDim * kWindowJointDim], b[kWindowJointDim], f;  // the factor at the current poses of its members
+  double d[kWindowJointMax][6], M[kWindowJointMax][18];                // member m: its offset from L_m; Jr^-1(d_r), then Exp(d_r)
+};
+// the member of `jt` that sits on `pose` (-1: none)
+MH_HD int window_joint_member(const WindowJoint & jt, int pose)
+{
+  for (int m = 0; m < jt.n; ++m)
+    if (jt.pose[m] == pose) return m;
+  return -1;
+}
+
 // One row per queued iteration, published as flagged words.
 enum WindowRow
 {
@@ -363,11 +390,93 @@ MH_HD bool window_relin_decide(const double d[6], double relin_rot, double relin
          fabs(d[5]) > relin_trans;
 }
 
+// window_transport for the joint factor: with d_m = window_local(L_m, T_m) per member, M = blockdiag(M_m) and d stacked,
+// jw.H = M^T H M block by block (H'_ij = M_i^T H_ij M_j for i <= j, H_ij M_j through 36 doubles of tmp, the lower blocks
+// mirrored), jw.b = M^T (b + H d), jw.f = f + 2 b^T d + d^T H d; every d zero: H, b, f untouched.  A factor of one member goes
+// through the operations of window_transport, in its order.  tmp: 36 doubles per block of the upper triangle (10 at most).
+template <typename Par>
+MH_HD void window_joint_transport(const WindowJoint & jt, const WindowState & st, WindowJointWork & jw, double (*tmp)[36], Par & par)
+{
+  constexpr int S = kWindowJointDim;
+  const int n = jt.n, nb = n * (n + 1) / 2;
+  par.each(n, [&](int m) {
+    const int i = jt.pose[m];
+    window_local(jt.LR[m], jt.Lt[m], st.R[i], st.t[i], jw.d[m]);
+    window_jrinv(jw.d[m], jw.M[m]);
+    align_expmap(jw.d[m], jw.M[m] + 9);
+  });
+  par.each(nb + 6 * n + 1, [&](int l) {
+    bool moved = false;
+    for (int m = 0; m < n; ++m)
+      for (int q = 0; q < 6; ++q) moved = moved || jw.d[m][q] != 0.0;
+    if (l < nb) {
+      int i = 0, q = l;
+      while (q >= n - i) {
+        q -= n - i;
+        ++i;
+      }
+      const int j = i + q;
+      const double * H = jt.H + 6 * i * S + 6 * j;
+      double * Ho = jw.H + 6 * i * S + 6 * j;
+      double * Hm = jw.H + 6 * j * S + 6 * i;  // the mirrored block (j, i)
+      double * tm = tmp[l];
+      if (moved)
+        for (int r = 0; r < 6; ++r)
+          for (int c = 0; c < 6; ++c) {
+            const double * blk = jw.M[j] + (c < 3 ? 0 : 9);
+            const int h0 = c < 3 ? 0 : 3, cc = c - h0;
+            tm[6 * r + c] = H[S * r + h0] * blk[cc] + H[S * r + h0 + 1] * blk[3 + cc] + H[S * r + h0 + 2] * blk[6 + cc];
+          }
+      for (int r = 0; r < 6; ++r) {
+        const double * blk = jw.M[i] + (r < 3 ? 0 : 9);
+        const int h0 = r < 3 ? 0 : 3, rr = r - h0;
+        for (int c = 0; c < 6; ++c) {
+          const double v = moved ? blk[rr] * tm[6 * h0 + c] + blk[3 + rr] * tm[6 * (h0 + 1) + c] + blk[6 + rr] * tm[6 * (h0 + 2) + c] : H[S * r + c];
+          Ho[S * r + c] = v;
+          if (i != j) Hm[S * c + r] = v;
+        }
+      }
+    } else if (l < nb + 6 * n) {
+      const int row = l - nb, m = row / 6, r = row % 6;
+      if (!moved) {
+        jw.b[row] = jt.b[row];
+        return;
+      }
+      const double * blk = jw.M[m] + (r < 3 ? 0 : 9);
+      const int h0 = r < 3 ? 0 : 3, rr = r - h0;
+      double g = 0.0;
+      for (int k = 0; k < 3; ++k) {
+        const int hr = 6 * m + h0 + k;
+        double v = jt.b[hr];
+        for (int j = 0; j < n; ++j)
+          for (int q = 0; q < 6; ++q) v += jt.H[S * hr + 6 * j + q] * jw.d[j][q];
+        g += blk[3 * k + rr] * v;
+      }
+      jw.b[row] = g;
+    } else {
+      if (!moved) {
+        jw.f = jt.f;
+        return;
+      }
+      double bd = 0.0, dHd = 0.0;
+      for (int row = 0; row < 6 * n; ++row) {
+        double hd = 0.0;
+        for (int j = 0; j < n; ++j)
+          for (int q = 0; q < 6; ++q) hd += jt.H[S * row + 6 * j + q] * jw.d[j][q];
+        bd += jt.b[row] * jw.d[row / 6][row % 6];
+        dHd += jw.d[row / 6][row % 6] * hd;
+      }
+      jw.f = jt.f + 2.0 * bd + dHd;
+    }
+  });
+}
+
 // ew.B over the profile: block (i, k), lo(i) <= k < i, is the has_Z term of the pair (k = i - 1), then its edges in list order;
 // a block of the profile that has neither is fill: zero.  A phase of its own: window_solve_profile runs it again behind the
-// factorisation, which leaves its updated blocks in ew.B.
-template <typename Par>
-MH_HD void window_assemble_blocks(int W, const WindowParams & p, const WindowWork & w, const WindowEdges & ed, WindowEdgeWork & ew, Par & par)
+// factorisation, which leaves its updated blocks in ew.B.  JOINT: in front of both, the joint factor's block of two member poses.
+template <bool JOINT = false, typename Par>
+MH_HD void window_assemble_blocks(int W, const WindowParams & p, const WindowWork & w, const WindowEdges & ed, WindowEdgeWork & ew, Par & par,
+                                  const WindowJoint * jt = nullptr, const WindowJointWork * jw = nullptr)
 {
   par.each(36 * (W * (W - 1) / 2), [&](int l) {
     const int q = l / 36, e = l % 36;
@@ -376,6 +485,10 @@ MH_HD void window_assemble_blocks(int W, const WindowParams & p, const WindowWor
     const int k = q - window_pair(i, 0);
     if (k < ew.lo[i]) return;
     double a = (k == i - 1 && ((p.has_Z >> i) & 1u)) ? w.E[i][e] : 0.0;
+    if (JOINT) {
+      const int mi = window_joint_member(*jt, i), mk = window_joint_member(*jt, k);
+      if (mi >= 0 && mk >= 0) a = jw->H[(6 * mi + e / 6) * kWindowJointDim + 6 * mk + e % 6] + a;
+    }
     for (int j = 0; j < ed.n; ++j)
       if (ed.b[j] == i && ed.a[j] == k) a += ew.Eba[j][e];
     ew.B[q][e] = a;
@@ -385,10 +498,13 @@ MH_HD void window_assemble_blocks(int W, const WindowParams & p, const WindowWor
 // w.A, w.E, w.rhs, w.cost from the factors' sums at the poses of `st`.  RELIN: the factors of `eval` from their sums (and into
 // rl, with the pose), the other non-empty ones from rl.  LIN: the linear factors of `lin` as well, carried to the poses of `st`.
 // EDGE: the edges of `ed` as well, and every block below the diagonal into ew->B over the profile ew->lo (w.E keeps the has_Z terms)
-template <bool RELIN, bool LIN, bool EDGE, typename Par>
+// JOINT (with LIN and EDGE): the joint factor `jt` as well, carried to the poses of `st` into jw (lw->tmp is its block scratch)
+template <bool RELIN, bool LIN, bool EDGE, bool JOINT = false, typename Par>
 MH_HD void window_assemble_impl(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, WindowRelin * rl, unsigned int eval,
-                                const WindowLinear * lin, WindowLinWork * lw, const WindowEdges * ed, WindowEdgeWork * ew, Par & par)
+                                const WindowLinear * lin, WindowLinWork * lw, const WindowEdges * ed, WindowEdgeWork * ew, Par & par,
+                                const WindowJoint * jt = nullptr, WindowJointWork * jw = nullptr)
 {
+  static_assert(!JOINT || (LIN && EDGE), "the joint factor rides on the edges chain");
   const int n_edge = EDGE ? ed->n : 0;
   const int W = p.W;
   const int n_lin = LIN ? lin->n : 0;
@@ -435,6 +551,7 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
       window_local(lin->LR[j], lin->Lt[j], st.R[i], st.t[i], d);
       window_transport(lin->H[j], lin->b[j], lin->f[j], d, lw->H[j], lw->b[j], lw->f[j], lw->tmp[j]);
     });
+  if (JOINT) window_joint_transport(*jt, st, *jw, lw->tmp, par);
   if (EDGE)
     par.each(n_edge + W, [&](int l) {
       if (l < n_edge) {
@@ -445,11 +562,12 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
         int lo = ((p.has_Z >> i) & 1u) ? i - 1 : i;
         for (int e = 0; e < n_edge; ++e)
           if (ed->b[e] == i && ed->a[e] < lo) lo = ed->a[e];
+        if (JOINT && window_joint_member(*jt, i) > 0 && jt->pose[0] < lo) lo = jt->pose[0];  // a member row reaches down to the smallest member
         ew->lo[i] = lo;
       }
     });
-  // per entry in the order optimise() adds: the factor, (the linear factors on its pose in list order,) the between factors in
-  // window order, (the edges in list order,) the prior, the damping
+  // per entry in the order optimise() adds: the factor, (the linear factors on its pose in list order,) (the joint factor's
+  // block,) the between factors in window order, (the edges in list order,) the prior, the damping
   par.each(36 * W + 6 * W + 1, [&](int l) {
     if (l < 36 * W) {
       const int i = l / 36, e = l % 36, r = e / 6, c = e % 6;
@@ -457,6 +575,10 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
       if (LIN)
         for (int j = 0; j < n_lin; ++j)
           if (lin->pose[j] == i) a += lw->H[j][e];
+      if (JOINT) {
+        const int m = window_joint_member(*jt, i);
+        if (m >= 0) a += jw->H[(6 * m + r) * kWindowJointDim + 6 * m + c];
+      }
       if (r == c && ((p.has_Z >> i) & 1u)) a += p.Wb[r];
       if (i + 1 < W && ((p.has_Z >> (i + 1)) & 1u)) a += w.Baa[i + 1][e];
       if (EDGE)
@@ -475,6 +597,10 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
       if (LIN)
         for (int j = 0; j < n_lin; ++j)
           if (lin->pose[j] == i) g += lw->b[j][r];
+      if (JOINT) {
+        const int m = window_joint_member(*jt, i);
+        if (m >= 0) g += jw->b[6 * m + r];
+      }
       if ((p.has_Z >> i) & 1u) g += w.gb[i][r];
       if (i + 1 < W && ((p.has_Z >> (i + 1)) & 1u)) g += w.ga[i + 1][r];
       if (EDGE)
@@ -488,6 +614,7 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
       for (int i = 0; i < W; ++i) cost += w.f[i];
       if (LIN)
         for (int j = 0; j < n_lin; ++j) cost += lw->f[j];
+      if (JOINT) cost += jw->f;
       for (int i = 1; i < W; ++i)
         if ((p.has_Z >> i) & 1u) cost += w.cz[i];
       if (EDGE)
@@ -495,7 +622,7 @@ MH_HD void window_assemble_impl(const double * sums, const WindowState & st, con
       w.cost = cost;
     }
   });
-  if (EDGE) window_assemble_blocks(W, p, w, *ed, *ew, par);
+  if (EDGE) window_assemble_blocks<JOINT>(W, p, w, *ed, *ew, par, jt, jw);
 }
 template <typename Par>
 MH_HD void window_assemble(const double * sums, const WindowState & st, const WindowParams & p, WindowWork & w, Par & par)
@@ -689,11 +816,12 @@ MH_HD void window_sweep_profile(int W, WindowWork & w, const WindowEdgeWork & ew
 // window_solve over the profile: w.x from w.A, ew.B, w.rhs.  The factorisation leaves its updated blocks in ew.B, so the
 // blocks are assembled again behind it (the same phase, the same digits; a third set of 120 blocks would not fit the LDS a
 // workgroup may declare): the refinement's residual is taken with every block of the system as assembled.
-template <typename Par>
-MH_HD bool window_solve_profile(int W, const WindowParams & p, WindowWork & w, const WindowEdges & ed, WindowEdgeWork & ew, Par & par)
+template <bool JOINT = false, typename Par>
+MH_HD bool window_solve_profile(int W, const WindowParams & p, WindowWork & w, const WindowEdges & ed, WindowEdgeWork & ew, Par & par,
+                                const WindowJoint * jt = nullptr, const WindowJointWork * jw = nullptr)
 {
   if (!window_factor_profile(W, w, ew, par)) return false;
-  window_assemble_blocks(W, p, w, ed, ew, par);
+  window_assemble_blocks<JOINT>(W, p, w, ed, ew, par, jt, jw);
   window_sweep_profile(W, w, ew, w.rhs, w.x, par);
   for (int it = 0; it < 2; ++it) {
     par.each(6 * W, [&](int row) {
@@ -731,9 +859,11 @@ MH_HD bool window_solve_profile(int W, const WindowParams & p, WindowWork & w, c
 // offset from its linearization pose and the factors the next iteration evaluates.
 // LIN: the system and the cost also hold the linear factors of `lin` (lw: their work arrays); nothing else changes.
 // EDGE: ... and the edges of `ed` (ew: their work arrays and the profile); the system is solved by window_solve_profile.
-template <bool RELIN, bool LIN, bool EDGE, typename Par>
+// JOINT: ... and the joint factor `jt` (jw: its work arrays); its off-diagonal blocks widen the profile.
+template <bool RELIN, bool LIN, bool EDGE, bool JOINT = false, typename Par>
 MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrived, const WindowParams & p, WindowWork & w, double * row, WindowRelin * rl,
-                              const WindowRelinParams * rp, const WindowLinear * lin, WindowLinWork * lw, const WindowEdges * ed, WindowEdgeWork * ew, Par & par)
+                              const WindowRelinParams * rp, const WindowLinear * lin, WindowLinWork * lw, const WindowEdges * ed, WindowEdgeWork * ew, Par & par,
+                              const WindowJoint * jt = nullptr, WindowJointWork * jw = nullptr)
 {
   const int W = p.W;
   const bool frozen = st.stopped != 0;
@@ -742,9 +872,9 @@ MH_HD int window_advance_impl(WindowState & st, const double * sums, bool arrive
   par.sync();  // (every index has read the state before index 0 changes it)
   bool stepped = false;
   if (!frozen && arrived) {
-    window_assemble_impl<RELIN, LIN, EDGE>(sums, st, p, w, rl, eval, lin, lw, ed, ew, par);
+    window_assemble_impl<RELIN, LIN, EDGE, JOINT>(sums, st, p, w, rl, eval, lin, lw, ed, ew, par, jt, jw);
     if (EDGE)
-      stepped = window_solve_profile(W, p, w, *ed, *ew, par);
+      stepped = window_solve_profile<JOINT>(W, p, w, *ed, *ew, par, jt, jw);
     else
       stepped = window_solve(W, w, par);
     par.each(W, [&](int i) {
@@ -847,6 +977,16 @@ MH_HD int window_advance_edges(WindowState & st, WindowRelin * rl, const double 
 {
   if (rl) return window_advance_impl<true, true, true>(st, sums, arrived, p, w, row, rl, rp, &lin, &lw, &ed, &ew, par);
   return window_advance_impl<false, true, true>(st, sums, arrived, p, w, row, nullptr, nullptr, &lin, &lw, &ed, &ew, par);
+}
+
+// mh_icp_window_optimise_joint: window_advance_edges with the joint factor `jt`
+template <typename Par>
+MH_HD int window_advance_joint(WindowState & st, WindowRelin * rl, const double * sums, bool arrived, const WindowParams & p, const WindowRelinParams * rp,
+                               const WindowLinear & lin, WindowLinWork & lw, const WindowEdges & ed, WindowEdgeWork & ew, const WindowJoint & jt,
+                               WindowJointWork & jw, WindowWork & w, double * row, Par & par)
+{
+  if (rl) return window_advance_impl<true, true, true, true>(st, sums, arrived, p, w, row, rl, rp, &lin, &lw, &ed, &ew, par, &jt, &jw);
+  return window_advance_impl<false, true, true, true>(st, sums, arrived, p, w, row, nullptr, nullptr, &lin, &lw, &ed, &ew, par, &jt, &jw);
 }
 
 // ---- the marginal prior of the oldest pose (mh_icp_window_marginalise) ------------------------------------------------------------
@@ -1029,6 +1169,224 @@ MH_HD void window_marginal_impl(const double * sums, const WindowState & st, con
   });
 }
 
+// ---- the joint marginal of the oldest pose (mh_icp_window_marginalise_joint) -------------------------------------------------------
+// window_marginal_impl for a pose 0 that is tied beyond pose 1.  The separator S: pose 1 (always), the far pose of every edge
+// (0, b), the members of the joint factor other than pose 0 — sorted, at most kWindowJointMax poses (more: the caller's to
+// refuse).  Every term on pose 0 in the assembly's per-entry order — the ICP factor, the linear factors on pose 0, the joint
+// factor carried to the current poses (it must contain pose 0: member 0), the has_Z[1] tie, the edges (0, b) in list order,
+// the prior, the damping — accumulated over {0} + S into A00, g0, A_S0 (6 |S| x 6), A_SS' (row stride kWindowJointDim), g_S', c
+// and eliminated as window_marginal_impl eliminates: the same factorisation of A00, its pivot test, then
+//   H_m = A_SS' - A_S0 A00^-1 A_S0^T,  b_m = g_S' - A_S0 A00^-1 g0,  f_m = c - g0^T A00^-1 g0.
+// With S = {1} and no joint factor every value goes through the operations of window_marginal_impl, in its order.
+// Returns |S| (sep: the first kWindowJointMax of them).  jt: null for none
+MH_HD int window_joint_separator(const WindowEdges & ed, const WindowJoint * jt, int sep[kWindowJointMax])
+{
+  unsigned int mask = 2u;
+  for (int e = 0; e < ed.n; ++e)
+    if (ed.a[e] == 0) mask |= 1u << ed.b[e];
+  for (int m = 0; jt && m < jt->n; ++m)
+    if (jt->pose[m] != 0) mask |= 1u << jt->pose[m];
+  int n = 0;
+  for (int i = 1; i < kWindowMax; ++i)
+    if ((mask >> i) & 1u) {
+      if (n < kWindowJointMax) sep[n] = i;
+      ++n;
+    }
+  return n;
+}
+struct WindowMarginalJointWork
+{
+  double H[36], b[6], f;  // the ICP factor of pose 0: H_ss, b_s, f
+  double Baa[kWindowTieMax][36], E[kWindowTieMax][36], ga[kWindowTieMax][6], gb[kWindowTieMax][6], cz[kWindowTieMax];
+  double A00[36], AS0[kWindowJointDim * 6], ASS[kWindowJointDim * kWindowJointDim], g0[6], gS[kWindowJointDim], c;
+  double L[36], Dv[6];               // A00 = L D L^T
+  double X[kWindowJointDim + 1][6];  // A00^-1 times column c of A_S0^T (c < 6 |S|), times g0 (the last)
+  int degen[2];
+  int ok, pad;
+};
+struct WindowMarginalJointOut
+{
+  double H[kWindowJointDim * kWindowJointDim], b[kWindowJointDim], f;  // the leading 6 |S|; zero behind
+  int valid, n_ties;
+  int degen[2];
+};
+
+// sums, p, st: as for window_marginal_impl, and R, t of every separator pose.  n_sep, sep: window_joint_separator's (n_sep <= kWindowJointMax).
+template <typename Par>
+MH_HD void window_marginal_joint_impl(const double * sums, const WindowState & st, const WindowParams & p, const WindowLinear & lin, WindowLinWork & lw,
+                                      const WindowEdges & ed, const WindowJoint * jt, WindowJointWork & jw, int n_sep, const int * sep,
+                                      WindowMarginalJointWork & w, WindowMarginalJointOut & out, Par & par)
+{
+  constexpr int S = kWindowJointDim;
+  const int n_lin = lin.n, n_edge = ed.n, N = 6 * n_sep;
+  const bool have = (p.have & 1u) != 0, tie = ((p.has_Z >> 1) & 1u) != 0;
+  auto on0 = [&](int e, int b) { return ed.a[e] == 0 && ed.b[e] == b; };
+  auto from0 = [&](int e) { return ed.a[e] == 0; };
+  auto member = [&](int pose) { return jt ? window_joint_member(*jt, pose) : -1; };
+  par.each(2, [&](int blk) { w.degen[blk] = have && align_block_degenerate(sums, blk, blk ? p.thresh_trans[0] : p.thresh_rot[0]) ? 1 : 0; });
+  par.each(1 + n_lin + kWindowTieMax, [&](int l) {
+    if (l == 0) {
+      if (have) {
+        AlignParams ap{};
+        for (int q = 0; q < 3; ++q) ap.gz[q] = p.gz[q];
+        ap.reg_4_dof = static_cast<int>(p.reg_4_dof & 1u);
+        ap.project_on_degeneracy = static_cast<int>(p.project_on_degeneracy & 1u);
+        align_hessian(sums, st.R[0], ap, w.degen[0] != 0, w.degen[1] != 0, w.H, w.b, w.f);
+      } else {
+        for (int q = 0; q < 36; ++q) w.H[q] = 0.0;
+        for (int q = 0; q < 6; ++q) w.b[q] = 0.0;
+        w.f = 0.0;
+      }
+    } else if (l <= n_lin) {
+      const int j = l - 1;
+      if (lin.pose[j] != 0) return;
+      double d[6];
+      window_local(lin.LR[j], lin.Lt[j], st.R[0], st.t[0], d);
+      window_transport(lin.H[j], lin.b[j], lin.f[j], d, lw.H[j], lw.b[j], lw.f[j], lw.tmp[j]);
+    } else if (l == n_lin + 1) {
+      if (tie) window_between(st.R[0], st.t[0], st.R[1], st.t[1], st.ZR[1], st.Zt[1], p.Wb, w.Baa[0], w.E[0], w.ga[0], w.gb[0], w.cz[0]);
+    } else {
+      const int e = l - n_lin - 2;
+      if (e < n_edge && from0(e)) {
+        const int b = ed.b[e];
+        window_between_dense(st.R[0], st.t[0], st.R[b], st.t[b], ed.ZR[e], ed.Zt[e], ed.Om[e], w.Baa[1 + e], w.E[1 + e], w.ga[1 + e], w.gb[1 + e], w.cz[1 + e]);
+      }
+    }
+  });
+  if (jt) window_joint_transport(*jt, st, jw, lw.tmp, par);  // (behind the linear factors: their scratch is free)
+  par.each(36 + 6 * N + N * N + 6 + N + 1, [&](int l) {
+    if (l < 36) {
+      const int r = l / 6, c = l % 6;
+      double a = w.H[l];
+      for (int j = 0; j < n_lin; ++j)
+        if (lin.pose[j] == 0) a += lw.H[j][l];
+      if (jt) a += jw.H[S * r + c];
+      if (tie) a += w.Baa[0][l];
+      for (int e = 0; e < n_edge; ++e)
+        if (from0(e)) a += w.Baa[1 + e][l];
+      if (r == c) {
+        a += p.prior[r];
+        a += p.damping;
+      }
+      w.A00[l] = a;
+      return;
+    }
+    l -= 36;
+    if (l < 6 * N) {
+      const int row = l / 6, c = l % 6, pose = sep[row / 6], q = 6 * (row % 6) + c, m = member(pose);
+      double a = (tie && pose == 1) ? w.E[0][q] : 0.0;
+      if (m >= 0) a = jw.H[S * (6 * m + row % 6) + c] + a;
+      for (int e = 0; e < n_edge; ++e)
+        if (on0(e, pose)) a += w.E[1 + e][q];
+      w.AS0[l] = a;
+      return;
+    }
+    l -= 6 * N;
+    if (l < N * N) {
+      const int row = l / N, col = l % N, pr = sep[row / 6], pc = sep[col / 6], r = row % 6, c = col % 6, mr = member(pr), mc = member(pc);
+      double a = (tie && pr == 1 && pc == 1 && r == c) ? p.Wb[r] : 0.0;
+      if (mr >= 0 && mc >= 0) a = jw.H[S * (6 * mr + r) + 6 * mc + c] + a;
+      if (pr == pc)
+        for (int e = 0; e < n_edge; ++e)
+          if (on0(e, pr)) a += ed.Om[e][6 * r + c];
+      w.ASS[S * row + col] = a;
+      return;
+    }
+    l -= N * N;
+    if (l < 6) {
+      const int r = l;
+      double g = w.b[r];
+      for (int j = 0; j < n_lin; ++j)
+        if (lin.pose[j] == 0) g += lw.b[j][r];
+      if (jt) g += jw.b[r];
+      if (tie) g += w.ga[0][r];
+      for (int e = 0; e < n_edge; ++e)
+        if (from0(e)) g += w.ga[1 + e][r];
+      w.g0[r] = g;
+      return;
+    }
+    l -= 6;
+    if (l < N) {
+      const int pose = sep[l / 6], r = l % 6, m = member(pose);
+      double g = (tie && pose == 1) ? w.gb[0][r] : 0.0;
+      if (m >= 0) g = jw.b[6 * m + r] + g;
+      for (int e = 0; e < n_edge; ++e)
+        if (on0(e, pose)) g += w.gb[1 + e][r];
+      w.gS[l] = g;
+      return;
+    }
+    double c = w.f;
+    for (int j = 0; j < n_lin; ++j)
+      if (lin.pose[j] == 0) c += lw.f[j];
+    if (jt) c += jw.f;
+    if (tie) c += w.cz[0];
+    int n = tie ? 1 : 0;
+    for (int e = 0; e < n_edge; ++e)
+      if (from0(e)) {
+        c += w.cz[1 + e];
+        n += 1;
+      }
+    w.c = c;
+    w.ok = 1;
+    out.n_ties = n;
+    out.degen[0] = w.degen[0];
+    out.degen[1] = w.degen[1];
+  });
+  // A00 = L D L^T: the columns of window_factor, its pivot test
+  for (int j = 0; j < 6 && w.ok; ++j) {
+    par.each(6 - j, [&](int l) {
+      double d = w.A00[7 * j];
+      for (int k = 0; k < j; ++k) d -= w.L[6 * j + k] * w.L[6 * j + k] * w.Dv[k];
+      if (l == 0) {
+        w.Dv[j] = d;
+        if (!(d > 0.0) || !(d < 1e300)) w.ok = 0;
+      } else {
+        const int row = j + l;
+        double s = w.A00[6 * row + j];
+        for (int k = 0; k < j; ++k) s -= w.L[6 * row + k] * w.L[6 * j + k] * w.Dv[k];
+        w.L[6 * row + j] = s / d;
+      }
+    });
+  }
+  par.each(S * S + S + 1, [&](int l) {
+    if (l < S * S)
+      out.H[l] = 0.0;
+    else if (l < S * S + S)
+      out.b[l - S * S] = 0.0;
+    else {
+      out.f = 0.0;
+      out.valid = 0;
+    }
+  });
+  if (!w.ok) return;
+  par.each(N + 1, [&](int c) { window_solve6(w.L, w.Dv, c < N ? &w.AS0[6 * c] : w.g0, w.X[c < N ? c : S]); });  // column c of A_S0^T = row c of A_S0
+  // the upper triangle of H_m, mirrored
+  par.each(N * (N + 1) / 2 + N + 1, [&](int l) {
+    if (l < N * (N + 1) / 2) {
+      int r = 0, q = l;
+      while (q >= N - r) {
+        q -= N - r;
+        ++r;
+      }
+      const int c = r + q;
+      double s = w.ASS[S * r + c];
+      for (int m = 0; m < 6; ++m) s -= w.AS0[6 * r + m] * w.X[c][m];
+      out.H[S * r + c] = s;
+      out.H[S * c + r] = s;
+    } else if (l < N * (N + 1) / 2 + N) {
+      const int r = l - N * (N + 1) / 2;
+      double s = w.gS[r];
+      for (int m = 0; m < 6; ++m) s -= w.AS0[6 * r + m] * w.X[S][m];
+      out.b[r] = s;
+    } else {
+      double s = w.c;
+      for (int m = 0; m < 6; ++m) s -= w.g0[m] * w.X[S][m];
+      out.f = s;
+      out.valid = 1;
+    }
+  });
+}
+
 }  // namespace mh
 
 #if defined(__HIPCC__)
@@ -1108,5 +1466,34 @@ struct WindowMarginalArgs
   unsigned int seq;
 };
 hipError_t launch_window_marginal(const WindowMarginalArgs & a, hipStream_t stream);
+
+// One step of an mh_icp_window_optimise_joint chain (window_joint_kernels.hip): the edge step with the joint factor `joint`,
+// which the host wrote once per call.
+struct WindowJointStepArgs
+{
+  WindowEdgeStepArgs e;
+  const WindowJoint * joint;  // device memory the context owns
+};
+hipError_t launch_window_joint_step(const WindowJointStepArgs & a, bool relin, hipStream_t stream);
+
+// mh_icp_window_marginalise_joint (window_joint_kernels.hip): as launch_window_marginal, with the joint factor (null: none) and
+// the separator the host worked out; the kernel publishes one row of kWJMargWords flagged words.
+enum WindowJointMarginalRow
+{
+  kWJMargValid = 0,
+  kWJMargTies,
+  kWJMargF,
+  kWJMargBits,  // 8: the factor's sums were missing (nothing was computed)
+  kWJMargB = 4,
+  kWJMargH = kWJMargB + kWindowJointDim,
+  kWJMargWords = kWJMargH + kWindowJointDim * kWindowJointDim,
+};
+struct WindowMarginalJointArgs
+{
+  WindowMarginalArgs m;
+  const WindowJoint * joint;
+  int n_sep, sep[kWindowJointMax];
+};
+hipError_t launch_window_marginal_joint(const WindowMarginalJointArgs & a, hipStream_t stream);
 }  // namespace mh
 #endif

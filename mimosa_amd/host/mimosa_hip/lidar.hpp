@@ -676,10 +676,33 @@ public:
     int n_ties = 0;  // the between entry of pose 1 plus the edges on (0, 1)
     WindowLinear prior;
   };
-  // a call in flight (optimiseWindowAsync, marginaliseWindowAsync): wait() / waitMarginal() collects it
+  // ONE dense factor on up to four poses of the window (mh_window_joint_factor): the model f + 2 b^T x + x^T H x, x the stacked
+  // tangents of the member poses at their `at`; what eliminating the oldest pose leaves once an odometry edge reaches from it
+  // past pose 1.  H: 6 n x 6 n row-major, b: 6 n, n = poses.size().
+  struct WindowJoint
+  {
+    std::vector<size_t> poses;  // strictly ascending indices into the window
+    std::vector<Pose3> at;      // the linearization pose of each member
+    std::vector<double> H, b;
+    double f = 0.0;
+  };
+  // mh_icp_window_marginalise_joint: `here` carries the separator's indices in the window the call was made on, `prior` the same
+  // factor rebased to the window WITHOUT its oldest pose (every index minus one) — what optimiseWindowJoint takes there.
+  struct WindowJointMarginal
+  {
+    bool valid = false;
+    int n_ties = 0;  // the between entry of pose 1 plus every edge from pose 0
+    WindowJoint here, prior;
+  };
+  // a call in flight (optimiseWindowAsync, marginaliseWindowAsync, ...): wait() / waitMarginal() / waitJointMarginal() collects it
   class WindowCall
   {
   public:
+    WindowJointMarginal waitJointMarginal()
+    {
+      factors_[0]->ctx().check(mh_icp_window_wait(factors_[0]->ctx().get()), "mh_icp_window_wait");
+      return finishJointMarginal();
+    }
     WindowResult wait()
     {
       factors_[0]->ctx().check(mh_icp_window_wait(factors_[0]->ctx().get()), "mh_icp_window_wait");
@@ -707,6 +730,29 @@ public:
       return out;
     }
     std::unique_ptr<mh_window_marginal> m_;  // set: the call is mh_icp_window_marginalise
+    WindowJointMarginal finishJointMarginal()
+    {
+      WindowJointMarginal out;
+      out.valid = jm_->valid != 0;
+      out.n_ties = jm_->n_ties;
+      const mh_window_joint_factor & q = jm_->prior;
+      const size_t n = static_cast<size_t>(q.n_poses);
+      for (size_t m = 0; m < n; ++m) {
+        out.here.poses.push_back(static_cast<size_t>(q.pose[m]));
+        out.here.at.push_back(pose3(q.L_R + 9 * m, q.L_t + 3 * m));
+      }
+      out.here.H.resize(36 * n * n);
+      out.here.b.assign(q.b, q.b + 6 * n);
+      for (size_t r = 0; r < 6 * n; ++r)
+        for (size_t c = 0; c < 6 * n; ++c) out.here.H[6 * n * r + c] = q.H[24 * r + c];
+      out.here.f = q.f;
+      out.prior = out.here;
+      for (size_t & i : out.prior.poses) i -= 1;
+      factors_[0]->last_ = jm_->oldest;
+      return out;
+    }
+    std::unique_ptr<mh_window_joint_marginal> jm_;  // set: the call is mh_icp_window_marginalise_joint
+    std::unique_ptr<mh_window_joint_factor> joint_;
     WindowResult finish()
     {
       WindowResult out;
@@ -797,6 +843,36 @@ public:
     return startWindow(factors, poses, between, g, config, false, nullptr, &linear, &edges, true);
   }
 
+  // optimiseWindowEdges with one joint factor (mh_icp_window_optimise_joint); joint == nullptr: optimiseWindowEdges itself
+  static WindowResult optimiseWindowJoint(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
+                                          const Unit3 & g, const WindowConfig & config, const std::vector<WindowLinear> & linear,
+                                          const std::vector<WindowEdge> & edges, const WindowJoint * joint, const WindowRelin * relin = nullptr)
+  {
+    return startWindow(factors, poses, between, g, config, true, relin, &linear, &edges, false, joint, true)->finish();
+  }
+  static std::unique_ptr<WindowCall> optimiseWindowJointAsync(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses,
+                                                              const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config,
+                                                              const std::vector<WindowLinear> & linear, const std::vector<WindowEdge> & edges,
+                                                              const WindowJoint * joint, const WindowRelin * relin = nullptr)
+  {
+    return startWindow(factors, poses, between, g, config, false, relin, &linear, &edges, false, joint, true);
+  }
+  // marginaliseWindow for an oldest pose tied beyond pose 1, by edges (0, b) or by the carried joint factor (which must contain
+  // pose 0; nullptr: none): the marginal on the separator, up to four poses (mh_icp_window_marginalise_joint)
+  static WindowJointMarginal marginaliseWindowJoint(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses,
+                                                    const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config,
+                                                    const std::vector<WindowLinear> & linear, const std::vector<WindowEdge> & edges, const WindowJoint * joint)
+  {
+    return startWindow(factors, poses, between, g, config, true, nullptr, &linear, &edges, true, joint, true)->finishJointMarginal();
+  }
+  static std::unique_ptr<WindowCall> marginaliseWindowJointAsync(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses,
+                                                                 const std::vector<WindowBetween> & between, const Unit3 & g, const WindowConfig & config,
+                                                                 const std::vector<WindowLinear> & linear, const std::vector<WindowEdge> & edges,
+                                                                 const WindowJoint * joint)
+  {
+    return startWindow(factors, poses, between, g, config, false, nullptr, &linear, &edges, true, joint, true);
+  }
+
   // getters, :48-72
   std::vector<RejectStatus> getStatuses() const
   {
@@ -866,7 +942,7 @@ private:
   static std::unique_ptr<WindowCall> startWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
                                                  const Unit3 & g, const WindowConfig & config, bool blocking, const WindowRelin * relin = nullptr,
                                                  const std::vector<WindowLinear> * linear = nullptr, const std::vector<WindowEdge> * edges = nullptr,
-                                                 bool marginal = false)
+                                                 bool marginal = false, const WindowJoint * joint = nullptr, bool joint_call = false)
   {
     const size_t n = factors.size();
     if (!n || poses.size() != n || between.size() != n) throw std::runtime_error("ICPFactor::optimiseWindow: one pose and one between entry per factor");
@@ -933,6 +1009,43 @@ private:
           for (int r = 0; r < 6; ++r)
             for (int c = 0; c < 6; ++c) q.info[6 * r + c] = e.info(r, c);
           w->edges_.push_back(q);
+        }
+        if (joint) {
+          const size_t nj = joint->poses.size();
+          if (joint->at.size() != nj || joint->H.size() != 36 * nj * nj || joint->b.size() != 6 * nj)
+            throw std::runtime_error("ICPFactor::optimiseWindowJoint: one linearization pose per member, H of 6n x 6n, b of 6n");
+          w->joint_.reset(new mh_window_joint_factor);
+          mh_window_joint_factor & q = *w->joint_;
+          std::memset(&q, 0, sizeof(q));
+          q.n_poses = static_cast<int32_t>(nj);  // (out of range: the library's to refuse)
+          const size_t nm = nj < static_cast<size_t>(MH_WINDOW_JOINT_POSES) ? nj : static_cast<size_t>(MH_WINDOW_JOINT_POSES);
+          for (size_t m = 0; m < nm; ++m) {
+            q.pose[m] = joint->poses[m] < n ? static_cast<int32_t>(joint->poses[m]) : -1;
+            const PoseRM L = rowMajor(joint->at[m]);
+            std::memcpy(q.L_R + 9 * m, L.R.data(), 72);
+            std::memcpy(q.L_t + 3 * m, L.t.data(), 24);
+          }
+          for (size_t r = 0; r < 6 * nm; ++r) {
+            for (size_t c = 0; c < 6 * nm; ++c) q.H[24 * r + c] = joint->H[6 * nj * r + c];
+            q.b[r] = joint->b[r];
+          }
+          q.f = joint->f;
+        }
+        if (marginal && joint_call) {
+          w->jm_.reset(new mh_window_joint_marginal);
+          const auto fm = blocking ? mh_icp_window_marginalise_joint : mh_icp_window_marginalise_joint_async;
+          factors[0]->ctx().check(fm(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_,
+                                     w->lin_.data(), w->lin_.size(), w->edges_.data(), w->edges_.size(), w->joint_.get(), w->jm_.get()),
+                                  blocking ? "mh_icp_window_marginalise_joint" : "mh_icp_window_marginalise_joint_async");
+          return w;
+        }
+        if (joint_call) {
+          const auto fj = blocking ? mh_icp_window_optimise_joint : mh_icp_window_optimise_joint_async;
+          factors[0]->ctx().check(fj(w->h_.data(), n, w->R_.data(), w->t_.data(), w->has_Z_.data(), w->ZR_.data(), w->Zt_.data(), w->g_.data(), &w->c_,
+                                     relin ? &w->relin_ : nullptr, w->lin_.data(), w->lin_.size(), w->edges_.data(), w->edges_.size(), w->r_.get(), nullptr,
+                                     relin ? w->masks_.data() : nullptr, w->joint_.get()),
+                                  blocking ? "mh_icp_window_optimise_joint" : "mh_icp_window_optimise_joint_async");
+          return w;
         }
         if (marginal) {
           w->m_.reset(new mh_window_marginal);

@@ -270,6 +270,12 @@ struct Config
   // is carried as a linear factor on the window's pose 0 instead of the 1e-4 rad / 1e-4 m pin; a marginal that is not valid falls
   // back to the pin for that window.  Refused without device_window and with odometry_every > 1
   bool window_marginal = false;
+  // window_marginal for an oldest pose that odometry edges tie beyond pose 1: it is marginalised with every live edge from it
+  // (ICPFactor::marginaliseWindowJoint) and the dense Gaussian this leaves on its separator, up to four poses, is carried as the
+  // one joint prior of the window calls (ICPFactor::optimiseWindowJoint, prior_info = 0) and absorbed by the next marginalisation;
+  // a marginal that is not valid falls back to the pin for that window.  Offered only with device_window and odometry_every
+  // 1 .. 4, refused otherwise and together with window_marginal
+  bool window_marginal_joint = false;
   double odometry_sigma_rot_deg = 1.0, odometry_sigma_trans_m = 0.5;
   A3 gravity{0.0, 0.0, -9.81};
   lidar::RegistrationConfig reg = lidar::defaultRegistrationConfig();
@@ -294,6 +300,7 @@ struct Result
   std::vector<RT> poses;
   std::vector<int> photo_valid;
   std::vector<int> marginal_valid;   // window_marginal: the valid flag of every marginal computed
+  std::vector<int> separator_sizes;  // window_marginal_joint: the number of poses every marginal was left on
   std::vector<int> photo_in_window;  // photo_window: photometric factors in the window at each scan's optimisation
   std::vector<std::vector<double>> costs;
   int n_keyframes = 0;
@@ -412,7 +419,7 @@ public:
     }
     win.push_back(lv);
     if (static_cast<int>(win.size()) > window_) {
-      if (window_marginal_) marginaliseOldest();
+      if (window_marginal_ || window_marginal_joint_) marginaliseOldest();
       win.pop_front();
     }
     expireEdges();
@@ -451,7 +458,10 @@ public:
   void setWindowPhotoLinear(bool on) { window_photo_linear_ = on; }
   // on (with the device window): the pose that leaves the window is marginalised and its marginal carried as the prior
   void setWindowMarginal(bool on) { window_marginal_ = on; }
+  // ... with the edges that reach from it beyond pose 1, its marginal carried as the window calls' joint factor
+  void setWindowMarginalJoint(bool on) { window_marginal_joint_ = on; }
   const std::vector<int> & marginalValid() const { return marginal_valid_; }
+  const std::vector<int> & separatorSizes() const { return separator_sizes_; }
   void setWindowRelin(bool on, double rot, double trans)
   {
     window_relin_ = on;
@@ -681,6 +691,8 @@ private:
         linear.push_back(carried_);
         for (double & v : wc.prior_info) v = 0.0;
       }
+      if (has_carried_joint_)  // ... or the joint prior
+        for (double & v : wc.prior_info) v = 0.0;
       const Unit3 down(0.0, 0.0, -1.0);
       std::vector<ICPFactor::WindowEdge> edges;
       for (const Edge & e : edges_) {
@@ -691,7 +703,8 @@ private:
         q.info = matrix6(e.info);
         edges.push_back(q);
       }
-      const ICPFactor::WindowResult r = edges_on_ ? ICPFactor::optimiseWindowEdges(factors, poses, between, down, wc, linear, edges, window_relin_ ? &rl : nullptr)
+      const ICPFactor::WindowResult r = has_carried_joint_ ? ICPFactor::optimiseWindowJoint(factors, poses, between, down, wc, linear, edges, &carried_joint_, window_relin_ ? &rl : nullptr)
+                                        : edges_on_ ? ICPFactor::optimiseWindowEdges(factors, poses, between, down, wc, linear, edges, window_relin_ ? &rl : nullptr)
                                         : (window_photo_linear_ || has_carried_) ? ICPFactor::optimiseWindowLin(factors, poses, between, down, wc, linear, window_relin_ ? &rl : nullptr)
                                         : window_relin_      ? ICPFactor::optimiseWindowRelin(factors, poses, between, down, wc, rl)
                                                              : ICPFactor::optimiseWindow(factors, poses, between, down, wc);
@@ -756,10 +769,19 @@ private:
       for (int p = 0; p < 3; ++p) {
         wc.between_info[p] = Wb_[p];
         wc.between_info[3 + p] = Wb_[3 + p];
-        wc.prior_info[p] = has_carried_ ? 0.0 : 1.0 / (sr * sr);
-        wc.prior_info[3 + p] = has_carried_ ? 0.0 : 1.0 / (st * st);
+        wc.prior_info[p] = (has_carried_ || has_carried_joint_) ? 0.0 : 1.0 / (sr * sr);
+        wc.prior_info[3 + p] = (has_carried_ || has_carried_joint_) ? 0.0 : 1.0 / (st * st);
       }
       wc.damping = 1e-9;
+      if (window_marginal_joint_) {  // every live edge from pose 0, the carried joint prior: the marginal absorbs it
+        const ICPFactor::WindowJointMarginal mj = ICPFactor::marginaliseWindowJoint(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc, linear, edges,
+                                                                                    has_carried_joint_ ? &carried_joint_ : nullptr);
+        marginal_valid_.push_back(mj.valid ? 1 : 0);
+        separator_sizes_.push_back(static_cast<int>(mj.prior.poses.size()));
+        has_carried_joint_ = mj.valid;
+        carried_joint_ = mj.prior;
+        return;
+      }
       const ICPFactor::WindowMarginal m = ICPFactor::marginaliseWindow(factors, poses, between, Unit3(0.0, 0.0, -1.0), wc, linear, edges);
       marginal_valid_.push_back(m.valid ? 1 : 0);
       has_carried_ = m.valid;
@@ -781,7 +803,9 @@ private:
   bool device_window_ = false, window_relin_ = false, window_photo_linear_ = false, window_marginal_ = false;
   bool has_carried_ = false;          // window_marginal: a marginal prior sits on the window's pose 0 (false: the pin)
   ICPFactor::WindowLinear carried_;
-  std::vector<int> marginal_valid_;
+  bool window_marginal_joint_ = false, has_carried_joint_ = false;  // window_marginal_joint: a joint prior is carried (false: the pin)
+  ICPFactor::WindowJoint carried_joint_;
+  std::vector<int> marginal_valid_, separator_sizes_;
   double relin_rot_ = 0.0, relin_trans_ = 0.0;
   int window_, update_iters_;
   double Wb_[6];
@@ -859,7 +883,14 @@ public:
     if (cfg_.window_marginal && cfg_.odometry_every > 1)
       throw std::runtime_error("replay: window_marginal is not offered with odometry_every > 1: an odometry edge would reach from pose 0 beyond pose 1");
     if (cfg_.window_marginal && cfg_.window < 2) throw std::runtime_error("replay: window_marginal needs a window of at least two poses");
+    if (cfg_.window_marginal_joint && !cfg_.device_window) throw std::runtime_error("replay: window_marginal_joint is only offered with device_window");
+    if (cfg_.window_marginal_joint && cfg_.window_marginal)
+      throw std::runtime_error("replay: window_marginal_joint is not offered together with window_marginal");
+    if (cfg_.window_marginal_joint && (cfg_.odometry_every < 1 || cfg_.odometry_every > 4))
+      throw std::runtime_error("replay: window_marginal_joint is offered with odometry_every 1 .. 4: the separator of the oldest pose may have at most four poses");
+    if (cfg_.window_marginal_joint && cfg_.window < 2) throw std::runtime_error("replay: window_marginal_joint needs a window of at least two poses");
     smoother.setWindowMarginal(cfg_.window_marginal);
+    smoother.setWindowMarginalJoint(cfg_.window_marginal_joint);
     smoother.setDeviceWindow(cfg_.device_window);
     smoother.setWindowPhotoLinear(cfg_.window_photo_linear);
     smoother.setWindowRelin(cfg_.window_relin, cfg_.window_relin_rot, cfg_.window_relin_trans);
@@ -1084,6 +1115,7 @@ public:
     if (photo_worker) photo_worker->wait();
     win.clear();
     res.marginal_valid = smoother.marginalValid();
+    res.separator_sizes = smoother.separatorSizes();
     res.seconds = secs(t_begin, clk::now());
     return res;
   }

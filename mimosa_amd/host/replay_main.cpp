@@ -1,12 +1,14 @@
 // Native sequence replay: drives mimosa_hip::replay::FixedLagReplay (host/mimosa_hip/replay.hpp) on an input file written
 // by mimosa_amd/replay.py:write_native_input and prints one JSON object (estimated poses, per-stage seconds, scans/s).
-//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear][+marginal] | device-window-relin=<rot>,<trans>[+photo-linear][+marginal]] [odometry] [device-poses]
+//   replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear][+marginal | +marginal-joint] | device-window-relin=<rot>,<trans>[+photo-linear][+marginal | +marginal-joint]] [odometry] [device-poses]
 //     device-poses (last word): replay::Config::device_poses — the per-timestamp deskew poses are computed on the device
 //     device-window (in front of it): replay::Config::device_window — the smoother's iterations run as one chain of launches on
 //       the device (FixedLagReplay without the photometric factor; refused elsewhere).  +photo-linear behind either form:
 //       replay::Config::window_photo_linear — the photometric factor is accepted, linearized once per window call on the host
 //       and carried by the chain as a linear factor.  +marginal behind all of that: replay::Config::window_marginal — the pose
-//       that leaves the window is marginalised on the device and its marginal carried as the prior on the oldest pose
+//       that leaves the window is marginalised on the device and its marginal carried as the prior on the oldest pose;
+//       +marginal-joint in its place: replay::Config::window_marginal_joint — with the odometry edges that reach from that pose
+//       beyond pose 1, the marginal carried as the one joint factor of the window calls (needs odometry, every 1 .. 4 scans)
 //     odometry (in front of device-poses, behind the window word): replay::Config::odometry_every — the input file ends with the
 //       external odometry section (odometry_every; sigma_rot_deg, sigma_trans_m; per message scan index, pose, covariance); each
 //       message goes through odometry::Manager and ties the window poses of two scans (FixedLagReplay; refused elsewhere)
@@ -28,7 +30,7 @@ using binio::read_vec;
 int main(int argc, char ** argv)
 {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear][+marginal] | device-window-relin=<rot>,<trans>[+photo-linear][+marginal]] [odometry] [device-poses]\n");
+    std::fprintf(stderr, "usage: replay_native <input.bin> [repeats] [manager | sequential | sharded <world> | sharded-rccl] [device-window[+photo-linear][+marginal | +marginal-joint] | device-window-relin=<rot>,<trans>[+photo-linear][+marginal | +marginal-joint]] [odometry] [device-poses]\n");
     return 2;
   }
   const bool device_poses = argc > 2 && std::string(argv[argc - 1]) == "device-poses";
@@ -38,6 +40,9 @@ int main(int argc, char ** argv)
   if (odometry) --argc;
   // device-window-relin=<rot>,<trans>: device-window with replay::Config::window_relin (relinearization thresholds, rad and m)
   std::string window_word = argc > 2 ? argv[argc - 1] : "";
+  const std::string joint_suffix = "+marginal-joint";
+  const bool window_marginal_joint = window_word.size() > joint_suffix.size() && window_word.compare(window_word.size() - joint_suffix.size(), joint_suffix.size(), joint_suffix) == 0;
+  if (window_marginal_joint) window_word.resize(window_word.size() - joint_suffix.size());
   const std::string marginal_suffix = "+marginal";
   const bool window_marginal = window_word.size() > marginal_suffix.size() && window_word.compare(window_word.size() - marginal_suffix.size(), marginal_suffix.size(), marginal_suffix) == 0;
   if (window_marginal) window_word.resize(window_word.size() - marginal_suffix.size());
@@ -88,6 +93,7 @@ int main(int argc, char ** argv)
     cfg.window_relin_trans = relin_trans;
     cfg.window_photo_linear = device_window && window_photo_linear;
     cfg.window_marginal = device_window && window_marginal;
+    cfg.window_marginal_joint = device_window && window_marginal_joint;
     const auto bias = read_vec<double>(f);
     for (size_t i = 0; i + 2 < bias.size(); i += 3) cfg.bias_directions.push_back(V3D(bias[i], bias[i + 1], bias[i + 2]));
     const auto seed = read_vec<float>(f);
@@ -195,6 +201,8 @@ int main(int argc, char ** argv)
     for (size_t i = 0; i < r.photo_in_window.size(); ++i) std::printf("%d%s", r.photo_in_window[i], i + 1 < r.photo_in_window.size() ? ", " : "");
     std::printf("],\n\"marginal_valid\": [");
     for (size_t i = 0; i < r.marginal_valid.size(); ++i) std::printf("%d%s", r.marginal_valid[i], i + 1 < r.marginal_valid.size() ? ", " : "");
+    std::printf("],\n\"separator_sizes\": [");
+    for (size_t i = 0; i < r.separator_sizes.size(); ++i) std::printf("%d%s", r.separator_sizes[i], i + 1 < r.separator_sizes.size() ? ", " : "");
     std::printf("],\n\"init_align_iters\": %d,\n\"first_costs\": [", r.init_align_iters);
     for (size_t i = 0; !r.costs.empty() && i < r.costs.at(0).size(); ++i) std::printf("%.17g%s", r.costs[0][i], i + 1 < r.costs[0].size() ? ", " : "");
     std::printf("],\n\"poses\": [");

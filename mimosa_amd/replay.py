@@ -94,6 +94,12 @@ class ReplayConfig:
     # falls back to the pin for that window.  Refused without device_window, and with odometry_every > 1 (an odometry edge would
     # reach from pose 0 beyond pose 1: the marginal would be a joint factor on several poses)
     window_marginal: bool = False
+    # window_marginal for a window whose oldest pose is tied beyond pose 1 by odometry edges: the pose that leaves is marginalised
+    # with every live edge from it (mh_icp_window_marginalise_joint) and the dense Gaussian this leaves on its separator — up to
+    # four poses — is carried as the one joint prior of the window calls (mh_icp_window_optimise_joint, prior_info = 0), absorbed
+    # by the next marginalisation.  A marginal that is not valid falls back to the pin for that window.  Offered only with
+    # device_window and odometry_every 1 .. 4 (a separator of at most four poses), refused otherwise; not together with window_marginal
+    window_marginal_joint: bool = False
     odometry_sigma_rot_deg: float = 1.0
     odometry_sigma_trans_m: float = 0.5
     reg: dict = field(default_factory=synth.enwide_config)
@@ -336,7 +342,7 @@ class HipBackend:
         rs = self.capi.linearize_batch(factors, [p[0] for p in poses], [p[1] for p in poses])
         return [(np.asarray(r["H_ss"]).reshape(6, 6), np.asarray(r["b_s"]), float(r["f"])) for r in rs]
 
-    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping, relin=None, linear=None, edges=None):
+    def optimise_window(self, factors, poses, Zs, iters, between_info, prior_info, damping, relin=None, linear=None, edges=None, joint=None):
         """device_window: the smoother's loop over the window as one call; the poses after it and the cost before each iteration.
         linear: host-linearized Hessian factors on poses of the window (capi.optimise_window)"""
         cfg = self.capi.make_window_config(iters=iters, between_info=between_info, prior_info=prior_info, damping=damping)
@@ -346,6 +352,8 @@ class HipBackend:
             kw["linear"] = linear
         if edges is not None:  # mh_icp_window_optimise_edges, also with an empty list
             kw["edges"] = edges
+        if joint is not None:  # mh_icp_window_optimise_joint
+            kw["joint"] = joint
         r = self.capi.optimise_window(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs], **kw)
         if r["iters"] != iters:
             raise np.linalg.LinAlgError("Singular matrix")
@@ -357,6 +365,13 @@ class HipBackend:
         I3, z3 = np.eye(3), np.zeros(3)
         return self.capi.marginalise_window(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs],
                                             linear=linear, edges=edges)
+
+    def marginalise_window_joint(self, factors, poses, Zs, between_info, prior_info, damping, linear, edges, joint):
+        """window_marginal_joint: what eliminating the oldest pose leaves on its separator (capi.marginalise_window_joint's dict)"""
+        cfg = self.capi.make_window_config(iters=1, between_info=between_info, prior_info=prior_info, damping=damping)
+        I3, z3 = np.eye(3), np.zeros(3)
+        return self.capi.marginalise_window_joint(factors, poses, cfg, has_Z=[Z is not None for Z in Zs], Z=[(I3, z3) if Z is None else Z for Z in Zs],
+                                                  linear=linear, edges=edges, joint=joint)
 
     def linearize_photo(self, pf, R, t):
         r = pf.linearize(R, t)
@@ -442,6 +457,15 @@ def write_native_input(path, cfg: ReplayConfig, scans, rng_seed=7, mode=synth.EN
 
 
 def _check_window_marginal(cfg, error):
+    if cfg.window_marginal_joint:
+        if not cfg.device_window:
+            raise error("window_marginal_joint is only offered with device_window")
+        if cfg.window_marginal:
+            raise error("window_marginal_joint is not offered together with window_marginal")
+        if not 1 <= cfg.odometry_every <= 4:
+            raise error("window_marginal_joint is offered with odometry_every 1 .. 4: the separator of the oldest pose may have at most four poses")
+        if cfg.window < 2:
+            raise error("window_marginal_joint needs a window of at least two poses")
     if not cfg.window_marginal:
         return
     if not cfg.device_window:
@@ -484,7 +508,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
         mode = ["sharded-rccl"]
     if cfg.device_window:
         word = "device-window" if cfg.window_relin is None else "device-window-relin=%r,%r" % (float(cfg.window_relin[0]), float(cfg.window_relin[1]))
-        mode = mode + [word + ("+photo-linear" if cfg.window_photo_linear else "") + ("+marginal" if cfg.window_marginal else "")]
+        mode = mode + [word + ("+photo-linear" if cfg.window_photo_linear else "") + ("+marginal" if cfg.window_marginal else "")
+                       + ("+marginal-joint" if cfg.window_marginal_joint else "")]
     if cfg.odometry_every > 0:
         mode = mode + ["odometry"]
     if cfg.device_poses:
@@ -526,6 +551,7 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     win = []          # live window: dicts(k, R, t, factor, Z (relative pose to the previous scan), fresh)
     est, kf_poses, n_kf, costs, n_photo_valid, n_photo_window = [], [], 0, [], [], []
     carried, marginal_valid = None, []  # window_marginal: the marginal prior on the window's pose 0 (None: the pin), every marginal's valid flag
+    carried_joint, separator_sizes = None, []  # window_marginal_joint: the joint prior (None: the pin), the separator of every marginal
     pin = [1.0 / 1e-4**2] * 6
     loose_info = [1.0 / np.deg2rad(1.0)**2] * 3 + [1.0 / 0.1**2] * 3
     R_prev = t_prev = vel_prev = None
@@ -563,9 +589,10 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
             R_w, t_w = backend.align_first(f, R_pred, p_pred, cfg.init_align_iters)
         win.append(dict(k=k, R=R_w, t=t_w, f=f, Z=Z, pf=pf if cfg.photo_window else None))
         if len(win) > cfg.window:
-            if cfg.window_marginal:
+            if cfg.window_marginal or cfg.window_marginal_joint:
                 # the window as it was optimised (without the scan that just arrived), at its current poses, with the carried
-                # prior and, where the window call passes it, the oldest pose's photometric factor as linear factors on pose 0
+                # prior and, where the window call passes it, the oldest pose's photometric factor as a linear factor on pose 0;
+                # the live edges as edges (window_marginal_joint: those from pose 0 reach beyond pose 1)
                 live = win[:-1]
                 mlin = [] if carried is None else [carried]
                 if cfg.window_photo_linear and cfg.photo_window and live[0]["pf"] is not None:
@@ -574,11 +601,17 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
                     if nv and np.all(np.isfinite(Hp)) and np.all(np.isfinite(bp)) and np.isfinite(fp):
                         mlin.append(dict(pose=0, at=T0, H=Hp, b=bp, f=fp))
                 medges = [dict(a=e["ka"] - live[0]["k"], b=e["kb"] - live[0]["k"], Z=e["Z"], info=e["info"]) for e in edges]
-                prior = [0.0] * 6 if carried is not None else (loose_info if live[0]["k"] == 0 else pin)
-                m = backend.marginalise_window([w["f"] for w in live], [(w["R"], w["t"]) for w in live], [None] + [w["Z"] for w in live[1:]],
-                                               list(np.diag(Wb)), prior, 1e-9, mlin, medges)
+                has_prior = carried is not None or carried_joint is not None
+                prior = [0.0] * 6 if has_prior else (loose_info if live[0]["k"] == 0 else pin)
+                margs = ([w["f"] for w in live], [(w["R"], w["t"]) for w in live], [None] + [w["Z"] for w in live[1:]], list(np.diag(Wb)), prior, 1e-9, mlin, medges)
+                if cfg.window_marginal:
+                    m = backend.marginalise_window(*margs)
+                    carried = m["linear"] if m["valid"] else None
+                else:  # the carried joint prior goes in and is absorbed
+                    m = backend.marginalise_window_joint(*margs, carried_joint)
+                    separator_sizes.append(len(m["joint"]["poses"]))
+                    carried_joint = m["joint"] if m["valid"] else None
                 marginal_valid.append(int(m["valid"]))
-                carried = m["linear"] if m["valid"] else None
             old = win.pop(0)
             backend.release(old["f"])
             if old["pf"] is not None:
@@ -619,6 +652,9 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
             prior = [1.0 / sr**2] * 3 + [1.0 / st**2] * 3
             if carried is not None:  # the marginal prior stands in for the pin
                 kw["linear"] = kw.get("linear", []) + [carried]
+                prior = [0.0] * 6
+            if carried_joint is not None:  # ... or the joint prior
+                kw["joint"] = carried_joint
                 prior = [0.0] * 6
             new_poses, fs = backend.optimise_window([w["f"] for w in win], [(w["R"], w["t"]) for w in win], [None] + [w["Z"] for w in win[1:]],
                                                     cfg.update_iters, list(np.diag(Wb)), prior, 1e-9, **kw)
@@ -725,4 +761,4 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     rerr = [float(np.rad2deg(np.linalg.norm(_so3_log(Re.T @ s["R_gt"])))) for (Re, _), s in zip(est, scans)]
     return {"poses_est": est, "trans_err": terr, "rot_err_deg": rerr, "n_keyframes": n_kf, "seconds": total,
             "scans_per_s": len(scans) / total, "stage_s": stage, "costs": costs, "photo_valid": n_photo_valid,
-            "photo_in_window": n_photo_window, "marginal_valid": marginal_valid}
+            "photo_in_window": n_photo_window, "marginal_valid": marginal_valid, "separator_sizes": separator_sizes}
