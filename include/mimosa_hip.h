@@ -319,6 +319,77 @@ int mh_icp_align(mh_icp * icp, const double R0[9], const double t0[3], const dou
 int mh_icp_align_async(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3],
                        const mh_icp_align_config * cfg, mh_icp_align_result * out);
 
+/* ---- relocalisation: score candidate poses against the map, refine the best ---------------------
+ * Every call above wants a pose that already lies inside the association gate.  These two serve the caller who has none: up to
+ * MH_RELOC_MAX_POSES candidate poses of the factor's cloud are scored against its map in one chain of launches and ranked on
+ * the device; mh_icp_relocalise then refines the few best with mh_icp_align.  No reference counterpart.
+ *
+ * Score of a pose (R, t) with gate g and stride s, over the factor's points i with i % s == 0 (i counts in the order the
+ * points were given to mh_icp_create*): q = R p + t in fp64, q_a = ((R[3a] x + R[3a+1] y) + R[3a+2] z) + t[a]; the point is
+ * `occupied` when the voxel of q holds a map point, and an `inlier` when the nearest map point over the map's neighbour voxels —
+ * the k = 1 answer of mh_map_knn for q, bit for bit in sq_dists[0] — exists and has d2 <= g * g; sum_sq adds d2 over the
+ * inliers.  A point farther than 2^20 voxels from the origin (or not finite after the transform) is neither: a pose far
+ * outside the map is ordinary input and scores zeros.  The sums are taken in a fixed order that does not depend on n_poses: a
+ * pose gives the same bits alone, at any position of any batch and on every repeat.
+ * Ranking: n_inliers descending, then sum_sq ascending, then pose index ascending.  best[] receives the top_k pose indices in
+ * rank order, -1 behind the last pose (all MH_RELOC_MAX_REFINE entries are written).
+ * The call reads the map and the source cloud only: association state, linearize count and results of the factor are untouched.
+ * MH_ERR_INVALID_ARG: a NULL icp, R, t or cfg, best == NULL with top_k > 0, a factor with a call in flight or without points,
+ * n_poses outside 1 .. MH_RELOC_MAX_POSES, a gate that is not finite and > 0, stride < 1, top_k outside 0 .. MH_RELOC_MAX_REFINE,
+ * a pose with an entry that is not finite (the message names its index).  MH_ERR_UNSUPPORTED: binary factors and the factors
+ * of the map-sharded path.  Nothing is enqueued then. */
+#define MH_RELOC_MAX_POSES 65536
+#define MH_RELOC_MAX_REFINE 8
+typedef struct mh_pose_score {
+  int32_t n_points;   /* points looked at: ceil(n / stride) */
+  int32_t n_occupied, n_inliers, reserved;
+  double sum_sq;      /* sum of d2 over the inliers */
+} mh_pose_score;      /* 24 bytes */
+
+typedef struct mh_icp_score_config {
+  double gate;        /* m, finite and > 0 */
+  int32_t stride;     /* >= 1 */
+  int32_t top_k;      /* 0 .. MH_RELOC_MAX_REFINE: how many winners the device selects */
+} mh_icp_score_config;
+
+/* R: 9 n_poses doubles (row-major), t: 3 n_poses.  scores (n_poses entries) may be NULL: a caller who wants only the winners
+ * downloads MH_RELOC_MAX_REFINE indices.  best (MH_RELOC_MAX_REFINE entries) may be NULL iff top_k == 0. */
+int mh_icp_score_poses(mh_icp * icp, const double * R, const double * t, size_t n_poses, const mh_icp_score_config * cfg,
+                       mh_pose_score * scores, int32_t * best);
+/* The same without waiting: scores / best (which must stay valid; R and t may go) are filled when mh_icp_wait returns.  No
+ * other call on the factor until then. */
+int mh_icp_score_poses_async(mh_icp * icp, const double * R, const double * t, size_t n_poses, const mh_icp_score_config * cfg,
+                             mh_pose_score * scores, int32_t * best);
+
+typedef struct mh_icp_reloc_config {
+  mh_icp_score_config score;  /* the coarse pass; top_k >= 1 candidates are refined */
+  mh_icp_align_config align;  /* the refinement of each */
+  double final_gate;          /* m, finite and > 0: the gate of the re-score of the aligned poses (stride 1) */
+} mh_icp_reloc_config;
+
+typedef struct mh_icp_reloc_candidate {
+  int32_t index;              /* into the caller's poses */
+  int32_t iters, converged, reserved; /* of its alignment */
+  mh_pose_score coarse;       /* its score in the coarse pass */
+  double R[9], t[3];          /* the aligned pose (the unaligned one where the alignment ended on the singular path at once) */
+  mh_pose_score fine;         /* the score of the aligned pose: stride 1, gate final_gate */
+} mh_icp_reloc_candidate;
+
+typedef struct mh_icp_reloc_result {
+  int32_t n_candidates;       /* min(top_k, n_poses) */
+  int32_t best;               /* the first of cand[] under the ranking on `fine` (ties: the earlier candidate) */
+  double R[9], t[3];          /* its aligned pose */
+  mh_icp_reloc_candidate cand[MH_RELOC_MAX_REFINE]; /* in the rank order of the coarse pass */
+} mh_icp_reloc_result;
+
+/* Score and select (one wait); for each selected candidate in rank order mh_icp_reset and mh_icp_align from its pose; one more
+ * score call over the aligned poses.  The refusals of mh_icp_score_poses and mh_icp_align apply, and further
+ * MH_ERR_INVALID_ARG for a NULL g_unit or out, score.top_k == 0 and a final_gate that is not finite and > 0.
+ * On return the factor is RESET (its association state is that of a freshly constructed factor) and its linearize count has
+ * advanced by the sum of the candidates' iters. */
+int mh_icp_relocalise(mh_icp * icp, const double * R, const double * t, size_t n_poses, const double g_unit[3],
+                      const mh_icp_reloc_config * cfg, mh_icp_reloc_result * out);
+
 /* ---- fixed-lag window: the smoother's Gauss-Newton loop on the device ---------------------------
  * W unary factors, one pose each, tied by between factors and a prior on the oldest pose: what a caller otherwise writes
  * around mh_icp_linearize_batch — one blocking batch call, a 6W x 6W system assembled and solved on the host, W retractions,

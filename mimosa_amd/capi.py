@@ -25,6 +25,7 @@ EXPORTS = [
     "mh_icp_create", "mh_icp_clone", "mh_icp_destroy", "mh_icp_linearize", "mh_icp_linearize_async",
     "mh_icp_wait", "mh_icp_linearize_batch", "mh_icp_get_state", "mh_icp_reset", "mh_icp_set_components", "mh_icp_size",
     "mh_icp_align", "mh_icp_align_async",
+    "mh_icp_score_poses", "mh_icp_score_poses_async", "mh_icp_relocalise",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
     "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
     "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
@@ -145,6 +146,90 @@ class AlignResult(C.Structure):
 def make_align_config(max_iters=10, eps_rot=1e-6, eps_trans=1e-6, damping=0.0, prior_sigma_rot=0.0, prior_sigma_trans=0.0,
                       check_every=0) -> AlignConfig:
     return AlignConfig(max_iters, eps_rot, eps_trans, damping, prior_sigma_rot, prior_sigma_trans, check_every)
+
+
+MH_RELOC_MAX_POSES = 65536
+MH_RELOC_MAX_REFINE = 8
+
+
+class PoseScore(C.Structure):
+    """mh_pose_score"""
+    _fields_ = [("n_points", C.c_int32), ("n_occupied", C.c_int32), ("n_inliers", C.c_int32), ("reserved", C.c_int32), ("sum_sq", C.c_double)]
+
+    def as_dict(self):
+        return {"n_points": int(self.n_points), "n_occupied": int(self.n_occupied), "n_inliers": int(self.n_inliers), "sum_sq": float(self.sum_sq)}
+
+
+# the same record as a numpy dtype: ICPFactor.score_poses returns its scores as such an array
+POSE_SCORE_DTYPE = np.dtype([("n_points", np.int32), ("n_occupied", np.int32), ("n_inliers", np.int32), ("reserved", np.int32), ("sum_sq", np.float64)])
+
+
+class ScoreConfig(C.Structure):
+    """mh_icp_score_config"""
+    _fields_ = [("gate", C.c_double), ("stride", C.c_int32), ("top_k", C.c_int32)]
+
+
+class RelocConfig(C.Structure):
+    """mh_icp_reloc_config"""
+    _fields_ = [("score", ScoreConfig), ("align", AlignConfig), ("final_gate", C.c_double)]
+
+
+class RelocCandidate(C.Structure):
+    """mh_icp_reloc_candidate"""
+    _fields_ = [("index", C.c_int32), ("iters", C.c_int32), ("converged", C.c_int32), ("reserved", C.c_int32), ("coarse", PoseScore),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("fine", PoseScore)]
+
+
+class RelocResult(C.Structure):
+    """mh_icp_reloc_result"""
+    _fields_ = [("n_candidates", C.c_int32), ("best", C.c_int32), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("cand", RelocCandidate * MH_RELOC_MAX_REFINE)]
+
+    def as_dict(self):
+        n = int(self.n_candidates)
+        return {
+            "n_candidates": n, "best": int(self.best), "R": np.array(self.R).reshape(3, 3), "t": np.array(self.t),
+            "cand": [{"index": int(c.index), "iters": int(c.iters), "converged": int(c.converged), "coarse": c.coarse.as_dict(),
+                      "R": np.array(c.R).reshape(3, 3), "t": np.array(c.t), "fine": c.fine.as_dict()} for c in (self.cand[i] for i in range(n))],
+        }
+
+
+def make_reloc_config(gate=1.0, stride=1, top_k=4, align: AlignConfig = None, final_gate=0.3) -> RelocConfig:
+    return RelocConfig(ScoreConfig(gate, stride, top_k), align if align is not None else make_align_config(), final_gate)
+
+
+def score_key(scores):
+    """The ranking of mh_icp_score_poses as a numpy sort: n_inliers descending, sum_sq ascending, pose index ascending.
+    Returns the pose indices in rank order."""
+    idx = np.arange(len(scores))
+    return np.lexsort((idx, scores["sum_sq"], -scores["n_inliers"].astype(np.int64)))
+
+
+def pose_grid(R0, t0, half_xy, step_xy, half_yaw, step_yaw):
+    """Candidate poses around (R0, t0): translations t0 + (ix * step_xy, iy * step_xy, 0) for ix, iy in -nx .. nx with
+    nx = floor(half_xy / step_xy + 1e-9), and rotations Rz(iw * step_yaw) @ R0 (a yaw about the WORLD z axis, radians) for iw in
+    -nw .. nw with nw = floor(half_yaw / step_yaw + 1e-9).  A step <= 0 gives that axis its centre node alone.
+    Order (the pose index is part of the ranking): yaw slowest, then x, then y fastest, each ascending from its negative end:
+    index = (iw + nw) * (2 nx + 1)^2 + (ix + nx) * (2 nx + 1) + (iy + nx).  Returns (R [n, 3, 3], t [n, 3])."""
+    R0 = np.asarray(R0, np.float64).reshape(3, 3)
+    t0 = np.asarray(t0, np.float64).reshape(3)
+    nx = int(np.floor(half_xy / step_xy + 1e-9)) if step_xy > 0 else 0
+    nw = int(np.floor(half_yaw / step_yaw + 1e-9)) if step_yaw > 0 else 0
+    side = 2 * nx + 1
+    n = (2 * nw + 1) * side * side
+    R = np.empty((n, 3, 3))
+    t = np.empty((n, 3))
+    i = 0
+    for iw in range(-nw, nw + 1):
+        a = iw * step_yaw
+        c, s = np.cos(a), np.sin(a)
+        Rw = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]) @ R0
+        for ix in range(-nx, nx + 1):
+            for iy in range(-nx, nx + 1):
+                R[i] = Rw
+                t[i] = (t0[0] + ix * step_xy, t0[1] + iy * step_xy, t0[2])
+                i += 1
+    return R, t
 
 
 MH_WINDOW_MAX = 16
@@ -620,6 +705,9 @@ def load(build_if_missing: bool = True):
     L.mh_icp_size.argtypes = [vp]
     L.mh_icp_align.argtypes = [vp, vp, vp, vp, C.POINTER(AlignConfig), C.POINTER(AlignResult)]
     L.mh_icp_align_async.argtypes = [vp, vp, vp, vp, C.POINTER(AlignConfig), C.POINTER(AlignResult)]
+    L.mh_icp_score_poses.argtypes = [vp, vp, vp, sz, C.POINTER(ScoreConfig), vp, vp]
+    L.mh_icp_score_poses_async.argtypes = [vp, vp, vp, sz, C.POINTER(ScoreConfig), vp, vp]
+    L.mh_icp_relocalise.argtypes = [vp, vp, vp, sz, vp, C.POINTER(RelocConfig), C.POINTER(RelocResult)]
     L.mh_icp_window_optimise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_optimise_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_wait.argtypes = [vp]
@@ -1239,6 +1327,41 @@ class ICPFactor:
         self._keep.append((out, R, t, g, cfg))
         self.ctx.check(self.L.mh_icp_align_async(self.h, _p(R), _p(t), _p(g), C.byref(cfg), C.byref(out)))
         return out
+
+    def _score_args(self, R, t, gate, stride, top_k, want_scores):
+        R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1, 9))
+        t = np.ascontiguousarray(np.asarray(t, np.float64).reshape(-1, 3))
+        assert len(R) == len(t)
+        cfg = ScoreConfig(gate, stride, top_k)
+        scores = np.zeros(len(R), POSE_SCORE_DTYPE) if want_scores else None
+        best = np.full(MH_RELOC_MAX_REFINE, -2, np.int32) if top_k > 0 else None
+        return R, t, cfg, scores, best
+
+    def score_poses(self, R, t, gate, stride=1, top_k=0, want_scores=True):
+        """mh_icp_score_poses: R [n, 3, 3], t [n, 3].  Returns (scores, best): scores a POSE_SCORE_DTYPE array (None without
+        want_scores: scores = NULL, nothing but the winners is downloaded), best the top_k pose indices in rank order (None for
+        top_k == 0; -1 behind the last pose)."""
+        R, t, cfg, scores, best = self._score_args(R, t, gate, stride, top_k, want_scores)
+        self.ctx.check(self.L.mh_icp_score_poses(self.h, _p(R), _p(t), len(R), C.byref(cfg), _p(scores), _p(best)))
+        return scores, (best[:top_k] if best is not None else None)
+
+    def score_poses_async(self, R, t, gate, stride=1, top_k=0, want_scores=True):
+        """mh_icp_score_poses_async: collected by wait(); the returned arrays (scores, all MH_RELOC_MAX_REFINE entries of best) are
+        filled then."""
+        R, t, cfg, scores, best = self._score_args(R, t, gate, stride, top_k, want_scores)
+        self._keep.append((R, t, cfg, scores, best))
+        self.ctx.check(self.L.mh_icp_score_poses_async(self.h, _p(R), _p(t), len(R), C.byref(cfg), _p(scores), _p(best)))
+        return scores, best
+
+    def relocalise(self, R, t, cfg: RelocConfig, g_unit=(0.0, 0.0, -1.0)) -> dict:
+        """mh_icp_relocalise: score the poses, align the cfg.score.top_k best, re-score; the factor is left reset."""
+        R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1, 9))
+        t = np.ascontiguousarray(np.asarray(t, np.float64).reshape(-1, 3))
+        assert len(R) == len(t)
+        g = _f64(g_unit)
+        out = RelocResult()
+        self.ctx.check(self.L.mh_icp_relocalise(self.h, _p(R), _p(t), len(R), _p(g), C.byref(cfg), C.byref(out)))
+        return out.as_dict()
 
     def set_components(self, enabled: bool):
         """component localizabilities + status histogram (K4) on / off for the following linearize calls"""

@@ -538,6 +538,8 @@ void mh_icp_destroy(mh_icp * icp)
   if (icp->h_ll) AllocCache::free_pinned(icp->h_ll, icp->ll_words * sizeof(uint4) * kMaxPending);
   icp->d_align.release(true);
   if (icp->h_align) AllocCache::free_pinned(icp->h_align, kAlignStageBytes);
+  icp->d_reloc.release(true);
+  if (icp->h_reloc) AllocCache::free_pinned(icp->h_reloc, icp->h_reloc_cap);
   if (icp->events_ready)
     for (auto & ev : icp->events)
       for (auto & e : ev) (void)hipEventDestroy(e);
@@ -571,6 +573,7 @@ static int mh_icp_reset_impl(mh_icp * icp)
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_reset: icp is NULL");
   if (icp->in_window) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: the factor is in a window call in flight");
   if (icp->align.active) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: an alignment is in flight");  // (its books would overwrite the reset)
+  if (icp->score.active) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: a pose scoring call is in flight");
   icp->cold = true;  // the next linearize treats the cached state as all-zero (no memset needed)
   return MH_OK;
 }
@@ -857,6 +860,7 @@ static int mh_icp_wait_impl(mh_icp * icp)
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_wait: icp is NULL");
   if (icp->in_window) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_wait: the factor is in a window call: mh_icp_window_wait collects it");
   if (icp->align.active) return mhi::align_wait(icp);
+  if (icp->score.active) return mhi::score_wait(icp);
   mh_ctx * ctx = icp->ctx;
   MH_HIP(ctx, mh_enter(ctx));
   // Every value a call produces arrives in mapped pinned memory tagged with the call's sequence number: the host polls the

@@ -713,6 +713,19 @@ struct mh_icp
     mh::AlignParams p;
   } align;
   bool in_window = false;  // held by the mh_icp_window_optimise call in flight on its context (which also holds the whole ring)
+  // mh_icp_score_poses (reloc_api.hip): the call's device block [poses | strided cloud | per-workgroup partials | scores]
+  // (d_reloc), its mapped pinned block [winners | poses | scores] (h_reloc), and the call in flight.  Like an alignment it
+  // holds the whole ring (n_pending == kMaxPending) until mh_icp_wait collects it; it touches nothing else of the factor.
+  DevBuf d_reloc;
+  void * h_reloc = nullptr;
+  size_t h_reloc_cap = 0;
+  struct ScoreCall
+  {
+    bool active = false;
+    size_t n_poses = 0;
+    mh_pose_score * scores = nullptr;
+    int32_t * best = nullptr;
+  } score;
 };
 
 // The window call on ctx is over (collected, or abandoned behind a drained stream): its factors are free again.
@@ -761,4 +774,6 @@ int chain_k3_block(mh_icp * icp, const double R[9], const double t[3], const dou
 // is in flight
 std::vector<LaunchGroup> window_launch_groups(mh_icp * const * icps, size_t n_factors);
 int align_wait(mh_icp * icp);
+// reloc_api.hip: mh_icp_wait on a factor whose mh_icp_score_poses_async is in flight
+int score_wait(mh_icp * icp);
 }  // namespace mhi

@@ -592,6 +592,135 @@ public:
     return out;
   }
 
+  // Relocalisation (no counterpart in the reference): candidate poses of this factor's cloud scored against its map in one chain
+  // of launches and ranked on the device (mh_icp_score_poses), and the few best refined with align() (mh_icp_relocalise).  For
+  // the caller who has no pose inside the association gate yet.
+  struct ScoreConfig
+  {
+    double gate = 1.0;  // m
+    int stride = 1;     // every stride-th point, counted in the order the cloud was given
+    int top_k = 0;      // winners selected on the device (0 .. MH_RELOC_MAX_REFINE)
+  };
+  struct ScoreResult
+  {
+    std::vector<mh_pose_score> scores;  // one per pose; empty when they were not asked for
+    std::vector<int> best;              // top_k pose indices in rank order (fewer when there are fewer poses)
+  };
+  ScoreResult scorePoses(const std::vector<Pose3> & poses, const ScoreConfig & config, bool want_scores = true)
+  {
+    ScoreCall call = scorePosesBegin(poses, config, want_scores, false);
+    return call.take();
+  }
+  // The same without waiting: wait() collects it (mh_icp_wait).  No other call on the factor until then; the call object must
+  // outlive the wait.
+  class ScoreCall
+  {
+  public:
+    ScoreResult wait()
+    {
+      if (pending_) {
+        pending_ = false;
+        owner_->ctx().check(mh_icp_wait(owner_->icp_), "mh_icp_wait");
+      }
+      return take();
+    }
+
+  private:
+    friend class ICPFactor;
+    ScoreResult take()
+    {
+      ScoreResult r;
+      r.scores = *scores_;
+      for (int i = 0; i < top_k_ && (*best_)[static_cast<size_t>(i)] >= 0; ++i) r.best.push_back((*best_)[static_cast<size_t>(i)]);
+      return r;
+    }
+    ICPFactor * owner_ = nullptr;
+    bool pending_ = false;
+    int top_k_ = 0;
+    // on the heap: the library writes into them when the call is collected, wherever the call object has moved to
+    std::unique_ptr<std::vector<mh_pose_score>> scores_;
+    std::unique_ptr<std::array<int32_t, MH_RELOC_MAX_REFINE>> best_;
+  };
+  ScoreCall scorePosesAsync(const std::vector<Pose3> & poses, const ScoreConfig & config, bool want_scores = true)
+  {
+    return scorePosesBegin(poses, config, want_scores, true);
+  }
+
+  struct RelocConfig
+  {
+    ScoreConfig score{1.0, 4, 4};
+    AlignConfig align;
+    double final_gate = 0.1;  // m: the gate of the re-score of the aligned poses (every point)
+  };
+  struct RelocCandidate
+  {
+    int index = -1, iters = 0;
+    bool converged = false;
+    mh_pose_score coarse{}, fine{};
+    Pose3 pose;  // aligned
+  };
+  struct RelocResult
+  {
+    Pose3 pose;    // the winner's aligned pose
+    int best = -1; // into candidates
+    std::vector<RelocCandidate> candidates;  // in the rank order of the coarse pass
+  };
+  // The factor is left reset (its association state is a freshly constructed factor's); getLinearizeCount() has advanced by the
+  // iterations the alignments ran.
+  RelocResult relocalise(const std::vector<Pose3> & poses, const Unit3 & g, const RelocConfig & config)
+  {
+    std::vector<double> R, t;
+    flattenPoses(poses, R, t);
+    const A3 gu = toArray(g.unitVector());
+    mh_icp_reloc_config c;
+    c.score = scoreConfig(config.score);
+    c.align = alignConfig(config.align);
+    c.final_gate = config.final_gate;
+    std::unique_ptr<mh_icp_reloc_result> r(new mh_icp_reloc_result);
+    ctx().check(mh_icp_relocalise(icp_, R.data(), t.data(), poses.size(), gu.data(), &c, r.get()), "mh_icp_relocalise");
+    RelocResult out;
+    out.pose = pose3(r->R, r->t);
+    out.best = r->best;
+    for (int i = 0; i < r->n_candidates; ++i) {
+      const mh_icp_reloc_candidate & q = r->cand[i];
+      RelocCandidate k;
+      k.index = q.index;
+      k.iters = q.iters;
+      k.converged = q.converged != 0;
+      k.coarse = q.coarse;
+      k.fine = q.fine;
+      k.pose = pose3(q.R, q.t);
+      last_.linearize_count += q.iters;  // what getLinearizeCount() reports: the library's count moved with the alignments
+      out.candidates.push_back(k);
+    }
+    return out;
+  }
+  // Candidate poses around T0: translations T0.t + (ix step_xy, iy step_xy, 0), ix, iy in -nx .. nx with nx = floor(half_xy /
+  // step_xy + 1e-9), and rotations Rz(iw step_yaw) T0.R (a yaw about the WORLD z axis, radians), iw in -nw .. nw with nw =
+  // floor(half_yaw / step_yaw + 1e-9); a step <= 0 gives that axis its centre node alone.  Order (the pose index is part of the
+  // ranking): yaw slowest, then x, then y fastest, each ascending from its negative end — the enumeration of capi.pose_grid.
+  static std::vector<Pose3> poseGrid(const Pose3 & T0, double half_xy, double step_xy, double half_yaw, double step_yaw)
+  {
+    const PoseRM T = rowMajor(T0);
+    const int nx = step_xy > 0.0 ? static_cast<int>(std::floor(half_xy / step_xy + 1e-9)) : 0;
+    const int nw = step_yaw > 0.0 ? static_cast<int>(std::floor(half_yaw / step_yaw + 1e-9)) : 0;
+    std::vector<Pose3> out;
+    out.reserve(static_cast<size_t>(2 * nw + 1) * static_cast<size_t>(2 * nx + 1) * static_cast<size_t>(2 * nx + 1));
+    for (int iw = -nw; iw <= nw; ++iw) {
+      const double a = iw * step_yaw, c = std::cos(a), s = std::sin(a);
+      const double Rz[9] = {c, -s, 0.0, s, c, 0.0, 0.0, 0.0, 1.0};
+      double Rw[9];
+      for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) Rw[3 * r + k] = (Rz[3 * r] * T.R[k] + Rz[3 * r + 1] * T.R[3 + k]) + Rz[3 * r + 2] * T.R[6 + k];
+      for (int ix = -nx; ix <= nx; ++ix)
+        for (int iy = -nx; iy <= nx; ++iy) {
+          const double tt[3] = {T.t[0] + ix * step_xy, T.t[1] + iy * step_xy, T.t[2]};
+          out.push_back(pose3(Rw, tt));
+        }
+    }
+    return out;
+  }
+
   // The smoother's loop over a window of unary factors (no counterpart in the reference, which leaves it to ISAM2): linearize
   // every factor, assemble the block-tridiagonal system of the factors, the between factors and the prior on the oldest pose,
   // solve, retract every pose — as one chain of launches on the device, one wait (mh_icp_window_optimise).
@@ -939,6 +1068,56 @@ private:
                 "mh_icp_create");
   }
   const Context & ctx() const { return *ivox_target_->context(); }
+  static void flattenPoses(const std::vector<Pose3> & poses, std::vector<double> & R, std::vector<double> & t)
+  {
+    R.resize(9 * poses.size());
+    t.resize(3 * poses.size());
+    for (size_t i = 0; i < poses.size(); ++i) {
+      const PoseRM T = rowMajor(poses[i]);
+      std::memcpy(&R[9 * i], T.R.data(), 72);
+      std::memcpy(&t[3 * i], T.t.data(), 24);
+    }
+  }
+  static mh_icp_score_config scoreConfig(const ScoreConfig & config)
+  {
+    mh_icp_score_config c;
+    c.gate = config.gate;
+    c.stride = config.stride;
+    c.top_k = config.top_k;
+    return c;
+  }
+  static mh_icp_align_config alignConfig(const AlignConfig & config)
+  {
+    mh_icp_align_config c;
+    c.max_iters = config.max_iters;
+    c.eps_rot = config.eps_rot;
+    c.eps_trans = config.eps_trans;
+    c.damping = config.damping;
+    c.prior_sigma_rot = config.prior_sigma_rot;
+    c.prior_sigma_trans = config.prior_sigma_trans;
+    c.check_every = config.check_every;
+    return c;
+  }
+  ScoreCall scorePosesBegin(const std::vector<Pose3> & poses, const ScoreConfig & config, bool want_scores, bool async)
+  {
+    std::vector<double> R, t;
+    flattenPoses(poses, R, t);  // (the library has copied the poses when the call returns)
+    const mh_icp_score_config c = scoreConfig(config);
+    ScoreCall call;
+    call.owner_ = this;
+    call.top_k_ = config.top_k;
+    call.scores_.reset(new std::vector<mh_pose_score>(want_scores ? poses.size() : 0));
+    call.best_.reset(new std::array<int32_t, MH_RELOC_MAX_REFINE>());
+    call.best_->fill(-1);
+    mh_pose_score * s = want_scores ? call.scores_->data() : nullptr;
+    if (async) {
+      ctx().check(mh_icp_score_poses_async(icp_, R.data(), t.data(), poses.size(), &c, s, call.best_->data()), "mh_icp_score_poses_async");
+      call.pending_ = true;
+    } else {
+      ctx().check(mh_icp_score_poses(icp_, R.data(), t.data(), poses.size(), &c, s, call.best_->data()), "mh_icp_score_poses");
+    }
+    return call;
+  }
   static std::unique_ptr<WindowCall> startWindow(const std::vector<Ptr> & factors, const std::vector<Pose3> & poses, const std::vector<WindowBetween> & between,
                                                  const Unit3 & g, const WindowConfig & config, bool blocking, const WindowRelin * relin = nullptr,
                                                  const std::vector<WindowLinear> * linear = nullptr, const std::vector<WindowEdge> * edges = nullptr,

@@ -70,6 +70,19 @@ class ReplayConfig:
     # propagated first guess) before its factor goes to the smoother.  HIP backend and the native FixedLagReplay only
     init_align: bool = False
     init_align_iters: int = 10
+    # the first scan's pose comes from mh_icp_relocalise instead of from first_state's truth-based guess: the propagated first
+    # guess is displaced by relocalise_guess_offset (m, world frame) and relocalise_guess_yaw_deg (about the world z axis) — further
+    # than the association gate reaches — and candidate poses on a grid around THAT pose (capi.pose_grid: +-half_xy in steps of
+    # step_xy, +-half_yaw in steps of step_yaw) are scored against the map, the best aligned and re-scored.  The sweep itself is
+    # deskewed from first_state as before (the motion within a sweep, not where it is); every later scan is unchanged.
+    # HipBackend only; the native replay has no such switch
+    relocalise_first: bool = False
+    relocalise_half_xy: float = 2.0
+    relocalise_step_xy: float = 0.5
+    relocalise_half_yaw_deg: float = 30.0
+    relocalise_step_yaw_deg: float = 7.5
+    relocalise_guess_offset: tuple = (1.2, -0.9, 0.0)   # 1.5 m
+    relocalise_guess_yaw_deg: float = 20.0
     # the smoother's update_iters iterations run as ONE chain of launches on the device (mh_icp_window_optimise: linearize,
     # assembly, block-tridiagonal solve, retraction) instead of a batched linearize, a numpy solve and the retractions per
     # iteration.  Without the photometric factor only; HIP backend and the native FixedLagReplay
@@ -334,6 +347,16 @@ class HipBackend:
         r = f.align(R, t, self.capi.make_align_config(max_iters=max_iters, eps_rot=1e-6, eps_trans=1e-6, damping=1e-9))
         return r["R"], r["t"]
 
+    def relocalise_first(self, f, R, t, cfg: "ReplayConfig"):
+        """relocalise_first: the pose of the factor's scan from a grid of candidates around the (wrong) guess (R, t); the factor
+        comes back reset, as fresh as make_factor left it.  Returns (R, t, the call's result)"""
+        Rs, ts = self.capi.pose_grid(R, t, cfg.relocalise_half_xy, cfg.relocalise_step_xy, np.deg2rad(cfg.relocalise_half_yaw_deg),
+                                     np.deg2rad(cfg.relocalise_step_yaw_deg))
+        align = self.capi.make_align_config(max_iters=30, eps_rot=1e-6, eps_trans=1e-6, damping=1e-9)
+        rc = self.capi.make_reloc_config(gate=self.regd["max_corres_distance"], stride=4, top_k=4, align=align, final_gate=0.1)
+        r = f.relocalise(Rs, ts, rc)
+        return r["R"], r["t"], r
+
     def make_photo_factor(self):
         return self.photo.make_factor() if self.photo is not None and self.photo.features() else None
 
@@ -495,6 +518,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
     if cfg.window_photo_linear and not cfg.device_window:
         raise RuntimeError("window_photo_linear is only offered with device_window")
     _check_window_marginal(cfg, RuntimeError)
+    if cfg.relocalise_first:
+        raise RuntimeError("relocalise_first is only offered by the python replay with HipBackend")
     exe = build.build_replay_native()
     path = os.path.join(workdir, "replay_input.bin")
     write_native_input(path, cfg, scans, rng_seed)
@@ -541,6 +566,11 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         raise ValueError("device_window needs a backend with mh_icp_window_optimise (HipBackend)")
     if cfg.init_align and not hasattr(backend, "align_first"):
         raise ValueError("init_align needs a backend with mh_icp_align (HipBackend)")
+    if cfg.relocalise_first and not hasattr(backend, "relocalise_first"):
+        raise ValueError("relocalise_first needs a backend with mh_icp_relocalise (HipBackend)")
+    if cfg.relocalise_first and cfg.init_align:
+        raise ValueError("relocalise_first aligns the first scan itself: not offered together with init_align")
+    relocalised = None
     backend.seed_map(synth.make_room(synth.BASE_SEED, 0, 0, room=np.asarray(cfg.room)))
     stage = {"front_end": 0.0, "imu": 0.0, "factor_create": 0.0, "optimise": 0.0, "update_map": 0.0}
     v_body = np.asarray(cfg.v, float)
@@ -587,6 +617,12 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         R_w, t_w = R_pred, p_pred
         if cfg.init_align and R_prev is None:
             R_w, t_w = backend.align_first(f, R_pred, p_pred, cfg.init_align_iters)
+        if cfg.relocalise_first and R_prev is None:
+            R_guess = synth.rot_z(np.deg2rad(cfg.relocalise_guess_yaw_deg)) @ R_pred
+            t_guess = p_pred + np.asarray(cfg.relocalise_guess_offset, float)
+            R_w, t_w, rr = backend.relocalise_first(f, R_guess, t_guess, cfg)
+            relocalised = dict(guess=(R_guess, t_guess), pose=(R_w, t_w), predicted=(R_pred, p_pred), best=rr["best"],
+                               candidates=[c["index"] for c in rr["cand"]], fine=[c["fine"] for c in rr["cand"]])
         win.append(dict(k=k, R=R_w, t=t_w, f=f, Z=Z, pf=pf if cfg.photo_window else None))
         if len(win) > cfg.window:
             if cfg.window_marginal or cfg.window_marginal_joint:
@@ -761,4 +797,4 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     rerr = [float(np.rad2deg(np.linalg.norm(_so3_log(Re.T @ s["R_gt"])))) for (Re, _), s in zip(est, scans)]
     return {"poses_est": est, "trans_err": terr, "rot_err_deg": rerr, "n_keyframes": n_kf, "seconds": total,
             "scans_per_s": len(scans) / total, "stage_s": stage, "costs": costs, "photo_valid": n_photo_valid,
-            "photo_in_window": n_photo_window, "marginal_valid": marginal_valid, "separator_sizes": separator_sizes}
+            "photo_in_window": n_photo_window, "marginal_valid": marginal_valid, "separator_sizes": separator_sizes, "relocalised": relocalised}
