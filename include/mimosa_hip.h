@@ -319,6 +319,38 @@ int mh_icp_align(mh_icp * icp, const double R0[9], const double t0[3], const dou
 int mh_icp_align_async(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3],
                        const mh_icp_align_config * cfg, mh_icp_align_result * out);
 
+/* ---- several alignments side by side: one chain for B (factor, start pose) pairs ----------------
+ * B independent alignments, member i from (R0 + 9 i, t0 + 3 i); out[i] is member i's result.  Each is exactly the
+ * mh_icp_align chain of that factor under cfg: the same H_ss, b_s, the degeneracy quirk, the prior on the step's own pose,
+ * damping, the singular rule and the trace rows.  One cfg serves all members; the degeneracy thresholds, reg_4_dof and
+ * project_on_degneneracy are each factor's own.  Nothing ties the members to each other: this is not a window.
+ * Per iteration: the batch's K3 launches (component pass off; launch groups and launch classes chosen as
+ * mh_icp_window_optimise chooses them for the same factors, i.e. by the batch's total point count — where that moves a
+ * member to another class than a call of its own, its rows are added in another order, see mh_icp_linearize_batch), then ONE
+ * step launch of B one-wave workgroups.  Member i's workgroup advances member i alone, writes its next pose into its
+ * argument block of the next iteration and publishes its sums and trace row to the factor's own pinned ring.
+ * Stopping is per member: one that converged or met a singular system evaluates nothing more (its later K3 blocks get
+ * n = 0), its association state stays as its last evaluated pose left it, its linearize count advances by its own iters, its
+ * result is what mh_icp_align gives (a singular member: MH_OK, converged = 0, bit 4 in its last row); the others go on.
+ * check_every: iterations queued per host look; the host stops queueing once EVERY member's row carries the stop bit.  The
+ * result does not depend on it.  The return value is MH_OK or the first member's error (a HIP failure).
+ * Refused with nothing enqueued and every factor usable afterwards — MH_ERR_INVALID_ARG: a NULL argument or member, B
+ * outside 1 .. MH_ALIGN_BATCH_MAX, the same factor twice, factors of different contexts, a member with a call in flight or
+ * without points, a batch call already in flight on the context, the cfg ranges of mh_icp_align; MH_ERR_UNSUPPORTED: binary
+ * factors and the factors of the map-sharded path.
+ * While a call is in flight its members hold their whole ring: mh_icp_reset and mh_icp_wait refuse them, every other entry
+ * point refuses them as factors with calls in flight.  Destroying a member inside a call nobody waited for abandons the call
+ * as a whole. */
+#define MH_ALIGN_BATCH_MAX 16
+int mh_icp_align_batch(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3],
+                       const mh_icp_align_config * cfg, mh_icp_align_result * out);
+/* The same without waiting: out[] (which must stay valid; the other arguments may go) is filled by
+ * mh_icp_align_batch_wait.  No other call on a member until then. */
+int mh_icp_align_batch_async(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3],
+                             const mh_icp_align_config * cfg, mh_icp_align_result * out);
+/* Collects the one batch call in flight on the context (MH_ERR_INVALID_ARG when there is none). */
+int mh_icp_align_batch_wait(mh_ctx * ctx);
+
 /* ---- relocalisation: score candidate poses against the map, refine the best ---------------------
  * Every call above wants a pose that already lies inside the association gate.  These two serve the caller who has none: up to
  * MH_RELOC_MAX_POSES candidate poses of the factor's cloud are scored against its map in one chain of launches and ranked on
@@ -389,6 +421,19 @@ typedef struct mh_icp_reloc_result {
  * advanced by the sum of the candidates' iters. */
 int mh_icp_relocalise(mh_icp * icp, const double * R, const double * t, size_t n_poses, const double g_unit[3],
                       const mh_icp_reloc_config * cfg, mh_icp_reloc_result * out);
+/* mh_icp_relocalise with the candidates aligned side by side: candidate c, in rank order, is aligned on work[c], which the
+ * call resets first, and all candidates run in ONE mh_icp_align_batch.  Score, re-score, ranking and *out are as above (a
+ * candidate's launch class follows the batch's total point count, so its aligned pose agrees with mh_icp_relocalise's to
+ * rounding, ~1e-13 relative in the sums, not in bits).
+ * work[]: n_work >= min(score.top_k, n_poses) clones of icp made by the caller with mh_icp_clone (a clone carries the
+ * identity of its source's cloud; every created factor has a fresh one).  MH_ERR_INVALID_ARG for too few, for a NULL entry, an
+ * entry twice, icp itself, an entry whose cloud identity, size, map or mh_reg_config differ from icp's, and an entry with a
+ * call in flight; the refusals of mh_icp_relocalise and mh_icp_align_batch apply.  Nothing is enqueued then.
+ * The one difference from mh_icp_relocalise: icp is only READ — its association state, linearize count and results do not
+ * move (it is not reset).  The work[] factors that took a candidate are left as their alignments left them, and their
+ * linearize counts advance by their own iters. */
+int mh_icp_relocalise_batch(mh_icp * icp, mh_icp * const * work, size_t n_work, const double * R, const double * t,
+                            size_t n_poses, const double g_unit[3], const mh_icp_reloc_config * cfg, mh_icp_reloc_result * out);
 
 /* ---- fixed-lag window: the smoother's Gauss-Newton loop on the device ---------------------------
  * W unary factors, one pose each, tied by between factors and a prior on the oldest pose: what a caller otherwise writes

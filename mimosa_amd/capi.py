@@ -25,7 +25,8 @@ EXPORTS = [
     "mh_icp_create", "mh_icp_clone", "mh_icp_destroy", "mh_icp_linearize", "mh_icp_linearize_async",
     "mh_icp_wait", "mh_icp_linearize_batch", "mh_icp_get_state", "mh_icp_reset", "mh_icp_set_components", "mh_icp_size",
     "mh_icp_align", "mh_icp_align_async",
-    "mh_icp_score_poses", "mh_icp_score_poses_async", "mh_icp_relocalise",
+    "mh_icp_align_batch", "mh_icp_align_batch_async", "mh_icp_align_batch_wait",
+    "mh_icp_score_poses", "mh_icp_score_poses_async", "mh_icp_relocalise", "mh_icp_relocalise_batch",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
     "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
     "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
@@ -148,6 +149,7 @@ def make_align_config(max_iters=10, eps_rot=1e-6, eps_trans=1e-6, damping=0.0, p
     return AlignConfig(max_iters, eps_rot, eps_trans, damping, prior_sigma_rot, prior_sigma_trans, check_every)
 
 
+MH_ALIGN_BATCH_MAX = 16
 MH_RELOC_MAX_POSES = 65536
 MH_RELOC_MAX_REFINE = 8
 
@@ -708,6 +710,10 @@ def load(build_if_missing: bool = True):
     L.mh_icp_score_poses.argtypes = [vp, vp, vp, sz, C.POINTER(ScoreConfig), vp, vp]
     L.mh_icp_score_poses_async.argtypes = [vp, vp, vp, sz, C.POINTER(ScoreConfig), vp, vp]
     L.mh_icp_relocalise.argtypes = [vp, vp, vp, sz, vp, C.POINTER(RelocConfig), C.POINTER(RelocResult)]
+    L.mh_icp_align_batch.argtypes = [vp, sz, vp, vp, vp, C.POINTER(AlignConfig), vp]
+    L.mh_icp_align_batch_async.argtypes = L.mh_icp_align_batch.argtypes
+    L.mh_icp_align_batch_wait.argtypes = [vp]
+    L.mh_icp_relocalise_batch.argtypes = [vp, vp, sz, vp, vp, sz, vp, C.POINTER(RelocConfig), C.POINTER(RelocResult)]
     L.mh_icp_window_optimise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_optimise_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_wait.argtypes = [vp]
@@ -1092,6 +1098,41 @@ def linearize_batch(factors, Rs, ts, g_units=None, R_tgts=None, t_tgts=None) -> 
     return [out[i].as_dict() for i in range(n)]
 
 
+class AlignBatchCall:
+    """an mh_icp_align_batch_async call in flight: wait() collects it and returns the list of results"""
+
+    def __init__(self, ctx, keep, out):
+        self.ctx, self._keep, self.out = ctx, keep, out
+
+    def wait(self) -> list:
+        self.ctx.check(self.ctx.L.mh_icp_align_batch_wait(self.ctx.h))
+        res = [r.as_dict() for r in self.out]
+        self._keep = None
+        return res
+
+
+def align_batch(factors, poses, cfg: AlignConfig, g_unit=(0.0, 0.0, -1.0), wait=True):
+    """mh_icp_align_batch: the alignments of `factors`, member i from poses[i] = (R, t), side by side in one chain of launches.
+    Returns the list of the dicts ICPFactor.align returns, one per member.  wait=False: mh_icp_align_batch_async; returns an
+    AlignBatchCall whose wait() gives the same list."""
+    B = len(factors)
+    if B == 0:
+        raise ValueError("align_batch: no factor")
+    if len(poses) != B:
+        raise ValueError("align_batch: one start pose per factor")
+    ctx = factors[0].ctx
+    R = np.ascontiguousarray(np.array([np.asarray(p[0], np.float64).reshape(9) for p in poses]))
+    t = np.ascontiguousarray(np.array([np.asarray(p[1], np.float64).reshape(3) for p in poses]))
+    g = _f64(g_unit)
+    handles = (C.c_void_p * B)(*[f.h for f in factors])
+    out = (AlignResult * B)()
+    if not wait:
+        ctx.check(ctx.L.mh_icp_align_batch_async(handles, B, _p(R), _p(t), _p(g), C.byref(cfg), out))
+        return AlignBatchCall(ctx, (handles, R, t, g, cfg), out)
+    ctx.check(ctx.L.mh_icp_align_batch(handles, B, _p(R), _p(t), _p(g), C.byref(cfg), out))
+    return [r.as_dict() for r in out]
+
+
 class WindowCall:
     """an mh_icp_window_optimise_async call in flight: wait() collects it and returns the result"""
 
@@ -1273,6 +1314,7 @@ class ICPFactor:
 
     def __init__(self, ctx: Context, map_: VoxelMap, pts, cfg: RegConfig, binary=False, _h=None, _n=None):
         self.ctx, self.L, self.map = ctx, ctx.L, map_
+        self._reloc_work = []  # relocalise(batch=True): the clones its candidates are aligned on
         ctx._children += 1
         if _h is not None:
             self.h, self.n = _h, _n
@@ -1353,13 +1395,22 @@ class ICPFactor:
         self.ctx.check(self.L.mh_icp_score_poses_async(self.h, _p(R), _p(t), len(R), C.byref(cfg), _p(scores), _p(best)))
         return scores, best
 
-    def relocalise(self, R, t, cfg: RelocConfig, g_unit=(0.0, 0.0, -1.0)) -> dict:
-        """mh_icp_relocalise: score the poses, align the cfg.score.top_k best, re-score; the factor is left reset."""
+    def relocalise(self, R, t, cfg: RelocConfig, g_unit=(0.0, 0.0, -1.0), batch=False) -> dict:
+        """mh_icp_relocalise: score the poses, align the cfg.score.top_k best, re-score; the factor is left reset.
+        batch=True: mh_icp_relocalise_batch — the candidates are aligned side by side on clones of this factor, which are made
+        on first use, kept on this object and destroyed with it (or by release_reloc_work()); this factor is only read."""
         R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1, 9))
         t = np.ascontiguousarray(np.asarray(t, np.float64).reshape(-1, 3))
         assert len(R) == len(t)
         g = _f64(g_unit)
         out = RelocResult()
+        if batch:
+            work = self._reloc_work
+            while len(work) < min(int(cfg.score.top_k), len(R)):
+                work.append(self.clone())
+            handles = (C.c_void_p * max(len(work), 1))(*[w.h for w in work])
+            self.ctx.check(self.L.mh_icp_relocalise_batch(self.h, handles, len(work), _p(R), _p(t), len(R), _p(g), C.byref(cfg), C.byref(out)))
+            return out.as_dict()
         self.ctx.check(self.L.mh_icp_relocalise(self.h, _p(R), _p(t), len(R), _p(g), C.byref(cfg), C.byref(out)))
         return out.as_dict()
 
@@ -1374,7 +1425,14 @@ class ICPFactor:
         self.ctx.check(self.L.mh_icp_get_state(self.h, _p(st), _p(means), _p(normals)))
         return st, means, normals
 
+    def release_reloc_work(self):
+        """destroy the clones relocalise(batch=True) made; the next such call makes new ones"""
+        work, self._reloc_work = getattr(self, "_reloc_work", []), []
+        for w in work:
+            w.destroy()
+
     def destroy(self):
+        self.release_reloc_work()
         if getattr(self, "h", None):
             self.L.mh_icp_destroy(self.h)
             self.h = None

@@ -296,5 +296,15 @@ struct AlignStepArgs
   unsigned int seq;      // tags K3's words and everything this step publishes
 };
 hipError_t launch_align_step(const AlignStepArgs & a, hipStream_t stream);
+
+// align_kernels.hip — one step of an mh_icp_align_batch chain: workgroup m is the step above for member m, on m[m] alone.  The
+// members' arguments travel in the kernel-argument segment.
+constexpr int kAlignBatchMax = 16;
+struct AlignBatchStepArgs
+{
+  AlignStepArgs m[kAlignBatchMax];
+};
+static_assert(sizeof(AlignBatchStepArgs) <= 3072, "mh_icp_align_batch: the step's arguments ride in the kernel-argument segment");
+hipError_t launch_align_batch_step(const AlignBatchStepArgs & a, int n_members, hipStream_t stream);
 }  // namespace mh
 #endif

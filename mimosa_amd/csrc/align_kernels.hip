@@ -7,6 +7,10 @@
 // Lanes: 0 and 1 decompose the rotation and the translation block side by side (the two eigen problems are the longest
 // dependent chains of the step), lane 0 solves and retracts, lanes 0..31 forward the words.  Everything is fp64; the file is
 // compiled without floating-point contraction so that the host build of align_device.hpp gives the same digits.
+//
+// icp_align_batch_step_kernel: the same step for the B members of an mh_icp_align_batch chain in one launch, one one-wave
+// workgroup per member.  The members share nothing — no barrier across workgroups, no atomics: workgroup m reads and writes
+// what member m's arguments point at.
 #include <hip/hip_runtime.h>
 
 #include "align_device.hpp"
@@ -14,11 +18,9 @@
 
 namespace mh
 {
-__global__ __launch_bounds__(64) void icp_align_step_kernel(const AlignStepArgs a)
+// one wave, one chain: what both kernels run
+__device__ __forceinline__ void align_step_wave(const AlignStepArgs & a, double * s_sum, double * s_row, int * s_stop)
 {
-  __shared__ double s_sum[32];
-  __shared__ double s_row[kRowWords];
-  __shared__ int s_stop;
   const int lane = static_cast<int>(threadIdx.x);
 
   // K3's words of this iteration (written by the kernel in front of this one on the stream: ordinary loads)
@@ -38,7 +40,7 @@ __global__ __launch_bounds__(64) void icp_align_step_kernel(const AlignStepArgs 
 
   if (lane == 0) {
     AlignState st = *a.state;
-    s_stop = align_advance(st, s_sum, !missing, a.p, (dm & 1ull) != 0, (dm & 2ull) != 0, s_row) & 1;
+    *s_stop = align_advance(st, s_sum, !missing, a.p, (dm & 1ull) != 0, (dm & 2ull) != 0, s_row) & 1;
     *a.state = st;
   }
   __syncthreads();
@@ -48,16 +50,39 @@ __global__ __launch_bounds__(64) void icp_align_step_kernel(const AlignStepArgs 
   if (a.next) {
     if (lane < 9) a.next->R[lane] = s_row[kRowR + lane];
     if (lane >= 16 && lane < 19) a.next->t[lane - 16] = s_row[kRowT + lane - 16];
-    if (lane == 32 && s_stop) a.next->n = 0;
+    if (lane == 32 && *s_stop) a.next->n = 0;
   }
   // to the host: the sums + counters of an evaluated iteration, then the row
   if (lane < 32 && !frozen && !missing) ll_store(a.ll_host + lane, s_sum[lane], a.seq);
   if (lane < kRowWords) ll_store(a.ll_host + kLlSums + lane, s_row[lane], a.seq);
 }
 
+__global__ __launch_bounds__(64) void icp_align_step_kernel(const AlignStepArgs a)
+{
+  __shared__ double s_sum[32];
+  __shared__ double s_row[kRowWords];
+  __shared__ int s_stop;
+  align_step_wave(a, s_sum, s_row, &s_stop);
+}
+
+__global__ __launch_bounds__(64) void icp_align_batch_step_kernel(const AlignBatchStepArgs b)
+{
+  __shared__ double s_sum[32];
+  __shared__ double s_row[kRowWords];
+  __shared__ int s_stop;
+  align_step_wave(b.m[blockIdx.x], s_sum, s_row, &s_stop);  // (the grid is the number of members: launch_align_batch_step)
+}
+
 hipError_t launch_align_step(const AlignStepArgs & a, hipStream_t stream)
 {
   hipLaunchKernelGGL(icp_align_step_kernel, dim3(1), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_align_batch_step(const AlignBatchStepArgs & a, int n_members, hipStream_t stream)
+{
+  if (n_members < 1 || n_members > kAlignBatchMax) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(icp_align_batch_step_kernel, dim3(n_members), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

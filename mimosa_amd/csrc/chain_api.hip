@@ -1,7 +1,9 @@
-// The device-chain drivers of the C ABI (include/mimosa_hip.h): mh_icp_align[_async], mh_icp_window_optimise[_async],
-// mh_icp_window_optimise_relin[_async], mh_icp_window_optimise_lin[_async], mh_icp_window_optimise_edges[_async],
-// mh_icp_window_marginalise[_async], mh_icp_window_optimise_joint[_async], mh_icp_window_marginalise_joint[_async] and mh_icp_window_wait.  A chain is K3 (icp_kernels.hip), a step kernel (align_kernels.hip, window_kernels.hip,
-// window_relin_kernels.hip, window_lin_kernels.hip, window_edge_kernels.hip, window_joint_kernels.hip; window_marginal_kernels.hip and window_joint_kernels.hip for the marginals),
+// The device-chain drivers of the C ABI (include/mimosa_hip.h): mh_icp_align[_async], mh_icp_align_batch[_async|_wait],
+// mh_icp_window_optimise[_async], mh_icp_window_optimise_relin[_async], mh_icp_window_optimise_lin[_async],
+// mh_icp_window_optimise_edges[_async], mh_icp_window_marginalise[_async], mh_icp_window_optimise_joint[_async],
+// mh_icp_window_marginalise_joint[_async] and mh_icp_window_wait.  A chain is K3 (icp_kernels.hip), a step kernel
+// (align_kernels.hip, window_kernels.hip, window_relin_kernels.hip, window_lin_kernels.hip, window_edge_kernels.hip,
+// window_joint_kernels.hip; window_marginal_kernels.hip and window_joint_kernels.hip for the marginals),
 // K3, step ... on the context's stream with one wait at its
 // end; every step publishes a row of flagged words the host reads.  What the two families share is written once at the top;
 // argument checks, staging layout, the step launch and the decoding of a row are each family's own.  The factor handle,
@@ -289,16 +291,18 @@ static int align_enqueue(mh_icp * icp, int upto)
   return MH_OK;
 }
 
-// every queued iteration has run (the caller waited for the last row): the result, and the handle's books
-static int align_finish(mh_icp * icp)
+// The result of one alignment whose queued iterations have run, for mh_icp_align and for a member of mh_icp_align_batch: the
+// factor's rows (tagged seq[i]) decoded into *out, first / last from the host epilogue.  lost: a row did not arrive or no
+// iteration was evaluated — the caller abandons its call; otherwise the caller moves the handle's books by out->iters.
+static int align_collect(mh_icp * icp, const unsigned int * seq, int queued, const double R0[9], const double gz[3], int count0, mh_icp_align_result * out,
+                         const char * what, bool & lost)
 {
   mh_ctx * ctx = icp->ctx;
-  mh_icp::AlignCall & c = icp->align;
-  mh_icp_align_result * out = c.out;
   std::memset(static_cast<void *>(out), 0, sizeof(*out));
   int iters = 0, converged = 0;
   double row_buf[mh::kRowWords];
-  const int rc = chain_trace(ctx, align_rows(icp), c.queued, mh::kRowFlags, "mh_icp_align", row_buf, 0, [&](int i, const double * row) {
+  const ChainRows rows{icp->h_ll + mh::kLlSums, icp->ll_words, mh::kRowWords, seq};
+  const int rc = chain_trace(ctx, rows, queued, mh::kRowFlags, what, row_buf, 0, [&](int i, const double * row) {
     mh_icp_align_trace & tr = out->trace[i];
     tr.f = row[mh::kRowF];
     tr.step_rot = row[mh::kRowStepRot];
@@ -308,12 +312,10 @@ static int align_finish(mh_icp * icp)
     std::memcpy(tr.R, row + mh::kRowR, sizeof(tr.R));
     std::memcpy(tr.t, row + mh::kRowT, sizeof(tr.t));
   }, iters, converged);
-  if (rc != MH_OK || iters == 0) {
-    align_abandon(icp);
-    return rc != MH_OK ? rc : fail(ctx, MH_ERR_HIP, "mh_icp_align: no iteration was evaluated");
-  }
+  lost = rc != MH_OK || iters == 0;
+  if (lost) return rc != MH_OK ? rc : fail(ctx, MH_ERR_HIP, std::string(what) + ": no iteration was evaluated");
   int rc_all = MH_OK;
-  if (out->trace[iters - 1].degenerate & 8) rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_align: a step did not find its K3's sums");
+  if (out->trace[iters - 1].degenerate & 8) rc_all = fail(ctx, MH_ERR_HIP, std::string(what) + ": a step did not find its K3's sums");
   out->iters = iters;
   out->converged = converged;
   std::memcpy(out->R, out->trace[iters - 1].R, sizeof(out->R));
@@ -321,14 +323,27 @@ static int align_finish(mh_icp * icp)
   // first / last: at the initial and at the last evaluated pose
   for (int which = 0; which < 2 && rc_all == MH_OK; ++which) {
     const int i = which == 0 ? 0 : iters - 1;
-    if (!chain_epilogue(icp, i, i == 0 ? c.R0 : out->trace[i - 1].R, c.gz, c.count0 + i + 1, c.seq[i], which == 0 ? &out->first : &out->last))
-      rc_all = fail(ctx, MH_ERR_HIP, "mh_icp_align: an iteration's sums did not arrive");
+    if (!chain_epilogue(icp, i, i == 0 ? R0 : out->trace[i - 1].R, gz, count0 + i + 1, seq[i], which == 0 ? &out->first : &out->last))
+      rc_all = fail(ctx, MH_ERR_HIP, std::string(what) + ": an iteration's sums did not arrive");
   }
-  icp->linearize_count = c.count0 + iters;
+  return rc_all;
+}
+
+// every queued iteration has run (the caller waited for the last row): the result, and the handle's books
+static int align_finish(mh_icp * icp)
+{
+  mh_icp::AlignCall & c = icp->align;
+  bool lost = false;
+  const int rc = align_collect(icp, c.seq, c.queued, c.R0, c.gz, c.count0, c.out, "mh_icp_align", lost);
+  if (lost) {
+    align_abandon(icp);
+    return rc;
+  }
+  icp->linearize_count = c.count0 + c.out->iters;
   icp->cold = false;
   icp->n_pending = 0;
   c.active = false;
-  return rc_all;
+  return rc;
 }
 
 static int align_run(mh_icp * icp, int chunk)
@@ -351,6 +366,232 @@ static int mh_icp_align_impl(mh_icp * icp, const double R0[9], const double t0[3
   if (rc != MH_OK) return rc;
   if (!blocking) return align_enqueue(icp, cfg->max_iters);
   return align_run(icp, cfg->check_every > 0 ? cfg->check_every : cfg->max_iters);
+}
+
+// ---- several alignments side by side: [K3 batch launches, one step launch] x iters, one wait ------------------------------
+// mh_icp_align_batch's block of device memory (mh_ctx::d_align_batch) and the pinned staging of its first part (h_align_batch):
+// [grid prefixes, 256 B | one AlignState per member | max_iters x n_slots argument blocks | 256 B that load_uniform may read
+//  past the last block | one landing slot of 32 flagged words per member for K3's sums and counters (every iteration's words
+//  carry its own number)]
+// K3 runs as in a window call (staged batch form, one launch per launch group, tail = 1); the step launch has one workgroup per
+// member, which forwards that member's words and row to the iteration's slot of the member's own pinned ring — where
+// mh_icp_align's arrive, so a member is collected like a call of its own (align_collect).
+constexpr size_t kABStateAt = 256;
+constexpr size_t kABStateStride = 192;
+constexpr size_t kABBlocksAt = kABStateAt + kABStateStride * MH_ALIGN_BATCH_MAX;
+constexpr size_t kABStageBytes = kABBlocksAt + sizeof(mh::IcpArgs) * MH_ALIGN_BATCH_MAX * kMaxPending;
+constexpr size_t kABLlAt = (kABStageBytes + 256 + 255) & ~size_t(255);
+constexpr size_t kABBytes = kABLlAt + 32 * sizeof(uint4) * MH_ALIGN_BATCH_MAX;
+static_assert(sizeof(mh::AlignState) <= kABStateStride && MH_ALIGN_BATCH_MAX == mh::kAlignBatchMax && kABBlocksAt % 256 == 0 &&
+                2 * MH_ALIGN_BATCH_MAX * sizeof(int) <= kABStateAt, "mh_icp_align_batch layout");
+
+static mh_ctx * batch_ctx(mh_icp * const * icps, size_t B) { return (icps && B && icps[0]) ? icps[0]->ctx : nullptr; }
+
+static void align_batch_abandon(mh_ctx * ctx)
+{
+  (void)hipStreamSynchronize(ctx->stream);
+  align_batch_release(ctx);
+}
+
+static int align_batch_begin(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3], const mh_icp_align_config * cfg,
+                             mh_icp_align_result * out)
+{
+  mh_ctx * ctx = batch_ctx(icps, B);
+  if (!icps || !R0 || !t0 || !g_unit || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: NULL argument");
+  if (B < 1 || B > static_cast<size_t>(MH_ALIGN_BATCH_MAX)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: B must be in 1..16");
+  for (size_t m = 0; m < B; ++m)
+    if (!icps[m]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: NULL member");
+  ctx = icps[0]->ctx;
+  if (ctx->align_batch.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: the context has a batch call in flight");
+  for (size_t m = 0; m < B; ++m) {
+    const mh_icp * c = icps[m];
+    if (c->ctx != ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: factors of different contexts");
+    if (c->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align_batch: unary factors only");
+    if (c->no_order || c->cap_n > c->n) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align_batch: not for the factors of the map-sharded path");
+    if (c->n_pending || c->align.active || c->in_window || c->in_align_batch) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: a member has calls in flight");
+    if (c->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: a member has no points");
+    for (size_t g = 0; g < m; ++g)
+      if (icps[g] == c) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: the same factor twice");
+  }
+  if (cfg->max_iters < 1 || cfg->max_iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: max_iters must be in 1..64");
+  if (!(cfg->eps_rot >= 0.0) || !(cfg->eps_trans >= 0.0) || !(cfg->damping >= 0.0) || !(cfg->prior_sigma_rot >= 0.0) ||
+      !(cfg->prior_sigma_trans >= 0.0) || cfg->check_every < 0)
+    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: eps, damping, prior sigmas and check_every must be >= 0");
+  MH_HIP(ctx, mh_enter(ctx));
+  if (!ctx->h_align_batch) MH_HIP(ctx, hipHostMalloc(&ctx->h_align_batch, kABStageBytes, hipHostMallocDefault));
+  if (!ctx->d_align_batch) MH_HIP(ctx, hipMalloc(&ctx->d_align_batch, kABBytes));
+
+  AlignBatchCall & c = ctx->align_batch;
+  const int iters = cfg->max_iters;
+  c.B = static_cast<int>(B);
+  c.cfg = *cfg;
+  c.queued = 0;
+  c.out = out;
+  for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
+  // launch groups in slot order, as mh_icp_window_optimise lays the same factors out
+  const std::vector<LaunchGroup> groups = mhi::window_launch_groups(icps, B);
+  c.launches.clear();
+  c.n_slots = 0;
+  for (const LaunchGroup & g : groups) {
+    WindowLaunch wl{g.tpb, g.k, g.n_off, c.n_slots, static_cast<int>(g.members.size()), 0};
+    for (size_t m : g.members) c.slot[m] = c.n_slots++;
+    c.launches.push_back(wl);
+  }
+
+  char * h = static_cast<char *>(ctx->h_align_batch);
+  char * d = static_cast<char *>(ctx->d_align_batch);
+  auto * blocks = reinterpret_cast<mh::IcpArgs *>(h + kABBlocksAt);
+  for (int it = 0; it < iters; ++it) c.seq[it] = mhi::next_call_seq();
+  for (size_t m = 0; m < B; ++m) {
+    mh_icp * icp = icps[m];
+    c.icps[m] = icp;
+    c.count0[m] = icp->linearize_count;
+    std::memcpy(c.R0[m], R0 + 9 * m, sizeof(c.R0[m]));
+    mh::IcpArgs a;
+    const int rc = mhi::chain_k3_block(icp, R0 + 9 * m, t0 + 3 * m, g_unit, a);
+    if (rc != MH_OK) return rc;
+    a.ll = reinterpret_cast<uint4 *>(d + kABLlAt) + 32 * m;
+    mh::AlignState st;
+    std::memset(&st, 0, sizeof(st));
+    std::memcpy(st.R, a.R, sizeof(st.R));
+    std::memcpy(st.t, a.t, sizeof(st.t));
+    std::memcpy(h + kABStateAt + kABStateStride * m, &st, sizeof(st));
+    chain_fill_blocks(a, icp->cold, iters, c.seq, blocks + c.slot[m], static_cast<size_t>(c.n_slots), 0);
+
+    mh::AlignParams & p = c.p[m];
+    for (int i = 0; i < 3; ++i) p.gz[i] = c.gz[i];
+    p.eps_rot = cfg->eps_rot;
+    p.eps_trans = cfg->eps_trans;
+    p.damping = cfg->damping;
+    p.prior_rot = cfg->prior_sigma_rot > 0.0 ? 1.0 / (cfg->prior_sigma_rot * cfg->prior_sigma_rot) : 0.0;
+    p.prior_trans = cfg->prior_sigma_trans > 0.0 ? 1.0 / (cfg->prior_sigma_trans * cfg->prior_sigma_trans) : 0.0;
+    p.thresh_rot = icp->cfg.degen_thresh_rot;
+    p.thresh_trans = icp->cfg.degen_thresh_trans;
+    p.reg_4_dof = icp->cfg.reg_4_dof;
+    p.project_on_degeneracy = icp->cfg.project_on_degneneracy;
+  }
+  int * prefix = reinterpret_cast<int *>(h);
+  for (size_t gi = 0; gi < c.launches.size(); ++gi) {
+    WindowLaunch & wl = c.launches[gi];
+    int * start = prefix + wl.first + static_cast<int>(gi);
+    int acc = 0;
+    for (int i = 0; i < wl.n; ++i) {
+      start[i] = acc;
+      acc += mh::class_grid(blocks[wl.first + i].n, wl.tpb);
+    }
+    start[wl.n] = acc;
+    wl.grid = acc;
+  }
+  MH_HIP(ctx, hipMemcpyAsync(d, h, kABBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(iters), hipMemcpyHostToDevice, ctx->stream));
+  c.active = true;
+  for (size_t m = 0; m < B; ++m) {
+    icps[m]->in_align_batch = true;
+    icps[m]->n_pending = kMaxPending;  // the chain holds the whole ring
+  }
+  return MH_OK;
+}
+
+// iterations [queued, upto) onto the stream
+static int align_batch_enqueue(mh_ctx * ctx, int upto)
+{
+  AlignBatchCall & c = ctx->align_batch;
+  char * d = static_cast<char *>(ctx->d_align_batch);
+  auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + kABBlocksAt);
+  const int * prefix = reinterpret_cast<const int *>(d);
+  for (int it = c.queued; it < upto; ++it) {
+    hipError_t e = hipSuccess;
+    for (size_t gi = 0; gi < c.launches.size() && e == hipSuccess; ++gi) {
+      const WindowLaunch & wl = c.launches[gi];
+      e = mh::launch_linearize_batch(blocks + static_cast<size_t>(it) * c.n_slots + wl.first, prefix + wl.first + static_cast<int>(gi), wl.n, wl.grid, wl.tpb, wl.k,
+                                     wl.n_off, false, ctx->stream);
+    }
+    if (e == hipSuccess) {
+      mh::AlignBatchStepArgs s;
+      std::memset(static_cast<void *>(&s), 0, sizeof(s));
+      for (int m = 0; m < c.B; ++m) {
+        mh::AlignStepArgs & a = s.m[m];
+        a.ll_dev = reinterpret_cast<const uint4 *>(d + kABLlAt) + 32 * m;
+        a.ll_host = c.icps[m]->d_h_ll + static_cast<size_t>(it) * c.icps[m]->ll_words;
+        a.next = it + 1 < c.cfg.max_iters ? blocks + static_cast<size_t>(it + 1) * c.n_slots + c.slot[m] : nullptr;
+        a.state = reinterpret_cast<mh::AlignState *>(d + kABStateAt + kABStateStride * m);
+        a.p = c.p[m];
+        a.seq = c.seq[it];
+      }
+      e = mh::launch_align_batch_step(s, c.B, ctx->stream);
+    }
+    if (e != hipSuccess) {
+      align_batch_abandon(ctx);
+      return hip_fail(ctx, e, "mh_icp_align_batch: launch");
+    }
+    c.queued = it + 1;
+  }
+  return MH_OK;
+}
+
+// every queued iteration has run (the caller waited for every member's last row): the results, and the handles' books
+static int align_batch_finish(mh_ctx * ctx)
+{
+  AlignBatchCall & c = ctx->align_batch;
+  int rc_all = MH_OK;
+  for (int m = 0; m < c.B; ++m) {
+    bool lost = false;
+    const int rc = align_collect(c.icps[m], c.seq, c.queued, c.R0[m], c.gz, c.count0[m], &c.out[m], "mh_icp_align_batch", lost);
+    if (lost) {  // the members collected so far keep their books; the call is over for all
+      align_batch_abandon(ctx);
+      return rc;
+    }
+    c.icps[m]->linearize_count = c.count0[m] + c.out[m].iters;
+    c.icps[m]->cold = false;
+    if (rc_all == MH_OK) rc_all = rc;
+  }
+  align_batch_release(ctx);
+  return rc_all;
+}
+
+// The row of iteration i as chain_drive looks at it: every member's row has arrived, and the stop bit is set when every
+// member's is.
+static int align_batch_wait_row(mh_ctx * ctx, int i, double * row)
+{
+  const AlignBatchCall & c = ctx->align_batch;
+  int all = 1;
+  for (int m = 0; m < c.B; ++m) {
+    const mh_icp * icp = c.icps[m];
+    const int rc = chain_wait_row(ctx, ChainRows{icp->h_ll + mh::kLlSums, icp->ll_words, mh::kRowWords, c.seq}, i, row, "mh_icp_align_batch");
+    if (rc != MH_OK) return rc;
+    all &= static_cast<int>(row[mh::kRowFlags]);
+  }
+  row[mh::kRowFlags] = static_cast<double>(all & 1);
+  return MH_OK;
+}
+
+static int align_batch_run(mh_ctx * ctx, int chunk)
+{
+  return chain_drive(ctx->align_batch.queued, ctx->align_batch.cfg.max_iters, chunk, mh::kRowFlags, [ctx](int upto) { return align_batch_enqueue(ctx, upto); },
+                     [ctx](int i, double * row) { return align_batch_wait_row(ctx, i, row); }, [ctx] { align_batch_abandon(ctx); },
+                     [ctx] { return align_batch_finish(ctx); });
+}
+
+static int mh_icp_align_batch_impl(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3],
+                                   const mh_icp_align_config * cfg, mh_icp_align_result * out, bool blocking)
+{
+  const int rc = align_batch_begin(icps, B, R0, t0, g_unit, cfg, out);
+  if (rc != MH_OK) return rc;
+  if (!blocking) return align_batch_enqueue(icps[0]->ctx, cfg->max_iters);
+  return align_batch_run(icps[0]->ctx, cfg->check_every > 0 ? cfg->check_every : cfg->max_iters);
+}
+
+int mhi::align_batch(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3], const mh_icp_align_config * cfg,
+                     mh_icp_align_result * out)
+{
+  return mh_icp_align_batch_impl(icps, B, R0, t0, g_unit, cfg, out, true);
+}
+
+static int mh_icp_align_batch_wait_impl(mh_ctx * ctx)
+{
+  if (!ctx) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_align_batch_wait: ctx is NULL");
+  if (!ctx->align_batch.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch_wait: no batch call in flight");
+  MH_HIP(ctx, mh_enter(ctx));
+  return align_batch_run(ctx, 0);
 }
 
 // ---- fixed-lag window: [K3 batch launches, step] x iters on the context's stream, one wait --------------------------------
@@ -965,6 +1206,20 @@ int mh_icp_align_async(mh_icp * icp, const double R0[9], const double t0[3], con
                        mh_icp_align_result * out)
 {
   return guarded(icp ? icp->ctx : nullptr, "mh_icp_align_async", [&]() -> int { return mh_icp_align_impl(icp, R0, t0, g_unit, cfg, out, false); });
+}
+int mh_icp_align_batch(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3], const mh_icp_align_config * cfg,
+                       mh_icp_align_result * out)
+{
+  return guarded(batch_ctx(icps, B), "mh_icp_align_batch", [&]() -> int { return mh_icp_align_batch_impl(icps, B, R0, t0, g_unit, cfg, out, true); });
+}
+int mh_icp_align_batch_async(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3], const mh_icp_align_config * cfg,
+                             mh_icp_align_result * out)
+{
+  return guarded(batch_ctx(icps, B), "mh_icp_align_batch_async", [&]() -> int { return mh_icp_align_batch_impl(icps, B, R0, t0, g_unit, cfg, out, false); });
+}
+int mh_icp_align_batch_wait(mh_ctx * ctx)
+{
+  return guarded(ctx, "mh_icp_align_batch_wait", [&]() -> int { return mh_icp_align_batch_wait_impl(ctx); });
 }
 
 int mh_icp_window_optimise(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,

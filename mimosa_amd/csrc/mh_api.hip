@@ -266,6 +266,9 @@ void mh_shutdown(mh_ctx * ctx)
   if (ctx->h_window) (void)hipHostFree(ctx->h_window);
   if (ctx->d_window) (void)hipFree(ctx->d_window);
   if (ctx->h_window_rows) (void)hipHostFree(ctx->h_window_rows);
+  if (ctx->align_batch.active) align_batch_release(ctx);  // (likewise an mh_icp_align_batch call nobody waited for)
+  if (ctx->h_align_batch) (void)hipHostFree(ctx->h_align_batch);
+  if (ctx->d_align_batch) (void)hipFree(ctx->d_align_batch);
   if (ctx->copy_stream) {
     (void)hipStreamSynchronize(ctx->copy_stream);
     (void)hipStreamDestroy(ctx->copy_stream);
@@ -438,6 +441,8 @@ static int icp_create_common(mh_ctx * ctx, mh_map * map, const mh_point32 * sour
   icp->binary = is_binary != 0;
   icp->no_order = no_order;
   icp->cap_n = capacity > n ? capacity : n;
+  static std::atomic<uint64_t> next_cloud_id{1};  // (0: never handed out)
+  icp->cloud_id = next_cloud_id.fetch_add(1, std::memory_order_relaxed);
   int rc = icp_alloc(icp);
   if (rc != MH_OK) {
     mh_icp_destroy(icp);
@@ -481,6 +486,7 @@ static int mh_icp_clone_impl(const mh_icp * src, mh_icp ** out)
   icp->n = src->n;
   icp->cfg = src->cfg;
   icp->binary = src->binary;
+  icp->cloud_id = src->cloud_id;
   int rc = icp_alloc(icp);
   if (rc != MH_OK) {
     mh_icp_destroy(icp);
@@ -521,6 +527,7 @@ void mh_icp_destroy(mh_icp * icp)
   // a factor destroyed inside a window call nobody waited for: the stream has drained, the call is abandoned as a whole (its
   // books keep pointers to every factor of it)
   if (icp->in_window && icp->ctx->window.active) window_release(icp->ctx);
+  if (icp->in_align_batch && icp->ctx->align_batch.active) align_batch_release(icp->ctx);  // (an mh_icp_align_batch call likewise)
   icp->d_rec.release(true);
   icp->d_src.release(true);
   icp->d_qda.release(true);
@@ -573,6 +580,7 @@ static int mh_icp_reset_impl(mh_icp * icp)
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_reset: icp is NULL");
   if (icp->in_window) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: the factor is in a window call in flight");
   if (icp->align.active) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: an alignment is in flight");  // (its books would overwrite the reset)
+  if (icp->in_align_batch) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: the factor is in a batch alignment in flight");
   if (icp->score.active) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: a pose scoring call is in flight");
   icp->cold = true;  // the next linearize treats the cached state as all-zero (no memset needed)
   return MH_OK;
@@ -859,6 +867,8 @@ static int mh_icp_wait_impl(mh_icp * icp)
   const double tw_enter = g_wt.on ? WaitTrace::now() : 0.0;
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_wait: icp is NULL");
   if (icp->in_window) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_wait: the factor is in a window call: mh_icp_window_wait collects it");
+  if (icp->in_align_batch)
+    return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_wait: the factor is in a batch alignment: mh_icp_align_batch_wait collects it");
   if (icp->align.active) return mhi::align_wait(icp);
   if (icp->score.active) return mhi::score_wait(icp);
   mh_ctx * ctx = icp->ctx;

@@ -69,6 +69,25 @@ struct WindowCall
   double LSR[MH_WINDOW_JOINT_POSES][9], LSt[MH_WINDOW_JOINT_POSES][3];         // ... and those poses as the caller gave them
 };
 
+// mh_icp_align_batch (chain_api.hip): the call in flight on a context (at most one).  Like a window call its argument blocks, grid
+// prefixes, the members' AlignStates and K3's landing slots live in device memory the context owns (d_align_batch), their pinned
+// staging in h_align_batch; every member's rows arrive in that member's own pinned ring, as mh_icp_align's do.
+struct AlignBatchCall
+{
+  bool active = false;
+  int B = 0, queued = 0, n_slots = 0;
+  mh_icp_align_config cfg{};
+  mh_icp * icps[MH_ALIGN_BATCH_MAX];
+  int slot[MH_ALIGN_BATCH_MAX];  // member m's argument block within an iteration
+  int count0[MH_ALIGN_BATCH_MAX];
+  double R0[MH_ALIGN_BATCH_MAX][9];
+  double gz[3];
+  unsigned int seq[64];
+  mh::AlignParams p[MH_ALIGN_BATCH_MAX];
+  std::vector<WindowLaunch> launches;
+  mh_icp_align_result * out = nullptr;  // B of them
+};
+
 struct mh_ctx
 {
   int device = 0;
@@ -86,6 +105,9 @@ struct mh_ctx
   uint4 * h_window_rows = nullptr; // ... the rows of its iterations (mapped pinned), and their device-side address
   uint4 * d_window_rows = nullptr;
   WindowCall window;
+  void * h_align_batch = nullptr;  // mh_icp_align_batch: pinned staging of the chain's block
+  void * d_align_batch = nullptr;  // ... the block itself
+  AlignBatchCall align_batch;
   hipStream_t copy_stream = nullptr;  // mh_scan_prefetch: uploads beside the compute stream (created on first use: an HSA queue costs ~1 ms)
   std::mutex copy_mu;
   // what mh_shutdown takes back from the sharded handles (shard_api.hip): the sharded factors created on this context, and
@@ -713,6 +735,15 @@ struct mh_icp
     mh::AlignParams p;
   } align;
   bool in_window = false;  // held by the mh_icp_window_optimise call in flight on its context (which also holds the whole ring)
+  // ... by the mh_icp_align_batch call in flight on its context (likewise).  The calls that need to tell such a factor apart test
+  // the flag (mh_icp_reset, which looks at no ring; mh_icp_wait, which would read the ring as its own calls; mh_icp_destroy;
+  // the new batch entry points).  Every other entry point — mh_icp_linearize*, mh_icp_linearize_batch, mh_icp_clone,
+  // mh_icp_align, the window chains, mh_icp_score_poses — refuses a member through n_pending == kMaxPending alone, as it refuses a
+  // factor whose ring is full; their checks are as they were.
+  bool in_align_batch = false;
+  // which cloud this is: a fresh number for every created factor, the source's for a clone (mh_icp_relocalise_batch asks
+  // whether its work factors are clones of the factor it scores)
+  uint64_t cloud_id = 0;
   // mh_icp_score_poses (reloc_api.hip): the call's device block [poses | strided cloud | per-workgroup partials | scores]
   // (d_reloc), its mapped pinned block [winners | poses | scores] (h_reloc), and the call in flight.  Like an alignment it
   // holds the whole ring (n_pending == kMaxPending) until mh_icp_wait collects it; it touches nothing else of the factor.
@@ -734,6 +765,17 @@ inline void window_release(mh_ctx * ctx)
   WindowCall & c = ctx->window;
   for (int i = 0; i < c.W; ++i) {
     c.icps[i]->in_window = false;
+    c.icps[i]->n_pending = 0;
+  }
+  c.active = false;
+}
+
+// The same for the mh_icp_align_batch call on ctx.
+inline void align_batch_release(mh_ctx * ctx)
+{
+  AlignBatchCall & c = ctx->align_batch;
+  for (int i = 0; i < c.B; ++i) {
+    c.icps[i]->in_align_batch = false;
     c.icps[i]->n_pending = 0;
   }
   c.active = false;
@@ -776,4 +818,7 @@ std::vector<LaunchGroup> window_launch_groups(mh_icp * const * icps, size_t n_fa
 int align_wait(mh_icp * icp);
 // reloc_api.hip: mh_icp_wait on a factor whose mh_icp_score_poses_async is in flight
 int score_wait(mh_icp * icp);
+// chain_api.hip: mh_icp_align_batch without the guard, for mh_icp_relocalise_batch
+int align_batch(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3], const mh_icp_align_config * cfg,
+                mh_icp_align_result * out);
 }  // namespace mhi

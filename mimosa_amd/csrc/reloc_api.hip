@@ -1,8 +1,9 @@
-// Relocalisation entry points of the C ABI (include/mimosa_hip.h): mh_icp_score_poses[_async] and mh_icp_relocalise.  The
-// kernels are reloc_kernels.hip, the arithmetic reloc_device.hpp; the refinement of a candidate is mh_icp_align (chain_api.hip),
-// called as a caller would call it.
+// Relocalisation entry points of the C ABI (include/mimosa_hip.h): mh_icp_score_poses[_async], mh_icp_relocalise and
+// mh_icp_relocalise_batch.  The kernels are reloc_kernels.hip, the arithmetic reloc_device.hpp; the refinement of a candidate is
+// mh_icp_align, of all candidates at once mh_icp_align_batch (chain_api.hip), called as a caller would call them.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <memory>
 
@@ -131,10 +132,25 @@ static bool key_before(const mh_pose_score & a, int ia, const mh_pose_score & b,
   return mh::reloc_before(mh::reloc_key_of(sa, ia), mh::reloc_key_of(sb, ib));
 }
 
-static int relocalise_impl(mh_icp * icp, const double * R, const double * t, size_t n_poses, const double g_unit[3], const mh_icp_reloc_config * cfg,
-                           mh_icp_reloc_result * out)
+// (through the public calls only mh_icp_clone hands an identity on, and it copies the config with it: for such callers the
+// identity decides first and this comparison cannot fail on its own; it states the contract's fourth condition)
+static bool same_reg_config(const mh_reg_config & a, const mh_reg_config & b)
 {
-  if (!icp || !R || !t || !g_unit || !cfg || !out) return fail(icp ? icp->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_relocalise: NULL argument");
+  return a.source_voxel_grid_filter_leaf_size == b.source_voxel_grid_filter_leaf_size &&
+         a.source_voxel_grid_min_dist_in_voxel == b.source_voxel_grid_min_dist_in_voxel && a.target_ivox_map_leaf_size == b.target_ivox_map_leaf_size &&
+         a.target_ivox_map_min_dist_in_voxel == b.target_ivox_map_min_dist_in_voxel && a.num_corres_points == b.num_corres_points &&
+         a.max_corres_distance == b.max_corres_distance && a.plane_validity_distance == b.plane_validity_distance &&
+         a.lidar_point_noise_std_dev == b.lidar_point_noise_std_dev && a.use_huber == b.use_huber && a.huber_threshold == b.huber_threshold &&
+         a.reg_4_dof == b.reg_4_dof && a.project_on_degneneracy == b.project_on_degneneracy && a.degen_thresh_rot == b.degen_thresh_rot &&
+         a.degen_thresh_trans == b.degen_thresh_trans;
+}
+
+// batch: mh_icp_relocalise_batch — step 2 is one mh_icp_align_batch over work[], and icp is only read
+static int relocalise_impl(mh_icp * icp, const double * R, const double * t, size_t n_poses, const double g_unit[3], const mh_icp_reloc_config * cfg,
+                           mh_icp_reloc_result * out, bool batch = false, mh_icp * const * work = nullptr, size_t n_work = 0)
+{
+  if (!icp || !R || !t || !g_unit || !cfg || !out || (batch && !work))
+    return fail(icp ? icp->ctx : nullptr, MH_ERR_INVALID_ARG, batch ? "mh_icp_relocalise_batch: NULL argument" : "mh_icp_relocalise: NULL argument");
   mh_ctx * ctx = icp->ctx;
   if (cfg->score.top_k == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise: score.top_k must be in 1..8");
   if (!(std::isfinite(cfg->final_gate) && cfg->final_gate > 0.0)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise: final_gate must be finite and > 0");
@@ -144,6 +160,24 @@ static int relocalise_impl(mh_icp * icp, const double * R, const double * t, siz
   if (!(ac.eps_rot >= 0.0) || !(ac.eps_trans >= 0.0) || !(ac.damping >= 0.0) || !(ac.prior_sigma_rot >= 0.0) || !(ac.prior_sigma_trans >= 0.0) ||
       ac.check_every < 0)
     return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise: align's eps, damping, prior sigmas and check_every must be >= 0");
+  if (batch) {
+    // the work factors, before anything runs: enough of them, each a free clone of icp, none twice
+    const size_t need = std::min(static_cast<size_t>(std::max(cfg->score.top_k, 0)), n_poses);
+    if (n_work < need) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: fewer work factors than candidates to refine");
+    if (ctx->align_batch.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: the context has a batch call in flight");
+    for (size_t c = 0; c < n_work; ++c) {
+      const mh_icp * w = work[c];
+      if (!w) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: NULL work factor");
+      if (w == icp) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: a work factor is the scored factor itself");
+      if (w->cloud_id != icp->cloud_id || w->n != icp->n || w->map != icp->map || w->ctx != ctx || w->binary != icp->binary ||
+          !same_reg_config(w->cfg, icp->cfg))
+        return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: a work factor is not a clone of the scored factor");
+      if (w->n_pending || w->align.active || w->score.active || w->in_window || w->in_align_batch)
+        return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: a work factor has calls in flight");
+      for (size_t g = 0; g < c; ++g)
+        if (work[g] == w) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: the same work factor twice");
+    }
+  }
   std::memset(static_cast<void *>(out), 0, sizeof(*out));
   out->best = -1;
   // 1. score and select: one wait
@@ -154,28 +188,42 @@ static int relocalise_impl(mh_icp * icp, const double * R, const double * t, siz
   int nc = 0;
   while (nc < MH_RELOC_MAX_REFINE && best[nc] >= 0) ++nc;
   out->n_candidates = nc;
-  // 2. the align chain from each, in rank order
-  std::unique_ptr<mh_icp_align_result> ar(new mh_icp_align_result);
+  // 2. the align chain from each, in rank order: one after another on icp, or (batch) side by side, candidate c on work[c]
+  std::unique_ptr<mh_icp_align_result[]> ar(new mh_icp_align_result[nc]);
   double Ra[9 * MH_RELOC_MAX_REFINE], ta[3 * MH_RELOC_MAX_REFINE];
   for (int c = 0; c < nc; ++c) {
     mh_icp_reloc_candidate & q = out->cand[c];
     q.index = best[c];
     std::memcpy(&q.coarse, &coarse.score[c], sizeof(q.coarse));
-    rc = mh_icp_reset(icp);
-    if (rc == MH_OK) rc = mh_icp_align(icp, R + 9 * static_cast<size_t>(q.index), t + 3 * static_cast<size_t>(q.index), g_unit, &cfg->align, ar.get());
-    if (rc != MH_OK) {
-      (void)mh_icp_reset(icp);
-      return rc;
-    }
-    q.iters = ar->iters;
-    q.converged = ar->converged;
-    std::memcpy(q.R, ar->R, sizeof(q.R));
-    std::memcpy(q.t, ar->t, sizeof(q.t));
-    std::memcpy(Ra + 9 * c, ar->R, sizeof(q.R));
-    std::memcpy(ta + 3 * c, ar->t, sizeof(q.t));
+    std::memcpy(Ra + 9 * c, R + 9 * static_cast<size_t>(q.index), 9 * sizeof(double));
+    std::memcpy(ta + 3 * c, t + 3 * static_cast<size_t>(q.index), 3 * sizeof(double));
   }
-  rc = mh_icp_reset(icp);
-  if (rc != MH_OK) return rc;
+  if (batch) {
+    for (int c = 0; c < nc; ++c)
+      if ((rc = mh_icp_reset(work[c])) != MH_OK) return rc;
+    rc = mhi::align_batch(work, static_cast<size_t>(nc), Ra, ta, g_unit, &cfg->align, ar.get());
+    if (rc != MH_OK) return rc;
+  } else {
+    for (int c = 0; c < nc; ++c) {
+      rc = mh_icp_reset(icp);
+      if (rc == MH_OK) rc = mh_icp_align(icp, Ra + 9 * c, ta + 3 * c, g_unit, &cfg->align, &ar[c]);
+      if (rc != MH_OK) {
+        (void)mh_icp_reset(icp);
+        return rc;
+      }
+    }
+    rc = mh_icp_reset(icp);
+    if (rc != MH_OK) return rc;
+  }
+  for (int c = 0; c < nc; ++c) {
+    mh_icp_reloc_candidate & q = out->cand[c];
+    q.iters = ar[c].iters;
+    q.converged = ar[c].converged;
+    std::memcpy(q.R, ar[c].R, sizeof(q.R));
+    std::memcpy(q.t, ar[c].t, sizeof(q.t));
+    std::memcpy(Ra + 9 * c, ar[c].R, sizeof(q.R));
+    std::memcpy(ta + 3 * c, ar[c].t, sizeof(q.t));
+  }
   // 3. the aligned poses once more: every point, the final gate
   mh_icp_score_config fc;
   fc.gate = cfg->final_gate;
@@ -212,6 +260,12 @@ int mh_icp_relocalise(mh_icp * icp, const double * R, const double * t, size_t n
                       mh_icp_reloc_result * out)
 {
   return guarded(icp ? icp->ctx : nullptr, "mh_icp_relocalise", [&]() -> int { return relocalise_impl(icp, R, t, n_poses, g_unit, cfg, out); });
+}
+int mh_icp_relocalise_batch(mh_icp * icp, mh_icp * const * work, size_t n_work, const double * R, const double * t, size_t n_poses, const double g_unit[3],
+                            const mh_icp_reloc_config * cfg, mh_icp_reloc_result * out)
+{
+  return guarded(icp ? icp->ctx : nullptr, "mh_icp_relocalise_batch",
+                 [&]() -> int { return relocalise_impl(icp, R, t, n_poses, g_unit, cfg, out, true, work, n_work); });
 }
 
 }  // extern "C"

@@ -592,6 +592,54 @@ public:
     return out;
   }
 
+  // Several alignments side by side (mh_icp_align_batch): factors[i] from T0[i], all in one chain of launches — per iteration the
+  // batch's K3 launches and one step launch — with one wait.  Every member is aligned exactly as align() aligns it and stops on
+  // its own; one config serves all.  1 .. MH_ALIGN_BATCH_MAX unary factors of one context, each at most once.
+  static std::vector<AlignResult> alignBatch(const std::vector<ICPFactor *> & factors, const std::vector<Pose3> & T0, const Unit3 & g,
+                                             const AlignConfig & config)
+  {
+    AlignBatchCall call = alignBatchBegin(factors, T0, g, config, false);
+    return call.take();
+  }
+  // The same without waiting: wait() collects it (mh_icp_align_batch_wait).  No other call on a member until then; the call
+  // object must outlive the wait, and the factors the call object.
+  class AlignBatchCall
+  {
+  public:
+    std::vector<AlignResult> wait()
+    {
+      if (pending_) {
+        pending_ = false;
+        factors_[0]->ctx().check(mh_icp_align_batch_wait(factors_[0]->ctx().get()), "mh_icp_align_batch_wait");
+      }
+      return take();
+    }
+
+  private:
+    friend class ICPFactor;
+    std::vector<AlignResult> take()
+    {
+      std::vector<AlignResult> out(factors_.size());
+      for (size_t i = 0; i < factors_.size(); ++i) {
+        const mh_icp_align_result & r = results_[i];
+        factors_[i]->last_ = r.last;
+        out[i].pose = pose3(r.R, r.t);
+        out[i].iters = r.iters;
+        out[i].converged = r.converged != 0;
+        out[i].trace.assign(r.trace, r.trace + r.iters);
+      }
+      return out;
+    }
+    std::vector<ICPFactor *> factors_;
+    bool pending_ = false;
+    std::unique_ptr<mh_icp_align_result[]> results_;  // on the heap: the library writes into them when the call is collected
+  };
+  static AlignBatchCall alignBatchAsync(const std::vector<ICPFactor *> & factors, const std::vector<Pose3> & T0, const Unit3 & g,
+                                        const AlignConfig & config)
+  {
+    return alignBatchBegin(factors, T0, g, config, true);
+  }
+
   // Relocalisation (no counterpart in the reference): candidate poses of this factor's cloud scored against its map in one chain
   // of launches and ranked on the device (mh_icp_score_poses), and the few best refined with align() (mh_icp_relocalise).  For
   // the caller who has no pose inside the association gate yet.
@@ -691,6 +739,42 @@ public:
       k.fine = q.fine;
       k.pose = pose3(q.R, q.t);
       last_.linearize_count += q.iters;  // what getLinearizeCount() reports: the library's count moved with the alignments
+      out.candidates.push_back(k);
+    }
+    return out;
+  }
+  // relocalise() with the candidates aligned side by side (mh_icp_relocalise_batch) on clones of this factor, which it makes on
+  // first use and keeps.  The one difference: this factor is only read — it is NOT reset, and neither its association state nor
+  // getLinearizeCount() move.
+  RelocResult relocaliseBatch(const std::vector<Pose3> & poses, const Unit3 & g, const RelocConfig & config)
+  {
+    std::vector<double> R, t;
+    flattenPoses(poses, R, t);
+    const A3 gu = toArray(g.unitVector());
+    mh_icp_reloc_config c;
+    c.score = scoreConfig(config.score);
+    c.align = alignConfig(config.align);
+    c.final_gate = config.final_gate;
+    const size_t need = std::min(static_cast<size_t>(std::max(config.score.top_k, 0)), poses.size());
+    while (reloc_work_.size() < need) reloc_work_.push_back(Ptr(new ICPFactor(*this, CloneTag{})));
+    std::vector<mh_icp *> work;
+    for (const Ptr & w : reloc_work_) work.push_back(w->icp_);
+    std::unique_ptr<mh_icp_reloc_result> r(new mh_icp_reloc_result);
+    ctx().check(mh_icp_relocalise_batch(icp_, work.data(), work.size(), R.data(), t.data(), poses.size(), gu.data(), &c, r.get()),
+                "mh_icp_relocalise_batch");
+    RelocResult out;
+    out.pose = pose3(r->R, r->t);
+    out.best = r->best;
+    for (int i = 0; i < r->n_candidates; ++i) {
+      const mh_icp_reloc_candidate & q = r->cand[i];
+      RelocCandidate k;
+      k.index = q.index;
+      k.iters = q.iters;
+      k.converged = q.converged != 0;
+      k.coarse = q.coarse;
+      k.fine = q.fine;
+      k.pose = pose3(q.R, q.t);
+      reloc_work_[static_cast<size_t>(i)]->last_.linearize_count += q.iters;
       out.candidates.push_back(k);
     }
     return out;
@@ -1098,6 +1182,31 @@ private:
     c.check_every = config.check_every;
     return c;
   }
+  static AlignBatchCall alignBatchBegin(const std::vector<ICPFactor *> & factors, const std::vector<Pose3> & T0, const Unit3 & g,
+                                        const AlignConfig & config, bool async)
+  {
+    const size_t n = factors.size();
+    if (!n || T0.size() != n) throw std::runtime_error("ICPFactor::alignBatch: one start pose per factor, at least one factor");
+    for (const ICPFactor * f : factors)
+      if (!f) throw std::runtime_error("ICPFactor::alignBatch: null factor");
+    std::vector<double> R, t;
+    flattenPoses(T0, R, t);  // (the library has copied the poses when the call returns)
+    const A3 gu = toArray(g.unitVector());
+    const mh_icp_align_config c = alignConfig(config);
+    std::vector<mh_icp *> h(n);
+    for (size_t i = 0; i < n; ++i) h[i] = factors[i]->icp_;
+    AlignBatchCall call;
+    call.factors_ = factors;
+    call.results_.reset(new mh_icp_align_result[n]);
+    const Context & cx = factors[0]->ctx();
+    if (async) {
+      cx.check(mh_icp_align_batch_async(h.data(), n, R.data(), t.data(), gu.data(), &c, call.results_.get()), "mh_icp_align_batch_async");
+      call.pending_ = true;
+    } else {
+      cx.check(mh_icp_align_batch(h.data(), n, R.data(), t.data(), gu.data(), &c, call.results_.get()), "mh_icp_align_batch");
+    }
+    return call;
+  }
   ScoreCall scorePosesBegin(const std::vector<Pose3> & poses, const ScoreConfig & config, bool want_scores, bool async)
   {
     std::vector<double> R, t;
@@ -1269,6 +1378,7 @@ private:
   size_t n_;
   mh_icp * icp_ = nullptr;
   mutable mh_icp_result last_;
+  std::vector<Ptr> reloc_work_;  // relocaliseBatch: the clones its candidates are aligned on, made on first use
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -83,6 +83,9 @@ class ReplayConfig:
     relocalise_step_yaw_deg: float = 7.5
     relocalise_guess_offset: tuple = (1.2, -0.9, 0.0)   # 1.5 m
     relocalise_guess_yaw_deg: float = 20.0
+    # with relocalise_first: the candidates are aligned side by side in one chain of launches (mh_icp_relocalise_batch, on clones of
+    # the scan's factor that live for the call) instead of one after another.  Refused without relocalise_first
+    relocalise_batch: bool = False
     # the smoother's update_iters iterations run as ONE chain of launches on the device (mh_icp_window_optimise: linearize,
     # assembly, block-tridiagonal solve, retraction) instead of a batched linearize, a numpy solve and the retractions per
     # iteration.  Without the photometric factor only; HIP backend and the native FixedLagReplay
@@ -354,7 +357,8 @@ class HipBackend:
                                      np.deg2rad(cfg.relocalise_step_yaw_deg))
         align = self.capi.make_align_config(max_iters=30, eps_rot=1e-6, eps_trans=1e-6, damping=1e-9)
         rc = self.capi.make_reloc_config(gate=self.regd["max_corres_distance"], stride=4, top_k=4, align=align, final_gate=0.1)
-        r = f.relocalise(Rs, ts, rc)
+        r = f.relocalise(Rs, ts, rc, batch=cfg.relocalise_batch)
+        f.release_reloc_work()  # relocalise_batch: the clones the candidates were aligned on
         return r["R"], r["t"], r
 
     def make_photo_factor(self):
@@ -570,6 +574,8 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         raise ValueError("relocalise_first needs a backend with mh_icp_relocalise (HipBackend)")
     if cfg.relocalise_first and cfg.init_align:
         raise ValueError("relocalise_first aligns the first scan itself: not offered together with init_align")
+    if cfg.relocalise_batch and not cfg.relocalise_first:
+        raise ValueError("relocalise_batch is only offered with relocalise_first")
     relocalised = None
     backend.seed_map(synth.make_room(synth.BASE_SEED, 0, 0, room=np.asarray(cfg.room)))
     stage = {"front_end": 0.0, "imu": 0.0, "factor_create": 0.0, "optimise": 0.0, "update_map": 0.0}
