@@ -135,6 +135,17 @@ typedef struct mh_map_stats {
   int64_t full_uploads;      /* always 0 since the map is maintained on the device (kept for ABI stability) */
 } mh_map_stats;
 
+/* What the next insert of a batch would do (mh_map_preview_insert*): the outcome of every point under the insert's sequential
+ * per-voxel rule.  n_added + n_too_close + n_voxel_full == n_points.  48 bytes. */
+typedef struct mh_map_insert_preview {
+  int64_t n_points;          /* the batch */
+  int64_t n_added;           /* points the insert would keep */
+  int64_t n_too_close;       /* refused by the min-distance rule */
+  int64_t n_voxel_full;      /* refused because their voxel holds max_points_in_cell */
+  int64_t n_touched_voxels;  /* distinct voxels of the batch */
+  int64_t n_new_voxels;      /* of those, voxels the map does not hold yet */
+} mh_map_insert_preview;
+
 /*
  * What gtsam::HessianFactor(key[, key2], G11, [G12,] g1, [G22, g2,] f) receives from
  * ICPFactor::linearize (geometric_factor.hpp:459-462, 559-560) plus every getter-visible side
@@ -206,6 +217,30 @@ int mh_map_insert_device(mh_map * map, const void * d_points, size_t n, size_t s
 /* Geometric::updateMap's insert (geometric.cpp:483-495) straight from a device-resident scan: Be_cloud_ (the body-frame
  * geometric subset of mh_scan_preprocess_geometric) transformed by T_W_Be in f32 and inserted, no host round trip. */
 int mh_map_insert_from_scan(mh_map * map, const mh_scan * scan, const float R_W_Be[9], const float t_W_Be[3]);
+/* Insert preview: what the three inserts above WOULD do to this batch, read-only.  The information content of a scan with respect
+ * to the map, which Geometric::updateMap replaces by a pose test (geometric.cpp:460-464), without forking the map and inserting.
+ * Arguments: those of mh_map_insert / mh_map_insert_device / mh_map_insert_from_scan (same f32 transform, Eigen's order, no FMA),
+ *   then `out` (required) and `outcome` (n bytes of HOST memory, or NULL): outcome[i] of input point i is 1 = added, 2 = too
+ *   close (a resident point or a point of the batch kept earlier lies within min_dist_in_cell), 3 = voxel full (the voxel holds
+ *   max_points_in_cell points when the point's turn comes).  Without `outcome` nothing is stored per point.
+ * Synchronous on the map's context.
+ * Meaning: the counts describe the insertion step of the insert that would come next, before any LRU purge that insert might
+ *   trigger.  When it triggers none: mh_map_get_stats' n_points after minus before == n_added, n_voxels after minus before ==
+ *   n_new_voxels, and the points that appear in mh_map_get_cloud are exactly the points with outcome 1.
+ * Nothing observable moves: the eight fields of mh_map_get_stats (uploads and upload_bytes included), mh_map_get_cloud,
+ *   mh_map_knn, the LRU stamps and counter and every factor on the map are what they were; a later real insert gives the map
+ *   that a never-previewed twin gets, bit for bit.  The call writes nothing that factors read, so — unlike the inserts — it does
+ *   not wait for the streams of other contexts that hold factors on the map.
+ * n == 0: MH_OK, all zeros.
+ * Refusals, each with the map untouched and usable: MH_ERR_INVALID_ARG for a NULL map or `out` (mh_last_error(NULL) names the
+ *   function), for R without t or the reverse; MH_ERR_UNSUPPORTED for a NaN point, a voxel coordinate beyond +-2^20, a batch too
+ *   large or a total above 2^27 voxels, as the insert; MH_ERR_HIP on a map a failed mutation left inconsistent.
+ * The sharded inserts (mh_map_insert_shard*) have no preview. */
+int mh_map_preview_insert(mh_map * map, const float * xyz, size_t n, size_t stride_floats, mh_map_insert_preview * out, uint8_t * outcome);
+int mh_map_preview_insert_device(mh_map * map, const void * d_points, size_t n, size_t stride_floats, const float * R, const float * t,
+                                 mh_map_insert_preview * out, uint8_t * outcome);
+int mh_map_preview_insert_from_scan(mh_map * map, const mh_scan * scan, const float R_W_Be[9], const float t_W_Be[3],
+                                    mh_map_insert_preview * out, uint8_t * outcome);
 /* Deep copy — IncrementalVoxelMapPCL copy ctor (incremental_voxel_map.hpp:33-42) used by Geometric::updateMap's
  * copy-then-insert (geometric.cpp:494): device to device, both maps stay writable. */
 int mh_map_copy(const mh_map * map, mh_map ** out);

@@ -20,7 +20,7 @@ MH_OK, MH_ERR_INVALID_ARG, MH_ERR_HIP, MH_ERR_NO_DEVICE, MH_ERR_OOM, MH_ERR_UNSU
 EXPORTS = [
     "mh_abi_version", "mh_init", "mh_shutdown", "mh_last_error", "mh_set_profiling",
     "mh_stream", "mh_synchronize", "mh_timer_begin", "mh_timer_end",
-    "mh_map_create", "mh_map_insert", "mh_map_insert_device", "mh_map_insert_from_scan", "mh_map_copy", "mh_map_retain", "mh_map_release", "mh_map_get_stats",
+    "mh_map_create", "mh_map_insert", "mh_map_insert_device", "mh_map_insert_from_scan", "mh_map_preview_insert", "mh_map_preview_insert_device", "mh_map_preview_insert_from_scan", "mh_map_copy", "mh_map_retain", "mh_map_release", "mh_map_get_stats",
     "mh_map_get_cloud", "mh_map_knn",
     "mh_icp_create", "mh_icp_clone", "mh_icp_destroy", "mh_icp_linearize", "mh_icp_linearize_async",
     "mh_icp_wait", "mh_icp_linearize_batch", "mh_icp_get_state", "mh_icp_reset", "mh_icp_set_components", "mh_icp_size",
@@ -88,6 +88,11 @@ class MapConfig(C.Structure):
 class MapStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_voxels", "n_points", "n_blocks", "device_bytes", "uploads", "upload_bytes",
                                          "delta_uploads", "full_uploads")]
+
+
+class MapInsertPreview(C.Structure):
+    """mh_map_insert_preview: what the next insert of a batch would do (48 bytes)."""
+    _fields_ = [(n, C.c_int64) for n in ("n_points", "n_added", "n_too_close", "n_voxel_full", "n_touched_voxels", "n_new_voxels")]
 
 
 class IcpResult(C.Structure):
@@ -686,6 +691,9 @@ def load(build_if_missing: bool = True):
     L.mh_map_insert.argtypes = [vp, vp, sz, sz]
     L.mh_map_insert_device.argtypes = [vp, vp, sz, sz, vp, vp]
     L.mh_map_insert_from_scan.argtypes = [vp, vp, vp, vp]
+    L.mh_map_preview_insert.argtypes = [vp, vp, sz, sz, C.POINTER(MapInsertPreview), vp]
+    L.mh_map_preview_insert_device.argtypes = [vp, vp, sz, sz, vp, vp, C.POINTER(MapInsertPreview), vp]
+    L.mh_map_preview_insert_from_scan.argtypes = [vp, vp, vp, vp, C.POINTER(MapInsertPreview), vp]
     L.mh_map_copy.argtypes = [vp, pvp]
     L.mh_map_retain.argtypes = [vp]
     L.mh_map_release.argtypes = [vp]
@@ -923,6 +931,44 @@ class VoxelMap:
         R = np.ascontiguousarray(R_W_Be, np.float32)
         t = np.ascontiguousarray(t_W_Be, np.float32)
         self.ctx.check(self.L.mh_map_insert_from_scan(self.h, scan.h, _p(R), _p(t)))
+
+    @staticmethod
+    def _preview_dict(pv, outcome):
+        d = {n: getattr(pv, n) for n, _ in pv._fields_}
+        if outcome is not None:
+            d["outcome"] = outcome
+        return d
+
+    def preview_insert(self, xyz, want_outcome=False):
+        """mh_map_preview_insert: what insert(xyz) would do, read-only.  The six counts, plus `outcome` (uint8 per point:
+        1 added, 2 too close, 3 voxel full) when asked for."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        pv = MapInsertPreview()
+        oc = np.zeros(xyz.shape[0], np.uint8) if want_outcome else None
+        self.ctx.check(self.L.mh_map_preview_insert(self.h, _p(xyz), xyz.shape[0], 3, C.byref(pv), _p(oc)))
+        return self._preview_dict(pv, oc)
+
+    def preview_insert_device(self, d_points, n, stride_floats, R=None, t=None, want_outcome=False):
+        """mh_map_preview_insert_device: the same for n points at a device address, optionally through the f32 transform."""
+        R = np.ascontiguousarray(R, np.float32) if R is not None else None
+        t = np.ascontiguousarray(t, np.float32) if t is not None else None
+        pv = MapInsertPreview()
+        oc = np.zeros(n, np.uint8) if want_outcome else None
+        self.ctx.check(self.L.mh_map_preview_insert_device(self.h, d_points, n, stride_floats, _p(R), _p(t), C.byref(pv), _p(oc)))
+        return self._preview_dict(pv, oc)
+
+    def preview_insert_from_scan(self, scan, R_W_Be, t_W_Be, want_outcome=False):
+        """mh_map_preview_insert_from_scan: what insert_from_scan(scan, R, t) would do, read-only."""
+        R = np.ascontiguousarray(R_W_Be, np.float32)
+        t = np.ascontiguousarray(t_W_Be, np.float32)
+        pv = MapInsertPreview()
+        oc = None
+        if want_outcome:
+            d, n = C.c_void_p(), C.c_size_t()
+            self.ctx.check(self.L.mh_scan_device_points(scan.h, Scan.BODY, C.byref(d), C.byref(n)))
+            oc = np.zeros(n.value, np.uint8)
+        self.ctx.check(self.L.mh_map_preview_insert_from_scan(self.h, scan.h, _p(R), _p(t), C.byref(pv), _p(oc)))
+        return self._preview_dict(pv, oc)
 
     def copy(self):
         h = C.c_void_p()

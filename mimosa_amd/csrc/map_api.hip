@@ -9,6 +9,7 @@
 
 #include <cstring>
 #include <new>
+#include <string>
 
 #include "mh_internal.hpp"
 
@@ -266,10 +267,54 @@ int insert_device(mh_map * m, const float * d_src, size_t n, size_t stride, cons
   return MH_OK;
 }
 
+// What insert_device would do to this batch, without doing it: phase A as the insert runs it, then phase C's rule on buckets held
+// in registers (map_preview_points_kernel).  Nothing a reader of the map sees is written — only the insert scratch and the
+// per-insert words of the state block — so the streams of other contexts' factors are not waited for.  One wait for the device.
+int preview_device(mh_map * m, const char * who, const float * d_src, size_t n, size_t stride, const float * d_Rt12, mh_map_insert_preview * out,
+                   uint8_t * outcome)
+{
+  mh_ctx * ctx = m->ctx;
+  std::memset(out, 0, sizeof(*out));
+  if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": batch too large");
+  if (m->poisoned) return fail(ctx, MH_ERR_HIP, std::string(who) + ": the map is inconsistent after a failed mutation");
+  if (n == 0) return MH_OK;
+  int rc = ensure_scratch(m, n);
+  if (rc != MH_OK) return rc;
+  const size_t words = 2 * n * sizeof(uint32_t);
+  MH_HIP(ctx, m->s_preview.reserve(words + n, ctx->stream, false));
+  uint32_t * seg_close = static_cast<uint32_t *>(m->s_preview.p);
+  uint8_t * d_outcome = outcome ? reinterpret_cast<uint8_t *>(m->s_preview.p) + words : nullptr;
+  const mh::InsertScratch s = scratch_of(m);
+  const mh::MapArrays a = arrays_of(m);
+  MH_HIP(ctx, mh::launch_map_insert_prepare(a, d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), d_Rt12, m->inv_leaf, s, ctx->stream));
+  // a rejected batch (bad_coord) is grouped well-formed under voxel (0,0,0) and the kernel below only reads: it can run before the
+  // flag has been looked at, which spares a second wait
+  MH_HIP(ctx, mh::launch_map_preview_points(a, static_cast<uint32_t>(n), m->n_voxels, static_cast<uint32_t>(m->cfg.max_points_in_cell), m->min_sq, s,
+                                            seg_close, seg_close + n, d_outcome, ctx->stream));
+  rc = fetch_state(m);
+  if (rc != MH_OK) return rc;
+  if (m->h_state->bad_coord) {
+    (void)push_state(m);  // clears the flag, as the insert does
+    return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": a point is NaN or its voxel coordinate exceeds +-2^20");
+  }
+  if (static_cast<uint64_t>(m->n_voxels) + m->h_state->n_new_voxels >= (1u << 27)) return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": more than 2^27 voxels");
+  if (outcome) {
+    MH_HIP(ctx, hipMemcpyAsync(outcome, d_outcome, n, hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  out->n_points = static_cast<int64_t>(n);
+  out->n_added = m->h_state->preview[0];
+  out->n_too_close = m->h_state->preview[1];
+  out->n_voxel_full = m->h_state->preview[2];
+  out->n_touched_voxels = m->h_state->n_segments;
+  out->n_new_voxels = m->h_state->n_new_voxels;
+  return MH_OK;
+}
+
 void map_free(mh_map * m)
 {
   for (DevBuf * b : {&m->d_table, &m->d_cells, &m->d_buckets, &m->d_qbuckets, &m->d_vox, &m->d_lru, &m->s_in, &m->s_pts, &m->s_group, &m->s_seg_vid,
-                     &m->s_seg_added, &m->s_blk_new, &m->s_flags, &m->s_pos, &m->s_temp, &m->s_rt, &m->s_shard})
+                     &m->s_seg_added, &m->s_blk_new, &m->s_flags, &m->s_pos, &m->s_temp, &m->s_rt, &m->s_shard, &m->s_preview})
     b->release();
   if (m->d_state) dev_free(m->d_state);
   if (m->h_state) (void)hipHostFree(m->h_state);
@@ -332,7 +377,7 @@ int mh_map_create(mh_ctx * ctx, const mh_map_config * cfg, mh_map ** out)
 }
 
 // the batch goes to the device through pinned staging as packed xyz (a pageable strided source would copy at a few GB/s)
-static int stage_batch(mh_map * map, const float * xyz, size_t n, size_t stride_floats)
+static int stage_batch(mh_map * map, const float * xyz, size_t n, size_t stride_floats, bool count_upload = true)
 {
   mh_ctx * ctx = map->ctx;
   if (n > (size_t(1) << 40) / 12) return fail(ctx, MH_ERR_OOM, "mh_map_insert: batch too large");
@@ -356,7 +401,7 @@ static int stage_batch(mh_map * map, const float * xyz, size_t n, size_t stride_
   }
   MH_HIP(ctx, map->s_in.reserve(bytes, ctx->stream, false));
   MH_HIP(ctx, hipMemcpyAsync(map->s_in.p, st, bytes, hipMemcpyHostToDevice, ctx->stream));
-  map->upload_bytes += static_cast<int64_t>(bytes);
+  if (count_upload) map->upload_bytes += static_cast<int64_t>(bytes);  // a preview is no upload of the map's (mh_map_get_stats)
   return MH_OK;
 }
 
@@ -479,6 +524,53 @@ int mh_map_insert_from_scan(mh_map * map, const mh_scan * scan, const float R_W_
   if (!scan->preprocessed) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_insert_from_scan: no mh_scan_preprocess_geometric before");
   if (scan->ctx->device != map->ctx->device) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_insert_from_scan: scan lives on another device");
   return mh_map_insert_device(map, scan->d_body.p, scan->n_body, sizeof(mh_point32) / sizeof(float), R_W_Be, t_W_Be);
+}
+
+int mh_map_preview_insert(mh_map * map, const float * xyz, size_t n, size_t stride_floats, mh_map_insert_preview * out, uint8_t * outcome)
+{
+  if (!map || !out || (!xyz && n)) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_preview_insert: NULL argument");
+  mh_ctx * ctx = map->ctx;
+  return guarded(ctx, "mh_map_preview_insert", [&]() -> int {
+    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert: stride_floats must be >= 3");
+    MH_HIP(ctx, mh_enter(ctx));
+    if (n && n <= 0x3fffffffu && !map->poisoned) {
+      const int rc = stage_batch(map, xyz, n, stride_floats, false);
+      if (rc != MH_OK) return rc;
+    }
+    return preview_device(map, "mh_map_preview_insert", static_cast<const float *>(map->s_in.p), n, 3, nullptr, out, outcome);
+  });
+}
+
+int mh_map_preview_insert_device(mh_map * map, const void * d_points, size_t n, size_t stride_floats, const float * R, const float * t,
+                                 mh_map_insert_preview * out, uint8_t * outcome)
+{
+  if (!map || !out || (!d_points && n)) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_preview_insert_device: NULL argument");
+  mh_ctx * ctx = map->ctx;
+  return guarded(ctx, "mh_map_preview_insert_device", [&]() -> int {
+    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_device: stride_floats must be >= 3");
+    if ((R == nullptr) != (t == nullptr)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_device: R and t go together");
+    MH_HIP(ctx, mh_enter(ctx));
+    const float * d_rt = nullptr;
+    if (R) {
+      float rt[12];
+      std::memcpy(rt, R, 9 * sizeof(float));
+      std::memcpy(rt + 9, t, 3 * sizeof(float));
+      MH_HIP(ctx, map->s_rt.reserve(sizeof(rt), ctx->stream, false));
+      MH_HIP(ctx, hipMemcpyAsync(map->s_rt.p, rt, sizeof(rt), hipMemcpyHostToDevice, ctx->stream));
+      MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // rt is a stack buffer
+      d_rt = static_cast<const float *>(map->s_rt.p);
+    }
+    return preview_device(map, "mh_map_preview_insert_device", static_cast<const float *>(d_points), n, stride_floats, d_rt, out, outcome);
+  });
+}
+
+int mh_map_preview_insert_from_scan(mh_map * map, const mh_scan * scan, const float R_W_Be[9], const float t_W_Be[3], mh_map_insert_preview * out,
+                                    uint8_t * outcome)
+{
+  if (!map || !scan || !out) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_preview_insert_from_scan: NULL argument");
+  if (!scan->preprocessed) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_from_scan: no mh_scan_preprocess_geometric before");
+  if (scan->ctx->device != map->ctx->device) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_from_scan: scan lives on another device");
+  return mh_map_preview_insert_device(map, scan->d_body.p, scan->n_body, sizeof(mh_point32) / sizeof(float), R_W_Be, t_W_Be, out, outcome);
 }
 
 int mh_map_copy(const mh_map * src, mh_map ** out)

@@ -40,7 +40,7 @@ struct MapState
   uint32_t bad_coord;     // a coordinate did not fit kVoxCoordBits
   uint32_t n_keep;        // LRU purge: voxels that survive
   uint32_t cloud_points;  // get_cloud: total points
-  uint32_t pad[3];
+  uint32_t preview[3];    // insert preview: points it would add / refuse as too close / refuse because their voxel is full
 };
 
 // Everything the insert / purge kernels need to reach the map arrays.
@@ -78,6 +78,11 @@ hipError_t launch_map_create_voxels(const MapArrays & m, uint32_t n, uint32_t n_
 // phase C: FlatContainer::add per touched voxel, one wave each; cell words, counts, lru; publishes n_voxels, n_points
 hipError_t launch_map_insert_points(const MapArrays & m, uint32_t n, uint32_t n_voxels_after, uint32_t max_pts, double min_sq,
                                     double inv_leaf, unsigned long long lru_counter, const InsertScratch & s, hipStream_t stream);
+// insert preview, after phase A and INSTEAD of phases B and C: phase C's rule per touched voxel on a bucket held in registers,
+// nothing of the map is written.  seg_close / seg_full: n words each; outcome: n bytes (1 added, 2 too close, 3 voxel full,
+// at the point's input index) or null.  Publishes MapState::preview.
+hipError_t launch_map_preview_points(const MapArrays & m, uint32_t n, uint32_t n_voxels_before, uint32_t max_pts, double min_sq,
+                                     const InsertScratch & s, uint32_t * seg_close, uint32_t * seg_full, uint8_t * outcome, hipStream_t stream);
 // hash table of a new capacity from the block coordinates stored in the old one
 hipError_t launch_map_rehash(const int4 * old_table, uint32_t old_cap, int4 * new_table, uint32_t new_cap, hipStream_t stream);
 // LRU purge (iVox: voxels with lru + horizon < counter are erased, the rest keep their order): flags + count,

@@ -309,6 +309,122 @@ __global__ __launch_bounds__(1024) void map_totals_kernel(const MapArrays m, con
   }
 }
 
+// ---- insert preview (read-only) --------------------------------------------------------------------------
+// Phase C's rule on a bucket held in registers only: what map_insert_points_kernel would do to every point of the batch,
+// with nothing written to the map.  Same segment order, same fp64 expression, same 64-candidates-per-trip structure.
+// A segment whose voxel the map does not hold yet (seg_vid >= n_voxels_before; phase B did not run) starts empty and reads
+// neither m.vox nor m.buckets at that id.  Per-point outcome under the sequential rule: 3 = the bucket holds max_pts points
+// when the point's turn comes, else 2 = a resident or earlier-kept point lies within min_dist, else 1 = added.  Within a
+// trip the bucket fills up at the candidate that takes the last slot: every later candidate is "full", every earlier one
+// that was not taken was blocked by a point kept before its turn ("too close").
+__global__ __launch_bounds__(kT) void map_preview_points_kernel(const MapArrays m, const float4 * pts, const uint32_t * __restrict__ idx_unsorted,
+                                                                 uint32_t * idx_sorted, uint32_t * idx_tmp, const uint2 * __restrict__ seg,
+                                                                 const uint32_t * seg_vid, uint32_t n_voxels_before, uint32_t * seg_added,
+                                                                 uint32_t * seg_close, uint32_t * seg_full, uint8_t * outcome, uint32_t max_pts,
+                                                                 double min_sq)
+{
+  __shared__ uint32_t sort_lds[kT / 64][2][vg::kLdsSort];
+  const uint32_t ns = m.state->n_segments;
+  const uint32_t lane = threadIdx.x & 63u, wave_in_block = threadIdx.x >> 6;
+  const uint32_t wave = (blockIdx.x * kT + threadIdx.x) >> 6, n_waves = (gridDim.x * kT) >> 6;
+  for (uint32_t s = wave; s < ns; s += n_waves) {
+    const uint2 sg = seg[s];
+    const uint32_t vid = __builtin_amdgcn_readfirstlane(seg_vid[s]), s0 = __builtin_amdgcn_readfirstlane(sg.x),
+                   len = __builtin_amdgcn_readfirstlane(sg.y), s1 = s0 + len;
+    const uint32_t first_chunk = vg::sort_segment_indices(idx_unsorted, idx_sorted, idx_tmp, sort_lds[wave_in_block][0], sort_lds[wave_in_block][1], s0, len);
+    uint32_t count = 0;
+    if (vid < n_voxels_before) count = static_cast<uint32_t>(m.vox[vid].w);
+    float fx = 0.f, fy = 0.f, fz = 0.f;  // this lane's bucket point
+    if (lane < count) {
+      const float4 b = m.buckets[static_cast<size_t>(vid) * kBucketStride + lane];
+      fx = b.x;
+      fy = b.y;
+      fz = b.z;
+    }
+    uint32_t n_add = 0, n_close = 0, n_full = 0;
+    for (uint32_t base = s0; base < s1; base += 64u) {
+      const uint32_t sp = base + lane;
+      const bool valid = sp < s1;
+      const uint32_t n_valid = min(s1 - base, 64u);
+      uint32_t pi = 0;
+      float px = 0.f, py = 0.f, pz = 0.f;
+      if (valid) {
+        pi = vg::sorted_index_at(first_chunk, sort_lds[wave_in_block][0], idx_sorted, s0, len, sp);
+        const float4 p = pts[pi];
+        px = p.x;
+        py = p.y;
+        pz = p.z;
+      }
+      uint64_t added = 0ull;      // lanes of this trip that the insert would keep
+      uint32_t full_from = 64u;   // first lane of this trip whose turn comes with the bucket full
+      if (count >= max_pts) {
+        full_from = 0u;  // where the insert stops looking at the segment
+      } else {
+        const double qx = static_cast<double>(px), qy = static_cast<double>(py), qz = static_cast<double>(pz);
+        bool blocked = !valid;
+        for (uint32_t i = 0; i < count; ++i) {
+          const double dx = static_cast<double>(lane_value(fx, i)) - qx, dy = static_cast<double>(lane_value(fy, i)) - qy,
+                       dz = static_cast<double>(lane_value(fz, i)) - qz;
+          blocked = blocked || ((dx * dx + dz * dz) + (dy * dy + 0.0)) < min_sq;
+        }
+        uint64_t open = __ballot(!blocked);
+        while (open != 0ull && count < max_pts) {
+          const uint32_t u = static_cast<uint32_t>(__ffsll(static_cast<long long>(open))) - 1u;
+          const float ux = lane_value(px, u), uy = lane_value(py, u), uz = lane_value(pz, u);
+          if (lane == count) {
+            fx = ux;
+            fy = uy;
+            fz = uz;
+          }
+          ++count;
+          added |= 1ull << u;
+          if (count >= max_pts) full_from = u + 1u;
+          const double dx = static_cast<double>(ux) - qx, dy = static_cast<double>(uy) - qy, dz = static_cast<double>(uz) - qz;
+          blocked = blocked || ((dx * dx + dz * dz) + (dy * dy + 0.0)) < min_sq;
+          open = __ballot(!blocked) & (u == 63u ? 0ull : (~0ull << (u + 1u)));
+        }
+      }
+      const uint32_t t_add = static_cast<uint32_t>(__popcll(added));
+      const uint32_t t_full = full_from < n_valid ? n_valid - full_from : 0u;
+      n_add += t_add;
+      n_full += t_full;
+      n_close += n_valid - t_add - t_full;
+      if (outcome != nullptr && valid) outcome[pi] = ((added >> lane) & 1ull) ? uint8_t(1) : (lane >= full_from ? uint8_t(3) : uint8_t(2));
+    }
+    if (lane == 0) {
+      seg_added[s] = n_add;
+      seg_close[s] = n_close;
+      seg_full[s] = n_full;
+    }
+  }
+}
+
+// the three per-segment counts folded by one workgroup, like map_totals_kernel; the totals go into the state block's spare words
+__global__ __launch_bounds__(1024) void map_preview_totals_kernel(const MapArrays m, const uint32_t * seg_added, const uint32_t * seg_close,
+                                                                   const uint32_t * seg_full)
+{
+  __shared__ uint32_t s_w[3][16];
+  const uint32_t ns = m.state->n_segments;
+  uint32_t t[3] = {0u, 0u, 0u};  // a batch holds < 2^30 points
+  for (uint32_t s = threadIdx.x; s < ns; s += 1024u) {
+    t[0] += seg_added[s];
+    t[1] += seg_close[s];
+    t[2] += seg_full[s];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int mk = 32; mk >= 1; mk >>= 1) t[k] += __shfl_xor(t[k], mk, 64);
+    if ((threadIdx.x & 63u) == 0u) s_w[k][threadIdx.x >> 6] = t[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    uint32_t tot = 0;
+    for (int w = 0; w < 16; ++w) tot += s_w[threadIdx.x][w];
+    m.state->preview[threadIdx.x] = tot;
+  }
+}
+
 __global__ __launch_bounds__(kT) void map_rehash_kernel(const int4 * old_table, uint32_t old_cap, int4 * new_table, uint32_t new_mask)
 {
   for (uint32_t i = blockIdx.x * kT + threadIdx.x; i < old_cap; i += gridDim.x * kT) {
@@ -466,6 +582,18 @@ hipError_t launch_map_insert_points(const MapArrays & m, uint32_t n, uint32_t n_
   hipLaunchKernelGGL(map_insert_points_kernel, dim3(grid > 0 ? grid : 1), dim3(kT), 0, stream, m, s.pts, B.idx_unsorted, B.idx_sorted, B.idx_tmp,
                      B.seg, s.seg_vid, s.seg_added, max_pts, min_sq, inv_leaf, lru_counter);
   hipLaunchKernelGGL(map_totals_kernel, dim3(1), dim3(1024), 0, stream, m, s.seg_added, n_voxels_after);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_preview_points(const MapArrays & m, uint32_t n, uint32_t n_voxels_before, uint32_t max_pts, double min_sq,
+                                     const InsertScratch & s, uint32_t * seg_close, uint32_t * seg_full, uint8_t * outcome, hipStream_t stream)
+{
+  const vg::Buffers B = vg::carve(s.group, n);
+  const size_t waves = static_cast<size_t>(n);  // <= one wave per point (segments <= points)
+  const int grid = static_cast<int>(std::min<size_t>((waves * 64 + kT - 1) / kT, 16384));
+  hipLaunchKernelGGL(map_preview_points_kernel, dim3(grid > 0 ? grid : 1), dim3(kT), 0, stream, m, s.pts, B.idx_unsorted, B.idx_sorted, B.idx_tmp,
+                     B.seg, s.seg_vid, n_voxels_before, s.seg_added, seg_close, seg_full, outcome, max_pts, min_sq);
+  hipLaunchKernelGGL(map_preview_totals_kernel, dim3(1), dim3(1024), 0, stream, m, s.seg_added, seg_close, seg_full);
   return hipGetLastError();
 }
 

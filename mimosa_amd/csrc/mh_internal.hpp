@@ -607,6 +607,7 @@ struct mh_map
   uint64_t n_points = 0, lru_counter = 0;
   // insert scratch (grown on demand, reused)
   DevBuf s_in, s_pts, s_group, s_seg_vid, s_seg_added, s_blk_new, s_flags, s_pos, s_temp, s_rt, s_shard;
+  DevBuf s_preview;  // mh_map_preview_insert*: [too close | voxel full] per segment (n words each), then n outcome bytes
   void * h_in = nullptr;  // pinned staging of a host batch
   size_t h_in_cap = 0;
   int64_t inserts = 0, upload_bytes = 0, purges = 0;

@@ -59,6 +59,9 @@ struct GeometricConfig
   int ring_skip_divisor = 1;
   float map_keyframe_trans_thresh = 0.1f;
   float map_keyframe_rot_thresh_deg = 10;
+  // Not in the reference: > 0 replaces the pose test of updateMap by what the test stands in for (geometric.cpp:460-464) — the
+  // scan becomes a keyframe when an insert preview says the map would keep at least this fraction of its points.  0 = the pose test.
+  double map_keyframe_min_new_fraction = 0;
   size_t initial_clouds_to_force_map_update = 10;
   size_t lru_horizon = 100;
   size_t neighbor_voxel_mode = 7;
@@ -145,6 +148,32 @@ public:
     float Rt[12];
     toFloat12(T_W_Be, Rt);
     ctx_->check(mh_map_insert_from_scan(map_, scan, Rt, Rt + 9), "mh_map_insert_from_scan");
+  }
+  // What insert() / insertBodyCloud() would do to the map, read-only (mh_map_preview_insert*): counts of the points it would keep,
+  // refuse as too close, refuse because their voxel is full; outcome (optional) receives one byte per point.
+  mh_map_insert_preview previewInsert(const PointCloud & cloud, uint8_t * outcome = nullptr)
+  {
+    ensure();
+    mh_map_insert_preview pv{};
+    ctx_->check(mh_map_preview_insert(map_, cloud.empty() ? nullptr : &cloud[0].x, cloud.size(), sizeof(Point) / sizeof(float), &pv, outcome),
+                "mh_map_preview_insert");
+    return pv;
+  }
+  mh_map_insert_preview previewInsert(const float * xyz, size_t n, uint8_t * outcome = nullptr)
+  {
+    ensure();
+    mh_map_insert_preview pv{};
+    ctx_->check(mh_map_preview_insert(map_, xyz, n, 3, &pv, outcome), "mh_map_preview_insert");
+    return pv;
+  }
+  mh_map_insert_preview previewInsertBodyCloud(mh_scan * scan, const Pose3 & T_W_Be, uint8_t * outcome = nullptr)
+  {
+    ensure();
+    float Rt[12];
+    toFloat12(T_W_Be, Rt);
+    mh_map_insert_preview pv{};
+    ctx_->check(mh_map_preview_insert_from_scan(map_, scan, Rt, Rt + 9, &pv, outcome), "mh_map_preview_insert_from_scan");
+    return pv;
   }
   // incremental_voxel_map.cpp:26-32: true iff k neighbours were found; coordinates instead of ids
   bool knn_search(const V3D & point, const size_t k, std::vector<V3D> & neighbours, std::vector<double> & sq_dists)
@@ -1391,6 +1420,10 @@ struct GeometricDebug
   bool degen_rot_bool[3] = {false, false, false}, degen_trans_bool[3] = {false, false, false};
   int n_linearize_calls = 0;
   bool map_updated = false;
+  // GeometricConfig::map_keyframe_min_new_fraction > 0: n_added / n_points of the insert preview updateMap decided by, and its
+  // counts; -1 and zeros when no preview ran (switch off, forced update, first keyframe)
+  double map_new_fraction = -1;
+  mh_map_insert_preview map_preview{};
 };
 
 class Geometric
@@ -1487,7 +1520,27 @@ public:
     if (factor_) debug_.n_linearize_calls = factor_->getLinearizeCount();
     const Pose3 T_W_Be = values.at<Pose3>(key);
     bool update_map = true;
-    if (!map_poses_.empty()) {
+    debug_.map_new_fraction = -1;
+    debug_.map_preview = mh_map_insert_preview{};
+    if (config.map_keyframe_min_new_fraction > 0) {
+      // the quantity the pose test is a proxy for (geometric.cpp:460-464): what the map would keep of this scan.  Forced updates
+      // and the first keyframe need no preview; the pose test is not evaluated.
+      if (!map_poses_.empty() && initial_clouds_to_force_map_update_ == 0) {
+        mh_map_insert_preview pv{};
+        if (device_scan_) {
+          pv = ivox_map_->previewInsertBodyCloud(device_scan_->underlying(), T_W_Be);
+        } else {
+          PointCloud W = Be_cloud_;
+          float Rt[12];
+          toFloat12(T_W_Be, Rt);
+          if (!W.empty()) ctx_->check(mh_transform_f32(ctx_->get(), W.data(), W.size(), Rt, Rt + 9), "mh_transform_f32");
+          pv = ivox_map_->previewInsert(W);
+        }
+        debug_.map_preview = pv;
+        debug_.map_new_fraction = pv.n_points > 0 ? static_cast<double>(pv.n_added) / static_cast<double>(pv.n_points) : 0.0;
+        update_map = static_cast<double>(pv.n_added) >= config.map_keyframe_min_new_fraction * static_cast<double>(pv.n_points);
+      }
+    } else if (!map_poses_.empty()) {
       float min_diff_trans = std::numeric_limits<float>::max();
       size_t min_diff_index = 0;
       for (size_t i = 0; i < map_poses_.size(); ++i) {

@@ -58,6 +58,10 @@ class ReplayConfig:
     between_sigma_trans: float = 1e-2
     keyframe_trans_thresh: float = 1.0                # ENWIDE: map_keyframe_trans_thresh
     keyframe_rot_thresh_deg: float = 20.0
+    # > 0: the keyframe decision is made by what the pose test stands in for (geometric.cpp:460-464) — a scan becomes a keyframe when an
+    # insert preview of its body cloud at the estimated pose (mh_map_preview_insert_from_scan) says the map would keep at least this
+    # fraction of its points; the first scan always is one.  0: the reference's pose test.  HipBackend only; not in the native replay
+    keyframe_new_fraction: float = 0.0
     photometric: bool = True
     # every scan's photometric factor stays in the window on its own pose (released with the pose) and all of them are
     # re-linearized per iteration, as the reference's smoother does; off: the photometric factor on the newest pose only
@@ -416,6 +420,10 @@ class HipBackend:
         self.map.release()
         self.map = new
 
+    def preview_map(self, R, t):
+        """keyframe_new_fraction: what update_map(R, t) would add to the map, without the copy and the insert (the six counts)"""
+        return self.map.preview_insert_from_scan(self.scan, R, t)
+
     def photo_update_map(self, pf, R, t):
         self.photo.update_map(pf, R, t, synth_photo.BIAS_DIRECTIONS)
 
@@ -524,6 +532,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
     _check_window_marginal(cfg, RuntimeError)
     if cfg.relocalise_first:
         raise RuntimeError("relocalise_first is only offered by the python replay with HipBackend")
+    if cfg.keyframe_new_fraction > 0:
+        raise RuntimeError("keyframe_new_fraction is only offered by the python replay with HipBackend")
     exe = build.build_replay_native()
     path = os.path.join(workdir, "replay_input.bin")
     write_native_input(path, cfg, scans, rng_seed)
@@ -576,7 +586,10 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         raise ValueError("relocalise_first aligns the first scan itself: not offered together with init_align")
     if cfg.relocalise_batch and not cfg.relocalise_first:
         raise ValueError("relocalise_batch is only offered with relocalise_first")
+    if cfg.keyframe_new_fraction > 0 and not hasattr(backend, "preview_map"):
+        raise ValueError("keyframe_new_fraction needs a backend with mh_map_preview_insert (HipBackend)")
     relocalised = None
+    new_fraction, kf_scans = [], []
     backend.seed_map(synth.make_room(synth.BASE_SEED, 0, 0, room=np.asarray(cfg.room)))
     stage = {"front_end": 0.0, "imu": 0.0, "factor_create": 0.0, "optimise": 0.0, "update_map": 0.0}
     v_body = np.asarray(cfg.v, float)
@@ -769,7 +782,11 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         # ---- Geometric::updateMap's keyframe test (geometric.cpp:445-478): nearest stored pose by translation, then
         # the largest of |yaw|, |pitch|, |roll| of the relative rotation against the threshold
         is_kf = True
-        if kf_poses:
+        if cfg.keyframe_new_fraction > 0:  # first keyframe, or the map would keep enough of the scan; the pose test is not evaluated
+            pv = backend.preview_map(R, t)
+            new_fraction.append(pv["n_added"] / pv["n_points"] if pv["n_points"] else 0.0)
+            is_kf = not kf_poses or pv["n_added"] >= cfg.keyframe_new_fraction * pv["n_points"]
+        elif kf_poses:
             dists = [np.linalg.norm(t - tk) for _, tk in kf_poses]
             j = int(np.argmin(dists))
             d = kf_poses[j][0].T @ R
@@ -778,6 +795,7 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         if is_kf:
             backend.update_map(R, t)
             kf_poses.append((R, t))
+            kf_scans.append(k)
             n_kf += 1
         if cfg.photometric:
             if pf is not None:
@@ -803,4 +821,5 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     rerr = [float(np.rad2deg(np.linalg.norm(_so3_log(Re.T @ s["R_gt"])))) for (Re, _), s in zip(est, scans)]
     return {"poses_est": est, "trans_err": terr, "rot_err_deg": rerr, "n_keyframes": n_kf, "seconds": total,
             "scans_per_s": len(scans) / total, "stage_s": stage, "costs": costs, "photo_valid": n_photo_valid,
-            "photo_in_window": n_photo_window, "marginal_valid": marginal_valid, "separator_sizes": separator_sizes, "relocalised": relocalised}
+            "photo_in_window": n_photo_window, "marginal_valid": marginal_valid, "separator_sizes": separator_sizes, "relocalised": relocalised,
+            "new_fraction": new_fraction, "keyframe_scans": kf_scans}
