@@ -947,6 +947,95 @@ __device__ __forceinline__ void null_vector3(const double a00, const double a01,
   }
 }
 
+// Rayleigh quotient v'Av of a unit vector
+__device__ __forceinline__ double rayleigh3(const double a00, const double a01, const double a02, const double a11, const double a12,
+                                            const double a22, const double (&v)[3])
+{
+  const double Av0 = a00 * v[0] + a01 * v[1] + a02 * v[2], Av1 = a01 * v[0] + a11 * v[1] + a12 * v[2],
+               Av2 = a02 * v[0] + a12 * v[1] + a22 * v[2];
+  return v[0] * Av0 + v[1] * Av1 + v[2] * Av2;
+}
+
+// The rare lanes of plane_eigen (below), from where Newton on the cubic stopped (x): Rayleigh refinement on the matrix, then a
+// deflation that decides on the matrix which eigenvalue is the smallest.
+struct PlaneEigenHard
+{
+  double w0, w1, w2, v0, v1, v2;
+};
+__device__ __attribute__((noinline)) PlaneEigenHard plane_eigen_hard(const double a00, const double a01, const double a02, const double a11,
+                                                                     const double a12, const double a22, const double c2, const double x)
+{
+  double v[3], w1, w2;
+  double w0 = x;
+  null_vector3(a00, a01, a02, a11, a12, a22, w0, v);
+#pragma unroll 1
+  for (int r = 0; r < 8; ++r) {  // three rounds, then until the quotient stands still (a tight cluster of three needs more)
+    const double rq = rayleigh3(a00, a01, a02, a11, a12, a22, v);
+    const bool done = r >= 3 && fabs(rq - w0) <= 4e-16 * c2;
+    w0 = rq;
+    if (done) break;
+    null_vector3(a00, a01, a02, a11, a12, a22, w0, v);
+  }
+  // (w0, v) is an eigenpair of A now, but of WHICH eigenvalue the cubic cannot say once its roots lie nearer to each other
+  // than it resolves them (three eigenvalues within ~1e-5 relative: the Rayleigh rounds then settle on whichever is nearest
+  // to where Newton stopped; the zoo found a normal 90 degrees off) or when it is noise (rank 1, above).  So deflate on the
+  // matrix: the other two eigenpairs are those of A restricted to v's complement, a 2 x 2 problem with a closed, stable answer.
+  w0 = rayleigh3(a00, a01, a02, a11, a12, a22, v);
+  const double f0 = fabs(v[0]), f1 = fabs(v[1]), f2 = fabs(v[2]);
+  double u1[3];  // v x (the axis v has least of), normalised; u2 = v x u1
+  if (f0 <= f1 && f0 <= f2) {
+    u1[0] = 0.0;
+    u1[1] = v[2];
+    u1[2] = -v[1];
+  } else if (f1 <= f2) {
+    u1[0] = -v[2];
+    u1[1] = 0.0;
+    u1[2] = v[0];
+  } else {
+    u1[0] = v[1];
+    u1[1] = -v[0];
+    u1[2] = 0.0;
+  }
+  const double iu = mh_rsqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);  // >= 2/3: v is a unit vector
+  u1[0] *= iu;
+  u1[1] *= iu;
+  u1[2] *= iu;
+  const double u2[3] = {v[1] * u1[2] - v[2] * u1[1], v[2] * u1[0] - v[0] * u1[2], v[0] * u1[1] - v[1] * u1[0]};
+  const double A2[3] = {a00 * u2[0] + a01 * u2[1] + a02 * u2[2], a01 * u2[0] + a11 * u2[1] + a12 * u2[2],
+                        a02 * u2[0] + a12 * u2[1] + a22 * u2[2]};
+  const double b11 = rayleigh3(a00, a01, a02, a11, a12, a22, u1), b12 = u1[0] * A2[0] + u1[1] * A2[1] + u1[2] * A2[2],
+               b22 = u2[0] * A2[0] + u2[1] * A2[1] + u2[2] * A2[2];
+  const double h = 0.5 * (b11 + b22), d = 0.5 * (b11 - b22), rr = sqrt(d * d + b12 * b12);
+  const double lo = h - rr, hi = h + rr;
+  if (lo < w0) {
+    // the smallest eigenvalue lives in the complement: its vector there from the row of B - lo I that does not cancel,
+    // then Rayleigh rounds again (the complement is only as invariant as v was an eigenvector)
+    double y0 = d >= 0.0 ? -b12 : rr - d, y1 = d >= 0.0 ? d + rr : -b12;
+    const double ny = y0 * y0 + y1 * y1;
+    const double iy = ny > 0.0 ? mh_rsqrt(ny) : 0.0;
+    y0 = ny > 0.0 ? y0 * iy : 1.0;
+    y1 *= iy;
+    v[0] = y0 * u1[0] + y1 * u2[0];
+    v[1] = y0 * u1[1] + y1 * u2[1];
+    v[2] = y0 * u1[2] + y1 * u2[2];
+    w1 = fmin(w0, hi);
+    w2 = fmax(w0, hi);
+    w0 = lo;
+#pragma unroll 1
+    for (int r = 0; r < 4; ++r) {
+      const double rq = rayleigh3(a00, a01, a02, a11, a12, a22, v);
+      const bool done = fabs(rq - w0) <= 4e-16 * c2;
+      w0 = rq;
+      if (done) break;
+      null_vector3(a00, a01, a02, a11, a12, a22, w0, v);
+    }
+  } else {
+    w1 = lo;
+    w2 = hi;
+  }
+  return {w0, w1, w2, v[0], v[1], v[2]};
+}
+
 // Eigen-decomposition of a symmetric PSD 3x3 (covariance of k points) for the plane fit:
 // eigenvalues ascending + unit eigenvector of the smallest.  Replaces the
 // Eigen::SelfAdjointEigenSolver call of estimatePlane (geometric_factor.hpp:196), which only consumes
@@ -955,6 +1044,8 @@ __device__ __forceinline__ void null_vector3(const double a00, const double a01,
 //       matrix p is increasing and concave on [0, w0], so the iterates rise monotonically to the
 //       smallest root with no overshoot; convergence is quadratic (<= 6 steps from 0 in fp64).
 //   w1, w2: the deflated quadratic.  v0: best-conditioned cross product of two rows of A - w0 I.
+//   Lanes whose cubic does not resolve its roots (a close pair, a tight cluster of three, a needle or a line of neighbours)
+//   leave through plane_eigen_hard (above).  tests/test_gpu_plane_zoo.py holds all of it to an mpmath reference.
 // fp64 throughout; |dw| ~ eps |A|, far inside the 1e-5 parity bar and the plane gates' margins.
 // (The trigonometric closed form costs three fp64 transcendental calls per point: 2x this.)
 __device__ __forceinline__ void plane_eigen(const double a00, const double a01, const double a02, const double a11,
@@ -965,13 +1056,18 @@ __device__ __forceinline__ void plane_eigen(const double a00, const double a01, 
   const double c0 = a00 * (a11 * a22 - a12 * a12) - a01 * (a01 * a22 - a12 * a02) + a02 * (a01 * a12 - a11 * a02);
   double x = 0.0;
 #pragma unroll 1
-  for (int it = 0; it < 8; ++it) {
+  for (int it = 0; it < 64; ++it) {
     const double p = ((x - c2) * x + c1) * x - c0;
     const double dp = (3.0 * x - 2.0 * c2) * x + c1;
     if (!(dp > 0.0)) break;
     const double step = p * mh_rcp1(dp);  // (a Newton step need not be divided exactly: the fixed point is p(x) = 0 either way)
     x -= step;
     if (fabs(step) <= 1e-16 * fabs(x)) break;
+    // Eight steps as a rule.  With w1 within ~2 w0 (yet outside the 25 % of the refinement below) the linear phase lasts longer
+    // and eight steps ended up to 6e-8 |A| short, the normal 1e-9 off (the zoo's pair family).  Newton's error obeys
+    // e' <= e^2 |p''| / (2 p'), and the step is e: go on while that still predicts more than rounding (one step more, rarely
+    // two).  A converged lane's step is the cubic's noise, eps c2^3 / c1, whose square stays below this: it ends as it always has.
+    if (it >= 7 && !(step * step * fabs(3.0 * x - c2) > 4e-16 * c2 * dp)) break;
   }
   double w0 = x;
   null_vector3(a00, a01, a02, a11, a12, a22, w0, v);
@@ -986,7 +1082,12 @@ __device__ __forceinline__ void plane_eigen(const double a00, const double a01, 
     // "w1 - w0 < 25 % of w1", i.e. w1 < (4/3) w0, without extracting w1: w1, w2 are the roots of t^2 - S0 t + P0, so the test
     // point t = (4/3) w0 lies at or above w1 iff the quadratic is <= 0 there or t is already past the roots' midpoint
     const double S0 = c2 - w0, P0 = c1 - w0 * S0, tq = (4.0 / 3.0) * w0;
-    if (tq >= 0.5 * S0 || (tq - S0) * tq + P0 <= 0.0) {
+    // The same lanes also where the cubic itself is not to be trusted.  c0 carries eps c2^3 of rounding, so its root carries
+    // eps c2^3 / c1 ~ eps c2^2 / w1: beyond 1e-12 c2 once w1 < 1e-4 c2, a needle of a neighbourhood.  At rank 1 (collinear
+    // neighbours, as lattice-like maps have them) c1 and c0 are pure noise, and Newton on noise has returned the LARGEST
+    // eigenvalue (status Line where the reference says MinEigenValueLow); a smallest eigenvalue cannot exceed a third of the trace.
+    const bool off = c1 < 1e-4 * (c2 * c2) || 3.0 * w0 > c2;
+    if (off || tq >= 0.5 * S0 || (tq - S0) * tq + P0 <= 0.0) {
       double prev = kDblMax;
 #pragma unroll 1
       for (int it = 0; it < 56; ++it) {
@@ -999,15 +1100,15 @@ __device__ __forceinline__ void plane_eigen(const double a00, const double a01, 
         prev = fabs(step);
         if (fabs(step) <= 1e-16 * fabs(x)) break;
       }
-      w0 = x;
-      null_vector3(a00, a01, a02, a11, a12, a22, w0, v);
-#pragma unroll 1
-      for (int r = 0; r < 3; ++r) {
-        const double Av0 = a00 * v[0] + a01 * v[1] + a02 * v[2], Av1 = a01 * v[0] + a11 * v[1] + a12 * v[2],
-                     Av2 = a02 * v[0] + a12 * v[1] + a22 * v[2];
-        w0 = v[0] * Av0 + v[1] * Av1 + v[2] * Av2;
-        null_vector3(a00, a01, a02, a11, a12, a22, w0, v);
-      }
+      // (out of line: the usual lane never gets here, and inlined its registers would cost the whole kernel a wave of occupancy)
+      const PlaneEigenHard r = plane_eigen_hard(a00, a01, a02, a11, a12, a22, c2, x);
+      w[0] = r.w0;
+      w[1] = r.w1;
+      w[2] = r.w2;
+      v[0] = r.v0;
+      v[1] = r.v1;
+      v[2] = r.v2;
+      return;
     }
   }
   const double S = c2 - w0;               // w1 + w2

@@ -1,5 +1,8 @@
 // CPU check of mh::sym_eigen3 (non-iterative, verified, Jacobi fallback) against mh::sym_eigen3_jacobi on 400 000 random symmetric
 // PSD matrices: well separated, two eigenvalues within 1e-6 / 1e-9, rank deficient, multiples of the identity, scales 1e-3 .. 1e9.
+// Compiled for the host, this covers the HOST branches of math3.hpp only (1.0 / x, std::sqrt); the __HIP_DEVICE_COMPILE__
+// branches (mh_rcp1, mh_rsqrt) are reached through K3's plane_eigen / null_vector3 in tests/test_gpu_plane_zoo.py (designed
+// spectra against an mpmath reference) and through K4's bases in tests/test_gpu_reported_basis.py.
 #include <cstdio>
 #include <random>
 #include <cmath>
