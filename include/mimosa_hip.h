@@ -241,6 +241,91 @@ int mh_map_preview_insert_device(mh_map * map, const void * d_points, size_t n, 
                                  mh_map_insert_preview * out, uint8_t * outcome);
 int mh_map_preview_insert_from_scan(mh_map * map, const mh_scan * scan, const float R_W_Be[9], const float t_W_Be[3],
                                     mh_map_insert_preview * out, uint8_t * outcome);
+/* Map carving: remove the map points a new scan sees through.  Not in the reference, whose map only grows or loses whole
+ * voxels by age; a point a person, a door or a vehicle left in a voxel the robot keeps observing stays there for good.
+ *
+ * The rule is a visibility test on a direction grid (a cube map around the sensor), conservative on purpose, without any
+ * transcendental function.  All arithmetic is fp64, in the written order, without FMA contraction, so a restatement in numpy
+ * (tests/map_carve_ref.py) matches it decision for decision.
+ *
+ * Inputs: `obs`, n points (f32 xyz, `stride_floats` apart) in some frame F; origin_F[3], the sensor origin in F; R_W_F[9]
+ *   (row-major), t_W_F[3], the pose of F in the map frame, in doubles; and a config:
+ *     grid N, 4 .. 512;  ring, 0 .. 2;  range_min, with 0 < range_min < range_max;  range_max;  margin_abs >= 0;
+ *     margin_rel >= 0;  apply, 0 or 1.  All real values must be finite.
+ *
+ * Direction cell of a vector s = (s0, s1, s2), a cube map:
+ *   1. Let a_k = |s_k|.
+ *   2. The major axis f is 0 if a0 >= a1 and a0 >= a2, else 1 if a1 >= a2, else 2.
+ *   3. m = a_f.  A vector with m == 0 has no cell (nor has one with a component that is not finite).
+ *   4. face = 2f + (s_f < 0).
+ *   5. (u, v) = (s_{(f+1)%3} / m, s_{(f+2)%3} / m).
+ *   6. i = min(N-1, (int)floor((u + 1.0) * (0.5 * N))).
+ *   7. j is formed the same way from v.
+ *   8. cell = (face * N + j) * N + i.
+ *
+ * Observation image, 6 N^2 doubles, initially "not hit":
+ *   1. For each obs point with finite coordinates, s = p - origin_F.  The f32 coordinates are widened first.
+ *   2. r2 = (s0*s0 + s1*s1) + s2*s2.
+ *   3. If r2 >= range_min^2 (and s has a cell), the point's cell takes min(cell, r2).
+ *   4. Points beyond range_max still count.  They prove free space up to themselves.
+ *
+ * Map point test, for a bucket point p (f32 widened):
+ *   1. d = p - t_W_F.
+ *   2. s_a = ((R[a]*d0 + R[3+a]*d1) + R[6+a]*d2) - origin_F[a].  That is R^T d, with R row-major.
+ *   3. r2 is computed as above.  r = sqrt(r2).
+ *   4. The point is TESTED iff range_min^2 <= r2 <= range_max^2 (and s has a cell).
+ *   5. The point is SEEN THROUGH iff both conditions hold:
+ *      - Every cell (i+di, j+dj) with |di|, |dj| <= ring that lies inside [0, N) on the point's own face is hit.  Cells off
+ *        the face are ignored.
+ *      - With q the minimum of those cells and lim = r + (margin_abs + margin_rel * r), lim * lim < q.
+ *   ring = 0 trusts a single cell, whose nearest return may belong to a surface beside the ray: in a 20 x 16 x 5 m room scanned
+ *   with 64 x 1024 beams it removed hundreds to thousands of static points, ring = 1 none (at N = 64 and 128, margin 0.3 m).  A
+ *   grid finer than the scan (N = 256 for 64 rows) leaves cells unhit and removes nothing.
+ *
+ * apply = 1: seen-through points leave their buckets.  A bucket's survivors keep their relative order and move to the front;
+ *   the coarse copies, the voxel's count and its cell word in every block table it sits in follow.  A voxel left with no
+ *   point is erased (a cell word with count 0 does not exist).  The surviving voxels keep their order and their LRU stamps;
+ *   ids, block table and cell words are rebuilt exactly as the LRU purge rebuilds them.  The LRU counter and mh_map_get_stats'
+ *   uploads and upload_bytes do not move.  The call is a mutation like the insert: it waits for the streams of the contexts
+ *   that hold factors on the map, is synchronous, and refuses a map a failed mutation left inconsistent.  Factors created
+ *   before the call keep per-point association state that names the old map: mh_icp_reset them.
+ * apply = 0 (preview): the same counts, and nothing observable moves — mh_map_preview_insert's contract, including not
+ *   waiting for readers.
+ *
+ * n == 0: MH_OK, nothing removed.
+ * Refusals, each with the map untouched and usable: MH_ERR_INVALID_ARG for a NULL argument, a stride below 3, a config
+ *   outside the stated ranges, a pose entry or origin that is not finite, `which` outside 0 .. 1, a scan without that stage
+ *   or on another device; MH_ERR_UNSUPPORTED for a batch too large, as the insert; MH_ERR_HIP on an inconsistent map. */
+typedef struct mh_map_carve_config {
+  int32_t grid;       /* N: cells per cube-face edge, 4 .. 512 */
+  int32_t ring;       /* 0 .. 2: neighbour cells on the point's face that must agree */
+  double range_min;   /* m; observations nearer than this are not used, map points nearer than this not tested */
+  double range_max;   /* m; map points farther than this are not tested */
+  double margin_abs;  /* m */
+  double margin_rel;  /* per metre of range */
+  int32_t apply;      /* 0 = preview, 1 = carve */
+  int32_t reserved;   /* 0 */
+} mh_map_carve_config; /* 48 bytes */
+
+typedef struct mh_map_carve_result {
+  int64_t n_obs_used;        /* observation points that entered the image */
+  int64_t n_cells_hit;       /* cells of the image that are hit */
+  int64_t n_tested;          /* map points inside the range gates */
+  int64_t n_removed;         /* of those, seen through */
+  int64_t n_voxels_touched;  /* voxels that lose at least one point */
+  int64_t n_voxels_emptied;  /* of those, voxels that lose all of theirs */
+} mh_map_carve_result; /* 48 bytes */
+
+int mh_map_carve(mh_map * map, const float * xyz, size_t n, size_t stride_floats, const double origin_F[3], const double R_W_F[9],
+                 const double t_W_F[3], const mh_map_carve_config * cfg, mh_map_carve_result * out);
+/* The same for a batch that is already on the map's device (d_points: device pointer). */
+int mh_map_carve_device(mh_map * map, const void * d_points, size_t n, size_t stride_floats, const double origin_F[3], const double R_W_F[9],
+                        const double t_W_F[3], const mh_map_carve_config * cfg, mh_map_carve_result * out);
+/* The same straight from a device-resident scan.  which = 0: points_full_, the deskewed cloud in the lidar frame (the origin is
+ * usually zero; needs mh_scan_prepare_input*); which = 1: Be_cloud_, the body frame (the origin is the caller's t_B_L; needs
+ * mh_scan_preprocess_geometric). */
+int mh_map_carve_from_scan(mh_map * map, const mh_scan * scan, int which, const double origin_F[3], const double R_W_F[9],
+                           const double t_W_F[3], const mh_map_carve_config * cfg, mh_map_carve_result * out);
 /* Deep copy — IncrementalVoxelMapPCL copy ctor (incremental_voxel_map.hpp:33-42) used by Geometric::updateMap's
  * copy-then-insert (geometric.cpp:494): device to device, both maps stay writable. */
 int mh_map_copy(const mh_map * map, mh_map ** out);

@@ -27,6 +27,7 @@ SOURCES = [
     ("chain_api.hip", []),
     ("map_kernels.hip", ["-ffp-contract=off"]),
     ("map_api.hip", []),
+    ("carve_kernels.hip", ["-ffp-contract=off"]),  # the host build of carve_device.hpp (tests/cpp/map_carve_cells.cpp) gives the same digits
     ("shard_kernels.hip", []),
     ("shard_api.hip", []),
     ("photo_kernels.hip", ["-ffp-contract=off"]),
@@ -43,7 +44,7 @@ SOURCES = [
     ("reloc_kernels.hip", ["-ffp-contract=off"]),  # likewise reloc_device.hpp (tests/cpp/reloc_select.cpp)
     ("reloc_api.hip", []),
 ]
-HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "window_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", "reloc_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
+HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "window_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", "reloc_device.hpp", "carve_device.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
 
 
 def _hipcc() -> str:
@@ -211,6 +212,7 @@ HOST_TESTS = {
     "window_marginal_step": ("window_marginal_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "window_joint_step": ("window_joint_step.cpp", ["window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "reloc_select": ("reloc_select.cpp", ["reloc_device.hpp", "voxel_map.hpp", "math3.hpp"]),
+    "map_carve_cells": ("map_carve_cells.cpp", ["carve_device.hpp", "math3.hpp"]),
 }
 
 

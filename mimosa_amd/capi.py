@@ -20,7 +20,7 @@ MH_OK, MH_ERR_INVALID_ARG, MH_ERR_HIP, MH_ERR_NO_DEVICE, MH_ERR_OOM, MH_ERR_UNSU
 EXPORTS = [
     "mh_abi_version", "mh_init", "mh_shutdown", "mh_last_error", "mh_set_profiling",
     "mh_stream", "mh_synchronize", "mh_timer_begin", "mh_timer_end",
-    "mh_map_create", "mh_map_insert", "mh_map_insert_device", "mh_map_insert_from_scan", "mh_map_preview_insert", "mh_map_preview_insert_device", "mh_map_preview_insert_from_scan", "mh_map_copy", "mh_map_retain", "mh_map_release", "mh_map_get_stats",
+    "mh_map_create", "mh_map_insert", "mh_map_insert_device", "mh_map_insert_from_scan", "mh_map_preview_insert", "mh_map_preview_insert_device", "mh_map_preview_insert_from_scan", "mh_map_carve", "mh_map_carve_device", "mh_map_carve_from_scan", "mh_map_copy", "mh_map_retain", "mh_map_release", "mh_map_get_stats",
     "mh_map_get_cloud", "mh_map_knn",
     "mh_icp_create", "mh_icp_clone", "mh_icp_destroy", "mh_icp_linearize", "mh_icp_linearize_async",
     "mh_icp_wait", "mh_icp_linearize_batch", "mh_icp_get_state", "mh_icp_reset", "mh_icp_set_components", "mh_icp_size",
@@ -93,6 +93,21 @@ class MapStats(C.Structure):
 class MapInsertPreview(C.Structure):
     """mh_map_insert_preview: what the next insert of a batch would do (48 bytes)."""
     _fields_ = [(n, C.c_int64) for n in ("n_points", "n_added", "n_too_close", "n_voxel_full", "n_touched_voxels", "n_new_voxels")]
+
+
+class MapCarveConfig(C.Structure):
+    """mh_map_carve_config (48 bytes)."""
+    _fields_ = [("grid", C.c_int32), ("ring", C.c_int32), ("range_min", C.c_double), ("range_max", C.c_double), ("margin_abs", C.c_double),
+                ("margin_rel", C.c_double), ("apply", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapCarveResult(C.Structure):
+    """mh_map_carve_result (48 bytes)."""
+    _fields_ = [(n, C.c_int64) for n in ("n_obs_used", "n_cells_hit", "n_tested", "n_removed", "n_voxels_touched", "n_voxels_emptied")]
+
+
+def make_carve_config(grid=64, ring=1, range_min=0.5, range_max=60.0, margin_abs=0.3, margin_rel=0.0, apply=True) -> MapCarveConfig:
+    return MapCarveConfig(int(grid), int(ring), float(range_min), float(range_max), float(margin_abs), float(margin_rel), int(apply), 0)
 
 
 class IcpResult(C.Structure):
@@ -694,6 +709,9 @@ def load(build_if_missing: bool = True):
     L.mh_map_preview_insert.argtypes = [vp, vp, sz, sz, C.POINTER(MapInsertPreview), vp]
     L.mh_map_preview_insert_device.argtypes = [vp, vp, sz, sz, vp, vp, C.POINTER(MapInsertPreview), vp]
     L.mh_map_preview_insert_from_scan.argtypes = [vp, vp, vp, vp, C.POINTER(MapInsertPreview), vp]
+    L.mh_map_carve.argtypes = [vp, vp, sz, sz, vp, vp, vp, C.POINTER(MapCarveConfig), C.POINTER(MapCarveResult)]
+    L.mh_map_carve_device.argtypes = [vp, vp, sz, sz, vp, vp, vp, C.POINTER(MapCarveConfig), C.POINTER(MapCarveResult)]
+    L.mh_map_carve_from_scan.argtypes = [vp, vp, i32, vp, vp, vp, C.POINTER(MapCarveConfig), C.POINTER(MapCarveResult)]
     L.mh_map_copy.argtypes = [vp, pvp]
     L.mh_map_retain.argtypes = [vp]
     L.mh_map_release.argtypes = [vp]
@@ -969,6 +987,32 @@ class VoxelMap:
             oc = np.zeros(n.value, np.uint8)
         self.ctx.check(self.L.mh_map_preview_insert_from_scan(self.h, scan.h, _p(R), _p(t), C.byref(pv), _p(oc)))
         return self._preview_dict(pv, oc)
+
+    @staticmethod
+    def _carve_args(origin_F, R_W_F, t_W_F, cfg):
+        o, R, t = _f64(origin_F).reshape(3), _f64(R_W_F).reshape(9), _f64(t_W_F).reshape(3)
+        return o, R, t, (cfg if isinstance(cfg, MapCarveConfig) else make_carve_config(**cfg)), MapCarveResult()
+
+    def carve(self, obs_xyz, origin_F, R_W_F, t_W_F, cfg) -> dict:
+        """mh_map_carve: remove (cfg.apply) or count (preview) the map points the observations see through.  obs_xyz: points in a
+        frame F whose pose in the map frame is (R_W_F, t_W_F), sensor at origin_F in F.  cfg: MapCarveConfig or the keywords of
+        make_carve_config.  Returns the six counters."""
+        xyz = np.ascontiguousarray(obs_xyz, dtype=np.float32).reshape(-1, 3)
+        o, R, t, cfg, out = self._carve_args(origin_F, R_W_F, t_W_F, cfg)
+        self.ctx.check(self.L.mh_map_carve(self.h, _p(xyz), xyz.shape[0], 3, _p(o), _p(R), _p(t), C.byref(cfg), C.byref(out)))
+        return {n: getattr(out, n) for n, _ in out._fields_}
+
+    def carve_device(self, d_points, n, stride_floats, origin_F, R_W_F, t_W_F, cfg) -> dict:
+        """mh_map_carve_device: the same for n points at a device address."""
+        o, R, t, cfg, out = self._carve_args(origin_F, R_W_F, t_W_F, cfg)
+        self.ctx.check(self.L.mh_map_carve_device(self.h, d_points, n, stride_floats, _p(o), _p(R), _p(t), C.byref(cfg), C.byref(out)))
+        return {n: getattr(out, n) for n, _ in out._fields_}
+
+    def carve_from_scan(self, scan, which, origin_F, R_W_F, t_W_F, cfg) -> dict:
+        """mh_map_carve_from_scan: the same from a device-resident scan; which = Scan.FULL (lidar frame) or Scan.BODY (body frame)."""
+        o, R, t, cfg, out = self._carve_args(origin_F, R_W_F, t_W_F, cfg)
+        self.ctx.check(self.L.mh_map_carve_from_scan(self.h, scan.h, int(which), _p(o), _p(R), _p(t), C.byref(cfg), C.byref(out)))
+        return {n: getattr(out, n) for n, _ in out._fields_}
 
     def copy(self):
         h = C.c_void_p()

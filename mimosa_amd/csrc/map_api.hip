@@ -11,6 +11,7 @@
 #include <new>
 #include <string>
 
+#include "carve_device.hpp"
 #include "mh_internal.hpp"
 
 namespace
@@ -124,24 +125,15 @@ mh::InsertScratch scratch_of(const mh_map * m)
   return s;
 }
 
-// iVox's LRU purge (SURVEY.md Appendix B): voxels with lru + horizon < counter are erased, the survivors keep their
-// order; tables are rebuilt.  Everything stays on the device: the survivors are compacted into fresh arrays.
-int purge_lru(mh_map * m)
+// The compaction both erasures share (the LRU purge, and a carve that empties voxels): of the map's nv voxels those with
+// s_flags[v] != 0 survive, voxel v at id s_pos[v] (keep of them), in their order and with their LRU stamps; buckets, coarse
+// copies, coordinates and stamps move into fresh arrays, and the block table and every cell word are rebuilt from the
+// survivors' coordinates.
+int compact_voxels(mh_map * m, uint32_t nv, uint32_t keep, const char * what, const char * what_words)
 {
   mh_ctx * ctx = m->ctx;
-  if (m->n_voxels == 0) return MH_OK;
-  const uint32_t nv = m->n_voxels;
-  MH_HIP(ctx, m->s_flags.reserve(nv * sizeof(uint32_t), ctx->stream, false));
-  MH_HIP(ctx, m->s_pos.reserve(nv * sizeof(uint32_t), ctx->stream, false));
-  MH_HIP(ctx, m->s_temp.reserve(mh::map_temp_bytes(nv), ctx->stream, false));
+  int rc = MH_OK;
   mh::MapArrays a = arrays_of(m);
-  MH_HIP(ctx, mh::launch_map_purge_flags(a, nv, static_cast<unsigned long long>(m->cfg.lru_horizon), m->lru_counter,
-                                         static_cast<uint32_t *>(m->s_flags.p), static_cast<uint32_t *>(m->s_pos.p), m->s_temp.p, m->s_temp.cap,
-                                         ctx->stream));
-  int rc = fetch_state(m);
-  if (rc != MH_OK) return rc;
-  const uint32_t keep = m->h_state->n_keep;
-  if (keep == nv) return MH_OK;
   // fresh voxel arrays; the old ones are the compaction source
   DevBuf ob = m->d_buckets, oq = m->d_qbuckets, ov = m->d_vox, ol = m->d_lru;
   m->d_buckets = DevBuf{};
@@ -189,7 +181,7 @@ int purge_lru(mh_map * m)
     ov.release();
     ol.release();
     m->poisoned = true;
-    return rc != MH_OK ? rc : hip_fail(ctx, e, "mh_map_insert: LRU purge");
+    return rc != MH_OK ? rc : hip_fail(ctx, e, what);
   }
   m->n_blocks = m->h_state->n_blocks;
   m->n_points = m->h_state->n_points;
@@ -208,9 +200,32 @@ int purge_lru(mh_map * m)
     if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
     if (e2 != hipSuccess) {
       m->poisoned = true;
-      return hip_fail(ctx, e2, "mh_map_insert: LRU purge (cell words)");
+      return hip_fail(ctx, e2, what_words);
     }
   }
+  return MH_OK;
+}
+
+// iVox's LRU purge (SURVEY.md Appendix B): voxels with lru + horizon < counter are erased, the survivors keep their
+// order; tables are rebuilt.  Everything stays on the device: the survivors are compacted into fresh arrays.
+int purge_lru(mh_map * m)
+{
+  mh_ctx * ctx = m->ctx;
+  if (m->n_voxels == 0) return MH_OK;
+  const uint32_t nv = m->n_voxels;
+  MH_HIP(ctx, m->s_flags.reserve(nv * sizeof(uint32_t), ctx->stream, false));
+  MH_HIP(ctx, m->s_pos.reserve(nv * sizeof(uint32_t), ctx->stream, false));
+  MH_HIP(ctx, m->s_temp.reserve(mh::map_temp_bytes(nv), ctx->stream, false));
+  mh::MapArrays a = arrays_of(m);
+  MH_HIP(ctx, mh::launch_map_purge_flags(a, nv, static_cast<unsigned long long>(m->cfg.lru_horizon), m->lru_counter,
+                                         static_cast<uint32_t *>(m->s_flags.p), static_cast<uint32_t *>(m->s_pos.p), m->s_temp.p, m->s_temp.cap,
+                                         ctx->stream));
+  int rc = fetch_state(m);
+  if (rc != MH_OK) return rc;
+  const uint32_t keep = m->h_state->n_keep;
+  if (keep == nv) return MH_OK;
+  rc = compact_voxels(m, nv, keep, "mh_map_insert: LRU purge", "mh_map_insert: LRU purge (cell words)");
+  if (rc != MH_OK) return rc;
   m->purges++;
   return MH_OK;
 }
@@ -311,10 +326,101 @@ int preview_device(mh_map * m, const char * who, const float * d_src, size_t n, 
   return MH_OK;
 }
 
+// mh_map_carve* on a batch already on the device.  The image and the per-voxel words are scratch; with cfg.apply == 0 nothing else
+// is written (the counters travel in MapState::carve), so — like the insert preview — the streams of other contexts' factors
+// are not waited for.  With apply the buckets are compacted in place, and voxels left without a point are erased by the LRU
+// purge's compaction.
+int carve_check(const mh_ctx * ctx, const char * who, size_t stride, const double * origin, const double * R, const double * t,
+                const mh_map_carve_config & c)
+{
+  const std::string w(who);
+  if (stride < 3) return fail(ctx, MH_ERR_INVALID_ARG, w + ": stride_floats must be >= 3");
+  if (c.grid < mh::kCarveGridMin || c.grid > mh::kCarveGridMax) return fail(ctx, MH_ERR_INVALID_ARG, w + ": grid must be in 4..512");
+  if (c.ring < 0 || c.ring > mh::kCarveRingMax) return fail(ctx, MH_ERR_INVALID_ARG, w + ": ring must be in 0..2");
+  if (c.apply != 0 && c.apply != 1) return fail(ctx, MH_ERR_INVALID_ARG, w + ": apply must be 0 or 1");
+  for (double v : {c.range_min, c.range_max, c.margin_abs, c.margin_rel})
+    if (!std::isfinite(v)) return fail(ctx, MH_ERR_INVALID_ARG, w + ": a config value is not finite");
+  if (!(c.range_min > 0) || !(c.range_min < c.range_max)) return fail(ctx, MH_ERR_INVALID_ARG, w + ": 0 < range_min < range_max is required");
+  if (c.margin_abs < 0 || c.margin_rel < 0) return fail(ctx, MH_ERR_INVALID_ARG, w + ": margins must be >= 0");
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(R[i])) return fail(ctx, MH_ERR_INVALID_ARG, w + ": the pose is not finite");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(t[i]) || !std::isfinite(origin[i])) return fail(ctx, MH_ERR_INVALID_ARG, w + ": the pose or the origin is not finite");
+  return MH_OK;
+}
+
+int carve_device(mh_map * m, const char * who, const float * d_src, size_t n, size_t stride, const double * origin, const double * R, const double * t,
+                 const mh_map_carve_config & c, mh_map_carve_result * out)
+{
+  mh_ctx * ctx = m->ctx;
+  std::memset(out, 0, sizeof(*out));
+  if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": batch too large");
+  if (m->poisoned) return fail(ctx, MH_ERR_HIP, std::string(who) + ": the map is inconsistent after a failed mutation");
+  if (n == 0) return MH_OK;
+  if (c.apply) MH_HIP(ctx, map_wait_readers(m));
+  mh::CarveParams P;
+  std::memcpy(P.R, R, sizeof(P.R));
+  std::memcpy(P.t, t, sizeof(P.t));
+  std::memcpy(P.origin, origin, sizeof(P.origin));
+  P.range_min2 = c.range_min * c.range_min;
+  P.range_max2 = c.range_max * c.range_max;
+  P.margin_abs = c.margin_abs;
+  P.margin_rel = c.margin_rel;
+  P.N = c.grid;
+  P.ring = c.ring;
+  double sensor_W[3];  // for the per-voxel early-out only
+  for (int a = 0; a < 3; ++a) sensor_W[a] = R[3 * a] * origin[0] + R[3 * a + 1] * origin[1] + R[3 * a + 2] * origin[2] + t[a];
+  const uint32_t nv = m->n_voxels;
+  const size_t nvs = nv ? nv : 1;
+  MH_HIP(ctx, m->s_carve_img.reserve(mh::carve_image_bytes(c.grid), ctx->stream, false));
+  MH_HIP(ctx, m->s_carve_vox.reserve(nvs * sizeof(uint32_t), ctx->stream, false));
+  MH_HIP(ctx, m->s_flags.reserve(nvs * sizeof(uint32_t), ctx->stream, false));
+  if (c.apply) {  // what erasing emptied voxels needs, while a failure still leaves the map untouched
+    MH_HIP(ctx, m->s_pos.reserve(nvs * sizeof(uint32_t), ctx->stream, false));
+    MH_HIP(ctx, m->s_temp.reserve(mh::map_temp_bytes(nv), ctx->stream, false));
+  }
+  MH_HIP(ctx, mh::launch_carve_image(d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), P, m->s_carve_img.p, ctx->stream));
+  MH_HIP(ctx, mh::launch_carve_test(arrays_of(m), nv, P, m->s_carve_img.p, m->cfg.leaf_size, sensor_W, c.range_max, c.apply != 0,
+                                    static_cast<uint32_t *>(m->s_carve_vox.p), static_cast<uint32_t *>(m->s_flags.p), ctx->stream));
+  int rc = fetch_state(m);
+  if (rc != MH_OK) return rc;
+  const unsigned long long * c6 = m->h_state->carve;
+  out->n_obs_used = static_cast<int64_t>(c6[0]);
+  out->n_cells_hit = static_cast<int64_t>(c6[1]);
+  out->n_tested = static_cast<int64_t>(c6[2]);
+  out->n_removed = static_cast<int64_t>(c6[3]);
+  out->n_voxels_touched = static_cast<int64_t>(c6[4]);
+  out->n_voxels_emptied = static_cast<int64_t>(c6[5]);
+  if (!c.apply) return MH_OK;
+  m->n_points = m->h_state->n_points;
+  if (out->n_voxels_emptied == 0) return MH_OK;
+  // emptied voxels go the way the LRU purge's go: positions of the survivors, then the shared compaction.  Until it is through
+  // the map holds voxels without a point, which nothing else tolerates: a failure on the way leaves it marked unusable.
+  const hipError_t e = mh::launch_map_keep_positions(arrays_of(m), nv, static_cast<const uint32_t *>(m->s_flags.p), static_cast<uint32_t *>(m->s_pos.p),
+                                                     m->s_temp.p, m->s_temp.cap, ctx->stream);
+  rc = e == hipSuccess ? fetch_state(m) : hip_fail(ctx, e, who);
+  if (rc != MH_OK) {
+    m->poisoned = true;
+    return rc;
+  }
+  const uint32_t keep = m->h_state->n_keep;
+  const std::string what = std::string(who) + ": compaction", what_words = std::string(who) + ": compaction (cell words)";
+  rc = compact_voxels(m, nv, keep, what.c_str(), what_words.c_str());
+  if (rc != MH_OK) {
+    m->poisoned = true;  // also where the purge could go back to its old arrays: here they hold the emptied voxels
+    return rc;
+  }
+  if (m->n_blocks == 0) {  // nothing is left: block 0's table as mh_map_create leaves it
+    MH_HIP(ctx, hipMemsetAsync(m->d_cells.p, 0x00, mh::kCellsPerBlock * sizeof(uint32_t), ctx->stream));
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MH_OK;
+}
+
 void map_free(mh_map * m)
 {
   for (DevBuf * b : {&m->d_table, &m->d_cells, &m->d_buckets, &m->d_qbuckets, &m->d_vox, &m->d_lru, &m->s_in, &m->s_pts, &m->s_group, &m->s_seg_vid,
-                     &m->s_seg_added, &m->s_blk_new, &m->s_flags, &m->s_pos, &m->s_temp, &m->s_rt, &m->s_shard, &m->s_preview})
+                     &m->s_seg_added, &m->s_blk_new, &m->s_flags, &m->s_pos, &m->s_temp, &m->s_rt, &m->s_shard, &m->s_preview, &m->s_carve_img, &m->s_carve_vox})
     b->release();
   if (m->d_state) dev_free(m->d_state);
   if (m->h_state) (void)hipHostFree(m->h_state);
@@ -571,6 +677,52 @@ int mh_map_preview_insert_from_scan(mh_map * map, const mh_scan * scan, const fl
   if (!scan->preprocessed) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_from_scan: no mh_scan_preprocess_geometric before");
   if (scan->ctx->device != map->ctx->device) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_from_scan: scan lives on another device");
   return mh_map_preview_insert_device(map, scan->d_body.p, scan->n_body, sizeof(mh_point32) / sizeof(float), R_W_Be, t_W_Be, out, outcome);
+}
+
+int mh_map_carve(mh_map * map, const float * xyz, size_t n, size_t stride_floats, const double origin_F[3], const double R_W_F[9], const double t_W_F[3],
+                 const mh_map_carve_config * cfg, mh_map_carve_result * out)
+{
+  if (!map || !out || !cfg || !origin_F || !R_W_F || !t_W_F || (!xyz && n))
+    return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_carve: NULL argument");
+  mh_ctx * ctx = map->ctx;
+  return guarded(ctx, "mh_map_carve", [&]() -> int {
+    int rc = carve_check(ctx, "mh_map_carve", stride_floats, origin_F, R_W_F, t_W_F, *cfg);
+    if (rc != MH_OK) return rc;
+    MH_HIP(ctx, mh_enter(ctx));
+    if (n && n <= 0x3fffffffu && !map->poisoned) {
+      rc = stage_batch(map, xyz, n, stride_floats, false);  // no upload of the map's: upload_bytes does not move
+      if (rc != MH_OK) return rc;
+    }
+    return carve_device(map, "mh_map_carve", static_cast<const float *>(map->s_in.p), n, 3, origin_F, R_W_F, t_W_F, *cfg, out);
+  });
+}
+
+int mh_map_carve_device(mh_map * map, const void * d_points, size_t n, size_t stride_floats, const double origin_F[3], const double R_W_F[9],
+                        const double t_W_F[3], const mh_map_carve_config * cfg, mh_map_carve_result * out)
+{
+  if (!map || !out || !cfg || !origin_F || !R_W_F || !t_W_F || (!d_points && n))
+    return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_carve_device: NULL argument");
+  mh_ctx * ctx = map->ctx;
+  return guarded(ctx, "mh_map_carve_device", [&]() -> int {
+    const int rc = carve_check(ctx, "mh_map_carve_device", stride_floats, origin_F, R_W_F, t_W_F, *cfg);
+    if (rc != MH_OK) return rc;
+    MH_HIP(ctx, mh_enter(ctx));
+    return carve_device(map, "mh_map_carve_device", static_cast<const float *>(d_points), n, stride_floats, origin_F, R_W_F, t_W_F, *cfg, out);
+  });
+}
+
+int mh_map_carve_from_scan(mh_map * map, const mh_scan * scan, int which, const double origin_F[3], const double R_W_F[9], const double t_W_F[3],
+                           const mh_map_carve_config * cfg, mh_map_carve_result * out)
+{
+  if (!map || !scan || !out || !cfg || !origin_F || !R_W_F || !t_W_F)
+    return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: NULL argument");
+  if (which < 0 || which > 1) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: which must be 0 (points_full_) or 1 (Be_cloud_)");
+  if (!scan->prepared || (which == 1 && !scan->preprocessed)) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: that stage has not run");
+  if (scan->ctx->device != map->ctx->device) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: scan lives on another device");
+  const void * d = which == 0 ? scan->d_full.p : scan->d_body.p;
+  const size_t n = which == 0 ? static_cast<size_t>(scan->c.n_full) : scan->n_body;
+  if (n && !d) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: that stage has not run");
+  return mh_map_carve_device(map, d, n, sizeof(mh_point32) / sizeof(float), origin_F, R_W_F, t_W_F, cfg, out);
 }
 
 int mh_map_copy(const mh_map * src, mh_map ** out)

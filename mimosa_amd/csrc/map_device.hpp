@@ -41,6 +41,7 @@ struct MapState
   uint32_t n_keep;        // LRU purge: voxels that survive
   uint32_t cloud_points;  // get_cloud: total points
   uint32_t preview[3];    // insert preview: points it would add / refuse as too close / refuse because their voxel is full
+  unsigned long long carve[6];  // mh_map_carve*: the fields of mh_map_carve_result, in their order
 };
 
 // Everything the insert / purge kernels need to reach the map arrays.
@@ -55,6 +56,47 @@ struct MapArrays
   unsigned long long * lru;  // n_voxels: lru_counter at the last insert that touched the voxel
   MapState * state;       // device-visible (mapped pinned) counters
 };
+
+#if defined(__HIPCC__)
+// block id of block (bx, by, bz), or -1.  The table's load is <= 0.5, so an empty slot ends every probe.
+__device__ __forceinline__ int find_block(const MapArrays & m, int bx, int by, int bz)
+{
+  const uint64_t key = pack_coord_key(bx, by, bz);
+  uint32_t h = block_hash(bx, by, bz) & m.table_mask;
+  for (;;) {
+    const int4 e = m.table[h];
+    const uint64_t k = static_cast<uint64_t>(static_cast<uint32_t>(e.x)) | (static_cast<uint64_t>(static_cast<uint32_t>(e.y)) << 32);
+    if (k == kEmptyKey) return -1;
+    if (k == key) return e.z;
+    h = (h + 1) & m.table_mask;
+  }
+}
+
+// The <= 8 blocks whose halo'd table holds voxel (cx,cy,cz): its home block and, per axis, the neighbour it touches.
+// which in [0, 8): bit a selects the second block of axis a.  Returns false when that combination does not exist.
+__device__ __forceinline__ bool voxel_block(int cx, int cy, int cz, int which, int & bx, int & by, int & bz)
+{
+  const int c[3] = {cx, cy, cz};
+  int b[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int l = c[a] & (kBlockDim - 1);
+    b[a] = c[a] >> kBlockLog2;
+    if ((which >> a) & 1) {
+      if (l == 0)
+        b[a] -= 1;
+      else if (l == kBlockDim - 1)
+        b[a] += 1;
+      else
+        return false;
+    }
+  }
+  bx = b[0];
+  by = b[1];
+  bz = b[2];
+  return true;
+}
+#endif
 
 struct InsertScratch
 {
@@ -94,8 +136,23 @@ hipError_t launch_map_purge_compact(const MapArrays & src, const MapArrays & dst
 // (re)build table + cells from the voxel coordinates: claim blocks, then write every voxel's word
 hipError_t launch_map_claim_blocks(const MapArrays & m, uint32_t v0, uint32_t v1, hipStream_t stream);
 hipError_t launch_map_write_words(const MapArrays & m, uint32_t v0, uint32_t v1, hipStream_t stream);
+// positions of the kept voxels (exclusive scan of keep) and their number (MapState::n_keep): the second half of
+// launch_map_purge_flags, for callers that wrote the flags themselves
+hipError_t launch_map_keep_positions(const MapArrays & m, uint32_t n_voxels, const uint32_t * keep, uint32_t * pos, void * temp, size_t temp_bytes,
+                                     hipStream_t stream);
 // voxel_data(): all points in voxel order.  offsets: n_voxels + 1 scratch; out: packed xyz (3 floats per point)
 hipError_t launch_map_cloud(const MapArrays & m, uint32_t n_voxels, uint32_t * counts, uint32_t * offsets, float * out, size_t out_capacity_points,
                             void * temp, size_t temp_bytes, hipStream_t stream);
+
+// ---- map carving (carve_kernels.hip; the rule: carve_device.hpp) ------------------------------------------------
+struct CarveParams;
+size_t carve_image_bytes(int N);  // 6 N^2 cells + the call's observation counter
+// the observation image of n points `stride_floats` apart (device memory): a clear, then the 64-bit atomic-minimum splat
+hipError_t launch_carve_image(const float * src, uint32_t n, uint32_t stride_floats, const CarveParams & P, void * image, hipStream_t stream);
+// every map point against the image, one wave per voxel; apply: survivors compacted in their buckets, counts and cell words
+// follow.  per_voxel, keep: n_voxels words each (keep = 0 for a voxel left without a point).  Publishes MapState::carve, and
+// with apply MapState::n_points.
+hipError_t launch_carve_test(const MapArrays & m, uint32_t n_voxels, const CarveParams & P, const void * image, double leaf, const double sensor_W[3],
+                             double range_max, bool apply, uint32_t * per_voxel, uint32_t * keep, hipStream_t stream);
 
 }  // namespace mh

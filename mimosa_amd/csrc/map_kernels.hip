@@ -42,19 +42,6 @@ __device__ __forceinline__ void unpack_coord_key(uint64_t key, int & x, int & y,
   z = static_cast<int>(key & m) - kVoxCoordBias;
 }
 
-__device__ __forceinline__ int find_block(const MapArrays & m, int bx, int by, int bz)
-{
-  const uint64_t key = pack_coord_key(bx, by, bz);
-  uint32_t h = block_hash(bx, by, bz) & m.table_mask;
-  for (;;) {
-    const int4 e = m.table[h];
-    const uint64_t k = static_cast<uint64_t>(static_cast<uint32_t>(e.x)) | (static_cast<uint64_t>(static_cast<uint32_t>(e.y)) << 32);
-    if (k == kEmptyKey) return -1;
-    if (k == key) return e.z;
-    h = (h + 1) & m.table_mask;
-  }
-}
-
 // Claims a table slot for the block (no-op when it is there already).  Only the claiming thread assigns the id; readers
 // of ids run in a later kernel.
 __device__ __forceinline__ void claim_block(const MapArrays & m, int bx, int by, int bz)
@@ -71,31 +58,6 @@ __device__ __forceinline__ void claim_block(const MapArrays & m, int bx, int by,
     if (old == key) return;
     h = (h + 1) & m.table_mask;
   }
-}
-
-// The <= 8 blocks whose halo'd table holds voxel (cx,cy,cz): its home block and, per axis, the neighbour it touches.
-// which in [0, 8): bit a selects the second block of axis a.  Returns false when that combination does not exist.
-__device__ __forceinline__ bool voxel_block(int cx, int cy, int cz, int which, int & bx, int & by, int & bz)
-{
-  const int c[3] = {cx, cy, cz};
-  int b[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int l = c[a] & (kBlockDim - 1);
-    b[a] = c[a] >> kBlockLog2;
-    if ((which >> a) & 1) {
-      if (l == 0)
-        b[a] -= 1;
-      else if (l == kBlockDim - 1)
-        b[a] += 1;
-      else
-        return false;
-    }
-  }
-  bx = b[0];
-  by = b[1];
-  bz = b[2];
-  return true;
 }
 
 // ---- phase A ---------------------------------------------------------------------------------------------
@@ -608,6 +570,13 @@ hipError_t launch_map_purge_flags(const MapArrays & m, uint32_t n_voxels, unsign
 {
   if (!n_voxels) return hipSuccess;
   hipLaunchKernelGGL(map_purge_flags_kernel, dim3(grid_for(n_voxels)), dim3(kT), 0, stream, m.lru, n_voxels, horizon, lru_counter, keep);
+  return launch_map_keep_positions(m, n_voxels, keep, pos, temp, temp_bytes, stream);
+}
+
+hipError_t launch_map_keep_positions(const MapArrays & m, uint32_t n_voxels, const uint32_t * keep, uint32_t * pos, void * temp, size_t temp_bytes,
+                                     hipStream_t stream)
+{
+  if (!n_voxels) return hipSuccess;
   const hipError_t e = exclusive_sum(keep, pos, n_voxels, temp, temp_bytes, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(map_purge_count_kernel, dim3(1), dim3(kT), 0, stream, keep, pos, n_voxels, m.state);

@@ -608,6 +608,7 @@ struct mh_map
   // insert scratch (grown on demand, reused)
   DevBuf s_in, s_pts, s_group, s_seg_vid, s_seg_added, s_blk_new, s_flags, s_pos, s_temp, s_rt, s_shard;
   DevBuf s_preview;  // mh_map_preview_insert*: [too close | voxel full] per segment (n words each), then n outcome bytes
+  DevBuf s_carve_img, s_carve_vox;  // mh_map_carve*: the observation image (+ its counter); removed / tested / emptied per voxel
   void * h_in = nullptr;  // pinned staging of a host batch
   size_t h_in_cap = 0;
   int64_t inserts = 0, upload_bytes = 0, purges = 0;
@@ -616,7 +617,7 @@ struct mh_map
   // contexts (= HIP streams) that hold factors on this map: a mutation waits for THEIR streams, not for the whole device
   std::mutex readers_mu;
   std::vector<std::pair<mh_ctx *, int>> readers;
-  bool poisoned = false;  // a mutation failed half way (LRU purge): the device arrays and the counters disagree; every later call fails
+  bool poisoned = false;  // a mutation failed half way (LRU purge, carve): the device arrays and the counters disagree; every later call fails
 };
 
 inline void map_add_reader(mh_map * m, mh_ctx * c)

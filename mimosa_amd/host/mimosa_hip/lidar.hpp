@@ -62,6 +62,13 @@ struct GeometricConfig
   // Not in the reference: > 0 replaces the pose test of updateMap by what the test stands in for (geometric.cpp:460-464) — the
   // scan becomes a keyframe when an insert preview says the map would keep at least this fraction of its points.  0 = the pose test.
   double map_keyframe_min_new_fraction = 0;
+  // Not in the reference: > 0 carves the forked map by the keyframe's own scan before the insert (mh_map_carve*): map points the
+  // scan sees through, on a cube-map direction grid of this many cells per face edge, are removed.  0 = off, the reference's
+  // behaviour bit for bit.  The fields after it are mh_map_carve_config's.
+  int map_carve_grid = 0;
+  int map_carve_ring = 1;
+  double map_carve_range_min = 0.5, map_carve_range_max = 60.0;
+  double map_carve_margin_abs = 0.3, map_carve_margin_rel = 0.0;
   size_t initial_clouds_to_force_map_update = 10;
   size_t lru_horizon = 100;
   size_t neighbor_voxel_mode = 7;
@@ -174,6 +181,32 @@ public:
     mh_map_insert_preview pv{};
     ctx_->check(mh_map_preview_insert_from_scan(map_, scan, Rt, Rt + 9, &pv, outcome), "mh_map_preview_insert_from_scan");
     return pv;
+  }
+  // Map carving (mh_map_carve*): remove (cfg.apply) or count the map points that observations in a frame F — its pose in the map
+  // frame T_W_F, the sensor at origin_F in F — see through.  Not in the reference.
+  mh_map_carve_result carve(const PointCloud & cloud_F, const V3D & origin_F, const Pose3 & T_W_F, const mh_map_carve_config & cfg)
+  {
+    return carve(cloud_F.empty() ? nullptr : &cloud_F[0].x, cloud_F.size(), sizeof(Point) / sizeof(float), origin_F, T_W_F, cfg);
+  }
+  mh_map_carve_result carve(const float * xyz, size_t n, size_t stride_floats, const V3D & origin_F, const Pose3 & T_W_F,
+                            const mh_map_carve_config & cfg)
+  {
+    ensure();
+    const PoseRM T = rowMajor(T_W_F);
+    const A3 o = toArray(origin_F);
+    mh_map_carve_result r{};
+    ctx_->check(mh_map_carve(map_, xyz, n, stride_floats, o.data(), T.R.data(), T.t.data(), &cfg, &r), "mh_map_carve");
+    return r;
+  }
+  // ... by a device-resident scan: which = 0 points_full_ (the lidar frame), 1 Be_cloud_ (the body frame)
+  mh_map_carve_result carveFromScan(mh_scan * scan, int which, const V3D & origin_F, const Pose3 & T_W_F, const mh_map_carve_config & cfg)
+  {
+    ensure();
+    const PoseRM T = rowMajor(T_W_F);
+    const A3 o = toArray(origin_F);
+    mh_map_carve_result r{};
+    ctx_->check(mh_map_carve_from_scan(map_, scan, which, o.data(), T.R.data(), T.t.data(), &cfg, &r), "mh_map_carve_from_scan");
+    return r;
   }
   // incremental_voxel_map.cpp:26-32: true iff k neighbours were found; coordinates instead of ids
   bool knn_search(const V3D & point, const size_t k, std::vector<V3D> & neighbours, std::vector<double> & sq_dists)
@@ -1424,6 +1457,9 @@ struct GeometricDebug
   // counts; -1 and zeros when no preview ran (switch off, forced update, first keyframe)
   double map_new_fraction = -1;
   mh_map_insert_preview map_preview{};
+  // GeometricConfig::map_carve_grid > 0: what the carve before this keyframe's insert removed; zeros when none ran
+  bool map_carved = false;
+  mh_map_carve_result map_carve{};
 };
 
 class Geometric
@@ -1572,9 +1608,27 @@ public:
       initial_clouds_to_force_map_update_--;
     }
     debug_.map_updated = update_map;
+    debug_.map_carved = false;
+    debug_.map_carve = mh_map_carve_result{};
     if (!update_map) return;
     // world transform in f32 (:483-490), then copy-then-insert so live factors keep their snapshot (:494-495)
     ivox_map_ = ivox_map_->fork();  // device-to-device copy; the previous map lives on in the factors that hold it
+    if (config.map_carve_grid > 0) {
+      // the fork has no factor yet, so the carve disturbs nothing in the window.  Be_cloud_ is in the body frame, where the
+      // sensor sits at T_B_L's translation.
+      mh_map_carve_config cc{};
+      cc.grid = config.map_carve_grid;
+      cc.ring = config.map_carve_ring;
+      cc.range_min = config.map_carve_range_min;
+      cc.range_max = config.map_carve_range_max;
+      cc.margin_abs = config.map_carve_margin_abs;
+      cc.margin_rel = config.map_carve_margin_rel;
+      cc.apply = 1;
+      const V3D origin_B = config.T_B_L.translation();
+      debug_.map_carve = device_scan_ ? ivox_map_->carveFromScan(device_scan_->underlying(), 1, origin_B, T_W_Be, cc)
+                                      : ivox_map_->carve(Be_cloud_, origin_B, T_W_Be, cc);
+      debug_.map_carved = true;
+    }
     if (device_scan_) {
       ivox_map_->insertBodyCloud(device_scan_->underlying(), T_W_Be);  // transform + insert on the device
     } else {

@@ -62,6 +62,16 @@ class ReplayConfig:
     # insert preview of its body cloud at the estimated pose (mh_map_preview_insert_from_scan) says the map would keep at least this
     # fraction of its points; the first scan always is one.  0: the reference's pose test.  HipBackend only; not in the native replay
     keyframe_new_fraction: float = 0.0
+    # the forked map is carved by the keyframe's own scan at the estimated pose before the insert (mh_map_carve_from_scan on the body
+    # cloud): map points the scan sees through are removed.  Off: the reference's map, which only grows.  HipBackend only; not in the
+    # native replay.  The fields after it are mh_map_carve_config's.
+    carve_keyframes: bool = False
+    carve_grid: int = 64
+    carve_ring: int = 1
+    carve_range_min: float = 0.5
+    carve_range_max: float = 60.0
+    carve_margin_abs: float = 0.3
+    carve_margin_rel: float = 0.0
     photometric: bool = True
     # every scan's photometric factor stays in the window on its own pose (released with the pose) and all of them are
     # re-linearized per iteration, as the reference's smoother does; off: the photometric factor on the newest pose only
@@ -420,6 +430,19 @@ class HipBackend:
         self.map.release()
         self.map = new
 
+    def update_map_carved(self, R, t, carve_cfg):
+        """carve_keyframes: update_map with the fork carved by the scan's body cloud first (the replay's body frame is the lidar
+        frame: the sensor sits at its origin); returns the carve's six counters"""
+        new = self.map.copy()
+        counters = new.carve_from_scan(self.scan, self.capi.Scan.BODY, np.zeros(3), R, t, dict(carve_cfg, apply=True))
+        new.insert_from_scan(self.scan, R, t)
+        self.map.release()
+        self.map = new
+        return counters
+
+    def map_points(self):
+        return self.map.stats()["n_points"]
+
     def preview_map(self, R, t):
         """keyframe_new_fraction: what update_map(R, t) would add to the map, without the copy and the insert (the six counts)"""
         return self.map.preview_insert_from_scan(self.scan, R, t)
@@ -534,6 +557,8 @@ def run_native(cfg: ReplayConfig, scans, workdir, repeats=1, rng_seed=7, visible
         raise RuntimeError("relocalise_first is only offered by the python replay with HipBackend")
     if cfg.keyframe_new_fraction > 0:
         raise RuntimeError("keyframe_new_fraction is only offered by the python replay with HipBackend")
+    if cfg.carve_keyframes:
+        raise RuntimeError("carve_keyframes is only offered by the python replay with HipBackend")
     exe = build.build_replay_native()
     path = os.path.join(workdir, "replay_input.bin")
     write_native_input(path, cfg, scans, rng_seed)
@@ -588,8 +613,12 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
         raise ValueError("relocalise_batch is only offered with relocalise_first")
     if cfg.keyframe_new_fraction > 0 and not hasattr(backend, "preview_map"):
         raise ValueError("keyframe_new_fraction needs a backend with mh_map_preview_insert (HipBackend)")
+    if cfg.carve_keyframes and not hasattr(backend, "update_map_carved"):
+        raise ValueError("carve_keyframes needs a backend with mh_map_carve (HipBackend)")
+    carve_cfg = dict(grid=cfg.carve_grid, ring=cfg.carve_ring, range_min=cfg.carve_range_min, range_max=cfg.carve_range_max,
+                     margin_abs=cfg.carve_margin_abs, margin_rel=cfg.carve_margin_rel)
     relocalised = None
-    new_fraction, kf_scans = [], []
+    new_fraction, kf_scans, carved, map_points = [], [], [], []
     backend.seed_map(synth.make_room(synth.BASE_SEED, 0, 0, room=np.asarray(cfg.room)))
     stage = {"front_end": 0.0, "imu": 0.0, "factor_create": 0.0, "optimise": 0.0, "update_map": 0.0}
     v_body = np.asarray(cfg.v, float)
@@ -793,7 +822,12 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
             ypr = (np.arctan2(d[1, 0], d[0, 0]), np.arctan2(-d[2, 0], np.hypot(d[2, 1], d[2, 2])), np.arctan2(d[2, 1], d[2, 2]))
             is_kf = dists[j] > cfg.keyframe_trans_thresh or max(abs(a) for a in ypr) > cfg.keyframe_rot_thresh_deg * 0.017453293
         if is_kf:
-            backend.update_map(R, t)
+            if cfg.carve_keyframes:
+                carved.append(backend.update_map_carved(R, t, carve_cfg))
+            else:
+                backend.update_map(R, t)
+            if hasattr(backend, "map_points"):
+                map_points.append(backend.map_points())
             kf_poses.append((R, t))
             kf_scans.append(k)
             n_kf += 1
@@ -822,4 +856,4 @@ def run(cfg: ReplayConfig, backend, scans=None, rng_seed=7):
     return {"poses_est": est, "trans_err": terr, "rot_err_deg": rerr, "n_keyframes": n_kf, "seconds": total,
             "scans_per_s": len(scans) / total, "stage_s": stage, "costs": costs, "photo_valid": n_photo_valid,
             "photo_in_window": n_photo_window, "marginal_valid": marginal_valid, "separator_sizes": separator_sizes, "relocalised": relocalised,
-            "new_fraction": new_fraction, "keyframe_scans": kf_scans}
+            "new_fraction": new_fraction, "keyframe_scans": kf_scans, "carve": carved, "map_points": map_points}
