@@ -555,6 +555,109 @@ int mh_icp_relocalise(mh_icp * icp, const double * R, const double * t, size_t n
 int mh_icp_relocalise_batch(mh_icp * icp, mh_icp * const * work, size_t n_work, const double * R, const double * t,
                             size_t n_poses, const double g_unit[3], const mh_icp_reloc_config * cfg, mh_icp_reloc_result * out);
 
+/* ---- place recognition: scan descriptors and a keyframe database, searched on the device -----------
+ * mh_icp_score_poses and mh_icp_relocalise* search the candidate poses a caller hands them, in practice a grid around a
+ * guess.  This section answers "where in this map could this scan have been taken": a database of rotation-tolerant scan
+ * descriptors (a ring x sector height image in the style of Scan Context), searched by brute force over every entry and every
+ * column shift.  Its hits are the grid centres mh_icp_relocalise wants.  Not in the reference.
+ *
+ * The arithmetic uses no transcendental function.  It is fp64, every product and sum rounded on its own (no FMA contraction),
+ * in the written order, so a restatement in numpy (tests/place_ref.py) matches the descriptor bit for bit and the distance to
+ * rounding.  It is implemented once, in place_device.hpp, for the device and for the host.
+ *
+ * 1. The descriptor.  Input: n points (f32 xyz, `stride_floats` apart) in some frame F, and R_G_F[9], a row-major fp64 rotation
+ *    from F into a gravity-levelled frame G with the same origin (identity: the cloud is level).  Config: r_min, r_max, z_min,
+ *    z_max in metres.  For each point, widened to fp64:
+ *      p'_a = (R[3a] * x + R[3a+1] * y) + R[3a+2] * z
+ *      r2   = p'_x * p'_x + p'_y * p'_y
+ *    The point counts iff r2 >= r_min * r_min && r2 < b2[20] && p'_z > z_min && p'_z < z_max (a NaN fails), with
+ *      b2[i] = (i * w) * (i * w), w = r_max / 20, i = 0 .. 20, computed once on the host.
+ *    ring   = the number of i in 1 .. 19 with r2 >= b2[i].
+ *    sector = 15 * q + m, where the quadrant q is 0 for x' > 0, y' >= 0;  1 for x' <= 0, y' > 0;  2 for x' < 0, y' <= 0;  3
+ *      otherwise;  (u, v) = (x', y'), (y', -x'), (-x', -y'), (-y', x') for q = 0, 1, 2, 3;  and m = the number of j in 1 .. 14
+ *      with v * C[j] >= u * S[j], where C[j], S[j] = cos, sin(6 deg * j) are the 17-digit literals of place_device.hpp.  (The
+ *      axes fall into sectors 0 / 15 / 30 / 45, the point (1, 1) into sector 7.)
+ *    The value of a cell is the maximum over its points of (float)(p'_z - z_min); an empty cell is 0.0f.  A maximum does not
+ *    depend on the order of the points, so the descriptor is exact whatever the launch shape.  The descriptor is
+ *    MH_PLACE_RINGS x MH_PLACE_SECTORS floats, ring-major: desc[ring * 60 + sector].
+ *
+ * 2. The distance of a query Q to a candidate C:
+ *      n_X[j]  = sqrt(sum_i X[i][j]^2), fp64, i ascending.
+ *      Column j of Q is compared with column (j + s) % 60 of C; the pair is valid iff both norms are > 0.
+ *      c(s, j) = (sum_i Q[i][j] * C[i][(j+s)%60]) / (n_Q[j] * n_C[(j+s)%60]), i ascending.
+ *      N(s)    = the number of valid j.
+ *      d(s)    = N(s) >= min_overlap ? 1 - (sum_j c(s, j)) / N(s) : 2.0, the valid j ascending.
+ *      D       = min_s d(s);  shift = the smallest s that attains it;  no admissible shift: D = 2.0, shift = 0.
+ *    Nothing is summed across lanes, waves or workgroups, so an entry's {D, shift} has the same bits alone, at any database
+ *    size, at any position and on every repeat.
+ *    Hits are ranked by D ascending, then database index ascending.  An entry with D == 2.0 is never a hit.  All top_k hits are
+ *    written; those behind the last real one have index -1 (shift 0, dist 2.0, tag 0).
+ *    A hit with shift s means  T_W_Fq ~ T_W_Fk * (R_G_Fk^T * Rz(+s * 6 deg) * R_G_Fq, 0):  yaw_q - yaw_k = s * 6 deg.
+ *
+ * 3. The database holds, per entry, the 1 200 floats, their 60 column norms (computed on the device by the same kernel for
+ *    every way of adding) and an int64 tag of the caller's.  It holds no pose: poses stay with the caller, because a smoother
+ *    moves them.  Capacity is fixed at creation, 1 .. 65 536 entries.  A database belongs to its context and works on that
+ *    context's stream; after mh_shutdown of the context every call but mh_place_db_destroy refuses it.
+ *
+ * Refusals, each with nothing enqueued and the database unchanged: MH_ERR_INVALID_ARG for a NULL argument; config values that
+ *   are not finite; r_min <= 0, r_max <= r_min, z_min >= z_max; min_overlap outside 1 .. 60; capacity outside 1 .. 65 536;
+ *   top_k outside 1 .. MH_PLACE_MAX_HITS; n_search greater than the size; a query on an empty database; an add to a full
+ *   database; an index past the size; a stride below 3; `which` outside 0 .. 1, a scan without that stage or on another
+ *   device; a descriptor entry that is negative or not finite; an R_G_F entry that is not finite.  MH_ERR_UNSUPPORTED for more
+ *   than 2^30 - 1 points.  Zero points are no error: they give the all-zero descriptor, which matches nothing. */
+#define MH_PLACE_RINGS 20
+#define MH_PLACE_SECTORS 60
+#define MH_PLACE_MAX_HITS 16
+
+typedef struct mh_place_db mh_place_db;
+
+typedef struct mh_place_config {
+  double r_min, r_max;   /* m, horizontal range in G: 0 < r_min < r_max */
+  double z_min, z_max;   /* m, height in G: z_min < z_max */
+  int32_t min_overlap;   /* 1 .. 60: valid column pairs a shift needs to be admissible */
+  int32_t capacity;      /* 1 .. 65 536 entries */
+} mh_place_config; /* 40 bytes */
+
+typedef struct mh_place_hit {
+  int32_t index;   /* database index, -1 behind the last real hit */
+  int32_t shift;   /* 0 .. 59 */
+  double dist;     /* D */
+  int64_t tag;     /* the entry's tag */
+} mh_place_hit; /* 24 bytes */
+
+typedef struct mh_place_score {
+  double dist;     /* D of one searched entry (2.0: no admissible shift) */
+  int32_t shift;
+  int32_t reserved; /* 0 */
+} mh_place_score; /* 16 bytes */
+
+int mh_place_db_create(mh_ctx * ctx, const mh_place_config * cfg, mh_place_db ** out);
+void mh_place_db_destroy(mh_place_db * db);
+/* entries in the database; 0 for NULL or a database whose context was shut down */
+size_t mh_place_db_size(const mh_place_db * db);
+
+/* The descriptor of n host points under the database's config: desc[1200].  Synchronous; the database is not changed. */
+int mh_place_describe(mh_place_db * db, const float * xyz, size_t n, size_t stride_floats, const double R_G_F[9], float * desc);
+/* The same for points that are already on the database's device (d_points: device pointer). */
+int mh_place_describe_device(mh_place_db * db, const void * d_points, size_t n, size_t stride_floats, const double R_G_F[9], float * desc);
+/* The same straight from a device-resident scan; `which` as in mh_map_carve_from_scan (0: points_full_, 1: Be_cloud_). */
+int mh_place_describe_from_scan(mh_place_db * db, const mh_scan * scan, int which, const double R_G_F[9], float * desc);
+
+/* Append a host descriptor (one saved in an earlier session, say) under `tag`; *index (may be NULL) receives its index. */
+int mh_place_db_add(mh_place_db * db, const float * desc, int64_t tag, int32_t * index);
+/* Describe a device-resident scan and append the result, on the device: no host round trip. */
+int mh_place_db_add_from_scan(mh_place_db * db, const mh_scan * scan, int which, const double R_G_F[9], int64_t tag, int32_t * index);
+/* Read entry `index` back: desc[1200] and *tag (either may be NULL). */
+int mh_place_db_get(mh_place_db * db, int32_t index, float * desc, int64_t * tag);
+
+/* Search entries 0 .. n_search - 1 (n_search == 0: all of them; a loop-closure caller leaves out the newest keyframes) for the
+ * top_k nearest to `desc`: hits[top_k] in rank order; all (may be NULL) receives {D, shift} of every searched entry.  One chain
+ * of launches on the context's stream — norms of the query, distances, selection — and one wait. */
+int mh_place_db_query(mh_place_db * db, const float * desc, size_t n_search, int32_t top_k, mh_place_hit * hits, mh_place_score * all);
+/* The same with the query described from a device-resident scan within the chain. */
+int mh_place_db_query_from_scan(mh_place_db * db, const mh_scan * scan, int which, const double R_G_F[9], size_t n_search, int32_t top_k,
+                                mh_place_hit * hits, mh_place_score * all);
+
 /* ---- fixed-lag window: the smoother's Gauss-Newton loop on the device ---------------------------
  * W unary factors, one pose each, tied by between factors and a prior on the oldest pose: what a caller otherwise writes
  * around mh_icp_linearize_batch — one blocking batch call, a 6W x 6W system assembled and solved on the host, W retractions,

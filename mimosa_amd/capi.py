@@ -27,6 +27,8 @@ EXPORTS = [
     "mh_icp_align", "mh_icp_align_async",
     "mh_icp_align_batch", "mh_icp_align_batch_async", "mh_icp_align_batch_wait",
     "mh_icp_score_poses", "mh_icp_score_poses_async", "mh_icp_relocalise", "mh_icp_relocalise_batch",
+    "mh_place_db_create", "mh_place_db_destroy", "mh_place_db_size", "mh_place_describe", "mh_place_describe_device", "mh_place_describe_from_scan",
+    "mh_place_db_add", "mh_place_db_add_from_scan", "mh_place_db_get", "mh_place_db_query", "mh_place_db_query_from_scan",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
     "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
     "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
@@ -740,6 +742,19 @@ def load(build_if_missing: bool = True):
     L.mh_icp_align_batch_async.argtypes = L.mh_icp_align_batch.argtypes
     L.mh_icp_align_batch_wait.argtypes = [vp]
     L.mh_icp_relocalise_batch.argtypes = [vp, vp, sz, vp, vp, sz, vp, C.POINTER(RelocConfig), C.POINTER(RelocResult)]
+    L.mh_place_db_create.argtypes = [vp, C.POINTER(PlaceConfig), pvp]
+    L.mh_place_db_destroy.argtypes = [vp]
+    L.mh_place_db_destroy.restype = None
+    L.mh_place_db_size.argtypes = [vp]
+    L.mh_place_db_size.restype = sz
+    L.mh_place_describe.argtypes = [vp, vp, sz, sz, vp, vp]
+    L.mh_place_describe_device.argtypes = [vp, vp, sz, sz, vp, vp]
+    L.mh_place_describe_from_scan.argtypes = [vp, vp, i32, vp, vp]
+    L.mh_place_db_add.argtypes = [vp, vp, C.c_int64, vp]
+    L.mh_place_db_add_from_scan.argtypes = [vp, vp, i32, vp, C.c_int64, vp]
+    L.mh_place_db_get.argtypes = [vp, C.c_int32, vp, vp]
+    L.mh_place_db_query.argtypes = [vp, vp, sz, C.c_int32, vp, vp]
+    L.mh_place_db_query_from_scan.argtypes = [vp, vp, i32, vp, sz, C.c_int32, vp, vp]
     L.mh_icp_window_optimise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_optimise_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_wait.argtypes = [vp]
@@ -2042,3 +2057,181 @@ def photo_linearize_batch(factors, R_bs, t_bs, R_as=None, t_as=None) -> list:
 def photo_linearize_batch_async(factors, R_bs, t_bs, R_as=None, t_as=None) -> None:
     """The same enqueued without waiting: each PhotoFactor.wait() then returns its result, in any order."""
     _photo_batch_call("mh_photo_factor_linearize_batch_async", factors, R_bs, t_bs, R_as, t_as)
+
+
+# ---- place recognition (mh_place_*) -------------------------------------------------------------------------------------------
+MH_PLACE_RINGS, MH_PLACE_SECTORS, MH_PLACE_MAX_HITS = 20, 60, 16
+PLACE_CELLS = MH_PLACE_RINGS * MH_PLACE_SECTORS
+
+
+class PlaceConfig(C.Structure):
+    """mh_place_config (40 bytes)."""
+    _fields_ = [("r_min", C.c_double), ("r_max", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double), ("min_overlap", C.c_int32),
+                ("capacity", C.c_int32)]
+
+
+class PlaceHit(C.Structure):
+    """mh_place_hit (24 bytes)."""
+    _fields_ = [("index", C.c_int32), ("shift", C.c_int32), ("dist", C.c_double), ("tag", C.c_int64)]
+
+
+class PlaceScore(C.Structure):
+    """mh_place_score (16 bytes)."""
+    _fields_ = [("dist", C.c_double), ("shift", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the same records as numpy dtypes: what PlaceDatabase.query returns
+PLACE_HIT_DTYPE = np.dtype([("index", np.int32), ("shift", np.int32), ("dist", np.float64), ("tag", np.int64)])
+PLACE_SCORE_DTYPE = np.dtype([("dist", np.float64), ("shift", np.int32), ("reserved", np.int32)])
+
+
+def make_place_config(r_min=0.5, r_max=40.0, z_min=-2.0, z_max=30.0, min_overlap=30, capacity=1024) -> PlaceConfig:
+    return PlaceConfig(r_min, r_max, z_min, z_max, min_overlap, capacity)
+
+
+class PlaceDatabase:
+    """A keyframe database of ring x sector scan descriptors, searched on the device (mh_place_db_*).  It stores a tag per
+    entry and no pose: poses stay with the caller."""
+
+    def __init__(self, ctx: Context, cfg=None, **kw):
+        self.ctx, self.L = ctx, ctx.L
+        self.cfg = cfg if isinstance(cfg, PlaceConfig) else make_place_config(**(cfg or kw))
+        h = C.c_void_p()
+        ctx.check(self.L.mh_place_db_create(ctx.h, C.byref(self.cfg), C.byref(h)))
+        self.h = h
+        ctx._children += 1
+
+    @staticmethod
+    def _R(R_G_F):
+        return _f64(np.eye(3) if R_G_F is None else R_G_F).reshape(9)
+
+    def size(self) -> int:
+        return int(self.L.mh_place_db_size(self.h))
+
+    def describe(self, xyz, R_G_F=None):
+        """mh_place_describe: the descriptor (1 200 floats, ring-major) of host points in a frame F, R_G_F levelling it."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        R, desc = self._R(R_G_F), np.empty(PLACE_CELLS, np.float32)
+        self.ctx.check(self.L.mh_place_describe(self.h, _p(xyz) if len(xyz) else None, xyz.shape[0], 3, _p(R), _p(desc)))
+        return desc
+
+    def describe_device(self, d_points, n, stride_floats, R_G_F=None):
+        """mh_place_describe_device: the same for n points at a device address."""
+        R, desc = self._R(R_G_F), np.empty(PLACE_CELLS, np.float32)
+        self.ctx.check(self.L.mh_place_describe_device(self.h, d_points, n, stride_floats, _p(R), _p(desc)))
+        return desc
+
+    def describe_from_scan(self, scan, which, R_G_F=None):
+        """mh_place_describe_from_scan: the same from a device-resident scan; which = Scan.FULL or Scan.BODY."""
+        R, desc = self._R(R_G_F), np.empty(PLACE_CELLS, np.float32)
+        self.ctx.check(self.L.mh_place_describe_from_scan(self.h, scan.h, int(which), _p(R), _p(desc)))
+        return desc
+
+    def add(self, desc, tag=0) -> int:
+        """mh_place_db_add: append a host descriptor; returns its index."""
+        desc = np.ascontiguousarray(desc, dtype=np.float32).reshape(PLACE_CELLS)
+        idx = C.c_int32(-1)
+        self.ctx.check(self.L.mh_place_db_add(self.h, _p(desc), int(tag), C.byref(idx)))
+        return int(idx.value)
+
+    def add_from_scan(self, scan, which, R_G_F=None, tag=0) -> int:
+        """mh_place_db_add_from_scan: describe and append on the device; returns the index."""
+        R, idx = self._R(R_G_F), C.c_int32(-1)
+        self.ctx.check(self.L.mh_place_db_add_from_scan(self.h, scan.h, int(which), _p(R), int(tag), C.byref(idx)))
+        return int(idx.value)
+
+    def get(self, index):
+        """mh_place_db_get: (descriptor, tag) of an entry."""
+        desc, tag = np.empty(PLACE_CELLS, np.float32), C.c_int64(0)
+        self.ctx.check(self.L.mh_place_db_get(self.h, int(index), _p(desc), C.byref(tag)))
+        return desc, int(tag.value)
+
+    def _query_out(self, n_search, top_k, want_all):
+        hits = np.zeros(max(int(top_k), 0), PLACE_HIT_DTYPE)
+        m = int(n_search) if n_search else self.size()
+        return hits, (np.zeros(m, PLACE_SCORE_DTYPE) if want_all else None)
+
+    def query(self, desc, top_k=4, n_search=0, want_all=False):
+        """mh_place_db_query: (hits, all) — hits a PLACE_HIT_DTYPE array in rank order (index -1 behind the last real hit), all a
+        PLACE_SCORE_DTYPE array over the searched entries (None unless asked for).  n_search = 0 searches every entry."""
+        desc = np.ascontiguousarray(desc, dtype=np.float32).reshape(PLACE_CELLS)
+        hits, all_ = self._query_out(n_search, top_k, want_all)
+        self.ctx.check(self.L.mh_place_db_query(self.h, _p(desc), int(n_search), int(top_k), _p(hits), _p(all_)))
+        return hits, all_
+
+    def query_from_scan(self, scan, which, R_G_F=None, top_k=4, n_search=0, want_all=False):
+        """mh_place_db_query_from_scan: the same with the query described from a device-resident scan."""
+        R = self._R(R_G_F)
+        hits, all_ = self._query_out(n_search, top_k, want_all)
+        self.ctx.check(self.L.mh_place_db_query_from_scan(self.h, scan.h, int(which), _p(R), int(n_search), int(top_k), _p(hits), _p(all_)))
+        return hits, all_
+
+    def destroy(self):
+        if getattr(self, "h", None):
+            self.L.mh_place_db_destroy(self.h)
+            self.h = None
+            self.ctx._child_released()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def level_rotation(g_unit_F):
+    """R_G_F for a gravity direction measured in F: the smallest rotation that takes -g to +z (the antipodal case: a turn by pi
+    about x)."""
+    g = np.asarray(g_unit_F, np.float64).reshape(3)
+    a = -g / np.linalg.norm(g)
+    c = a[2]
+    if c <= -1.0 + 1e-12:
+        return np.diag([1.0, -1.0, -1.0])
+    v = np.array([a[1], -a[0], 0.0])                     # a x z
+    K = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return np.eye(3) + K + (K @ K) / (1.0 + c)
+
+
+def place_candidate_pose(T_k, R_G_Fk, R_G_Fq, shift):
+    """The pose a hit proposes for the query's frame: T_W_Fq = T_W_Fk * (R_G_Fk^T Rz(+shift * 6 deg) R_G_Fq, 0).  T_k = (R 3x3, t 3).
+    Returns (R, t)."""
+    R_k, t_k = np.asarray(T_k[0], np.float64).reshape(3, 3), np.asarray(T_k[1], np.float64).reshape(3)
+    a = np.deg2rad(360.0 / MH_PLACE_SECTORS) * int(shift)
+    c, s = np.cos(a), np.sin(a)
+    Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    Rk = np.eye(3) if R_G_Fk is None else np.asarray(R_G_Fk, np.float64).reshape(3, 3)
+    Rq = np.eye(3) if R_G_Fq is None else np.asarray(R_G_Fq, np.float64).reshape(3, 3)
+    return R_k @ (Rk.T @ Rz @ Rq), t_k.copy()
+
+
+def place_relocalise(factor, hits, keyframe_poses, cfg: RelocConfig = None, R_G_Fk=None, R_G_Fq=None, g_unit=(0.0, 0.0, -1.0), half_xy=1.5, step_xy=0.5,
+                     half_yaw=np.deg2rad(6.0), step_yaw=np.deg2rad(3.0)):
+    """From place-recognition hits to a pose: for each real hit in rank order a pose_grid round its candidate pose (+-1.5 m in
+    0.5 m steps, +-6 deg in 3 deg steps by default) and ONE factor.relocalise call on that grid; the winner is the call whose best
+    candidate's `fine` score ranks first under the relocalisation ranking (ties: the earlier hit).
+    keyframe_poses: indexable by a hit's database index (or a dict by it), each (R 3x3, t 3) of the keyframe's frame in the map.
+    R_G_Fk: None, one rotation for every keyframe, or indexable like keyframe_poses.
+    Returns None without a real hit, else {"hit": rank of the winning hit, "index": its database index, "R", "t": the pose,
+    "fine": its score, "results": every call's result}."""
+    cfg = cfg if cfg is not None else make_reloc_config()
+    best, results = None, []
+    for rank, h in enumerate(hits):
+        k = int(h["index"])
+        if k < 0:
+            break
+        Rk = R_G_Fk
+        if Rk is not None and np.ndim(Rk) != 2:
+            Rk = Rk[k]
+        R0, t0 = place_candidate_pose(keyframe_poses[k], Rk, R_G_Fq, int(h["shift"]))
+        Rg, tg = pose_grid(R0, t0, half_xy, step_xy, half_yaw, step_yaw)
+        res = factor.relocalise(Rg, tg, cfg, g_unit=g_unit)
+        results.append(res)
+        if res["best"] < 0:
+            continue
+        fine = res["cand"][res["best"]]["fine"]
+        key = (-fine["n_inliers"], fine["sum_sq"], rank)
+        if best is None or key < best[0]:
+            best = (key, dict(hit=rank, index=k, R=res["R"], t=res["t"], fine=fine))
+    if best is None:
+        return None
+    return dict(best[1], results=results)

@@ -114,6 +114,8 @@ struct mh_ctx
   // the communicators whose rounds run on it
   std::vector<mh_shard_icp *> shard_factors;
   std::vector<mh_shard_comm *> shard_comms;
+  // ... and from the place-recognition databases created on it (place_api.hip)
+  std::vector<mh_place_db *> place_dbs;
 };
 
 // The stream of the context the calling thread is working for (set by mh_enter at every entry point): what the allocation
@@ -805,6 +807,9 @@ int prepare(mh_icp * icp, const double R_src[9], const double t_src[3], const do
             mh_icp_result * out, mh::IcpArgs & a, mh::LocArgs & l);
 // shard_api.hip: called by mh_shutdown(ctx) so that the sharded handles listed on ctx let go of it
 void shard_ctx_gone(mh_ctx * ctx);
+// place_api.hip: likewise for the place-recognition databases listed on ctx — they give their memory back while the context is
+// alive and are left with ctx == nullptr: every entry point refuses them, mh_place_db_destroy just deletes them
+void place_ctx_gone(mh_ctx * ctx);
 // a call's DeviceResult from its flagged words in pending slot `slot` (spin_ns > 0: wait up to that long for words that have
 // not arrived); false = something is still missing
 bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, long spin_ns, mh::DeviceResult & d);

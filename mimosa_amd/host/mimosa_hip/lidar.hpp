@@ -501,6 +501,126 @@ private:
   double corrected_ts_ = 0;
 };
 
+// ---------------------------------------------------------------------------------------------
+// Place recognition (mh_place_*; not in the reference): a keyframe database of ring x sector scan descriptors, searched on the
+// device.  It stores a tag per entry and no pose: poses stay with the caller, because a smoother moves them.
+using PlaceDescriptor = std::vector<float>;  // MH_PLACE_RINGS * MH_PLACE_SECTORS floats, ring-major
+
+namespace detail
+{
+inline A9 mul33(const A9 & a, const A9 & b)
+{
+  A9 c{};
+  for (int r = 0; r < 3; ++r)
+    for (int k = 0; k < 3; ++k)
+      for (int j = 0; j < 3; ++j) c[3 * r + j] += a[3 * r + k] * b[3 * k + j];
+  return c;
+}
+inline A9 transposed33(const A9 & a) { return A9{a[0], a[3], a[6], a[1], a[4], a[7], a[2], a[5], a[8]}; }
+inline A9 identity33() { return A9{1, 0, 0, 0, 1, 0, 0, 0, 1}; }
+}  // namespace detail
+
+// R_G_F for a gravity direction measured in F: the smallest rotation that takes -g to +z (row-major).  The antipodal case is a
+// turn by pi about x.
+inline A9 levelRotation(const A3 & g_unit_F)
+{
+  const double n = std::sqrt(g_unit_F[0] * g_unit_F[0] + g_unit_F[1] * g_unit_F[1] + g_unit_F[2] * g_unit_F[2]);
+  const double a0 = -g_unit_F[0] / n, a1 = -g_unit_F[1] / n, c = -g_unit_F[2] / n;
+  if (c <= -1.0 + 1e-12) return A9{1, 0, 0, 0, -1, 0, 0, 0, -1};
+  const double v0 = a1, v1 = -a0;  // a x z = (v0, v1, 0)
+  const A9 K{0, 0, v1, 0, 0, -v0, -v1, v0, 0};
+  const A9 KK = detail::mul33(K, K);
+  A9 R = detail::identity33();
+  for (int i = 0; i < 9; ++i) R[i] += K[i] + KK[i] / (1.0 + c);
+  return R;
+}
+
+// The pose a hit proposes for the query's frame: T_W_Fq = T_W_Fk * (R_G_Fk^T Rz(+shift * 6 deg) R_G_Fq, 0)
+inline Pose3 placeCandidatePose(const Pose3 & T_W_Fk, const A9 & R_G_Fk, const A9 & R_G_Fq, int shift)
+{
+  const double a = static_cast<double>(shift) * (2.0 * 3.14159265358979323846 / MH_PLACE_SECTORS);
+  const A9 Rz{std::cos(a), -std::sin(a), 0, std::sin(a), std::cos(a), 0, 0, 0, 1};
+  const PoseRM k = rowMajor(T_W_Fk);
+  const A9 R = detail::mul33(k.R, detail::mul33(detail::transposed33(R_G_Fk), detail::mul33(Rz, R_G_Fq)));
+  return pose3(R.data(), k.t.data());
+}
+
+class PlaceDatabase
+{
+public:
+  PlaceDatabase(const std::shared_ptr<Context> & ctx, const mh_place_config & cfg) : ctx_(ctx), cfg_(cfg)
+  {
+    ctx_->check(mh_place_db_create(ctx_->get(), &cfg_, &db_), "mh_place_db_create");
+  }
+  ~PlaceDatabase() { mh_place_db_destroy(db_); }
+  PlaceDatabase(const PlaceDatabase &) = delete;
+  PlaceDatabase & operator=(const PlaceDatabase &) = delete;
+
+  size_t size() const { return mh_place_db_size(db_); }
+  const mh_place_config & config() const { return cfg_; }
+
+  // the descriptor of a cloud in a frame F that R_G_F levels
+  PlaceDescriptor describe(const PointCloud & cloud_F, const A9 & R_G_F = detail::identity33())
+  {
+    PlaceDescriptor d(kCells);
+    ctx_->check(mh_place_describe(db_, cloud_F.empty() ? nullptr : &cloud_F[0].x, cloud_F.size(), sizeof(Point) / sizeof(float), R_G_F.data(), d.data()),
+                "mh_place_describe");
+    return d;
+  }
+  // which: 0 points_full_, 1 Be_cloud_
+  PlaceDescriptor describeFromScan(mh_scan * scan, int which, const A9 & R_G_F = detail::identity33())
+  {
+    PlaceDescriptor d(kCells);
+    ctx_->check(mh_place_describe_from_scan(db_, scan, which, R_G_F.data(), d.data()), "mh_place_describe_from_scan");
+    return d;
+  }
+  int32_t add(const PlaceDescriptor & desc, int64_t tag)
+  {
+    if (desc.size() != kCells) throw std::runtime_error("PlaceDatabase::add: a descriptor has 1200 floats");
+    int32_t index = -1;
+    ctx_->check(mh_place_db_add(db_, desc.data(), tag, &index), "mh_place_db_add");
+    return index;
+  }
+  int32_t addFromScan(mh_scan * scan, int which, int64_t tag, const A9 & R_G_F = detail::identity33())
+  {
+    int32_t index = -1;
+    ctx_->check(mh_place_db_add_from_scan(db_, scan, which, R_G_F.data(), tag, &index), "mh_place_db_add_from_scan");
+    return index;
+  }
+  PlaceDescriptor get(int32_t index, int64_t * tag = nullptr)
+  {
+    PlaceDescriptor d(kCells);
+    ctx_->check(mh_place_db_get(db_, index, d.data(), tag), "mh_place_db_get");
+    return d;
+  }
+  // the top_k hits in rank order (index -1 behind the last real one); n_search = 0 searches every entry; all (optional) receives
+  // {D, shift} of every searched entry
+  std::vector<mh_place_hit> query(const PlaceDescriptor & desc, int32_t top_k, size_t n_search = 0, std::vector<mh_place_score> * all = nullptr)
+  {
+    if (desc.size() != kCells) throw std::runtime_error("PlaceDatabase::query: a descriptor has 1200 floats");
+    std::vector<mh_place_hit> hits(top_k > 0 ? static_cast<size_t>(top_k) : 0);
+    if (all) all->resize(n_search ? n_search : size());
+    ctx_->check(mh_place_db_query(db_, desc.data(), n_search, top_k, hits.data(), all ? all->data() : nullptr), "mh_place_db_query");
+    return hits;
+  }
+  std::vector<mh_place_hit> queryFromScan(mh_scan * scan, int which, int32_t top_k, const A9 & R_G_F = detail::identity33(), size_t n_search = 0,
+                                          std::vector<mh_place_score> * all = nullptr)
+  {
+    std::vector<mh_place_hit> hits(top_k > 0 ? static_cast<size_t>(top_k) : 0);
+    if (all) all->resize(n_search ? n_search : size());
+    ctx_->check(mh_place_db_query_from_scan(db_, scan, which, R_G_F.data(), n_search, top_k, hits.data(), all ? all->data() : nullptr),
+                "mh_place_db_query_from_scan");
+    return hits;
+  }
+  mh_place_db * underlying() { return db_; }
+
+private:
+  static constexpr size_t kCells = static_cast<size_t>(MH_PLACE_RINGS) * MH_PLACE_SECTORS;
+  std::shared_ptr<Context> ctx_;  // (declared first: the database goes before its context)
+  mh_place_config cfg_;
+  mh_place_db * db_ = nullptr;
+};
+
 // The GaussianFactor ICPFactor::linearize returns: gtsam::HessianFactor(keys()[0], H, -b, f) (geometric_factor.hpp:559-560),
 // binary HessianFactor(k0, k1, H_ss, H_st, -b_s, H_tt, -b_t, f) (:459-462), from the C ABI's row-major result.
 inline std::shared_ptr<HessianFactor> hessianFrom(const KeyVector & keys, bool binary, const mh_icp_result & r)
