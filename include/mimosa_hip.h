@@ -927,6 +927,87 @@ int mh_icp_window_marginalise_joint_async(mh_icp * const * icps, size_t W, const
                                           const mh_window_edge * edges, size_t n_edges, const mh_window_joint_factor * joint,
                                           mh_window_joint_marginal * out);
 
+/* ---- pose graph over all keyframes: close loops on the device -----------------------------------
+ * The fixed-lag window takes at most MH_WINDOW_MAX poses; a loop closure ties a keyframe to one hundreds of keyframes back.
+ * A pose graph holds n poses (world from keyframe: R row-major, t), relative-pose edges in the shape the window takes them
+ * (mh_window_edge, unchanged: one loop measurement serves both) and a fixed flag per pose, and runs Gauss-Newton over all
+ * of them as ONE chain of launches on the context's stream and one wait.  The rule:
+ *
+ * 1. Edge e of the poses a < b at the current poses, exactly as mh_icp_window_optimise_edges evaluates it: with
+ *    T_ab = T_a^-1 T_b the residual r = [Log(Z.R^T R_ab), Z.R^T (t_ab - Z.t)], J_a = -Ad(T_ab^-1), J_b = I; with Om = info (all 36
+ *    entries read as given) it adds J_a^T Om J_a to the diagonal block of a, Om J_a to the block in block row b, block column
+ *    a (its transpose above the diagonal), Om to the diagonal block of b, J_a^T Om r and Om r to the gradients, r^T Om r to f.
+ * 2. A fixed pose takes no step: its block row and column are the identity, its right-hand side is zero, its edges act only
+ *    on their other end.  `damping` is added to every diagonal entry of the free poses.  The system is A xi = -g.
+ * 3. Every sum of a pose's block row is taken over the pose's edges in edge-list order; nothing is added by atomics.
+ *    f = sum_{l < 256} (sum_k c[l + 256 k]), c[e] = r^T Om r of edge e, k and l ascending: the same bits whatever the launch.
+ * 4. The edges are split into near ones (pose_b - pose_a == 1) and far ones (>= 2; at most MH_PGO_FAR_MAX of them, else
+ *    MH_ERR_UNSUPPORTED).  A = T + sum_f W_f^T Om_f W_f: T block-tridiagonal (near edges, damping, the identity rows), W_f the
+ *    6 x 6n matrix with J_a in block column a and I in block column b of far edge f (the block column of a fixed pose
+ *    zeroed).  With Y = T^-1 [W^T | -g] and C = blockdiag(Om_f^-1) + W Y (6F x 6F) the step is xi = y - Y C^-1 W y, followed by
+ *    two refinement steps whose residual is taken against A itself in twice the working precision.  T is factorised by the
+ *    window chains' block L D L^T, every Om_f and C by L D L^T; nothing pivots.
+ * 5. Retraction R <- R Exp(xi_r), t <- t + R xi_t.  The call stops behind a step whose largest |xi_r| over the poses is below
+ *    eps_rot and whose largest |xi_t| is below eps_trans (0: never), or behind `iters` iterations.
+ * 6. A pivot of T, of an Om_f or of C that is not positive: no step, the poses unchanged, trace[].flags = 4, the call ends with
+ *    MH_OK and converged = 0 — the window chains' rule.  LIMIT: T must be positive definite by itself, so every run of poses
+ *    joined by near edges needs a fixed pose or damping; a gap in the chain bridged only by a far edge makes A regular but T
+ *    singular and ends in flag 4, as does a far edge whose info is only positive semi-definite.
+ *
+ * mh_pose_graph_set_poses copies n poses (1 .. max_poses); with an n other than the last one it also drops the edges and the
+ * fixed flags.  mh_pose_graph_set_fixed: n flags (NULL: none fixed).  mh_pose_graph_set_edges replaces the edge list (n_edges
+ * 0 .. max_edges; copied before the call returns).  mh_pose_graph_get_poses: the poses as the last call left them; capacity in
+ * poses, *n_out (may be NULL) the count; R and t may each be NULL.  mh_pose_graph_residuals evaluates every edge at the stored
+ * poses and moves nothing: r[6 E] the residuals, chi2[E] = r^T Om r per edge — what a caller needs to reject a false loop
+ * before accepting it — and *f their sum in the order of 3.; each may be NULL.  mh_pose_graph_optimise: cfg->iters iterations
+ * are queued, or check_every at a time with a look at the chain's stop word in between (the result does not depend on it);
+ * launches behind a stopped iteration return at once.  trace_poses: NULL, or iters x n x 12 doubles the caller owns — the
+ * poses (R, then t) behind every executed step; rows of iterations that were not executed are left untouched.
+ *
+ * Refusals, each with nothing enqueued and the graph unchanged — MH_ERR_INVALID_ARG: a NULL argument; max_poses outside
+ * 1 .. MH_PGO_MAX_POSES, max_edges above MH_PGO_MAX_EDGES; n outside 1 .. max_poses; a pose entry that is not finite; a call
+ * that needs poses before any were set; n_edges above max_edges; pose_a < 0, pose_a >= pose_b, pose_b >= n; an entry of Z_R,
+ * Z_t or info that is not finite; info[6 r + c] != info[6 c + r]; capacity below n; iters outside 1 .. 64; a negative or
+ * non-finite damping, eps or check_every.  MH_ERR_UNSUPPORTED: more than MH_PGO_FAR_MAX far edges.  A graph belongs to its
+ * context; after mh_shutdown of the context every call but mh_pose_graph_destroy refuses it.
+ * Not here: unary priors on a pose, robust kernels on edges, an asynchronous form, the sharded path. */
+#define MH_PGO_MAX_POSES 4096
+#define MH_PGO_MAX_EDGES 32768
+#define MH_PGO_FAR_MAX 32 /* edges with pose_b - pose_a >= 2 */
+
+typedef struct mh_pose_graph mh_pose_graph;
+
+typedef struct mh_pose_graph_config {
+  int32_t iters;             /* 1 .. 64 iterations queued */
+  int32_t check_every;       /* iterations queued per host look at the stop word; 0 = all at once */
+  double damping;            /* >= 0, added to every diagonal entry of the free poses */
+  double eps_rot, eps_trans; /* rad, m: stop when the largest step norms fall below (0 = never) */
+} mh_pose_graph_config; /* 32 bytes */
+
+typedef struct mh_pose_graph_trace {
+  double f;                    /* sum of r^T Om r at the poses the iteration evaluated */
+  double step_rot, step_trans; /* max over the poses of |xi_r|, |xi_t| */
+  int32_t flags;               /* 4: a pivot was not positive (no step; the call ends here) */
+  int32_t reserved;            /* 0 */
+} mh_pose_graph_trace; /* 32 bytes */
+
+typedef struct mh_pose_graph_result {
+  int32_t iters, converged;
+  int32_t n_poses, n_far;
+  double f_first, f_last;          /* trace[0].f, trace[iters - 1].f */
+  mh_pose_graph_trace trace[64];   /* one row per executed iteration */
+} mh_pose_graph_result;
+
+int mh_pose_graph_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_pose_graph ** out);
+void mh_pose_graph_destroy(mh_pose_graph * pg);
+int mh_pose_graph_set_poses(mh_pose_graph * pg, const double * R /* 9 n */, const double * t /* 3 n */, size_t n);
+int mh_pose_graph_set_fixed(mh_pose_graph * pg, const uint8_t * fixed /* n, NULL = none */);
+int mh_pose_graph_set_edges(mh_pose_graph * pg, const mh_window_edge * edges, size_t n_edges);
+int mh_pose_graph_get_poses(mh_pose_graph * pg, double * R, double * t, size_t capacity, size_t * n_out);
+int mh_pose_graph_residuals(mh_pose_graph * pg, double * r /* 6 E or NULL */, double * chi2 /* E or NULL */, double * f);
+int mh_pose_graph_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_graph_result * out,
+                           double * trace_poses /* NULL or iters x n x 12 */);
+
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals
  * unique_ns[g] gets p <- R_g p + t_g in float (no FMA, Eigen's evaluation order).  Rt12 = n_groups x

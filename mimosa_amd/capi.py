@@ -29,6 +29,8 @@ EXPORTS = [
     "mh_icp_score_poses", "mh_icp_score_poses_async", "mh_icp_relocalise", "mh_icp_relocalise_batch",
     "mh_place_db_create", "mh_place_db_destroy", "mh_place_db_size", "mh_place_describe", "mh_place_describe_device", "mh_place_describe_from_scan",
     "mh_place_db_add", "mh_place_db_add_from_scan", "mh_place_db_get", "mh_place_db_query", "mh_place_db_query_from_scan",
+    "mh_pose_graph_create", "mh_pose_graph_destroy", "mh_pose_graph_set_poses", "mh_pose_graph_set_fixed", "mh_pose_graph_set_edges",
+    "mh_pose_graph_get_poses", "mh_pose_graph_residuals", "mh_pose_graph_optimise",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
     "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
     "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
@@ -755,6 +757,15 @@ def load(build_if_missing: bool = True):
     L.mh_place_db_get.argtypes = [vp, C.c_int32, vp, vp]
     L.mh_place_db_query.argtypes = [vp, vp, sz, C.c_int32, vp, vp]
     L.mh_place_db_query_from_scan.argtypes = [vp, vp, i32, vp, sz, C.c_int32, vp, vp]
+    L.mh_pose_graph_create.argtypes = [vp, sz, sz, pvp]
+    L.mh_pose_graph_destroy.argtypes = [vp]
+    L.mh_pose_graph_destroy.restype = None
+    L.mh_pose_graph_set_poses.argtypes = [vp, vp, vp, sz]
+    L.mh_pose_graph_set_fixed.argtypes = [vp, vp]
+    L.mh_pose_graph_set_edges.argtypes = [vp, C.POINTER(WindowEdge), sz]
+    L.mh_pose_graph_get_poses.argtypes = [vp, vp, vp, sz, C.POINTER(sz)]
+    L.mh_pose_graph_residuals.argtypes = [vp, vp, vp, vp]
+    L.mh_pose_graph_optimise.argtypes = [vp, C.POINTER(PoseGraphConfig), C.POINTER(PoseGraphResult), vp]
     L.mh_icp_window_optimise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_optimise_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_wait.argtypes = [vp]
@@ -2235,3 +2246,99 @@ def place_relocalise(factor, hits, keyframe_poses, cfg: RelocConfig = None, R_G_
     if best is None:
         return None
     return dict(best[1], results=results)
+
+
+# ---- pose graph over all keyframes (mh_pose_graph_*) ----------------------------------------------------------------------------
+MH_PGO_MAX_POSES, MH_PGO_MAX_EDGES, MH_PGO_FAR_MAX = 4096, 32768, 32
+
+
+class PoseGraphConfig(C.Structure):
+    """mh_pose_graph_config (32 bytes)."""
+    _fields_ = [("iters", C.c_int32), ("check_every", C.c_int32), ("damping", C.c_double), ("eps_rot", C.c_double), ("eps_trans", C.c_double)]
+
+
+class PoseGraphTrace(C.Structure):
+    """mh_pose_graph_trace (32 bytes)."""
+    _fields_ = [("f", C.c_double), ("step_rot", C.c_double), ("step_trans", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PoseGraphResult(C.Structure):
+    """mh_pose_graph_result"""
+    _fields_ = [("iters", C.c_int32), ("converged", C.c_int32), ("n_poses", C.c_int32), ("n_far", C.c_int32), ("f_first", C.c_double), ("f_last", C.c_double),
+                ("trace", PoseGraphTrace * 64)]
+
+
+def make_pose_graph_config(iters=16, check_every=0, damping=0.0, eps_rot=1e-9, eps_trans=1e-9) -> PoseGraphConfig:
+    return PoseGraphConfig(int(iters), int(check_every), float(damping), float(eps_rot), float(eps_trans))
+
+
+class PoseGraph:
+    """A pose graph over all keyframes, optimised on the device (mh_pose_graph_*): poses (world from keyframe), relative-pose
+    edges in the shape the window chains take them, a fixed flag per pose."""
+
+    def __init__(self, ctx: Context, max_poses, max_edges):
+        self.ctx, self.L = ctx, ctx.L
+        h = C.c_void_p()
+        ctx.check(self.L.mh_pose_graph_create(ctx.h, int(max_poses), int(max_edges), C.byref(h)))
+        self.h = h
+        self.n = self.n_edges = 0
+        ctx._children += 1
+
+    def set_poses(self, R, t):
+        """mh_pose_graph_set_poses: R n x 3 x 3, t n x 3.  Another n than before drops the edges and the fixed flags."""
+        R, t = _f64(R).reshape(-1, 9), _f64(t).reshape(-1, 3)
+        self.ctx.check(self.L.mh_pose_graph_set_poses(self.h, _p(R), _p(t), R.shape[0]))
+        if R.shape[0] != self.n:
+            self.n, self.n_edges = R.shape[0], 0
+
+    def set_fixed(self, fixed=None):
+        """mh_pose_graph_set_fixed: n flags, or None for no fixed pose."""
+        f = None if fixed is None else np.ascontiguousarray(np.asarray(fixed) != 0, dtype=np.uint8).reshape(self.n)
+        self.ctx.check(self.L.mh_pose_graph_set_fixed(self.h, _p(f)))
+
+    def set_edges(self, edges):
+        """mh_pose_graph_set_edges: dicts as make_window_edge takes them, or an array it made."""
+        n = len(edges)
+        arr = edges if isinstance(edges, C.Array) else make_window_edge(edges)
+        self.ctx.check(self.L.mh_pose_graph_set_edges(self.h, arr, n))
+        self.n_edges = n
+
+    def poses(self):
+        """mh_pose_graph_get_poses: (R n x 3 x 3, t n x 3) as the last call left them."""
+        R, t, n = np.empty((self.n, 3, 3)), np.empty((self.n, 3)), C.c_size_t(0)
+        self.ctx.check(self.L.mh_pose_graph_get_poses(self.h, _p(R), _p(t), self.n, C.byref(n)))
+        assert n.value == self.n
+        return R, t
+
+    def residuals(self):
+        """mh_pose_graph_residuals: (r E x 6, chi2 E, f) at the stored poses; nothing moves."""
+        r, chi2, f = np.empty((self.n_edges, 6)), np.empty(self.n_edges), C.c_double(0.0)
+        self.ctx.check(self.L.mh_pose_graph_residuals(self.h, _p(r) if self.n_edges else None, _p(chi2) if self.n_edges else None, C.byref(f)))
+        return r, chi2, float(f.value)
+
+    def optimise(self, cfg: PoseGraphConfig = None, trace_poses=False, **kw):
+        """mh_pose_graph_optimise: {"iters", "converged", "n_poses", "n_far", "f_first", "f_last", "trace": [{"f", "step_rot",
+        "step_trans", "flags"}], "R", "t": the final poses, "trace_poses": iters x n x 12 (R, then t) when asked for}."""
+        cfg = cfg if cfg is not None else make_pose_graph_config(**kw)
+        res = PoseGraphResult()
+        tp = np.full((cfg.iters, self.n, 12), np.nan) if trace_poses else None
+        self.ctx.check(self.L.mh_pose_graph_optimise(self.h, C.byref(cfg), C.byref(res), _p(tp)))
+        R, t = self.poses()
+        out = {"iters": int(res.iters), "converged": int(res.converged), "n_poses": int(res.n_poses), "n_far": int(res.n_far), "f_first": float(res.f_first),
+               "f_last": float(res.f_last), "R": R, "t": t,
+               "trace": [{"f": float(q.f), "step_rot": float(q.step_rot), "step_trans": float(q.step_trans), "flags": int(q.flags)} for q in res.trace[:res.iters]]}
+        if trace_poses:
+            out["trace_poses"] = tp[:res.iters]
+        return out
+
+    def destroy(self):
+        if getattr(self, "h", None):
+            self.L.mh_pose_graph_destroy(self.h)
+            self.h = None
+            self.ctx._child_released()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass

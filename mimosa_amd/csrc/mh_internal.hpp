@@ -116,6 +116,8 @@ struct mh_ctx
   std::vector<mh_shard_comm *> shard_comms;
   // ... and from the place-recognition databases created on it (place_api.hip)
   std::vector<mh_place_db *> place_dbs;
+  // ... and from the pose graphs created on it (pose_graph_api.hip)
+  std::vector<mh_pose_graph *> pose_graphs;
 };
 
 // The stream of the context the calling thread is working for (set by mh_enter at every entry point): what the allocation
@@ -810,6 +812,8 @@ void shard_ctx_gone(mh_ctx * ctx);
 // place_api.hip: likewise for the place-recognition databases listed on ctx — they give their memory back while the context is
 // alive and are left with ctx == nullptr: every entry point refuses them, mh_place_db_destroy just deletes them
 void place_ctx_gone(mh_ctx * ctx);
+// pose_graph_api.hip: likewise for the pose graphs listed on ctx
+void pose_graph_ctx_gone(mh_ctx * ctx);
 // a call's DeviceResult from its flagged words in pending slot `slot` (spin_ns > 0: wait up to that long for words that have
 // not arrived); false = something is still missing
 bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, long spin_ns, mh::DeviceResult & d);

@@ -1,0 +1,463 @@
+// Pose-graph entry points of the C ABI (include/mimosa_hip.h): mh_pose_graph_*.  The kernels are pose_graph_kernels.hip, the
+// arithmetic pose_graph_device.hpp.  Everything runs on the context's stream; mh_pose_graph_optimise queues its iterations
+// (all of them, or check_every at a time, looking at the last queued iteration's flagged word in between) and ends in one wait.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "flagged_word.hpp"
+#include "mh_internal.hpp"
+#include "pose_graph_device.hpp"
+
+static_assert(sizeof(mh_pose_graph_config) == 32 && sizeof(mh_pose_graph_trace) == 32 && sizeof(mh_pose_graph_result) == 32 + 64 * 32, "mh_pose_graph_* layout");
+static_assert(MH_PGO_MAX_POSES == mh::kPgoMaxPoses && MH_PGO_MAX_EDGES == mh::kPgoMaxEdges && MH_PGO_FAR_MAX == mh::kPgoFarMax && mh::kPgoMaxIters == 64,
+              "mh_pose_graph_* constants");
+
+namespace mh
+{
+hipError_t launch_pgo_edges(const PgoGraph & g, bool want_res, hipStream_t stream);
+hipError_t launch_pgo_cost(const PgoGraph & g, hipStream_t stream);
+hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream);
+}  // namespace mh
+
+struct mh_pose_graph
+{
+  mh_ctx * ctx = nullptr;  // null: mh_shutdown of the context ran first (pose_graph_ctx_gone), the handle can only be destroyed
+  size_t max_poses = 0, max_edges = 0;
+  size_t n = 0, n_edges = 0, n_far = 0;
+  char * d_block = nullptr;  // every array of mh::PgoGraph (pgo_layout)
+  size_t off[mh::kPgArrays] = {};
+  mh::PgoGraph g{};          // device pointers into d_block
+  double * d_trace = nullptr;  // iters x n x 12: the poses behind every step (grown on demand)
+  size_t d_trace_bytes = 0;
+  uint4 * h_words = nullptr;  // one flagged word per iteration (mapped pinned) and its device-side address
+  uint4 * d_words = nullptr;
+  char * h_out = nullptr;     // pinned staging of whatever a call hands to the host (grown on demand)
+  size_t h_out_bytes = 0;
+  unsigned int seq = 0;
+};
+
+namespace
+{
+void pgo_release_device(mh_pose_graph * pg)
+{
+  AllocCache::free(pg->d_block);
+  AllocCache::free(pg->d_trace);
+  if (pg->h_words) (void)hipHostFree(pg->h_words);
+  if (pg->h_out) (void)hipHostFree(pg->h_out);
+  pg->d_block = nullptr;
+  pg->d_trace = nullptr;
+  pg->h_words = pg->d_words = nullptr;
+  pg->h_out = nullptr;
+  pg->d_trace_bytes = pg->h_out_bytes = 0;
+}
+
+// every entry point but destroy: a graph whose context was shut down
+int pgo_alive(const mh_pose_graph * pg, const char * who)
+{
+  if (!pg->ctx) return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the graph's context was shut down; the handle can only be destroyed");
+  return MH_OK;
+}
+
+// (every call that used the block has waited)
+int pgo_host(mh_pose_graph * pg, size_t bytes)
+{
+  if (bytes <= pg->h_out_bytes) return MH_OK;
+  size_t cap = size_t(64) << 10;
+  while (cap < bytes) cap <<= 1;
+  if (pg->h_out) (void)hipHostFree(pg->h_out);
+  pg->h_out = nullptr;
+  pg->h_out_bytes = 0;
+  MH_HIP(pg->ctx, hipHostMalloc(reinterpret_cast<void **>(&pg->h_out), cap, hipHostMallocDefault));
+  pg->h_out_bytes = cap;
+  return MH_OK;
+}
+
+// host -> device behind everything on the stream, through the pinned block at `at`
+template <typename T>
+hipError_t pgo_up(mh_pose_graph * pg, size_t & at, T * dst, const T * src, size_t count)
+{
+  if (!count) return hipSuccess;
+  std::memcpy(pg->h_out + at, src, count * sizeof(T));
+  const hipError_t e = hipMemcpyAsync(dst, pg->h_out + at, count * sizeof(T), hipMemcpyHostToDevice, pg->ctx->stream);
+  at += (count * sizeof(T) + 15) / 16 * 16;
+  return e;
+}
+
+int pgo_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_pose_graph ** out)
+{
+  MH_HIP(ctx, mh_enter(ctx));
+  mh_pose_graph * pg = new mh_pose_graph;
+  pg->ctx = ctx;
+  pg->max_poses = max_poses;
+  pg->max_edges = max_edges;
+  const size_t bytes = mh::pgo_layout(max_poses, std::max<size_t>(max_edges, 1), pg->off);
+  void * p = nullptr;
+  hipError_t e = AllocCache::alloc(&p, bytes);
+  pg->d_block = static_cast<char *>(p);
+  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&pg->h_words), mh::kPgoMaxIters * sizeof(uint4), hipHostMallocMapped);
+  if (e == hipSuccess) {
+    std::memset(pg->h_words, 0, mh::kPgoMaxIters * sizeof(uint4));
+    e = hipHostGetDevicePointer(reinterpret_cast<void **>(&pg->d_words), pg->h_words, 0);
+  }
+  if (e != hipSuccess) {
+    pgo_release_device(pg);
+    delete pg;
+    return hip_fail(ctx, e, "mh_pose_graph_create");
+  }
+  mh::pgo_bind(pg->g, pg->d_block, pg->off);
+  ctx->pose_graphs.push_back(pg);
+  *out = pg;
+  return MH_OK;
+}
+
+// the graph without edges: every pose's incidence list empty
+int pgo_drop_edges(mh_pose_graph * pg)
+{
+  pg->n_edges = pg->n_far = 0;
+  MH_HIP(pg->ctx, hipMemsetAsync(pg->g.inc_off, 0, (pg->n + 1) * sizeof(int), pg->ctx->stream));
+  return MH_OK;
+}
+
+int pgo_check_edges(const mh_pose_graph * pg, const mh_window_edge * edges, size_t n_edges, size_t & n_far)
+{
+  const mh_ctx * ctx = pg->ctx;
+  if (n_edges > pg->max_edges) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: more edges than the graph was created for");
+  n_far = 0;
+  for (size_t e = 0; e < n_edges; ++e) {
+    const mh_window_edge & q = edges[e];
+    if (q.pose_a < 0 || q.pose_a >= q.pose_b || static_cast<size_t>(q.pose_b) >= pg->n)
+      return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: edge " + std::to_string(e) + " needs 0 <= pose_a < pose_b < n");
+    bool finite = true;
+    for (double v : q.Z_R) finite = finite && std::isfinite(v);
+    for (double v : q.Z_t) finite = finite && std::isfinite(v);
+    for (double v : q.info) finite = finite && std::isfinite(v);
+    if (!finite) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: edge " + std::to_string(e) + " has an entry that is not finite");
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < r; ++c)
+        if (q.info[6 * r + c] != q.info[6 * c + r]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: an edge's info is not symmetric");
+    if (q.pose_b - q.pose_a >= 2) ++n_far;
+  }
+  if (n_far > MH_PGO_FAR_MAX) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_pose_graph_set_edges: more than MH_PGO_FAR_MAX edges with pose_b - pose_a >= 2");
+  return MH_OK;
+}
+
+int pgo_set_edges(mh_pose_graph * pg, const mh_window_edge * edges, size_t E, size_t n_far)
+{
+  mh_ctx * ctx = pg->ctx;
+  const size_t N = pg->n;
+  std::vector<int> ea(E), eb(E), slot(E), inc_off(N + 1, 0), inc(2 * E), far(n_far);
+  std::vector<double> ZR(9 * E), Zt(3 * E), Om(36 * E);
+  for (size_t e = 0; e < E; ++e) {
+    const mh_window_edge & q = edges[e];
+    ea[e] = q.pose_a;
+    eb[e] = q.pose_b;
+    std::memcpy(&ZR[9 * e], q.Z_R, sizeof(q.Z_R));
+    std::memcpy(&Zt[3 * e], q.Z_t, sizeof(q.Z_t));
+    std::memcpy(&Om[36 * e], q.info, sizeof(q.info));
+  }
+  far.resize(mh::kPgoFarMax);
+  (void)mh::pgo_index_edges(static_cast<int>(N), static_cast<int>(E), ea.data(), eb.data(), slot.data(), inc_off.data(), inc.data(), far.data());
+  MH_HIP(ctx, mh_enter(ctx));
+  const int rc = pgo_host(pg, (48 * E + 5 * E + N + 1 + n_far) * 8 + 16 * 16);
+  if (rc != MH_OK) return rc;
+  size_t at = 0;
+  const mh::PgoGraph & g = pg->g;
+  hipError_t e = pgo_up(pg, at, g.ea, ea.data(), E);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.eb, eb.data(), E);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.eslot, slot.data(), E);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.inc_off, inc_off.data(), N + 1);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.inc, inc.data(), 2 * E);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.far, far.data(), n_far);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.ZR, ZR.data(), 9 * E);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.Zt, Zt.data(), 3 * E);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.Om, Om.data(), 36 * E);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);  // (the pinned block is the next call's too)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) {
+    pg->n_edges = pg->n_far = 0;  // what is on the device is not a graph any more
+    return hip_fail(ctx, e, "mh_pose_graph_set_edges");
+  }
+  pg->n_edges = E;
+  pg->n_far = n_far;
+  return MH_OK;
+}
+
+mh::PgoGraph pgo_graph(const mh_pose_graph * pg)
+{
+  mh::PgoGraph g = pg->g;
+  g.N = static_cast<int>(pg->n);
+  g.E = static_cast<int>(pg->n_edges);
+  g.F = static_cast<int>(pg->n_far);
+  g.K = 6 * g.F + 1;
+  return g;
+}
+
+// the word of iteration `it`: its flags once they have arrived
+bool pgo_read_word(const mh_pose_graph * pg, int it, unsigned int seq, long spin_ns, int & flags)
+{
+  double v = 0.0;
+  if (!mh::spin_until([&] { return mh::ll_read(reinterpret_cast<const uint64_t *>(pg->h_words + it), seq, v); }, spin_ns)) return false;
+  flags = static_cast<int>(v);
+  return true;
+}
+
+int pgo_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_graph_result * out, double * trace_poses)
+{
+  mh_ctx * ctx = pg->ctx;
+  const size_t N = pg->n;
+  const int iters = cfg->iters, chunk = cfg->check_every > 0 ? cfg->check_every : iters;
+  MH_HIP(ctx, mh_enter(ctx));
+  const size_t pose_bytes = 12 * N * sizeof(double), head = sizeof(mh::PgoState) + mh::kPgoMaxIters * sizeof(mh::PgoRow);
+  const size_t trace_bytes = trace_poses ? static_cast<size_t>(iters) * pose_bytes : 0;
+  int rc = pgo_host(pg, head + trace_bytes);
+  if (rc != MH_OK) return rc;
+  if (trace_bytes > pg->d_trace_bytes) {
+    AllocCache::free(pg->d_trace);
+    pg->d_trace = nullptr;
+    pg->d_trace_bytes = 0;
+    void * p = nullptr;
+    MH_HIP(ctx, AllocCache::alloc(&p, trace_bytes));
+    pg->d_trace = static_cast<double *>(p);
+    pg->d_trace_bytes = trace_bytes;
+  }
+  const mh::PgoGraph g = pgo_graph(pg);
+  const mh::PgoParams p{cfg->damping, cfg->eps_rot, cfg->eps_trans};
+  unsigned int seq[mh::kPgoMaxIters];
+  for (int i = 0; i < iters; ++i) {
+    if (++pg->seq == 0u) ++pg->seq;
+    seq[i] = pg->seq;
+  }
+  hipError_t e = hipMemsetAsync(g.st, 0, sizeof(mh::PgoState), ctx->stream);
+  int queued = 0, flags = 0;
+  while (e == hipSuccess && queued < iters && !(flags & 1)) {
+    const int upto = std::min(queued + chunk, iters);
+    for (; e == hipSuccess && queued < upto; ++queued)
+      e = mh::launch_pgo_iteration(g, p, queued, trace_poses ? pg->d_trace + static_cast<size_t>(queued) * 12 * N : nullptr, pg->d_words + queued,
+                                   seq[queued], ctx->stream);
+    if (e != hipSuccess || queued == iters) break;
+    // the last queued iteration's word: the value itself, then the stream behind it
+    if (!pgo_read_word(pg, queued - 1, seq[queued - 1], 50000000L, flags)) {
+      e = hipStreamSynchronize(ctx->stream);
+      if (e == hipSuccess && !pgo_read_word(pg, queued - 1, seq[queued - 1], 2000000L, flags)) {
+        return fail(ctx, MH_ERR_HIP, "mh_pose_graph_optimise: the stream drained without the chain's results");
+      }
+    }
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out, g.st, sizeof(mh::PgoState), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out + sizeof(mh::PgoState), g.rows, mh::kPgoMaxIters * sizeof(mh::PgoRow), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && trace_poses)
+    e = hipMemcpyAsync(pg->h_out + head, pg->d_trace, static_cast<size_t>(queued) * pose_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return hip_fail(ctx, e, "mh_pose_graph_optimise");
+  }
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  mh::PgoState st;
+  std::memcpy(&st, pg->h_out, sizeof(st));
+  const mh::PgoRow * rows = reinterpret_cast<const mh::PgoRow *>(pg->h_out + sizeof(mh::PgoState));
+  if (st.iters < 1 || st.iters > queued) return fail(ctx, MH_ERR_HIP, "mh_pose_graph_optimise: the chain left no result");
+  std::memset(out, 0, sizeof(*out));
+  out->iters = st.iters;
+  out->converged = st.converged;
+  out->n_poses = static_cast<int32_t>(N);
+  out->n_far = static_cast<int32_t>(pg->n_far);
+  for (int i = 0; i < st.iters; ++i) {
+    out->trace[i].f = rows[i].f;
+    out->trace[i].step_rot = rows[i].step_rot;
+    out->trace[i].step_trans = rows[i].step_trans;
+    out->trace[i].flags = rows[i].flags & 4;
+  }
+  out->f_first = rows[0].f;
+  out->f_last = rows[st.iters - 1].f;
+  if (trace_poses) std::memcpy(trace_poses, pg->h_out + head, static_cast<size_t>(st.iters) * pose_bytes);
+  return MH_OK;
+}
+
+int pgo_residuals(mh_pose_graph * pg, double * r, double * chi2, double * f)
+{
+  mh_ctx * ctx = pg->ctx;
+  const size_t E = pg->n_edges;
+  MH_HIP(ctx, mh_enter(ctx));
+  const int rc = pgo_host(pg, 16 + 7 * E * sizeof(double));
+  if (rc != MH_OK) return rc;
+  const mh::PgoGraph g = pgo_graph(pg);
+  hipError_t e = hipMemsetAsync(g.st, 0, sizeof(mh::PgoState), ctx->stream);
+  if (e == hipSuccess) e = mh::launch_pgo_edges(g, true, ctx->stream);
+  if (e == hipSuccess) e = mh::launch_pgo_cost(g, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out, &g.rows[0].f, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && E) e = hipMemcpyAsync(pg->h_out + 16, g.res, 6 * E * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && E) e = hipMemcpyAsync(pg->h_out + 16 + 6 * E * sizeof(double), g.cz, E * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return hip_fail(ctx, e, "mh_pose_graph_residuals");
+  }
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (f) std::memcpy(f, pg->h_out, sizeof(double));
+  if (r && E) std::memcpy(r, pg->h_out + 16, 6 * E * sizeof(double));
+  if (chi2 && E) std::memcpy(chi2, pg->h_out + 16 + 6 * E * sizeof(double), E * sizeof(double));
+  return MH_OK;
+}
+}  // namespace
+
+namespace mhi
+{
+void pose_graph_ctx_gone(mh_ctx * ctx)
+{
+  if (ctx->pose_graphs.empty()) return;
+  (void)mh_enter(ctx);
+  (void)hipStreamSynchronize(ctx->stream);
+  for (mh_pose_graph * pg : ctx->pose_graphs) {
+    pgo_release_device(pg);
+    pg->n = pg->n_edges = pg->n_far = 0;
+    pg->ctx = nullptr;
+  }
+  ctx->pose_graphs.clear();
+}
+}  // namespace mhi
+
+extern "C" {
+
+int mh_pose_graph_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_pose_graph ** out)
+{
+  if (out) *out = nullptr;
+  if (!out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create: NULL argument");
+  return guarded(ctx, "mh_pose_graph_create", [&]() -> int {
+    // (before the context is looked at: sizes are refused the same way with and without one)
+    if (max_poses < 1 || max_poses > MH_PGO_MAX_POSES) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create: max_poses must be in 1..4096");
+    if (max_edges > MH_PGO_MAX_EDGES) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create: max_edges must be in 0..32768");
+    if (!ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create: NULL argument");
+    return pgo_create(ctx, max_poses, max_edges, out);
+  });
+}
+
+void mh_pose_graph_destroy(mh_pose_graph * pg)
+{
+  if (!pg) return;
+  if (mh_ctx * ctx = pg->ctx) {
+    (void)mh_enter(ctx);
+    (void)hipStreamSynchronize(ctx->stream);  // the pinned blocks go back: nothing may still be copying into them
+    pgo_release_device(pg);
+    auto & v = ctx->pose_graphs;
+    v.erase(std::remove(v.begin(), v.end(), pg), v.end());
+  }
+  delete pg;
+}
+
+int mh_pose_graph_set_poses(mh_pose_graph * pg, const double * R, const double * t, size_t n)
+{
+  if (!pg || !R || !t) return fail(pg ? pg->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_set_poses: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_set_poses", [&]() -> int {
+    int rc = pgo_alive(pg, "mh_pose_graph_set_poses");
+    if (rc != MH_OK) return rc;
+    mh_ctx * ctx = pg->ctx;
+    if (n < 1 || n > pg->max_poses) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_poses: n must be in 1..max_poses");
+    for (size_t i = 0; i < 9 * n; ++i)
+      if (!std::isfinite(R[i])) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_poses: R of pose " + std::to_string(i / 9) + " has an entry that is not finite");
+    for (size_t i = 0; i < 3 * n; ++i)
+      if (!std::isfinite(t[i])) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_poses: t of pose " + std::to_string(i / 3) + " has an entry that is not finite");
+    MH_HIP(ctx, mh_enter(ctx));
+    if ((rc = pgo_host(pg, 12 * n * sizeof(double) + 32)) != MH_OK) return rc;
+    size_t at = 0;
+    MH_HIP(ctx, pgo_up(pg, at, pg->g.R, R, 9 * n));
+    MH_HIP(ctx, pgo_up(pg, at, pg->g.t, t, 3 * n));
+    if (n != pg->n) {  // another graph: its edges and fixed poses are the caller's to set again
+      pg->n = n;
+      MH_HIP(ctx, hipMemsetAsync(pg->g.fixed, 0, n, ctx->stream));
+      if ((rc = pgo_drop_edges(pg)) != MH_OK) return rc;
+    }
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the pinned block is the next call's too)
+    return MH_OK;
+  });
+}
+
+int mh_pose_graph_set_fixed(mh_pose_graph * pg, const uint8_t * fixed)
+{
+  if (!pg) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_set_fixed: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_set_fixed", [&]() -> int {
+    int rc = pgo_alive(pg, "mh_pose_graph_set_fixed");
+    if (rc != MH_OK) return rc;
+    mh_ctx * ctx = pg->ctx;
+    if (pg->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_fixed: no poses have been set");
+    MH_HIP(ctx, mh_enter(ctx));
+    if (!fixed) {
+      MH_HIP(ctx, hipMemsetAsync(pg->g.fixed, 0, pg->n, ctx->stream));
+      return MH_OK;
+    }
+    if ((rc = pgo_host(pg, pg->n + 16)) != MH_OK) return rc;
+    std::vector<unsigned char> f(pg->n);
+    for (size_t i = 0; i < pg->n; ++i) f[i] = fixed[i] ? 1 : 0;
+    size_t at = 0;
+    MH_HIP(ctx, pgo_up(pg, at, pg->g.fixed, f.data(), pg->n));
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MH_OK;
+  });
+}
+
+int mh_pose_graph_set_edges(mh_pose_graph * pg, const mh_window_edge * edges, size_t n_edges)
+{
+  if (!pg || (!edges && n_edges)) return fail(pg ? pg->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_set_edges", [&]() -> int {
+    int rc = pgo_alive(pg, "mh_pose_graph_set_edges");
+    if (rc != MH_OK) return rc;
+    if (pg->n == 0) return fail(pg->ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: no poses have been set");
+    size_t n_far = 0;
+    if ((rc = pgo_check_edges(pg, edges, n_edges, n_far)) != MH_OK) return rc;
+    return pgo_set_edges(pg, edges, n_edges, n_far);
+  });
+}
+
+int mh_pose_graph_get_poses(mh_pose_graph * pg, double * R, double * t, size_t capacity, size_t * n_out)
+{
+  if (!pg) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_get_poses: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_get_poses", [&]() -> int {
+    int rc = pgo_alive(pg, "mh_pose_graph_get_poses");
+    if (rc != MH_OK) return rc;
+    mh_ctx * ctx = pg->ctx;
+    const size_t n = pg->n;
+    if (n_out) *n_out = n;
+    if (!R && !t) return MH_OK;
+    if (capacity < n) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_get_poses: capacity is below the pose count");
+    if (n == 0) return MH_OK;
+    MH_HIP(ctx, mh_enter(ctx));
+    if ((rc = pgo_host(pg, 12 * n * sizeof(double))) != MH_OK) return rc;
+    MH_HIP(ctx, hipMemcpyAsync(pg->h_out, pg->g.R, 9 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(pg->h_out + 9 * n * sizeof(double), pg->g.t, 3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (R) std::memcpy(R, pg->h_out, 9 * n * sizeof(double));
+    if (t) std::memcpy(t, pg->h_out + 9 * n * sizeof(double), 3 * n * sizeof(double));
+    return MH_OK;
+  });
+}
+
+int mh_pose_graph_residuals(mh_pose_graph * pg, double * r, double * chi2, double * f)
+{
+  if (!pg) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_residuals: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_residuals", [&]() -> int {
+    const int rc = pgo_alive(pg, "mh_pose_graph_residuals");
+    if (rc != MH_OK) return rc;
+    if (pg->n == 0) return fail(pg->ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_residuals: no poses have been set");
+    return pgo_residuals(pg, r, chi2, f);
+  });
+}
+
+int mh_pose_graph_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_graph_result * out, double * trace_poses)
+{
+  if (!pg || !cfg || !out) return fail(pg ? pg->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_optimise: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_optimise", [&]() -> int {
+    const int rc = pgo_alive(pg, "mh_pose_graph_optimise");
+    if (rc != MH_OK) return rc;
+    const mh_ctx * ctx = pg->ctx;
+    if (cfg->iters < 1 || cfg->iters > mh::kPgoMaxIters) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_optimise: iters must be in 1..64");
+    const bool ok = cfg->damping >= 0.0 && cfg->eps_rot >= 0.0 && cfg->eps_trans >= 0.0 && cfg->check_every >= 0 && std::isfinite(cfg->damping) &&
+                    std::isfinite(cfg->eps_rot) && std::isfinite(cfg->eps_trans);
+    if (!ok) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_optimise: eps, damping and check_every must be >= 0 and finite");
+    if (pg->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_optimise: no poses have been set");
+    return pgo_optimise(pg, cfg, out, trace_poses);
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,554 @@
+// One Gauss-Newton iteration of a pose graph over all keyframes (mh_pose_graph_optimise, pose_graph_api.hip): N poses, E
+// relative-pose edges with dense information matrices, some poses held fixed.  The residual, J_a = -Ad(T_ab^-1), J_b = I and
+// the retraction are the window chains' (window_device.hpp: window_between_dense, window_so3log, window_adjoint,
+// window_solve6, align_retract), used here and not restated.
+//
+// The edges are split into near ones (pose_b - pose_a == 1) and far ones (>= 2; at most kPgoFarMax).  The system is
+//   A = T + sum_f W_f^T Om_f W_f,
+// T block-tridiagonal (near edges, damping, identity rows of the fixed poses), W_f the 6 x 6N matrix with J_a in block column
+// a and I in block column b of far edge f (a block column of a fixed pose zeroed).  It is solved as
+//   Y = T^-1 [W^T | rhs]   (6F + 1 columns),   C = blockdiag(Om_f^-1) + W Y[:, :6F],   x = y - Y C^-1 W y,  y = Y[:, 6F],
+// T by the block L D L^T of window_factor, C by L D L^T without pivoting, followed by the chains' two refinement steps with
+// the residual against A itself accumulated in twice the working precision.  T must be positive definite by itself: a run
+// of poses joined by near edges needs a fixed pose or damping.  A pivot of T, of an Om_f or of C that is not positive takes
+// no step (bit 4 of the row's flags).
+//
+// Plain fp64 for the device (pose_graph_kernels.hip) and the host (tests/cpp/pose_graph_step.cpp under g++), both compiled
+// without floating-point contraction.  Work that is independent per index is a function of the index (pgo_edge, pgo_gather,
+// pgo_sweep_col): the host loops over it, the kernels give an index to a lane.  Work of one workgroup is written as PHASES
+// over a `Par` executor, as in window_device.hpp.  Nothing is summed by atomics: a pose's contributions are added in
+// edge-list order from its incidence list, the cost is folded as sum_{l < 256} (sum_k cz[l + 256 k]), k and l ascending.
+#pragma once
+
+#include <cstddef>
+
+#include "window_device.hpp"
+
+namespace mh
+{
+constexpr int kPgoMaxPoses = 4096;
+constexpr int kPgoMaxEdges = 32768;
+constexpr int kPgoFarMax = 32;
+constexpr int kPgoFold = 256;   // partial sums of the cost fold (a constant of the rule, not of a launch)
+constexpr int kPgoMaxIters = 64;
+constexpr int kPgoGather = 78;  // outputs per pose of pgo_gather: 36 of A_ii, 36 of E_i, 6 of the right-hand side
+
+struct PgoParams
+{
+  double damping, eps_rot, eps_trans;
+};
+struct PgoRow
+{
+  double f, step_rot, step_trans;
+  int flags, iters;  // flags: 1 stopped after this step | 2 converged | 4 a pivot was not positive (no step)
+};
+struct PgoState
+{
+  int stopped, converged, iters, ok;
+};
+
+struct PgoGraph
+{
+  int N, E, F, K;  // K = 6 F + 1: the columns of Y
+  double *R, *t;                           // 9 N, 3 N: the poses the chain has reached
+  double *ZR, *Zt, *Om;                    // per edge: the measurement and its information matrix
+  double *Baa, *Eba, *ga, *gb, *cz, *res;  // per edge: window_between_dense's outputs; the residual (6)
+  double *Ja, *OmL, *OmD, *OmInv;          // per far edge: J_a; Om = L D L^T; Om^-1
+  double *A, *Eb, *rhs;                    // T's diagonal blocks, its blocks (i, i - 1), the right-hand side -g
+  double *L, *Dv, *G;                      // S_i = L D L^T, G_i = S_{i-1}^-1 E_i^T
+  double *Y;                               // 6 N x K, row-major
+  double *C, *u;                           // 6 F x 6 F (lower: L, diagonal: D, upper: L D), 6 F
+  double *x, *r, *y1, *d;                  // 6 N each (d: the step norms of pgo_finish)
+  double *fold;                            // 3 x kPgoFold
+  PgoRow * rows;                           // kPgoMaxIters
+  int *ea, *eb, *eslot;                    // per edge: its poses; its far slot (-1: a near edge)
+  int *inc_off, *inc;                      // N + 1; 2 E: pose i's edges in list order, (e << 1) | (i is the edge's b)
+  int * far;                               // F: the far edges, in list order
+  unsigned char * fixed;                   // N
+  PgoState * st;
+};
+
+// Byte offsets of every array in one block for at most maxN poses and maxE edges; returns the block's size.
+enum PgoArray
+{
+  kPgR, kPgT, kPgZR, kPgZt, kPgOm, kPgBaa, kPgEba, kPgGa, kPgGb, kPgCz, kPgRes, kPgJa, kPgOmL, kPgOmD, kPgOmInv, kPgA, kPgEb, kPgRhs, kPgL,
+  kPgDv, kPgG, kPgY, kPgC, kPgU, kPgX, kPgRr, kPgY1, kPgD, kPgFold, kPgRows, kPgEa, kPgEbI, kPgSlot, kPgIncOff, kPgInc, kPgFar, kPgFixed, kPgSt,
+  kPgArrays
+};
+inline size_t pgo_layout(size_t maxN, size_t maxE, size_t off[kPgArrays])
+{
+  const size_t F = kPgoFarMax, K = 6 * F + 1, D = sizeof(double), I = sizeof(int);
+  const size_t bytes[kPgArrays] = {9 * maxN * D, 3 * maxN * D, 9 * maxE * D, 3 * maxE * D, 36 * maxE * D, 36 * maxE * D, 36 * maxE * D, 6 * maxE * D,
+                                   6 * maxE * D, maxE * D, 6 * maxE * D, 36 * F * D, 36 * F * D, 6 * F * D, 36 * F * D, 36 * maxN * D, 36 * maxN * D,
+                                   6 * maxN * D, 36 * maxN * D, 6 * maxN * D, 36 * maxN * D, 6 * maxN * K * D, 36 * F * F * D, 6 * F * D, 6 * maxN * D,
+                                   6 * maxN * D, 6 * maxN * D, 6 * maxN * D, 3 * kPgoFold * D, kPgoMaxIters * sizeof(PgoRow), maxE * I, maxE * I, maxE * I,
+                                   (maxN + 1) * I, 2 * maxE * I, F * I, maxN, sizeof(PgoState)};
+  size_t at = 0;
+  for (int k = 0; k < kPgArrays; ++k) {
+    off[k] = at;
+    at += (bytes[k] + 15) / 16 * 16;
+  }
+  return at;
+}
+inline void pgo_bind(PgoGraph & g, char * base, const size_t off[kPgArrays])
+{
+  auto dp = [&](int k) { return reinterpret_cast<double *>(base + off[k]); };
+  auto ip = [&](int k) { return reinterpret_cast<int *>(base + off[k]); };
+  g.R = dp(kPgR), g.t = dp(kPgT), g.ZR = dp(kPgZR), g.Zt = dp(kPgZt), g.Om = dp(kPgOm);
+  g.Baa = dp(kPgBaa), g.Eba = dp(kPgEba), g.ga = dp(kPgGa), g.gb = dp(kPgGb), g.cz = dp(kPgCz), g.res = dp(kPgRes);
+  g.Ja = dp(kPgJa), g.OmL = dp(kPgOmL), g.OmD = dp(kPgOmD), g.OmInv = dp(kPgOmInv);
+  g.A = dp(kPgA), g.Eb = dp(kPgEb), g.rhs = dp(kPgRhs), g.L = dp(kPgL), g.Dv = dp(kPgDv), g.G = dp(kPgG);
+  g.Y = dp(kPgY), g.C = dp(kPgC), g.u = dp(kPgU), g.x = dp(kPgX), g.r = dp(kPgRr), g.y1 = dp(kPgY1), g.d = dp(kPgD), g.fold = dp(kPgFold);
+  g.rows = reinterpret_cast<PgoRow *>(base + off[kPgRows]);
+  g.ea = ip(kPgEa), g.eb = ip(kPgEbI), g.eslot = ip(kPgSlot), g.inc_off = ip(kPgIncOff), g.inc = ip(kPgInc), g.far = ip(kPgFar);
+  g.fixed = reinterpret_cast<unsigned char *>(base + off[kPgFixed]);
+  g.st = reinterpret_cast<PgoState *>(base + off[kPgSt]);
+}
+
+// host: the index arrays of an edge list (ea, eb: E entries, 0 <= ea < eb < N) — every edge's far slot (-1: near), the far
+// edges in list order, and per pose its incidence list in edge-list order.  Returns the number of far edges; `far` takes
+// kPgoFarMax entries at most (the caller refuses a list with more before it gets here).
+inline int pgo_index_edges(int N, int E, const int * ea, const int * eb, int * eslot, int * inc_off, int * inc, int * far)
+{
+  int F = 0;
+  for (int i = 0; i <= N; ++i) inc_off[i] = 0;
+  for (int e = 0; e < E; ++e) {
+    eslot[e] = -1;
+    if (eb[e] - ea[e] >= 2) {
+      if (F < kPgoFarMax) far[F] = e;
+      eslot[e] = F++;
+    }
+    ++inc_off[ea[e] + 1];
+    ++inc_off[eb[e] + 1];
+  }
+  for (int i = 0; i < N; ++i) inc_off[i + 1] += inc_off[i];
+  // ascending e: every pose's list is in edge-list order (the running fill position of pose i is kept in inc_off[i] and put back)
+  for (int e = 0; e < E; ++e) {
+    inc[inc_off[ea[e]]++] = e << 1;
+    inc[inc_off[eb[e]]++] = (e << 1) | 1;
+  }
+  for (int i = N; i > 0; --i) inc_off[i] = inc_off[i - 1];
+  inc_off[0] = 0;
+  return F;
+}
+
+// ---- per edge --------------------------------------------------------------------------------------------------------------------
+// Edge e at the current poses.  A far edge also leaves J_a = -Ad(T_ab^-1) in its slot; want_res: the residual itself into g.res.
+MH_HD void pgo_edge(const PgoGraph & g, int e, bool want_res)
+{
+  const int a = g.ea[e], b = g.eb[e], f = g.eslot[e];
+  const double *Ra = g.R + 9 * a, *ta = g.t + 3 * a, *Rb = g.R + 9 * b, *tb = g.t + 3 * b;
+  window_between_dense(Ra, ta, Rb, tb, g.ZR + 9 * e, g.Zt + 3 * e, g.Om + 36 * e, g.Baa + 36 * e, g.Eba + 36 * e, g.ga + 6 * e, g.gb + 6 * e, g.cz[e]);
+  if (f < 0 && !want_res) return;
+  double Rat[9], abR[9], abt[3];
+  win_tr(Ra, Rat);
+  win_mm(Rat, Rb, abR);
+  const double dt[3] = {tb[0] - ta[0], tb[1] - ta[1], tb[2] - ta[2]};
+  win_mv(Rat, dt, abt);
+  if (f >= 0) {
+    double Rabt[9], tinv[3], Ad[36];
+    win_tr(abR, Rabt);
+    const double nt[3] = {-abt[0], -abt[1], -abt[2]};
+    win_mv(Rabt, nt, tinv);
+    window_adjoint(Rabt, tinv, Ad);
+    for (int q = 0; q < 36; ++q) g.Ja[36 * f + q] = -Ad[q];
+  }
+  if (want_res) {
+    double Rzt[9], Re[9];
+    win_tr(g.ZR + 9 * e, Rzt);
+    win_mm(Rzt, abR, Re);
+    const double de[3] = {abt[0] - g.Zt[3 * e], abt[1] - g.Zt[3 * e + 1], abt[2] - g.Zt[3 * e + 2]};
+    window_so3log(Re, g.res + 6 * e);
+    win_mv(Rzt, de, g.res + 6 * e + 3);
+  }
+}
+
+// ---- per pose: T and the right-hand side ----------------------------------------------------------------------------------------
+// Output l % kPgoGather of pose l / kPgoGather, each sum over the pose's incidence list in edge-list order.  A fixed pose: the
+// identity block, no off-diagonal block on either side, a zero right-hand side.  Far edges go into the right-hand side only.
+MH_HD void pgo_gather(const PgoGraph & g, const PgoParams & p, int l)
+{
+  const int i = l / kPgoGather, q = l % kPgoGather;
+  const bool fx = g.fixed[i] != 0;
+  const int * inc = g.inc + g.inc_off[i];
+  const int n = g.inc_off[i + 1] - g.inc_off[i];
+  if (q < 36) {
+    double a = 0.0;
+    if (fx) {
+      a = (q / 6 == q % 6) ? 1.0 : 0.0;
+    } else {
+      for (int k = 0; k < n; ++k) {
+        const int e = inc[k] >> 1;
+        if (g.eslot[e] >= 0) continue;
+        a += (inc[k] & 1) ? g.Om[36 * e + q] : g.Baa[36 * e + q];
+      }
+      if (q / 6 == q % 6) a += p.damping;
+    }
+    g.A[36 * i + q] = a;
+  } else if (q < 72) {
+    const int c = q - 36;
+    double a = 0.0;
+    if (!fx && i > 0 && !g.fixed[i - 1])
+      for (int k = 0; k < n; ++k) {
+        const int e = inc[k] >> 1;
+        if ((inc[k] & 1) && g.eslot[e] < 0) a += g.Eba[36 * e + c];
+      }
+    g.Eb[36 * i + c] = a;
+  } else {
+    const int r = q - 72;
+    double s = 0.0;
+    if (!fx)
+      for (int k = 0; k < n; ++k) {
+        const int e = inc[k] >> 1;
+        s += (inc[k] & 1) ? g.gb[6 * e + r] : g.ga[6 * e + r];
+      }
+    g.rhs[6 * i + r] = fx ? 0.0 : -s;
+  }
+}
+
+// ---- per far edge: Om = L D L^T and Om^-1 -----------------------------------------------------------------------------------------
+MH_HD bool pgo_far_info(const PgoGraph & g, int f)
+{
+  const double * S = g.Om + 36 * g.far[f];
+  double *L = g.OmL + 36 * f, *D = g.OmD + 6 * f;
+  for (int q = 0; q < 36; ++q) L[q] = 0.0;
+  for (int j = 0; j < 6; ++j) {
+    double d = S[7 * j];
+    for (int k = 0; k < j; ++k) d -= L[6 * j + k] * L[6 * j + k] * D[k];
+    D[j] = d;
+    if (!(d > 0.0) || !(d < 1e300)) return false;
+    for (int row = j + 1; row < 6; ++row) {
+      double s = S[6 * row + j];
+      for (int k = 0; k < j; ++k) s -= L[6 * row + k] * L[6 * j + k] * D[k];
+      L[6 * row + j] = s / d;
+    }
+  }
+  for (int c = 0; c < 6; ++c) {
+    double e[6] = {0, 0, 0, 0, 0, 0}, col[6];
+    e[c] = 1.0;
+    window_solve6(L, D, e, col);
+    for (int m = 0; m < 6; ++m) g.OmInv[36 * f + 6 * m + c] = col[m];
+  }
+  return true;
+}
+
+// ---- T = block L D L^T: window_factor over N blocks -----------------------------------------------------------------------------
+// sm: 114 doubles the phases share (the host's stack, the kernel's LDS): S, then the current block's L, D and G.
+// false (g.st->ok == 0): a pivot is not positive.
+template <typename Par>
+MH_HD bool pgo_factor(const PgoGraph & g, double * sm, Par & par)
+{
+  double *S = sm, *Lc = sm + 36, *Dc = sm + 72, *Gc = sm + 78;
+  for (int i = 0; i < g.N; ++i) {
+    par.each(36, [&](int l) {
+      const int r = l / 6, c = l % 6;
+      double s = g.A[36 * i + l];
+      if (i > 0)
+        for (int m = 0; m < 6; ++m) s -= g.Eb[36 * i + 6 * r + m] * Gc[6 * m + c];
+      S[l] = s;
+      Lc[l] = 0.0;
+    });
+    for (int j = 0; j < 6; ++j) {
+      par.each(6 - j, [&](int l) {
+        double d = S[7 * j];
+        for (int k = 0; k < j; ++k) d -= Lc[6 * j + k] * Lc[6 * j + k] * Dc[k];
+        if (l == 0) {
+          Dc[j] = d;
+          if (!(d > 0.0) || !(d < 1e300)) g.st->ok = 0;
+        } else {
+          const int row = j + l;
+          double s = S[6 * row + j];
+          for (int k = 0; k < j; ++k) s -= Lc[6 * row + k] * Lc[6 * j + k] * Dc[k];
+          Lc[6 * row + j] = s / d;
+        }
+      });
+      if (!g.st->ok) return false;
+    }
+    par.each(42, [&](int l) {
+      if (l < 36)
+        g.L[36 * i + l] = Lc[l];
+      else
+        g.Dv[6 * i + l - 36] = Dc[l - 36];
+    });
+    if (i + 1 < g.N) {
+      par.each(6, [&](int c) {
+        double col[6];
+        window_solve6(Lc, Dc, &g.Eb[36 * (i + 1) + 6 * c], col);  // column c of E^T = row c of E
+        for (int m = 0; m < 6; ++m) Gc[6 * m + c] = col[m];
+      });
+      par.each(36, [&](int l) { g.G[36 * (i + 1) + l] = Gc[l]; });
+    }
+  }
+  return true;
+}
+
+// ---- T out = v for one column: window_sweep over N blocks -----------------------------------------------------------------------
+// col < 6 F: column col of W^T; col == 6 F: the right-hand side; src != nullptr: that vector instead.  out has `stride` doubles
+// between rows.  One lane per column; L_i, D_i, G_i are the same for every column.
+MH_HD void pgo_sweep_col(const PgoGraph & g, int col, const double * src, double * out, int stride)
+{
+  const int N = g.N;
+  int fa = -1, fb = -1, f = 0, c = 0;
+  if (!src && col < 6 * g.F) {
+    f = col / 6, c = col % 6;
+    const int e = g.far[f];
+    fa = g.fixed[g.ea[e]] ? -1 : g.ea[e];
+    fb = g.fixed[g.eb[e]] ? -1 : g.eb[e];
+  }
+  double y[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < N; ++i) {
+    double v[6];
+    for (int r = 0; r < 6; ++r) {
+      double s;
+      if (src)
+        s = src[6 * i + r];
+      else if (col == 6 * g.F)
+        s = g.rhs[6 * i + r];
+      else
+        s = i == fa ? g.Ja[36 * f + 6 * c + r] : (i == fb && r == c ? 1.0 : 0.0);
+      if (i > 0)
+        for (int m = 0; m < 6; ++m) s -= g.G[36 * i + 6 * m + r] * y[m];
+      v[r] = s;
+    }
+    for (int r = 0; r < 6; ++r) {
+      y[r] = v[r];
+      out[static_cast<size_t>(6 * i + r) * stride] = v[r];
+    }
+  }
+  double xn[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = N - 1; i >= 0; --i) {
+    double yi[6], z[6];
+    for (int r = 0; r < 6; ++r) yi[r] = out[static_cast<size_t>(6 * i + r) * stride];
+    window_solve6(g.L + 36 * i, g.Dv + 6 * i, yi, z);
+    for (int r = 0; r < 6; ++r) {
+      double s = z[r];
+      if (i + 1 < N)
+        for (int m = 0; m < 6; ++m) s -= g.G[36 * (i + 1) + 6 * r + m] * xn[m];
+      yi[r] = s;
+    }
+    for (int r = 0; r < 6; ++r) {
+      xn[r] = yi[r];
+      out[static_cast<size_t>(6 * i + r) * stride] = yi[r];
+    }
+  }
+}
+
+// ---- the far edges' correction ----------------------------------------------------------------------------------------------------
+// row `row` of W times the vector y (`stride` doubles between its entries)
+MH_HD double pgo_W_row(const PgoGraph & g, int row, const double * y, int stride)
+{
+  const int f = row / 6, p = row % 6, e = g.far[f], a = g.ea[e], b = g.eb[e];
+  double s = 0.0;
+  if (!g.fixed[a])
+    for (int r = 0; r < 6; ++r) s += g.Ja[36 * f + 6 * p + r] * y[static_cast<size_t>(6 * a + r) * stride];
+  if (!g.fixed[b]) s += y[static_cast<size_t>(6 * b + p) * stride];
+  return s;
+}
+
+// C = blockdiag(Om^-1) + W Y, then C = L D L^T in place, column by column: the lower triangle is read, L replaces it, the
+// pivots stay on the diagonal, the upper triangle keeps L D.  false (g.st->ok == 0): a pivot is not positive.
+template <typename Par>
+MH_HD bool pgo_factor_C(const PgoGraph & g, Par & par)
+{
+  const int n = 6 * g.F, K = g.K;
+  par.each(n * n, [&](int l) {
+    const int row = l / n, col = l % n;
+    double s = pgo_W_row(g, row, g.Y + col, K);
+    if (row / 6 == col / 6) s = g.OmInv[36 * (row / 6) + 6 * (row % 6) + col % 6] + s;
+    g.C[l] = s;
+  });
+  for (int j = 0; j < n; ++j) {
+    par.each(1, [&](int) {
+      const double d = g.C[j * n + j];
+      if (!(d > 0.0) || !(d < 1e300)) g.st->ok = 0;
+    });
+    if (!g.st->ok) return false;
+    par.each(n - j - 1, [&](int l) {
+      const int i = j + 1 + l;
+      const double t = g.C[i * n + j];
+      g.C[j * n + i] = t;
+      g.C[i * n + j] = t / g.C[j * n + j];
+    });
+    const int m = n - j - 1;
+    par.each(m * m, [&](int l) {
+      const int i = j + 1 + l / m, k = j + 1 + l % m;
+      if (k > i) return;
+      g.C[i * n + k] -= g.C[i * n + j] * g.C[j * n + k];
+    });
+  }
+  return true;
+}
+
+// u = C^-1 W y  (y: `stride` doubles between entries), by the factors pgo_factor_C left
+template <typename Par>
+MH_HD void pgo_solve_C(const PgoGraph & g, const double * y, int stride, Par & par)
+{
+  const int n = 6 * g.F;
+  par.each(n, [&](int row) { g.u[row] = pgo_W_row(g, row, y, stride); });
+  for (int j = 0; j + 1 < n; ++j) par.each(n - j - 1, [&](int l) { g.u[j + 1 + l] -= g.C[(j + 1 + l) * n + j] * g.u[j]; });
+  par.each(n, [&](int j) { g.u[j] = g.u[j] / g.C[j * n + j]; });
+  for (int j = n - 1; j >= 1; --j) par.each(j, [&](int i) { g.u[i] -= g.C[j * n + i] * g.u[j]; });
+}
+
+// entry `row` of y - Y u: into x (first) or added to it (a refinement step)
+MH_HD void pgo_apply_row(const PgoGraph & g, const double * y, int stride, bool first, int row)
+{
+  const int n = 6 * g.F;
+  double s = y[static_cast<size_t>(row) * stride];
+  for (int c = 0; c < n; ++c) s -= g.Y[static_cast<size_t>(row) * g.K + c] * g.u[c];
+  g.x[row] = first ? s : g.x[row] + s;
+}
+
+// entry `row` of g.r = rhs - A x against the system as assembled (T's blocks, then the pose's far edges in list order), in
+// twice the working precision as the window chains take it.  The row of a fixed pose is zero.
+MH_HD void pgo_residual_row(const PgoGraph & g, int row)
+{
+  const int i = row / 6, r = row % 6;
+  if (g.fixed[i]) {
+    g.r[row] = 0.0;
+    return;
+  }
+  double hi = g.rhs[row], lo = 0.0;
+  auto term = [&](double a, double xj) {
+    const double pr = a * xj, pe = fma(a, xj, -pr);  // a x = pr + pe exactly
+    const double s = hi - pr, bv = s - hi;
+    lo += ((hi - (s - bv)) + (-pr - bv)) - pe;  // two-sum of hi and -pr
+    hi = s;
+  };
+  if (i > 0)
+    for (int m = 0; m < 6; ++m) term(g.Eb[36 * i + 6 * r + m], g.x[6 * (i - 1) + m]);
+  for (int m = 0; m < 6; ++m) term(g.A[36 * i + 6 * r + m], g.x[6 * i + m]);
+  if (i + 1 < g.N)
+    for (int m = 0; m < 6; ++m) term(g.Eb[36 * (i + 1) + 6 * m + r], g.x[6 * (i + 1) + m]);
+  const int * inc = g.inc + g.inc_off[i];
+  const int n = g.inc_off[i + 1] - g.inc_off[i];
+  for (int k = 0; k < n; ++k) {
+    const int e = inc[k] >> 1;
+    if (g.eslot[e] < 0) continue;
+    const int a = g.ea[e], b = g.eb[e];
+    if (inc[k] & 1) {
+      if (!g.fixed[a])
+        for (int m = 0; m < 6; ++m) term(g.Eba[36 * e + 6 * r + m], g.x[6 * a + m]);
+      for (int m = 0; m < 6; ++m) term(g.Om[36 * e + 6 * r + m], g.x[6 * b + m]);
+    } else {
+      for (int m = 0; m < 6; ++m) term(g.Baa[36 * e + 6 * r + m], g.x[6 * a + m]);
+      if (!g.fixed[b])
+        for (int m = 0; m < 6; ++m) term(g.Eba[36 * e + 6 * m + r], g.x[6 * b + m]);
+    }
+  }
+  g.r[row] = hi + lo;
+}
+
+// ---- the phases of one iteration that one workgroup runs ------------------------------------------------------------------------
+// stage 0, behind the sweep of all K columns: C and its factors, u for y = Y[:, 6F]; stage 1, 2, behind the sweep of g.r into
+// g.y1: u for y = g.y1.  Behind it, per row and over any number of workgroups: pgo_apply_row, then (a launch of its own: a row
+// reads its neighbours' x) pgo_residual_row.
+template <typename Par>
+MH_HD void pgo_small(const PgoGraph & g, int stage, Par & par)
+{
+  if (stage == 0) {
+    if (!pgo_factor_C(g, par)) return;
+    pgo_solve_C(g, g.Y + 6 * g.F, g.K, par);
+  } else {
+    pgo_solve_C(g, g.y1, 1, par);
+  }
+}
+// the cost in its fixed order into g.fold[0 .. kPgoFold), its total into *f
+template <typename Par>
+MH_HD void pgo_cost(const PgoGraph & g, double * f, Par & par)
+{
+  par.each(kPgoFold, [&](int l) {
+    double s = 0.0;
+    for (int e = l; e < g.E; e += kPgoFold) s += g.cz[e];
+    g.fold[l] = s;
+  });
+  par.each(1, [&](int) {
+    double s = 0.0;
+    for (int l = 0; l < kPgoFold; ++l) s += g.fold[l];
+    *f = s;
+  });
+}
+// the step, the row of iteration `it`, the stop test.  trace: nullptr, or 12 N doubles for the poses behind the step.
+template <typename Par>
+MH_HD void pgo_finish(const PgoGraph & g, const PgoParams & p, int it, double * trace, Par & par)
+{
+  const int N = g.N;
+  PgoRow & row = g.rows[it];
+  par.each(6 * N, [&](int q) {
+    if (g.st->ok && !(fabs(g.x[q]) < 1e300)) g.st->ok = 0;
+  });
+  const bool stepped = g.st->ok != 0;
+  par.sync();
+  par.each(N, [&](int i) {
+    double sr = 0.0, st = 0.0;
+    if (stepped && !g.fixed[i]) {
+      const double * xi = g.x + 6 * i;
+      double Rn[9], tn[3];
+      sr = sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]);
+      st = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+      align_retract(g.R + 9 * i, g.t + 3 * i, xi, Rn, tn);
+      for (int q = 0; q < 9; ++q) g.R[9 * i + q] = Rn[q];
+      for (int q = 0; q < 3; ++q) g.t[3 * i + q] = tn[q];
+    }
+    g.d[2 * i] = sr;
+    g.d[2 * i + 1] = st;
+  });
+  if (trace)
+    par.each(12 * N, [&](int l) {
+      const int i = l / 12, q = l % 12;
+      trace[l] = q < 9 ? g.R[9 * i + q] : g.t[3 * i + q - 9];
+    });
+  par.each(kPgoFold, [&](int l) {
+    double mr = 0.0, mt = 0.0;
+    for (int i = l; i < N; i += kPgoFold) {
+      mr = g.d[2 * i] > mr ? g.d[2 * i] : mr;
+      mt = g.d[2 * i + 1] > mt ? g.d[2 * i + 1] : mt;
+    }
+    g.fold[kPgoFold + l] = mr;
+    g.fold[2 * kPgoFold + l] = mt;
+  });
+  pgo_cost(g, &row.f, par);
+  par.each(1, [&](int) {
+    double mr = 0.0, mt = 0.0;
+    for (int l = 0; l < kPgoFold; ++l) {
+      mr = g.fold[kPgoFold + l] > mr ? g.fold[kPgoFold + l] : mr;
+      mt = g.fold[2 * kPgoFold + l] > mt ? g.fold[2 * kPgoFold + l] : mt;
+    }
+    const bool conv = stepped && mr < p.eps_rot && mt < p.eps_trans;
+    g.st->converged = conv ? 1 : 0;
+    g.st->stopped = (conv || !stepped) ? 1 : 0;
+    g.st->iters += 1;
+    row.step_rot = mr;
+    row.step_trans = mt;
+    row.flags = g.st->stopped | (conv ? 2 : 0) | (stepped ? 0 : 4);
+    row.iters = g.st->iters;
+  });
+}
+
+// ---- the host's whole iteration (tests/cpp/pose_graph_step.cpp): the kernels' launches as loops ---------------------------------
+// sm: 114 doubles.  Returns the row's flags.
+inline int pgo_iterate_host(const PgoGraph & g, const PgoParams & p, int it, double * trace, double * sm)
+{
+  WindowSerial par;
+  if (g.st->stopped) return 1;
+  for (int e = 0; e < g.E; ++e) pgo_edge(g, e, false);
+  for (int l = 0; l < kPgoGather * g.N; ++l) pgo_gather(g, p, l);
+  g.st->ok = 1;
+  for (int f = 0; f < g.F; ++f)
+    if (!pgo_far_info(g, f)) g.st->ok = 0;
+  if (g.st->ok && pgo_factor(g, sm, par)) {
+    for (int c = 0; c < g.K; ++c) pgo_sweep_col(g, c, nullptr, g.Y + c, g.K);
+    for (int stage = 0; stage < 3 && g.st->ok; ++stage) {
+      if (stage > 0) pgo_sweep_col(g, 0, g.r, g.y1, 1);
+      pgo_small(g, stage, par);
+      if (!g.st->ok) break;
+      for (int row = 0; row < 6 * g.N; ++row) pgo_apply_row(g, stage ? g.y1 : g.Y + 6 * g.F, stage ? 1 : g.K, stage == 0, row);
+      if (stage < 2)
+        for (int row = 0; row < 6 * g.N; ++row) pgo_residual_row(g, row);
+    }
+  }
+  pgo_finish(g, p, it, trace, par);
+  return g.rows[it].flags;
+}
+
+}  // namespace mh

@@ -621,6 +621,93 @@ private:
   mh_place_db * db_ = nullptr;
 };
 
+// A pose graph over all keyframes, optimised on the device (mh_pose_graph_*): where a loop closure found by PlaceDatabase and
+// measured by mh_icp_relocalise goes when its ends are further apart than the fixed-lag window is long.  Poses are world from
+// keyframe, row-major as the C ABI takes them (PoseRM: no conversion touches a bit); an edge is the window's mh_window_edge.
+inline mh_window_edge poseGraphEdge(int32_t pose_a, int32_t pose_b, const PoseRM & Z_ab, const std::array<double, 36> & info)
+{
+  mh_window_edge e{};
+  e.pose_a = pose_a;
+  e.pose_b = pose_b;
+  std::copy(Z_ab.R.begin(), Z_ab.R.end(), e.Z_R);
+  std::copy(Z_ab.t.begin(), Z_ab.t.end(), e.Z_t);
+  std::copy(info.begin(), info.end(), e.info);
+  return e;
+}
+
+class PoseGraph
+{
+public:
+  PoseGraph(const std::shared_ptr<Context> & ctx, size_t max_poses, size_t max_edges) : ctx_(ctx)
+  {
+    ctx_->check(mh_pose_graph_create(ctx_->get(), max_poses, max_edges, &pg_), "mh_pose_graph_create");
+  }
+  ~PoseGraph() { mh_pose_graph_destroy(pg_); }
+  PoseGraph(const PoseGraph &) = delete;
+  PoseGraph & operator=(const PoseGraph &) = delete;
+
+  // another count than before drops the edges and the fixed flags
+  void setPoses(const std::vector<PoseRM> & poses)
+  {
+    std::vector<double> R(9 * poses.size()), t(3 * poses.size());
+    for (size_t i = 0; i < poses.size(); ++i) {
+      std::copy(poses[i].R.begin(), poses[i].R.end(), R.begin() + static_cast<std::ptrdiff_t>(9 * i));
+      std::copy(poses[i].t.begin(), poses[i].t.end(), t.begin() + static_cast<std::ptrdiff_t>(3 * i));
+    }
+    ctx_->check(mh_pose_graph_set_poses(pg_, R.data(), t.data(), poses.size()), "mh_pose_graph_set_poses");
+    if (poses.size() != n_) n_edges_ = 0;
+    n_ = poses.size();
+  }
+  // one flag per pose; empty: no pose is fixed
+  void setFixed(const std::vector<uint8_t> & fixed)
+  {
+    if (!fixed.empty() && fixed.size() != n_) throw std::runtime_error("PoseGraph::setFixed: one flag per pose");
+    ctx_->check(mh_pose_graph_set_fixed(pg_, fixed.empty() ? nullptr : fixed.data()), "mh_pose_graph_set_fixed");
+  }
+  void setEdges(const std::vector<mh_window_edge> & edges)
+  {
+    ctx_->check(mh_pose_graph_set_edges(pg_, edges.empty() ? nullptr : edges.data(), edges.size()), "mh_pose_graph_set_edges");
+    n_edges_ = edges.size();
+  }
+  std::vector<PoseRM> poses()
+  {
+    std::vector<double> R(9 * n_), t(3 * n_);
+    size_t n = 0;
+    ctx_->check(mh_pose_graph_get_poses(pg_, R.data(), t.data(), n_, &n), "mh_pose_graph_get_poses");
+    std::vector<PoseRM> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      std::copy(R.begin() + static_cast<std::ptrdiff_t>(9 * i), R.begin() + static_cast<std::ptrdiff_t>(9 * i + 9), out[i].R.begin());
+      std::copy(t.begin() + static_cast<std::ptrdiff_t>(3 * i), t.begin() + static_cast<std::ptrdiff_t>(3 * i + 3), out[i].t.begin());
+    }
+    return out;
+  }
+  // the cost at the stored poses; chi2 (optional): r^T Om r per edge — what rejects a false loop before it is accepted; r
+  // (optional): the residuals, 6 per edge.  Nothing moves.
+  double residuals(std::vector<double> * chi2 = nullptr, std::vector<double> * r = nullptr)
+  {
+    double f = 0.0;
+    if (chi2) chi2->resize(n_edges_);
+    if (r) r->resize(6 * n_edges_);
+    ctx_->check(mh_pose_graph_residuals(pg_, r && n_edges_ ? r->data() : nullptr, chi2 && n_edges_ ? chi2->data() : nullptr, &f), "mh_pose_graph_residuals");
+    return f;
+  }
+  // trace_poses (optional): cfg.iters x n x 12 doubles, the rows of executed iterations filled
+  mh_pose_graph_result optimise(const mh_pose_graph_config & cfg, std::vector<double> * trace_poses = nullptr)
+  {
+    mh_pose_graph_result out{};
+    if (trace_poses) trace_poses->assign(static_cast<size_t>(cfg.iters > 0 ? cfg.iters : 0) * n_ * 12, 0.0);
+    ctx_->check(mh_pose_graph_optimise(pg_, &cfg, &out, trace_poses ? trace_poses->data() : nullptr), "mh_pose_graph_optimise");
+    return out;
+  }
+  size_t size() const { return n_; }
+  mh_pose_graph * underlying() { return pg_; }
+
+private:
+  std::shared_ptr<Context> ctx_;  // (declared first: the graph goes before its context)
+  mh_pose_graph * pg_ = nullptr;
+  size_t n_ = 0, n_edges_ = 0;
+};
+
 // The GaussianFactor ICPFactor::linearize returns: gtsam::HessianFactor(keys()[0], H, -b, f) (geometric_factor.hpp:559-560),
 // binary HessianFactor(k0, k1, H_ss, H_st, -b_s, H_tt, -b_t, f) (:459-462), from the C ABI's row-major result.
 inline std::shared_ptr<HessianFactor> hessianFrom(const KeyVector & keys, bool binary, const mh_icp_result & r)
