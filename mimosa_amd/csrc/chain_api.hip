@@ -7,7 +7,8 @@
 // K3, step ... on the context's stream with one wait at its
 // end; every step publishes a row of flagged words the host reads.  What the two families share is written once at the top;
 // argument checks, staging layout, the step launch and the decoding of a row are each family's own.  The factor handle,
-// linearize and the flagged words of a call live in mh_api.hip (mh_internal.hpp: mhi).
+// linearize and the flagged words of a call live in mh_api.hip (mh_internal.hpp: mhi); what a window entry point was given
+// and the checks of it that need no device in window_request.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -124,6 +125,87 @@ static void chain_fill_blocks(const mh::IcpArgs & a, bool cold0, int iters, cons
   }
 }
 
+// What a chain with several factors asks of each of them, in this order; the words are the entry point's (empty == nullptr: a
+// factor without points is welcome).  None of icps[0 .. n) is NULL.
+struct FactorWords
+{
+  const char * contexts, * unary, * sharded, * in_flight, * empty, * twice;
+};
+
+static Refusal chain_check_factors(const mh_ctx * ctx, mh_icp * const * icps, size_t n, const FactorWords & w)
+{
+  for (size_t f = 0; f < n; ++f) {
+    const mh_icp * c = icps[f];
+    if (c->ctx != ctx) return {MH_ERR_INVALID_ARG, w.contexts};
+    if (c->binary) return {MH_ERR_UNSUPPORTED, w.unary};
+    if (c->no_order || c->cap_n > c->n) return {MH_ERR_UNSUPPORTED, w.sharded};
+    if (c->n_pending || c->align.active || c->in_window || c->in_align_batch) return {MH_ERR_INVALID_ARG, w.in_flight};
+    if (w.empty && c->n == 0) return {MH_ERR_INVALID_ARG, w.empty};
+    for (size_t g = 0; g < f; ++g)
+      if (icps[g] == c) return {MH_ERR_INVALID_ARG, w.twice};
+  }
+  return {};
+}
+
+// Launch groups in slot order, as mh_icp_linearize_batch lays the same factors out: one staged K3 launch per group, member m's
+// argument block at slot[m] of an iteration (a factor in no group keeps what slot[] held).  Returns the slots per iteration.
+static int chain_plan_launches(const std::vector<LaunchGroup> & groups, int * slot, std::vector<WindowLaunch> & launches)
+{
+  launches.clear();
+  int n_slots = 0;
+  for (const LaunchGroup & g : groups) {
+    launches.push_back(WindowLaunch{g.tpb, g.k, g.n_off, n_slots, static_cast<int>(g.members.size()), 0});
+    for (size_t m : g.members) slot[m] = n_slots++;
+  }
+  return n_slots;
+}
+
+// The grid prefix of every launch (where each member's workgroups start, and their sum: the launch's grid) from the first
+// iteration's argument blocks.  Launch gi has n + 1 entries, so its prefix starts gi entries behind its first slot — where
+// chain_launch_k3 looks for it.
+static void chain_fill_prefix(int * prefix, std::vector<WindowLaunch> & launches, const mh::IcpArgs * blocks)
+{
+  for (size_t gi = 0; gi < launches.size(); ++gi) {
+    WindowLaunch & wl = launches[gi];
+    int * start = prefix + wl.first + static_cast<int>(gi);
+    int acc = 0;
+    for (int i = 0; i < wl.n; ++i) {
+      start[i] = acc;
+      acc += mh::class_grid(blocks[wl.first + i].n, wl.tpb);
+    }
+    start[wl.n] = acc;
+    wl.grid = acc;
+  }
+}
+
+// ... and the K3 launches of one iteration whose argument blocks start at `blocks` (device), prefix as chain_fill_prefix left it
+static hipError_t chain_launch_k3(const std::vector<WindowLaunch> & launches, mh::IcpArgs * blocks, const int * prefix, hipStream_t stream)
+{
+  hipError_t e = hipSuccess;
+  for (size_t gi = 0; gi < launches.size() && e == hipSuccess; ++gi) {
+    const WindowLaunch & wl = launches[gi];
+    e = mh::launch_linearize_batch(blocks + wl.first, prefix + wl.first + static_cast<int>(gi), wl.n, wl.grid, wl.tpb, wl.k, wl.n_off, false, stream);
+  }
+  return e;
+}
+
+// the step's parameters of an alignment of icp under cfg, gz = -g_unit
+static mh::AlignParams align_params(const mh_icp_align_config & cfg, const mh_icp * icp, const double gz[3])
+{
+  mh::AlignParams p;
+  for (int i = 0; i < 3; ++i) p.gz[i] = gz[i];
+  p.eps_rot = cfg.eps_rot;
+  p.eps_trans = cfg.eps_trans;
+  p.damping = cfg.damping;
+  p.prior_rot = cfg.prior_sigma_rot > 0.0 ? 1.0 / (cfg.prior_sigma_rot * cfg.prior_sigma_rot) : 0.0;
+  p.prior_trans = cfg.prior_sigma_trans > 0.0 ? 1.0 / (cfg.prior_sigma_trans * cfg.prior_sigma_trans) : 0.0;
+  p.thresh_rot = icp->cfg.degen_thresh_rot;
+  p.thresh_trans = icp->cfg.degen_thresh_trans;
+  p.reg_4_dof = icp->cfg.reg_4_dof;
+  p.project_on_degeneracy = icp->cfg.project_on_degneneracy;
+  return p;
+}
+
 // The loop of a blocking call (chunk > 0: queue that many iterations, wait for the last row queued, and again until all are
 // queued or a row says the chain has stopped, bit 1 of its flags word) and the wait of a call that did not block (chunk == 0:
 // everything is queued, wait for its last row); then the result.  enqueue(upto) puts the iterations up to `upto` on the stream
@@ -232,17 +314,7 @@ static int align_begin(mh_icp * icp, const double R0[9], const double t0[3], con
   c.queued = 0;
   c.count0 = icp->linearize_count;
   c.cold0 = icp->cold;
-  mh::AlignParams & p = c.p;
-  for (int i = 0; i < 3; ++i) p.gz[i] = c.gz[i];
-  p.eps_rot = cfg->eps_rot;
-  p.eps_trans = cfg->eps_trans;
-  p.damping = cfg->damping;
-  p.prior_rot = cfg->prior_sigma_rot > 0.0 ? 1.0 / (cfg->prior_sigma_rot * cfg->prior_sigma_rot) : 0.0;
-  p.prior_trans = cfg->prior_sigma_trans > 0.0 ? 1.0 / (cfg->prior_sigma_trans * cfg->prior_sigma_trans) : 0.0;
-  p.thresh_rot = icp->cfg.degen_thresh_rot;
-  p.thresh_trans = icp->cfg.degen_thresh_trans;
-  p.reg_4_dof = icp->cfg.reg_4_dof;
-  p.project_on_degeneracy = icp->cfg.project_on_degneneracy;
+  c.p = align_params(*cfg, icp, c.gz);
 
   const int ppw = mh::linearize_class(a.n, a.k, false);
   int * start = reinterpret_cast<int *>(h);
@@ -403,16 +475,10 @@ static int align_batch_begin(mh_icp * const * icps, size_t B, const double * R0,
     if (!icps[m]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: NULL member");
   ctx = icps[0]->ctx;
   if (ctx->align_batch.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: the context has a batch call in flight");
-  for (size_t m = 0; m < B; ++m) {
-    const mh_icp * c = icps[m];
-    if (c->ctx != ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: factors of different contexts");
-    if (c->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align_batch: unary factors only");
-    if (c->no_order || c->cap_n > c->n) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align_batch: not for the factors of the map-sharded path");
-    if (c->n_pending || c->align.active || c->in_window || c->in_align_batch) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: a member has calls in flight");
-    if (c->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: a member has no points");
-    for (size_t g = 0; g < m; ++g)
-      if (icps[g] == c) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: the same factor twice");
-  }
+  static constexpr FactorWords words{"mh_icp_align_batch: factors of different contexts", "mh_icp_align_batch: unary factors only",
+                                     "mh_icp_align_batch: not for the factors of the map-sharded path", "mh_icp_align_batch: a member has calls in flight",
+                                     "mh_icp_align_batch: a member has no points", "mh_icp_align_batch: the same factor twice"};
+  if (const Refusal no = chain_check_factors(ctx, icps, B, words)) return fail(ctx, no.code, no.message);
   if (cfg->max_iters < 1 || cfg->max_iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: max_iters must be in 1..64");
   if (!(cfg->eps_rot >= 0.0) || !(cfg->eps_trans >= 0.0) || !(cfg->damping >= 0.0) || !(cfg->prior_sigma_rot >= 0.0) ||
       !(cfg->prior_sigma_trans >= 0.0) || cfg->check_every < 0)
@@ -428,15 +494,7 @@ static int align_batch_begin(mh_icp * const * icps, size_t B, const double * R0,
   c.queued = 0;
   c.out = out;
   for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
-  // launch groups in slot order, as mh_icp_window_optimise lays the same factors out
-  const std::vector<LaunchGroup> groups = mhi::window_launch_groups(icps, B);
-  c.launches.clear();
-  c.n_slots = 0;
-  for (const LaunchGroup & g : groups) {
-    WindowLaunch wl{g.tpb, g.k, g.n_off, c.n_slots, static_cast<int>(g.members.size()), 0};
-    for (size_t m : g.members) c.slot[m] = c.n_slots++;
-    c.launches.push_back(wl);
-  }
+  c.n_slots = chain_plan_launches(mhi::window_launch_groups(icps, B), c.slot, c.launches);  // as mh_icp_window_optimise lays the same factors out
 
   char * h = static_cast<char *>(ctx->h_align_batch);
   char * d = static_cast<char *>(ctx->d_align_batch);
@@ -457,31 +515,9 @@ static int align_batch_begin(mh_icp * const * icps, size_t B, const double * R0,
     std::memcpy(st.t, a.t, sizeof(st.t));
     std::memcpy(h + kABStateAt + kABStateStride * m, &st, sizeof(st));
     chain_fill_blocks(a, icp->cold, iters, c.seq, blocks + c.slot[m], static_cast<size_t>(c.n_slots), 0);
-
-    mh::AlignParams & p = c.p[m];
-    for (int i = 0; i < 3; ++i) p.gz[i] = c.gz[i];
-    p.eps_rot = cfg->eps_rot;
-    p.eps_trans = cfg->eps_trans;
-    p.damping = cfg->damping;
-    p.prior_rot = cfg->prior_sigma_rot > 0.0 ? 1.0 / (cfg->prior_sigma_rot * cfg->prior_sigma_rot) : 0.0;
-    p.prior_trans = cfg->prior_sigma_trans > 0.0 ? 1.0 / (cfg->prior_sigma_trans * cfg->prior_sigma_trans) : 0.0;
-    p.thresh_rot = icp->cfg.degen_thresh_rot;
-    p.thresh_trans = icp->cfg.degen_thresh_trans;
-    p.reg_4_dof = icp->cfg.reg_4_dof;
-    p.project_on_degeneracy = icp->cfg.project_on_degneneracy;
+    c.p[m] = align_params(*cfg, icp, c.gz);
   }
-  int * prefix = reinterpret_cast<int *>(h);
-  for (size_t gi = 0; gi < c.launches.size(); ++gi) {
-    WindowLaunch & wl = c.launches[gi];
-    int * start = prefix + wl.first + static_cast<int>(gi);
-    int acc = 0;
-    for (int i = 0; i < wl.n; ++i) {
-      start[i] = acc;
-      acc += mh::class_grid(blocks[wl.first + i].n, wl.tpb);
-    }
-    start[wl.n] = acc;
-    wl.grid = acc;
-  }
+  chain_fill_prefix(reinterpret_cast<int *>(h), c.launches, blocks);
   MH_HIP(ctx, hipMemcpyAsync(d, h, kABBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(iters), hipMemcpyHostToDevice, ctx->stream));
   c.active = true;
   for (size_t m = 0; m < B; ++m) {
@@ -499,12 +535,7 @@ static int align_batch_enqueue(mh_ctx * ctx, int upto)
   auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + kABBlocksAt);
   const int * prefix = reinterpret_cast<const int *>(d);
   for (int it = c.queued; it < upto; ++it) {
-    hipError_t e = hipSuccess;
-    for (size_t gi = 0; gi < c.launches.size() && e == hipSuccess; ++gi) {
-      const WindowLaunch & wl = c.launches[gi];
-      e = mh::launch_linearize_batch(blocks + static_cast<size_t>(it) * c.n_slots + wl.first, prefix + wl.first + static_cast<int>(gi), wl.n, wl.grid, wl.tpb, wl.k,
-                                     wl.n_off, false, ctx->stream);
-    }
+    hipError_t e = chain_launch_k3(c.launches, blocks + static_cast<size_t>(it) * c.n_slots, prefix, ctx->stream);
     if (e == hipSuccess) {
       mh::AlignBatchStepArgs s;
       std::memset(static_cast<void *>(&s), 0, sizeof(s));
@@ -610,114 +641,41 @@ static void window_abandon(mh_ctx * ctx)
   window_release(ctx);
 }
 
-static int window_begin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses,
-                        const mh_icp_window_relin * relin, uint32_t * evaluated_mask, bool lin_call, const mh_window_linear_factor * lin, size_t n_lin,
-                        const mh_window_edge * edges, size_t n_edges, bool mcall = false, mh_window_marginal * marg = nullptr,
-                        const mh_window_joint_factor * joint = nullptr, mh_window_joint_marginal * jmarg = nullptr, bool jmcall = false)
+// ---- the start of a window call: window_begin and its stages ---------------------------------------------------------------
+// What is asked of the factors themselves, where the order of the checks has it (window_request.hpp: behind the arguments,
+// before the config).
+static Refusal window_check_factors(const WindowRequest & q)
 {
-  // jmcall: mh_icp_window_marginalise_joint — mcall (set as well) whose edges may reach beyond pose 1 and whose result goes to jmarg
-  // mcall: mh_icp_window_marginalise — the same checks, staging and books for ONE queued "iteration" in which only icps[0] runs K3
-  // (a launch of its own class, as mh_icp_align runs it) and the marginal kernel stands in for the step
-  mh_ctx * ctx = window_ctx(icps, W);
-  // the edges first: what is wrong with them is told apart without a factor
-  if (n_edges > static_cast<size_t>(MH_WINDOW_EDGE_MAX)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: at most 32 edges per call");
-  if (n_edges && !edges) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: NULL edges");
-  for (size_t e = 0; e < n_edges; ++e) {
-    const mh_window_edge & q = edges[e];
-    if (q.pose_a < 0 || static_cast<size_t>(q.pose_b) >= W || q.pose_b < 0 || q.pose_a >= q.pose_b)
-      return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: an edge needs 0 <= pose_a < pose_b <= W - 1");
-    bool fin = true;
-    for (double v : q.Z_R) fin = fin && std::isfinite(v);
-    for (double v : q.Z_t) fin = fin && std::isfinite(v);
-    for (double v : q.info) fin = fin && std::isfinite(v);
-    if (!fin) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: an edge has an entry that is not finite");
-    for (int r = 0; r < 6; ++r)
-      for (int c = 0; c < r; ++c)
-        if (q.info[6 * r + c] != q.info[6 * c + r]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_edges: an edge's info is not symmetric");
-  }
-  for (size_t e = 0; mcall && !jmcall && e < n_edges; ++e)
-    if (edges[e].pose_a == 0 && edges[e].pose_b > 1)
-      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_marginalise: an edge from pose 0 beyond pose 1 makes the marginal a joint factor on several poses");
-  // the joint factor: behind the edges, before the factors and W
-  if (joint) {
-    const mh_window_joint_factor & q = *joint;
-    if (q.n_poses < 1 || q.n_poses > MH_WINDOW_JOINT_POSES) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_joint: n_poses must be in 1..4");
-    const int n = q.n_poses;
-    for (int m = 0; m < n; ++m)
-      if (q.pose[m] < 0 || static_cast<size_t>(q.pose[m]) >= W || (m > 0 && q.pose[m] <= q.pose[m - 1]))
-        return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_joint: the poses must be strictly ascending in 0 .. W - 1");
-    bool fin = std::isfinite(q.f);
-    for (int k = 0; k < 9 * n; ++k) fin = fin && std::isfinite(q.L_R[k]);
-    for (int k = 0; k < 3 * n; ++k) fin = fin && std::isfinite(q.L_t[k]);
-    for (int r = 0; r < 6 * n; ++r) {
-      fin = fin && std::isfinite(q.b[r]);
-      for (int c = 0; c < 6 * n; ++c) fin = fin && std::isfinite(q.H[24 * r + c]);
-    }
-    if (!fin) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_joint: the joint factor has an entry that is not finite");
-    for (int r = 0; r < 6 * n; ++r)
-      for (int c = 0; c < r; ++c)
-        if (q.H[24 * r + c] != q.H[24 * c + r]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_joint: the joint factor's H is not symmetric");
-  }
-  int sep[MH_WINDOW_JOINT_POSES] = {0, 0, 0, 0}, n_sep = 0;
-  if (jmcall) {
-    if (joint && joint->pose[0] != 0)
-      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_marginalise_joint: a joint factor without pose 0 would stay in the window as a second joint factor");
-    unsigned int smask = 2u;
-    for (size_t e = 0; e < n_edges; ++e)
-      if (edges[e].pose_a == 0) smask |= 1u << std::min(edges[e].pose_b, 31);  // (a window of more than 16 poses is refused below)
-    for (int m = 1; joint && m < joint->n_poses; ++m) smask |= 1u << std::min(joint->pose[m], 31);
-    for (int i = 1; i < 32; ++i)
-      if ((smask >> i) & 1u) {
-        if (n_sep < MH_WINDOW_JOINT_POSES) sep[n_sep] = i;
-        ++n_sep;
-      }
-    if (n_sep > MH_WINDOW_JOINT_POSES)
-      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_marginalise_joint: the separator of pose 0 has more than 4 poses");
-  }
-  if (!icps || !R || !t || !has_Z || !g_unit || !cfg || (jmcall ? !jmarg : mcall ? !marg : !out)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL argument");
-  if (W < 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the window has no pose");
-  if (mcall && W < 2) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_marginalise: the window needs a pose behind the oldest");
-  if (W > static_cast<size_t>(mh::kWindowMax)) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: at most 16 poses per call");
-  for (size_t f = 0; f < W; ++f)
-    if (!icps[f]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL factor");
-  ctx = icps[0]->ctx;
-  if (ctx->window.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the context has a window call in flight");
-  for (size_t f = 0; f < W; ++f) {
-    const mh_icp * c = icps[f];
-    if (c->ctx != ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: factors of different contexts");
-    if (c->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: unary factors only");
-    if (c->no_order || c->cap_n > c->n) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_window_optimise: not for the factors of the map-sharded path");
-    if (c->n_pending || c->align.active || c->in_window) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: a factor has calls in flight");
-    for (size_t g = 0; g < f; ++g)
-      if (icps[g] == c) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the same factor twice");
-  }
-  if (cfg->iters < 1 || cfg->iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: iters must be in 1..64");
-  bool ok = cfg->damping >= 0.0 && cfg->eps_rot >= 0.0 && cfg->eps_trans >= 0.0 && cfg->check_every >= 0;
-  for (int i = 0; i < 6; ++i) ok = ok && cfg->between_info[i] >= 0.0 && cfg->prior_info[i] >= 0.0;
-  if (!ok) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: eps, damping, between_info, prior_info and check_every must be >= 0");
-  if (relin && !(relin->relin_rot >= 0.0 && relin->relin_rot <= std::numeric_limits<double>::max() && relin->relin_trans >= 0.0 &&
-                 relin->relin_trans <= std::numeric_limits<double>::max()))
-    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: relin_rot and relin_trans must be finite and >= 0");
-  if (lin_call) {
-    if (n_lin > static_cast<size_t>(MH_WINDOW_LINEAR_MAX)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_lin: at most 32 linear factors per call");
-    if (n_lin && !lin) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_lin: NULL linear factors");
-    for (size_t j = 0; j < n_lin; ++j) {
-      const mh_window_linear_factor & q = lin[j];
-      if (q.pose < 0 || static_cast<size_t>(q.pose) >= W) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_lin: a linear factor's pose is outside the window");
-      bool fin = std::isfinite(q.f);
-      for (double v : q.L_R) fin = fin && std::isfinite(v);
-      for (double v : q.L_t) fin = fin && std::isfinite(v);
-      for (double v : q.H) fin = fin && std::isfinite(v);
-      for (double v : q.b) fin = fin && std::isfinite(v);
-      if (!fin) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise_lin: a linear factor has an entry that is not finite");
-    }
-  }
-  unsigned int zmask = 0;
-  for (size_t f = 1; f < W; ++f)
-    if (has_Z[f]) zmask |= 1u << f;
-  if (zmask && (!Z_R || !Z_t)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_optimise: NULL between measurements");
-  MH_HIP(ctx, mh_enter(ctx));
+  static_assert(kWindowItersMax == kMaxPending, "the chain holds a factor's whole ring: one pending slot per iteration");
+  const mh_ctx * ctx = q.icps[0]->ctx;
+  if (ctx->window.active) return {MH_ERR_INVALID_ARG, "mh_icp_window_optimise: the context has a window call in flight"};
+  static constexpr FactorWords words{"mh_icp_window_optimise: factors of different contexts", "mh_icp_window_optimise: unary factors only",
+                                     "mh_icp_window_optimise: not for the factors of the map-sharded path", "mh_icp_window_optimise: a factor has calls in flight",
+                                     nullptr, "mh_icp_window_optimise: the same factor twice"};
+  return chain_check_factors(ctx, q.icps, q.W, words);
+}
+
+// The shape of the call: its iterations, and which factor's K3 runs in which launch from which slot.  A marginal is ONE queued
+// "iteration" in which only icps[0] runs K3, in the class of a call of its own (as mh_icp_align runs it), and the marginal
+// kernel stands in for the step.
+static void window_plan(WindowCall & c, const WindowRequest & q)
+{
+  const bool marginal = q.kind != WindowKind::optimise;
+  c.W = static_cast<int>(q.W);
+  c.iters = marginal ? 1 : q.cfg->iters;
+  std::vector<LaunchGroup> groups;
+  if (!marginal)
+    groups = mhi::window_launch_groups(q.icps, q.W);
+  else if (const mh_icp * icp = q.icps[0]; icp->n)
+    groups.push_back(LaunchGroup{mh::linearize_class(static_cast<int>(icp->n), static_cast<int>(icp->cfg.num_corres_points), false),
+                                 icp->cfg.num_corres_points == 5 ? 5 : 8, icp->map->n_off, false, {0}});
+  for (size_t f = 0; f < q.W; ++f) c.slot[f] = -1;
+  c.n_slots = chain_plan_launches(groups, c.slot, c.launches);
+}
+
+// the context's three blocks, on first use
+static int window_alloc(mh_ctx * ctx)
+{
   if (!ctx->h_window) MH_HIP(ctx, hipHostMalloc(&ctx->h_window, kWinStageJointAt + sizeof(mh::WindowJoint), hipHostMallocDefault));
   if (!ctx->d_window) MH_HIP(ctx, hipMalloc(&ctx->d_window, kWinBytes));
   if (!ctx->h_window_rows) {
@@ -725,171 +683,185 @@ static int window_begin(mh_icp * const * icps, size_t W, const double * R, const
     std::memset(ctx->h_window_rows, 0, kWinRowWords * sizeof(uint4) * kMaxPending);
     MH_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->d_window_rows), ctx->h_window_rows, 0));
   }
+  return MH_OK;
+}
 
+// The first part of h_window: WindowState, per factor the argument blocks of a components-off linearize at its pose in every
+// iteration, the grid prefixes.  c.R0 keeps the caller's R for the epilogue of `first`; the chain starts from a.R, which for a
+// unary factor is the same matrix.
+static int window_stage_blocks(mh_ctx * ctx, const WindowRequest & q, unsigned int zmask)
+{
   WindowCall & c = ctx->window;
-  const int iters = mcall ? 1 : cfg->iters;
-  c.W = static_cast<int>(W);
-  c.iters = iters;
-  c.marginal = mcall;
-  c.mout = marg;
-  if (mcall) {
-    std::memcpy(c.L1R, R + 9, sizeof(c.L1R));
-    std::memcpy(c.L1t, t + 3, sizeof(c.L1t));
-  }
-  c.joint = joint != nullptr && !mcall;
-  c.jmarginal = jmcall;
-  c.jm_joint = jmcall && joint != nullptr;
-  c.jmout = jmarg;
-  c.n_sep = n_sep;
-  for (int k = 0; k < MH_WINDOW_JOINT_POSES; ++k) {
-    c.sep[k] = sep[k];
-    if (k < n_sep) {  // (W >= 2 and every separator pose inside the window: the edges' and the joint factor's checks)
-      std::memcpy(c.LSR[k], R + 9 * sep[k], sizeof(c.LSR[k]));
-      std::memcpy(c.LSt[k], t + 3 * sep[k], sizeof(c.LSt[k]));
-    }
-  }
-  c.queued = 0;
-  c.out = out;
-  c.trace_poses = trace_poses;
-  c.relin = relin != nullptr;
-  c.relin_rot = relin ? relin->relin_rot : 0.0;
-  c.relin_trans = relin ? relin->relin_trans : 0.0;
-  c.evaluated_mask = evaluated_mask;
-  c.lin = lin_call;
-  c.edges = n_edges > 0;
-  for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
-  // launch groups in slot order, as mh_icp_linearize_batch lays the same window out
-  std::vector<LaunchGroup> groups;
-  if (!mcall)
-    groups = mhi::window_launch_groups(icps, W);
-  else if (icps[0]->n)  // the oldest factor alone, in the class of a call of its own
-    groups.push_back(LaunchGroup{mh::linearize_class(static_cast<int>(icps[0]->n), static_cast<int>(icps[0]->cfg.num_corres_points), false),
-                                 icps[0]->cfg.num_corres_points == 5 ? 5 : 8, icps[0]->map->n_off, false, {0}});
-  c.launches.clear();
-  c.n_slots = 0;
-  for (size_t f = 0; f < W; ++f) c.slot[f] = -1;
-  for (const LaunchGroup & g : groups) {
-    WindowLaunch wl{g.tpb, g.k, g.n_off, c.n_slots, static_cast<int>(g.members.size()), 0};
-    for (size_t f : g.members) c.slot[f] = c.n_slots++;
-    c.launches.push_back(wl);
-  }
-
   char * h = static_cast<char *>(ctx->h_window);
-  char * d = static_cast<char *>(ctx->d_window);
   auto * blocks = reinterpret_cast<mh::IcpArgs *>(h + kWinBlocksAt);
   mh::WindowState st;
   std::memset(&st, 0, sizeof(st));
-  for (int it = 0; it < iters; ++it) c.seq[it] = mhi::next_call_seq();
-  // per factor the argument block of a components-off linearize at its pose.  c.R0 keeps the caller's R for the epilogue of
-  // `first`; the chain starts from a.R, which for a unary factor is the same matrix.
-  for (size_t f = 0; f < W; ++f) {
-    mh_icp * icp = icps[f];
+  for (size_t f = 0; f < q.W; ++f) {
+    mh_icp * icp = q.icps[f];
     c.icps[f] = icp;
     c.count0[f] = icp->linearize_count;
-    std::memcpy(c.R0[f], R + 9 * f, sizeof(c.R0[f]));
-    std::memcpy(st.R[f], R + 9 * f, sizeof(st.R[f]));
-    std::memcpy(st.t[f], t + 3 * f, sizeof(st.t[f]));
+    std::memcpy(c.R0[f], q.R + 9 * f, sizeof(c.R0[f]));
+    std::memcpy(st.R[f], q.R + 9 * f, sizeof(st.R[f]));
+    std::memcpy(st.t[f], q.t + 3 * f, sizeof(st.t[f]));
     if ((zmask >> f) & 1u) {
-      std::memcpy(st.ZR[f], Z_R + 9 * f, sizeof(st.ZR[f]));
-      std::memcpy(st.Zt[f], Z_t + 3 * f, sizeof(st.Zt[f]));
+      std::memcpy(st.ZR[f], q.Z_R + 9 * f, sizeof(st.ZR[f]));
+      std::memcpy(st.Zt[f], q.Z_t + 3 * f, sizeof(st.Zt[f]));
     }
-    if (icp->n == 0 || (mcall && f > 0)) continue;
+    if (c.slot[f] < 0) continue;  // an empty factor, or one a marginal leaves alone
     mh::IcpArgs a;
-    const int rc = mhi::chain_k3_block(icp, R + 9 * f, t + 3 * f, g_unit, a);
+    const int rc = mhi::chain_k3_block(icp, q.R + 9 * f, q.t + 3 * f, q.g_unit, a);
     if (rc != MH_OK) return rc;
-    a.ll = reinterpret_cast<uint4 *>(d + kWinLlAt) + 32 * f;
+    a.ll = reinterpret_cast<uint4 *>(static_cast<char *>(ctx->d_window) + kWinLlAt) + 32 * f;
     std::memcpy(st.R[f], a.R, sizeof(st.R[f]));
     std::memcpy(st.t[f], a.t, sizeof(st.t[f]));
-    chain_fill_blocks(a, icp->cold, iters, c.seq, blocks + c.slot[f], static_cast<size_t>(c.n_slots), 0);
+    chain_fill_blocks(a, icp->cold, c.iters, c.seq, blocks + c.slot[f], static_cast<size_t>(c.n_slots), 0);
   }
-  int * prefix = reinterpret_cast<int *>(h);
-  for (size_t gi = 0; gi < c.launches.size(); ++gi) {
-    WindowLaunch & wl = c.launches[gi];
-    int * start = prefix + wl.first + static_cast<int>(gi);
-    int acc = 0;
-    for (int i = 0; i < wl.n; ++i) {
-      start[i] = acc;
-      acc += mh::class_grid(blocks[wl.first + i].n, wl.tpb);
-    }
-    start[wl.n] = acc;
-    wl.grid = acc;
-  }
+  chain_fill_prefix(reinterpret_cast<int *>(h), c.launches, blocks);
   std::memcpy(h + kWinStateAt, &st, sizeof(st));
+  return MH_OK;
+}
 
-  mh::WindowParams & p = c.p;
+static void window_fill_params(mh::WindowParams & p, const WindowRequest & q, unsigned int zmask, const double gz[3])
+{
   std::memset(&p, 0, sizeof(p));
-  p.W = c.W;
+  p.W = static_cast<int>(q.W);
   p.has_Z = zmask;
-  for (size_t f = 0; f < W; ++f) {
-    const mh_icp * icp = icps[f];
+  for (size_t f = 0; f < q.W; ++f) {
+    const mh_icp * icp = q.icps[f];
     if (icp->n) p.have |= 1u << f;
     if (icp->cfg.reg_4_dof) p.reg_4_dof |= 1u << f;
     if (icp->cfg.project_on_degneneracy) p.project_on_degeneracy |= 1u << f;
     p.thresh_rot[f] = icp->cfg.degen_thresh_rot;
     p.thresh_trans[f] = icp->cfg.degen_thresh_trans;
   }
-  for (int i = 0; i < 3; ++i) p.gz[i] = c.gz[i];
+  for (int i = 0; i < 3; ++i) p.gz[i] = gz[i];
   for (int i = 0; i < 6; ++i) {
-    p.Wb[i] = cfg->between_info[i];
-    p.prior[i] = cfg->prior_info[i];
+    p.Wb[i] = q.cfg->between_info[i];
+    p.prior[i] = q.cfg->prior_info[i];
   }
-  p.damping = cfg->damping;
-  p.eps_rot = cfg->eps_rot;
-  p.eps_trans = cfg->eps_trans;
+  p.damping = q.cfg->damping;
+  p.eps_rot = q.cfg->eps_rot;
+  p.eps_trans = q.cfg->eps_trans;
+}
 
-  MH_HIP(ctx, hipMemcpyAsync(d, h, kWinBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(iters), hipMemcpyHostToDevice, ctx->stream));
-  if (lin_call) {
-    // the linear factors, once per call: the header and the factors in use
-    auto * wl = reinterpret_cast<mh::WindowLinear *>(h + kWinStageBytes);
-    wl->n = static_cast<int>(n_lin);
-    wl->pad = 0;
-    for (size_t j = 0; j < static_cast<size_t>(mh::kWindowLinMax); ++j) wl->pose[j] = j < n_lin ? lin[j].pose : 0;
-    for (size_t j = 0; j < n_lin; ++j) {
-      std::memcpy(wl->LR[j], lin[j].L_R, sizeof(wl->LR[j]));
-      std::memcpy(wl->Lt[j], lin[j].L_t, sizeof(wl->Lt[j]));
-      std::memcpy(wl->H[j], lin[j].H, sizeof(wl->H[j]));
-      std::memcpy(wl->b[j], lin[j].b, sizeof(wl->b[j]));
-      wl->f[j] = lin[j].f;
-    }
-    MH_HIP(ctx, hipMemcpyAsync(d + kWinLinAt, wl, sizeof(mh::WindowLinear), hipMemcpyHostToDevice, ctx->stream));
+// the linear factors, once per call: the header and the factors in use
+static int stage_linear(mh_ctx * ctx, const mh_window_linear_factor * lin, size_t n_lin)
+{
+  auto * wl = reinterpret_cast<mh::WindowLinear *>(static_cast<char *>(ctx->h_window) + kWinStageBytes);
+  wl->n = static_cast<int>(n_lin);
+  wl->pad = 0;
+  for (size_t j = 0; j < static_cast<size_t>(mh::kWindowLinMax); ++j) wl->pose[j] = j < n_lin ? lin[j].pose : 0;
+  for (size_t j = 0; j < n_lin; ++j) {
+    std::memcpy(wl->LR[j], lin[j].L_R, sizeof(wl->LR[j]));
+    std::memcpy(wl->Lt[j], lin[j].L_t, sizeof(wl->Lt[j]));
+    std::memcpy(wl->H[j], lin[j].H, sizeof(wl->H[j]));
+    std::memcpy(wl->b[j], lin[j].b, sizeof(wl->b[j]));
+    wl->f[j] = lin[j].f;
   }
-  if (n_edges || mcall || joint) {
-    // the edges, once per call (the marginal kernels and the joint step read the header of an empty list); the slots behind the last keep a valid pair, which nothing reads
-    auto * we = reinterpret_cast<mh::WindowEdges *>(h + kWinStageEdgeAt);
-    std::memset(static_cast<void *>(we), 0, sizeof(*we));
-    we->n = static_cast<int>(n_edges);
-    for (size_t e = 0; e < n_edges; ++e) {
-      we->a[e] = edges[e].pose_a;
-      we->b[e] = edges[e].pose_b;
-      std::memcpy(we->ZR[e], edges[e].Z_R, sizeof(we->ZR[e]));
-      std::memcpy(we->Zt[e], edges[e].Z_t, sizeof(we->Zt[e]));
-      std::memcpy(we->Om[e], edges[e].info, sizeof(we->Om[e]));
-    }
-    MH_HIP(ctx, hipMemcpyAsync(d + kWinEdgeAt, we, sizeof(mh::WindowEdges), hipMemcpyHostToDevice, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(static_cast<char *>(ctx->d_window) + kWinLinAt, wl, sizeof(mh::WindowLinear), hipMemcpyHostToDevice, ctx->stream));
+  return MH_OK;
+}
+
+// the edges, once per call; the slots behind the last keep a valid pair, which nothing reads
+static int stage_edges(mh_ctx * ctx, const mh_window_edge * edges, size_t n_edges)
+{
+  auto * we = reinterpret_cast<mh::WindowEdges *>(static_cast<char *>(ctx->h_window) + kWinStageEdgeAt);
+  std::memset(static_cast<void *>(we), 0, sizeof(*we));
+  we->n = static_cast<int>(n_edges);
+  for (size_t e = 0; e < n_edges; ++e) {
+    we->a[e] = edges[e].pose_a;
+    we->b[e] = edges[e].pose_b;
+    std::memcpy(we->ZR[e], edges[e].Z_R, sizeof(we->ZR[e]));
+    std::memcpy(we->Zt[e], edges[e].Z_t, sizeof(we->Zt[e]));
+    std::memcpy(we->Om[e], edges[e].info, sizeof(we->Om[e]));
   }
-  if (joint) {
-    // the joint factor, once per call: the members in use, everything behind them zero
-    auto * wj = reinterpret_cast<mh::WindowJoint *>(h + kWinStageJointAt);
-    std::memset(static_cast<void *>(wj), 0, sizeof(*wj));
-    const int n = joint->n_poses;
-    wj->n = n;
-    for (int m = 0; m < n; ++m) {
-      wj->pose[m] = joint->pose[m];
-      std::memcpy(wj->LR[m], joint->L_R + 9 * m, sizeof(wj->LR[m]));
-      std::memcpy(wj->Lt[m], joint->L_t + 3 * m, sizeof(wj->Lt[m]));
-    }
-    for (int r = 0; r < 6 * n; ++r) {
-      std::memcpy(wj->H + mh::kWindowJointDim * r, joint->H + 24 * r, sizeof(double) * 6 * n);
-      wj->b[r] = joint->b[r];
-    }
-    wj->f = joint->f;
-    MH_HIP(ctx, hipMemcpyAsync(d + kWinJointAt, wj, sizeof(mh::WindowJoint), hipMemcpyHostToDevice, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(static_cast<char *>(ctx->d_window) + kWinEdgeAt, we, sizeof(mh::WindowEdges), hipMemcpyHostToDevice, ctx->stream));
+  return MH_OK;
+}
+
+// the joint factor, once per call: the members in use, everything behind them zero
+static int stage_joint(mh_ctx * ctx, const mh_window_joint_factor & joint)
+{
+  auto * wj = reinterpret_cast<mh::WindowJoint *>(static_cast<char *>(ctx->h_window) + kWinStageJointAt);
+  std::memset(static_cast<void *>(wj), 0, sizeof(*wj));
+  const int n = joint.n_poses;
+  wj->n = n;
+  for (int m = 0; m < n; ++m) {
+    wj->pose[m] = joint.pose[m];
+    std::memcpy(wj->LR[m], joint.L_R + 9 * m, sizeof(wj->LR[m]));
+    std::memcpy(wj->Lt[m], joint.L_t + 3 * m, sizeof(wj->Lt[m]));
   }
+  for (int r = 0; r < 6 * n; ++r) {
+    std::memcpy(wj->H + mh::kWindowJointDim * r, joint.H + 24 * r, sizeof(double) * 6 * n);
+    wj->b[r] = joint.b[r];
+  }
+  wj->f = joint.f;
+  MH_HIP(ctx, hipMemcpyAsync(static_cast<char *>(ctx->d_window) + kWinJointAt, wj, sizeof(mh::WindowJoint), hipMemcpyHostToDevice, ctx->stream));
+  return MH_OK;
+}
+
+// Everything the chain reads, staged in pinned memory and sent: the first part in one copy, then each payload in its own.  A
+// failure (of chain_k3_block half way, of a copy) returns with nothing marked in flight.
+static int window_stage(mh_ctx * ctx, const WindowRequest & q, const WindowChecked & k)
+{
+  MH_HIP(ctx, mh_enter(ctx));
+  int rc = window_alloc(ctx);
+  if (rc != MH_OK) return rc;
+  WindowCall & c = ctx->window;
+  for (int i = 0; i < 3; ++i) c.gz[i] = -q.g_unit[i];
+  for (int it = 0; it < c.iters; ++it) c.seq[it] = mhi::next_call_seq();
+  if ((rc = window_stage_blocks(ctx, q, k.zmask)) != MH_OK) return rc;
+  window_fill_params(c.p, q, k.zmask, c.gz);
+  MH_HIP(ctx, hipMemcpyAsync(ctx->d_window, ctx->h_window, kWinBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(c.iters),
+                             hipMemcpyHostToDevice, ctx->stream));
+  if (q.lin_call && (rc = stage_linear(ctx, q.lin, q.n_lin)) != MH_OK) return rc;
+  // (the marginal kernels and the joint step read the header of an empty list of edges)
+  if ((q.n_edges || q.kind != WindowKind::optimise || q.joint) && (rc = stage_edges(ctx, q.edges, q.n_edges)) != MH_OK) return rc;
+  if (q.joint && (rc = stage_joint(ctx, *q.joint)) != MH_OK) return rc;
+  return MH_OK;
+}
+
+// The call is in flight: what its enqueue and its collectors need of the request, and the factors' books.
+static void window_claim(mh_ctx * ctx, const WindowRequest & q, const WindowChecked & k)
+{
+  WindowCall & c = ctx->window;
+  c.kind = q.kind;
+  c.outputs = q.outputs;
+  c.has_joint = q.joint != nullptr;
+  c.relin = q.relin != nullptr;
+  c.relin_rot = q.relin ? q.relin->relin_rot : 0.0;
+  c.relin_trans = q.relin ? q.relin->relin_trans : 0.0;
+  c.lin = q.lin_call;
+  c.edges = q.n_edges > 0;
+  if (q.kind != WindowKind::optimise) {
+    std::memcpy(c.L1R, q.R + 9, sizeof(c.L1R));
+    std::memcpy(c.L1t, q.t + 3, sizeof(c.L1t));
+  }
+  c.n_sep = k.n_sep;
+  for (int s = 0; s < MH_WINDOW_JOINT_POSES; ++s) {
+    c.sep[s] = k.sep[s];
+    if (s < k.n_sep) {  // (W >= 2 and every separator pose inside the window: the edges' and the joint factor's checks)
+      std::memcpy(c.LSR[s], q.R + 9 * k.sep[s], sizeof(c.LSR[s]));
+      std::memcpy(c.LSt[s], q.t + 3 * k.sep[s], sizeof(c.LSt[s]));
+    }
+  }
+  c.queued = 0;
   c.active = true;
-  for (size_t f = 0; f < W; ++f) {
-    icps[f]->in_window = true;
-    icps[f]->n_pending = kMaxPending;  // the chain holds the whole ring
+  for (size_t f = 0; f < q.W; ++f) {
+    q.icps[f]->in_window = true;
+    q.icps[f]->n_pending = kMaxPending;  // the chain holds the whole ring
   }
+}
+
+static int window_begin(const WindowRequest & q)
+{
+  WindowChecked k;
+  if (const Refusal no = window_check_request(q, k, [&q] { return window_check_factors(q); })) return fail(window_ctx(q.icps, q.W), no.code, no.message);
+  mh_ctx * ctx = q.icps[0]->ctx;
+  window_plan(ctx->window, q);
+  const int rc = window_stage(ctx, q, k);
+  if (rc != MH_OK) return rc;
+  window_claim(ctx, q, k);
   return MH_OK;
 }
 
@@ -900,16 +872,19 @@ static int window_enqueue(mh_ctx * ctx, int upto)
   char * d = static_cast<char *>(ctx->d_window);
   auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + kWinBlocksAt);
   const int * prefix = reinterpret_cast<const int *>(d);
+  // the step kernel of the call.  The argument structs nest in this order (window_device.hpp), each kernel taking the one of
+  // its name with everything inside it: joint { edge { lin { relin { plain } } } }
+  enum class Step { plain, relin, lin, edge, joint };
+  const Step step = !(c.relin || c.lin) ? Step::plain : c.has_joint ? Step::joint : c.edges ? Step::edge : c.lin ? Step::lin : Step::relin;
   for (int it = c.queued; it < upto; ++it) {
-    hipError_t e = hipSuccess;
-    for (size_t gi = 0; gi < c.launches.size() && e == hipSuccess; ++gi) {
-      const WindowLaunch & wl = c.launches[gi];
-      e = mh::launch_linearize_batch(blocks + static_cast<size_t>(it) * c.n_slots + wl.first, prefix + wl.first + static_cast<int>(gi), wl.n, wl.grid, wl.tpb, wl.k,
-                                     wl.n_off, false, ctx->stream);
-    }
+    hipError_t e = chain_launch_k3(c.launches, blocks + static_cast<size_t>(it) * c.n_slots, prefix, ctx->stream);
     if (e == hipSuccess) {
-      mh::WindowStepArgs s;
-      std::memset(static_cast<void *>(&s), 0, sizeof(s));
+      mh::WindowJointStepArgs ja;
+      std::memset(static_cast<void *>(&ja), 0, sizeof(ja));
+      mh::WindowEdgeStepArgs & ea = ja.e;
+      mh::WindowLinStepArgs & la = ea.l;
+      mh::WindowRelinStepArgs & ra = la.r;
+      mh::WindowStepArgs & s = ra.s;
       s.ll_dev = reinterpret_cast<const uint4 *>(d + kWinLlAt);
       for (int i = 0; i < c.W; ++i) {
         s.ll_host[i] = c.icps[i]->n ? c.icps[i]->d_h_ll + static_cast<size_t>(it) * c.icps[i]->ll_words : nullptr;
@@ -920,37 +895,22 @@ static int window_enqueue(mh_ctx * ctx, int upto)
       s.state = reinterpret_cast<mh::WindowState *>(d + kWinStateAt);
       s.p = c.p;
       s.seq = c.seq[it];
-      if (c.relin || c.lin) {
-        mh::WindowLinStepArgs la;
-        std::memset(static_cast<void *>(&la), 0, sizeof(la));
-        mh::WindowRelinStepArgs & ra = la.r;
-        ra.s = s;
-        if (c.relin) {
-          ra.relin = reinterpret_cast<mh::WindowRelin *>(d + kWinRelinAt);
-          ra.mask_host = s.row_host + kWinMaskWord;
-          ra.rp.relin_rot = c.relin_rot;
-          ra.rp.relin_trans = c.relin_trans;
-          ra.rp.first = it == 0 ? 1 : 0;
-        }
-        la.lin = reinterpret_cast<const mh::WindowLinear *>(d + kWinLinAt);
-        if (c.joint) {
-          mh::WindowJointStepArgs ja;
-          std::memset(static_cast<void *>(&ja), 0, sizeof(ja));
-          ja.e.l = la;
-          ja.e.edges = reinterpret_cast<const mh::WindowEdges *>(d + kWinEdgeAt);
-          ja.joint = reinterpret_cast<const mh::WindowJoint *>(d + kWinJointAt);
-          e = mh::launch_window_joint_step(ja, c.relin, ctx->stream);
-        } else if (c.edges) {
-          mh::WindowEdgeStepArgs ea;
-          std::memset(static_cast<void *>(&ea), 0, sizeof(ea));
-          ea.l = la;
-          ea.edges = reinterpret_cast<const mh::WindowEdges *>(d + kWinEdgeAt);
-          e = mh::launch_window_edge_step(ea, c.relin, ctx->stream);
-        } else {
-          e = c.lin ? mh::launch_window_lin_step(la, c.relin, ctx->stream) : mh::launch_window_relin_step(ra, ctx->stream);
-        }
-      } else {
-        e = mh::launch_window_step(s, ctx->stream);
+      if (c.relin) {
+        ra.relin = reinterpret_cast<mh::WindowRelin *>(d + kWinRelinAt);
+        ra.mask_host = s.row_host + kWinMaskWord;
+        ra.rp.relin_rot = c.relin_rot;
+        ra.rp.relin_trans = c.relin_trans;
+        ra.rp.first = it == 0 ? 1 : 0;
+      }
+      la.lin = reinterpret_cast<const mh::WindowLinear *>(d + kWinLinAt);
+      ea.edges = reinterpret_cast<const mh::WindowEdges *>(d + kWinEdgeAt);
+      ja.joint = reinterpret_cast<const mh::WindowJoint *>(d + kWinJointAt);
+      switch (step) {
+        case Step::plain: e = mh::launch_window_step(s, ctx->stream); break;
+        case Step::relin: e = mh::launch_window_relin_step(ra, ctx->stream); break;
+        case Step::lin: e = mh::launch_window_lin_step(la, c.relin, ctx->stream); break;
+        case Step::edge: e = mh::launch_window_edge_step(ea, c.relin, ctx->stream); break;
+        case Step::joint: e = mh::launch_window_joint_step(ja, c.relin, ctx->stream); break;
       }
     }
     if (e != hipSuccess) {
@@ -966,7 +926,7 @@ static int window_enqueue(mh_ctx * ctx, int upto)
 static int window_finish(mh_ctx * ctx)
 {
   WindowCall & c = ctx->window;
-  mh_icp_window_result * out = c.out;
+  mh_icp_window_result * out = c.outputs.out;
   std::memset(static_cast<void *>(out), 0, sizeof(*out));
   const int W = c.W, words = mh::window_row_words(W);
   std::vector<double> rows(static_cast<size_t>(c.queued) * words);
@@ -981,7 +941,7 @@ static int window_finish(mh_ctx * ctx)
     tr.flags = static_cast<int32_t>(row[mh::kWRowBits]) & mh::kAlignSingular;
     tr.degenerate = static_cast<uint32_t>(row[mh::kWRowDegen]);
     lost = lost || (static_cast<int>(row[mh::kWRowBits]) & 8);
-    if (c.trace_poses) std::memcpy(c.trace_poses + static_cast<size_t>(it) * W * 12, row + mh::kWRowPose, sizeof(double) * 12 * W);
+    if (c.outputs.trace_poses) std::memcpy(c.outputs.trace_poses + static_cast<size_t>(it) * W * 12, row + mh::kWRowPose, sizeof(double) * 12 * W);
   }, iters, converged);
   if (rc != MH_OK || iters == 0) {
     window_abandon(ctx);
@@ -1010,7 +970,7 @@ static int window_finish(mh_ctx * ctx)
       break;
     }
     masks[it] = static_cast<uint32_t>(m);
-    if (c.evaluated_mask) c.evaluated_mask[it] = masks[it];
+    if (c.outputs.evaluated_mask) c.outputs.evaluated_mask[it] = masks[it];
   }
   int last_it[mh::kWindowMax], n_eval[mh::kWindowMax];
   for (int i = 0; i < W; ++i) {
@@ -1053,12 +1013,7 @@ static int marginal_enqueue(mh_ctx * ctx)
 {
   WindowCall & c = ctx->window;
   char * d = static_cast<char *>(ctx->d_window);
-  hipError_t e = hipSuccess;
-  for (size_t gi = 0; gi < c.launches.size() && e == hipSuccess; ++gi) {
-    const WindowLaunch & wl = c.launches[gi];
-    e = mh::launch_linearize_batch(reinterpret_cast<mh::IcpArgs *>(d + kWinBlocksAt) + wl.first, reinterpret_cast<const int *>(d) + wl.first + static_cast<int>(gi), wl.n,
-                                   wl.grid, wl.tpb, wl.k, wl.n_off, false, ctx->stream);
-  }
+  hipError_t e = chain_launch_k3(c.launches, reinterpret_cast<mh::IcpArgs *>(d + kWinBlocksAt), reinterpret_cast<const int *>(d), ctx->stream);
   if (e == hipSuccess) {
     mh::WindowMarginalArgs a;
     std::memset(static_cast<void *>(&a), 0, sizeof(a));
@@ -1070,11 +1025,11 @@ static int marginal_enqueue(mh_ctx * ctx)
     a.edges = reinterpret_cast<const mh::WindowEdges *>(d + kWinEdgeAt);
     a.p = c.p;
     a.seq = c.seq[0];
-    if (c.jmarginal) {
+    if (c.kind == WindowKind::marginal_joint) {
       mh::WindowMarginalJointArgs ja;
       std::memset(static_cast<void *>(&ja), 0, sizeof(ja));
       ja.m = a;
-      ja.joint = c.jm_joint ? reinterpret_cast<const mh::WindowJoint *>(d + kWinJointAt) : nullptr;
+      ja.joint = c.has_joint ? reinterpret_cast<const mh::WindowJoint *>(d + kWinJointAt) : nullptr;
       ja.n_sep = c.n_sep;
       for (int k = 0; k < MH_WINDOW_JOINT_POSES; ++k) ja.sep[k] = c.sep[k];
       e = mh::launch_window_marginal_joint(ja, ctx->stream);
@@ -1123,7 +1078,7 @@ static int marginal_collect(mh_ctx * ctx, int words, int bits_word, const char *
 static int marginal_joint_finish(mh_ctx * ctx)
 {
   WindowCall & c = ctx->window;
-  mh_window_joint_marginal * out = c.jmout;
+  mh_window_joint_marginal * out = c.outputs.jmarg;
   return marginal_collect(ctx, mh::kWJMargWords, mh::kWJMargBits, "mh_icp_window_marginalise_joint", out, sizeof(*out), &out->oldest, [&](const double * row) {
     out->prior.n_poses = c.n_sep;  // the separator and its poses are reported whether or not A00 had a positive pivot
     for (int k = 0; k < c.n_sep; ++k) {
@@ -1144,8 +1099,8 @@ static int marginal_finish(mh_ctx * ctx)
 {
   static_assert(mh::kWMargWords <= static_cast<int>(kWinRowWords) && mh::kWMargH + 36 == mh::kWMargWords, "mh_icp_window_marginalise layout");
   WindowCall & c = ctx->window;
-  if (c.jmarginal) return marginal_joint_finish(ctx);
-  mh_window_marginal * out = c.mout;
+  if (c.kind == WindowKind::marginal_joint) return marginal_joint_finish(ctx);
+  mh_window_marginal * out = c.outputs.marg;
   return marginal_collect(ctx, mh::kWMargWords, mh::kWMargBits, "mh_icp_window_marginalise", out, sizeof(*out), &out->oldest, [&](const double * row) {
     out->prior.pose = 1;
     std::memcpy(out->prior.L_R, c.L1R, sizeof(c.L1R));
@@ -1163,36 +1118,27 @@ static int mh_icp_window_wait_impl(mh_ctx * ctx)
   if (!ctx) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_window_wait: ctx is NULL");
   if (!ctx->window.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_window_wait: no window call in flight");
   MH_HIP(ctx, mh_enter(ctx));
-  if (ctx->window.marginal) return marginal_finish(ctx);
+  if (ctx->window.kind != WindowKind::optimise) return marginal_finish(ctx);
   return window_run(ctx, 0);
 }
 
-static int mh_icp_window_marginalise_impl(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                                          const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
-                                          size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out, bool blocking,
-                                          bool jmcall = false, const mh_window_joint_factor * joint = nullptr, mh_window_joint_marginal * jout = nullptr)
+static int mh_icp_window_marginalise_impl(const WindowRequest & q)
 {
-  int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, nullptr, nullptr, nullptr, nullptr, true, lin, n_lin, edges, n_edges, true, out, joint, jout,
-                        jmcall);
+  int rc = window_begin(q);
   if (rc != MH_OK) return rc;
-  rc = marginal_enqueue(icps[0]->ctx);
-  if (rc != MH_OK || !blocking) return rc;
-  return marginal_finish(icps[0]->ctx);
+  mh_ctx * ctx = q.icps[0]->ctx;
+  rc = marginal_enqueue(ctx);
+  if (rc != MH_OK || !q.blocking) return rc;
+  return marginal_finish(ctx);
 }
 
-// relin_call: through mh_icp_window_optimise_relin[_async], whose thresholds are not optional
-static int mh_icp_window_optimise_impl(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
-                                       const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out,
-                                       double * trace_poses, bool blocking, bool relin_call, const mh_icp_window_relin * relin, uint32_t * evaluated_mask,
-                                       bool lin_call = false, const mh_window_linear_factor * lin = nullptr, size_t n_lin = 0,
-                                       const mh_window_edge * edges = nullptr, size_t n_edges = 0, const mh_window_joint_factor * joint = nullptr)
+static int mh_icp_window_optimise_impl(const WindowRequest & q)
 {
-  if (relin_call && !relin) return fail(window_ctx(icps, W), MH_ERR_INVALID_ARG, "mh_icp_window_optimise_relin: NULL argument");
-  const int rc = window_begin(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, relin, evaluated_mask, lin_call, lin, n_lin, edges, n_edges, false,
-                              nullptr, joint);
+  const int rc = window_begin(q);
   if (rc != MH_OK) return rc;
-  if (!blocking) return window_enqueue(icps[0]->ctx, cfg->iters);
-  return window_run(icps[0]->ctx, cfg->check_every > 0 ? cfg->check_every : cfg->iters);
+  mh_ctx * ctx = q.icps[0]->ctx;
+  if (!q.blocking) return window_enqueue(ctx, q.cfg->iters);
+  return window_run(ctx, q.cfg->check_every > 0 ? q.cfg->check_every : q.cfg->iters);
 }
 
 extern "C" {
@@ -1222,50 +1168,57 @@ int mh_icp_align_batch_wait(mh_ctx * ctx)
   return guarded(ctx, "mh_icp_align_batch_wait", [&]() -> int { return mh_icp_align_batch_wait_impl(ctx); });
 }
 
+// The window family: every entry point writes down what it was given (window_request.hpp) and hands that on.
 int mh_icp_window_optimise(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                            const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise",
-                 [&]() -> int { return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, false, nullptr, nullptr); });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = true, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .outputs = {.out = out, .trace_poses = trace_poses}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_optimise_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                  const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, mh_icp_window_result * out, double * trace_poses)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_async",
-                 [&]() -> int { return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, nullptr, nullptr); });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = false, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .outputs = {.out = out, .trace_poses = trace_poses}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_async", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_optimise_relin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                  const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
                                  mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_relin", [&]() -> int {
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, true, relin, evaluated_mask);
-  });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = true, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .relin = relin, .relin_required = true,
+                        .outputs = {.out = out, .trace_poses = trace_poses, .evaluated_mask = evaluated_mask}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_relin", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_optimise_relin_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
                                        mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_relin_async", [&]() -> int {
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, true, relin, evaluated_mask);
-  });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = false, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .relin = relin, .relin_required = true,
+                        .outputs = {.out = out, .trace_poses = trace_poses, .evaluated_mask = evaluated_mask}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_relin_async", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_optimise_lin(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
                                const mh_window_linear_factor * lin, size_t n_lin, mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_lin", [&]() -> int {
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, false, relin, evaluated_mask, true, lin, n_lin);
-  });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = true, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .relin = relin, .lin_call = true, .lin = lin, .n_lin = n_lin,
+                        .outputs = {.out = out, .trace_poses = trace_poses, .evaluated_mask = evaluated_mask}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_lin", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_optimise_lin_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                      const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
                                      const mh_window_linear_factor * lin, size_t n_lin, mh_icp_window_result * out, double * trace_poses,
                                      uint32_t * evaluated_mask)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_lin_async", [&]() -> int {
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, relin, evaluated_mask, true, lin, n_lin);
-  });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = false, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .relin = relin, .lin_call = true, .lin = lin, .n_lin = n_lin,
+                        .outputs = {.out = out, .trace_poses = trace_poses, .evaluated_mask = evaluated_mask}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_lin_async", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 // n_edges == 0: the lin call's own step kernels
 int mh_icp_window_optimise_edges(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
@@ -1273,36 +1226,36 @@ int mh_icp_window_optimise_edges(mh_icp * const * icps, size_t W, const double *
                                  const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_icp_window_result * out,
                                  double * trace_poses, uint32_t * evaluated_mask)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_edges", [&]() -> int {
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, false, relin, evaluated_mask, true, lin, n_lin, edges,
-                                       n_edges);
-  });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = true, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .relin = relin, .lin_call = true, .lin = lin, .n_lin = n_lin, .edges = edges, .n_edges = n_edges,
+                        .outputs = {.out = out, .trace_poses = trace_poses, .evaluated_mask = evaluated_mask}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_edges", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_optimise_edges_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
                                        const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges,
                                        mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_edges_async", [&]() -> int {
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, relin, evaluated_mask, true, lin, n_lin, edges,
-                                       n_edges);
-  });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = false, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .relin = relin, .lin_call = true, .lin = lin, .n_lin = n_lin, .edges = edges, .n_edges = n_edges,
+                        .outputs = {.out = out, .trace_poses = trace_poses, .evaluated_mask = evaluated_mask}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_edges_async", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_marginalise(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                               const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin, size_t n_lin,
                               const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise", [&]() -> int {
-    return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, out, true);
-  });
+  const WindowRequest q{.kind = WindowKind::marginal, .blocking = true, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .lin_call = true, .lin = lin, .n_lin = n_lin, .edges = edges, .n_edges = n_edges, .outputs = {.marg = out}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise", [&]() -> int { return mh_icp_window_marginalise_impl(q); });
 }
 int mh_icp_window_marginalise_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                     const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
                                     size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_window_marginal * out)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_async", [&]() -> int {
-    return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, out, false);
-  });
+  const WindowRequest q{.kind = WindowKind::marginal, .blocking = false, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .lin_call = true, .lin = lin, .n_lin = n_lin, .edges = edges, .n_edges = n_edges, .outputs = {.marg = out}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_async", [&]() -> int { return mh_icp_window_marginalise_impl(q); });
 }
 // joint == NULL: mh_icp_window_optimise_edges, its kernels
 int mh_icp_window_optimise_joint(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
@@ -1310,38 +1263,40 @@ int mh_icp_window_optimise_joint(mh_icp * const * icps, size_t W, const double *
                                  const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges, mh_icp_window_result * out,
                                  double * trace_poses, uint32_t * evaluated_mask, const mh_window_joint_factor * joint)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_joint", [&]() -> int {
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, true, false, relin, evaluated_mask, true, lin, n_lin, edges,
-                                       n_edges, joint);
-  });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = true, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .relin = relin, .lin_call = true, .lin = lin, .n_lin = n_lin, .edges = edges, .n_edges = n_edges,
+                        .joint = joint, .outputs = {.out = out, .trace_poses = trace_poses, .evaluated_mask = evaluated_mask}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_joint", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_optimise_joint_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                        const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_icp_window_relin * relin,
                                        const mh_window_linear_factor * lin, size_t n_lin, const mh_window_edge * edges, size_t n_edges,
                                        mh_icp_window_result * out, double * trace_poses, uint32_t * evaluated_mask, const mh_window_joint_factor * joint)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_joint_async", [&]() -> int {
-    return mh_icp_window_optimise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, out, trace_poses, false, false, relin, evaluated_mask, true, lin, n_lin, edges,
-                                       n_edges, joint);
-  });
+  const WindowRequest q{.kind = WindowKind::optimise, .blocking = false, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .relin = relin, .lin_call = true, .lin = lin, .n_lin = n_lin, .edges = edges, .n_edges = n_edges,
+                        .joint = joint, .outputs = {.out = out, .trace_poses = trace_poses, .evaluated_mask = evaluated_mask}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_optimise_joint_async", [&]() -> int { return mh_icp_window_optimise_impl(q); });
 }
 int mh_icp_window_marginalise_joint(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                     const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
                                     size_t n_lin, const mh_window_edge * edges, size_t n_edges, const mh_window_joint_factor * joint,
                                     mh_window_joint_marginal * out)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_joint", [&]() -> int {
-    return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, nullptr, true, true, joint, out);
-  });
+  const WindowRequest q{.kind = WindowKind::marginal_joint, .blocking = true, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .lin_call = true, .lin = lin, .n_lin = n_lin, .edges = edges, .n_edges = n_edges, .joint = joint,
+                        .outputs = {.jmarg = out}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_joint", [&]() -> int { return mh_icp_window_marginalise_impl(q); });
 }
 int mh_icp_window_marginalise_joint_async(mh_icp * const * icps, size_t W, const double * R, const double * t, const int32_t * has_Z, const double * Z_R,
                                           const double * Z_t, const double g_unit[3], const mh_icp_window_config * cfg, const mh_window_linear_factor * lin,
                                           size_t n_lin, const mh_window_edge * edges, size_t n_edges, const mh_window_joint_factor * joint,
                                           mh_window_joint_marginal * out)
 {
-  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_joint_async", [&]() -> int {
-    return mh_icp_window_marginalise_impl(icps, W, R, t, has_Z, Z_R, Z_t, g_unit, cfg, lin, n_lin, edges, n_edges, nullptr, false, true, joint, out);
-  });
+  const WindowRequest q{.kind = WindowKind::marginal_joint, .blocking = false, .icps = icps, .W = W, .R = R, .t = t, .has_Z = has_Z, .Z_R = Z_R, .Z_t = Z_t,
+                        .g_unit = g_unit, .cfg = cfg, .lin_call = true, .lin = lin, .n_lin = n_lin, .edges = edges, .n_edges = n_edges, .joint = joint,
+                        .outputs = {.jmarg = out}};
+  return guarded(window_ctx(icps, W), "mh_icp_window_marginalise_joint_async", [&]() -> int { return mh_icp_window_marginalise_impl(q); });
 }
 int mh_icp_window_wait(mh_ctx * ctx)
 {

@@ -27,6 +27,7 @@
 #include "map_device.hpp"
 #include "scan_device.hpp"
 #include "shard_device.hpp"
+#include "window_request.hpp"
 
 inline thread_local std::string g_mh_err;
 constexpr int kMaxPending = 64;
@@ -51,21 +52,18 @@ struct WindowCall
   unsigned int seq[64];
   mh::WindowParams p;
   std::vector<WindowLaunch> launches;
-  mh_icp_window_result * out = nullptr;
-  double * trace_poses = nullptr;
+  // optimise: iterations of K3 and a step kernel, the result to outputs.out; marginal / marginal_joint: one K3 launch of icps[0]
+  // and the (joint) marginal kernel, the result to outputs.marg / outputs.jmarg
+  WindowKind kind = WindowKind::optimise;
+  WindowOutputs outputs;
+  bool has_joint = false;  // the call carries a joint factor (optimise: the joint step kernel; marginal_joint: absorbed)
+  // the features of an optimise call, which choose its step kernel (window_enqueue)
   bool relin = false;  // mh_icp_window_optimise_relin: the step kernel chooses per factor and iteration whether K3 runs
   double relin_rot = 0.0, relin_trans = 0.0;
-  uint32_t * evaluated_mask = nullptr;
   bool lin = false;    // mh_icp_window_optimise_lin: the step kernel also carries the call's linear factors
   bool edges = false;  // mh_icp_window_optimise_edges with n_edges > 0: ... and the call's edges, solved over the row profile
-  bool marginal = false;  // mh_icp_window_marginalise: one K3 launch of icps[0] and the marginal kernel; the result goes to mout
-  mh_window_marginal * mout = nullptr;
-  double L1R[9], L1t[3];  // ... pose 1 as the caller gave it
-  bool joint = false;     // mh_icp_window_optimise_joint with a joint factor: the joint step kernel
-  bool jmarginal = false; // mh_icp_window_marginalise_joint (marginal is set as well): the joint marginal kernel; the result goes to jmout
-  bool jm_joint = false;  // ... with a joint factor
-  mh_window_joint_marginal * jmout = nullptr;
-  int n_sep = 0, sep[MH_WINDOW_JOINT_POSES];                                   // ... its separator
+  double L1R[9], L1t[3];  // marginal: pose 1 as the caller gave it
+  int n_sep = 0, sep[MH_WINDOW_JOINT_POSES];                                   // marginal_joint: its separator
   double LSR[MH_WINDOW_JOINT_POSES][9], LSt[MH_WINDOW_JOINT_POSES][3];         // ... and those poses as the caller gave them
 };
 

@@ -131,14 +131,8 @@ int pgo_check_edges(const mh_pose_graph * pg, const mh_window_edge * edges, size
     const mh_window_edge & q = edges[e];
     if (q.pose_a < 0 || q.pose_a >= q.pose_b || static_cast<size_t>(q.pose_b) >= pg->n)
       return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: edge " + std::to_string(e) + " needs 0 <= pose_a < pose_b < n");
-    bool finite = true;
-    for (double v : q.Z_R) finite = finite && std::isfinite(v);
-    for (double v : q.Z_t) finite = finite && std::isfinite(v);
-    for (double v : q.info) finite = finite && std::isfinite(v);
-    if (!finite) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: edge " + std::to_string(e) + " has an entry that is not finite");
-    for (int r = 0; r < 6; ++r)
-      for (int c = 0; c < r; ++c)
-        if (q.info[6 * r + c] != q.info[6 * c + r]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: an edge's info is not symmetric");
+    if (!window_edge_finite(q)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: edge " + std::to_string(e) + " has an entry that is not finite");
+    if (!exactly_symmetric(q.info, 6, 6)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: an edge's info is not symmetric");
     if (q.pose_b - q.pose_a >= 2) ++n_far;
   }
   if (n_far > MH_PGO_FAR_MAX) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_pose_graph_set_edges: more than MH_PGO_FAR_MAX edges with pose_b - pose_a >= 2");
