@@ -17,7 +17,8 @@ scan, _ = synth.make_scan(64)
 R, t = synth.query_pose()
 gm = capi.VoxelMap(ctx)
 gm.insert(m)
-keys = ("H_ss", "b_s", "f", "status_hist", "loc_trans_comp", "loc_rot_comp", "n_knn", "mean_candidates", "n_exact_fallback", "H_st", "H_tt", "b_t")
+keys = ("H_ss", "b_s", "f", "status_hist", "loc_trans_comp", "loc_rot_comp", "n_knn", "mean_candidates", "n_exact_fallback", "H_st", "H_tt", "b_t",
+        "loc_trans_final", "loc_rot_final", "eigvec_trans", "eigvec_rot")
 blob = {}
 for ci, (n_pts, binary) in enumerate(cases):
     pts = np.ascontiguousarray(scan[:: max(1, len(scan) // n_pts)][:n_pts])
