@@ -166,8 +166,19 @@ __device__ __forceinline__ double lane_get(double v, int l)
       (ptr)[(static_cast<size_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 16 + (i)] = \
         __builtin_amdgcn_s_memtime();                                                          \
   } while (0)
+// K3's entry stamp (slot 0) also says WHERE the wave runs: the low 16 bits of HW_ID (wave slot [3:0], SIMD [5:4], pipe [7:6], CU
+// [11:8], SH [12], SE [15:13]) in bits 48-63 of the word, the clock in the 48 below (tools/timeline.py masks every stamp to 48 bits
+// and pairs the waves of a SIMD by it).
+#define MH_STAMP_ENTRY(ptr)                                                                                               \
+  do {                                                                                                                    \
+    if ((ptr) && (threadIdx.x & 63) == 0)                                                                                 \
+      (ptr)[(static_cast<size_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 16] =                            \
+        (__builtin_amdgcn_s_memtime() & 0xFFFFFFFFFFFFull) |                                                              \
+        (static_cast<unsigned long long>(__builtin_amdgcn_s_getreg(4 | (15 << 11))) << 48); /* hwreg(HW_REG_HW_ID, 0, 16) */ \
+  } while (0)
 #else
 #define MH_STAMP(ptr, i) do { } while (0)
+#define MH_STAMP_ENTRY(ptr) do { } while (0)
 #endif
 // K4's waves: indexed by the factor's workgroup index
 #ifdef MH_TIMELINE
@@ -485,10 +496,26 @@ struct KnnPoints
   uint32_t member;  // bit u: pt[u] is one of the k nearest
 };
 constexpr int knn_survivors(int K) { return K + 3 + (K > 5 ? 1 : 0); }  // 8 for k = 5, 12 for the generic k <= 8 path
+// Wave priority by the work a wave has left (PRIO: the 512-thread one-lane-per-query class, where every SIMD holds two waves of
+// the workgroup and nothing else).  VALU issue between the two is arbitrated by priority, then by age: at equal priority the
+// wave dispatched first is served and the other gets what is left, whichever has more to do — and the workgroup ends with its
+// slowest wave.  So each wave sets s_setprio 0..3 from an estimate of the instructions it still has to issue, by the same
+// thresholds in every wave: the partner with more left never has the lower level, ties fall back to age.  The estimate is
+// the wave's remaining scan trips (~436 instructions each) on top of a constant tail (exact tier + plane + residual, ~1 700):
+//   level 3   kTrips3 or more trips left          level 1   fewer trips left, and the exact tier (kExact)
+//   level 2   kTrips2 or more trips left          level 0   plane fit and residual (kPlane), everything outside knn_query
+// Priority moves time only: no load, store, operation or summation order depends on it.
+struct K3Prio
+{
+  static constexpr int kTrips2 = 3, kTrips3 = 6;
+  static constexpr int kExact = 1, kPlane = 0;
+  static constexpr uint32_t kQuadsPerVoxel = 2u;  // what a voxel the cursor has not entered yet counts for (<= 5 quads, ~2 on average)
+};
 // QL > 1 (FAST only): QL adjacent lanes call with the SAME query and the same `list` column; `n_scanned` is then the calling
 // lane's own share (the caller sums the lanes), the return value and every result are the same in all lanes of the group, and the
 // exact fallback is run for the group's first lane only (the others' results are the caller's to ignore).
-template <int K, int NOFF, bool FAST = false, int PIPE = MH_PIPE, int QL = 1>
+// PRIO: the wave's priority follows the work it has left (K3Prio above); it is back at K3Prio::kPlane on return.
+template <int K, int NOFF, bool FAST = false, int PIPE = MH_PIPE, int QL = 1, bool PRIO = false>
 __device__ __forceinline__ uint32_t knn_query(const MapView & map, const double q0, const double q1, const double q2,
                                               int k, uint32_t * list, int lds_stride, const uint32_t * scan_lut,
                                               uint32_t (&bi)[K], double & dk, bool & fell_back, uint32_t & n_scanned,
@@ -670,6 +697,16 @@ __device__ __forceinline__ uint32_t knn_query(const MapView & map, const double 
     for (int u = 0; u < kPipe; ++u) stage[u] = cur.advance(list, lds_stride, lut4, map.qbuckets);
     for (int trip = 0;; ++trip) {
       if (!__any(static_cast<int>(stage[0].vcnt))) break;  // a dead stage 0 means dead stages 1..3
+      if constexpr (PRIO) {
+        // trips this lane has left: the one in flight + the quads still in the cursor (the rest of its voxel, kQuadsPerVoxel for
+        // every voxel not entered; the re-pruning below can only take some away), kPipe to a trip.  The wave has as many as its
+        // longest lane; lanes outside the call are not active here and count for nothing.
+        const uint32_t left = static_cast<uint32_t>(max(static_cast<int>(cur.nq_cur) - static_cast<int>(cur.qd), 0)) +
+                              K3Prio::kQuadsPerVoxel * static_cast<uint32_t>(__popc(cur.rem));
+        static_assert(K3Prio::kTrips2 >= 2 && K3Prio::kTrips3 >= K3Prio::kTrips2, "1 + ceil(left / kPipe) >= T  <=>  left > (T - 2) kPipe");
+        wave_setprio(1 + (__any(static_cast<int>(left > static_cast<uint32_t>((K3Prio::kTrips2 - 2) * kPipe))) ? 1 : 0) +
+                     (__any(static_cast<int>(left > static_cast<uint32_t>((K3Prio::kTrips3 - 2) * kPipe))) ? 1 : 0));
+      }
       if (MH_PRUNE_TRIPS) {
         if constexpr (QL > 1) {
           // the tightest k-th key any lane of the group has proven (each is an upper bound of the answer's k-th distance).
@@ -704,6 +741,7 @@ __device__ __forceinline__ uint32_t knn_query(const MapView & map, const double 
   // centre + every neighbour voxel the cursor entered
   const uint32_t scanned_mask = (amask & 1u) | (alive & ~rem);
   MH_STAMP(dbg, 2);
+  if constexpr (PRIO) __builtin_amdgcn_s_setprio(K3Prio::kExact);
 
   // ---- exact tier: re-rank the survivors in fp64 by (distance, traversal rank) -------------------
   double bd[K];
@@ -812,6 +850,7 @@ __device__ __forceinline__ uint32_t knn_query(const MapView & map, const double 
     }
   }
   MH_STAMP(dbg, 12);
+  if constexpr (PRIO) __builtin_amdgcn_s_setprio(K3Prio::kPlane);
   dk = kDblMax;
 #pragma unroll
   for (int i = 0; i < K; ++i)
@@ -1235,6 +1274,8 @@ __device__ __forceinline__ void icp_linearize_body(const IcpArgs & a, const int 
 {
   static_assert(QL == 1 || (!SHARD && K == 5), "several lanes per query: plain k = 5 factors only");
   constexpr int PPW = TPB / QL;  // points per workgroup
+  // the plain 512-thread class: two waves of the workgroup on every SIMD, their priority follows the work they have left (K3Prio)
+  constexpr bool kPrio = QL == 1 && TPB == 512 && !SHARD;
   [[maybe_unused]] const bool lead = QL == 1 || (threadIdx.x & static_cast<unsigned int>(QL - 1)) == 0u;
   constexpr int NV = BINARY ? 13 : 7;           // row vector v = [J_s(6) (, J_t(6)), e]
   constexpr int NENT = NV * (NV + 1) / 2;       // upper triangle of v v^T: 28 / 91 sums
@@ -1305,7 +1346,7 @@ __device__ __forceinline__ void icp_linearize_body(const IcpArgs & a, const int 
     __syncthreads();
   }
 #endif
-  MH_STAMP(a.dbg, 0);
+  MH_STAMP_ENTRY(a.dbg);
 #pragma unroll
   for (int j = 0; j < NV; ++j) row[j] = 0.0;
 
@@ -1366,7 +1407,7 @@ __device__ __forceinline__ void icp_linearize_body(const IcpArgs & a, const int 
       // quads in flight per lane: the 256-thread class (clouds of up to 65 536 points: at most one wave per SIMD, the scan waits
       // on memory, registers are plentiful) runs a deeper pipeline than the 512-thread class (two waves per SIMD: VALU-bound)
       constexpr int kPipeK3 = TPB <= 256 ? MH_PIPE_SMALL : MH_PIPE;
-      const uint32_t n_cand = knn_query<K, NOFF, kFast, kPipeK3, QL>(a.map, q0, q1, q2, k, s_list, PPW, s_scan, bi, dk, fell_back, n_scanned, a.dbg,
+      const uint32_t n_cand = knn_query<K, NOFF, kFast, kPipeK3, QL, kPrio>(a.map, q0, q1, q2, k, s_list, PPW, s_scan, bi, dk, fell_back, n_scanned, a.dbg,
                                                                             kFast ? &sel : nullptr);
       cnt_pack = (lead ? n_cand : 0u) | (n_scanned << 16);  // each <= 27 x 20 = 540: the 64-lane sums fit 16 bits (several lanes per query: every lane its own share of the scan)
       did_knn = lead;
@@ -1596,6 +1637,7 @@ __device__ __forceinline__ void icp_linearize_body(const IcpArgs & a, const int 
   //    critical path of the workgroup's slowest wave, is a sum of 8 (16) wave partials per entry.  (Rounds 1-4 built one tile per
   //    workgroup behind the barrier: 4.8 k cycles = 2 us after the slowest wave of every workgroup.)
   MH_STAMP(a.dbg, 3);
+  if constexpr (kPrio) __builtin_amdgcn_s_setprio(0);  // the row reduction, the barrier and what follows run as without K3Prio
   {
     constexpr int WSEG = NENT <= 32 ? 2 : 1;          // point segments per wave: lanes 0-31 / 32-63 (unary), all 64 points (binary)
     constexpr int WPTS = 64 / WSEG;

@@ -76,4 +76,16 @@ __device__ __forceinline__ void wave_sum_to_lane63_u32(uint32_t (&v)[N])
   wdpp_step_u32<N, 0x142, 0xA>(v);
   wdpp_step_u32<N, 0x143, 0xC>(v);
 }
+
+// The wave's issue priority, 0..3 (`level` must be the same in every active lane).  s_setprio takes an immediate, so this is a
+// scalar switch over four of them; a scalar instruction ignores EXEC: the wave runs it once, whichever lanes are active.
+__device__ __forceinline__ void wave_setprio(int level)
+{
+  switch (__builtin_amdgcn_readfirstlane(level)) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+  }
+}
 }  // namespace mh

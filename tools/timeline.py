@@ -4,6 +4,9 @@
 Stamps (s_memtime, shader-clock... 100 MHz REFCLK on gfx950 — calibrated below against the HIP-event
 kernel time): 0 entry, 1 neighbourhood list built, 2 candidate scan done, 3 per-point work done,
 4 after the block barrier, 5 partial row stored, 6 last block: won the ticket, 7 last block: done.
+Bits 48-63 of K3's stamp 0 carry the low half of HW_ID (wave slot, SIMD, CU, SH, SE): the SIMD-pair view at the end of K3's
+part pairs the two waves a SIMD holds in the 512-thread class by it.  MH_TL_LIB=<path> loads an already built diagnostic
+library (another commit's, for a before / after pair) instead of building this tree's.
 """
 import ctypes as C
 import os
@@ -15,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from mimosa_amd import build as hb, capi, synth  # noqa: E402
 
-lib = hb.build(timeline=True)  # add -DMH_BALANCE by hand for the lane-balance counters (MH_BALANCE=1 here)
+lib = os.environ.get("MH_TL_LIB") or hb.build(timeline=True)  # add -DMH_BALANCE by hand for the lane-balance counters (MH_BALANCE=1 here)
 capi._build.LIB = lib  # load the diagnostic variant
 ctx = capi.Context(0)
 L = ctx.L
@@ -40,12 +43,16 @@ n = C.c_size_t()
 buf = np.zeros(2 * 8 * 16 * 4096, np.uint64)
 rc = L.mh_icp_timeline(f.h, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n))
 assert rc == 0, rc
-Tall = buf[: n.value].reshape(-1, 16).astype(np.int64)
+Tall = buf[: n.value].reshape(-1, 16)
+HW = (Tall[:, 0] >> np.uint64(48)).astype(np.int64)  # K3's waves: where the wave ran (0 from a library without the stamp)
+Tall = (Tall & np.uint64((1 << 48) - 1)).astype(np.int64)
 T = Tall[: len(Tall) // 2]    # K3's waves
 T4 = Tall[len(Tall) // 2:]    # K4's waves (4 per workgroup), stamps of icp_localizability_body
 blk = np.arange(len(T)) // WPB
+wave_in_blk = np.arange(len(T)) % WPB
+HW = HW[: len(T)]
 live = T[:, 0] > 0
-T, blk = T[live], blk[live]
+T, blk, wave_in_blk, HW = T[live], blk[live], wave_in_blk[live], HW[live]
 k3_us = r["gpu_ms_linearize"] * 1e3
 print(f"points {len(pts)}  waves {len(T)}  K3 by HIP events {k3_us:.1f} us  (ticks = s_memtime; per-XCD counters, so cross-wave times are per XCD)")
 
@@ -103,6 +110,39 @@ work = T[:, 3] - T[:, 0]
 print(f"per-wave work before the barrier (0->3): mean {work.mean():.0f} p50 {np.percentile(work,50):.0f} p95 {np.percentile(work,95):.0f} p99 {np.percentile(work,99):.0f} max {work.max()}")
 bw = np.array([work[blk == b].max() for b in np.unique(blk)])
 print(f"per-block slowest wave: mean {bw.mean():.0f} p95 {np.percentile(bw,95):.0f} max {bw.max()}")
+
+# ---- SIMD pairs (512-thread class: every SIMD holds two waves of one workgroup for the whole kernel).  VALU issue between the two
+# is arbitrated by priority, then by age: who was dispatched first, who had more to do, and when the pair was done.
+if WPB == 8:
+    have_hw = bool(HW.any())
+    simd = (HW >> 4) & 3 if have_hw else wave_in_blk % 4
+    print("SIMD pairs: SIMD from " + ("HW_ID" if have_hw else "the wave index (wave w on SIMD w % 4: this library does not stamp HW_ID)"))
+    key = blk * 4 + simd
+    order = np.argsort(key, kind="stable")
+    ks, cnt = np.unique(key[order], return_counts=True)
+    print(f"  SIMDs holding 1 / 2 / other numbers of live waves: {(cnt == 1).sum()} / {(cnt == 2).sum()} / {((cnt != 1) & (cnt != 2)).sum()}")
+    first = np.cumsum(cnt) - cnt
+    ia, ib = order[first[cnt == 2]], order[first[cnt == 2] + 1]
+    if len(ia):
+        swap = T[ib, 0] < T[ia, 0]  # a = the wave that entered first (the older one)
+        ia, ib = np.where(swap, ib, ia), np.where(swap, ia, ib)
+        by_index = (wave_in_blk[ia] < wave_in_blk[ib]).mean()
+        by_slot = ((HW[ia] & 15) < (HW[ib] & 15)).mean() if have_hw else float("nan")
+        wa, wb = T[ia, 3] - T[ia, 0], T[ib, 3] - T[ib, 0]
+        t0 = np.minimum(T[ia, 0], T[ib, 0])
+        fin = np.maximum(T[ia, 3], T[ib, 3]) - t0
+        print(f"  pairs {len(ia)}: the first-dispatched wave has the lower wave index in {100 * by_index:.1f} %, the lower wave slot in {100 * by_slot:.1f} %; entry gap mean {np.abs(T[ib, 0] - T[ia, 0]).mean():.0f} ticks")
+        stat("  older wave: work (0->3)", wa)
+        stat("  younger wave: work (0->3)", wb)
+        stat("  older wave: scan (11->2)", T[ia, 2] - T[ia, 11])
+        stat("  younger wave: scan (11->2)", T[ib, 2] - T[ib, 11])
+        stat("  pair finish (first entry -> later 3)", fin)
+        heavier_young = T[ib, 3] > T[ia, 3]
+        print(f"  the younger wave finishes its work last in {100 * heavier_young.mean():.1f} % of the pairs; finish gap |3a - 3b| mean {np.abs(T[ia, 3] - T[ib, 3]).mean():.0f} ticks")
+        worst = np.argsort(-fin)[:8]
+        print("  slowest pairs: block simd | older: wave work scan | younger: wave work scan | finish")
+        for i in worst:
+            print(f"    {blk[ia[i]]:4d} {simd[ia[i]]} | {wave_in_blk[ia[i]]} {wa[i]:6d} {T[ia[i], 2] - T[ia[i], 11]:6d} | {wave_in_blk[ib[i]]} {wb[i]:6d} {T[ib[i], 2] - T[ib[i], 11]:6d} | {fin[i]:6d}")
 
 # ---- K4 (icp_localizability_kernel): 0 entry, 1 K3's rows folded, 2 record entries requested, 3 eigenbases (the two lanes that
 # decompose) / nothing, 5 after the barrier (bases known), 6 projections + histogram done,
