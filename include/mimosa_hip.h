@@ -1521,6 +1521,103 @@ int mh_shard_icp_stats(const mh_shard_icp * icp, mh_shard_stats * out);
  *   destroyed. */
 void mh_shard_icp_destroy(mh_shard_icp * icp);
 
+/* ---- keyframe cloud store, and the map rebuilt at corrected poses -------------------------------------------------------
+ * No reference counterpart: the reference never moves a keyframe once it is in the map.  With mh_place_* (find a revisit),
+ * mh_icp_relocalise* (measure it) and mh_pose_graph_* (correct every keyframe pose) a caller has corrected poses and a map whose
+ * points still sit where the drifted poses put them.  The store keeps every keyframe's cloud on the device; the rebuild makes
+ * the map those clouds give at any poses.
+ *
+ * 1. The store holds up to capacity_keyframes clouds (1 .. 65 536) and capacity_points points in total (>= 1), both fixed at
+ *    creation.  An entry is a cloud in its own frame — the body frame for what Geometric::updateMap inserts — and an int64 tag of
+ *    the caller's.  It holds no pose: poses live with the caller or the pose graph, and move.  The clouds are packed float4
+ *    (x, y, z, 1) in one device arena; the offset table is kept on the host and on the device.  A cloud of 0 points is a valid
+ *    entry.  A store belongs to its context and works on that context's stream; after mh_shutdown of the context every call but
+ *    mh_keyframes_destroy refuses it.
+ *    Refusals, each with MH_ERR_INVALID_ARG and the store as it was: a NULL argument; a full store, in keyframes or in points;
+ *    stride_floats < 3; `which` outside 0 .. 1; a scan without that stage or of another context; a NULL cloud with n > 0; an
+ *    index out of range; capacities outside their ranges. */
+typedef struct mh_keyframes mh_keyframes;
+
+typedef struct mh_keyframes_config {
+  int32_t capacity_keyframes; /* 1 .. 65 536 */
+  int32_t reserved;           /* 0 */
+  int64_t capacity_points;    /* >= 1, all entries together */
+} mh_keyframes_config; /* 16 bytes */
+
+typedef struct mh_keyframes_info {
+  int64_t keyframes;
+  int64_t points;
+  int64_t capacity_keyframes;
+  int64_t capacity_points;
+  int64_t device_bytes;       /* the arena and the offset table */
+} mh_keyframes_info; /* 40 bytes */
+
+int mh_keyframes_create(mh_ctx * ctx, const mh_keyframes_config * cfg, mh_keyframes ** out);
+void mh_keyframes_destroy(mh_keyframes * kf);
+/* entries in the store; 0 for NULL or a store whose context was shut down */
+size_t mh_keyframes_size(const mh_keyframes * kf);
+int mh_keyframes_get_info(const mh_keyframes * kf, mh_keyframes_info * out);
+/* Append n host points, `stride_floats` floats apart, under `tag`; *index (may be NULL) receives the entry's index.  Synchronous. */
+int mh_keyframes_add(mh_keyframes * kf, const float * xyz, size_t n, size_t stride_floats, int64_t tag, int32_t * index);
+/* The same for points that are already on the store's device (d_points: device pointer), as mh_map_insert_device takes them. */
+int mh_keyframes_add_device(mh_keyframes * kf, const void * d_points, size_t n, size_t stride_floats, int64_t tag, int32_t * index);
+/* The same straight from a device-resident scan; `which` as in mh_map_carve_from_scan (0: points_full_, 1: Be_cloud_).  Device to
+ * device on the context's stream; waits for nothing. */
+int mh_keyframes_add_from_scan(mh_keyframes * kf, const mh_scan * scan, int which, int64_t tag, int32_t * index);
+/* Read entry `index` back as packed xyz: at most capacity_points points into xyz (NULL: only the count), *n_out = the entry's
+ * size, *tag its tag (either may be NULL). */
+int mh_keyframes_get(mh_keyframes * kf, int32_t index, float * xyz, size_t capacity_points, size_t * n_out, int64_t * tag);
+/* The device address of entry `index`, 4 floats per point — what mh_map_insert_device(..., stride_floats = 4, ...) takes — and its
+ * size.  Valid until the store is destroyed (work enqueued on the store's context sees the entry's points). */
+int mh_keyframes_device_points(mh_keyframes * kf, int32_t index, const float ** d_xyz1, size_t * n);
+
+/* 2. mh_map_rebuild_from_keyframes creates a NEW map on the store's context and fills it.  Synchronous.  It reads the store and
+ *    touches no existing map, so live factors keep the map they hold: the copy-then-insert discipline of Geometric::updateMap.
+ *
+ *    Contract.  The returned map is what mh_map_create(cfg) gives, followed by one mh_map_insert_device per listed keyframe, in
+ *    list order.  Keyframe j uses the cloud cloud[order[j]], the stride 4, and the pose R_W_K + 9j, t_W_K + 3j.  The result is bit
+ *    for bit the same in everything a caller can observe, now or later:
+ *      - mh_map_get_cloud gives the same points in the same order.
+ *      - mh_map_knn gives the same answers.
+ *      - mh_icp_linearize on it gives the same result.
+ *      - mh_map_get_stats gives the same values in every field but device_bytes.
+ *      - Whatever later inserts, purges, previews and carves do to the two maps is the same.  That means the LRU stamps and
+ *        lru_counter are the same too.
+ *    The contract holds when LRU purges fall inside the sequence.  It also covers the case where a purge removes a voxel that a
+ *    later keyframe creates again.
+ *    The poses are f32.  The caller rounds them as toFloat12 does.  The per-point arithmetic is map_assign_kernel's expression,
+ *    unchanged: (r0 x + (r1 y + r2 z)) + t, no FMA.
+ *
+ *    How.  The list is cut into chunks (csrc/rebuild_plan.hpp): a chunk ends where the insert count reaches a multiple of
+ *    cfg->lru_clear_cycle, and before its point total would exceed chunk_points (0 = the default, 4 Mi points; a keyframe larger
+ *    than the budget is a chunk of its own).  A chunk is ONE insert of its clouds laid end to end — the insert's rule couples only
+ *    the points of one voxel, in input order, and numbers voxels in first-seen order — after which every voxel the chunk touched
+ *    is stamped with the counter of the last keyframe of the chunk that put a point into it; the purge runs at the chunk ends
+ *    that land on the cycle.  A keyframe of 0 points still counts as an insert.
+ *
+ *    order, n_order: the entries to insert, each at most once; NULL, 0: every entry in stored order.  R_W_K: 9 floats (row-major)
+ *    and t_W_K: 3 floats per LISTED keyframe.  rc: NULL = defaults.  An empty store or an empty list gives an empty map.
+ *    Refusals with MH_ERR_INVALID_ARG: a NULL kf, cfg, out or res; an invalid cfg (what mh_map_create refuses); an index out of
+ *    range or listed twice; n_order > 0 with NULL order; NULL poses with a non-empty list; a pose entry that is not finite; chunk_points < 0; a non-zero reserved word.
+ *    A point that lands as NaN or beyond +-2^20 voxels gives MH_ERR_UNSUPPORTED, as in the insert; the half-built map is released
+ *    and *out stays NULL.  The store is never changed. */
+typedef struct mh_map_rebuild_config {
+  int64_t chunk_points; /* the point budget of a chunk; 0 = 4 Mi */
+  int64_t reserved;     /* 0 */
+} mh_map_rebuild_config; /* 16 bytes */
+
+typedef struct mh_map_rebuild_result {
+  int64_t keyframes;      /* keyframes inserted */
+  int64_t points_offered; /* the points of their clouds */
+  int64_t chunks;
+  int64_t purges;         /* LRU purge passes run (the chunk ends that land on the cycle) */
+  int64_t n_points;       /* of the finished map */
+  int64_t n_voxels;
+} mh_map_rebuild_result; /* 48 bytes */
+
+int mh_map_rebuild_from_keyframes(mh_keyframes * kf, const mh_map_config * cfg, const int32_t * order, size_t n_order, const float * R_W_K,
+                                  const float * t_W_K, const mh_map_rebuild_config * rc, mh_map ** out, mh_map_rebuild_result * res);
+
 /* ---- diagnostics -------------------------------------------------------------------------------------------------------
  * With MH_ALLOC_CHECK=1 in the environment the device-allocation cache checks its hand-over rule (a block is re-used only
  * behind everything that was enqueued on it): freed blocks are poisoned behind their last use, verified when they are handed

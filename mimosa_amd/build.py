@@ -27,6 +27,8 @@ SOURCES = [
     ("chain_api.hip", []),
     ("map_kernels.hip", ["-ffp-contract=off"]),
     ("map_api.hip", []),
+    ("rebuild_kernels.hip", ["-ffp-contract=off"]),  # a chunk of keyframes as one insert: the transform feeds voxel assignment, as in map_kernels.hip
+    ("keyframes_api.hip", []),
     ("carve_kernels.hip", ["-ffp-contract=off"]),  # the host build of carve_device.hpp (tests/cpp/map_carve_cells.cpp) gives the same digits
     ("shard_kernels.hip", []),
     ("shard_api.hip", []),
@@ -48,7 +50,7 @@ SOURCES = [
     ("pose_graph_kernels.hip", ["-ffp-contract=off"]),  # likewise pose_graph_device.hpp (tests/cpp/pose_graph_step.cpp)
     ("pose_graph_api.hip", []),
 ]
-HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "window_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", "reloc_device.hpp", "carve_device.hpp", "place_device.hpp", "pose_graph_device.hpp", "window_request.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
+HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "window_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", "reloc_device.hpp", "carve_device.hpp", "place_device.hpp", "pose_graph_device.hpp", "window_request.hpp", "rebuild_plan.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
 
 
 def _hipcc() -> str:
@@ -219,7 +221,8 @@ HOST_TESTS = {
     "map_carve_cells": ("map_carve_cells.cpp", ["carve_device.hpp", "math3.hpp"]),
     "place_device_check": ("place_device_check.cpp", ["place_device.hpp", "math3.hpp"]),
     "pose_graph_step": ("pose_graph_step.cpp", ["pose_graph_device.hpp", "window_device.hpp", "align_device.hpp", "math3.hpp"]),
-    "window_request_check": ("window_request_check.cpp", ["window_request.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]),
+    "rebuild_plan_check": ("rebuild_plan_check.cpp", ["rebuild_plan.hpp"]),
+    "window_request_check": ("window_request_check.cpp", ["window_request.hpp", "rebuild_plan.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]),
 }
 
 

@@ -31,6 +31,8 @@ EXPORTS = [
     "mh_place_db_add", "mh_place_db_add_from_scan", "mh_place_db_get", "mh_place_db_query", "mh_place_db_query_from_scan",
     "mh_pose_graph_create", "mh_pose_graph_destroy", "mh_pose_graph_set_poses", "mh_pose_graph_set_fixed", "mh_pose_graph_set_edges",
     "mh_pose_graph_get_poses", "mh_pose_graph_residuals", "mh_pose_graph_optimise",
+    "mh_keyframes_create", "mh_keyframes_destroy", "mh_keyframes_size", "mh_keyframes_get_info", "mh_keyframes_add", "mh_keyframes_add_device",
+    "mh_keyframes_add_from_scan", "mh_keyframes_get", "mh_keyframes_device_points", "mh_map_rebuild_from_keyframes",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
     "mh_icp_window_optimise_relin", "mh_icp_window_optimise_relin_async",
     "mh_icp_window_optimise_lin", "mh_icp_window_optimise_lin_async",
@@ -766,6 +768,18 @@ def load(build_if_missing: bool = True):
     L.mh_pose_graph_get_poses.argtypes = [vp, vp, vp, sz, C.POINTER(sz)]
     L.mh_pose_graph_residuals.argtypes = [vp, vp, vp, vp]
     L.mh_pose_graph_optimise.argtypes = [vp, C.POINTER(PoseGraphConfig), C.POINTER(PoseGraphResult), vp]
+    L.mh_keyframes_create.argtypes = [vp, C.POINTER(KeyframesConfig), pvp]
+    L.mh_keyframes_destroy.argtypes = [vp]
+    L.mh_keyframes_destroy.restype = None
+    L.mh_keyframes_size.argtypes = [vp]
+    L.mh_keyframes_size.restype = sz
+    L.mh_keyframes_get_info.argtypes = [vp, C.POINTER(KeyframesInfo)]
+    L.mh_keyframes_add.argtypes = [vp, vp, sz, sz, C.c_int64, vp]
+    L.mh_keyframes_add_device.argtypes = [vp, vp, sz, sz, C.c_int64, vp]
+    L.mh_keyframes_add_from_scan.argtypes = [vp, vp, i32, C.c_int64, vp]
+    L.mh_keyframes_get.argtypes = [vp, C.c_int32, vp, sz, C.POINTER(sz), vp]
+    L.mh_keyframes_device_points.argtypes = [vp, C.c_int32, C.POINTER(vp), C.POINTER(sz)]
+    L.mh_map_rebuild_from_keyframes.argtypes = [vp, C.POINTER(MapConfig), vp, sz, vp, vp, C.POINTER(MapRebuildConfig), pvp, C.POINTER(MapRebuildResult)]
     L.mh_icp_window_optimise.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_optimise_async.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(WindowConfig), C.POINTER(WindowResult), vp]
     L.mh_icp_window_wait.argtypes = [vp]
@@ -2334,6 +2348,114 @@ class PoseGraph:
     def destroy(self):
         if getattr(self, "h", None):
             self.L.mh_pose_graph_destroy(self.h)
+            self.h = None
+            self.ctx._child_released()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class KeyframesConfig(C.Structure):
+    """mh_keyframes_config (16 bytes)."""
+    _fields_ = [("capacity_keyframes", C.c_int32), ("reserved", C.c_int32), ("capacity_points", C.c_int64)]
+
+
+class KeyframesInfo(C.Structure):
+    """mh_keyframes_info (40 bytes)."""
+    _fields_ = [("keyframes", C.c_int64), ("points", C.c_int64), ("capacity_keyframes", C.c_int64), ("capacity_points", C.c_int64),
+                ("device_bytes", C.c_int64)]
+
+
+class MapRebuildConfig(C.Structure):
+    """mh_map_rebuild_config (16 bytes)."""
+    _fields_ = [("chunk_points", C.c_int64), ("reserved", C.c_int64)]
+
+
+class MapRebuildResult(C.Structure):
+    """mh_map_rebuild_result (48 bytes)."""
+    _fields_ = [("keyframes", C.c_int64), ("points_offered", C.c_int64), ("chunks", C.c_int64), ("purges", C.c_int64), ("n_points", C.c_int64),
+                ("n_voxels", C.c_int64)]
+
+
+class KeyframeStore:
+    """The clouds of the keyframes on the device, each in its own frame, with a tag and no pose (mh_keyframes_*), and the map they
+    give at any poses (rebuild_map: mh_map_rebuild_from_keyframes)."""
+
+    def __init__(self, ctx: Context, capacity_keyframes=1024, capacity_points=1 << 24):
+        self.ctx, self.L = ctx, ctx.L
+        cfg = KeyframesConfig(int(capacity_keyframes), 0, int(capacity_points))
+        h = C.c_void_p()
+        ctx.check(self.L.mh_keyframes_create(ctx.h, C.byref(cfg), C.byref(h)))
+        self.h = h
+        ctx._children += 1
+
+    def size(self) -> int:
+        return int(self.L.mh_keyframes_size(self.h))
+
+    def info(self) -> dict:
+        out = KeyframesInfo()
+        self.ctx.check(self.L.mh_keyframes_get_info(self.h, C.byref(out)))
+        return {n: getattr(out, n) for n, _ in out._fields_}
+
+    def add(self, xyz, tag=0) -> int:
+        """mh_keyframes_add: append host points (n x 3, or n x s with s >= 3: the first three columns); returns the index."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        xyz = xyz.reshape(-1, 3) if xyz.ndim != 2 else xyz
+        idx = C.c_int32(-1)
+        self.ctx.check(self.L.mh_keyframes_add(self.h, _p(xyz) if len(xyz) else None, xyz.shape[0], xyz.shape[1], int(tag), C.byref(idx)))
+        return int(idx.value)
+
+    def add_device(self, d_points, n, stride_floats, tag=0) -> int:
+        """mh_keyframes_add_device: the same for n points at a device address."""
+        idx = C.c_int32(-1)
+        self.ctx.check(self.L.mh_keyframes_add_device(self.h, d_points, int(n), int(stride_floats), int(tag), C.byref(idx)))
+        return int(idx.value)
+
+    def add_from_scan(self, scan, which, tag=0) -> int:
+        """mh_keyframes_add_from_scan: device to device from a scan; which = Scan.FULL or Scan.BODY.  Waits for nothing."""
+        idx = C.c_int32(-1)
+        self.ctx.check(self.L.mh_keyframes_add_from_scan(self.h, scan.h, int(which), int(tag), C.byref(idx)))
+        return int(idx.value)
+
+    def get(self, index):
+        """mh_keyframes_get: (xyz as n x 3 float32, tag) of an entry."""
+        n, tag = C.c_size_t(0), C.c_int64(0)
+        self.ctx.check(self.L.mh_keyframes_get(self.h, int(index), None, 0, C.byref(n), C.byref(tag)))
+        xyz = np.empty((n.value, 3), np.float32)
+        self.ctx.check(self.L.mh_keyframes_get(self.h, int(index), _p(xyz), n.value, C.byref(n), C.byref(tag)))
+        return xyz, int(tag.value)
+
+    def device_points(self, index):
+        """mh_keyframes_device_points: (device address, n) of an entry, 4 floats per point; valid until the store is destroyed."""
+        d, n = C.c_void_p(), C.c_size_t(0)
+        self.ctx.check(self.L.mh_keyframes_device_points(self.h, int(index), C.byref(d), C.byref(n)))
+        return d, int(n.value)
+
+    def rebuild_map(self, poses, order=None, chunk_points=0, **map_cfg):
+        """mh_map_rebuild_from_keyframes: (VoxelMap, result dict).  poses: (R, t) with R of shape K x 3 x 3 and t of shape K x 3 for
+        the K listed keyframes (any float arrays, cast to float32 once); order: the entries to insert (None: all, in stored
+        order); map_cfg: the keywords of VoxelMap (leaf, min_dist, max_pts, mode, lru_horizon, lru_clear_cycle), with its defaults."""
+        d = dict(leaf=0.5, min_dist=0.15, max_pts=20, mode=19, lru_horizon=1000, lru_clear_cycle=10)
+        unknown = set(map_cfg) - set(d)
+        if unknown:
+            raise TypeError(f"rebuild_map: unknown map settings {sorted(unknown)}")
+        d.update(map_cfg)
+        cfg = MapConfig(d["leaf"], d["min_dist"], d["max_pts"], d["mode"], d["lru_horizon"], d["lru_clear_cycle"], 0)
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        K = self.size() if order is None else len(order)
+        R = np.ascontiguousarray(np.asarray(poses[0], dtype=np.float32).reshape(K, 9))
+        t = np.ascontiguousarray(np.asarray(poses[1], dtype=np.float32).reshape(K, 3))
+        rc, res, h = MapRebuildConfig(int(chunk_points), 0), MapRebuildResult(), C.c_void_p()
+        self.ctx.check(self.L.mh_map_rebuild_from_keyframes(self.h, C.byref(cfg), _p(order), 0 if order is None else len(order), _p(R) if K else None,
+                                                            _p(t) if K else None, C.byref(rc), C.byref(h), C.byref(res)))
+        return VoxelMap(self.ctx, _h=h), {n: getattr(res, n) for n, _ in res._fields_}
+
+    def destroy(self):
+        if getattr(self, "h", None):
+            self.L.mh_keyframes_destroy(self.h)
             self.h = None
             self.ctx._child_released()
 

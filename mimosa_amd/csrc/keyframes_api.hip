@@ -1,0 +1,263 @@
+// Keyframe cloud store of the C ABI (include/mimosa_hip.h): mh_keyframes_*.  One device arena of packed float4 (x, y, z, 1), an
+// offset table on the host and on the device, a tag per entry; no pose.  The pack kernel is in rebuild_kernels.hip; the reader
+// of the store, mh_map_rebuild_from_keyframes, in map_api.hip.  Everything runs on the context's stream.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "mh_internal.hpp"
+
+static_assert(sizeof(mh_keyframes_config) == 16 && sizeof(mh_keyframes_info) == 40, "mh_keyframes_* layout");
+
+namespace
+{
+constexpr int32_t kKeyframesMax = 65536;
+
+void keyframes_release_device(mh_keyframes * kf)
+{
+  AllocCache::free(kf->d_arena);
+  AllocCache::free(kf->d_offsets);
+  kf->d_arena = nullptr;
+  kf->d_offsets = nullptr;
+  kf->d_in.release();
+  if (kf->h_io) AllocCache::free_pinned(kf->h_io, kf->h_io_cap);
+  kf->h_io = nullptr;
+  kf->h_io_cap = 0;
+}
+
+// every entry point but destroy: a store whose context was shut down
+int keyframes_alive(const mh_keyframes * kf, const char * who)
+{
+  if (!kf->ctx) return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the store's context was shut down; the handle can only be destroyed");
+  return MH_OK;
+}
+
+// the checks every add shares: room for one more entry of n points
+int keyframes_add_check(const mh_keyframes * kf, const char * who, size_t n)
+{
+  if (kf->tags.size() >= static_cast<size_t>(kf->cfg.capacity_keyframes)) return fail(kf->ctx, MH_ERR_INVALID_ARG, std::string(who) + ": the store is full (keyframes)");
+  if (n > static_cast<uint64_t>(kf->cfg.capacity_points) - kf->offsets.back()) return fail(kf->ctx, MH_ERR_INVALID_ARG, std::string(who) + ": the store is full (points)");
+  return MH_OK;
+}
+
+int keyframes_io(mh_keyframes * kf, size_t bytes)
+{
+  if (bytes <= kf->h_io_cap) return MH_OK;
+  size_t cap = size_t(64) << 10;
+  while (cap < bytes) cap <<= 1;
+  if (kf->h_io) AllocCache::free_pinned(kf->h_io, kf->h_io_cap);  // (every call that used it has waited)
+  kf->h_io = nullptr;
+  kf->h_io_cap = 0;
+  MH_HIP(kf->ctx, AllocCache::alloc_pinned(&kf->h_io, cap));
+  kf->h_io_cap = cap;
+  return MH_OK;
+}
+
+// enqueue the new entry (n device points, `stride` floats apart) behind everything on the stream, and book it
+int keyframes_append(mh_keyframes * kf, const char * who, const float * d_src, size_t n, size_t stride, int64_t tag, int32_t * index)
+{
+  mh_ctx * ctx = kf->ctx;
+  const size_t i = kf->tags.size();
+  const uint64_t at = kf->offsets.back();
+  // (a launch that fails leaves the books where they were: the slot is simply written again)
+  const hipError_t e = mh::launch_keyframes_pack(d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), kf->d_arena + at, kf->d_offsets + i, at + n,
+                                                 ctx->stream);
+  if (e != hipSuccess) return hip_fail(ctx, e, who);
+  if (index) *index = static_cast<int32_t>(i);
+  kf->tags.push_back(tag);
+  kf->offsets.push_back(at + n);
+  return MH_OK;
+}
+
+int keyframes_create(mh_ctx * ctx, const mh_keyframes_config * cfg, mh_keyframes ** out)
+{
+  MH_HIP(ctx, mh_enter(ctx));
+  mh_keyframes * kf = new mh_keyframes;
+  kf->ctx = ctx;
+  kf->cfg = *cfg;
+  kf->tags.reserve(static_cast<size_t>(cfg->capacity_keyframes));
+  kf->offsets.reserve(static_cast<size_t>(cfg->capacity_keyframes) + 1);
+  void * p[2] = {nullptr, nullptr};
+  const size_t off_bytes = (static_cast<size_t>(cfg->capacity_keyframes) + 1) * sizeof(unsigned long long);
+  hipError_t e = AllocCache::alloc(&p[0], static_cast<size_t>(cfg->capacity_points) * sizeof(float4));
+  if (e == hipSuccess) e = AllocCache::alloc(&p[1], off_bytes);
+  kf->d_arena = static_cast<float4 *>(p[0]);
+  kf->d_offsets = static_cast<unsigned long long *>(p[1]);
+  if (e == hipSuccess) e = hipMemsetAsync(kf->d_offsets, 0, off_bytes, ctx->stream);
+  if (e != hipSuccess) {
+    keyframes_release_device(kf);
+    delete kf;
+    return hip_fail(ctx, e, "mh_keyframes_create");
+  }
+  ctx->keyframe_stores.push_back(kf);
+  *out = kf;
+  return MH_OK;
+}
+}  // namespace
+
+namespace mhi
+{
+void keyframes_ctx_gone(mh_ctx * ctx)
+{
+  if (ctx->keyframe_stores.empty()) return;
+  (void)mh_enter(ctx);
+  (void)hipStreamSynchronize(ctx->stream);
+  for (mh_keyframes * kf : ctx->keyframe_stores) {
+    keyframes_release_device(kf);
+    kf->tags.clear();
+    kf->offsets.assign(1, 0);
+    kf->ctx = nullptr;
+  }
+  ctx->keyframe_stores.clear();
+}
+}  // namespace mhi
+
+extern "C" {
+
+int mh_keyframes_create(mh_ctx * ctx, const mh_keyframes_config * cfg, mh_keyframes ** out)
+{
+  if (out) *out = nullptr;
+  if (!cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_create: NULL argument");
+  return guarded(ctx, "mh_keyframes_create", [&]() -> int {
+    if (cfg->capacity_keyframes < 1 || cfg->capacity_keyframes > kKeyframesMax)
+      return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_create: capacity_keyframes must be in 1..65536");
+    if (cfg->capacity_points < 1 || cfg->capacity_points > (int64_t(1) << 40)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_create: capacity_points must be in 1..2^40");
+    if (cfg->reserved != 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_create: reserved must be 0");
+    if (!ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_create: NULL argument");
+    return keyframes_create(ctx, cfg, out);
+  });
+}
+
+void mh_keyframes_destroy(mh_keyframes * kf)
+{
+  if (!kf) return;
+  if (mh_ctx * ctx = kf->ctx) {
+    (void)mh_enter(ctx);
+    (void)hipStreamSynchronize(ctx->stream);  // the arena goes back: nothing may still be reading it
+    keyframes_release_device(kf);
+    auto & v = ctx->keyframe_stores;
+    v.erase(std::remove(v.begin(), v.end(), kf), v.end());
+  }
+  delete kf;
+}
+
+size_t mh_keyframes_size(const mh_keyframes * kf) { return kf && kf->ctx ? kf->tags.size() : 0; }
+
+int mh_keyframes_get_info(const mh_keyframes * kf, mh_keyframes_info * out)
+{
+  if (!kf || !out) return fail(kf ? kf->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_keyframes_get_info: NULL argument");
+  return guarded(kf->ctx, "mh_keyframes_get_info", [&]() -> int {
+    const int rc = keyframes_alive(kf, "mh_keyframes_get_info");
+    if (rc != MH_OK) return rc;
+    out->keyframes = static_cast<int64_t>(kf->tags.size());
+    out->points = static_cast<int64_t>(kf->offsets.back());
+    out->capacity_keyframes = kf->cfg.capacity_keyframes;
+    out->capacity_points = kf->cfg.capacity_points;
+    out->device_bytes = kf->cfg.capacity_points * static_cast<int64_t>(sizeof(float4)) +
+                        (static_cast<int64_t>(kf->cfg.capacity_keyframes) + 1) * static_cast<int64_t>(sizeof(unsigned long long));
+    return MH_OK;
+  });
+}
+
+int mh_keyframes_add(mh_keyframes * kf, const float * xyz, size_t n, size_t stride_floats, int64_t tag, int32_t * index)
+{
+  if (!kf || (!xyz && n)) return fail(kf ? kf->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_keyframes_add: NULL argument");
+  return guarded(kf->ctx, "mh_keyframes_add", [&]() -> int {
+    int rc = keyframes_alive(kf, "mh_keyframes_add");
+    if (rc != MH_OK) return rc;
+    mh_ctx * ctx = kf->ctx;
+    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add: stride_floats must be >= 3");
+    if ((rc = keyframes_add_check(kf, "mh_keyframes_add", n)) != MH_OK) return rc;
+    if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_keyframes_add: batch too large");
+    MH_HIP(ctx, mh_enter(ctx));
+    if (n) {  // packed xyz through the pinned block, then the pack kernel every add shares
+      const size_t bytes = n * 3 * sizeof(float);
+      if ((rc = keyframes_io(kf, bytes)) != MH_OK) return rc;
+      MH_HIP(ctx, kf->d_in.reserve(bytes, ctx->stream, false));
+      float * h = static_cast<float *>(kf->h_io);
+      for (size_t i = 0; i < n; ++i) std::memcpy(h + 3 * i, xyz + i * stride_floats, 3 * sizeof(float));
+      MH_HIP(ctx, hipMemcpyAsync(kf->d_in.p, kf->h_io, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = keyframes_append(kf, "mh_keyframes_add", static_cast<const float *>(kf->d_in.p), n, 3, tag, index);
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the pinned block is the next call's too)
+    return rc;
+  });
+}
+
+int mh_keyframes_add_device(mh_keyframes * kf, const void * d_points, size_t n, size_t stride_floats, int64_t tag, int32_t * index)
+{
+  if (!kf || (!d_points && n)) return fail(kf ? kf->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_keyframes_add_device: NULL argument");
+  return guarded(kf->ctx, "mh_keyframes_add_device", [&]() -> int {
+    int rc = keyframes_alive(kf, "mh_keyframes_add_device");
+    if (rc != MH_OK) return rc;
+    mh_ctx * ctx = kf->ctx;
+    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_device: stride_floats must be >= 3");
+    if ((rc = keyframes_add_check(kf, "mh_keyframes_add_device", n)) != MH_OK) return rc;
+    if (n > 0x3fffffffu || stride_floats > 0xffffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_keyframes_add_device: batch too large");
+    MH_HIP(ctx, mh_enter(ctx));
+    return keyframes_append(kf, "mh_keyframes_add_device", static_cast<const float *>(d_points), n, stride_floats, tag, index);
+  });
+}
+
+int mh_keyframes_add_from_scan(mh_keyframes * kf, const mh_scan * scan, int which, int64_t tag, int32_t * index)
+{
+  if (!kf || !scan) return fail(kf ? kf->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: NULL argument");
+  return guarded(kf->ctx, "mh_keyframes_add_from_scan", [&]() -> int {
+    int rc = keyframes_alive(kf, "mh_keyframes_add_from_scan");
+    if (rc != MH_OK) return rc;
+    mh_ctx * ctx = kf->ctx;
+    if (which < 0 || which > 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: which must be 0 (points_full_) or 1 (Be_cloud_)");
+    // the entry is ordered behind the scan's stages by the stream they share: a scan of another context is refused
+    if (scan->ctx != ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: scan belongs to another context");
+    if (!scan->prepared || (which == 1 && !scan->preprocessed)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: that stage has not run");
+    const void * d = which == 0 ? scan->d_full.p : scan->d_body.p;
+    const size_t n = which == 0 ? static_cast<size_t>(scan->c.n_full) : scan->n_body;
+    if (n && !d) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: that stage has not run");
+    if ((rc = keyframes_add_check(kf, "mh_keyframes_add_from_scan", n)) != MH_OK) return rc;
+    if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_keyframes_add_from_scan: batch too large");
+    MH_HIP(ctx, mh_enter(ctx));
+    return keyframes_append(kf, "mh_keyframes_add_from_scan", static_cast<const float *>(d), n, sizeof(mh_point32) / sizeof(float), tag, index);
+  });
+}
+
+int mh_keyframes_get(mh_keyframes * kf, int32_t index, float * xyz, size_t capacity_points, size_t * n_out, int64_t * tag)
+{
+  if (!kf) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_keyframes_get: NULL argument");
+  return guarded(kf->ctx, "mh_keyframes_get", [&]() -> int {
+    int rc = keyframes_alive(kf, "mh_keyframes_get");
+    if (rc != MH_OK) return rc;
+    mh_ctx * ctx = kf->ctx;
+    if (index < 0 || static_cast<size_t>(index) >= kf->tags.size()) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_get: index out of range");
+    const uint64_t at = kf->offsets[static_cast<size_t>(index)], n = kf->offsets[static_cast<size_t>(index) + 1] - at;
+    const size_t take = xyz ? static_cast<size_t>(std::min<uint64_t>(n, capacity_points)) : 0;
+    if (take) {
+      MH_HIP(ctx, mh_enter(ctx));
+      if ((rc = keyframes_io(kf, take * sizeof(float4))) != MH_OK) return rc;
+      MH_HIP(ctx, hipMemcpyAsync(kf->h_io, kf->d_arena + at, take * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+      MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      const float * h = static_cast<const float *>(kf->h_io);
+      for (size_t i = 0; i < take; ++i) std::memcpy(xyz + 3 * i, h + 4 * i, 3 * sizeof(float));
+    }
+    if (n_out) *n_out = static_cast<size_t>(n);
+    if (tag) *tag = kf->tags[static_cast<size_t>(index)];
+    return MH_OK;
+  });
+}
+
+int mh_keyframes_device_points(mh_keyframes * kf, int32_t index, const float ** d_xyz1, size_t * n)
+{
+  if (!kf || !d_xyz1 || !n) return fail(kf ? kf->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_keyframes_device_points: NULL argument");
+  return guarded(kf->ctx, "mh_keyframes_device_points", [&]() -> int {
+    const int rc = keyframes_alive(kf, "mh_keyframes_device_points");
+    if (rc != MH_OK) return rc;
+    if (index < 0 || static_cast<size_t>(index) >= kf->tags.size()) return fail(kf->ctx, MH_ERR_INVALID_ARG, "mh_keyframes_device_points: index out of range");
+    const uint64_t at = kf->offsets[static_cast<size_t>(index)];
+    *d_xyz1 = reinterpret_cast<const float *>(kf->d_arena + at);
+    *n = static_cast<size_t>(kf->offsets[static_cast<size_t>(index) + 1] - at);
+    return MH_OK;
+  });
+}
+
+}  // extern "C"

@@ -7,12 +7,15 @@
 // the LRU cadence (every lru_clear_cycle-th insert).  Kernels: map_kernels.hip.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "carve_device.hpp"
 #include "mh_internal.hpp"
+#include "rebuild_plan.hpp"
 
 namespace
 {
@@ -230,6 +233,55 @@ int purge_lru(mh_map * m)
   return MH_OK;
 }
 
+// A chunk of keyframes inserted as one batch (mh_map_rebuild_from_keyframes): after phase C every touched voxel's stamp becomes
+// lru_counter + (the chunk's last keyframe with a point in it).  rel: the kc + 1 prefix offsets of the chunk, on the device.
+struct ChunkStamps
+{
+  const uint32_t * d_rel;
+  uint32_t kc;
+};
+
+// Phases A.2 to C of an insert of n > 0 points whose phase A.1 is enqueued (the points in s_pts, their keys in the batch hash):
+// grouping, new voxels, blocks, FlatContainer::add per touched voxel.  The insert and the rebuild share it; `stamps` is the rebuild's.
+// `who` names the entry point in error texts.
+int insert_grouped(mh_map * m, const char * who, size_t n, const ChunkStamps * stamps)
+{
+  mh_ctx * ctx = m->ctx;
+  const mh::InsertScratch s = scratch_of(m);
+  mh::MapArrays a = arrays_of(m);
+  MH_HIP(ctx, mh::launch_map_insert_group(a, static_cast<uint32_t>(n), s, ctx->stream));
+  int rc = fetch_state(m);
+  if (rc != MH_OK) return rc;
+  if (m->h_state->bad_coord) {
+    (void)push_state(m);  // clears the flag; nothing was modified yet
+    return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": a point is NaN or its voxel coordinate exceeds +-2^20");
+  }
+  const uint32_t n_new = m->h_state->n_new_voxels, before = m->n_voxels;
+  if (static_cast<uint64_t>(before) + n_new >= (1u << 27)) return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": more than 2^27 voxels");
+  rc = ensure_voxels(m, static_cast<size_t>(before) + n_new);
+  if (rc == MH_OK && n_new) rc = ensure_table(m, static_cast<size_t>(m->n_blocks) + 8 * static_cast<size_t>(n_new));
+  if (rc != MH_OK) return rc;
+  a = arrays_of(m);
+  if (n_new) {
+    MH_HIP(ctx, mh::launch_map_create_voxels(a, static_cast<uint32_t>(n), before, m->lru_counter, s, ctx->stream));
+    rc = fetch_state(m);
+    if (rc != MH_OK) return rc;
+    const uint32_t nb = m->h_state->n_blocks;
+    rc = ensure_blocks(m, nb, m->n_blocks);
+    if (rc != MH_OK) return rc;
+    m->n_blocks = nb;
+    a = arrays_of(m);
+  }
+  MH_HIP(ctx, mh::launch_map_insert_points(a, static_cast<uint32_t>(n), before + n_new, static_cast<uint32_t>(m->cfg.max_points_in_cell), m->min_sq,
+                                           m->inv_leaf, m->lru_counter, s, ctx->stream));
+  if (stamps) MH_HIP(ctx, mh::launch_map_rebuild_stamp(a, stamps->d_rel, stamps->kc, static_cast<uint32_t>(n), m->lru_counter, s, ctx->stream));
+  rc = fetch_state(m);
+  if (rc != MH_OK) return rc;
+  m->n_voxels = m->h_state->n_voxels;
+  m->n_points = m->h_state->n_points;
+  return MH_OK;
+}
+
 // iVox::insert on a batch already on the device: n points `stride` floats apart, optional f32 transform (12 floats on
 // the device).  Synchronous: the map is current when this returns.
 int insert_device(mh_map * m, const float * d_src, size_t n, size_t stride, const float * d_Rt12)
@@ -244,41 +296,88 @@ int insert_device(mh_map * m, const float * d_src, size_t n, size_t stride, cons
   if (n) {
     int rc = ensure_scratch(m, n);
     if (rc != MH_OK) return rc;
-    const mh::InsertScratch s = scratch_of(m);
-    mh::MapArrays a = arrays_of(m);
-    MH_HIP(ctx, mh::launch_map_insert_prepare(a, d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), d_Rt12, m->inv_leaf, s, ctx->stream));
-    rc = fetch_state(m);
+    MH_HIP(ctx, mh::launch_map_insert_assign(arrays_of(m), d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), d_Rt12, m->inv_leaf, scratch_of(m),
+                                             ctx->stream));
+    rc = insert_grouped(m, "mh_map_insert", n, nullptr);
     if (rc != MH_OK) return rc;
-    if (m->h_state->bad_coord) {
-      (void)push_state(m);  // clears the flag; nothing was modified yet
-      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_map_insert: a point is NaN or its voxel coordinate exceeds +-2^20");
-    }
-    const uint32_t n_new = m->h_state->n_new_voxels, before = m->n_voxels;
-    if (static_cast<uint64_t>(before) + n_new >= (1u << 27)) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_map_insert: more than 2^27 voxels");
-    rc = ensure_voxels(m, static_cast<size_t>(before) + n_new);
-    if (rc == MH_OK && n_new) rc = ensure_table(m, static_cast<size_t>(m->n_blocks) + 8 * static_cast<size_t>(n_new));
-    if (rc != MH_OK) return rc;
-    a = arrays_of(m);
-    if (n_new) {
-      MH_HIP(ctx, mh::launch_map_create_voxels(a, static_cast<uint32_t>(n), before, m->lru_counter, s, ctx->stream));
-      rc = fetch_state(m);
-      if (rc != MH_OK) return rc;
-      const uint32_t nb = m->h_state->n_blocks;
-      rc = ensure_blocks(m, nb, m->n_blocks);
-      if (rc != MH_OK) return rc;
-      m->n_blocks = nb;
-      a = arrays_of(m);
-    }
-    MH_HIP(ctx, mh::launch_map_insert_points(a, static_cast<uint32_t>(n), before + n_new, static_cast<uint32_t>(m->cfg.max_points_in_cell), m->min_sq,
-                                             m->inv_leaf, m->lru_counter, s, ctx->stream));
-    rc = fetch_state(m);
-    if (rc != MH_OK) return rc;
-    m->n_voxels = m->h_state->n_voxels;
-    m->n_points = m->h_state->n_points;
   }
   m->inserts++;
   // ++lru_counter; every lru_clear_cycle inserts the stale voxels go
   if ((++m->lru_counter) % static_cast<uint64_t>(m->cfg.lru_clear_cycle) == 0) return purge_lru(m);
+  return MH_OK;
+}
+
+// mh_map_rebuild_from_keyframes on a fresh map: the listed keyframes chunk by chunk (rebuild_plan.hpp).  sizes / src: points and
+// arena offset per listed keyframe; poses: 12 floats each (R row-major, t).
+int rebuild_fill(mh_map * m, const mh_keyframes * kf, const std::vector<uint64_t> & sizes, const std::vector<uint64_t> & src, const float * R, const float * t,
+                 uint64_t budget, mh_map_rebuild_result * res)
+{
+  mh_ctx * ctx = m->ctx;
+  const char * who = "mh_map_rebuild_from_keyframes";
+  const size_t K = sizes.size();
+  const std::vector<mh::RebuildChunk> plan = mh::rebuild_plan(sizes.data(), K, m->lru_counter, static_cast<uint64_t>(m->cfg.lru_clear_cycle), budget);
+  for (const mh::RebuildChunk & c : plan)
+    if (c.points > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": batch too large");
+  // the whole plan goes to the device once: [RebuildKeyframe x K | prefix offsets: (k1 - k0 + 1) words per chunk]
+  const size_t kf_bytes = K * sizeof(mh::RebuildKeyframe), rel_words = K + plan.size();
+  DevTemp<char> d_plan;
+  void * h_plan = nullptr;
+  const size_t plan_bytes = kf_bytes + rel_words * sizeof(uint32_t);
+  if (K) {
+    MH_HIP(ctx, d_plan.alloc(plan_bytes));
+    size_t pinned_bytes = 4096;  // (the pinned cache keeps blocks by their exact size)
+    while (pinned_bytes < plan_bytes) pinned_bytes <<= 1;
+    MH_HIP(ctx, AllocCache::alloc_pinned(&h_plan, pinned_bytes));
+    mh::RebuildKeyframe * hk = static_cast<mh::RebuildKeyframe *>(h_plan);
+    uint32_t * hr = reinterpret_cast<uint32_t *>(static_cast<char *>(h_plan) + kf_bytes);
+    for (size_t j = 0; j < K; ++j) {
+      hk[j].src = src[j];
+      std::memcpy(hk[j].Rt12, R + 9 * j, 9 * sizeof(float));
+      std::memcpy(hk[j].Rt12 + 9, t + 3 * j, 3 * sizeof(float));
+    }
+    size_t w = 0;
+    for (const mh::RebuildChunk & c : plan) {
+      uint32_t at = 0;
+      for (size_t j = c.k0; j < c.k1; ++j) {
+        hr[w++] = at;
+        at += static_cast<uint32_t>(sizes[j]);
+      }
+      hr[w++] = at;
+    }
+    hipError_t e = hipMemcpyAsync(d_plan.p, h_plan, plan_bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    AllocCache::free_pinned(h_plan, pinned_bytes);
+    if (e != hipSuccess) return hip_fail(ctx, e, who);
+  }
+  const mh::RebuildKeyframe * d_kf = reinterpret_cast<const mh::RebuildKeyframe *>(d_plan.p);
+  const uint32_t * d_rel = reinterpret_cast<const uint32_t *>(d_plan.p + kf_bytes);
+  size_t w = 0;
+  for (const mh::RebuildChunk & c : plan) {
+    const uint32_t kc = static_cast<uint32_t>(c.k1 - c.k0);
+    if (c.points) {
+      const size_t n = static_cast<size_t>(c.points);
+      int rc = ensure_scratch(m, n);
+      if (rc != MH_OK) return rc;
+      MH_HIP(ctx, mh::launch_map_rebuild_assign(arrays_of(m), kf->d_arena, d_kf + c.k0, d_rel + w, kc, static_cast<uint32_t>(n), m->inv_leaf, scratch_of(m),
+                                                ctx->stream));
+      const ChunkStamps stamps{d_rel + w, kc};
+      rc = insert_grouped(m, who, n, &stamps);
+      if (rc != MH_OK) return rc;
+    }
+    w += kc + 1;
+    m->inserts += kc;
+    m->lru_counter += kc;
+    res->keyframes += kc;
+    res->points_offered += static_cast<int64_t>(c.points);
+    res->chunks++;
+    if (c.purge_after) {
+      const int rc = purge_lru(m);
+      if (rc != MH_OK) return rc;
+      res->purges++;
+    }
+  }
+  res->n_points = static_cast<int64_t>(m->n_points);
+  res->n_voxels = m->n_voxels;
   return MH_OK;
 }
 
@@ -446,6 +545,36 @@ int map_alloc(mh_ctx * ctx, const mh_map_config & cfg, mh_map ** out)
   *out = m;
   return MH_OK;
 }
+
+// mh_map_create, also the first half of mh_map_rebuild_from_keyframes (`who` in the texts; cap_code: what a max_points_in_cell
+// outside 1..20 answers)
+int map_create(mh_ctx * ctx, const char * who, const mh_map_config * cfg, int cap_code, mh_map ** out)
+{
+  const std::string w(who);
+  if (!(cfg->leaf_size > 0)) return fail(ctx, MH_ERR_INVALID_ARG, w + ": leaf_size must be > 0");
+  if (cfg->max_points_in_cell < 1 || cfg->max_points_in_cell > mh::kBucketStride) return fail(ctx, cap_code, w + ": max_points_in_cell must be in 1..20");
+  const int md = cfg->neighbor_voxel_mode;
+  if (md != 1 && md != 7 && md != 19 && md != 27) return fail(ctx, MH_ERR_INVALID_ARG, w + ": neighbor_voxel_mode must be 1, 7, 19 or 27");
+  if (cfg->lru_clear_cycle < 1) return fail(ctx, MH_ERR_INVALID_ARG, w + ": lru_clear_cycle must be >= 1");
+  if (cfg->lru_horizon < 0) return fail(ctx, MH_ERR_INVALID_ARG, w + ": lru_horizon must be >= 0");
+  MH_HIP(ctx, mh_enter(ctx));
+  mh_map * m = nullptr;
+  int rc = map_alloc(ctx, *cfg, &m);
+  if (rc != MH_OK) return rc;
+  rc = ensure_table(m, 256);
+  if (rc == MH_OK) rc = ensure_voxels(m, 64);
+  if (rc == MH_OK) rc = ensure_blocks(m, 1, 0);  // block 0's table must exist: absent-block lookups read it
+  if (rc == MH_OK) rc = push_state(m);
+  if (rc != MH_OK) {
+    map_free(m);
+    return rc;
+  }
+  MH_HIP(ctx, hipMemsetAsync(m->d_buckets.p, 0, m->d_buckets.cap, ctx->stream));
+  MH_HIP(ctx, hipMemsetAsync(m->d_qbuckets.p, 0, m->d_qbuckets.cap, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *out = m;
+  return MH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -454,29 +583,53 @@ int mh_map_create(mh_ctx * ctx, const mh_map_config * cfg, mh_map ** out)
 {
   if (!ctx || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_create: NULL argument");
   *out = nullptr;
-  return guarded(ctx, "mh_map_create", [&]() -> int {
-    if (!(cfg->leaf_size > 0)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_create: leaf_size must be > 0");
-    if (cfg->max_points_in_cell < 1 || cfg->max_points_in_cell > mh::kBucketStride)
-      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_map_create: max_points_in_cell must be in 1..20");
-    const int md = cfg->neighbor_voxel_mode;
-    if (md != 1 && md != 7 && md != 19 && md != 27) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_create: neighbor_voxel_mode must be 1, 7, 19 or 27");
-    if (cfg->lru_clear_cycle < 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_create: lru_clear_cycle must be >= 1");
-    if (cfg->lru_horizon < 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_create: lru_horizon must be >= 0");
-    MH_HIP(ctx, mh_enter(ctx));
+  return guarded(ctx, "mh_map_create", [&]() -> int { return map_create(ctx, "mh_map_create", cfg, MH_ERR_UNSUPPORTED, out); });
+}
+
+int mh_map_rebuild_from_keyframes(mh_keyframes * kf, const mh_map_config * cfg, const int32_t * order, size_t n_order, const float * R_W_K,
+                                  const float * t_W_K, const mh_map_rebuild_config * rc_cfg, mh_map ** out, mh_map_rebuild_result * res)
+{
+  const char * who = "mh_map_rebuild_from_keyframes";
+  if (out) *out = nullptr;
+  if (!kf || !cfg || !out || !res) return fail(kf ? kf->ctx : nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+  mh_ctx * ctx = kf->ctx;
+  return guarded(ctx, who, [&]() -> int {
+    std::memset(res, 0, sizeof(*res));
+    if (!ctx) return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the store's context was shut down; the handle can only be destroyed");
+    if (n_order && !order) return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": n_order > 0 with a NULL order");
+    if (rc_cfg && (rc_cfg->chunk_points < 0 || rc_cfg->reserved != 0)) return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": chunk_points must be >= 0, reserved 0");
+    // the list: every entry in stored order, or `order` (each entry at most once)
+    const size_t size = kf->tags.size();
+    const size_t K = order ? n_order : size;
+    std::vector<uint64_t> sizes(K), src(K);
+    std::vector<char> seen(order ? size : 0, 0);
+    for (size_t j = 0; j < K; ++j) {
+      size_t i = j;
+      if (order) {
+        if (order[j] < 0 || static_cast<size_t>(order[j]) >= size) return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": order holds an index out of range");
+        i = static_cast<size_t>(order[j]);
+        if (seen[i]) return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": order lists an entry twice");
+        seen[i] = 1;
+      }
+      src[j] = kf->offsets[i];
+      sizes[j] = kf->offsets[i + 1] - kf->offsets[i];
+    }
+    if (K && (!R_W_K || !t_W_K)) return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": NULL poses with a non-empty list");
+    for (size_t j = 0; j < 9 * K; ++j)
+      if (!std::isfinite(R_W_K[j])) return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": a pose entry is not finite");
+    for (size_t j = 0; j < 3 * K; ++j)
+      if (!std::isfinite(t_W_K[j])) return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": a pose entry is not finite");
+    const uint64_t budget = rc_cfg && rc_cfg->chunk_points > 0 ? static_cast<uint64_t>(rc_cfg->chunk_points) : (uint64_t(4) << 20);
     mh_map * m = nullptr;
-    int rc = map_alloc(ctx, *cfg, &m);
+    int rc = map_create(ctx, who, cfg, MH_ERR_INVALID_ARG, &m);
     if (rc != MH_OK) return rc;
-    rc = ensure_table(m, 256);
-    if (rc == MH_OK) rc = ensure_voxels(m, 64);
-    if (rc == MH_OK) rc = ensure_blocks(m, 1, 0);  // block 0's table must exist: absent-block lookups read it
-    if (rc == MH_OK) rc = push_state(m);
-    if (rc != MH_OK) {
+    rc = rebuild_fill(m, kf, sizes, src, R_W_K, t_W_K, budget, res);
+    if (rc != MH_OK) {  // the half-built map is released; the text of the failure stays
+      (void)hipStreamSynchronize(ctx->stream);
       map_free(m);
+      std::memset(res, 0, sizeof(*res));
       return rc;
     }
-    MH_HIP(ctx, hipMemsetAsync(m->d_buckets.p, 0, m->d_buckets.cap, ctx->stream));
-    MH_HIP(ctx, hipMemsetAsync(m->d_qbuckets.p, 0, m->d_qbuckets.cap, ctx->stream));
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *out = m;
     return MH_OK;
   });

@@ -96,6 +96,31 @@ __device__ __forceinline__ bool voxel_block(int cx, int cy, int cz, int which, i
   bz = b[2];
   return true;
 }
+
+// Geometric::updateMap's world transform (geometric.cpp:483-490): f32 R p + t, Eigen's r0 x + (r1 y + r2 z) order, no FMA (the
+// including kernels are compiled with -ffp-contract=off).  The one place the expression exists: map_assign_kernel and
+// map_rebuild_assign_kernel both call it.
+__device__ __forceinline__ void map_world_point(const float * Rt12, float px, float py, float pz, float & x, float & y, float & z)
+{
+  x = (Rt12[0] * px + (Rt12[1] * py + Rt12[2] * pz)) + Rt12[9];
+  y = (Rt12[3] * px + (Rt12[4] * py + Rt12[5] * pz)) + Rt12[10];
+  z = (Rt12[6] * px + (Rt12[7] * py + Rt12[8] * pz)) + Rt12[11];
+}
+
+// Voxel key of an insert's point.  A NaN or a coordinate beyond the key range raises MapState::bad_coord and is filed under
+// voxel (0,0,0): the grouping stays well-formed, the host rejects the batch before anything is modified.
+__device__ __forceinline__ uint64_t map_point_key(float x, float y, float z, double inv_leaf, MapState * st)
+{
+  const int cx = fast_floor(static_cast<double>(x) * inv_leaf), cy = fast_floor(static_cast<double>(y) * inv_leaf),
+            cz = fast_floor(static_cast<double>(z) * inv_leaf);
+  // one voxel of margin: the blocks a voxel touches must fit the key as well
+  const int lim = kVoxCoordBias - 8;
+  if (cx < -lim || cx >= lim || cy < -lim || cy >= lim || cz < -lim || cz >= lim || !(x == x) || !(y == y) || !(z == z)) {
+    atomicOr(&st->bad_coord, 1u);
+    return pack_coord_key(0, 0, 0);
+  }
+  return pack_coord_key(cx, cy, cz);
+}
 #endif
 
 struct InsertScratch
@@ -114,6 +139,27 @@ size_t map_temp_bytes(size_t n);
 // transform p <- R p + t first (Geometric::updateMap's world transform, geometric.cpp:483-490).
 hipError_t launch_map_insert_prepare(const MapArrays & m, const float * src, uint32_t n, uint32_t stride_floats, const float * Rt12,
                                      double inv_leaf, const InsertScratch & s, hipStream_t stream);
+// The two halves of launch_map_insert_prepare.  A.1: the batch hash cleared, then map_assign_kernel (s.pts, the keys).  A.2 to A.4:
+// grouping, lookup, creation ranks — also what follows a caller's own phase A.1 (launch_map_rebuild_assign).
+hipError_t launch_map_insert_assign(const MapArrays & m, const float * src, uint32_t n, uint32_t stride_floats, const float * Rt12, double inv_leaf,
+                                    const InsertScratch & s, hipStream_t stream);
+hipError_t launch_map_insert_group(const MapArrays & m, uint32_t n, const InsertScratch & s, hipStream_t stream);
+// ---- mh_map_rebuild_from_keyframes (rebuild_kernels.hip): a chunk of keyframes as one insert ------------------------------
+struct RebuildKeyframe
+{
+  unsigned long long src;  // first point of the keyframe's cloud in the store's arena (float4 per point)
+  float Rt12[12];          // its pose: R row-major, then t
+};
+// phase A.1 of a chunk: point i of the n points of kc keyframes laid end to end (rel[j] = first point of keyframe j, rel[kc] = n)
+// is loaded from the arena, moved by its keyframe's pose (map_world_point) and keyed, as map_assign_kernel does for one batch.
+hipError_t launch_map_rebuild_assign(const MapArrays & m, const float4 * arena, const RebuildKeyframe * kf, const uint32_t * rel, uint32_t kc,
+                                     uint32_t n, double inv_leaf, const InsertScratch & s, hipStream_t stream);
+// after phase C: lru[voxel of segment s] = counter_start + (the last keyframe of the chunk with a point in the segment)
+hipError_t launch_map_rebuild_stamp(const MapArrays & m, const uint32_t * rel, uint32_t kc, uint32_t n, unsigned long long counter_start,
+                                    const InsertScratch & s, hipStream_t stream);
+// a keyframe store's entry: n points `stride_floats` apart (device memory) -> float4 (x, y, z, 1); offsets[1] = offsets[0] + n
+hipError_t launch_keyframes_pack(const float * src, uint32_t n, uint32_t stride_floats, float4 * dst, unsigned long long * offsets,
+                                 unsigned long long end, hipStream_t stream);
 // phase B: create the new voxels (coordinates, lru) and claim their blocks in the hash table; publishes n_blocks
 hipError_t launch_map_create_voxels(const MapArrays & m, uint32_t n, uint32_t n_voxels_before, unsigned long long lru_counter,
                                     const InsertScratch & s, hipStream_t stream);

@@ -70,23 +70,9 @@ __global__ __launch_bounds__(kT) void map_assign_kernel(const float * src, uint3
   uint64_t key = vg::kEmpty64;
   if (valid) {
     float x = src[static_cast<size_t>(i) * stride], y = src[static_cast<size_t>(i) * stride + 1], z = src[static_cast<size_t>(i) * stride + 2];
-    if (Rt12) {  // geometric.cpp:483-490: f32 R p + t, Eigen's r0 x + (r1 y + r2 z) order, no FMA
-      const float px = x, py = y, pz = z;
-      x = (Rt12[0] * px + (Rt12[1] * py + Rt12[2] * pz)) + Rt12[9];
-      y = (Rt12[3] * px + (Rt12[4] * py + Rt12[5] * pz)) + Rt12[10];
-      z = (Rt12[6] * px + (Rt12[7] * py + Rt12[8] * pz)) + Rt12[11];
-    }
+    if (Rt12) map_world_point(Rt12, x, y, z, x, y, z);  // (by value in, by reference out)
     pts[i] = make_float4(x, y, z, 1.0f);
-    const int cx = fast_floor(static_cast<double>(x) * inv_leaf), cy = fast_floor(static_cast<double>(y) * inv_leaf),
-              cz = fast_floor(static_cast<double>(z) * inv_leaf);
-    // one voxel of margin: the blocks a voxel touches must fit the key as well
-    const int lim = kVoxCoordBias - 8;
-    if (cx < -lim || cx >= lim || cy < -lim || cy >= lim || cz < -lim || cz >= lim || !(x == x) || !(y == y) || !(z == z)) {
-      atomicOr(&st->bad_coord, 1u);
-      key = pack_coord_key(0, 0, 0);  // keeps the grouping well-formed; the host rejects the batch before anything is modified
-    } else {
-      key = pack_coord_key(cx, cy, cz);
-    }
+    key = map_point_key(x, y, z, inv_leaf, st);
   }
   const uint32_t slot = vg::voxel_assign(h, valid, key, i);
   if (valid) slot_of[i] = slot;
@@ -515,13 +501,27 @@ size_t map_group_bytes(size_t n) { return vg::layout(n).bytes; }
 hipError_t launch_map_insert_prepare(const MapArrays & m, const float * src, uint32_t n, uint32_t stride_floats, const float * Rt12,
                                      double inv_leaf, const InsertScratch & s, hipStream_t stream)
 {
+  const hipError_t e = launch_map_insert_assign(m, src, n, stride_floats, Rt12, inv_leaf, s, stream);
+  return e != hipSuccess ? e : launch_map_insert_group(m, n, s, stream);
+}
+
+hipError_t launch_map_insert_assign(const MapArrays & m, const float * src, uint32_t n, uint32_t stride_floats, const float * Rt12, double inv_leaf,
+                                    const InsertScratch & s, hipStream_t stream)
+{
   const vg::Layout L = vg::layout(n);
   const vg::Buffers B = vg::carve(s.group, n);
-  hipError_t e = hipMemsetAsync(s.group, 0xFF, L.clear_bytes, stream);
+  const hipError_t e = hipMemsetAsync(s.group, 0xFF, L.clear_bytes, stream);
   if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(map_assign_kernel, dim3((n + kT - 1) / kT), dim3(kT), 0, stream, src, n, stride_floats, Rt12, inv_leaf, s.pts, B.h, B.slot_of, m.state);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_insert_group(const MapArrays & m, uint32_t n, const InsertScratch & s, hipStream_t stream)
+{
+  const vg::Buffers B = vg::carve(s.group, n);
   const dim3 g((n + kT - 1) / kT), b(kT);
-  hipLaunchKernelGGL(map_assign_kernel, g, b, 0, stream, src, n, stride_floats, Rt12, inv_leaf, s.pts, B.h, B.slot_of, m.state);
-  if ((e = vg::launch_group(B, n, &m.state->n_segments, stream)) != hipSuccess) return e;
+  const hipError_t e = vg::launch_group(B, n, &m.state->n_segments, stream);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(map_lookup_kernel, g, b, 0, stream, m, B.h, B.vox_slot, s.seg_vid, s.blk_new);  // <= n segments
   hipLaunchKernelGGL(map_new_ids_kernel, g, b, 0, stream, m, s.blk_new, s.seg_vid);
   return hipGetLastError();

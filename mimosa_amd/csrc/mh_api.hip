@@ -255,6 +255,7 @@ void mh_shutdown(mh_ctx * ctx)
   mhi::shard_ctx_gone(ctx);
   mhi::place_ctx_gone(ctx);
   mhi::pose_graph_ctx_gone(ctx);
+  mhi::keyframes_ctx_gone(ctx);
   if (ctx->stream) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);

@@ -116,6 +116,8 @@ struct mh_ctx
   std::vector<mh_place_db *> place_dbs;
   // ... and from the pose graphs created on it (pose_graph_api.hip)
   std::vector<mh_pose_graph *> pose_graphs;
+  // ... and from the keyframe cloud stores created on it (keyframes_api.hip)
+  std::vector<mh_keyframes *> keyframe_stores;
 };
 
 // The stream of the context the calling thread is working for (set by mh_enter at every entry point): what the allocation
@@ -622,6 +624,21 @@ struct mh_map
   bool poisoned = false;  // a mutation failed half way (LRU purge, carve): the device arrays and the counters disagree; every later call fails
 };
 
+// mh_keyframes_*: the clouds of the keyframes, each in its own frame, packed float4 (x, y, z, 1) in one device arena of fixed size
+// (keyframes_api.hip).  An entry holds no pose.  mh_map_rebuild_from_keyframes (map_api.hip) reads it.
+struct mh_keyframes
+{
+  mh_ctx * ctx = nullptr;  // null: mh_shutdown of the context ran first (keyframes_ctx_gone), the handle can only be destroyed
+  mh_keyframes_config cfg{};
+  float4 * d_arena = nullptr;                // capacity_points entries
+  unsigned long long * d_offsets = nullptr;  // capacity_keyframes + 1: entry i is points [d_offsets[i], d_offsets[i + 1]) of the arena
+  std::vector<uint64_t> offsets{0};          // the same on the host: size() + 1 entries
+  std::vector<int64_t> tags;
+  DevBuf d_in;             // a host batch, packed float4
+  void * h_io = nullptr;   // pinned staging of a host batch / of a read-back
+  size_t h_io_cap = 0;
+};
+
 inline void map_add_reader(mh_map * m, mh_ctx * c)
 {
   std::lock_guard<std::mutex> g(m->readers_mu);
@@ -812,6 +829,8 @@ void shard_ctx_gone(mh_ctx * ctx);
 void place_ctx_gone(mh_ctx * ctx);
 // pose_graph_api.hip: likewise for the pose graphs listed on ctx
 void pose_graph_ctx_gone(mh_ctx * ctx);
+// keyframes_api.hip: likewise for the keyframe cloud stores listed on ctx
+void keyframes_ctx_gone(mh_ctx * ctx);
 // a call's DeviceResult from its flagged words in pending slot `slot` (spin_ns > 0: wait up to that long for words that have
 // not arrived); false = something is still missing
 bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, long spin_ns, mh::DeviceResult & d);

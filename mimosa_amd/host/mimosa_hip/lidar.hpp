@@ -69,6 +69,12 @@ struct GeometricConfig
   int map_carve_ring = 1;
   double map_carve_range_min = 0.5, map_carve_range_max = 60.0;
   double map_carve_margin_abs = 0.3, map_carve_margin_rel = 0.0;
+  // Not in the reference: > 0 keeps every keyframe's Be_cloud_ in a device-resident KeyframeStore of this many keyframes and
+  // map_keyframe_store_points points in all (both > 0), so that Geometric::rebuildMap can rebuild the map at corrected poses after
+  // a loop closure.  0 = off: no store exists and the reference's behaviour holds bit for bit.  The caller sizes the store: a
+  // keyframe that does not fit makes updateMap throw.
+  int map_keyframe_store_capacity = 0;
+  int64_t map_keyframe_store_points = 0;
   size_t initial_clouds_to_force_map_update = 10;
   size_t lru_horizon = 100;
   size_t neighbor_voxel_mode = 7;
@@ -242,8 +248,10 @@ public:
     return map_;
   }
   const std::shared_ptr<Context> & context() const { return ctx_; }
+  const mh_map_config & config() const { return cfg_; }
 
 private:
+  friend class KeyframeStore;  // rebuild() hands a finished mh_map over
   IncrementalVoxelMapPCL(const std::shared_ptr<Context> & ctx, const mh_map_config & cfg, std::nullptr_t) : ctx_(ctx), cfg_(cfg) {}
   void ensure()
   {
@@ -619,6 +627,86 @@ private:
   std::shared_ptr<Context> ctx_;  // (declared first: the database goes before its context)
   mh_place_config cfg_;
   mh_place_db * db_ = nullptr;
+};
+
+// The clouds of the keyframes on the device, each in its own frame, with a tag and no pose (mh_keyframes_*): what a map needs to
+// be rebuilt at the poses a pose graph corrected.  Capacities are fixed at creation; an add that does not fit throws.
+class KeyframeStore
+{
+public:
+  KeyframeStore(const std::shared_ptr<Context> & ctx, int32_t capacity_keyframes, int64_t capacity_points) : ctx_(ctx)
+  {
+    mh_keyframes_config cfg{};
+    cfg.capacity_keyframes = capacity_keyframes;
+    cfg.capacity_points = capacity_points;
+    ctx_->check(mh_keyframes_create(ctx_->get(), &cfg, &kf_), "mh_keyframes_create");
+  }
+  ~KeyframeStore() { mh_keyframes_destroy(kf_); }
+  KeyframeStore(const KeyframeStore &) = delete;
+  KeyframeStore & operator=(const KeyframeStore &) = delete;
+
+  size_t size() const { return mh_keyframes_size(kf_); }
+  mh_keyframes_info info() const
+  {
+    mh_keyframes_info i{};
+    ctx_->check(mh_keyframes_get_info(kf_, &i), "mh_keyframes_get_info");
+    return i;
+  }
+  int32_t add(const PointCloud & cloud, int64_t tag)
+  {
+    int32_t index = -1;
+    ctx_->check(mh_keyframes_add(kf_, cloud.empty() ? nullptr : &cloud[0].x, cloud.size(), sizeof(Point) / sizeof(float), tag, &index), "mh_keyframes_add");
+    return index;
+  }
+  // Be_cloud_ of a device-resident scan, device to device, nothing waits
+  int32_t addBodyCloud(mh_scan * scan, int64_t tag)
+  {
+    int32_t index = -1;
+    ctx_->check(mh_keyframes_add_from_scan(kf_, scan, 1, tag, &index), "mh_keyframes_add_from_scan");
+    return index;
+  }
+  PointCloud get(int32_t index, int64_t * tag = nullptr)
+  {
+    size_t n = 0;
+    ctx_->check(mh_keyframes_get(kf_, index, nullptr, 0, &n, tag), "mh_keyframes_get");
+    std::vector<float> xyz(3 * n);
+    ctx_->check(mh_keyframes_get(kf_, index, xyz.data(), n, &n, tag), "mh_keyframes_get");
+    PointCloud out(n, Point{});
+    for (size_t i = 0; i < n; ++i) {
+      out[i].x = xyz[3 * i];
+      out[i].y = xyz[3 * i + 1];
+      out[i].z = xyz[3 * i + 2];
+    }
+    return out;
+  }
+  // mh_map_rebuild_from_keyframes: the map that map_cfg and one insert per listed keyframe at poses[j] give (poses rounded by
+  // toFloat12, as updateMap's are), bit for bit.  order empty: every entry in stored order.
+  IncrementalVoxelMapPCL::Ptr rebuild(const std::vector<Pose3> & poses, const mh_map_config & map_cfg, const std::vector<int32_t> & order = {},
+                                      int64_t chunk_points = 0, mh_map_rebuild_result * result = nullptr)
+  {
+    const size_t K = order.empty() ? size() : order.size();
+    if (poses.size() != K) throw std::runtime_error("KeyframeStore::rebuild: one pose per listed keyframe");
+    std::vector<float> R(9 * K), t(3 * K);
+    for (size_t j = 0; j < K; ++j) {
+      float Rt[12];
+      toFloat12(poses[j], Rt);
+      std::copy(Rt, Rt + 9, R.begin() + 9 * j);
+      std::copy(Rt + 9, Rt + 12, t.begin() + 3 * j);
+    }
+    mh_map_rebuild_config rc{};
+    rc.chunk_points = chunk_points;
+    mh_map_rebuild_result res{};
+    IncrementalVoxelMapPCL::Ptr out(new IncrementalVoxelMapPCL(ctx_, map_cfg, nullptr));
+    ctx_->check(mh_map_rebuild_from_keyframes(kf_, &map_cfg, order.empty() ? nullptr : order.data(), order.size(), R.data(), t.data(), &rc, &out->map_, &res),
+                "mh_map_rebuild_from_keyframes");
+    if (result) *result = res;
+    return out;
+  }
+  mh_keyframes * underlying() { return kf_; }
+
+private:
+  std::shared_ptr<Context> ctx_;  // (declared first: the store goes before its context)
+  mh_keyframes * kf_ = nullptr;
 };
 
 // A pose graph over all keyframes, optimised on the device (mh_pose_graph_*): where a loop closure found by PlaceDatabase and
@@ -1682,6 +1770,8 @@ public:
     ivox_map_->set_neighbor_voxel_mode(config.neighbor_voxel_mode);
     ivox_map_->set_min_dist_in_cell(config.scan_to_map.target_ivox_map_min_dist_in_voxel);
     initial_clouds_to_force_map_update_ = config.initial_clouds_to_force_map_update;
+    if (config.map_keyframe_store_capacity > 0)
+      keyframe_store_ = std::make_shared<KeyframeStore>(ctx_, config.map_keyframe_store_capacity, config.map_keyframe_store_points);
   }
 
   // geometric.cpp:128-183: subset -> body frame (f32, on the GPU) -> voxel down-sample (host, :55-126)
@@ -1845,8 +1935,33 @@ public:
       if (!W.empty()) ctx_->check(mh_transform_f32(ctx_->get(), W.data(), W.size(), Rt, Rt + 9), "mh_transform_f32");
       ivox_map_->insert(W);
     }
+    if (keyframe_store_) {  // a full store throws: the caller sizes it (GeometricConfig::map_keyframe_store_*)
+      const int64_t tag = static_cast<int64_t>(map_poses_.size());
+      if (device_scan_)
+        keyframe_store_->addBodyCloud(device_scan_->underlying(), tag);
+      else
+        keyframe_store_->add(Be_cloud_, tag);
+    }
     map_poses_.push_back(T_W_Be);
   }
+
+  // After a loop closure: ivox_map_ becomes the map that the stored keyframe clouds give at `corrected` (one pose per keyframe, in
+  // map_poses_' order), map_poses_ becomes `corrected`.  The previous map lives on in the factors that hold it, as after updateMap.
+  // Needs GeometricConfig::map_keyframe_store_capacity > 0.  Refused with map_carve_grid > 0: a carved map is not a pure insert
+  // sequence, so the stored clouds do not reproduce it.
+  mh_map_rebuild_result rebuildMap(const std::vector<Pose3> & corrected)
+  {
+    if (!keyframe_store_) throw std::runtime_error("Geometric::rebuildMap: no keyframe store (GeometricConfig::map_keyframe_store_capacity is 0)");
+    if (config.map_carve_grid > 0) throw std::runtime_error("Geometric::rebuildMap: a carved map (map_carve_grid > 0) is not a pure insert sequence");
+    if (corrected.size() != map_poses_.size() || corrected.size() != keyframe_store_->size())
+      throw std::runtime_error("Geometric::rebuildMap: one corrected pose per keyframe");
+    mh_map_rebuild_result res{};
+    ivox_map_ = keyframe_store_->rebuild(corrected, ivox_map_->config(), {}, 0, &res);
+    map_poses_ = corrected;
+    return res;
+  }
+  const std::shared_ptr<KeyframeStore> & keyframeStore() const { return keyframe_store_; }
+  const std::vector<Pose3> & mapPoses() const { return map_poses_; }
 
   const GeometricDebug & debug() const { return debug_; }
   const PointCloud & sourceCloud() const { return sm_Be_cloud_ds_; }
@@ -1910,6 +2025,7 @@ private:
   ScanFrontEnd * device_scan_ = nullptr;  // set by the device preprocess: the factor takes its cloud from there
   ICPFactor::Ptr factor_;
   IncrementalVoxelMapPCL::Ptr ivox_map_;
+  std::shared_ptr<KeyframeStore> keyframe_store_;  // null unless GeometricConfig::map_keyframe_store_capacity > 0
   std::vector<Pose3> map_poses_;
   size_t initial_clouds_to_force_map_update_ = 0;
   double ts_ = 0;
