@@ -953,24 +953,52 @@ int mh_icp_window_marginalise_joint_async(mh_icp * const * icps, size_t W, const
  *    MH_OK and converged = 0 — the window chains' rule.  LIMIT: T must be positive definite by itself, so every run of poses
  *    joined by near edges needs a fixed pose or damping; a gap in the chain bridged only by a far edge makes A regular but T
  *    singular and ends in flag 4, as does a far edge whose info is only positive semi-definite.
+ * 7. A prior p on pose i (mh_pose_graph_set_priors) has a measured pose Z (world from keyframe) and a dense symmetric info[36]
+ *    = Om in (rotation, translation) order.  Its residual is d = [Log(Z.R^T R_i), Z.R^T (t_i - Z.t)] (the window chains' local
+ *    coordinates of T_i around Z), its Jacobian M = blockdiag(Jr^-1(d_r), Exp(d_r)), Jr^-1 the inverse right Jacobian of SO(3)
+ *    (the matrix the window chains transport a factor with).  It adds M^T Om M to the diagonal block of i, M^T Om d to the
+ *    gradient and d^T Om d to f.  A prior on a fixed pose acts on nothing but f.  A pose may carry several priors.  Priors
+ *    belong to T: they make T positive definite for a run of poses that has no fixed pose, as far as their info reaches.
+ * 8. Every edge and every prior may carry a loss {kind, param} (mh_pose_graph_set_loss).  With s = r^T Om r, its chi^2 as
+ *    mh_pose_graph_residuals / mh_pose_graph_prior_residuals report it, the term has a weight w and a cost rho:
+ *      0 none                 w = 1                                       rho = s
+ *      1 Huber, param k > 0   w = 1 if s <= k^2, else k / sqrt(s)         rho = s if s <= k^2, else 2 k sqrt(s) - k^2
+ *      2 Cauchy, param k > 0  w = 1 / (1 + s / k^2)                       rho = k^2 log(1 + s / k^2)
+ *      3 DCS, param Phi > 0   w = c^2, c = min(1, 2 Phi / (Phi + s))      rho = c^2 s + Phi (1 - c)^2
+ *    (kinds 1 .. 3 read an s that is not positive as 0).  A w below 1e-12 is taken as 1e-12, so that Om_f^-1 / w of a far edge
+ *    stays far from the pivot test's 1e300.  The term enters the system with w times each of its contributions of 1. and 7.;
+ *    f sums rho.  WHERE w is applied: the term's blocks and gradients are formed unweighted, and every entry of them is
+ *    multiplied by w, once, as one rounded product w * entry, at the point where it is added into a sum of a pose's block row
+ *    or right-hand side or is read as a matrix entry (w_f Om_f is what 4. factorises and inverts for a far edge; the refinement
+ *    residual reads w_f times the edge's blocks).  With w = 1 that product is the entry itself.
+ * 9. Order of sums: a pose's sums run over its edges in edge-list order, then over its priors in prior-list order, then the
+ *    damping.  The cost fold of 3. runs over c[0 .. E + P), c[j] = rho of term j, edges then priors.  With no prior and every
+ *    kind 0, every launch does what it does without 7. - 9. and the result has the same bits.
  *
- * mh_pose_graph_set_poses copies n poses (1 .. max_poses); with an n other than the last one it also drops the edges and the
- * fixed flags.  mh_pose_graph_set_fixed: n flags (NULL: none fixed).  mh_pose_graph_set_edges replaces the edge list (n_edges
- * 0 .. max_edges; copied before the call returns).  mh_pose_graph_get_poses: the poses as the last call left them; capacity in
+ * mh_pose_graph_set_poses copies n poses (1 .. max_poses); with an n other than the last one it also drops the edges, the
+ * fixed flags, the priors and the losses.  mh_pose_graph_set_fixed: n flags (NULL: none fixed).  mh_pose_graph_set_edges replaces the edge list (n_edges
+ * 0 .. max_edges; copied before the call returns) and drops the edges' losses.  mh_pose_graph_set_priors replaces the prior
+ * list (0 .. max_poses entries, copied) and drops the priors' losses.  mh_pose_graph_set_loss replaces both lists of losses:
+ * `edges` has one entry per edge, `priors` one per prior, each in list order; NULL: no loss on any of them.  mh_pose_graph_get_poses: the poses as the last call left them; capacity in
  * poses, *n_out (may be NULL) the count; R and t may each be NULL.  mh_pose_graph_residuals evaluates every edge at the stored
  * poses and moves nothing: r[6 E] the residuals, chi2[E] = r^T Om r per edge — what a caller needs to reject a false loop
  * before accepting it — and *f their sum in the order of 3.; each may be NULL.  mh_pose_graph_optimise: cfg->iters iterations
  * are queued, or check_every at a time with a look at the chain's stop word in between (the result does not depend on it);
- * launches behind a stopped iteration return at once.  trace_poses: NULL, or iters x n x 12 doubles the caller owns — the
+ * launches behind a stopped iteration return at once.  With losses trace[].f is the sum of rho.  mh_pose_graph_prior_residuals
+ * (d[6 P], chi2[P] = d^T Om d) and mh_pose_graph_weights (w_edges[E], w_priors[P], *f the sum of rho in the order of 9.) evaluate
+ * at the stored poses and move nothing; each output may be NULL.  mh_pose_graph_residuals keeps reporting the edges' chi^2 and
+ * their plain sum, whatever the losses.  trace_poses: NULL, or iters x n x 12 doubles the caller owns — the
  * poses (R, then t) behind every executed step; rows of iterations that were not executed are left untouched.
  *
  * Refusals, each with nothing enqueued and the graph unchanged — MH_ERR_INVALID_ARG: a NULL argument; max_poses outside
  * 1 .. MH_PGO_MAX_POSES, max_edges above MH_PGO_MAX_EDGES; n outside 1 .. max_poses; a pose entry that is not finite; a call
  * that needs poses before any were set; n_edges above max_edges; pose_a < 0, pose_a >= pose_b, pose_b >= n; an entry of Z_R,
  * Z_t or info that is not finite; info[6 r + c] != info[6 c + r]; capacity below n; iters outside 1 .. 64; a negative or
- * non-finite damping, eps or check_every.  MH_ERR_UNSUPPORTED: more than MH_PGO_FAR_MAX far edges.  A graph belongs to its
+ * non-finite damping, eps or check_every; a prior whose pose is outside 0 .. n - 1, with an entry that is
+ * not finite or an asymmetric info; more priors than max_poses; a loss kind outside 0 .. 3; a kind 1 .. 3 whose param is not
+ * finite and positive; edge losses given before edges were set.  MH_ERR_UNSUPPORTED: more than MH_PGO_FAR_MAX far edges.  A graph belongs to its
  * context; after mh_shutdown of the context every call but mh_pose_graph_destroy refuses it.
- * Not here: unary priors on a pose, robust kernels on edges, an asynchronous form, the sharded path. */
+ * Not here: an asynchronous form, the sharded path. */
 #define MH_PGO_MAX_POSES 4096
 #define MH_PGO_MAX_EDGES 32768
 #define MH_PGO_FAR_MAX 32 /* edges with pose_b - pose_a >= 2 */
@@ -985,7 +1013,7 @@ typedef struct mh_pose_graph_config {
 } mh_pose_graph_config; /* 32 bytes */
 
 typedef struct mh_pose_graph_trace {
-  double f;                    /* sum of r^T Om r at the poses the iteration evaluated */
+  double f;                    /* sum of rho (r^T Om r where no loss is set) at the poses the iteration evaluated */
   double step_rot, step_trans; /* max over the poses of |xi_r|, |xi_t| */
   int32_t flags;               /* 4: a pivot was not positive (no step; the call ends here) */
   int32_t reserved;            /* 0 */
@@ -1007,6 +1035,29 @@ int mh_pose_graph_get_poses(mh_pose_graph * pg, double * R, double * t, size_t c
 int mh_pose_graph_residuals(mh_pose_graph * pg, double * r /* 6 E or NULL */, double * chi2 /* E or NULL */, double * f);
 int mh_pose_graph_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_graph_result * out,
                            double * trace_poses /* NULL or iters x n x 12 */);
+
+#define MH_PGO_LOSS_NONE 0
+#define MH_PGO_LOSS_HUBER 1
+#define MH_PGO_LOSS_CAUCHY 2
+#define MH_PGO_LOSS_DCS 3
+
+typedef struct mh_pose_prior {
+  int32_t pose, reserved;   /* 0 .. n - 1; 0 */
+  double Z_R[9], Z_t[3];    /* the measured pose, world from keyframe */
+  double info[36];          /* dense, symmetric, (rotation, translation) order */
+} mh_pose_prior; /* 392 bytes */
+
+typedef struct mh_pose_graph_loss {
+  int32_t kind, reserved;   /* MH_PGO_LOSS_*; 0 */
+  double param;             /* k (Huber, Cauchy) or Phi (DCS): finite and > 0; not read for kind 0 */
+} mh_pose_graph_loss; /* 16 bytes */
+
+int mh_pose_graph_set_priors(mh_pose_graph * pg, const mh_pose_prior * priors, size_t n /* 0 .. max_poses */);
+int mh_pose_graph_set_loss(mh_pose_graph * pg, const mh_pose_graph_loss * edges /* E or NULL = none */,
+                           const mh_pose_graph_loss * priors /* P or NULL = none */);
+int mh_pose_graph_prior_residuals(mh_pose_graph * pg, double * d /* 6 P or NULL */, double * chi2 /* P or NULL */);
+int mh_pose_graph_weights(mh_pose_graph * pg, double * w_edges /* E or NULL */, double * w_priors /* P or NULL */,
+                          double * f /* sum of rho, rule order; or NULL */);
 
 /* ---- deskew / rigid transforms ----------------------------------------------------------------
  * Manager::deskewPoints hot loop (src/lidar/manager.cpp:496-509): every point whose t equals

@@ -31,6 +31,7 @@ EXPORTS = [
     "mh_place_db_add", "mh_place_db_add_from_scan", "mh_place_db_get", "mh_place_db_query", "mh_place_db_query_from_scan",
     "mh_pose_graph_create", "mh_pose_graph_destroy", "mh_pose_graph_set_poses", "mh_pose_graph_set_fixed", "mh_pose_graph_set_edges",
     "mh_pose_graph_get_poses", "mh_pose_graph_residuals", "mh_pose_graph_optimise",
+    "mh_pose_graph_set_priors", "mh_pose_graph_set_loss", "mh_pose_graph_prior_residuals", "mh_pose_graph_weights",
     "mh_keyframes_create", "mh_keyframes_destroy", "mh_keyframes_size", "mh_keyframes_get_info", "mh_keyframes_add", "mh_keyframes_add_device",
     "mh_keyframes_add_from_scan", "mh_keyframes_get", "mh_keyframes_device_points", "mh_map_rebuild_from_keyframes",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
@@ -768,6 +769,10 @@ def load(build_if_missing: bool = True):
     L.mh_pose_graph_get_poses.argtypes = [vp, vp, vp, sz, C.POINTER(sz)]
     L.mh_pose_graph_residuals.argtypes = [vp, vp, vp, vp]
     L.mh_pose_graph_optimise.argtypes = [vp, C.POINTER(PoseGraphConfig), C.POINTER(PoseGraphResult), vp]
+    L.mh_pose_graph_set_priors.argtypes = [vp, C.POINTER(PosePrior), sz]
+    L.mh_pose_graph_set_loss.argtypes = [vp, C.POINTER(PoseGraphLoss), C.POINTER(PoseGraphLoss)]
+    L.mh_pose_graph_prior_residuals.argtypes = [vp, vp, vp]
+    L.mh_pose_graph_weights.argtypes = [vp, vp, vp, vp]
     L.mh_keyframes_create.argtypes = [vp, C.POINTER(KeyframesConfig), pvp]
     L.mh_keyframes_destroy.argtypes = [vp]
     L.mh_keyframes_destroy.restype = None
@@ -2282,6 +2287,40 @@ class PoseGraphResult(C.Structure):
                 ("trace", PoseGraphTrace * 64)]
 
 
+MH_PGO_LOSS_NONE, MH_PGO_LOSS_HUBER, MH_PGO_LOSS_CAUCHY, MH_PGO_LOSS_DCS = 0, 1, 2, 3
+PGO_LOSS_KINDS = {None: 0, "none": 0, "huber": 1, "cauchy": 2, "dcs": 3}
+
+
+class PosePrior(C.Structure):
+    """mh_pose_prior (392 bytes)."""
+    _fields_ = [("pose", C.c_int32), ("reserved", C.c_int32), ("Z_R", C.c_double * 9), ("Z_t", C.c_double * 3), ("info", C.c_double * 36)]
+
+
+class PoseGraphLoss(C.Structure):
+    """mh_pose_graph_loss (16 bytes)."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("param", C.c_double)]
+
+
+def make_pose_prior(priors):
+    """an array of mh_pose_prior from dicts {"pose": i, "Z": (R, t) the measured pose (world from keyframe), "info": 6 x 6}"""
+    arr = (PosePrior * max(len(priors), 1))()
+    for q, e in zip(arr, priors):
+        q.pose = int(e["pose"])
+        q.Z_R[:] = [float(v) for v in np.asarray(e["Z"][0], np.float64).reshape(9)]
+        q.Z_t[:] = [float(v) for v in np.asarray(e["Z"][1], np.float64).reshape(3)]
+        q.info[:] = [float(v) for v in np.asarray(e["info"], np.float64).reshape(36)]
+    return arr
+
+
+def make_pose_graph_loss(losses):
+    """an array of mh_pose_graph_loss from (kind, param) pairs; kind a number or "none" / "huber" / "cauchy" / "dcs", or None"""
+    arr = (PoseGraphLoss * max(len(losses), 1))()
+    for q, e in zip(arr, losses):
+        kind, param = (0, 0.0) if e is None else e
+        q.kind, q.param = int(PGO_LOSS_KINDS.get(kind, kind)), float(param)
+    return arr
+
+
 def make_pose_graph_config(iters=16, check_every=0, damping=0.0, eps_rot=1e-9, eps_trans=1e-9) -> PoseGraphConfig:
     return PoseGraphConfig(int(iters), int(check_every), float(damping), float(eps_rot), float(eps_trans))
 
@@ -2295,15 +2334,16 @@ class PoseGraph:
         h = C.c_void_p()
         ctx.check(self.L.mh_pose_graph_create(ctx.h, int(max_poses), int(max_edges), C.byref(h)))
         self.h = h
-        self.n = self.n_edges = 0
+        self.n = self.n_edges = self.n_priors = 0
         ctx._children += 1
 
     def set_poses(self, R, t):
-        """mh_pose_graph_set_poses: R n x 3 x 3, t n x 3.  Another n than before drops the edges and the fixed flags."""
+        """mh_pose_graph_set_poses: R n x 3 x 3, t n x 3.  Another n than before drops the edges, the fixed flags, the priors and
+        the losses."""
         R, t = _f64(R).reshape(-1, 9), _f64(t).reshape(-1, 3)
         self.ctx.check(self.L.mh_pose_graph_set_poses(self.h, _p(R), _p(t), R.shape[0]))
         if R.shape[0] != self.n:
-            self.n, self.n_edges = R.shape[0], 0
+            self.n, self.n_edges, self.n_priors = R.shape[0], 0, 0
 
     def set_fixed(self, fixed=None):
         """mh_pose_graph_set_fixed: n flags, or None for no fixed pose."""
@@ -2316,6 +2356,35 @@ class PoseGraph:
         arr = edges if isinstance(edges, C.Array) else make_window_edge(edges)
         self.ctx.check(self.L.mh_pose_graph_set_edges(self.h, arr, n))
         self.n_edges = n
+
+    def set_priors(self, priors):
+        """mh_pose_graph_set_priors: dicts as make_pose_prior takes them, or an array it made.  Drops the priors' losses."""
+        n = len(priors)
+        arr = priors if isinstance(priors, C.Array) else make_pose_prior(priors)
+        self.ctx.check(self.L.mh_pose_graph_set_priors(self.h, arr, n))
+        self.n_priors = n
+
+    def set_loss(self, edges=None, priors=None):
+        """mh_pose_graph_set_loss: one (kind, param) per edge and per prior as make_pose_graph_loss takes them; None: no loss."""
+        def arr(v, n, what):
+            if v is None or isinstance(v, C.Array):
+                return v
+            if len(v) != n:
+                raise ValueError("set_loss: %d %s losses for %d %ss" % (len(v), what, n, what))
+            return make_pose_graph_loss(v)
+        self.ctx.check(self.L.mh_pose_graph_set_loss(self.h, arr(edges, self.n_edges, "edge"), arr(priors, self.n_priors, "prior")))
+
+    def prior_residuals(self):
+        """mh_pose_graph_prior_residuals: (d P x 6, chi2 P) at the stored poses; nothing moves."""
+        d, chi2 = np.empty((self.n_priors, 6)), np.empty(self.n_priors)
+        self.ctx.check(self.L.mh_pose_graph_prior_residuals(self.h, _p(d) if self.n_priors else None, _p(chi2) if self.n_priors else None))
+        return d, chi2
+
+    def weights(self):
+        """mh_pose_graph_weights: (w per edge, w per prior, f = the sum of rho) at the stored poses; nothing moves."""
+        we, wp, f = np.empty(self.n_edges), np.empty(self.n_priors), C.c_double(0.0)
+        self.ctx.check(self.L.mh_pose_graph_weights(self.h, _p(we) if self.n_edges else None, _p(wp) if self.n_priors else None, C.byref(f)))
+        return we, wp, float(f.value)
 
     def poses(self):
         """mh_pose_graph_get_poses: (R n x 3 x 3, t n x 3) as the last call left them."""

@@ -13,13 +13,17 @@
 #include "pose_graph_device.hpp"
 
 static_assert(sizeof(mh_pose_graph_config) == 32 && sizeof(mh_pose_graph_trace) == 32 && sizeof(mh_pose_graph_result) == 32 + 64 * 32, "mh_pose_graph_* layout");
+static_assert(sizeof(mh_pose_prior) == 392 && sizeof(mh_pose_graph_loss) == 16, "mh_pose_prior, mh_pose_graph_loss layout");
+static_assert(MH_PGO_LOSS_NONE == mh::kPgoLossNone && MH_PGO_LOSS_HUBER == mh::kPgoLossHuber && MH_PGO_LOSS_CAUCHY == mh::kPgoLossCauchy &&
+                MH_PGO_LOSS_DCS == mh::kPgoLossDcs,
+              "MH_PGO_LOSS_*");
 static_assert(MH_PGO_MAX_POSES == mh::kPgoMaxPoses && MH_PGO_MAX_EDGES == mh::kPgoMaxEdges && MH_PGO_FAR_MAX == mh::kPgoFarMax && mh::kPgoMaxIters == 64,
               "mh_pose_graph_* constants");
 
 namespace mh
 {
 hipError_t launch_pgo_edges(const PgoGraph & g, bool want_res, hipStream_t stream);
-hipError_t launch_pgo_cost(const PgoGraph & g, hipStream_t stream);
+hipError_t launch_pgo_cost(const PgoGraph & g, bool chi2, hipStream_t stream);
 hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream);
 }  // namespace mh
 
@@ -27,7 +31,7 @@ struct mh_pose_graph
 {
   mh_ctx * ctx = nullptr;  // null: mh_shutdown of the context ran first (pose_graph_ctx_gone), the handle can only be destroyed
   size_t max_poses = 0, max_edges = 0;
-  size_t n = 0, n_edges = 0, n_far = 0;
+  size_t n = 0, n_edges = 0, n_far = 0, n_priors = 0;
   char * d_block = nullptr;  // every array of mh::PgoGraph (pgo_layout)
   size_t off[mh::kPgArrays] = {};
   mh::PgoGraph g{};          // device pointers into d_block
@@ -103,12 +107,16 @@ int pgo_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_pose_graph *
     std::memset(pg->h_words, 0, mh::kPgoMaxIters * sizeof(uint4));
     e = hipHostGetDevicePointer(reinterpret_cast<void **>(&pg->d_words), pg->h_words, 0);
   }
+  mh::pgo_bind(pg->g, pg->d_block, pg->off);
+  // no loss on any term until mh_pose_graph_set_loss says otherwise
+  if (e == hipSuccess) e = hipMemsetAsync(pg->g.lkind, 0, std::max<size_t>(max_edges, 1) * sizeof(int), ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(pg->g.plkind, 0, max_poses * sizeof(int), ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) {
     pgo_release_device(pg);
     delete pg;
     return hip_fail(ctx, e, "mh_pose_graph_create");
   }
-  mh::pgo_bind(pg->g, pg->d_block, pg->off);
   ctx->pose_graphs.push_back(pg);
   *out = pg;
   return MH_OK;
@@ -160,7 +168,8 @@ int pgo_set_edges(mh_pose_graph * pg, const mh_window_edge * edges, size_t E, si
   if (rc != MH_OK) return rc;
   size_t at = 0;
   const mh::PgoGraph & g = pg->g;
-  hipError_t e = pgo_up(pg, at, g.ea, ea.data(), E);
+  hipError_t e = hipMemsetAsync(g.lkind, 0, std::max<size_t>(E, 1) * sizeof(int), ctx->stream);  // the edges' losses go with the list
+  if (e == hipSuccess) e = pgo_up(pg, at, g.ea, ea.data(), E);
   if (e == hipSuccess) e = pgo_up(pg, at, g.eb, eb.data(), E);
   if (e == hipSuccess) e = pgo_up(pg, at, g.eslot, slot.data(), E);
   if (e == hipSuccess) e = pgo_up(pg, at, g.inc_off, inc_off.data(), N + 1);
@@ -187,6 +196,7 @@ mh::PgoGraph pgo_graph(const mh_pose_graph * pg)
   g.E = static_cast<int>(pg->n_edges);
   g.F = static_cast<int>(pg->n_far);
   g.K = 6 * g.F + 1;
+  g.P = static_cast<int>(pg->n_priors);
   return g;
 }
 
@@ -278,10 +288,11 @@ int pgo_residuals(mh_pose_graph * pg, double * r, double * chi2, double * f)
   MH_HIP(ctx, mh_enter(ctx));
   const int rc = pgo_host(pg, 16 + 7 * E * sizeof(double));
   if (rc != MH_OK) return rc;
-  const mh::PgoGraph g = pgo_graph(pg);
+  mh::PgoGraph g = pgo_graph(pg);
+  g.P = 0;  // the edges alone
   hipError_t e = hipMemsetAsync(g.st, 0, sizeof(mh::PgoState), ctx->stream);
   if (e == hipSuccess) e = mh::launch_pgo_edges(g, true, ctx->stream);
-  if (e == hipSuccess) e = mh::launch_pgo_cost(g, ctx->stream);
+  if (e == hipSuccess) e = mh::launch_pgo_cost(g, true, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out, &g.rows[0].f, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && E) e = hipMemcpyAsync(pg->h_out + 16, g.res, 6 * E * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && E) e = hipMemcpyAsync(pg->h_out + 16 + 6 * E * sizeof(double), g.cz, E * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
@@ -295,6 +306,139 @@ int pgo_residuals(mh_pose_graph * pg, double * r, double * chi2, double * f)
   if (chi2 && E) std::memcpy(chi2, pg->h_out + 16 + 6 * E * sizeof(double), E * sizeof(double));
   return MH_OK;
 }
+
+bool pgo_prior_finite(const mh_pose_prior & q)
+{
+  for (double v : q.Z_R)
+    if (!std::isfinite(v)) return false;
+  for (double v : q.Z_t)
+    if (!std::isfinite(v)) return false;
+  for (double v : q.info)
+    if (!std::isfinite(v)) return false;
+  return true;
+}
+
+int pgo_check_priors(const mh_pose_graph * pg, const mh_pose_prior * priors, size_t P)
+{
+  const mh_ctx * ctx = pg->ctx;
+  if (P > pg->max_poses) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_priors: more priors than max_poses");
+  for (size_t p = 0; p < P; ++p) {
+    const mh_pose_prior & q = priors[p];
+    if (q.pose < 0 || static_cast<size_t>(q.pose) >= pg->n)
+      return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_priors: prior " + std::to_string(p) + " needs 0 <= pose < n");
+    if (!pgo_prior_finite(q)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_priors: prior " + std::to_string(p) + " has an entry that is not finite");
+    if (!exactly_symmetric(q.info, 6, 6)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_priors: a prior's info is not symmetric");
+  }
+  return MH_OK;
+}
+
+int pgo_set_priors(mh_pose_graph * pg, const mh_pose_prior * priors, size_t P)
+{
+  mh_ctx * ctx = pg->ctx;
+  const size_t N = pg->n;
+  std::vector<int> pose(P), pinc_off(N + 1, 0), pinc(P);
+  std::vector<double> ZR(9 * P), Zt(3 * P), Om(36 * P);
+  for (size_t p = 0; p < P; ++p) {
+    const mh_pose_prior & q = priors[p];
+    pose[p] = q.pose;
+    std::memcpy(&ZR[9 * p], q.Z_R, sizeof(q.Z_R));
+    std::memcpy(&Zt[3 * p], q.Z_t, sizeof(q.Z_t));
+    std::memcpy(&Om[36 * p], q.info, sizeof(q.info));
+  }
+  mh::pgo_index_priors(static_cast<int>(N), static_cast<int>(P), pose.data(), pinc_off.data(), pinc.data());
+  MH_HIP(ctx, mh_enter(ctx));
+  const int rc = pgo_host(pg, (48 * P + P + N + 1) * 8 + 8 * 16);
+  if (rc != MH_OK) return rc;
+  size_t at = 0;
+  const mh::PgoGraph & g = pg->g;
+  hipError_t e = hipMemsetAsync(g.plkind, 0, pg->max_poses * sizeof(int), ctx->stream);  // the priors' losses go with the list
+  if (e == hipSuccess) e = pgo_up(pg, at, g.ppose, pose.data(), P);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.pinc_off, pinc_off.data(), N + 1);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.pinc, pinc.data(), P);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.pZR, ZR.data(), 9 * P);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.pZt, Zt.data(), 3 * P);
+  if (e == hipSuccess) e = pgo_up(pg, at, g.pOm, Om.data(), 36 * P);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);  // (the pinned block is the next call's too)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) {
+    pg->n_priors = 0;  // what is on the device is not a prior list any more
+    return hip_fail(ctx, e, "mh_pose_graph_set_priors");
+  }
+  pg->n_priors = P;
+  return MH_OK;
+}
+
+int pgo_check_loss(const mh_ctx * ctx, const mh_pose_graph_loss * loss, size_t n, const char * what)
+{
+  for (size_t k = 0; loss && k < n; ++k) {
+    if (loss[k].kind < MH_PGO_LOSS_NONE || loss[k].kind > MH_PGO_LOSS_DCS)
+      return fail(ctx, MH_ERR_INVALID_ARG, std::string("mh_pose_graph_set_loss: ") + what + " " + std::to_string(k) + " has a kind outside 0 .. 3");
+    if (loss[k].kind != MH_PGO_LOSS_NONE && !(std::isfinite(loss[k].param) && loss[k].param > 0.0))
+      return fail(ctx, MH_ERR_INVALID_ARG, std::string("mh_pose_graph_set_loss: ") + what + " " + std::to_string(k) + " needs a finite param > 0");
+  }
+  return MH_OK;
+}
+
+// one list of losses: kinds and params of n terms, or no loss on any of them
+hipError_t pgo_up_loss(mh_pose_graph * pg, size_t & at, const mh_pose_graph_loss * loss, size_t n, int * kind, double * param)
+{
+  if (!loss || !n) return hipMemsetAsync(kind, 0, std::max<size_t>(n, 1) * sizeof(int), pg->ctx->stream);
+  std::vector<int> k(n);
+  std::vector<double> v(n);
+  for (size_t i = 0; i < n; ++i) {
+    k[i] = loss[i].kind;
+    v[i] = loss[i].kind != MH_PGO_LOSS_NONE ? loss[i].param : 1.0;
+  }
+  hipError_t e = pgo_up(pg, at, kind, k.data(), n);
+  if (e == hipSuccess) e = pgo_up(pg, at, param, v.data(), n);
+  return e;
+}
+
+int pgo_set_loss(mh_pose_graph * pg, const mh_pose_graph_loss * edges, const mh_pose_graph_loss * priors)
+{
+  mh_ctx * ctx = pg->ctx;
+  MH_HIP(ctx, mh_enter(ctx));
+  const int rc = pgo_host(pg, (pg->n_edges + pg->n_priors) * 16 + 4 * 16);
+  if (rc != MH_OK) return rc;
+  size_t at = 0;
+  hipError_t e = pgo_up_loss(pg, at, edges, pg->n_edges, pg->g.lkind, pg->g.lparam);
+  if (e == hipSuccess) e = pgo_up_loss(pg, at, priors, pg->n_priors, pg->g.plkind, pg->g.plparam);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail(ctx, e, "mh_pose_graph_set_loss");
+  return MH_OK;
+}
+
+// every term at the stored poses, for mh_pose_graph_prior_residuals (d, chi2) and mh_pose_graph_weights (w_edges, w_priors, f)
+int pgo_evaluate(mh_pose_graph * pg, const char * who, double * d, double * chi2, double * w_edges, double * w_priors, double * f)
+{
+  mh_ctx * ctx = pg->ctx;
+  const size_t E = pg->n_edges, P = pg->n_priors, D = sizeof(double);
+  MH_HIP(ctx, mh_enter(ctx));
+  const int rc = pgo_host(pg, 16 + (E + 8 * P) * D);
+  if (rc != MH_OK) return rc;
+  const mh::PgoGraph g = pgo_graph(pg);
+  char * const h_w = pg->h_out + 16, * const h_pw = h_w + E * D, * const h_d = h_pw + P * D, * const h_c = h_d + 6 * P * D;
+  hipError_t e = hipMemsetAsync(g.st, 0, sizeof(mh::PgoState), ctx->stream);
+  if (e == hipSuccess) e = mh::launch_pgo_edges(g, false, ctx->stream);
+  if (e == hipSuccess) e = mh::launch_pgo_cost(g, false, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out, &g.rows[0].f, D, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && E) e = hipMemcpyAsync(h_w, g.w, E * D, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && P) e = hipMemcpyAsync(h_pw, g.pw, P * D, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && P) e = hipMemcpyAsync(h_d, g.pres, 6 * P * D, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && P) e = hipMemcpyAsync(h_c, g.pcz, P * D, hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return hip_fail(ctx, e, who);
+  }
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (f) std::memcpy(f, pg->h_out, D);
+  if (w_edges && E) std::memcpy(w_edges, h_w, E * D);
+  if (w_priors && P) std::memcpy(w_priors, h_pw, P * D);
+  if (d && P) std::memcpy(d, h_d, 6 * P * D);
+  if (chi2 && P) std::memcpy(chi2, h_c, P * D);
+  return MH_OK;
+}
 }  // namespace
 
 namespace mhi
@@ -306,7 +450,7 @@ void pose_graph_ctx_gone(mh_ctx * ctx)
   (void)hipStreamSynchronize(ctx->stream);
   for (mh_pose_graph * pg : ctx->pose_graphs) {
     pgo_release_device(pg);
-    pg->n = pg->n_edges = pg->n_far = 0;
+    pg->n = pg->n_edges = pg->n_far = pg->n_priors = 0;
     pg->ctx = nullptr;
   }
   ctx->pose_graphs.clear();
@@ -358,8 +502,9 @@ int mh_pose_graph_set_poses(mh_pose_graph * pg, const double * R, const double *
     size_t at = 0;
     MH_HIP(ctx, pgo_up(pg, at, pg->g.R, R, 9 * n));
     MH_HIP(ctx, pgo_up(pg, at, pg->g.t, t, 3 * n));
-    if (n != pg->n) {  // another graph: its edges and fixed poses are the caller's to set again
+    if (n != pg->n) {  // another graph: its edges, fixed poses, priors and losses are the caller's to set again
       pg->n = n;
+      pg->n_priors = 0;
       MH_HIP(ctx, hipMemsetAsync(pg->g.fixed, 0, n, ctx->stream));
       if ((rc = pgo_drop_edges(pg)) != MH_OK) return rc;
     }
@@ -401,6 +546,55 @@ int mh_pose_graph_set_edges(mh_pose_graph * pg, const mh_window_edge * edges, si
     size_t n_far = 0;
     if ((rc = pgo_check_edges(pg, edges, n_edges, n_far)) != MH_OK) return rc;
     return pgo_set_edges(pg, edges, n_edges, n_far);
+  });
+}
+
+int mh_pose_graph_set_priors(mh_pose_graph * pg, const mh_pose_prior * priors, size_t n)
+{
+  if (!pg || (!priors && n)) return fail(pg ? pg->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_set_priors: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_set_priors", [&]() -> int {
+    int rc = pgo_alive(pg, "mh_pose_graph_set_priors");
+    if (rc != MH_OK) return rc;
+    if (pg->n == 0) return fail(pg->ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_priors: no poses have been set");
+    if ((rc = pgo_check_priors(pg, priors, n)) != MH_OK) return rc;
+    return pgo_set_priors(pg, priors, n);
+  });
+}
+
+int mh_pose_graph_set_loss(mh_pose_graph * pg, const mh_pose_graph_loss * edges, const mh_pose_graph_loss * priors)
+{
+  if (!pg) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_set_loss: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_set_loss", [&]() -> int {
+    int rc = pgo_alive(pg, "mh_pose_graph_set_loss");
+    if (rc != MH_OK) return rc;
+    const mh_ctx * ctx = pg->ctx;
+    if (pg->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_loss: no poses have been set");
+    if (edges && pg->n_edges == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_loss: no edges have been set");
+    if ((rc = pgo_check_loss(ctx, edges, pg->n_edges, "edge")) != MH_OK) return rc;
+    if ((rc = pgo_check_loss(ctx, priors, pg->n_priors, "prior")) != MH_OK) return rc;
+    return pgo_set_loss(pg, edges, priors);
+  });
+}
+
+int mh_pose_graph_prior_residuals(mh_pose_graph * pg, double * d, double * chi2)
+{
+  if (!pg) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_prior_residuals: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_prior_residuals", [&]() -> int {
+    const int rc = pgo_alive(pg, "mh_pose_graph_prior_residuals");
+    if (rc != MH_OK) return rc;
+    if (pg->n == 0) return fail(pg->ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_prior_residuals: no poses have been set");
+    return pgo_evaluate(pg, "mh_pose_graph_prior_residuals", d, chi2, nullptr, nullptr, nullptr);
+  });
+}
+
+int mh_pose_graph_weights(mh_pose_graph * pg, double * w_edges, double * w_priors, double * f)
+{
+  if (!pg) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_weights: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_weights", [&]() -> int {
+    const int rc = pgo_alive(pg, "mh_pose_graph_weights");
+    if (rc != MH_OK) return rc;
+    if (pg->n == 0) return fail(pg->ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_weights: no poses have been set");
+    return pgo_evaluate(pg, "mh_pose_graph_weights", nullptr, nullptr, w_edges, w_priors, f);
   });
 }
 

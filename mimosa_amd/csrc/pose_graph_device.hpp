@@ -17,7 +17,16 @@
 // without floating-point contraction.  Work that is independent per index is a function of the index (pgo_edge, pgo_gather,
 // pgo_sweep_col): the host loops over it, the kernels give an index to a lane.  Work of one workgroup is written as PHASES
 // over a `Par` executor, as in window_device.hpp.  Nothing is summed by atomics: a pose's contributions are added in
-// edge-list order from its incidence list, the cost is folded as sum_{l < 256} (sum_k cz[l + 256 k]), k and l ascending.
+// edge-list order from its incidence list, the cost is folded as sum_{l < 256} (sum_k c[l + 256 k]), k and l ascending.
+//
+// Priors and losses (mh_pose_graph_set_priors, mh_pose_graph_set_loss).  Prior p on pose i is term E + p of the edge pass
+// (pgo_term): d = window_local(Z, T_i), and window_transport of the model (Om, 0, 0) by d gives M^T Om M, M^T Om d and
+// s = d^T Om d, M = blockdiag(Jr^-1(d_r), Exp(d_r)).  Every term has a weight w and a cost rho from its chi^2 s (pgo_loss).  The
+// per-term products stay unweighted in memory; w multiplies an entry WHERE IT IS READ into a sum or a matrix — in pgo_gather, in
+// pgo_far_info (w_f Om_f is what is factorised and inverted) and in pgo_residual_row — as one product w * entry, rounded, before
+// the addition.  With w == 1.0 that product is the entry itself, so a graph without priors and losses keeps its bits.  A pose's
+// sums run over its edges in edge-list order, then over its priors in prior-list order, then the damping; the cost fold runs
+// over c[j] = rho of term j, j < E + P, edges then priors.
 #pragma once
 
 #include <cstddef>
@@ -66,13 +75,29 @@ struct PgoGraph
   int * far;                               // F: the far edges, in list order
   unsigned char * fixed;                   // N
   PgoState * st;
+  // priors and losses; all zero (P, every kind): none
+  int P;                                   // priors: the terms E .. E + P of the edge pass
+  double *w, *rho, *lparam;                // per edge: the weight and cost pgo_loss gave; the loss's parameter
+  int * lkind;                             // per edge: the loss's kind (kPgoLoss*)
+  double *pZR, *pZt, *pOm;                 // per prior: the measured pose and its information matrix
+  double *pH, *pg, *pres, *pcz;            // per prior: M^T Om M, M^T Om d, d, d^T Om d
+  double *pw, *prho, *plparam;             // per prior: as w, rho, lparam
+  int *plkind, *ppose;                     // per prior: as lkind; its pose
+  int *pinc_off, *pinc;                    // N + 1; P: pose i's priors in list order
 };
+enum PgoLossKind
+{
+  kPgoLossNone, kPgoLossHuber, kPgoLossCauchy, kPgoLossDcs
+};
+constexpr double kPgoMinWeight = 1e-12;  // a smaller w is taken as this: Om_f^-1 / w stays far below the pivot test's 1e300
 
 // Byte offsets of every array in one block for at most maxN poses and maxE edges; returns the block's size.
 enum PgoArray
 {
   kPgR, kPgT, kPgZR, kPgZt, kPgOm, kPgBaa, kPgEba, kPgGa, kPgGb, kPgCz, kPgRes, kPgJa, kPgOmL, kPgOmD, kPgOmInv, kPgA, kPgEb, kPgRhs, kPgL,
   kPgDv, kPgG, kPgY, kPgC, kPgU, kPgX, kPgRr, kPgY1, kPgD, kPgFold, kPgRows, kPgEa, kPgEbI, kPgSlot, kPgIncOff, kPgInc, kPgFar, kPgFixed, kPgSt,
+  kPgW, kPgRho, kPgLParam, kPgLKind, kPgPZR, kPgPZt, kPgPOm, kPgPH, kPgPG, kPgPRes, kPgPCz, kPgPW, kPgPRho, kPgPLParam, kPgPLKind, kPgPPose,
+  kPgPIncOff, kPgPInc,
   kPgArrays
 };
 inline size_t pgo_layout(size_t maxN, size_t maxE, size_t off[kPgArrays])
@@ -82,7 +107,9 @@ inline size_t pgo_layout(size_t maxN, size_t maxE, size_t off[kPgArrays])
                                    6 * maxE * D, maxE * D, 6 * maxE * D, 36 * F * D, 36 * F * D, 6 * F * D, 36 * F * D, 36 * maxN * D, 36 * maxN * D,
                                    6 * maxN * D, 36 * maxN * D, 6 * maxN * D, 36 * maxN * D, 6 * maxN * K * D, 36 * F * F * D, 6 * F * D, 6 * maxN * D,
                                    6 * maxN * D, 6 * maxN * D, 6 * maxN * D, 3 * kPgoFold * D, kPgoMaxIters * sizeof(PgoRow), maxE * I, maxE * I, maxE * I,
-                                   (maxN + 1) * I, 2 * maxE * I, F * I, maxN, sizeof(PgoState)};
+                                   (maxN + 1) * I, 2 * maxE * I, F * I, maxN, sizeof(PgoState),
+                                   maxE * D, maxE * D, maxE * D, maxE * I, 9 * maxN * D, 3 * maxN * D, 36 * maxN * D, 36 * maxN * D, 6 * maxN * D,
+                                   6 * maxN * D, maxN * D, maxN * D, maxN * D, maxN * D, maxN * I, maxN * I, (maxN + 1) * I, maxN * I};
   size_t at = 0;
   for (int k = 0; k < kPgArrays; ++k) {
     off[k] = at;
@@ -103,6 +130,10 @@ inline void pgo_bind(PgoGraph & g, char * base, const size_t off[kPgArrays])
   g.ea = ip(kPgEa), g.eb = ip(kPgEbI), g.eslot = ip(kPgSlot), g.inc_off = ip(kPgIncOff), g.inc = ip(kPgInc), g.far = ip(kPgFar);
   g.fixed = reinterpret_cast<unsigned char *>(base + off[kPgFixed]);
   g.st = reinterpret_cast<PgoState *>(base + off[kPgSt]);
+  g.w = dp(kPgW), g.rho = dp(kPgRho), g.lparam = dp(kPgLParam), g.lkind = ip(kPgLKind);
+  g.pZR = dp(kPgPZR), g.pZt = dp(kPgPZt), g.pOm = dp(kPgPOm), g.pH = dp(kPgPH), g.pg = dp(kPgPG), g.pres = dp(kPgPRes), g.pcz = dp(kPgPCz);
+  g.pw = dp(kPgPW), g.prho = dp(kPgPRho), g.plparam = dp(kPgPLParam), g.plkind = ip(kPgPLKind), g.ppose = ip(kPgPPose);
+  g.pinc_off = ip(kPgPIncOff), g.pinc = ip(kPgPInc);
 }
 
 // host: the index arrays of an edge list (ea, eb: E entries, 0 <= ea < eb < N) — every edge's far slot (-1: near), the far
@@ -132,6 +163,48 @@ inline int pgo_index_edges(int N, int E, const int * ea, const int * eb, int * e
   return F;
 }
 
+// host: per pose its priors in prior-list order (ppose: P entries, 0 <= ppose < N)
+inline void pgo_index_priors(int N, int P, const int * ppose, int * pinc_off, int * pinc)
+{
+  for (int i = 0; i <= N; ++i) pinc_off[i] = 0;
+  for (int p = 0; p < P; ++p) ++pinc_off[ppose[p] + 1];
+  for (int i = 0; i < N; ++i) pinc_off[i + 1] += pinc_off[i];
+  for (int p = 0; p < P; ++p) pinc[pinc_off[ppose[p]]++] = p;
+  for (int i = N; i > 0; --i) pinc_off[i] = pinc_off[i - 1];
+  pinc_off[0] = 0;
+}
+
+// ---- the loss of a term ------------------------------------------------------------------------------------------------------------
+// w and rho of a term whose chi^2 is s.  kind 0: w = 1, rho = s as it is.  Huber (k): w = 1, rho = s up to s = k^2, then
+// w = k / sqrt(s), rho = 2 k sqrt(s) - k^2.  Cauchy (k): w = 1 / (1 + s / k^2), rho = k^2 log(1 + s / k^2).  DCS (Phi):
+// c = min(1, 2 Phi / (Phi + s)), w = c^2, rho = c^2 s + Phi (1 - c)^2.  Kinds 1 .. 3 read an s that is not positive (zero; an
+// indefinite info) as 0, which keeps sqrt and log inside their domains; w is not below kPgoMinWeight.
+MH_HD void pgo_loss(int kind, double param, double s, double & w, double & rho)
+{
+  w = 1.0;
+  rho = s;
+  if (kind == kPgoLossNone) return;
+  const double sp = s > 0.0 ? s : 0.0;
+  if (kind == kPgoLossHuber) {
+    const double k2 = param * param;
+    rho = sp;
+    if (sp > k2) {
+      const double q = sqrt(sp);
+      w = param / q;
+      rho = 2.0 * param * q - k2;
+    }
+  } else if (kind == kPgoLossCauchy) {
+    const double k2 = param * param, u = 1.0 + sp / k2;
+    w = 1.0 / u;
+    rho = k2 * log(u);
+  } else {
+    const double c0 = 2.0 * param / (param + sp), c = c0 < 1.0 ? c0 : 1.0;
+    w = c * c;
+    rho = w * sp + param * ((1.0 - c) * (1.0 - c));
+  }
+  if (w < kPgoMinWeight) w = kPgoMinWeight;
+}
+
 // ---- per edge --------------------------------------------------------------------------------------------------------------------
 // Edge e at the current poses.  A far edge also leaves J_a = -Ad(T_ab^-1) in its slot; want_res: the residual itself into g.res.
 MH_HD void pgo_edge(const PgoGraph & g, int e, bool want_res)
@@ -139,6 +212,7 @@ MH_HD void pgo_edge(const PgoGraph & g, int e, bool want_res)
   const int a = g.ea[e], b = g.eb[e], f = g.eslot[e];
   const double *Ra = g.R + 9 * a, *ta = g.t + 3 * a, *Rb = g.R + 9 * b, *tb = g.t + 3 * b;
   window_between_dense(Ra, ta, Rb, tb, g.ZR + 9 * e, g.Zt + 3 * e, g.Om + 36 * e, g.Baa + 36 * e, g.Eba + 36 * e, g.ga + 6 * e, g.gb + 6 * e, g.cz[e]);
+  pgo_loss(g.lkind[e], g.lparam[e], g.cz[e], g.w[e], g.rho[e]);
   if (f < 0 && !want_res) return;
   double Rat[9], abR[9], abt[3];
   win_tr(Ra, Rat);
@@ -163,15 +237,39 @@ MH_HD void pgo_edge(const PgoGraph & g, int e, bool want_res)
   }
 }
 
+// ---- per prior --------------------------------------------------------------------------------------------------------------------
+// Prior p at the current pose of its keyframe: the model (Om, 0, 0) around Z seen from the offset d (window_transport).
+MH_HD void pgo_prior(const PgoGraph & g, int p)
+{
+  const int i = g.ppose[p];
+  const double zero[6] = {0, 0, 0, 0, 0, 0};
+  double d[6], tmp[36];
+  window_local(g.pZR + 9 * p, g.pZt + 3 * p, g.R + 9 * i, g.t + 3 * i, d);
+  window_transport(g.pOm + 36 * p, zero, 0.0, d, g.pH + 36 * p, g.pg + 6 * p, g.pcz[p], tmp);
+  for (int q = 0; q < 6; ++q) g.pres[6 * p + q] = d[q];
+  pgo_loss(g.plkind[p], g.plparam[p], g.pcz[p], g.pw[p], g.prho[p]);
+}
+// term j of the edge pass: an edge, or prior j - E
+MH_HD void pgo_term(const PgoGraph & g, int j, bool want_res)
+{
+  if (j < g.E)
+    pgo_edge(g, j, want_res);
+  else
+    pgo_prior(g, j - g.E);
+}
+
 // ---- per pose: T and the right-hand side ----------------------------------------------------------------------------------------
 // Output l % kPgoGather of pose l / kPgoGather, each sum over the pose's incidence list in edge-list order.  A fixed pose: the
 // identity block, no off-diagonal block on either side, a zero right-hand side.  Far edges go into the right-hand side only.
+// Every entry read is multiplied by its term's weight; the pose's priors follow its edges.
 MH_HD void pgo_gather(const PgoGraph & g, const PgoParams & p, int l)
 {
   const int i = l / kPgoGather, q = l % kPgoGather;
   const bool fx = g.fixed[i] != 0;
   const int * inc = g.inc + g.inc_off[i];
   const int n = g.inc_off[i + 1] - g.inc_off[i];
+  const int * pinc = g.pinc + (g.P > 0 ? g.pinc_off[i] : 0);
+  const int np = g.P > 0 ? g.pinc_off[i + 1] - g.pinc_off[i] : 0;
   if (q < 36) {
     double a = 0.0;
     if (fx) {
@@ -180,8 +278,9 @@ MH_HD void pgo_gather(const PgoGraph & g, const PgoParams & p, int l)
       for (int k = 0; k < n; ++k) {
         const int e = inc[k] >> 1;
         if (g.eslot[e] >= 0) continue;
-        a += (inc[k] & 1) ? g.Om[36 * e + q] : g.Baa[36 * e + q];
+        a += g.w[e] * ((inc[k] & 1) ? g.Om[36 * e + q] : g.Baa[36 * e + q]);
       }
+      for (int k = 0; k < np; ++k) a += g.pw[pinc[k]] * g.pH[36 * pinc[k] + q];
       if (q / 6 == q % 6) a += p.damping;
     }
     g.A[36 * i + q] = a;
@@ -191,25 +290,30 @@ MH_HD void pgo_gather(const PgoGraph & g, const PgoParams & p, int l)
     if (!fx && i > 0 && !g.fixed[i - 1])
       for (int k = 0; k < n; ++k) {
         const int e = inc[k] >> 1;
-        if ((inc[k] & 1) && g.eslot[e] < 0) a += g.Eba[36 * e + c];
+        if ((inc[k] & 1) && g.eslot[e] < 0) a += g.w[e] * g.Eba[36 * e + c];
       }
     g.Eb[36 * i + c] = a;
   } else {
     const int r = q - 72;
     double s = 0.0;
-    if (!fx)
+    if (!fx) {
       for (int k = 0; k < n; ++k) {
         const int e = inc[k] >> 1;
-        s += (inc[k] & 1) ? g.gb[6 * e + r] : g.ga[6 * e + r];
+        s += g.w[e] * ((inc[k] & 1) ? g.gb[6 * e + r] : g.ga[6 * e + r]);
       }
+      for (int k = 0; k < np; ++k) s += g.pw[pinc[k]] * g.pg[6 * pinc[k] + r];
+    }
     g.rhs[6 * i + r] = fx ? 0.0 : -s;
   }
 }
 
-// ---- per far edge: Om = L D L^T and Om^-1 -----------------------------------------------------------------------------------------
+// ---- per far edge: w Om = L D L^T and (w Om)^-1 -----------------------------------------------------------------------------------
 MH_HD bool pgo_far_info(const PgoGraph & g, int f)
 {
-  const double * S = g.Om + 36 * g.far[f];
+  const double * Sf = g.Om + 36 * g.far[f];
+  const double wf = g.w[g.far[f]];
+  double S[36];
+  for (int q = 0; q < 36; ++q) S[q] = wf * Sf[q];
   double *L = g.OmL + 36 * f, *D = g.OmD + 6 * f;
   for (int q = 0; q < 36; ++q) L[q] = 0.0;
   for (int j = 0; j < 6; ++j) {
@@ -399,8 +503,8 @@ MH_HD void pgo_apply_row(const PgoGraph & g, const double * y, int stride, bool 
   g.x[row] = first ? s : g.x[row] + s;
 }
 
-// entry `row` of g.r = rhs - A x against the system as assembled (T's blocks, then the pose's far edges in list order), in
-// twice the working precision as the window chains take it.  The row of a fixed pose is zero.
+// entry `row` of g.r = rhs - A x against the system as assembled (T's blocks, then the pose's far edges in list order, each
+// entry times the edge's weight), in twice the working precision as the window chains take it.  The row of a fixed pose is zero.
 MH_HD void pgo_residual_row(const PgoGraph & g, int row)
 {
   const int i = row / 6, r = row % 6;
@@ -426,14 +530,15 @@ MH_HD void pgo_residual_row(const PgoGraph & g, int row)
     const int e = inc[k] >> 1;
     if (g.eslot[e] < 0) continue;
     const int a = g.ea[e], b = g.eb[e];
+    const double we = g.w[e];
     if (inc[k] & 1) {
       if (!g.fixed[a])
-        for (int m = 0; m < 6; ++m) term(g.Eba[36 * e + 6 * r + m], g.x[6 * a + m]);
-      for (int m = 0; m < 6; ++m) term(g.Om[36 * e + 6 * r + m], g.x[6 * b + m]);
+        for (int m = 0; m < 6; ++m) term(we * g.Eba[36 * e + 6 * r + m], g.x[6 * a + m]);
+      for (int m = 0; m < 6; ++m) term(we * g.Om[36 * e + 6 * r + m], g.x[6 * b + m]);
     } else {
-      for (int m = 0; m < 6; ++m) term(g.Baa[36 * e + 6 * r + m], g.x[6 * a + m]);
+      for (int m = 0; m < 6; ++m) term(we * g.Baa[36 * e + 6 * r + m], g.x[6 * a + m]);
       if (!g.fixed[b])
-        for (int m = 0; m < 6; ++m) term(g.Eba[36 * e + 6 * m + r], g.x[6 * b + m]);
+        for (int m = 0; m < 6; ++m) term(we * g.Eba[36 * e + 6 * m + r], g.x[6 * b + m]);
     }
   }
   g.r[row] = hi + lo;
@@ -453,13 +558,13 @@ MH_HD void pgo_small(const PgoGraph & g, int stage, Par & par)
     pgo_solve_C(g, g.y1, 1, par);
   }
 }
-// the cost in its fixed order into g.fold[0 .. kPgoFold), its total into *f
+// the cost (rho of the terms, edges then priors) in its fixed order into g.fold[0 .. kPgoFold), its total into *f
 template <typename Par>
 MH_HD void pgo_cost(const PgoGraph & g, double * f, Par & par)
 {
   par.each(kPgoFold, [&](int l) {
     double s = 0.0;
-    for (int e = l; e < g.E; e += kPgoFold) s += g.cz[e];
+    for (int e = l; e < g.E + g.P; e += kPgoFold) s += e < g.E ? g.rho[e] : g.prho[e - g.E];
     g.fold[l] = s;
   });
   par.each(1, [&](int) {
@@ -531,7 +636,7 @@ inline int pgo_iterate_host(const PgoGraph & g, const PgoParams & p, int it, dou
 {
   WindowSerial par;
   if (g.st->stopped) return 1;
-  for (int e = 0; e < g.E; ++e) pgo_edge(g, e, false);
+  for (int j = 0; j < g.E + g.P; ++j) pgo_term(g, j, false);
   for (int l = 0; l < kPgoGather * g.N; ++l) pgo_gather(g, p, l);
   g.st->ok = 1;
   for (int f = 0; f < g.F; ++f)

@@ -1,7 +1,8 @@
 // The kernels of an mh_pose_graph_optimise chain (pose_graph_api.hip); the arithmetic is pose_graph_device.hpp.  One iteration
 // is a fixed run of launches on the context's stream, each phase that needs ALL of the phase before it a launch of its own (no
 // rendezvous between workgroups inside a kernel):
-//   pgo_edge_kernel      one lane per edge: window_between_dense into per-edge rows; J_a of a far edge
+//   pgo_edge_kernel      one lane per term: an edge (window_between_dense into per-edge rows; J_a of a far edge) or, behind the
+//                        edges, a prior (window_local, window_transport into per-prior rows); its weight and cost (pgo_loss)
 //   pgo_gather_kernel    one lane per output of a pose (78): T's blocks and the right-hand side from the incidence list
 //   pgo_factor_kernel    one wave: Om_f = L D L^T and Om_f^-1 per far edge, then T's block L D L^T, N dependent 6 x 6 steps
 //   pgo_sweep_kernel     one lane per column of [W^T | rhs] (6 F + 1), forward and back over the N blocks
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(kPgoLanes) void pgo_edge_kernel(const PgoGraph g, c
 {
   if (g.st->stopped) return;
   const int e = static_cast<int>(blockIdx.x) * kPgoLanes + static_cast<int>(threadIdx.x);
-  if (e < g.E) pgo_edge(g, e, want_res != 0);
+  if (e < g.E + g.P) pgo_term(g, e, want_res != 0);
 }
 
 __global__ __launch_bounds__(kPgoLanes) void pgo_gather_kernel(const PgoGraph g, const PgoParams p)
@@ -118,30 +119,37 @@ __global__ __launch_bounds__(kPgoLanes) void pgo_finish_kernel(const PgoGraph g,
   if (lane == 0) ll_store(word, static_cast<double>(g.rows[it].flags), seq);
 }
 
-// mh_pose_graph_residuals: the cost of the edges pgo_edge_kernel evaluated, into rows[0].f
-__global__ __launch_bounds__(kPgoLanes) void pgo_cost_kernel(const PgoGraph g)
+// the cost of the terms pgo_edge_kernel evaluated, into rows[0].f.  chi2 != 0 (mh_pose_graph_residuals): the sum of the edges'
+// chi^2 instead, whatever their losses
+__global__ __launch_bounds__(kPgoLanes) void pgo_cost_kernel(const PgoGraph g, const int chi2)
 {
   PgoGroup<kPgoLanes> par{static_cast<int>(threadIdx.x)};
-  pgo_cost(g, &g.rows[0].f, par);
+  PgoGraph h = g;
+  if (chi2) {
+    h.rho = g.cz;
+    h.P = 0;
+  }
+  pgo_cost(h, &g.rows[0].f, par);
 }
 
 hipError_t launch_pgo_edges(const PgoGraph & g, bool want_res, hipStream_t stream)
 {
-  if (g.E < 1 || g.E > kPgoMaxEdges) return g.E == 0 ? hipSuccess : hipErrorInvalidValue;
-  hipLaunchKernelGGL(pgo_edge_kernel, dim3((g.E + kPgoLanes - 1) / kPgoLanes), dim3(kPgoLanes), 0, stream, g, want_res ? 1 : 0);
+  if (g.E < 0 || g.E > kPgoMaxEdges || g.P < 0 || g.P > kPgoMaxPoses) return hipErrorInvalidValue;
+  if (g.E + g.P == 0) return hipSuccess;
+  hipLaunchKernelGGL(pgo_edge_kernel, dim3((g.E + g.P + kPgoLanes - 1) / kPgoLanes), dim3(kPgoLanes), 0, stream, g, want_res ? 1 : 0);
   return hipGetLastError();
 }
 
-hipError_t launch_pgo_cost(const PgoGraph & g, hipStream_t stream)
+hipError_t launch_pgo_cost(const PgoGraph & g, bool chi2, hipStream_t stream)
 {
-  hipLaunchKernelGGL(pgo_cost_kernel, dim3(1), dim3(kPgoLanes), 0, stream, g);
+  hipLaunchKernelGGL(pgo_cost_kernel, dim3(1), dim3(kPgoLanes), 0, stream, g, chi2 ? 1 : 0);
   return hipGetLastError();
 }
 
 // one iteration behind whatever is on the stream
 hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream)
 {
-  if (g.N < 1 || g.N > kPgoMaxPoses || g.E < 0 || g.E > kPgoMaxEdges || g.F < 0 || g.F > kPgoFarMax || g.K != 6 * g.F + 1 || it < 0 || it >= kPgoMaxIters)
+  if (g.N < 1 || g.N > kPgoMaxPoses || g.E < 0 || g.E > kPgoMaxEdges || g.P < 0 || g.P > kPgoMaxPoses || g.F < 0 || g.F > kPgoFarMax || g.K != 6 * g.F + 1 || it < 0 || it >= kPgoMaxIters)
     return hipErrorInvalidValue;
   hipError_t e = launch_pgo_edges(g, false, stream);
   if (e != hipSuccess) return e;

@@ -723,6 +723,26 @@ inline mh_window_edge poseGraphEdge(int32_t pose_a, int32_t pose_b, const PoseRM
   return e;
 }
 
+// a prior on keyframe `pose`: the measured pose Z (world from keyframe) and its information in (rotation, translation) order
+inline mh_pose_prior posePrior(int32_t pose, const Pose3 & Z, const gtsam::Matrix6 & info)
+{
+  mh_pose_prior p{};
+  const PoseRM z = rowMajor(Z);
+  p.pose = pose;
+  std::copy(z.R.begin(), z.R.end(), p.Z_R);
+  std::copy(z.t.begin(), z.t.end(), p.Z_t);
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) p.info[6 * r + c] = info(r, c);
+  return p;
+}
+inline mh_pose_graph_loss poseGraphLoss(int32_t kind, double param)
+{
+  mh_pose_graph_loss l{};
+  l.kind = kind;
+  l.param = param;
+  return l;
+}
+
 class PoseGraph
 {
 public:
@@ -734,7 +754,7 @@ public:
   PoseGraph(const PoseGraph &) = delete;
   PoseGraph & operator=(const PoseGraph &) = delete;
 
-  // another count than before drops the edges and the fixed flags
+  // another count than before drops the edges, the fixed flags, the priors and the losses
   void setPoses(const std::vector<PoseRM> & poses)
   {
     std::vector<double> R(9 * poses.size()), t(3 * poses.size());
@@ -743,7 +763,7 @@ public:
       std::copy(poses[i].t.begin(), poses[i].t.end(), t.begin() + static_cast<std::ptrdiff_t>(3 * i));
     }
     ctx_->check(mh_pose_graph_set_poses(pg_, R.data(), t.data(), poses.size()), "mh_pose_graph_set_poses");
-    if (poses.size() != n_) n_edges_ = 0;
+    if (poses.size() != n_) n_edges_ = n_priors_ = 0;
     n_ = poses.size();
   }
   // one flag per pose; empty: no pose is fixed
@@ -756,6 +776,37 @@ public:
   {
     ctx_->check(mh_pose_graph_set_edges(pg_, edges.empty() ? nullptr : edges.data(), edges.size()), "mh_pose_graph_set_edges");
     n_edges_ = edges.size();
+  }
+  // replaces the prior list (and drops the priors' losses)
+  void setPriors(const std::vector<mh_pose_prior> & priors)
+  {
+    ctx_->check(mh_pose_graph_set_priors(pg_, priors.empty() ? nullptr : priors.data(), priors.size()), "mh_pose_graph_set_priors");
+    n_priors_ = priors.size();
+  }
+  // one loss per edge and one per prior, each in list order; an empty vector: no loss on any of them
+  void setLoss(const std::vector<mh_pose_graph_loss> & edges, const std::vector<mh_pose_graph_loss> & priors = {})
+  {
+    if (!edges.empty() && edges.size() != n_edges_) throw std::runtime_error("PoseGraph::setLoss: one loss per edge");
+    if (!priors.empty() && priors.size() != n_priors_) throw std::runtime_error("PoseGraph::setLoss: one loss per prior");
+    ctx_->check(mh_pose_graph_set_loss(pg_, edges.empty() ? nullptr : edges.data(), priors.empty() ? nullptr : priors.data()), "mh_pose_graph_set_loss");
+  }
+  // every prior at the stored poses: d (6 per prior) and chi2 = d^T Om d, each optional.  Nothing moves.
+  void priorResiduals(std::vector<double> * d, std::vector<double> * chi2 = nullptr)
+  {
+    if (d) d->resize(6 * n_priors_);
+    if (chi2) chi2->resize(n_priors_);
+    ctx_->check(mh_pose_graph_prior_residuals(pg_, d && n_priors_ ? d->data() : nullptr, chi2 && n_priors_ ? chi2->data() : nullptr),
+                "mh_pose_graph_prior_residuals");
+  }
+  // the sum of rho at the stored poses; the weight of every edge and of every prior (each optional).  Nothing moves.
+  double weights(std::vector<double> * w_edges = nullptr, std::vector<double> * w_priors = nullptr)
+  {
+    double f = 0.0;
+    if (w_edges) w_edges->resize(n_edges_);
+    if (w_priors) w_priors->resize(n_priors_);
+    ctx_->check(mh_pose_graph_weights(pg_, w_edges && n_edges_ ? w_edges->data() : nullptr, w_priors && n_priors_ ? w_priors->data() : nullptr, &f),
+                "mh_pose_graph_weights");
+    return f;
   }
   std::vector<PoseRM> poses()
   {
@@ -793,7 +844,7 @@ public:
 private:
   std::shared_ptr<Context> ctx_;  // (declared first: the graph goes before its context)
   mh_pose_graph * pg_ = nullptr;
-  size_t n_ = 0, n_edges_ = 0;
+  size_t n_ = 0, n_edges_ = 0, n_priors_ = 0;
 };
 
 // The GaussianFactor ICPFactor::linearize returns: gtsam::HessianFactor(keys()[0], H, -b, f) (geometric_factor.hpp:559-560),
