@@ -283,9 +283,10 @@ MH_HD int align_advance(AlignState & st, const double * sums, bool have_sums, co
 
 namespace mh
 {
-// align_kernels.hip — one step of an mh_icp_align chain, launched behind the K3 (staged batch form, one factor, tail = 1) whose
-// flagged words landed in ll_dev.  `next`: the argument block of the K3 launch queued behind this step (device memory the
-// factor owns; null behind the last launch of the call): the step writes R, t there, and n = 0 once the chain has stopped.
+// align_kernels.hip — one member's step of an alignment chain (mh_icp_align, mh_icp_align_batch), launched behind the K3
+// (staged batch form, tail = 1) whose flagged words landed in ll_dev.  `next`: the member's argument block of the K3 launch
+// queued behind this step (in the chain's device block; null behind the last launch of the call): the step writes R, t there,
+// and n = 0 once the member has stopped.
 struct AlignStepArgs
 {
   const uint4 * ll_dev;  // K3's 28 sums + 4 counters of this iteration (device memory)
@@ -295,16 +296,16 @@ struct AlignStepArgs
   AlignParams p;
   unsigned int seq;      // tags K3's words and everything this step publishes
 };
-hipError_t launch_align_step(const AlignStepArgs & a, hipStream_t stream);
 
-// align_kernels.hip — one step of an mh_icp_align_batch chain: workgroup m is the step above for member m, on m[m] alone.  The
-// members' arguments travel in the kernel-argument segment.
+// align_kernels.hip — one step of a chain of n_members: one member runs icp_align_step_kernel on m[0]; several run
+// icp_align_batch_step_kernel, whose workgroup m is the same step for member m, on m[m] alone.  Either way the arguments travel
+// in the kernel-argument segment.
 constexpr int kAlignBatchMax = 16;
 struct AlignBatchStepArgs
 {
   AlignStepArgs m[kAlignBatchMax];
 };
 static_assert(sizeof(AlignBatchStepArgs) <= 3072, "mh_icp_align_batch: the step's arguments ride in the kernel-argument segment");
-hipError_t launch_align_batch_step(const AlignBatchStepArgs & a, int n_members, hipStream_t stream);
+hipError_t launch_align_chain_step(const AlignBatchStepArgs & a, int n_members, hipStream_t stream);
 }  // namespace mh
 #endif

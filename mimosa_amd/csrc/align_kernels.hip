@@ -1,6 +1,6 @@
-// icp_align_step_kernel: the link between two K3 launches of an mh_icp_align chain (chain_api.hip).  One workgroup of one wave,
-// launched behind each K3 (batch form, tail = 1: its last workgroup folds the rows and publishes the 28 sums + 4 counters as
-// flagged words — here into a device-resident slot).  The step turns the sums into the next pose (align_device.hpp), writes it
+// icp_align_step_kernel: the link between two K3 launches of an alignment chain with one member (chain_api.hip: mh_icp_align,
+// a one-member mh_icp_align_batch).  One workgroup of one wave, launched behind each K3 (batch form, tail = 1: its last workgroup
+// folds the rows and publishes the 28 sums + 4 counters as flagged words — here into a device-resident slot).  The step turns the sums into the next pose (align_device.hpp), writes it
 // into the argument block of the K3 launch queued behind it, and publishes the iteration's sums and its trace row to the
 // call's slot in mapped pinned memory, every double as one self-validating 16-byte store.
 //
@@ -8,8 +8,8 @@
 // dependent chains of the step), lane 0 solves and retracts, lanes 0..31 forward the words.  Everything is fp64; the file is
 // compiled without floating-point contraction so that the host build of align_device.hpp gives the same digits.
 //
-// icp_align_batch_step_kernel: the same step for the B members of an mh_icp_align_batch chain in one launch, one one-wave
-// workgroup per member.  The members share nothing — no barrier across workgroups, no atomics: workgroup m reads and writes
+// icp_align_batch_step_kernel: the same step for the members of a chain with several in one launch, one one-wave workgroup
+// per member.  The members share nothing — no barrier across workgroups, no atomics: workgroup m reads and writes
 // what member m's arguments point at.
 #include <hip/hip_runtime.h>
 
@@ -70,19 +70,16 @@ __global__ __launch_bounds__(64) void icp_align_batch_step_kernel(const AlignBat
   __shared__ double s_sum[32];
   __shared__ double s_row[kRowWords];
   __shared__ int s_stop;
-  align_step_wave(b.m[blockIdx.x], s_sum, s_row, &s_stop);  // (the grid is the number of members: launch_align_batch_step)
+  align_step_wave(b.m[blockIdx.x], s_sum, s_row, &s_stop);  // (the grid is the number of members: launch_align_chain_step)
 }
 
-hipError_t launch_align_step(const AlignStepArgs & a, hipStream_t stream)
-{
-  hipLaunchKernelGGL(icp_align_step_kernel, dim3(1), dim3(64), 0, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_align_batch_step(const AlignBatchStepArgs & a, int n_members, hipStream_t stream)
+hipError_t launch_align_chain_step(const AlignBatchStepArgs & a, int n_members, hipStream_t stream)
 {
   if (n_members < 1 || n_members > kAlignBatchMax) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(icp_align_batch_step_kernel, dim3(n_members), dim3(64), 0, stream, a);
+  if (n_members == 1)  // (the small kernel-argument segment of one member's arguments)
+    hipLaunchKernelGGL(icp_align_step_kernel, dim3(1), dim3(64), 0, stream, a.m[0]);
+  else
+    hipLaunchKernelGGL(icp_align_batch_step_kernel, dim3(n_members), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -5,10 +5,13 @@
 // (align_kernels.hip, window_kernels.hip, window_relin_kernels.hip, window_lin_kernels.hip, window_edge_kernels.hip,
 // window_joint_kernels.hip; window_marginal_kernels.hip and window_joint_kernels.hip for the marginals),
 // K3, step ... on the context's stream with one wait at its
-// end; every step publishes a row of flagged words the host reads.  What the two families share is written once at the top;
-// argument checks, staging layout, the step launch and the decoding of a row are each family's own.  The factor handle,
-// linearize and the flagged words of a call live in mh_api.hip (mh_internal.hpp: mhi); what a window entry point was given
-// and the checks of it that need no device in window_request.hpp.
+// end; every step publishes a row of flagged words the host reads.  There are two families: the alignment chains (mh_icp_align
+// is the chain of one member on the factor's own record and storage, mh_icp_align_batch the chain of up to 16 on the context's:
+// one record, one layout, one driver) and the window calls.  What the two share is written once at the top; staging layout,
+// the step launch and the decoding of a row are each family's own, argument checks each entry point's.  A factor in a chain is
+// held (mh_internal.hpp: hold / let_go) until the chain is collected or abandoned.  The factor handle, linearize and the
+// flagged words of a call live in mh_api.hip (mh_internal.hpp: mhi); what a window entry point was given and the checks of it
+// that need no device in window_request.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,15 +20,7 @@
 
 #include "mh_internal.hpp"
 
-// mh_icp_align's block of device memory (mh_icp::d_align) and the pinned staging of its first part (h_align, kAlignStageBytes
-// of mh_internal.hpp):
-// [grid prefix, 64 B | AlignState, 192 B | 64 argument blocks | 256 B that load_uniform may read past the last block |
-//  64 landing slots of 32 flagged words for K3's sums and counters]
-constexpr size_t kAlignLlAt = (kAlignStageBytes + 256 + 255) & ~size_t(255);
-constexpr size_t kAlignLlWords = 32;
-constexpr size_t kAlignBytes = kAlignLlAt + kAlignLlWords * sizeof(uint4) * kMaxPending;
-static_assert(sizeof(mh::AlignState) <= 192 && mh::kRowWords <= mh::kLlEig, "mh_icp_align layout");
-
+// (The block of an alignment chain, a function of its capacity, stands with its record: AlignChain in mh_internal.hpp.)
 // mh_icp_window_optimise's block of device memory (mh_ctx::d_window) and the pinned staging of its first part (h_window):
 // [grid prefixes, 256 B | WindowState | iters x n_slots argument blocks | 256 B that load_uniform may read past the last block |
 //  one landing slot of 32 flagged words per pose for K3's sums and counters (every iteration's words carry its own number) |
@@ -139,7 +134,7 @@ static Refusal chain_check_factors(const mh_ctx * ctx, mh_icp * const * icps, si
     if (c->ctx != ctx) return {MH_ERR_INVALID_ARG, w.contexts};
     if (c->binary) return {MH_ERR_UNSUPPORTED, w.unary};
     if (c->no_order || c->cap_n > c->n) return {MH_ERR_UNSUPPORTED, w.sharded};
-    if (c->n_pending || c->align.active || c->in_window || c->in_align_batch) return {MH_ERR_INVALID_ARG, w.in_flight};
+    if (c->n_pending) return {MH_ERR_INVALID_ARG, w.in_flight};
     if (w.empty && c->n == 0) return {MH_ERR_INVALID_ARG, w.empty};
     for (size_t g = 0; g < f; ++g)
       if (icps[g] == c) return {MH_ERR_INVALID_ARG, w.twice};
@@ -268,104 +263,111 @@ static bool chain_epilogue(const mh_icp * icp, int it, const double R_at[9], con
   return true;
 }
 
-// ---- scan-to-map alignment: K3, step, K3, step ... on the context's stream, one wait ---------------------------------------
-// The argument blocks of every iteration sit in device memory (d_align), filled here except R, t of the iterations after the
-// first, which the step kernel in front of each writes (align_kernels.hip).  K3 runs in the staged batch form with one factor
-// and the class a call of its own would get, tail = 1, its flagged words landing in a device slot; the step forwards them and
-// its own row to the iteration's slot of the factor's pinned ring.
-static ChainRows align_rows(const mh_icp * icp) { return {icp->h_ll + mh::kLlSums, icp->ll_words, mh::kRowWords, icp->align.seq}; }
+// ---- alignment chains: [K3 batch launches, one step launch] x iters on the context's stream, one wait ----------------------
+// mh_icp_align is the chain of one member on the factor's own record and storage, mh_icp_align_batch the chain of up to
+// MH_ALIGN_BATCH_MAX members on the context's (AlignChain, mh_internal.hpp); one driver serves both.  The argument blocks of
+// every iteration sit in the chain's device block, filled here except R, t of the iterations after the first, which the step in
+// front of each writes (align_kernels.hip).  K3 runs as in a window call (staged batch form, one launch per launch group, tail =
+// 1 — for one member the class a call of its own would get), its flagged words landing in the member's device slot; the step
+// launch has one workgroup per member, which forwards that member's words and its own row to the iteration's slot of the
+// member's pinned ring.  So a member of a batch is collected like a call of its own (align_collect).
+static mh_ctx * batch_ctx(mh_icp * const * icps, size_t B) { return (icps && B && icps[0]) ? icps[0]->ctx : nullptr; }
 
-static void align_abandon(mh_icp * icp)
+static void align_abandon(AlignChain & c)
 {
-  (void)hipStreamSynchronize(icp->ctx->stream);
-  icp->align.active = false;
-  icp->n_pending = 0;
+  (void)hipStreamSynchronize(c.icps[0]->ctx->stream);
+  let_go(c.icps, c.n);
+  c.n = 0;
 }
 
-static int align_begin(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
-                       mh_icp_align_result * out)
+// What mh_icp_align refuses of a config, for every entry point that takes one (each words the two messages with its own prefix).
+int mhi::align_check_config(const mh_ctx * ctx, const mh_icp_align_config & cfg, const char * iters_prefix, const char * ranges_prefix)
 {
-  if (!icp || !R0 || !t0 || !g_unit || !cfg || !out) return fail(icp ? icp->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_align: NULL argument");
-  mh_ctx * ctx = icp->ctx;
-  if (icp->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align: unary factors only");
-  if (icp->n_pending || icp->align.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: the factor has calls in flight");
-  if (cfg->max_iters < 1 || cfg->max_iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: max_iters must be in 1..64");
-  if (!(cfg->eps_rot >= 0.0) || !(cfg->eps_trans >= 0.0) || !(cfg->damping >= 0.0) || !(cfg->prior_sigma_rot >= 0.0) ||
-      !(cfg->prior_sigma_trans >= 0.0) || cfg->check_every < 0)
-    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: eps, damping, prior sigmas and check_every must be >= 0");
-  if (icp->no_order || icp->cap_n > icp->n) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align: not for the factors of the map-sharded path");
-  if (icp->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: the factor has no points");
-  MH_HIP(ctx, mh_enter(ctx));
-  MH_HIP(ctx, icp->d_align.reserve(kAlignBytes, ctx->stream, false));
-  if (!icp->h_align) MH_HIP(ctx, AllocCache::alloc_pinned(&icp->h_align, kAlignStageBytes));
+  if (cfg.max_iters < 1 || cfg.max_iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, std::string(iters_prefix) + "max_iters must be in 1..64");
+  if (!(cfg.eps_rot >= 0.0) || !(cfg.eps_trans >= 0.0) || !(cfg.damping >= 0.0) || !(cfg.prior_sigma_rot >= 0.0) || !(cfg.prior_sigma_trans >= 0.0) ||
+      cfg.check_every < 0)
+    return fail(ctx, MH_ERR_INVALID_ARG, std::string(ranges_prefix) + "eps, damping, prior sigmas and check_every must be >= 0");
+  return MH_OK;
+}
 
-  char * h = static_cast<char *>(icp->h_align);
-  char * d = static_cast<char *>(icp->d_align.p);
-  mh::IcpArgs a;
-  const int rc = mhi::chain_k3_block(icp, R0, t0, g_unit, a);
-  if (rc != MH_OK) return rc;
-  a.ll = reinterpret_cast<uint4 *>(d + kAlignLlAt);
-
-  mh_icp::AlignCall & c = icp->align;
+// The call is staged and its members are held: the entry point `what` has checked its arguments and c.h, c.d are allocated
+// (the context is entered).  A failure half way returns with nothing held.
+static int align_begin(AlignChain & c, const char * what, Held as, mh_icp * const * icps, size_t B, const double * R0, const double * t0,
+                       const double g_unit[3], const mh_icp_align_config * cfg, mh_icp_align_result * out)
+{
+  mh_ctx * ctx = icps[0]->ctx;
+  const int iters = cfg->max_iters;
+  c.what = what;
   c.cfg = *cfg;
-  c.out = out;
-  std::memcpy(c.R0, R0, sizeof(c.R0));
-  for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
   c.queued = 0;
-  c.count0 = icp->linearize_count;
-  c.cold0 = icp->cold;
-  c.p = align_params(*cfg, icp, c.gz);
+  c.out = out;
+  for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
+  c.n_slots = chain_plan_launches(mhi::window_launch_groups(icps, B), c.slot, c.launches);  // as mh_icp_window_optimise lays the same factors out
 
-  const int ppw = mh::linearize_class(a.n, a.k, false);
-  int * start = reinterpret_cast<int *>(h);
-  start[0] = 0;
-  start[1] = mh::class_grid(a.n, ppw);
-  mh::AlignState st;
-  std::memset(&st, 0, sizeof(st));
-  std::memcpy(st.R, a.R, sizeof(st.R));
-  std::memcpy(st.t, a.t, sizeof(st.t));
-  std::memcpy(h + 64, &st, sizeof(st));
-  for (int i = 0; i < cfg->max_iters; ++i) c.seq[i] = mhi::next_call_seq();
-  chain_fill_blocks(a, c.cold0, cfg->max_iters, c.seq, reinterpret_cast<mh::IcpArgs *>(h + kAlignBlocksAt), 1, kAlignLlWords);
-  MH_HIP(ctx, hipMemcpyAsync(d, h, kAlignBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(cfg->max_iters), hipMemcpyHostToDevice, ctx->stream));
-  c.active = true;
-  icp->n_pending = kMaxPending;  // the chain holds the whole ring
+  char * h = static_cast<char *>(c.h);
+  char * d = static_cast<char *>(c.d);
+  auto * blocks = reinterpret_cast<mh::IcpArgs *>(h + align_blocks_at(c.capacity));
+  for (int it = 0; it < iters; ++it) c.seq[it] = mhi::next_call_seq();
+  for (size_t m = 0; m < B; ++m) {
+    mh_icp * icp = icps[m];
+    c.icps[m] = icp;
+    c.count0[m] = icp->linearize_count;
+    std::memcpy(c.R0[m], R0 + 9 * m, sizeof(c.R0[m]));
+    mh::IcpArgs a;
+    const int rc = mhi::chain_k3_block(icp, R0 + 9 * m, t0 + 3 * m, g_unit, a);
+    if (rc != MH_OK) return rc;
+    a.ll = reinterpret_cast<uint4 *>(d + align_ll_at(c.capacity)) + kAlignLlWords * m;
+    mh::AlignState st;
+    std::memset(&st, 0, sizeof(st));
+    std::memcpy(st.R, a.R, sizeof(st.R));
+    std::memcpy(st.t, a.t, sizeof(st.t));
+    std::memcpy(h + kAlignStateAt + kAlignStateStride * m, &st, sizeof(st));
+    chain_fill_blocks(a, icp->cold, iters, c.seq, blocks + c.slot[m], static_cast<size_t>(c.n_slots), 0);
+    c.p[m] = align_params(*cfg, icp, c.gz);
+  }
+  chain_fill_prefix(reinterpret_cast<int *>(h), c.launches, blocks);
+  MH_HIP(ctx, hipMemcpyAsync(d, h, align_blocks_at(c.capacity) + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(iters),
+                             hipMemcpyHostToDevice, ctx->stream));
+  c.n = static_cast<int>(B);
+  for (size_t m = 0; m < B; ++m) hold(icps[m], as);
   return MH_OK;
 }
 
 // iterations [queued, upto) onto the stream
-static int align_enqueue(mh_icp * icp, int upto)
+static int align_enqueue(AlignChain & c, int upto)
 {
-  mh_ctx * ctx = icp->ctx;
-  mh_icp::AlignCall & c = icp->align;
-  char * d = static_cast<char *>(icp->d_align.p);
-  auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + kAlignBlocksAt);
-  const int n = static_cast<int>(icp->n), k = static_cast<int>(icp->cfg.num_corres_points);
-  const int ppw = mh::linearize_class(n, k, false), grid = mh::class_grid(n, ppw);
-  for (int i = c.queued; i < upto; ++i) {
-    hipError_t e = mh::launch_linearize_batch(blocks + i, reinterpret_cast<const int *>(d), 1, grid, ppw, k == 5 ? 5 : 8, icp->map->n_off, false, ctx->stream);
+  mh_ctx * ctx = c.icps[0]->ctx;
+  char * d = static_cast<char *>(c.d);
+  auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + align_blocks_at(c.capacity));
+  const int * prefix = reinterpret_cast<const int *>(d);
+  for (int it = c.queued; it < upto; ++it) {
+    hipError_t e = chain_launch_k3(c.launches, blocks + static_cast<size_t>(it) * c.n_slots, prefix, ctx->stream);
     if (e == hipSuccess) {
-      mh::AlignStepArgs s;
-      s.ll_dev = reinterpret_cast<const uint4 *>(d + kAlignLlAt) + static_cast<size_t>(i) * kAlignLlWords;
-      s.ll_host = icp->d_h_ll + static_cast<size_t>(i) * icp->ll_words;
-      s.next = i + 1 < c.cfg.max_iters ? blocks + i + 1 : nullptr;
-      s.state = reinterpret_cast<mh::AlignState *>(d + 64);
-      s.p = c.p;
-      s.seq = c.seq[i];
-      e = mh::launch_align_step(s, ctx->stream);
+      mh::AlignBatchStepArgs s;
+      std::memset(static_cast<void *>(&s), 0, sizeof(s));
+      for (int m = 0; m < c.n; ++m) {
+        mh::AlignStepArgs & a = s.m[m];
+        a.ll_dev = reinterpret_cast<const uint4 *>(d + align_ll_at(c.capacity)) + kAlignLlWords * m;
+        a.ll_host = c.icps[m]->d_h_ll + static_cast<size_t>(it) * c.icps[m]->ll_words;
+        a.next = it + 1 < c.cfg.max_iters ? blocks + static_cast<size_t>(it + 1) * c.n_slots + c.slot[m] : nullptr;
+        a.state = reinterpret_cast<mh::AlignState *>(d + kAlignStateAt + kAlignStateStride * m);
+        a.p = c.p[m];
+        a.seq = c.seq[it];
+      }
+      e = mh::launch_align_chain_step(s, c.n, ctx->stream);
     }
     if (e != hipSuccess) {
-      align_abandon(icp);
-      return hip_fail(ctx, e, "mh_icp_align: launch");
+      align_abandon(c);
+      return hip_fail(ctx, e, (std::string(c.what) + ": launch").c_str());
     }
-    c.queued = i + 1;
+    c.queued = it + 1;
   }
   return MH_OK;
 }
 
-// The result of one alignment whose queued iterations have run, for mh_icp_align and for a member of mh_icp_align_batch: the
-// factor's rows (tagged seq[i]) decoded into *out, first / last from the host epilogue.  lost: a row did not arrive or no
-// iteration was evaluated — the caller abandons its call; otherwise the caller moves the handle's books by out->iters.
+// The result of one member whose queued iterations have run: the factor's rows (tagged seq[i]) decoded into *out, first /
+// last from the host epilogue.  lost: a row did not arrive or no iteration was evaluated — the caller abandons its call;
+// otherwise the caller moves the handle's books by out->iters.
 static int align_collect(mh_icp * icp, const unsigned int * seq, int queued, const double R0[9], const double gz[3], int count0, mh_icp_align_result * out,
                          const char * what, bool & lost)
 {
@@ -401,193 +403,34 @@ static int align_collect(mh_icp * icp, const unsigned int * seq, int queued, con
   return rc_all;
 }
 
-// every queued iteration has run (the caller waited for the last row): the result, and the handle's books
-static int align_finish(mh_icp * icp)
-{
-  mh_icp::AlignCall & c = icp->align;
-  bool lost = false;
-  const int rc = align_collect(icp, c.seq, c.queued, c.R0, c.gz, c.count0, c.out, "mh_icp_align", lost);
-  if (lost) {
-    align_abandon(icp);
-    return rc;
-  }
-  icp->linearize_count = c.count0 + c.out->iters;
-  icp->cold = false;
-  icp->n_pending = 0;
-  c.active = false;
-  return rc;
-}
-
-static int align_run(mh_icp * icp, int chunk)
-{
-  return chain_drive(icp->align.queued, icp->align.cfg.max_iters, chunk, mh::kRowFlags, [icp](int upto) { return align_enqueue(icp, upto); },
-                     [icp](int i, double * row) { return chain_wait_row(icp->ctx, align_rows(icp), i, row, "mh_icp_align"); },
-                     [icp] { align_abandon(icp); }, [icp] { return align_finish(icp); });
-}
-
-int mhi::align_wait(mh_icp * icp)
-{
-  MH_HIP(icp->ctx, mh_enter(icp->ctx));
-  return align_run(icp, 0);
-}
-
-static int mh_icp_align_impl(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
-                             mh_icp_align_result * out, bool blocking)
-{
-  const int rc = align_begin(icp, R0, t0, g_unit, cfg, out);
-  if (rc != MH_OK) return rc;
-  if (!blocking) return align_enqueue(icp, cfg->max_iters);
-  return align_run(icp, cfg->check_every > 0 ? cfg->check_every : cfg->max_iters);
-}
-
-// ---- several alignments side by side: [K3 batch launches, one step launch] x iters, one wait ------------------------------
-// mh_icp_align_batch's block of device memory (mh_ctx::d_align_batch) and the pinned staging of its first part (h_align_batch):
-// [grid prefixes, 256 B | one AlignState per member | max_iters x n_slots argument blocks | 256 B that load_uniform may read
-//  past the last block | one landing slot of 32 flagged words per member for K3's sums and counters (every iteration's words
-//  carry its own number)]
-// K3 runs as in a window call (staged batch form, one launch per launch group, tail = 1); the step launch has one workgroup per
-// member, which forwards that member's words and row to the iteration's slot of the member's own pinned ring — where
-// mh_icp_align's arrive, so a member is collected like a call of its own (align_collect).
-constexpr size_t kABStateAt = 256;
-constexpr size_t kABStateStride = 192;
-constexpr size_t kABBlocksAt = kABStateAt + kABStateStride * MH_ALIGN_BATCH_MAX;
-constexpr size_t kABStageBytes = kABBlocksAt + sizeof(mh::IcpArgs) * MH_ALIGN_BATCH_MAX * kMaxPending;
-constexpr size_t kABLlAt = (kABStageBytes + 256 + 255) & ~size_t(255);
-constexpr size_t kABBytes = kABLlAt + 32 * sizeof(uint4) * MH_ALIGN_BATCH_MAX;
-static_assert(sizeof(mh::AlignState) <= kABStateStride && MH_ALIGN_BATCH_MAX == mh::kAlignBatchMax && kABBlocksAt % 256 == 0 &&
-                2 * MH_ALIGN_BATCH_MAX * sizeof(int) <= kABStateAt, "mh_icp_align_batch layout");
-
-static mh_ctx * batch_ctx(mh_icp * const * icps, size_t B) { return (icps && B && icps[0]) ? icps[0]->ctx : nullptr; }
-
-static void align_batch_abandon(mh_ctx * ctx)
-{
-  (void)hipStreamSynchronize(ctx->stream);
-  align_batch_release(ctx);
-}
-
-static int align_batch_begin(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3], const mh_icp_align_config * cfg,
-                             mh_icp_align_result * out)
-{
-  mh_ctx * ctx = batch_ctx(icps, B);
-  if (!icps || !R0 || !t0 || !g_unit || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: NULL argument");
-  if (B < 1 || B > static_cast<size_t>(MH_ALIGN_BATCH_MAX)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: B must be in 1..16");
-  for (size_t m = 0; m < B; ++m)
-    if (!icps[m]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: NULL member");
-  ctx = icps[0]->ctx;
-  if (ctx->align_batch.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: the context has a batch call in flight");
-  static constexpr FactorWords words{"mh_icp_align_batch: factors of different contexts", "mh_icp_align_batch: unary factors only",
-                                     "mh_icp_align_batch: not for the factors of the map-sharded path", "mh_icp_align_batch: a member has calls in flight",
-                                     "mh_icp_align_batch: a member has no points", "mh_icp_align_batch: the same factor twice"};
-  if (const Refusal no = chain_check_factors(ctx, icps, B, words)) return fail(ctx, no.code, no.message);
-  if (cfg->max_iters < 1 || cfg->max_iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: max_iters must be in 1..64");
-  if (!(cfg->eps_rot >= 0.0) || !(cfg->eps_trans >= 0.0) || !(cfg->damping >= 0.0) || !(cfg->prior_sigma_rot >= 0.0) ||
-      !(cfg->prior_sigma_trans >= 0.0) || cfg->check_every < 0)
-    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: eps, damping, prior sigmas and check_every must be >= 0");
-  MH_HIP(ctx, mh_enter(ctx));
-  if (!ctx->h_align_batch) MH_HIP(ctx, hipHostMalloc(&ctx->h_align_batch, kABStageBytes, hipHostMallocDefault));
-  if (!ctx->d_align_batch) MH_HIP(ctx, hipMalloc(&ctx->d_align_batch, kABBytes));
-
-  AlignBatchCall & c = ctx->align_batch;
-  const int iters = cfg->max_iters;
-  c.B = static_cast<int>(B);
-  c.cfg = *cfg;
-  c.queued = 0;
-  c.out = out;
-  for (int i = 0; i < 3; ++i) c.gz[i] = -g_unit[i];
-  c.n_slots = chain_plan_launches(mhi::window_launch_groups(icps, B), c.slot, c.launches);  // as mh_icp_window_optimise lays the same factors out
-
-  char * h = static_cast<char *>(ctx->h_align_batch);
-  char * d = static_cast<char *>(ctx->d_align_batch);
-  auto * blocks = reinterpret_cast<mh::IcpArgs *>(h + kABBlocksAt);
-  for (int it = 0; it < iters; ++it) c.seq[it] = mhi::next_call_seq();
-  for (size_t m = 0; m < B; ++m) {
-    mh_icp * icp = icps[m];
-    c.icps[m] = icp;
-    c.count0[m] = icp->linearize_count;
-    std::memcpy(c.R0[m], R0 + 9 * m, sizeof(c.R0[m]));
-    mh::IcpArgs a;
-    const int rc = mhi::chain_k3_block(icp, R0 + 9 * m, t0 + 3 * m, g_unit, a);
-    if (rc != MH_OK) return rc;
-    a.ll = reinterpret_cast<uint4 *>(d + kABLlAt) + 32 * m;
-    mh::AlignState st;
-    std::memset(&st, 0, sizeof(st));
-    std::memcpy(st.R, a.R, sizeof(st.R));
-    std::memcpy(st.t, a.t, sizeof(st.t));
-    std::memcpy(h + kABStateAt + kABStateStride * m, &st, sizeof(st));
-    chain_fill_blocks(a, icp->cold, iters, c.seq, blocks + c.slot[m], static_cast<size_t>(c.n_slots), 0);
-    c.p[m] = align_params(*cfg, icp, c.gz);
-  }
-  chain_fill_prefix(reinterpret_cast<int *>(h), c.launches, blocks);
-  MH_HIP(ctx, hipMemcpyAsync(d, h, kABBlocksAt + sizeof(mh::IcpArgs) * static_cast<size_t>(c.n_slots) * static_cast<size_t>(iters), hipMemcpyHostToDevice, ctx->stream));
-  c.active = true;
-  for (size_t m = 0; m < B; ++m) {
-    icps[m]->in_align_batch = true;
-    icps[m]->n_pending = kMaxPending;  // the chain holds the whole ring
-  }
-  return MH_OK;
-}
-
-// iterations [queued, upto) onto the stream
-static int align_batch_enqueue(mh_ctx * ctx, int upto)
-{
-  AlignBatchCall & c = ctx->align_batch;
-  char * d = static_cast<char *>(ctx->d_align_batch);
-  auto * blocks = reinterpret_cast<mh::IcpArgs *>(d + kABBlocksAt);
-  const int * prefix = reinterpret_cast<const int *>(d);
-  for (int it = c.queued; it < upto; ++it) {
-    hipError_t e = chain_launch_k3(c.launches, blocks + static_cast<size_t>(it) * c.n_slots, prefix, ctx->stream);
-    if (e == hipSuccess) {
-      mh::AlignBatchStepArgs s;
-      std::memset(static_cast<void *>(&s), 0, sizeof(s));
-      for (int m = 0; m < c.B; ++m) {
-        mh::AlignStepArgs & a = s.m[m];
-        a.ll_dev = reinterpret_cast<const uint4 *>(d + kABLlAt) + 32 * m;
-        a.ll_host = c.icps[m]->d_h_ll + static_cast<size_t>(it) * c.icps[m]->ll_words;
-        a.next = it + 1 < c.cfg.max_iters ? blocks + static_cast<size_t>(it + 1) * c.n_slots + c.slot[m] : nullptr;
-        a.state = reinterpret_cast<mh::AlignState *>(d + kABStateAt + kABStateStride * m);
-        a.p = c.p[m];
-        a.seq = c.seq[it];
-      }
-      e = mh::launch_align_batch_step(s, c.B, ctx->stream);
-    }
-    if (e != hipSuccess) {
-      align_batch_abandon(ctx);
-      return hip_fail(ctx, e, "mh_icp_align_batch: launch");
-    }
-    c.queued = it + 1;
-  }
-  return MH_OK;
-}
-
 // every queued iteration has run (the caller waited for every member's last row): the results, and the handles' books
-static int align_batch_finish(mh_ctx * ctx)
+static int align_finish(AlignChain & c)
 {
-  AlignBatchCall & c = ctx->align_batch;
   int rc_all = MH_OK;
-  for (int m = 0; m < c.B; ++m) {
+  for (int m = 0; m < c.n; ++m) {
     bool lost = false;
-    const int rc = align_collect(c.icps[m], c.seq, c.queued, c.R0[m], c.gz, c.count0[m], &c.out[m], "mh_icp_align_batch", lost);
+    const int rc = align_collect(c.icps[m], c.seq, c.queued, c.R0[m], c.gz, c.count0[m], &c.out[m], c.what, lost);
     if (lost) {  // the members collected so far keep their books; the call is over for all
-      align_batch_abandon(ctx);
+      align_abandon(c);
       return rc;
     }
     c.icps[m]->linearize_count = c.count0[m] + c.out[m].iters;
     c.icps[m]->cold = false;
     if (rc_all == MH_OK) rc_all = rc;
   }
-  align_batch_release(ctx);
+  let_go(c.icps, c.n);
+  c.n = 0;
   return rc_all;
 }
 
 // The row of iteration i as chain_drive looks at it: every member's row has arrived, and the stop bit is set when every
 // member's is.
-static int align_batch_wait_row(mh_ctx * ctx, int i, double * row)
+static int align_wait_row(const AlignChain & c, int i, double * row)
 {
-  const AlignBatchCall & c = ctx->align_batch;
   int all = 1;
-  for (int m = 0; m < c.B; ++m) {
+  for (int m = 0; m < c.n; ++m) {
     const mh_icp * icp = c.icps[m];
-    const int rc = chain_wait_row(ctx, ChainRows{icp->h_ll + mh::kLlSums, icp->ll_words, mh::kRowWords, c.seq}, i, row, "mh_icp_align_batch");
+    const int rc = chain_wait_row(icp->ctx, ChainRows{icp->h_ll + mh::kLlSums, icp->ll_words, mh::kRowWords, c.seq}, i, row, c.what);
     if (rc != MH_OK) return rc;
     all &= static_cast<int>(row[mh::kRowFlags]);
   }
@@ -595,20 +438,66 @@ static int align_batch_wait_row(mh_ctx * ctx, int i, double * row)
   return MH_OK;
 }
 
-static int align_batch_run(mh_ctx * ctx, int chunk)
+// the call after align_begin: everything queued and left in flight, or driven to its result
+static int align_run(AlignChain & c, int chunk)
 {
-  return chain_drive(ctx->align_batch.queued, ctx->align_batch.cfg.max_iters, chunk, mh::kRowFlags, [ctx](int upto) { return align_batch_enqueue(ctx, upto); },
-                     [ctx](int i, double * row) { return align_batch_wait_row(ctx, i, row); }, [ctx] { align_batch_abandon(ctx); },
-                     [ctx] { return align_batch_finish(ctx); });
+  return chain_drive(c.queued, c.cfg.max_iters, chunk, mh::kRowFlags, [&c](int upto) { return align_enqueue(c, upto); },
+                     [&c](int i, double * row) { return align_wait_row(c, i, row); }, [&c] { align_abandon(c); }, [&c] { return align_finish(c); });
+}
+
+static int align_start(AlignChain & c, bool blocking)
+{
+  const mh_icp_align_config & cfg = c.cfg;
+  if (!blocking) return align_enqueue(c, cfg.max_iters);
+  return align_run(c, cfg.check_every > 0 ? cfg.check_every : cfg.max_iters);
+}
+
+int mhi::align_wait(mh_icp * icp)
+{
+  MH_HIP(icp->ctx, mh_enter(icp->ctx));
+  return align_run(icp->align, 0);
+}
+
+static int mh_icp_align_impl(mh_icp * icp, const double R0[9], const double t0[3], const double g_unit[3], const mh_icp_align_config * cfg,
+                             mh_icp_align_result * out, bool blocking)
+{
+  if (!icp || !R0 || !t0 || !g_unit || !cfg || !out) return fail(icp ? icp->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_align: NULL argument");
+  mh_ctx * ctx = icp->ctx;
+  if (icp->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align: unary factors only");
+  if (icp->n_pending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: the factor has calls in flight");
+  if (const int rc = mhi::align_check_config(ctx, *cfg, "mh_icp_align: ", "mh_icp_align: ")) return rc;
+  if (icp->no_order || icp->cap_n > icp->n) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_align: not for the factors of the map-sharded path");
+  if (icp->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align: the factor has no points");
+  MH_HIP(ctx, mh_enter(ctx));
+  AlignChain & c = icp->align;
+  MH_HIP(ctx, icp->d_align.reserve(align_bytes(1), ctx->stream, false));
+  if (!c.h) MH_HIP(ctx, AllocCache::alloc_pinned(&c.h, align_stage_bytes(1)));
+  c.d = icp->d_align.p;
+  const int rc = align_begin(c, "mh_icp_align", Held::align, &icp, 1, R0, t0, g_unit, cfg, out);
+  return rc != MH_OK ? rc : align_start(c, blocking);
 }
 
 static int mh_icp_align_batch_impl(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3],
                                    const mh_icp_align_config * cfg, mh_icp_align_result * out, bool blocking)
 {
-  const int rc = align_batch_begin(icps, B, R0, t0, g_unit, cfg, out);
-  if (rc != MH_OK) return rc;
-  if (!blocking) return align_batch_enqueue(icps[0]->ctx, cfg->max_iters);
-  return align_batch_run(icps[0]->ctx, cfg->check_every > 0 ? cfg->check_every : cfg->max_iters);
+  mh_ctx * ctx = batch_ctx(icps, B);
+  if (!icps || !R0 || !t0 || !g_unit || !cfg || !out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: NULL argument");
+  if (B < 1 || B > static_cast<size_t>(MH_ALIGN_BATCH_MAX)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: B must be in 1..16");
+  for (size_t m = 0; m < B; ++m)
+    if (!icps[m]) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: NULL member");
+  ctx = icps[0]->ctx;
+  AlignChain & c = ctx->align_batch;
+  if (c.n) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch: the context has a batch call in flight");
+  static constexpr FactorWords words{"mh_icp_align_batch: factors of different contexts", "mh_icp_align_batch: unary factors only",
+                                     "mh_icp_align_batch: not for the factors of the map-sharded path", "mh_icp_align_batch: a member has calls in flight",
+                                     "mh_icp_align_batch: a member has no points", "mh_icp_align_batch: the same factor twice"};
+  if (const Refusal no = chain_check_factors(ctx, icps, B, words)) return fail(ctx, no.code, no.message);
+  if (const int rc = mhi::align_check_config(ctx, *cfg, "mh_icp_align_batch: ", "mh_icp_align_batch: ")) return rc;
+  MH_HIP(ctx, mh_enter(ctx));
+  if (!c.h) MH_HIP(ctx, hipHostMalloc(&c.h, align_stage_bytes(c.capacity), hipHostMallocDefault));
+  if (!c.d) MH_HIP(ctx, hipMalloc(&c.d, align_bytes(c.capacity)));
+  const int rc = align_begin(c, "mh_icp_align_batch", Held::align_batch, icps, B, R0, t0, g_unit, cfg, out);
+  return rc != MH_OK ? rc : align_start(c, blocking);
 }
 
 int mhi::align_batch(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3], const mh_icp_align_config * cfg,
@@ -620,9 +509,9 @@ int mhi::align_batch(mh_icp * const * icps, size_t B, const double * R0, const d
 static int mh_icp_align_batch_wait_impl(mh_ctx * ctx)
 {
   if (!ctx) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_align_batch_wait: ctx is NULL");
-  if (!ctx->align_batch.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch_wait: no batch call in flight");
+  if (!ctx->align_batch.n) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_align_batch_wait: no batch call in flight");
   MH_HIP(ctx, mh_enter(ctx));
-  return align_batch_run(ctx, 0);
+  return align_run(ctx->align_batch, 0);
 }
 
 // ---- fixed-lag window: [K3 batch launches, step] x iters on the context's stream, one wait --------------------------------
@@ -634,6 +523,13 @@ static ChainRows window_rows(const mh_ctx * ctx) { return {ctx->h_window_rows, k
 
 // the context of a window's factors (where a message goes: mh_last_error(ctx) as well as mh_last_error(NULL))
 static mh_ctx * window_ctx(mh_icp * const * icps, size_t W) { return (icps && W && icps[0]) ? icps[0]->ctx : nullptr; }
+
+// the window call on ctx is over (collected, or abandoned behind a drained stream): its factors are free again
+static void window_release(mh_ctx * ctx)
+{
+  let_go(ctx->window.icps, ctx->window.W);
+  ctx->window.active = false;
+}
 
 static void window_abandon(mh_ctx * ctx)
 {
@@ -847,10 +743,7 @@ static void window_claim(mh_ctx * ctx, const WindowRequest & q, const WindowChec
   }
   c.queued = 0;
   c.active = true;
-  for (size_t f = 0; f < q.W; ++f) {
-    q.icps[f]->in_window = true;
-    q.icps[f]->n_pending = kMaxPending;  // the chain holds the whole ring
-  }
+  for (size_t f = 0; f < q.W; ++f) hold(q.icps[f], Held::window);
 }
 
 static int window_begin(const WindowRequest & q)

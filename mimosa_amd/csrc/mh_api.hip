@@ -265,13 +265,13 @@ void mh_shutdown(mh_ctx * ctx)
   if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
   if (ctx->d_batch) (void)hipFree(ctx->d_batch);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-  if (ctx->window.active) window_release(ctx);  // (the stream has drained: a window call nobody waited for is abandoned, its factors are free)
+  if (ctx->window.active) let_go(ctx->window.icps, ctx->window.W);  // (the stream has drained: a window call nobody waited for is abandoned, its factors are free)
   if (ctx->h_window) (void)hipHostFree(ctx->h_window);
   if (ctx->d_window) (void)hipFree(ctx->d_window);
   if (ctx->h_window_rows) (void)hipHostFree(ctx->h_window_rows);
-  if (ctx->align_batch.active) align_batch_release(ctx);  // (likewise an mh_icp_align_batch call nobody waited for)
-  if (ctx->h_align_batch) (void)hipHostFree(ctx->h_align_batch);
-  if (ctx->d_align_batch) (void)hipFree(ctx->d_align_batch);
+  let_go(ctx->align_batch.icps, ctx->align_batch.n);  // (likewise the members of an mh_icp_align_batch call nobody waited for)
+  if (ctx->align_batch.h) (void)hipHostFree(ctx->align_batch.h);
+  if (ctx->align_batch.d) (void)hipFree(ctx->align_batch.d);
   if (ctx->copy_stream) {
     (void)hipStreamSynchronize(ctx->copy_stream);
     (void)hipStreamDestroy(ctx->copy_stream);
@@ -529,8 +529,13 @@ void mh_icp_destroy(mh_icp * icp)
   (void)hipStreamSynchronize(icp->ctx->stream);
   // a factor destroyed inside a window call nobody waited for: the stream has drained, the call is abandoned as a whole (its
   // books keep pointers to every factor of it)
-  if (icp->in_window && icp->ctx->window.active) window_release(icp->ctx);
-  if (icp->in_align_batch && icp->ctx->align_batch.active) align_batch_release(icp->ctx);  // (an mh_icp_align_batch call likewise)
+  if (icp->held == Held::window) {
+    let_go(icp->ctx->window.icps, icp->ctx->window.W);
+    icp->ctx->window.active = false;
+  } else if (icp->held == Held::align_batch) {
+    let_go(icp->ctx->align_batch.icps, icp->ctx->align_batch.n);
+    icp->ctx->align_batch.n = 0;
+  }
   icp->d_rec.release(true);
   icp->d_src.release(true);
   icp->d_qda.release(true);
@@ -547,7 +552,7 @@ void mh_icp_destroy(mh_icp * icp)
   if (icp->h_counts) (void)hipHostFree(icp->h_counts);
   if (icp->h_ll) AllocCache::free_pinned(icp->h_ll, icp->ll_words * sizeof(uint4) * kMaxPending);
   icp->d_align.release(true);
-  if (icp->h_align) AllocCache::free_pinned(icp->h_align, kAlignStageBytes);
+  if (icp->align.h) AllocCache::free_pinned(icp->align.h, align_stage_bytes(1));
   icp->d_reloc.release(true);
   if (icp->h_reloc) AllocCache::free_pinned(icp->h_reloc, icp->h_reloc_cap);
   if (icp->events_ready)
@@ -581,10 +586,13 @@ int mh_icp_timeline(mh_icp * icp, unsigned long long * out, size_t capacity_word
 static int mh_icp_reset_impl(mh_icp * icp)
 {
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_reset: icp is NULL");
-  if (icp->in_window) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: the factor is in a window call in flight");
-  if (icp->align.active) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: an alignment is in flight");  // (its books would overwrite the reset)
-  if (icp->in_align_batch) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: the factor is in a batch alignment in flight");
-  if (icp->score.active) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: a pose scoring call is in flight");
+  switch (icp->held) {  // (a holder's books would overwrite the reset)
+    case Held::window: return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: the factor is in a window call in flight");
+    case Held::align: return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: an alignment is in flight");
+    case Held::align_batch: return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: the factor is in a batch alignment in flight");
+    case Held::score: return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_reset: a pose scoring call is in flight");
+    case Held::none: break;
+  }
   icp->cold = true;  // the next linearize treats the cached state as all-zero (no memset needed)
   return MH_OK;
 }
@@ -869,11 +877,14 @@ static int mh_icp_wait_impl(mh_icp * icp)
 {
   const double tw_enter = g_wt.on ? WaitTrace::now() : 0.0;
   if (!icp) return fail(nullptr, MH_ERR_INVALID_ARG, "mh_icp_wait: icp is NULL");
-  if (icp->in_window) return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_wait: the factor is in a window call: mh_icp_window_wait collects it");
-  if (icp->in_align_batch)
-    return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_wait: the factor is in a batch alignment: mh_icp_align_batch_wait collects it");
-  if (icp->align.active) return mhi::align_wait(icp);
-  if (icp->score.active) return mhi::score_wait(icp);
+  switch (icp->held) {
+    case Held::window: return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_wait: the factor is in a window call: mh_icp_window_wait collects it");
+    case Held::align_batch:
+      return fail(icp->ctx, MH_ERR_INVALID_ARG, "mh_icp_wait: the factor is in a batch alignment: mh_icp_align_batch_wait collects it");
+    case Held::align: return mhi::align_wait(icp);
+    case Held::score: return mhi::score_wait(icp);
+    case Held::none: break;
+  }
   mh_ctx * ctx = icp->ctx;
   MH_HIP(ctx, mh_enter(ctx));
   // Every value a call produces arrives in mapped pinned memory tagged with the call's sequence number: the host polls the

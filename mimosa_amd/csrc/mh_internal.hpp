@@ -33,25 +33,32 @@ inline thread_local std::string g_mh_err;
 constexpr int kMaxPending = 64;
 constexpr int kMaxBatch = 64;  // factors per mh_icp_linearize_batch call
 
-// mh_icp_window_optimise (chain_api.hip): the call in flight on a context (at most one).  Its argument blocks, grid prefixes, state and K3's
-// landing slots live in device memory the context owns (d_window), their pinned staging in h_window, the rows the step
-// kernel publishes in mapped pinned memory (h_window_rows).
 struct WindowLaunch
 {
   int tpb, k, n_off, first, n, grid;  // one staged K3 launch per iteration: class, kernel path, its first slot and members, its grid
 };
-struct WindowCall
+// What every chain over several factors keeps of them while it is in flight (a window's poses, an alignment chain's members).
+constexpr int kChainMax = 16;
+static_assert(kChainMax == mh::kWindowMax && kChainMax == MH_ALIGN_BATCH_MAX, "one member table for the window and the alignment chains");
+struct ChainMembers
+{
+  int queued = 0, n_slots = 0;  // iterations on the stream so far; argument blocks per iteration
+  mh_icp * icps[kChainMax];
+  int slot[kChainMax];  // member i's argument block within an iteration (-1: a factor that runs no K3)
+  int count0[kChainMax];  // its linearize count and its pose when the call began
+  double R0[kChainMax][9];
+  double gz[3];
+  unsigned int seq[64];  // one sequence number per iteration
+  std::vector<WindowLaunch> launches;
+};
+// mh_icp_window_optimise (chain_api.hip): the call in flight on a context (at most one).  Its argument blocks, grid prefixes, state and K3's
+// landing slots live in device memory the context owns (d_window), their pinned staging in h_window, the rows the step
+// kernel publishes in mapped pinned memory (h_window_rows).
+struct WindowCall : ChainMembers
 {
   bool active = false;
-  int W = 0, iters = 0, queued = 0, n_slots = 0;
-  mh_icp * icps[mh::kWindowMax];
-  int slot[mh::kWindowMax];  // pose i's argument block within an iteration (-1: empty factor)
-  int count0[mh::kWindowMax];
-  double R0[mh::kWindowMax][9];
-  double gz[3];
-  unsigned int seq[64];
+  int W = 0, iters = 0;
   mh::WindowParams p;
-  std::vector<WindowLaunch> launches;
   // optimise: iterations of K3 and a step kernel, the result to outputs.out; marginal / marginal_joint: one K3 launch of icps[0]
   // and the (joint) marginal kernel, the result to outputs.marg / outputs.jmarg
   WindowKind kind = WindowKind::optimise;
@@ -67,23 +74,33 @@ struct WindowCall
   double LSR[MH_WINDOW_JOINT_POSES][9], LSt[MH_WINDOW_JOINT_POSES][3];         // ... and those poses as the caller gave them
 };
 
-// mh_icp_align_batch (chain_api.hip): the call in flight on a context (at most one).  Like a window call its argument blocks, grid
-// prefixes, the members' AlignStates and K3's landing slots live in device memory the context owns (d_align_batch), their pinned
-// staging in h_align_batch; every member's rows arrive in that member's own pinned ring, as mh_icp_align's do.
-struct AlignBatchCall
+// An alignment chain (chain_api.hip): the mh_icp_align call in flight on a factor (mh_icp::align, capacity 1) or the
+// mh_icp_align_batch call in flight on a context (mh_ctx::align_batch, capacity MH_ALIGN_BATCH_MAX); at most one of each.  Its
+// argument blocks, grid prefixes, the members' AlignStates and K3's landing slots live in the device block `d`, the pinned
+// staging of the first part in `h`; whoever owns the record owns both.  Every member's rows arrive in that member's own pinned
+// ring.  The block, as a function of the capacity:
+// [grid prefixes, 256 B | capacity x AlignState at a 192 B stride | max_iters x n_slots argument blocks | 256 B that load_uniform
+//  may read past the last block | one landing slot of 32 flagged words per member for K3's sums and counters (every iteration's
+//  words carry its own number, and the step that reads them is on the stream in front of the next K3)]
+constexpr size_t kAlignStateAt = 256;
+constexpr size_t kAlignStateStride = 192;
+constexpr size_t kAlignLlWords = 32;
+constexpr size_t align_blocks_at(int capacity) { return (kAlignStateAt + kAlignStateStride * static_cast<size_t>(capacity) + 255) & ~size_t(255); }
+constexpr size_t align_stage_bytes(int capacity) { return align_blocks_at(capacity) + sizeof(mh::IcpArgs) * static_cast<size_t>(capacity) * kMaxPending; }
+constexpr size_t align_ll_at(int capacity) { return (align_stage_bytes(capacity) + 256 + 255) & ~size_t(255); }
+constexpr size_t align_bytes(int capacity) { return align_ll_at(capacity) + kAlignLlWords * sizeof(uint4) * static_cast<size_t>(capacity); }
+static_assert(sizeof(mh::AlignState) <= kAlignStateStride && mh::kRowWords <= mh::kLlEig && MH_ALIGN_BATCH_MAX == mh::kAlignBatchMax &&
+                2 * MH_ALIGN_BATCH_MAX * sizeof(int) <= kAlignStateAt, "alignment chain layout");
+struct AlignChain : ChainMembers
 {
-  bool active = false;
-  int B = 0, queued = 0, n_slots = 0;
+  explicit AlignChain(int members_max) : capacity(members_max) {}
+  const int capacity;
+  int n = 0;  // members of the call in flight (0: none)
+  const char * what = "";  // the entry point's name, for its messages
   mh_icp_align_config cfg{};
-  mh_icp * icps[MH_ALIGN_BATCH_MAX];
-  int slot[MH_ALIGN_BATCH_MAX];  // member m's argument block within an iteration
-  int count0[MH_ALIGN_BATCH_MAX];
-  double R0[MH_ALIGN_BATCH_MAX][9];
-  double gz[3];
-  unsigned int seq[64];
-  mh::AlignParams p[MH_ALIGN_BATCH_MAX];
-  std::vector<WindowLaunch> launches;
-  mh_icp_align_result * out = nullptr;  // B of them
+  mh::AlignParams p[kChainMax];
+  mh_icp_align_result * out = nullptr;  // n of them
+  void * h = nullptr, * d = nullptr;
 };
 
 struct mh_ctx
@@ -103,9 +120,7 @@ struct mh_ctx
   uint4 * h_window_rows = nullptr; // ... the rows of its iterations (mapped pinned), and their device-side address
   uint4 * d_window_rows = nullptr;
   WindowCall window;
-  void * h_align_batch = nullptr;  // mh_icp_align_batch: pinned staging of the chain's block
-  void * d_align_batch = nullptr;  // ... the block itself
-  AlignBatchCall align_batch;
+  AlignChain align_batch{MH_ALIGN_BATCH_MAX};  // mh_icp_align_batch: its storage is allocated at the first call and freed by mh_shutdown
   hipStream_t copy_stream = nullptr;  // mh_scan_prefetch: uploads beside the compute stream (created on first use: an HSA queue costs ~1 ms)
   std::mutex copy_mu;
   // what mh_shutdown takes back from the sharded handles (shard_api.hip): the sharded factors created on this context, and
@@ -687,10 +702,10 @@ inline mh::MapView map_view(const mh_map * m)
 }
 
 // ---- ICP factor handle (mh_api.hip; shared with shard_api.hip and chain_api.hip) ----------------------------------
-// mh_icp::h_align, which mh_icp_destroy gives back: [grid prefix and AlignState, 256 B | 64 argument blocks] (chain_api.hip has
-// the whole layout)
-constexpr size_t kAlignBlocksAt = 256;
-constexpr size_t kAlignStageBytes = kAlignBlocksAt + sizeof(mh::IcpArgs) * kMaxPending;
+// Which chain holds a factor: while one does, the factor's whole ring is the chain's (n_pending == kMaxPending), so every entry
+// point that needs the factor free refuses it through n_pending alone, as it refuses one with 64 calls in flight.  The entry
+// points that must tell the holders apart (mh_icp_wait, mh_icp_reset, mh_icp_destroy) switch on this.
+enum class Held { none, align, align_batch, window, score };
 
 struct PendingCall
 {
@@ -739,67 +754,44 @@ struct mh_icp
   uint32_t * h_counts = nullptr;  // pinned
   bool origin_ready = false, plan_open = false;
   uint32_t n_movers = 0;
-  // mh_icp_align (chain_api.hip): the chain's argument blocks, grid prefix, state and K3's landing slots in device memory the factor owns
-  // (d_align), their pinned staging (h_align), and the call in flight.  While one is, it holds the whole ring (n_pending ==
-  // kMaxPending): every other entry point refuses the factor as it refuses one with 64 calls in flight.
+  Held held = Held::none;  // set and cleared with n_pending: hold(), let_go()
+  // mh_icp_align (chain_api.hip): the factor's own alignment chain, capacity 1.  Its device block comes from the allocation
+  // cache (d_align; align.d points into it), its pinned staging (align.h) from AllocCache::alloc_pinned at the first call;
+  // mh_icp_destroy gives both back.
   DevBuf d_align;
-  void * h_align = nullptr;
-  struct AlignCall
-  {
-    bool active = false;
-    mh_icp_align_config cfg{};
-    mh_icp_align_result * out = nullptr;
-    double R0[9], gz[3];
-    int queued = 0, count0 = 0;
-    bool cold0 = true;
-    unsigned int seq[kMaxPending];
-    mh::AlignParams p;
-  } align;
-  bool in_window = false;  // held by the mh_icp_window_optimise call in flight on its context (which also holds the whole ring)
-  // ... by the mh_icp_align_batch call in flight on its context (likewise).  The calls that need to tell such a factor apart test
-  // the flag (mh_icp_reset, which looks at no ring; mh_icp_wait, which would read the ring as its own calls; mh_icp_destroy;
-  // the new batch entry points).  Every other entry point — mh_icp_linearize*, mh_icp_linearize_batch, mh_icp_clone,
-  // mh_icp_align, the window chains, mh_icp_score_poses — refuses a member through n_pending == kMaxPending alone, as it refuses a
-  // factor whose ring is full; their checks are as they were.
-  bool in_align_batch = false;
+  AlignChain align{1};
   // which cloud this is: a fresh number for every created factor, the source's for a clone (mh_icp_relocalise_batch asks
   // whether its work factors are clones of the factor it scores)
   uint64_t cloud_id = 0;
   // mh_icp_score_poses (reloc_api.hip): the call's device block [poses | strided cloud | per-workgroup partials | scores]
   // (d_reloc), its mapped pinned block [winners | poses | scores] (h_reloc), and the call in flight.  Like an alignment it
-  // holds the whole ring (n_pending == kMaxPending) until mh_icp_wait collects it; it touches nothing else of the factor.
+  // holds the factor (Held::score) until mh_icp_wait collects it; it touches nothing else of the factor.
   DevBuf d_reloc;
   void * h_reloc = nullptr;
   size_t h_reloc_cap = 0;
   struct ScoreCall
   {
-    bool active = false;
     size_t n_poses = 0;
     mh_pose_score * scores = nullptr;
     int32_t * best = nullptr;
   } score;
 };
 
-// The window call on ctx is over (collected, or abandoned behind a drained stream): its factors are free again.
-inline void window_release(mh_ctx * ctx)
+// A call takes hold of a factor, and lets go of it — of all its factors — when it is over: collected, or abandoned behind a
+// drained stream.
+inline void hold(mh_icp * icp, Held by)
 {
-  WindowCall & c = ctx->window;
-  for (int i = 0; i < c.W; ++i) {
-    c.icps[i]->in_window = false;
-    c.icps[i]->n_pending = 0;
-  }
-  c.active = false;
+  icp->held = by;
+  icp->n_pending = kMaxPending;  // the chain holds the whole ring
 }
-
-// The same for the mh_icp_align_batch call on ctx.
-inline void align_batch_release(mh_ctx * ctx)
+inline void let_go(mh_icp * icp)
 {
-  AlignBatchCall & c = ctx->align_batch;
-  for (int i = 0; i < c.B; ++i) {
-    c.icps[i]->in_align_batch = false;
-    c.icps[i]->n_pending = 0;
-  }
-  c.active = false;
+  icp->held = Held::none;
+  icp->n_pending = 0;
+}
+inline void let_go(mh_icp * const * icps, int n)
+{
+  for (int i = 0; i < n; ++i) let_go(icps[i]);
 }
 
 // The factors of a window that share a kernel instantiation — launch class, k == 5 or the generic k <= 8 path, neighbour mode,
@@ -846,7 +838,9 @@ std::vector<LaunchGroup> window_launch_groups(mh_icp * const * icps, size_t n_fa
 int align_wait(mh_icp * icp);
 // reloc_api.hip: mh_icp_wait on a factor whose mh_icp_score_poses_async is in flight
 int score_wait(mh_icp * icp);
-// chain_api.hip: mh_icp_align_batch without the guard, for mh_icp_relocalise_batch
+// chain_api.hip: what mh_icp_align refuses of a config, worded with the caller's prefixes ("<prefix>max_iters must be ...",
+// "<prefix>eps, damping, ... must be >= 0"); mh_icp_align_batch without the guard, for mh_icp_relocalise_batch
+int align_check_config(const mh_ctx * ctx, const mh_icp_align_config & cfg, const char * iters_prefix, const char * ranges_prefix);
 int align_batch(mh_icp * const * icps, size_t B, const double * R0, const double * t0, const double g_unit[3], const mh_icp_align_config * cfg,
                 mh_icp_align_result * out);
 }  // namespace mhi

@@ -23,8 +23,7 @@ static int score_begin(mh_icp * icp, const double * R, const double * t, size_t 
   if (!icp || !R || !t || !cfg) return fail(icp ? icp->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_icp_score_poses: NULL argument");
   mh_ctx * ctx = icp->ctx;
   if (icp->binary) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_icp_score_poses: unary factors only");
-  if (icp->n_pending || icp->align.active || icp->score.active || icp->in_window)
-    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_score_poses: the factor has calls in flight");
+  if (icp->n_pending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_score_poses: the factor has calls in flight");
   if (n_poses < 1 || n_poses > static_cast<size_t>(MH_RELOC_MAX_POSES)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_score_poses: n_poses must be in 1..65536");
   if (!(std::isfinite(cfg->gate) && cfg->gate > 0.0)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_score_poses: the gate must be finite and > 0");
   if (cfg->stride < 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_score_poses: stride must be >= 1");
@@ -94,20 +93,18 @@ static int score_begin(mh_icp * icp, const double * R, const double * t, size_t 
     (void)hipStreamSynchronize(ctx->stream);
     return hip_fail(ctx, e, "mh_icp_score_poses: launch");
   }
-  icp->score.active = true;
   icp->score.n_poses = n_poses;
   icp->score.scores = scores;
   icp->score.best = best;
-  icp->n_pending = kMaxPending;  // the call holds the whole ring
+  hold(icp, Held::score);
   return MH_OK;
 }
 
 int mhi::score_wait(mh_icp * icp)
 {
   mh_ctx * ctx = icp->ctx;
-  mh_icp::ScoreCall & c = icp->score;
-  c.active = false;
-  icp->n_pending = 0;
+  const mh_icp::ScoreCall & c = icp->score;
+  let_go(icp);
   MH_HIP(ctx, mh_enter(ctx));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const char * h = static_cast<const char *>(icp->h_reloc);
@@ -155,16 +152,12 @@ static int relocalise_impl(mh_icp * icp, const double * R, const double * t, siz
   if (cfg->score.top_k == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise: score.top_k must be in 1..8");
   if (!(std::isfinite(cfg->final_gate) && cfg->final_gate > 0.0)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise: final_gate must be finite and > 0");
   // what mh_icp_align would refuse, before anything runs (the factor's own refusals are mh_icp_score_poses's, just below)
-  const mh_icp_align_config & ac = cfg->align;
-  if (ac.max_iters < 1 || ac.max_iters > kMaxPending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise: align.max_iters must be in 1..64");
-  if (!(ac.eps_rot >= 0.0) || !(ac.eps_trans >= 0.0) || !(ac.damping >= 0.0) || !(ac.prior_sigma_rot >= 0.0) || !(ac.prior_sigma_trans >= 0.0) ||
-      ac.check_every < 0)
-    return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise: align's eps, damping, prior sigmas and check_every must be >= 0");
+  if (const int no = mhi::align_check_config(ctx, cfg->align, "mh_icp_relocalise: align.", "mh_icp_relocalise: align's ")) return no;
   if (batch) {
     // the work factors, before anything runs: enough of them, each a free clone of icp, none twice
     const size_t need = std::min(static_cast<size_t>(std::max(cfg->score.top_k, 0)), n_poses);
     if (n_work < need) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: fewer work factors than candidates to refine");
-    if (ctx->align_batch.active) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: the context has a batch call in flight");
+    if (ctx->align_batch.n) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: the context has a batch call in flight");
     for (size_t c = 0; c < n_work; ++c) {
       const mh_icp * w = work[c];
       if (!w) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: NULL work factor");
@@ -172,8 +165,7 @@ static int relocalise_impl(mh_icp * icp, const double * R, const double * t, siz
       if (w->cloud_id != icp->cloud_id || w->n != icp->n || w->map != icp->map || w->ctx != ctx || w->binary != icp->binary ||
           !same_reg_config(w->cfg, icp->cfg))
         return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: a work factor is not a clone of the scored factor");
-      if (w->n_pending || w->align.active || w->score.active || w->in_window || w->in_align_batch)
-        return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: a work factor has calls in flight");
+      if (w->n_pending) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: a work factor has calls in flight");
       for (size_t g = 0; g < c; ++g)
         if (work[g] == w) return fail(ctx, MH_ERR_INVALID_ARG, "mh_icp_relocalise_batch: the same work factor twice");
     }

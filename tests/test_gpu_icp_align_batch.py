@@ -141,6 +141,29 @@ def destroy(*lists):
             f.destroy()
 
 
+def device_factors(world):
+    """(from_device, free): from_device() makes a factor of the 257-point cloud with mh_icp_create_from_device, which keeps the
+    caller's point order as the pieces of a map-sharded factor do; free() gives the device cloud back once those factors are gone"""
+    capi, synth = world["capi"], world["synth"]
+    ctx, L = world["ctx"], world["ctx"].L
+    pts = world["cloud"](257)
+    d_pts = C.c_void_p()
+    assert L.hipMalloc(C.byref(d_pts), C.c_size_t(pts.nbytes)) == 0
+    assert L.hipMemcpy(d_pts, C.c_void_p(pts.ctypes.data), C.c_size_t(pts.nbytes), 1) == 0
+    reg = capi.make_reg_config(**synth.enwide_config())
+
+    def from_device():
+        h = C.c_void_p()
+        ctx.check(L.mh_icp_create_from_device(ctx.h, world["gmap"](19).h, d_pts, len(pts), C.byref(reg), 0, C.byref(h)))
+        return capi.ICPFactor(ctx, world["gmap"](19), None, None, _h=h, _n=len(pts))
+
+    def free():
+        ctx.synchronize()
+        assert L.hipFree(d_pts) == 0
+
+    return from_device, free
+
+
 def count_of(f, world):
     """the factor's linearize count (one more linearize shows it)"""
     return f.linearize(*world["truth"], G)["linearize_count"] - 1
@@ -394,26 +417,150 @@ def test_refusals(world):
     refused(capi.MH_ERR_UNSUPPORTED, [fs[0], binary], word="unary")
     # the factors of the map-sharded path: mh_icp_create_from_device keeps the caller's point order, as the sharded factor's
     # pieces do.  Alone and among ordinary members; afterwards it still linearizes as a twin made from the same device cloud
-    pts = world["cloud"](257)
-    d_pts = C.c_void_p()
-    assert L.hipMalloc(C.byref(d_pts), C.c_size_t(pts.nbytes)) == 0
-    assert L.hipMemcpy(d_pts, C.c_void_p(pts.ctypes.data), C.c_size_t(pts.nbytes), 1) == 0
-    reg = capi.make_reg_config(**synth.enwide_config())
-
-    def from_device():
-        h = C.c_void_p()
-        ctx.check(L.mh_icp_create_from_device(ctx.h, world["gmap"](19).h, d_pts, len(pts), C.byref(reg), 0, C.byref(h)))
-        return capi.ICPFactor(ctx, world["gmap"](19), None, None, _h=h, _n=len(pts))
-
+    from_device, free_device_cloud = device_factors(world)
     kept, kept_twin = from_device(), from_device()
     same_result(kept.linearize(*probe, G), kept_twin.linearize(*probe, G), "device factors")
     for members in ([kept], [fs[0], kept, fs[1]], [kept, fs[2]]):
         refused(capi.MH_ERR_UNSUPPORTED, members, word="map-sharded")
         same_result(kept.linearize(*probe, G), kept_twin.linearize(*probe, G), "the device factor after a refusal")
     destroy([kept, kept_twin])
-    ctx.synchronize()
-    assert L.hipFree(d_pts) == 0
+    free_device_cloud()
     destroy(fs, twins)
+
+
+# ---- mh_icp_align and mh_icp_align_batch are one chain driver: where the two forms meet -----------------------------------
+def test_chains_side_by_side(world):
+    """two mh_icp_align_async chains (each on its factor's own storage) and one mh_icp_align_batch_async chain (on the context's)
+    in flight at once with a plain linearize between them, collected in the reverse of the order they were started: everything
+    as blocking calls on fresh clones from the same starts give it"""
+    capi = world["capi"]
+    big, one = world["factor"](257), world["factor"](1, 3, 27)
+    bases = [big, one, big, one, big]
+    starts = [perturbed(world["truth"], 71 + i) for i in range(5)]
+    cfg = align_cfg()
+    fs, refs = [b.clone() for b in bases], [b.clone() for b in bases]
+    singles = [fs[0].align_async(*starts[0], cfg, G), fs[1].align_async(*starts[1], cfg, G)]
+    call = capi.align_batch(fs[2:4], starts[2:4], cfg, G, wait=False)
+    lin = fs[4].linearize(*starts[4], G)
+    got_batch = call.wait()
+    fs[1].wait()
+    fs[0].wait()
+    got = [singles[0].as_dict(), singles[1].as_dict()] + got_batch
+    ref = [refs[0].align(*starts[0], cfg, G), refs[1].align(*starts[1], cfg, G)] + capi.align_batch(refs[2:4], starts[2:4], cfg, G)
+    print("iters", [r["iters"] for r in ref])
+    for m in range(4):
+        same_bits(got[m], ref[m], f"side by side {m}")
+    same_result(lin, refs[4].linearize(*starts[4], G), "the linearize between the chains")
+    for m in range(5):
+        same_state(fs[m], refs[m], f"side by side {m}")
+    destroy(fs, refs)
+
+
+def test_one_landing_slot_is_enough(world):
+    """all 64 iterations evaluated (eps = 0: nothing converges), queued at once and one by one: K3's words of every iteration
+    land in the same device slot, told apart by the iteration's sequence number; a one-member batch gives the same trace"""
+    capi = world["capi"]
+    base = world["factor"](257)
+    start = perturbed(world["truth"], 81)
+    runs = []
+    for ce in (0, 1):
+        f = base.clone()
+        runs.append((f, f.align(*start, align_cfg(max_iters=64, eps_rot=0.0, eps_trans=0.0, check_every=ce), G)))
+    member = base.clone()
+    batch = capi.align_batch([member], [start], align_cfg(max_iters=64, eps_rot=0.0, eps_trans=0.0), G)
+    assert runs[0][1]["iters"] == 64 and runs[1][1]["iters"] == 64
+    same_bits(runs[1][1], runs[0][1], "check_every 1 against 0")
+    same_state(runs[1][0], runs[0][0], "check_every 1 against 0")
+    same_bits(batch[0], runs[0][1], "one-member batch")
+    same_state(member, runs[0][0], "one-member batch")
+    destroy([f for f, _ in runs], [member])
+
+
+def test_order_of_the_refusals(world):
+    """which refusal comes first where an argument earns two: each entry point keeps its own order (codes and texts as the
+    commit before the two forms shared a driver gave them)"""
+    capi, synth = world["capi"], world["synth"]
+    ctx = world["ctx"]
+    base = world["factor"](257)
+    good, twin, busy = base.clone(), base.clone(), base.clone()
+    start, probe = perturbed(world["truth"], 91), perturbed(world["truth"], 92)
+    from_device, free_device_cloud = device_factors(world)
+    kept = from_device()
+    binary = world["factor"](257, binary=True)
+    empty = capi.ICPFactor(ctx, world["gmap"](19), world["cloud"](257)[:0], capi.make_reg_config(**synth.enwide_config()))
+
+    def refused(call, code, word, without=None):
+        with pytest.raises(capi.MhError) as e:
+            call()
+        print(e.value.code, str(e.value))
+        assert e.value.code == code and word in str(e.value), str(e.value)
+        assert without is None or without not in str(e.value), str(e.value)
+        same_result(good.linearize(*probe, G), twin.linearize(*probe, G), "the good factor after a refusal")
+
+    # mh_icp_align: NULL, unary, in flight, max_iters, the other ranges, the sharded path, no points
+    refused(lambda: binary.align(*start, align_cfg(max_iters=0), G), capi.MH_ERR_UNSUPPORTED, "unary")
+    refused(lambda: kept.align(*start, align_cfg(max_iters=0), G), capi.MH_ERR_INVALID_ARG, "max_iters")
+    refused(lambda: kept.align(*start, align_cfg(), G), capi.MH_ERR_UNSUPPORTED, "map-sharded")
+    refused(lambda: empty.align(*start, align_cfg(damping=-1.0), G), capi.MH_ERR_INVALID_ARG, "must be >= 0", without="no points")
+    # mh_icp_align_batch: the factors before the config
+    refused(lambda: capi.align_batch([good, kept], [start] * 2, align_cfg(max_iters=0), G), capi.MH_ERR_UNSUPPORTED, "map-sharded")
+    pending = busy.linearize_async(*probe, G)
+    refused(lambda: capi.align_batch([good, busy], [start] * 2, align_cfg(max_iters=0), G), capi.MH_ERR_INVALID_ARG, "in flight")
+    busy.wait()
+    fresh = base.clone()
+    same_result(pending.as_dict(), fresh.linearize(*probe, G), "the call that was in flight")
+    destroy([kept, empty])
+    free_device_cloud()
+    destroy([good, twin, busy, fresh])
+
+
+def test_held_factors_every_holder(world):
+    """a factor held by each of the four calls that take its whole ring — mh_icp_align_async, mh_icp_align_batch_async, a window
+    call, mh_icp_score_poses_async — refuses reset, linearize, align, score_poses, clone (and wait, where the holder's own wait is
+    the context's) with the code and the words it always had; after the holder's own wait every one of them works"""
+    capi = world["capi"]
+    base = world["factor"](257)
+    start, probe = perturbed(world["truth"], 95), perturbed(world["truth"], 96)
+    cfg = align_cfg()
+    I = (np.eye(3), np.zeros(3))
+
+    def hold_align(f, mate):
+        f.align_async(*start, cfg, G)
+        return f.wait
+
+    def hold_batch(f, mate):
+        return capi.align_batch([mate, f], [start] * 2, cfg, G, wait=False).wait
+
+    def hold_window(f, mate):
+        return capi.optimise_window([mate, f], [start] * 2, capi.make_window_config(iters=3), has_Z=[0, 1], Z=[I, I], wait=False).wait
+
+    def hold_score(f, mate):
+        f.score_poses_async(start[0][None], start[1][None], 1.0)
+        return f.wait
+
+    # holder: (how it takes hold, mh_icp_reset's words, mh_icp_wait's where it refuses)
+    holders = {"align": (hold_align, "an alignment is in flight", None),
+               "align_batch": (hold_batch, "batch alignment in flight", "mh_icp_align_batch_wait collects it"),
+               "window": (hold_window, "window call in flight", "mh_icp_window_wait collects it"),
+               "score": (hold_score, "pose scoring call is in flight", None)}
+    for name, (hold, reset_words, wait_words) in holders.items():
+        f, mate = base.clone(), base.clone()
+        calls = {"reset": (f.reset, reset_words),
+                 "linearize": (lambda: f.linearize(*probe, G), "too many calls in flight"),
+                 "align": (lambda: f.align(*start, cfg, G), "mh_icp_align: the factor has calls in flight"),
+                 "score_poses": (lambda: f.score_poses(start[0][None], start[1][None], 1.0), "mh_icp_score_poses: the factor has calls in flight"),
+                 "clone": (lambda: f.clone().destroy(), "source has linearize calls in flight")}
+        release = hold(f, mate)
+        for what, (call, words) in list(calls.items()) + ([("wait", (f.wait, wait_words))] if wait_words else []):
+            with pytest.raises(capi.MhError) as e:
+                call()
+            print(name, what, e.value.code, str(e.value))
+            assert e.value.code == capi.MH_ERR_INVALID_ARG and words in str(e.value), (name, what, str(e.value))
+        release()
+        for what, (call, _) in calls.items():
+            call()
+        f.wait()  # nothing pending: not refused
+        destroy([f, mate])
 
 
 # ---- mh_icp_relocalise_batch on the scene of test_gpu_reloc.py's test_relocalise_recovers_the_pose ------------------------
