@@ -375,7 +375,7 @@ static int align_collect(mh_icp * icp, const unsigned int * seq, int queued, con
   std::memset(static_cast<void *>(out), 0, sizeof(*out));
   int iters = 0, converged = 0;
   double row_buf[mh::kRowWords];
-  const ChainRows rows{icp->h_ll + mh::kLlSums, icp->ll_words, mh::kRowWords, seq};
+  const ChainRows rows{icp->h_ll.as<uint4>() + mh::kLlSums, icp->ll_words, mh::kRowWords, seq};
   const int rc = chain_trace(ctx, rows, queued, mh::kRowFlags, what, row_buf, 0, [&](int i, const double * row) {
     mh_icp_align_trace & tr = out->trace[i];
     tr.f = row[mh::kRowF];
@@ -430,7 +430,7 @@ static int align_wait_row(const AlignChain & c, int i, double * row)
   int all = 1;
   for (int m = 0; m < c.n; ++m) {
     const mh_icp * icp = c.icps[m];
-    const int rc = chain_wait_row(icp->ctx, ChainRows{icp->h_ll + mh::kLlSums, icp->ll_words, mh::kRowWords, c.seq}, i, row, c.what);
+    const int rc = chain_wait_row(icp->ctx, ChainRows{icp->h_ll.as<uint4>() + mh::kLlSums, icp->ll_words, mh::kRowWords, c.seq}, i, row, c.what);
     if (rc != MH_OK) return rc;
     all &= static_cast<int>(row[mh::kRowFlags]);
   }
@@ -471,7 +471,8 @@ static int mh_icp_align_impl(mh_icp * icp, const double R0[9], const double t0[3
   MH_HIP(ctx, mh_enter(ctx));
   AlignChain & c = icp->align;
   MH_HIP(ctx, icp->d_align.reserve(align_bytes(1), ctx->stream, false));
-  if (!c.h) MH_HIP(ctx, AllocCache::alloc_pinned(&c.h, align_stage_bytes(1)));
+  MH_HIP(ctx, icp->h_align.reserve(align_stage_bytes(1), align_stage_bytes(1)));
+  c.h = icp->h_align.p;
   c.d = icp->d_align.p;
   const int rc = align_begin(c, "mh_icp_align", Held::align, &icp, 1, R0, t0, g_unit, cfg, out);
   return rc != MH_OK ? rc : align_start(c, blocking);

@@ -15,43 +15,14 @@ namespace
 {
 constexpr int32_t kKeyframesMax = 65536;
 
-void keyframes_release_device(mh_keyframes * kf)
-{
-  AllocCache::free(kf->d_arena);
-  AllocCache::free(kf->d_offsets);
-  kf->d_arena = nullptr;
-  kf->d_offsets = nullptr;
-  kf->d_in.release();
-  if (kf->h_io) AllocCache::free_pinned(kf->h_io, kf->h_io_cap);
-  kf->h_io = nullptr;
-  kf->h_io_cap = 0;
-}
-
 // every entry point but destroy: a store whose context was shut down
-int keyframes_alive(const mh_keyframes * kf, const char * who)
-{
-  if (!kf->ctx) return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the store's context was shut down; the handle can only be destroyed");
-  return MH_OK;
-}
+int keyframes_alive(const mh_keyframes * kf, const char * who) { return ctx_alive(kf, who, "store"); }
 
 // the checks every add shares: room for one more entry of n points
 int keyframes_add_check(const mh_keyframes * kf, const char * who, size_t n)
 {
   if (kf->tags.size() >= static_cast<size_t>(kf->cfg.capacity_keyframes)) return fail(kf->ctx, MH_ERR_INVALID_ARG, std::string(who) + ": the store is full (keyframes)");
   if (n > static_cast<uint64_t>(kf->cfg.capacity_points) - kf->offsets.back()) return fail(kf->ctx, MH_ERR_INVALID_ARG, std::string(who) + ": the store is full (points)");
-  return MH_OK;
-}
-
-int keyframes_io(mh_keyframes * kf, size_t bytes)
-{
-  if (bytes <= kf->h_io_cap) return MH_OK;
-  size_t cap = size_t(64) << 10;
-  while (cap < bytes) cap <<= 1;
-  if (kf->h_io) AllocCache::free_pinned(kf->h_io, kf->h_io_cap);  // (every call that used it has waited)
-  kf->h_io = nullptr;
-  kf->h_io_cap = 0;
-  MH_HIP(kf->ctx, AllocCache::alloc_pinned(&kf->h_io, cap));
-  kf->h_io_cap = cap;
   return MH_OK;
 }
 
@@ -62,7 +33,7 @@ int keyframes_append(mh_keyframes * kf, const char * who, const float * d_src, s
   const size_t i = kf->tags.size();
   const uint64_t at = kf->offsets.back();
   // (a launch that fails leaves the books where they were: the slot is simply written again)
-  const hipError_t e = mh::launch_keyframes_pack(d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), kf->d_arena + at, kf->d_offsets + i, at + n,
+  const hipError_t e = mh::launch_keyframes_pack(d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), kf->arena() + at, kf->mem.d_offsets.as<unsigned long long>() + i, at + n,
                                                  ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, who);
   if (index) *index = static_cast<int32_t>(i);
@@ -75,44 +46,22 @@ int keyframes_create(mh_ctx * ctx, const mh_keyframes_config * cfg, mh_keyframes
 {
   MH_HIP(ctx, mh_enter(ctx));
   mh_keyframes * kf = new mh_keyframes;
-  kf->ctx = ctx;
   kf->cfg = *cfg;
   kf->tags.reserve(static_cast<size_t>(cfg->capacity_keyframes));
   kf->offsets.reserve(static_cast<size_t>(cfg->capacity_keyframes) + 1);
-  void * p[2] = {nullptr, nullptr};
   const size_t off_bytes = (static_cast<size_t>(cfg->capacity_keyframes) + 1) * sizeof(unsigned long long);
-  hipError_t e = AllocCache::alloc(&p[0], static_cast<size_t>(cfg->capacity_points) * sizeof(float4));
-  if (e == hipSuccess) e = AllocCache::alloc(&p[1], off_bytes);
-  kf->d_arena = static_cast<float4 *>(p[0]);
-  kf->d_offsets = static_cast<unsigned long long *>(p[1]);
-  if (e == hipSuccess) e = hipMemsetAsync(kf->d_offsets, 0, off_bytes, ctx->stream);
+  hipError_t e = kf->mem.d_arena.alloc(static_cast<size_t>(cfg->capacity_points) * sizeof(float4));
+  if (e == hipSuccess) e = kf->mem.d_offsets.alloc(off_bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(kf->mem.d_offsets.p, 0, off_bytes, ctx->stream);
   if (e != hipSuccess) {
-    keyframes_release_device(kf);
     delete kf;
     return hip_fail(ctx, e, "mh_keyframes_create");
   }
-  ctx->keyframe_stores.push_back(kf);
+  ctx_register(kf, ctx);
   *out = kf;
   return MH_OK;
 }
 }  // namespace
-
-namespace mhi
-{
-void keyframes_ctx_gone(mh_ctx * ctx)
-{
-  if (ctx->keyframe_stores.empty()) return;
-  (void)mh_enter(ctx);
-  (void)hipStreamSynchronize(ctx->stream);
-  for (mh_keyframes * kf : ctx->keyframe_stores) {
-    keyframes_release_device(kf);
-    kf->tags.clear();
-    kf->offsets.assign(1, 0);
-    kf->ctx = nullptr;
-  }
-  ctx->keyframe_stores.clear();
-}
-}  // namespace mhi
 
 extern "C" {
 
@@ -136,9 +85,7 @@ void mh_keyframes_destroy(mh_keyframes * kf)
   if (mh_ctx * ctx = kf->ctx) {
     (void)mh_enter(ctx);
     (void)hipStreamSynchronize(ctx->stream);  // the arena goes back: nothing may still be reading it
-    keyframes_release_device(kf);
-    auto & v = ctx->keyframe_stores;
-    v.erase(std::remove(v.begin(), v.end(), kf), v.end());
+    ctx_unregister(kf);
   }
   delete kf;
 }
@@ -174,13 +121,13 @@ int mh_keyframes_add(mh_keyframes * kf, const float * xyz, size_t n, size_t stri
     MH_HIP(ctx, mh_enter(ctx));
     if (n) {  // packed xyz through the pinned block, then the pack kernel every add shares
       const size_t bytes = n * 3 * sizeof(float);
-      if ((rc = keyframes_io(kf, bytes)) != MH_OK) return rc;
-      MH_HIP(ctx, kf->d_in.reserve(bytes, ctx->stream, false));
-      float * h = static_cast<float *>(kf->h_io);
+      MH_HIP(ctx, kf->mem.h_io.reserve(bytes));  // (every call that used it has waited)
+      MH_HIP(ctx, kf->mem.d_in.reserve(bytes, ctx->stream, false));
+      float * h = kf->mem.h_io.as<float>();
       for (size_t i = 0; i < n; ++i) std::memcpy(h + 3 * i, xyz + i * stride_floats, 3 * sizeof(float));
-      MH_HIP(ctx, hipMemcpyAsync(kf->d_in.p, kf->h_io, bytes, hipMemcpyHostToDevice, ctx->stream));
+      MH_HIP(ctx, hipMemcpyAsync(kf->mem.d_in.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    rc = keyframes_append(kf, "mh_keyframes_add", static_cast<const float *>(kf->d_in.p), n, 3, tag, index);
+    rc = keyframes_append(kf, "mh_keyframes_add", kf->mem.d_in.as<const float>(), n, 3, tag, index);
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the pinned block is the next call's too)
     return rc;
   });
@@ -234,10 +181,10 @@ int mh_keyframes_get(mh_keyframes * kf, int32_t index, float * xyz, size_t capac
     const size_t take = xyz ? static_cast<size_t>(std::min<uint64_t>(n, capacity_points)) : 0;
     if (take) {
       MH_HIP(ctx, mh_enter(ctx));
-      if ((rc = keyframes_io(kf, take * sizeof(float4))) != MH_OK) return rc;
-      MH_HIP(ctx, hipMemcpyAsync(kf->h_io, kf->d_arena + at, take * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+      MH_HIP(ctx, kf->mem.h_io.reserve(take * sizeof(float4)));  // (every call that used it has waited)
+      MH_HIP(ctx, hipMemcpyAsync(kf->mem.h_io.p, kf->arena() + at, take * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
       MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      const float * h = static_cast<const float *>(kf->h_io);
+      const float * h = kf->mem.h_io.as<const float>();
       for (size_t i = 0; i < take; ++i) std::memcpy(xyz + 3 * i, h + 4 * i, 3 * sizeof(float));
     }
     if (n_out) *n_out = static_cast<size_t>(n);
@@ -254,7 +201,7 @@ int mh_keyframes_device_points(mh_keyframes * kf, int32_t index, const float ** 
     if (rc != MH_OK) return rc;
     if (index < 0 || static_cast<size_t>(index) >= kf->tags.size()) return fail(kf->ctx, MH_ERR_INVALID_ARG, "mh_keyframes_device_points: index out of range");
     const uint64_t at = kf->offsets[static_cast<size_t>(index)];
-    *d_xyz1 = reinterpret_cast<const float *>(kf->d_arena + at);
+    *d_xyz1 = reinterpret_cast<const float *>(kf->arena() + at);
     *n = static_cast<size_t>(kf->offsets[static_cast<size_t>(index) + 1] - at);
     return MH_OK;
   });

@@ -30,14 +30,14 @@ mh::MapArrays arrays_of(const mh_map * m)
   a.qbuckets = static_cast<uint32_t *>(m->d_qbuckets.p);
   a.vox = static_cast<int4 *>(m->d_vox.p);
   a.lru = static_cast<unsigned long long *>(m->d_lru.p);
-  a.state = m->d_state;
+  a.state = m->d_state.as<mh::MapState>();
   return a;
 }
 
 int fetch_state(mh_map * m)
 {
   mh_ctx * ctx = m->ctx;
-  MH_HIP(ctx, hipMemcpyAsync(m->h_state, m->d_state, sizeof(mh::MapState), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(m->h_state, m->d_state.as<mh::MapState>(), sizeof(mh::MapState), hipMemcpyDeviceToHost, ctx->stream));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MH_OK;
 }
@@ -48,7 +48,7 @@ int push_state(mh_map * m)
   m->h_state->n_blocks = m->n_blocks;
   m->h_state->n_points = m->n_points;
   m->h_state->bad_coord = 0;
-  MH_HIP(ctx, hipMemcpyAsync(m->d_state, m->h_state, sizeof(mh::MapState), hipMemcpyHostToDevice, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(m->d_state.as<mh::MapState>(), m->h_state, sizeof(mh::MapState), hipMemcpyHostToDevice, ctx->stream));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // h_state is reused as the read-back target
   return MH_OK;
 }
@@ -98,10 +98,7 @@ int ensure_table(mh_map * m, size_t n_blocks_bound)
     MH_HIP(ctx, mh::launch_map_rehash(static_cast<const int4 *>(m->d_table.p), static_cast<uint32_t>(m->table_cap), static_cast<int4 *>(nt.p),
                                       static_cast<uint32_t>(cap), ctx->stream));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  m->d_table.release();
-  m->d_table = nt;
-  nt.p = nullptr;
-  nt.cap = 0;
+  m->d_table = std::move(nt);
   m->table_cap = cap;
   return MH_OK;
 }
@@ -138,22 +135,14 @@ int compact_voxels(mh_map * m, uint32_t nv, uint32_t keep, const char * what, co
   int rc = MH_OK;
   mh::MapArrays a = arrays_of(m);
   // fresh voxel arrays; the old ones are the compaction source
-  DevBuf ob = m->d_buckets, oq = m->d_qbuckets, ov = m->d_vox, ol = m->d_lru;
-  m->d_buckets = DevBuf{};
-  m->d_qbuckets = DevBuf{};
-  m->d_vox = DevBuf{};
-  m->d_lru = DevBuf{};
+  DevBuf ob = std::move(m->d_buckets), oq = std::move(m->d_qbuckets), ov = std::move(m->d_vox), ol = std::move(m->d_lru);
   const size_t old_cap = m->vox_cap;
   m->vox_cap = 0;
-  auto restore = [&]() {
-    m->d_buckets.release();
-    m->d_qbuckets.release();
-    m->d_vox.release();
-    m->d_lru.release();
-    m->d_buckets = ob;
-    m->d_qbuckets = oq;
-    m->d_vox = ov;
-    m->d_lru = ol;
+  auto restore = [&]() {  // (whatever of the fresh arrays exists is released by the assignments)
+    m->d_buckets = std::move(ob);
+    m->d_qbuckets = std::move(oq);
+    m->d_vox = std::move(ov);
+    m->d_lru = std::move(ol);
     m->vox_cap = old_cap;
   };
   rc = ensure_voxels(m, keep);
@@ -179,12 +168,8 @@ int compact_voxels(mh_map * m, uint32_t nv, uint32_t keep, const char * what, co
     // the fresh arrays and the table are half written and the counters already name the compacted map: there is no way back
     // to the old state from here.  The map is marked unusable instead of being left to answer from garbage ids.
     (void)hipStreamSynchronize(ctx->stream);
-    ob.release();
-    oq.release();
-    ov.release();
-    ol.release();
     m->poisoned = true;
-    return rc != MH_OK ? rc : hip_fail(ctx, e, what);
+    return rc != MH_OK ? rc : hip_fail(ctx, e, what);  // (the old arrays go back on the way out)
   }
   m->n_blocks = m->h_state->n_blocks;
   m->n_points = m->h_state->n_points;
@@ -321,15 +306,15 @@ int rebuild_fill(mh_map * m, const mh_keyframes * kf, const std::vector<uint64_t
   // the whole plan goes to the device once: [RebuildKeyframe x K | prefix offsets: (k1 - k0 + 1) words per chunk]
   const size_t kf_bytes = K * sizeof(mh::RebuildKeyframe), rel_words = K + plan.size();
   DevTemp<char> d_plan;
-  void * h_plan = nullptr;
   const size_t plan_bytes = kf_bytes + rel_words * sizeof(uint32_t);
   if (K) {
     MH_HIP(ctx, d_plan.alloc(plan_bytes));
     size_t pinned_bytes = 4096;  // (the pinned cache keeps blocks by their exact size)
     while (pinned_bytes < plan_bytes) pinned_bytes <<= 1;
-    MH_HIP(ctx, AllocCache::alloc_pinned(&h_plan, pinned_bytes));
-    mh::RebuildKeyframe * hk = static_cast<mh::RebuildKeyframe *>(h_plan);
-    uint32_t * hr = reinterpret_cast<uint32_t *>(static_cast<char *>(h_plan) + kf_bytes);
+    PinnedBuf h_plan;
+    MH_HIP(ctx, h_plan.reserve(plan_bytes, pinned_bytes));
+    mh::RebuildKeyframe * hk = h_plan.as<mh::RebuildKeyframe>();
+    uint32_t * hr = reinterpret_cast<uint32_t *>(h_plan.as<char>() + kf_bytes);
     for (size_t j = 0; j < K; ++j) {
       hk[j].src = src[j];
       std::memcpy(hk[j].Rt12, R + 9 * j, 9 * sizeof(float));
@@ -344,9 +329,8 @@ int rebuild_fill(mh_map * m, const mh_keyframes * kf, const std::vector<uint64_t
       }
       hr[w++] = at;
     }
-    hipError_t e = hipMemcpyAsync(d_plan.p, h_plan, plan_bytes, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(d_plan.p, h_plan.p, plan_bytes, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    AllocCache::free_pinned(h_plan, pinned_bytes);
     if (e != hipSuccess) return hip_fail(ctx, e, who);
   }
   const mh::RebuildKeyframe * d_kf = reinterpret_cast<const mh::RebuildKeyframe *>(d_plan.p);
@@ -358,7 +342,7 @@ int rebuild_fill(mh_map * m, const mh_keyframes * kf, const std::vector<uint64_t
       const size_t n = static_cast<size_t>(c.points);
       int rc = ensure_scratch(m, n);
       if (rc != MH_OK) return rc;
-      MH_HIP(ctx, mh::launch_map_rebuild_assign(arrays_of(m), kf->d_arena, d_kf + c.k0, d_rel + w, kc, static_cast<uint32_t>(n), m->inv_leaf, scratch_of(m),
+      MH_HIP(ctx, mh::launch_map_rebuild_assign(arrays_of(m), kf->arena(), d_kf + c.k0, d_rel + w, kc, static_cast<uint32_t>(n), m->inv_leaf, scratch_of(m),
                                                 ctx->stream));
       const ChunkStamps stamps{d_rel + w, kc};
       rc = insert_grouped(m, who, n, &stamps);
@@ -518,12 +502,7 @@ int carve_device(mh_map * m, const char * who, const float * d_src, size_t n, si
 
 void map_free(mh_map * m)
 {
-  for (DevBuf * b : {&m->d_table, &m->d_cells, &m->d_buckets, &m->d_qbuckets, &m->d_vox, &m->d_lru, &m->s_in, &m->s_pts, &m->s_group, &m->s_seg_vid,
-                     &m->s_seg_added, &m->s_blk_new, &m->s_flags, &m->s_pos, &m->s_temp, &m->s_rt, &m->s_shard, &m->s_preview, &m->s_carve_img, &m->s_carve_vox})
-    b->release();
-  if (m->d_state) dev_free(m->d_state);
   if (m->h_state) (void)hipHostFree(m->h_state);
-  if (m->h_in) (void)hipHostFree(m->h_in);
   delete m;
 }
 
@@ -535,7 +514,7 @@ int map_alloc(mh_ctx * ctx, const mh_map_config & cfg, mh_map ** out)
   m->inv_leaf = 1.0 / cfg.leaf_size;
   m->min_sq = cfg.min_dist_in_cell * cfg.min_dist_in_cell;
   m->n_off = mh::neighbor_offsets(cfg.neighbor_voxel_mode, m->off);
-  hipError_t e = dev_alloc(&m->d_state, sizeof(mh::MapState));
+  hipError_t e = m->d_state.alloc(sizeof(mh::MapState));
   if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&m->h_state), sizeof(mh::MapState), hipHostMallocDefault);
   if (e != hipSuccess) {
     map_free(m);
@@ -641,14 +620,8 @@ static int stage_batch(mh_map * map, const float * xyz, size_t n, size_t stride_
   mh_ctx * ctx = map->ctx;
   if (n > (size_t(1) << 40) / 12) return fail(ctx, MH_ERR_OOM, "mh_map_insert: batch too large");
   const size_t bytes = n * 3 * sizeof(float);
-  if (map->h_in_cap < bytes) {
-    if (map->h_in) (void)hipHostFree(map->h_in);
-    map->h_in = nullptr;
-    map->h_in_cap = 0;
-    MH_HIP(ctx, hipHostMalloc(&map->h_in, bytes + bytes / 2, hipHostMallocDefault));
-    map->h_in_cap = bytes + bytes / 2;
-  }
-  float * st = static_cast<float *>(map->h_in);
+  MH_HIP(ctx, map->h_in.reserve(bytes));
+  float * st = map->h_in.as<float>();
   if (stride_floats == 3) {
     std::memcpy(st, xyz, bytes);
   } else {
@@ -702,7 +675,7 @@ int mh_map_insert_shard(mh_map * map, const float * xyz, size_t n, size_t stride
       MH_HIP(ctx, map->s_shard.reserve(n * 3 * sizeof(float), ctx->stream, false));
       MH_HIP(ctx, mh::launch_shard_filter(static_cast<const float *>(map->s_in.p), static_cast<uint32_t>(n), 3, map->inv_leaf, static_cast<uint32_t>(world),
                                           static_cast<uint32_t>(rank), block_log2, static_cast<uint32_t *>(map->s_flags.p),
-                                          static_cast<uint32_t *>(map->s_pos.p), static_cast<float *>(map->s_shard.p), &map->d_state->n_keep, map->s_temp.p,
+                                          static_cast<uint32_t *>(map->s_pos.p), static_cast<float *>(map->s_shard.p), &map->d_state.as<mh::MapState>()->n_keep, map->s_temp.p,
                                           map->s_temp.cap, ctx->stream));
       rc = fetch_state(map);
       if (rc != MH_OK) return rc;
@@ -746,7 +719,7 @@ int mh_map_insert_shard_from_scan(mh_map * map, const mh_scan * scan, const floa
       MH_HIP(ctx, mh::launch_shard_filter(static_cast<const float *>(map->s_in.p), static_cast<uint32_t>(n), static_cast<uint32_t>(sizeof(mh_point32) / sizeof(float)),
                                           map->inv_leaf, static_cast<uint32_t>(world), static_cast<uint32_t>(rank), block_log2,
                                           static_cast<uint32_t *>(map->s_flags.p), static_cast<uint32_t *>(map->s_pos.p), static_cast<float *>(map->s_shard.p),
-                                          &map->d_state->n_keep, map->s_temp.p, map->s_temp.cap, ctx->stream));
+                                          &map->d_state.as<mh::MapState>()->n_keep, map->s_temp.p, map->s_temp.cap, ctx->stream));
       const int rc = fetch_state(map);
       if (rc != MH_OK) return rc;
       kept = map->h_state->n_keep;

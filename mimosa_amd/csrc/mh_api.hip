@@ -253,9 +253,16 @@ void mh_shutdown(mh_ctx * ctx)
   }
   (void)mh_enter(ctx);
   mhi::shard_ctx_gone(ctx);
-  mhi::place_ctx_gone(ctx);
-  mhi::pose_graph_ctx_gone(ctx);
-  mhi::keyframes_ctx_gone(ctx);
+  if (!ctx->owned.empty()) {
+    // the handles that may outlive the context give their memory back while it is alive: one wait, then each in turn
+    (void)mh_enter(ctx);  // (the sharded handles may have left another device current)
+    (void)hipStreamSynchronize(ctx->stream);
+    for (CtxOwned * h : ctx->owned) {
+      h->ctx_gone();
+      h->ctx = nullptr;
+    }
+    ctx->owned.clear();
+  }
   if (ctx->stream) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
@@ -361,8 +368,9 @@ static int icp_alloc(mh_icp * icp)
     for (int ppw : {64, 128, 256, 512}) rows = std::max(rows, mh::class_loc_grid(ni, ppw));
     icp->ll_words = mh::ll_slot_words((rows + 15) & ~15);
   }
-  MH_HIP(ctx, AllocCache::alloc_pinned(reinterpret_cast<void **>(&icp->h_ll), icp->ll_words * sizeof(uint4) * kMaxPending));
-  MH_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&icp->d_h_ll), icp->h_ll, 0));
+  const size_t ll_bytes = icp->ll_words * sizeof(uint4) * kMaxPending;
+  MH_HIP(ctx, icp->h_ll.reserve(ll_bytes, ll_bytes));
+  MH_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&icp->d_h_ll), icp->h_ll.p, 0));
   return MH_OK;
 }
 
@@ -536,33 +544,20 @@ void mh_icp_destroy(mh_icp * icp)
     let_go(icp->ctx->align_batch.icps, icp->ctx->align_batch.n);
     icp->ctx->align_batch.n = 0;
   }
-  icp->d_rec.release(true);
-  icp->d_src.release(true);
-  icp->d_qda.release(true);
-  icp->d_mean.release(true);
-  icp->d_normal.release(true);
-  icp->d_status.release(true);
-  icp->d_partials.release(true);
-  icp->d_ticket.release(true);
-  icp->d_dbg.release(true);
-  icp->d_perm.release(true);
-  for (DevBuf * b : {&icp->d_origin, &icp->x_src, &icp->x_qda, &icp->x_mean, &icp->x_normal, &icp->x_status, &icp->x_origin, &icp->s_keys_a,
-                     &icp->s_keys_b, &icp->s_idx_a, &icp->s_idx_b, &icp->s_counts, &icp->s_temp, &icp->d_sums})
-    b->release(true);
   if (icp->h_counts) (void)hipHostFree(icp->h_counts);
-  if (icp->h_ll) AllocCache::free_pinned(icp->h_ll, icp->ll_words * sizeof(uint4) * kMaxPending);
-  icp->d_align.release(true);
-  if (icp->align.h) AllocCache::free_pinned(icp->align.h, align_stage_bytes(1));
-  icp->d_reloc.release(true);
-  if (icp->h_reloc) AllocCache::free_pinned(icp->h_reloc, icp->h_reloc_cap);
   if (icp->events_ready)
     for (auto & ev : icp->events)
       for (auto & e : ev) (void)hipEventDestroy(e);
-  if (icp->map) {
-    map_remove_reader(icp->map, icp->ctx);
-    mh_map_release(icp->map);
+  mh_ctx * const ctx = icp->ctx;
+  mh_map * const map = icp->map;
+  {
+    const DrainedScope drained;  // the stream was waited for above: the factor's buffers are idle
+    delete icp;
   }
-  delete icp;
+  if (map) {  // (the map's own blocks, if this was its last reference, go back behind an event like everything a map frees)
+    map_remove_reader(map, ctx);
+    mh_map_release(map);
+  }
 }
 
 size_t mh_icp_size(const mh_icp * icp) { return icp ? icp->n : 0; }
@@ -817,7 +812,7 @@ static bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, l
 {
   std::memset(&d, 0, sizeof(d));
   if (pc.seq == 0) return true;  // nothing was launched (empty cloud)
-  const uint4 * base = icp->h_ll + static_cast<size_t>(slot) * icp->ll_words;
+  const uint4 * base = icp->h_ll.as<uint4>() + static_cast<size_t>(slot) * icp->ll_words;
   mh::SpinBudget spin(spin_ns);  // one budget for the whole call
   auto get = [&](const uint4 * p, double & v) { return spin.until([&] { return mh::ll_read(reinterpret_cast<const uint64_t *>(p), pc.seq, v); }); };
   const int nent = icp->binary ? 91 : 28;
@@ -1208,11 +1203,7 @@ namespace
 constexpr size_t kScanPinnedBytes = sizeof(mh::ScanCounters) + mh_scan::kUniqueCached * sizeof(uint32_t) + 16;
 int scan_ensure_pinned(mh_scan * s)
 {
-  if (!s->h_c) {
-    void * p = nullptr;
-    MH_HIP(s->ctx, AllocCache::alloc_pinned(&p, kScanPinnedBytes));
-    s->h_c = static_cast<mh::ScanCounters *>(p);
-  }
+  MH_HIP(s->ctx, s->h_c.reserve(kScanPinnedBytes, kScanPinnedBytes));
   return MH_OK;
 }
 int scan_fetch_counters(mh_scan * s, bool with_unique = false)
@@ -1220,14 +1211,15 @@ int scan_fetch_counters(mh_scan * s, bool with_unique = false)
   mh_ctx * ctx = s->ctx;
   const int rcp = scan_ensure_pinned(s);
   if (rcp != MH_OK) return rcp;
-  MH_HIP(ctx, hipMemcpyAsync(s->h_c, s->d_counters.p, sizeof(s->c), hipMemcpyDeviceToHost, ctx->stream));
+  mh::ScanCounters * const h_c = s->h_c.as<mh::ScanCounters>();
+  MH_HIP(ctx, hipMemcpyAsync(h_c, s->d_counters.p, sizeof(s->c), hipMemcpyDeviceToHost, ctx->stream));
   size_t n_copy = 0;
   if (with_unique) {  // the distinct timestamps ride along: the caller asks for them next (IMU propagation), one wait instead of two
     n_copy = std::min(mh_scan::kUniqueCached, s->d_unique.cap / sizeof(uint32_t));
-    MH_HIP(ctx, hipMemcpyAsync(s->h_c + 1, s->d_unique.p, n_copy * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(h_c + 1, s->d_unique.p, n_copy * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  s->c = *s->h_c;
+  s->c = *h_c;
   s->c.n_unique_ns += s->c.has_max_ns;  // the value 0xFFFFFFFF travels as a flag (scan_kernels.hip: input_scatter_kernel)
   if (with_unique) s->n_unique_cached = s->c.n_unique_ns <= n_copy ? s->c.n_unique_ns : 0;
   return MH_OK;
@@ -1271,19 +1263,10 @@ void mh_scan_destroy(mh_scan * s)
   // a staged upload (mh_scan_prefetch, on the context's copy stream) may still be WRITING d_raw: it is not "drained" before
   // that copy has finished
   if (s->copy_done) (void)hipEventSynchronize(s->copy_done);
-  s->d_full_raw.release(true);
-  for (DevBuf * b : {&s->d_raw, &s->d_full, &s->d_geo_idx, &s->d_unique, &s->d_body, &s->d_ds, &s->d_kept_idx, &s->d_counters,
-                     &s->d_rt, &s->d_prep, &s->d_vox, &s->d_sensor, &s->d_imu, &s->d_pose})
-    b->release(true);
-  if (s->h_c) AllocCache::free_pinned(s->h_c, kScanPinnedBytes);  // the size it was taken with (flag words included)
-  if (s->copy_done) (void)hipEventDestroy(s->copy_done);
-  if (s->compute_mark) (void)hipEventDestroy(s->compute_mark);
-  if (s->h_stage) AllocCache::free_pinned(s->h_stage, s->h_stage_cap);
-  if (s->rt_done) {
-    (void)hipEventSynchronize(s->rt_done);
-    (void)hipEventDestroy(s->rt_done);
-  }
-  if (s->h_rt) AllocCache::free_pinned(s->h_rt, s->h_rt_cap);
+  if (s->rt_done) (void)hipEventSynchronize(s->rt_done);
+  for (hipEvent_t ev : {s->copy_done, s->compute_mark, s->rt_done})
+    if (ev) (void)hipEventDestroy(ev);
+  const DrainedScope drained;
   delete s;
 }
 
@@ -1358,23 +1341,18 @@ static int mh_scan_prefetch_impl(mh_scan * s, const mh_ouster_point * raw, size_
   MH_HIP(ctx, hipStreamWaitEvent(copy_stream, s->compute_mark, 0));
   g_mh_stream = copy_stream;  // what this call allocates / frees is ordered by the copy stream
   const size_t bytes = (n ? n : 1) * sizeof(mh_ouster_point);
-  if (bytes > s->h_stage_cap) {
+  if (bytes > s->h_stage.cap) {
     // pinned staging comes from the process-wide cache in 1 MiB classes (pinning 4 MiB costs ~2 ms: a front end that lives for
     // one sequence must not pay it again)
     MH_HIP(ctx, hipStreamSynchronize(copy_stream));  // an earlier copy may still read the old staging buffer
-    if (s->h_stage) AllocCache::free_pinned(s->h_stage, s->h_stage_cap);
-    s->h_stage = nullptr;
-    s->h_stage_cap = 0;
-    const size_t cap = (bytes + (size_t(1) << 20) - 1) & ~((size_t(1) << 20) - 1);
-    MH_HIP(ctx, AllocCache::alloc_pinned(&s->h_stage, cap));
-    s->h_stage_cap = cap;
+    MH_HIP(ctx, s->h_stage.reserve(bytes, (bytes + (size_t(1) << 20) - 1) & ~((size_t(1) << 20) - 1)));
   }
   s->prefetch_valid = false;
   MH_HIP(ctx, hipStreamSynchronize(copy_stream));  // the previous cloud staged here has left the buffer
   MH_HIP(ctx, s->d_raw.reserve(bytes, copy_stream, false));
   if (n) {
-    std::memcpy(s->h_stage, raw, n * sizeof(mh_ouster_point));
-    MH_HIP(ctx, hipMemcpyAsync(s->d_raw.p, s->h_stage, n * sizeof(mh_ouster_point), hipMemcpyHostToDevice, copy_stream));
+    std::memcpy(s->h_stage.p, raw, n * sizeof(mh_ouster_point));
+    MH_HIP(ctx, hipMemcpyAsync(s->d_raw.p, s->h_stage.p, n * sizeof(mh_ouster_point), hipMemcpyHostToDevice, copy_stream));
   }
   MH_HIP(ctx, hipEventRecord(s->copy_done, copy_stream));
   s->n_prefetched = n;
@@ -1470,7 +1448,7 @@ static int mh_scan_get_unique_ns_impl(const mh_scan * s, uint32_t * out, size_t 
   if (!out) return MH_OK;
   if (capacity < *n_out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_get_unique_ns: buffer too small");
   if (s->n_unique_cached == *n_out) {  // came back with the counters of mh_scan_prepare_input
-    std::memcpy(out, s->h_c + 1, *n_out * sizeof(uint32_t));
+    std::memcpy(out, s->h_c.as<mh::ScanCounters>() + 1, *n_out * sizeof(uint32_t));
     return MH_OK;
   }
   MH_HIP(ctx, mh_enter(ctx));
@@ -1481,6 +1459,16 @@ static int mh_scan_get_unique_ns_impl(const mh_scan * s, uint32_t * out, size_t 
 int mh_scan_get_unique_ns(const mh_scan * s, uint32_t * out, size_t capacity, size_t * n_out)
 {
   return guarded(s ? s->ctx : nullptr, "mh_scan_get_unique_ns", [&]() -> int { return mh_scan_get_unique_ns_impl(s, out, capacity, n_out); });
+}
+
+// the scan's pinned transfer block (h_rt), at least `bytes` large and no longer read by an earlier call's copy kernel
+static int scan_rt_block(mh_scan * s, size_t bytes)
+{
+  mh_ctx * ctx = s->ctx;
+  if (s->rt_done) MH_HIP(ctx, hipEventSynchronize(s->rt_done));  // the previous call's copy out of the block (long done)
+  MH_HIP(ctx, s->h_rt.reserve(bytes));
+  if (!s->rt_done) MH_HIP(ctx, hipEventCreateWithFlags(&s->rt_done, hipEventDisableTiming));
+  return MH_OK;
 }
 
 static int mh_scan_deskew_impl(mh_scan * s, const float * Rt12, size_t n_groups)
@@ -1501,22 +1489,13 @@ static int mh_scan_deskew_impl(mh_scan * s, const float * Rt12, size_t n_groups)
   {
     // the poses leave the caller's buffer here, on the host: pinned block -> device in stream order, no wait
     const size_t bytes = n_groups * 12 * sizeof(float);
-    if (s->rt_done) MH_HIP(ctx, hipEventSynchronize(s->rt_done));  // the previous call's copy out of the block (long done)
-    if (bytes > s->h_rt_cap) {
-      size_t cap = size_t(64) << 10;
-      while (cap < bytes) cap <<= 1;
-      if (s->h_rt) AllocCache::free_pinned(s->h_rt, s->h_rt_cap);
-      s->h_rt = nullptr;
-      s->h_rt_cap = 0;
-      MH_HIP(ctx, AllocCache::alloc_pinned(&s->h_rt, cap));
-      s->h_rt_cap = cap;
-    }
-    if (!s->rt_done) MH_HIP(ctx, hipEventCreateWithFlags(&s->rt_done, hipEventDisableTiming));
-    std::memcpy(s->h_rt, Rt12, bytes);
+    const int rcb = scan_rt_block(s, bytes);
+    if (rcb != MH_OK) return rcb;
+    std::memcpy(s->h_rt.p, Rt12, bytes);
     // a copy KERNEL reading the mapped block, not hipMemcpyAsync: a small host-to-device copy call was seen to block its caller
     // for 0.1-0.4 ms whenever another thread's 4 MiB upload (mh_scan_prefetch of the next cloud) was in flight
     void * d_src = nullptr;
-    MH_HIP(ctx, hipHostGetDevicePointer(&d_src, s->h_rt, 0));
+    MH_HIP(ctx, hipHostGetDevicePointer(&d_src, s->h_rt.p, 0));
     MH_HIP(ctx, mh::launch_copy16(d_src, s->d_rt.p, (bytes + 15) & ~size_t(15), ctx->stream));
     MH_HIP(ctx, hipEventRecord(s->rt_done, ctx->stream));
   }
@@ -1529,24 +1508,6 @@ static int mh_scan_deskew_impl(mh_scan * s, const float * Rt12, size_t n_groups)
 int mh_scan_deskew(mh_scan * s, const float * Rt12, size_t n_groups)
 {
   return guarded(s ? s->ctx : nullptr, "mh_scan_deskew", [&]() -> int { return mh_scan_deskew_impl(s, Rt12, n_groups); });
-}
-
-// the scan's pinned transfer block (h_rt), at least `bytes` large and no longer read by an earlier call's copy kernel
-static int scan_rt_block(mh_scan * s, size_t bytes)
-{
-  mh_ctx * ctx = s->ctx;
-  if (s->rt_done) MH_HIP(ctx, hipEventSynchronize(s->rt_done));  // the previous call's copy out of the block (long done)
-  if (bytes > s->h_rt_cap) {
-    size_t cap = size_t(64) << 10;
-    while (cap < bytes) cap <<= 1;
-    if (s->h_rt) AllocCache::free_pinned(s->h_rt, s->h_rt_cap);
-    s->h_rt = nullptr;
-    s->h_rt_cap = 0;
-    MH_HIP(ctx, AllocCache::alloc_pinned(&s->h_rt, cap));
-    s->h_rt_cap = cap;
-  }
-  if (!s->rt_done) MH_HIP(ctx, hipEventCreateWithFlags(&s->rt_done, hipEventDisableTiming));
-  return MH_OK;
 }
 
 static int mh_scan_deskew_imu_impl(mh_scan * s, const mh_imu_segment * seg, size_t n_seg, double header_ts, const double gravity[3],
@@ -1576,7 +1537,7 @@ static int mh_scan_deskew_imu_impl(mh_scan * s, const mh_imu_segment * seg, size
     // mapped block itself under the kernel: every workgroup stages all of it, 512 times for a cloud with per-point timestamps
     const int rcb = scan_rt_block(s, sizeof(mh::DeskewImuBlock));
     if (rcb != MH_OK) return rcb;
-    auto * b = static_cast<mh::DeskewImuBlock *>(s->h_rt);
+    auto * b = static_cast<mh::DeskewImuBlock *>(s->h_rt.p);
     b->header_ts = header_ts;
     std::memcpy(b->gravity, gravity, sizeof(b->gravity));
     std::memcpy(b->R_Le_W, R_Le_W, sizeof(b->R_Le_W));
@@ -1587,7 +1548,7 @@ static int mh_scan_deskew_imu_impl(mh_scan * s, const mh_imu_segment * seg, size
     std::memcpy(b->seg, seg, n_seg * sizeof(mh_imu_segment));
     const size_t bytes = (offsetof(mh::DeskewImuBlock, seg) + n_seg * sizeof(mh_imu_segment) + 15) & ~size_t(15);
     void * d_src = nullptr;
-    MH_HIP(ctx, hipHostGetDevicePointer(&d_src, s->h_rt, 0));
+    MH_HIP(ctx, hipHostGetDevicePointer(&d_src, s->h_rt.p, 0));
     MH_HIP(ctx, mh::launch_copy16(d_src, s->d_imu.p, bytes, ctx->stream));
     MH_HIP(ctx, hipEventRecord(s->rt_done, ctx->stream));
   }

@@ -3,6 +3,7 @@
 // the boundary.
 #pragma once
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -103,6 +104,18 @@ struct AlignChain : ChainMembers
   void * h = nullptr, * d = nullptr;
 };
 
+// A handle that may outlive its context: it is listed on the context from create to destroy.  mh_shutdown waits for the stream
+// once, then tells every listed handle (ctx_gone: give the device and pinned memory back while the context is alive) and leaves
+// it with ctx == nullptr; from then on every entry point refuses the handle (ctx_alive) and its destroy just deletes it.
+struct CtxOwned
+{
+  mh_ctx * ctx = nullptr;
+  virtual void ctx_gone() = 0;
+
+protected:
+  ~CtxOwned() = default;
+};
+
 struct mh_ctx
 {
   int device = 0;
@@ -127,12 +140,8 @@ struct mh_ctx
   // the communicators whose rounds run on it
   std::vector<mh_shard_icp *> shard_factors;
   std::vector<mh_shard_comm *> shard_comms;
-  // ... and from the place-recognition databases created on it (place_api.hip)
-  std::vector<mh_place_db *> place_dbs;
-  // ... and from the pose graphs created on it (pose_graph_api.hip)
-  std::vector<mh_pose_graph *> pose_graphs;
-  // ... and from the keyframe cloud stores created on it (keyframes_api.hip)
-  std::vector<mh_keyframes *> keyframe_stores;
+  // ... and the handles that may outlive it (CtxOwned: place databases, pose graphs, keyframe stores)
+  std::vector<CtxOwned *> owned;
 };
 
 // The stream of the context the calling thread is working for (set by mh_enter at every entry point): what the allocation
@@ -143,12 +152,42 @@ inline hipError_t mh_enter(const mh_ctx * ctx)
   g_mh_stream = ctx->stream;
   return hipSetDevice(ctx->device);
 }
+// While one of these lives, the blocks the calling thread frees go back to the cache as drained (AllocCache::free): a destroy
+// function constructs it AFTER it has waited for every stream that touched the handle's buffers, around the `delete` that
+// runs their destructors.
+inline thread_local bool g_mh_drained = false;
+struct DrainedScope
+{
+  const bool was = g_mh_drained;
+  DrainedScope() { g_mh_drained = true; }
+  DrainedScope(const DrainedScope &) = delete;
+  DrainedScope & operator=(const DrainedScope &) = delete;
+  ~DrainedScope() { g_mh_drained = was; }
+};
 
 inline int fail(const mh_ctx * ctx, int code, const std::string & msg)
 {
   g_mh_err = msg;
   if (ctx) const_cast<mh_ctx *>(ctx)->err = msg;
   return code;
+}
+// CtxOwned: listed at create, unlisted at destroy (a no-op once the context is gone), and what every other entry point asks first
+// (noun: "database", "graph", "store")
+inline void ctx_register(CtxOwned * h, mh_ctx * ctx)
+{
+  h->ctx = ctx;
+  ctx->owned.push_back(h);
+}
+inline void ctx_unregister(CtxOwned * h)
+{
+  if (!h->ctx) return;
+  auto & v = h->ctx->owned;
+  v.erase(std::remove(v.begin(), v.end(), h), v.end());
+}
+inline int ctx_alive(const CtxOwned * h, const char * who, const char * noun)
+{
+  if (h->ctx) return MH_OK;
+  return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the " + noun + "'s context was shut down; the handle can only be destroyed");
 }
 inline int hip_fail(const mh_ctx * ctx, hipError_t e, const char * what)
 {
@@ -256,8 +295,9 @@ public:
   }
   // drained: the caller has already waited for every stream that ever touched the block (a factor's or a scan's own
   // buffers after a synchronisation of their context's stream — and of the copy stream where one wrote them): it can be
-  // handed out at once
-  static void free(void * p, bool drained = false)
+  // handed out at once.  The default is what the enclosing DrainedScope says (none: not drained)
+  // (one copy per translation unit, not one per member of every handle's destructor)
+  __attribute__((noinline)) static void free(void * p, bool drained = g_mh_drained)
   {
     if (!p) return;
     Block b{0, 0};
@@ -308,33 +348,6 @@ public:
       if (c.ev) event_pool()[b.dev].push_back(c.ev);  // (the block itself goes back to the runtime below: hipFree waits for the device)
     }
     (void)hipFree(p);
-  }
-  // pinned, mapped result rings (one fixed size)
-  static hipError_t alloc_pinned(void ** out, size_t bytes)
-  {
-    {
-      std::lock_guard<std::mutex> g(mu());
-      auto & v = pinned()[bytes];
-      if (!v.empty()) {
-        *out = v.back();
-        v.pop_back();
-        return hipSuccess;
-      }
-    }
-    return hipHostMalloc(out, bytes, hipHostMallocMapped);
-  }
-  static void free_pinned(void * p, size_t bytes)
-  {
-    if (!p) return;
-    {
-      std::lock_guard<std::mutex> g(mu());
-      auto & v = pinned()[bytes];
-      if (v.size() < 64) {
-        v.push_back(p);
-        return;
-      }
-    }
-    (void)hipHostFree(p);
   }
   // context bookkeeping (mh_init / mh_shutdown): per device, under the cache mutex
   static void context_created(int dev)
@@ -389,6 +402,40 @@ public:
   }
 
 private:
+  friend struct PinnedBuf;
+  // pinned, mapped blocks, recycled by their EXACT size (PinnedBuf is the only caller)
+  static hipError_t alloc_pinned(void ** out, size_t bytes)
+  {
+    {
+      std::lock_guard<std::mutex> g(mu());
+      auto & v = pinned()[bytes];
+      if (!v.empty()) {
+        *out = v.back();
+        v.pop_back();
+        return hipSuccess;
+      }
+    }
+    static const bool trace = std::getenv("MH_ALLOC_TRACE") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipError_t e = hipHostMalloc(out, bytes, hipHostMallocMapped);
+    if (trace)
+      std::fprintf(stderr, "AllocCache: hipHostMalloc(%zu) %.0f us (stream %p)\n", bytes,
+                   std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), static_cast<void *>(g_mh_stream));
+    return e;
+  }
+  static void free_pinned(void * p, size_t bytes)
+  {
+    if (!p) return;
+    {
+      std::lock_guard<std::mutex> g(mu());
+      auto & v = pinned()[bytes];
+      if (v.size() < 64) {
+        v.push_back(p);
+        return;
+      }
+    }
+    (void)hipHostFree(p);
+  }
   static std::unordered_map<int, int> & contexts_of()
   {
     static std::unordered_map<int, int> m;
@@ -530,11 +577,42 @@ struct DevTemp
   operator T *() const { return p; }
 };
 
-// Growable device buffer
+// Growable device buffer.  Owns its block: move-only, and the destructor gives the block back to the cache (as drained inside a
+// DrainedScope, behind an event otherwise).
 struct DevBuf
 {
   void * p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf & operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf && o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DevBuf & operator=(DevBuf && o) noexcept
+  {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~DevBuf()
+  {
+    if (p) AllocCache::free(p);
+  }
+  // exactly `bytes` (rounded by the cache alone), for the blocks of fixed size; what was held before is released
+  hipError_t alloc(size_t bytes)
+  {
+    release();
+    const hipError_t e = AllocCache::alloc(&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+  template <typename T>
+  T * as() const
+  {
+    return static_cast<T *>(p);
+  }
   hipError_t reserve(size_t bytes, hipStream_t stream, bool keep)
   {
     if (bytes <= cap) return hipSuccess;
@@ -547,18 +625,64 @@ struct DevBuf
       e = hipMemcpyAsync(np, p, cap, hipMemcpyDeviceToDevice, stream);
       if (e == hipSuccess) e = hipStreamSynchronize(stream);
       if (e != hipSuccess) {
-        AllocCache::free(np);
+        AllocCache::free(np, false);
         return e;
       }
     }
-    if (p) AllocCache::free(p);
+    if (p) AllocCache::free(p, false);  // (growth is mid-life: work on the old block may be in flight)
     p = np;
     cap = ncap;
     return hipSuccess;
   }
-  void release(bool drained = false)
+  void release(bool drained = g_mh_drained)
   {
     if (p) AllocCache::free(p, drained);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// Pinned (mapped) host block from the cache: the pinned counterpart of DevBuf.  It remembers the size it was taken with, which
+// is the size the cache files it under again.
+struct PinnedBuf
+{
+  void * p = nullptr;
+  size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf & operator=(const PinnedBuf &) = delete;
+  PinnedBuf(PinnedBuf && o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  PinnedBuf & operator=(PinnedBuf && o) noexcept
+  {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~PinnedBuf() { release(); }
+  // At least `bytes`; the contents are NOT kept, and nothing may still be reading the old block.  A block that grows is taken
+  // with `capacity` bytes (a fixed size, or a site's own rounding), by default with the power-of-two class from 64 KiB: the
+  // cache recycles by exact size, so sizes that repeat are what makes it hit.
+  hipError_t reserve(size_t bytes, size_t capacity = 0)
+  {
+    if (bytes <= cap) return hipSuccess;
+    if (!capacity)
+      for (capacity = size_t(64) << 10; capacity < bytes;) capacity <<= 1;
+    release();
+    const hipError_t e = AllocCache::alloc_pinned(&p, capacity);
+    if (e == hipSuccess) cap = capacity;
+    return e;
+  }
+  template <typename T>
+  T * as() const
+  {
+    return static_cast<T *>(p);
+  }
+  void release()
+  {
+    AllocCache::free_pinned(p, cap);
     p = nullptr;
     cap = 0;
   }
@@ -573,7 +697,7 @@ struct mh_scan
   bool keep_raw = false, raw_valid = false;
   DevBuf d_sensor;       // other sensors (mh_scan_prepare_input_layout): raw records, organise-by-ring scratch
   DevBuf d_prep, d_vox;  // scratch of launch_prepare_input / launch_preprocess (scan_device.hpp: prepare_layout, voxel_layout)
-  mh::ScanCounters * h_c = nullptr;  // pinned landing buffer: the device counters, then the first kUniqueCached distinct timestamps
+  PinnedBuf h_c;  // pinned landing buffer: the device counters (a ScanCounters), then the first kUniqueCached distinct timestamps
   static constexpr size_t kUniqueCached = 4096;
   size_t n_unique_cached = 0;        // how many of unique_ns_ sit behind h_c (0 = ask the device)
   mh::ScanCounters c{};
@@ -582,13 +706,12 @@ struct mh_scan
   // mh_scan_prefetch: the NEXT cloud staged (pinned buffer -> d_raw on a copy stream of its own) while another scan is processed
   hipEvent_t copy_done = nullptr;
   hipEvent_t compute_mark = nullptr;  // recorded on the compute stream at every prefetch: the copy stream queues behind it
-  void * h_stage = nullptr;
-  size_t h_stage_cap = 0, n_prefetched = 0;
+  PinnedBuf h_stage;
+  size_t n_prefetched = 0;
   bool prefetch_valid = false;
   // mh_scan_deskew: the poses travel through a pinned block of the scan's own, so the call neither touches the caller's
   // (pageable) buffer from the stream nor waits for it
-  void * h_rt = nullptr;
-  size_t h_rt_cap = 0;
+  PinnedBuf h_rt;
   hipEvent_t rt_done = nullptr;
   // mh_scan_deskew_imu: the IMU intervals travel the same way (h_rt -> d_imu); d_pose = [timestamps | double[12] per group], the
   // table the photometric frame and mh_scan_get_deskew_poses read; the float cast goes into d_rt, where K1 reads it
@@ -599,13 +722,13 @@ struct mh_scan
 // >= 128 (mh_scan_prepare_input_layout), [1] deskew_pose_kernel met a timestamp behind the last IMU interval
 inline uint32_t * scan_pinned_flag(const mh_scan * s)
 {
-  return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(s->h_c) + sizeof(mh::ScanCounters) + mh_scan::kUniqueCached * sizeof(uint32_t));
+  return reinterpret_cast<uint32_t *>(s->h_c.as<char>() + sizeof(mh::ScanCounters) + mh_scan::kUniqueCached * sizeof(uint32_t));
 }
 // for the calls that have just waited for the device: what the pose kernel could not report by throwing (lidar/manager.cpp:469-476
 // runs off the end of the IMU buffer there)
 inline int scan_imu_error(const mh_scan * s, const mh_ctx * ctx, const char * who)
 {
-  if (s && s->imu_deskewed && s->h_c && scan_pinned_flag(s)[1])
+  if (s && s->imu_deskewed && s->h_c.p && scan_pinned_flag(s)[1])
     return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": deskewPoints: IMU samples end before the last point of the cloud");
   return MH_OK;
 }
@@ -620,7 +743,7 @@ struct mh_map
   double inv_leaf = 0, min_sq = 0;
   DevBuf d_table, d_cells, d_buckets, d_qbuckets, d_vox, d_lru;
   size_t table_cap = 0, vox_cap = 0, block_cap = 0;  // capacities in entries (table slots, voxels, blocks)
-  mh::MapState * d_state = nullptr;                  // device counters the kernels maintain
+  DevBuf d_state;                                    // device counters the kernels maintain (a MapState)
   mh::MapState * h_state = nullptr;                  // pinned host copy
   uint32_t n_voxels = 0, n_blocks = 0;
   uint64_t n_points = 0, lru_counter = 0;
@@ -628,8 +751,7 @@ struct mh_map
   DevBuf s_in, s_pts, s_group, s_seg_vid, s_seg_added, s_blk_new, s_flags, s_pos, s_temp, s_rt, s_shard;
   DevBuf s_preview;  // mh_map_preview_insert*: [too close | voxel full] per segment (n words each), then n outcome bytes
   DevBuf s_carve_img, s_carve_vox;  // mh_map_carve*: the observation image (+ its counter); removed / tested / emptied per voxel
-  void * h_in = nullptr;  // pinned staging of a host batch
-  size_t h_in_cap = 0;
+  PinnedBuf h_in;  // pinned staging of a host batch
   int64_t inserts = 0, upload_bytes = 0, purges = 0;
   int n_off = 0;
   int8_t off[27][3];
@@ -641,17 +763,26 @@ struct mh_map
 
 // mh_keyframes_*: the clouds of the keyframes, each in its own frame, packed float4 (x, y, z, 1) in one device arena of fixed size
 // (keyframes_api.hip).  An entry holds no pose.  mh_map_rebuild_from_keyframes (map_api.hip) reads it.
-struct mh_keyframes
+struct mh_keyframes final : CtxOwned
 {
-  mh_ctx * ctx = nullptr;  // null: mh_shutdown of the context ran first (keyframes_ctx_gone), the handle can only be destroyed
   mh_keyframes_config cfg{};
-  float4 * d_arena = nullptr;                // capacity_points entries
-  unsigned long long * d_offsets = nullptr;  // capacity_keyframes + 1: entry i is points [d_offsets[i], d_offsets[i + 1]) of the arena
-  std::vector<uint64_t> offsets{0};          // the same on the host: size() + 1 entries
+  std::vector<uint64_t> offsets{0};  // d_offsets on the host: size() + 1 entries
   std::vector<int64_t> tags;
-  DevBuf d_in;             // a host batch, packed float4
-  void * h_io = nullptr;   // pinned staging of a host batch / of a read-back
-  size_t h_io_cap = 0;
+  // what goes back when the context does
+  struct Memory
+  {
+    DevBuf d_arena;    // float4: capacity_points entries
+    DevBuf d_offsets;  // unsigned long long: capacity_keyframes + 1, entry i is points [d_offsets[i], d_offsets[i + 1]) of the arena
+    DevBuf d_in;       // a host batch, packed float4
+    PinnedBuf h_io;    // pinned staging of a host batch / of a read-back
+  } mem;
+  float4 * arena() const { return mem.d_arena.as<float4>(); }
+  void ctx_gone() override
+  {
+    mem = Memory{};
+    tags.clear();
+    offsets.assign(1, 0);
+  }
 };
 
 inline void map_add_reader(mh_map * m, mh_ctx * c)
@@ -734,7 +865,7 @@ struct mh_icp
   // K4 follows its K3 on the context's stream, so one of each serves every call of the factor
   DevBuf d_rec;
   bool ordered = false;  // d_src / per-point state are in Morton order, d_perm maps back
-  uint4 * h_ll = nullptr;     // pinned, mapped ring of flagged-word slots (icp_device.hpp): what a plain call's kernels publish
+  PinnedBuf h_ll;             // pinned, mapped ring of flagged-word slots (icp_device.hpp, uint4): what a plain call's kernels publish
   uint4 * d_h_ll = nullptr;   // its device-side address
   size_t ll_words = 0;        // 16-byte words per slot
   PendingCall pending[kMaxPending];
@@ -756,9 +887,9 @@ struct mh_icp
   uint32_t n_movers = 0;
   Held held = Held::none;  // set and cleared with n_pending: hold(), let_go()
   // mh_icp_align (chain_api.hip): the factor's own alignment chain, capacity 1.  Its device block comes from the allocation
-  // cache (d_align; align.d points into it), its pinned staging (align.h) from AllocCache::alloc_pinned at the first call;
-  // mh_icp_destroy gives both back.
+  // cache (d_align; align.d points into it), and so does its pinned staging (h_align; align.h), at the first call.
   DevBuf d_align;
+  PinnedBuf h_align;
   AlignChain align{1};
   // which cloud this is: a fresh number for every created factor, the source's for a clone (mh_icp_relocalise_batch asks
   // whether its work factors are clones of the factor it scores)
@@ -767,8 +898,7 @@ struct mh_icp
   // (d_reloc), its mapped pinned block [winners | poses | scores] (h_reloc), and the call in flight.  Like an alignment it
   // holds the factor (Held::score) until mh_icp_wait collects it; it touches nothing else of the factor.
   DevBuf d_reloc;
-  void * h_reloc = nullptr;
-  size_t h_reloc_cap = 0;
+  PinnedBuf h_reloc;
   struct ScoreCall
   {
     size_t n_poses = 0;
@@ -816,13 +946,6 @@ int prepare(mh_icp * icp, const double R_src[9], const double t_src[3], const do
             mh_icp_result * out, mh::IcpArgs & a, mh::LocArgs & l);
 // shard_api.hip: called by mh_shutdown(ctx) so that the sharded handles listed on ctx let go of it
 void shard_ctx_gone(mh_ctx * ctx);
-// place_api.hip: likewise for the place-recognition databases listed on ctx — they give their memory back while the context is
-// alive and are left with ctx == nullptr: every entry point refuses them, mh_place_db_destroy just deletes them
-void place_ctx_gone(mh_ctx * ctx);
-// pose_graph_api.hip: likewise for the pose graphs listed on ctx
-void pose_graph_ctx_gone(mh_ctx * ctx);
-// keyframes_api.hip: likewise for the keyframe cloud stores listed on ctx
-void keyframes_ctx_gone(mh_ctx * ctx);
 // a call's DeviceResult from its flagged words in pending slot `slot` (spin_ns > 0: wait up to that long for words that have
 // not arrived); false = something is still missing
 bool collect_call(const mh_icp * icp, int slot, const PendingCall & pc, long spin_ns, mh::DeviceResult & d);

@@ -39,15 +39,7 @@ struct PhotoFrame  // include/mimosa/lidar/photometric_utils.hpp:42-92, shared_p
   size_t n_points = 0;
   DevBuf d_points, d_intensity, d_range, d_dx, d_dy, d_mask, d_idx, d_proj, d_yaw, d_pose_ns, d_pose_Rt;  // (d_pose_Rt unused: the poses sit behind the timestamps in d_pose_ns)
   size_t pose_rt_offset = 0;
-  void * h_pose = nullptr;  // pinned: the pose table and its timestamps on their way to the device (no pageable copy, no wait)
-  size_t h_pose_cap = 0;
-  void release_buffers()
-  {
-    for (DevBuf * b : {&d_points, &d_intensity, &d_range, &d_dx, &d_dy, &d_mask, &d_idx, &d_proj, &d_yaw, &d_pose_ns, &d_pose_Rt})
-      b->release();
-    if (h_pose) AllocCache::free_pinned(h_pose, h_pose_cap);
-    h_pose = nullptr;
-  }
+  PinnedBuf h_pose;  // pinned: the pose table and its timestamps on their way to the device (no pageable copy, no wait)
 };
 
 void frame_release(PhotoFrame * f)
@@ -56,7 +48,6 @@ void frame_release(PhotoFrame * f)
   if (f->refs.fetch_sub(1) == 1) {
     (void)mh_enter(f->ctx);
     (void)hipStreamSynchronize(f->ctx->stream);
-    f->release_buffers();
     delete f;
   }
 }
@@ -77,23 +68,22 @@ constexpr size_t kBatchBytes = (kBatchDescBytes + kBatchPrefixBytes + kBatchCoun
 struct PhotoBatch
 {
   int members = 0;  // factors not yet collected or destroyed
-  void * h = nullptr;
+  PinnedBuf h;
   void * d = nullptr;  // device address of h
   unsigned int seq = 0;  // completion number the launch publishes (0: wait on the stream)
   bool timed = false;
   hipEvent_t ev[2] = {nullptr, nullptr};
-  mh::PhotoFactorDesc * descs() const { return static_cast<mh::PhotoFactorDesc *>(h); }
-  int32_t * prefix() const { return reinterpret_cast<int32_t *>(static_cast<char *>(h) + kBatchDescBytes); }
-  mh::PhotoCounters * counters() const { return reinterpret_cast<mh::PhotoCounters *>(static_cast<char *>(h) + kBatchDescBytes + kBatchPrefixBytes); }
-  unsigned int * host_seq() const { return reinterpret_cast<unsigned int *>(static_cast<char *>(h) + kBatchDescBytes + kBatchPrefixBytes + kBatchCounterBytes); }
-  template <class T> T * dev(T * host_ptr) const { return reinterpret_cast<T *>(static_cast<char *>(d) + (reinterpret_cast<char *>(host_ptr) - static_cast<char *>(h))); }
+  mh::PhotoFactorDesc * descs() const { return h.as<mh::PhotoFactorDesc>(); }
+  int32_t * prefix() const { return reinterpret_cast<int32_t *>(h.as<char>() + kBatchDescBytes); }
+  mh::PhotoCounters * counters() const { return reinterpret_cast<mh::PhotoCounters *>(h.as<char>() + kBatchDescBytes + kBatchPrefixBytes); }
+  unsigned int * host_seq() const { return reinterpret_cast<unsigned int *>(h.as<char>() + kBatchDescBytes + kBatchPrefixBytes + kBatchCounterBytes); }
+  template <class T> T * dev(T * host_ptr) const { return reinterpret_cast<T *>(static_cast<char *>(d) + (reinterpret_cast<char *>(host_ptr) - h.as<char>())); }
 };
 
 // the stream has passed the launch (or never got it) when this is called
 void batch_release(PhotoBatch * b)
 {
   if (!b || --b->members > 0) return;
-  if (b->h) AllocCache::free_pinned(b->h, kBatchBytes);
   for (auto & e : b->ev)
     if (e) (void)hipEventDestroy(e);
   delete b;
@@ -123,10 +113,8 @@ struct mh_photo
   mh::PhotoCounters * d_counters = nullptr;
   DevBuf d_batch_ticket;    // finished blocks of a mh_photo_factor_linearize_batch launch (the launches share the stream)
   unsigned int batch_seq = 0;  // completion numbers of those launches
-  float * h_int_out = nullptr;  // pinned staging of the corrected intensities
-  size_t h_int_cap = 0;
-  char * h_stage = nullptr;     // pinned staging of detectFeatures' small transfers (candidate list, gather records)
-  size_t h_stage_cap = 0;
+  PinnedBuf h_int_out;  // pinned staging of the corrected intensities (float)
+  PinnedBuf h_stage;    // pinned staging of detectFeatures' small transfers (candidate list, gather records)
   PhotoFrame * frame = nullptr;
   PhotoFrame * next_frame = nullptr;  // built by mh_photo_preprocess_scan_begin, current after mh_photo_preprocess_commit
   mh_scan * next_scan = nullptr;      // ... the scan it was built from (its cloud receives the corrected intensities at the commit)
@@ -148,9 +136,8 @@ struct mh_photo_factor
   DevBuf d_Le, d_psi, d_npts, d_rows;
   // per-feature outputs of the kernel (statuses, new centres, Hessian sums): mapped pinned host memory the kernel writes
   // straight into — ~21 KB per linearize, no copy nodes behind the kernel
-  void * h_out = nullptr;
+  PinnedBuf h_out;
   void * d_out = nullptr;  // device address of h_out
-  size_t out_bytes = 0;
   bool pending = false, pending_timed = false;  // a linearize is enqueued and not yet collected
   DevBuf d_ticket;              // one counter: blocks of the linearize kernel that have finished
   unsigned int seq_counter = 0, pending_seq = 0;  // completion number the pending call publishes (0: wait on the stream)
@@ -175,12 +162,7 @@ void photo_release(mh_photo * p)
   if (p->cand_ev) (void)hipEventDestroy(p->cand_ev);
   if (p->next_ev) (void)hipEventDestroy(p->next_ev);
   if (p->scan_ev) (void)hipEventDestroy(p->scan_ev);
-  for (DevBuf * b : {&p->d_alt, &p->d_shift, &p->d_hp, &p->d_lp, &p->d_static, &p->d_raw_pts, &p->d_img_raw, &p->d_tmp_a, &p->d_tmp_b,
-                     &p->d_mask_raw, &p->d_yaw_valid, &p->d_int_out, &p->d_grad, &p->d_detmask, &p->d_xyz, &p->d_cand, &p->d_gather, &p->d_stamps, &p->d_proj_pre, &p->d_batch_ticket})
-    b->release();
   if (p->h_counters) (void)hipHostFree(p->h_counters);
-  if (p->h_int_out) (void)hipHostFree(p->h_int_out);
-  if (p->h_stage) (void)hipHostFree(p->h_stage);
   delete p;
 }
 
@@ -387,11 +369,8 @@ int preprocess_device(mh_photo * ph, PhotoFrame * fr, const mh_point32 * d_raw, 
     pose_bytes = n_groups ? b_ns + ((b_rt + 15) & ~size_t(15)) : 0;
   } else {
     const size_t b_ns = (n_groups * sizeof(uint32_t) + 255) & ~size_t(255), b_rt = n_groups * 12 * sizeof(double);
-    size_t cap = size_t(64) << 10;
-    while (cap < b_ns + b_rt) cap <<= 1;
-    MH_HIP(ctx, AllocCache::alloc_pinned(&fr->h_pose, cap));
-    fr->h_pose_cap = cap;
-    char * h = static_cast<char *>(fr->h_pose);
+    MH_HIP(ctx, fr->h_pose.reserve(std::max<size_t>(b_ns + b_rt, 1)));  // (a fresh frame: the block is always taken here)
+    char * h = fr->h_pose.as<char>();
     if (n_groups) {
       std::memcpy(h, unique_ns, n_groups * sizeof(uint32_t));
       std::memcpy(h + b_ns, T_Le_Lt, b_rt);
@@ -523,13 +502,7 @@ int preprocess_device(mh_photo * ph, PhotoFrame * fr, const mh_point32 * d_raw, 
 // synchronisation each)
 int photo_stage(mh_photo * ph, size_t bytes)
 {
-  if (ph->h_stage_cap >= bytes) return MH_OK;
-  if (ph->h_stage) (void)hipHostFree(ph->h_stage);
-  ph->h_stage = nullptr;
-  ph->h_stage_cap = 0;
-  const size_t cap = (bytes + bytes / 2 + 4095) & ~size_t(4095);
-  MH_HIP(ph->ctx, hipHostMalloc(reinterpret_cast<void **>(&ph->h_stage), cap, hipHostMallocDefault));
-  ph->h_stage_cap = cap;
+  MH_HIP(ph->ctx, ph->h_stage.reserve(bytes));
   return MH_OK;
 }
 
@@ -601,7 +574,7 @@ int detect_enqueue_candidates(mh_photo * ph, PhotoFrame * fr)
   // copy KERNELS writing the pinned block (small hipMemcpyAsync calls can block their caller behind another thread's upload,
   // see mh_scan_deskew)
   void * hd = nullptr;
-  MH_HIP(ctx, hipHostGetDevicePointer(&hd, ph->h_stage, 0));
+  MH_HIP(ctx, hipHostGetDevicePointer(&hd, ph->h_stage.p, 0));
   {
     // d_n's 16-byte neighbourhood lands at the start of the block; the reader picks the word at the same offset
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_n) & ~uintptr_t(15);
@@ -641,11 +614,11 @@ int detect_features_impl(mh_photo * ph, int num_to_detect, const double R_W_Be[9
   }
   frame_release(ph->cand_frame);
   ph->cand_frame = nullptr;
-  uint32_t * h_list = reinterpret_cast<uint32_t *>(ph->h_stage + 256);
+  uint32_t * h_list = reinterpret_cast<uint32_t *>(ph->h_stage.as<char>() + 256);
   const uint32_t n_list = [&] {  // the count's 16-byte neighbourhood was copied: same offset inside it
     const int n_blk_ = (npx + 255) / 256;
     const uintptr_t dn = reinterpret_cast<uintptr_t>(static_cast<uint32_t *>(ph->d_cand.p) + npx + n_blk_);
-    return reinterpret_cast<const uint32_t *>(ph->h_stage)[(dn & 15u) / 4];
+    return reinterpret_cast<const uint32_t *>(ph->h_stage.p)[(dn & 15u) / 4];
   }();
   if (n_list > prefix) {
     const uint32_t * d_all = static_cast<const uint32_t *>(ph->d_cand.p);
@@ -707,10 +680,10 @@ int detect_features_impl(mh_photo * ph, int num_to_detect, const double R_W_Be[9
     const int rcs = photo_stage(ph, b_uv + b_out + 16);
     if (rcs != MH_OK) return rcs;
     char * d = static_cast<char *>(ph->d_gather.p);
-    std::memcpy(ph->h_stage, uv.data(), uv.size() * 4);
+    std::memcpy(ph->h_stage.p, uv.data(), uv.size() * 4);
     {
       void * d_src = nullptr;  // (a copy kernel, see upload_pinned; b_uv is a multiple of 256 on both sides)
-      MH_HIP(ctx, hipHostGetDevicePointer(&d_src, ph->h_stage, 0));
+      MH_HIP(ctx, hipHostGetDevicePointer(&d_src, ph->h_stage.p, 0));
       MH_HIP(ctx, mh::launch_copy16(d_src, d, (uv.size() * 4 + 15) & ~size_t(15), ctx->stream));
     }
     MH_HIP(ctx, mh::launch_photo_gather(reinterpret_cast<const int2 *>(d), m_off, count, per_candidate, static_cast<const float *>(fr->d_intensity.p),
@@ -719,11 +692,11 @@ int detect_features_impl(mh_photo * ph, int num_to_detect, const double R_W_Be[9
                                         reinterpret_cast<int32_t *>(d + b_uv + b_win + b_rec), ctx->stream));
     {
       void * hd = nullptr;  // (a copy kernel writing the pinned block, see detect_enqueue_candidates)
-      MH_HIP(ctx, hipHostGetDevicePointer(&hd, ph->h_stage, 0));
+      MH_HIP(ctx, hipHostGetDevicePointer(&hd, ph->h_stage.p, 0));
       MH_HIP(ctx, mh::launch_copy16(d + b_uv, static_cast<char *>(hd) + b_uv, (b_out + 15) & ~size_t(15), ctx->stream));
     }
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const char * h = ph->h_stage + b_uv;
+    const char * h = ph->h_stage.as<char>() + b_uv;
     win.assign(reinterpret_cast<const float *>(h), reinterpret_cast<const float *>(h) + n_win);
     rec.assign(reinterpret_cast<const float *>(h + b_win), reinterpret_cast<const float *>(h + b_win) + n_rec);
     rec_idx.assign(reinterpret_cast<const int32_t *>(h + b_win + b_rec), reinterpret_cast<const int32_t *>(h + b_win + b_rec) + n_idx);
@@ -963,14 +936,8 @@ static int photo_finish_preprocess(mh_photo * photo, PhotoFrame * fr, mh_point32
   mh_ctx * ctx = photo->ctx;
   // corrected intensities back into the caller's cloud (:307-314)
   if (host_desk && n) {
-    if (photo->h_int_cap < n) {
-      if (photo->h_int_out) (void)hipHostFree(photo->h_int_out);
-      photo->h_int_out = nullptr;
-      photo->h_int_cap = 0;
-      MH_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&photo->h_int_out), (n + n / 2) * sizeof(float), hipHostMallocDefault));
-      photo->h_int_cap = n + n / 2;
-    }
-    MH_HIP(ctx, hipMemcpyAsync(photo->h_int_out, photo->d_int_out.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, photo->h_int_out.reserve(n * sizeof(float)));
+    MH_HIP(ctx, hipMemcpyAsync(photo->h_int_out.p, photo->d_int_out.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   {
@@ -1026,7 +993,7 @@ int mh_photo_preprocess(mh_photo * photo, const mh_point32 * points_raw, mh_poin
     if (rc != MH_OK) return rc;
     // the Frame keeps the cloud as it was handed over; the corrected intensities go to the caller's copy only (:115-116, :307-314)
     for (size_t i = 0; i < n; ++i) {
-      const float v = photo->h_int_out[i];
+      const float v = photo->h_int_out.as<float>()[i];
       if (v == v) points_deskewed[i].intensity = v;  // NaN = "no pixel"
     }
     return MH_OK;
@@ -1086,7 +1053,7 @@ static int photo_preprocess_scan(mh_photo * photo, mh_scan * scan, const double 
     if (resident) {
       // nothing to fetch: the timestamps sit in front of the poses in the scan's table
     } else if (n_groups && scan->n_unique_cached == n_groups) {  // the host copy that came back with mh_scan_prepare_input's counters
-      std::memcpy(uns.data(), scan->h_c + 1, n_groups * sizeof(uint32_t));
+      std::memcpy(uns.data(), scan->h_c.as<mh::ScanCounters>() + 1, n_groups * sizeof(uint32_t));
     } else {
       if (n_groups) MH_HIP(ctx, hipMemcpyAsync(uns.data(), scan->d_unique.p, n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
       MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1333,12 +1300,12 @@ static int photo_factor_build(mh_photo * photo, PhotoFrame * frame, const std::v
   // counts): the uploads run from memory that lives as long as the factor, so creating a factor does not wait for them.
   const size_t out_part = (nf * (2 + mh::kPhotoPartial) * sizeof(double) + nf * sizeof(int32_t) + 64 + 255) & ~size_t(255);
   const size_t b_Le = nf * mh::kPhotoMaxPatch * 3 * sizeof(double), b_ps = nf * mh::kPhotoMaxPatch * sizeof(double), b_np = nf * sizeof(int32_t);
-  f->out_bytes = (out_part + b_Le + b_ps + b_np + 64 + 4095) & ~size_t(4095);  // few size classes for the pinned cache
-  hipError_t e = AllocCache::alloc_pinned(&f->h_out, f->out_bytes);
+  const size_t out_bytes = (out_part + b_Le + b_ps + b_np + 64 + 4095) & ~size_t(4095);  // few size classes for the pinned cache
+  hipError_t e = f->h_out.reserve(out_bytes, out_bytes);
   int rc = MH_OK;
-  if (e == hipSuccess) e = hipHostGetDevicePointer(&f->d_out, f->h_out, 0);
+  if (e == hipSuccess) e = hipHostGetDevicePointer(&f->d_out, f->h_out.p, 0);
   if (e == hipSuccess) {
-    char * stage = static_cast<char *>(f->h_out) + out_part;
+    char * stage = f->h_out.as<char>() + out_part;
     double * Le = reinterpret_cast<double *>(stage);
     double * ps = reinterpret_cast<double *>(stage + b_Le);
     int32_t * np = reinterpret_cast<int32_t *>(stage + b_Le + b_ps);
@@ -1403,14 +1370,17 @@ void mh_photo_factor_destroy(mh_photo_factor * f)
   mh_ctx * ctx = f->photo->ctx;
   (void)mh_enter(ctx);
   (void)hipStreamSynchronize(ctx->stream);
-  for (DevBuf * b : {&f->d_Le, &f->d_psi, &f->d_npts, &f->d_rows, &f->d_ticket}) b->release(true);
-  if (f->h_out) AllocCache::free_pinned(f->h_out, f->out_bytes);
   if (f->pending) batch_release(f->batch);  // (after the stream synchronisation above: the launch is done)
   for (auto & e : f->ev)
     if (e) (void)hipEventDestroy(e);
-  frame_release(f->frame);
-  photo_release(f->photo);
-  delete f;
+  PhotoFrame * const frame = f->frame;
+  mh_photo * const photo = f->photo;
+  {
+    const DrainedScope drained;
+    delete f;
+  }
+  frame_release(frame);  // (their own blocks, if these were the last references, go back behind an event)
+  photo_release(photo);
 }
 
 size_t mh_photo_factor_size(const mh_photo_factor * f) { return f ? f->features.size() : 0; }
@@ -1505,7 +1475,7 @@ static int photo_linearize_enqueue(mh_photo_factor * f, const double R_b[9], con
     if (!timed && nf > 0) {  // (no kernel is launched for an empty factor)
       if (++f->seq_counter == 0) ++f->seq_counter;
       a.launch.seq = f->pending_seq = f->seq_counter;
-      __atomic_store_n(reinterpret_cast<unsigned int *>(static_cast<char *>(f->h_out) + seq_off), 0u, __ATOMIC_RELEASE);  // re-arm
+      __atomic_store_n(reinterpret_cast<unsigned int *>(f->h_out.as<char>() + seq_off), 0u, __ATOMIC_RELEASE);  // re-arm
     }
     f->photo->h_counters[1].project_throw = f->photo->h_counters[1].pose_missing = 0;
     if (timed && !f->ev[0]) {
@@ -1542,11 +1512,11 @@ static int photo_linearize_finish(mh_photo_factor * f, mh_photo_result * out)
     bool need_sync = want == 0;
     if (!need_sync) {  // spin on the completion number the kernel's last block publishes (mh_icp_wait does the same)
       const volatile unsigned int * flag =
-          batch ? batch->host_seq() : reinterpret_cast<const volatile unsigned int *>(static_cast<const char *>(f->h_out) + photo_seq_offset(nf));
+          batch ? batch->host_seq() : reinterpret_cast<const volatile unsigned int *>(f->h_out.as<const char>() + photo_seq_offset(nf));
       need_sync = !mh::spin_until([&] { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == want; }, 20000000L);  // 20 ms: fall back
     }
     if (need_sync) MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the end of the kernel makes its host writes visible
-    const double * new_centers = static_cast<const double *>(f->h_out);
+    const double * new_centers = f->h_out.as<const double>();
     f->partials.assign(new_centers + 2 * nf, new_centers + 2 * nf + nf * mh::kPhotoPartial);
     std::memcpy(f->statuses.data(), new_centers + 2 * nf + nf * mh::kPhotoPartial, nf * sizeof(int32_t));
     std::memset(out, 0, sizeof(*out));
@@ -1683,8 +1653,8 @@ static int photo_batch_enqueue(mh_photo_factor * const * factors, size_t n, cons
       batch_release(b);
     }
   } drop{B, ctx->stream};
-  MH_HIP(ctx, AllocCache::alloc_pinned(&B->h, kBatchBytes));
-  MH_HIP(ctx, hipHostGetDevicePointer(&B->d, B->h, 0));
+  MH_HIP(ctx, B->h.reserve(kBatchBytes, kBatchBytes));
+  MH_HIP(ctx, hipHostGetDevicePointer(&B->d, B->h.p, 0));
   mh::PhotoFactorDesc * descs = B->descs();
   int32_t * prefix = B->prefix();
   mh::PhotoCounters * counters = B->counters();

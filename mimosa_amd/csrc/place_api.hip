@@ -18,51 +18,41 @@ constexpr size_t kPlaceDescBytes = mh::kPlaceCells * sizeof(float);
 constexpr size_t kPlaceHostDescAt = sizeof(mh::PlaceBest);
 constexpr size_t kPlaceHostScoresAt = kPlaceHostDescAt + 4864;
 
-struct mh_place_db
+struct mh_place_db final : CtxOwned
 {
-  mh_ctx * ctx = nullptr;  // null: mh_shutdown of the context ran first (place_ctx_gone), the handle can only be destroyed
   mh_place_config cfg{};
   mh::PlaceParams P{};     // everything of the descriptor rule but R
   size_t size = 0;
   std::vector<int64_t> tags;
-  float * d_desc = nullptr;           // capacity x 1 200
-  double * d_norms = nullptr;         // capacity x 60
-  mh::PlaceScore * d_scores = nullptr;  // capacity
-  char * d_query = nullptr;           // [a descriptor, 4 864 B | its norms, 512 B | hits, 256 B]
-  DevBuf d_in;                        // a host batch, packed xyz
-  char * h = nullptr;                 // the pinned block
-  size_t h_bytes = 0;
-  void * h_in = nullptr;              // pinned staging of a host batch
-  size_t h_in_cap = 0;
+  // what goes back when the context does
+  struct Memory
+  {
+    DevBuf desc;     // float: capacity x 1 200
+    DevBuf norms;    // double: capacity x 60
+    DevBuf scores;   // PlaceScore: capacity
+    DevBuf query;    // [a descriptor, 4 864 B | its norms, 512 B | hits, 256 B]
+    DevBuf d_in;     // a host batch, packed xyz
+    PinnedBuf h;     // the pinned block
+    PinnedBuf h_in;  // pinned staging of a host batch
+  } mem;
+  float * d_desc() const { return mem.desc.as<float>(); }
+  double * d_norms() const { return mem.norms.as<double>(); }
+  mh::PlaceScore * d_scores() const { return mem.scores.as<mh::PlaceScore>(); }
+  char * d_query() const { return mem.query.as<char>(); }
+  char * h() const { return mem.h.as<char>(); }
+  void ctx_gone() override
+  {
+    mem = Memory{};
+    size = 0;
+    tags.clear();
+  }
 };
 constexpr size_t kPlaceQueryNormsAt = 4864, kPlaceQueryBestAt = kPlaceQueryNormsAt + 512, kPlaceQueryBytes = kPlaceQueryBestAt + sizeof(mh::PlaceBest);
 
 namespace
 {
-void place_release_device(mh_place_db * db)
-{
-  AllocCache::free(db->d_desc);
-  AllocCache::free(db->d_norms);
-  AllocCache::free(db->d_scores);
-  AllocCache::free(db->d_query);
-  db->d_desc = nullptr;
-  db->d_norms = nullptr;
-  db->d_scores = nullptr;
-  db->d_query = nullptr;
-  db->d_in.release();
-  if (db->h) AllocCache::free_pinned(db->h, db->h_bytes);
-  if (db->h_in) AllocCache::free_pinned(db->h_in, db->h_in_cap);
-  db->h = nullptr;
-  db->h_in = nullptr;
-  db->h_bytes = db->h_in_cap = 0;
-}
-
 // every entry point but destroy: a database whose context was shut down
-int place_alive(const mh_place_db * db, const char * who)
-{
-  if (!db->ctx) return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the database's context was shut down; the handle can only be destroyed");
-  return MH_OK;
-}
+int place_alive(const mh_place_db * db, const char * who) { return ctx_alive(db, who, "database"); }
 
 int place_check_R(const mh_ctx * ctx, const char * who, const double * R)
 {
@@ -107,19 +97,11 @@ int place_stage(mh_place_db * db, const float * xyz, size_t n, size_t stride)
 {
   mh_ctx * ctx = db->ctx;
   const size_t bytes = n * 3 * sizeof(float);
-  if (bytes > db->h_in_cap) {
-    size_t cap = size_t(64) << 10;
-    while (cap < bytes) cap <<= 1;
-    if (db->h_in) AllocCache::free_pinned(db->h_in, db->h_in_cap);  // (every call that used it has waited)
-    db->h_in = nullptr;
-    db->h_in_cap = 0;
-    MH_HIP(ctx, AllocCache::alloc_pinned(&db->h_in, cap));
-    db->h_in_cap = cap;
-  }
-  MH_HIP(ctx, db->d_in.reserve(bytes, ctx->stream, false));
-  float * h = static_cast<float *>(db->h_in);
+  MH_HIP(ctx, db->mem.h_in.reserve(bytes));  // (every call that used it has waited)
+  MH_HIP(ctx, db->mem.d_in.reserve(bytes, ctx->stream, false));
+  float * h = db->mem.h_in.as<float>();
   for (size_t i = 0; i < n; ++i) std::memcpy(h + 3 * i, xyz + i * stride, 3 * sizeof(float));
-  MH_HIP(ctx, hipMemcpyAsync(db->d_in.p, db->h_in, bytes, hipMemcpyHostToDevice, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(db->mem.d_in.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
   return MH_OK;
 }
 
@@ -127,11 +109,11 @@ int place_stage(mh_place_db * db, const float * xyz, size_t n, size_t stride)
 int place_describe_out(mh_place_db * db, const char * who, const float * d_src, size_t n, size_t stride, const double * R, float * desc)
 {
   mh_ctx * ctx = db->ctx;
-  const int rc = place_describe_to(db, who, d_src, n, stride, R, reinterpret_cast<float *>(db->d_query));
+  const int rc = place_describe_to(db, who, d_src, n, stride, R, reinterpret_cast<float *>(db->d_query()));
   if (rc != MH_OK) return rc;
-  MH_HIP(ctx, hipMemcpyAsync(db->h + kPlaceHostDescAt, db->d_query, kPlaceDescBytes, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(db->h() + kPlaceHostDescAt, db->d_query(), kPlaceDescBytes, hipMemcpyDeviceToHost, ctx->stream));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(desc, db->h + kPlaceHostDescAt, kPlaceDescBytes);
+  std::memcpy(desc, db->h() + kPlaceHostDescAt, kPlaceDescBytes);
   return MH_OK;
 }
 
@@ -149,21 +131,21 @@ int place_query_chain(mh_place_db * db, const char * who, size_t n_search, int32
 {
   mh_ctx * ctx = db->ctx;
   const int m = static_cast<int>(n_search ? n_search : db->size);
-  const float * q = reinterpret_cast<const float *>(db->d_query);
-  double * qn = reinterpret_cast<double *>(db->d_query + kPlaceQueryNormsAt);
-  mh::PlaceBest * d_best = reinterpret_cast<mh::PlaceBest *>(db->d_query + kPlaceQueryBestAt);
+  const float * q = reinterpret_cast<const float *>(db->d_query());
+  double * qn = reinterpret_cast<double *>(db->d_query() + kPlaceQueryNormsAt);
+  mh::PlaceBest * d_best = reinterpret_cast<mh::PlaceBest *>(db->d_query() + kPlaceQueryBestAt);
   hipError_t e = mh::launch_place_norms(q, qn, ctx->stream);
-  if (e == hipSuccess) e = mh::launch_place_query(q, qn, db->d_desc, db->d_norms, m, db->cfg.min_overlap, db->d_scores, ctx->stream);
-  if (e == hipSuccess) e = mh::launch_place_select(db->d_scores, m, top_k, d_best, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(db->h, d_best, sizeof(mh::PlaceBest), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = mh::launch_place_query(q, qn, db->d_desc(), db->d_norms(), m, db->cfg.min_overlap, db->d_scores(), ctx->stream);
+  if (e == hipSuccess) e = mh::launch_place_select(db->d_scores(), m, top_k, d_best, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(db->h(), d_best, sizeof(mh::PlaceBest), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && all)
-    e = hipMemcpyAsync(db->h + kPlaceHostScoresAt, db->d_scores, static_cast<size_t>(m) * sizeof(mh::PlaceScore), hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(db->h() + kPlaceHostScoresAt, db->d_scores(), static_cast<size_t>(m) * sizeof(mh::PlaceScore), hipMemcpyDeviceToHost, ctx->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(ctx->stream);
     return hip_fail(ctx, e, who);
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const mh::PlaceBest * b = reinterpret_cast<const mh::PlaceBest *>(db->h);
+  const mh::PlaceBest * b = reinterpret_cast<const mh::PlaceBest *>(db->h());
   for (int k = 0; k < top_k; ++k) {
     mh_place_hit & hk = hits[k];
     hk.index = b->index[k];
@@ -175,7 +157,7 @@ int place_query_chain(mh_place_db * db, const char * who, size_t n_search, int32
       hk.tag = db->tags[static_cast<size_t>(hk.index)];
     }
   }
-  if (all) std::memcpy(all, db->h + kPlaceHostScoresAt, static_cast<size_t>(m) * sizeof(mh::PlaceScore));
+  if (all) std::memcpy(all, db->h() + kPlaceHostScoresAt, static_cast<size_t>(m) * sizeof(mh::PlaceScore));
   return MH_OK;
 }
 
@@ -195,7 +177,6 @@ int place_create(mh_ctx * ctx, const mh_place_config * cfg, mh_place_db ** out)
 {
   MH_HIP(ctx, mh_enter(ctx));
   mh_place_db * db = new mh_place_db;
-  db->ctx = ctx;
   db->cfg = *cfg;
   db->P.r_min2 = cfg->r_min * cfg->r_min;
   db->P.z_min = cfg->z_min;
@@ -203,25 +184,17 @@ int place_create(mh_ctx * ctx, const mh_place_config * cfg, mh_place_db ** out)
   mh::place_ring_table(cfg->r_max, db->P.b2);
   const size_t cap = static_cast<size_t>(cfg->capacity);
   db->tags.reserve(cap);
-  db->h_bytes = kPlaceHostScoresAt + cap * sizeof(mh::PlaceScore);
-  void * p[4] = {nullptr, nullptr, nullptr, nullptr}, * hp = nullptr;
-  hipError_t e = AllocCache::alloc(&p[0], cap * kPlaceDescBytes);
-  if (e == hipSuccess) e = AllocCache::alloc(&p[1], cap * mh::kPlaceSectors * sizeof(double));
-  if (e == hipSuccess) e = AllocCache::alloc(&p[2], cap * sizeof(mh::PlaceScore));
-  if (e == hipSuccess) e = AllocCache::alloc(&p[3], kPlaceQueryBytes);
-  if (e == hipSuccess) e = AllocCache::alloc_pinned(&hp, db->h_bytes);
-  db->d_desc = static_cast<float *>(p[0]);
-  db->d_norms = static_cast<double *>(p[1]);
-  db->d_scores = static_cast<mh::PlaceScore *>(p[2]);
-  db->d_query = static_cast<char *>(p[3]);
-  db->h = static_cast<char *>(hp);
+  const size_t h_bytes = kPlaceHostScoresAt + cap * sizeof(mh::PlaceScore);
+  hipError_t e = db->mem.desc.alloc(cap * kPlaceDescBytes);
+  if (e == hipSuccess) e = db->mem.norms.alloc(cap * mh::kPlaceSectors * sizeof(double));
+  if (e == hipSuccess) e = db->mem.scores.alloc(cap * sizeof(mh::PlaceScore));
+  if (e == hipSuccess) e = db->mem.query.alloc(kPlaceQueryBytes);
+  if (e == hipSuccess) e = db->mem.h.reserve(h_bytes, h_bytes);
   if (e != hipSuccess) {
-    if (!hp) db->h_bytes = 0;
-    place_release_device(db);
     delete db;
     return hip_fail(ctx, e, "mh_place_db_create");
   }
-  ctx->place_dbs.push_back(db);
+  ctx_register(db, ctx);
   *out = db;
   return MH_OK;
 }
@@ -233,23 +206,6 @@ int place_add_check(const mh_place_db * db, const char * who)
   return MH_OK;
 }
 }  // namespace
-
-namespace mhi
-{
-void place_ctx_gone(mh_ctx * ctx)
-{
-  if (ctx->place_dbs.empty()) return;
-  (void)mh_enter(ctx);
-  (void)hipStreamSynchronize(ctx->stream);
-  for (mh_place_db * db : ctx->place_dbs) {
-    place_release_device(db);
-    db->size = 0;
-    db->tags.clear();
-    db->ctx = nullptr;
-  }
-  ctx->place_dbs.clear();
-}
-}  // namespace mhi
 
 extern "C" {
 
@@ -271,9 +227,7 @@ void mh_place_db_destroy(mh_place_db * db)
   if (mh_ctx * ctx = db->ctx) {
     (void)mh_enter(ctx);
     (void)hipStreamSynchronize(ctx->stream);  // the pinned blocks go back: nothing may still be copying into them
-    place_release_device(db);
-    auto & v = ctx->place_dbs;
-    v.erase(std::remove(v.begin(), v.end(), db), v.end());
+    ctx_unregister(db);
   }
   delete db;
 }
@@ -292,7 +246,7 @@ int mh_place_describe(mh_place_db * db, const float * xyz, size_t n, size_t stri
     if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_place_describe: batch too large");
     MH_HIP(ctx, mh_enter(ctx));
     if (n && (rc = place_stage(db, xyz, n, stride_floats)) != MH_OK) return rc;
-    return place_describe_out(db, "mh_place_describe", static_cast<const float *>(db->d_in.p), n, 3, R_G_F, desc);
+    return place_describe_out(db, "mh_place_describe", static_cast<const float *>(db->mem.d_in.p), n, 3, R_G_F, desc);
   });
 }
 
@@ -337,10 +291,10 @@ int mh_place_db_add(mh_place_db * db, const float * desc, int64_t tag, int32_t *
     if ((rc = place_add_check(db, "mh_place_db_add")) != MH_OK) return rc;
     if ((rc = place_check_desc(ctx, "mh_place_db_add", desc)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    float * slot = db->d_desc + db->size * mh::kPlaceCells;
-    std::memcpy(db->h + kPlaceHostDescAt, desc, kPlaceDescBytes);
-    MH_HIP(ctx, hipMemcpyAsync(slot, db->h + kPlaceHostDescAt, kPlaceDescBytes, hipMemcpyHostToDevice, ctx->stream));
-    MH_HIP(ctx, mh::launch_place_norms(slot, db->d_norms + db->size * mh::kPlaceSectors, ctx->stream));
+    float * slot = db->d_desc() + db->size * mh::kPlaceCells;
+    std::memcpy(db->h() + kPlaceHostDescAt, desc, kPlaceDescBytes);
+    MH_HIP(ctx, hipMemcpyAsync(slot, db->h() + kPlaceHostDescAt, kPlaceDescBytes, hipMemcpyHostToDevice, ctx->stream));
+    MH_HIP(ctx, mh::launch_place_norms(slot, db->d_norms() + db->size * mh::kPlaceSectors, ctx->stream));
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the pinned block is the next call's too)
     if (index) *index = static_cast<int32_t>(db->size);
     db->tags.push_back(tag);
@@ -364,10 +318,10 @@ int mh_place_db_add_from_scan(mh_place_db * db, const mh_scan * scan, int which,
     MH_HIP(ctx, mh_enter(ctx));
     // on the device from end to end, and nothing waits: the entry is behind this call on the context's stream, where every
     // reader of it is enqueued.  (A launch that fails leaves the size where it was: the slot is simply written again.)
-    float * slot = db->d_desc + db->size * mh::kPlaceCells;
+    float * slot = db->d_desc() + db->size * mh::kPlaceCells;
     rc = place_describe_to(db, "mh_place_db_add_from_scan", static_cast<const float *>(d), n, sizeof(mh_point32) / sizeof(float), R_G_F, slot);
     if (rc != MH_OK) return rc;
-    MH_HIP(ctx, mh::launch_place_norms(slot, db->d_norms + db->size * mh::kPlaceSectors, ctx->stream));
+    MH_HIP(ctx, mh::launch_place_norms(slot, db->d_norms() + db->size * mh::kPlaceSectors, ctx->stream));
     if (index) *index = static_cast<int32_t>(db->size);
     db->tags.push_back(tag);
     ++db->size;
@@ -385,10 +339,10 @@ int mh_place_db_get(mh_place_db * db, int32_t index, float * desc, int64_t * tag
     if (index < 0 || static_cast<size_t>(index) >= db->size) return fail(ctx, MH_ERR_INVALID_ARG, "mh_place_db_get: index out of range");
     if (desc) {
       MH_HIP(ctx, mh_enter(ctx));
-      MH_HIP(ctx, hipMemcpyAsync(db->h + kPlaceHostDescAt, db->d_desc + static_cast<size_t>(index) * mh::kPlaceCells, kPlaceDescBytes,
+      MH_HIP(ctx, hipMemcpyAsync(db->h() + kPlaceHostDescAt, db->d_desc() + static_cast<size_t>(index) * mh::kPlaceCells, kPlaceDescBytes,
                                  hipMemcpyDeviceToHost, ctx->stream));
       MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      std::memcpy(desc, db->h + kPlaceHostDescAt, kPlaceDescBytes);
+      std::memcpy(desc, db->h() + kPlaceHostDescAt, kPlaceDescBytes);
     }
     if (tag) *tag = db->tags[static_cast<size_t>(index)];
     return MH_OK;
@@ -405,8 +359,8 @@ int mh_place_db_query(mh_place_db * db, const float * desc, size_t n_search, int
     if ((rc = place_check_query(db, "mh_place_db_query", n_search, top_k)) != MH_OK) return rc;
     if ((rc = place_check_desc(ctx, "mh_place_db_query", desc)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    std::memcpy(db->h + kPlaceHostDescAt, desc, kPlaceDescBytes);
-    MH_HIP(ctx, hipMemcpyAsync(db->d_query, db->h + kPlaceHostDescAt, kPlaceDescBytes, hipMemcpyHostToDevice, ctx->stream));
+    std::memcpy(db->h() + kPlaceHostDescAt, desc, kPlaceDescBytes);
+    MH_HIP(ctx, hipMemcpyAsync(db->d_query(), db->h() + kPlaceHostDescAt, kPlaceDescBytes, hipMemcpyHostToDevice, ctx->stream));
     return place_query_chain(db, "mh_place_db_query", n_search, top_k, hits, all);
   });
 }
@@ -426,7 +380,7 @@ int mh_place_db_query_from_scan(mh_place_db * db, const mh_scan * scan, int whic
     if ((rc = place_check_R(ctx, "mh_place_db_query_from_scan", R_G_F)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
     rc = place_describe_to(db, "mh_place_db_query_from_scan", static_cast<const float *>(d), n, sizeof(mh_point32) / sizeof(float), R_G_F,
-                           reinterpret_cast<float *>(db->d_query));
+                           reinterpret_cast<float *>(db->d_query()));
     if (rc != MH_OK) return rc;
     return place_query_chain(db, "mh_place_db_query_from_scan", n_search, top_k, hits, all);
   });

@@ -27,56 +27,42 @@ hipError_t launch_pgo_cost(const PgoGraph & g, bool chi2, hipStream_t stream);
 hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream);
 }  // namespace mh
 
-struct mh_pose_graph
+struct mh_pose_graph final : CtxOwned
 {
-  mh_ctx * ctx = nullptr;  // null: mh_shutdown of the context ran first (pose_graph_ctx_gone), the handle can only be destroyed
   size_t max_poses = 0, max_edges = 0;
   size_t n = 0, n_edges = 0, n_far = 0, n_priors = 0;
-  char * d_block = nullptr;  // every array of mh::PgoGraph (pgo_layout)
   size_t off[mh::kPgArrays] = {};
-  mh::PgoGraph g{};          // device pointers into d_block
-  double * d_trace = nullptr;  // iters x n x 12: the poses behind every step (grown on demand)
-  size_t d_trace_bytes = 0;
-  uint4 * h_words = nullptr;  // one flagged word per iteration (mapped pinned) and its device-side address
+  mh::PgoGraph g{};          // device pointers into mem.block
+  // what goes back when the context does
+  struct Memory
+  {
+    DevBuf block;     // every array of mh::PgoGraph (pgo_layout)
+    DevBuf trace;     // double, iters x n x 12: the poses behind every step (grown on demand)
+    PinnedBuf h_out;  // pinned staging of whatever a call hands to the host (grown on demand)
+  } mem;
+  uint4 * h_words = nullptr;  // one flagged word per iteration (mapped pinned, zeroed at create) and its device-side address
   uint4 * d_words = nullptr;
-  char * h_out = nullptr;     // pinned staging of whatever a call hands to the host (grown on demand)
-  size_t h_out_bytes = 0;
   unsigned int seq = 0;
+  char * h_out() const { return mem.h_out.as<char>(); }
+  void ctx_gone() override
+  {
+    mem = Memory{};
+    if (h_words) (void)hipHostFree(h_words);
+    h_words = d_words = nullptr;
+    n = n_edges = n_far = n_priors = 0;
+  }
+  ~mh_pose_graph() { ctx_gone(); }
 };
 
 namespace
 {
-void pgo_release_device(mh_pose_graph * pg)
-{
-  AllocCache::free(pg->d_block);
-  AllocCache::free(pg->d_trace);
-  if (pg->h_words) (void)hipHostFree(pg->h_words);
-  if (pg->h_out) (void)hipHostFree(pg->h_out);
-  pg->d_block = nullptr;
-  pg->d_trace = nullptr;
-  pg->h_words = pg->d_words = nullptr;
-  pg->h_out = nullptr;
-  pg->d_trace_bytes = pg->h_out_bytes = 0;
-}
-
 // every entry point but destroy: a graph whose context was shut down
-int pgo_alive(const mh_pose_graph * pg, const char * who)
-{
-  if (!pg->ctx) return fail(nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": the graph's context was shut down; the handle can only be destroyed");
-  return MH_OK;
-}
+int pgo_alive(const mh_pose_graph * pg, const char * who) { return ctx_alive(pg, who, "graph"); }
 
 // (every call that used the block has waited)
 int pgo_host(mh_pose_graph * pg, size_t bytes)
 {
-  if (bytes <= pg->h_out_bytes) return MH_OK;
-  size_t cap = size_t(64) << 10;
-  while (cap < bytes) cap <<= 1;
-  if (pg->h_out) (void)hipHostFree(pg->h_out);
-  pg->h_out = nullptr;
-  pg->h_out_bytes = 0;
-  MH_HIP(pg->ctx, hipHostMalloc(reinterpret_cast<void **>(&pg->h_out), cap, hipHostMallocDefault));
-  pg->h_out_bytes = cap;
+  MH_HIP(pg->ctx, pg->mem.h_out.reserve(bytes));
   return MH_OK;
 }
 
@@ -85,8 +71,8 @@ template <typename T>
 hipError_t pgo_up(mh_pose_graph * pg, size_t & at, T * dst, const T * src, size_t count)
 {
   if (!count) return hipSuccess;
-  std::memcpy(pg->h_out + at, src, count * sizeof(T));
-  const hipError_t e = hipMemcpyAsync(dst, pg->h_out + at, count * sizeof(T), hipMemcpyHostToDevice, pg->ctx->stream);
+  std::memcpy(pg->h_out() + at, src, count * sizeof(T));
+  const hipError_t e = hipMemcpyAsync(dst, pg->h_out() + at, count * sizeof(T), hipMemcpyHostToDevice, pg->ctx->stream);
   at += (count * sizeof(T) + 15) / 16 * 16;
   return e;
 }
@@ -95,29 +81,25 @@ int pgo_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_pose_graph *
 {
   MH_HIP(ctx, mh_enter(ctx));
   mh_pose_graph * pg = new mh_pose_graph;
-  pg->ctx = ctx;
   pg->max_poses = max_poses;
   pg->max_edges = max_edges;
   const size_t bytes = mh::pgo_layout(max_poses, std::max<size_t>(max_edges, 1), pg->off);
-  void * p = nullptr;
-  hipError_t e = AllocCache::alloc(&p, bytes);
-  pg->d_block = static_cast<char *>(p);
+  hipError_t e = pg->mem.block.alloc(bytes);
   if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&pg->h_words), mh::kPgoMaxIters * sizeof(uint4), hipHostMallocMapped);
   if (e == hipSuccess) {
     std::memset(pg->h_words, 0, mh::kPgoMaxIters * sizeof(uint4));
     e = hipHostGetDevicePointer(reinterpret_cast<void **>(&pg->d_words), pg->h_words, 0);
   }
-  mh::pgo_bind(pg->g, pg->d_block, pg->off);
+  mh::pgo_bind(pg->g, pg->mem.block.as<char>(), pg->off);
   // no loss on any term until mh_pose_graph_set_loss says otherwise
   if (e == hipSuccess) e = hipMemsetAsync(pg->g.lkind, 0, std::max<size_t>(max_edges, 1) * sizeof(int), ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(pg->g.plkind, 0, max_poses * sizeof(int), ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) {
-    pgo_release_device(pg);
     delete pg;
     return hip_fail(ctx, e, "mh_pose_graph_create");
   }
-  ctx->pose_graphs.push_back(pg);
+  ctx_register(pg, ctx);
   *out = pg;
   return MH_OK;
 }
@@ -219,15 +201,8 @@ int pgo_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_g
   const size_t trace_bytes = trace_poses ? static_cast<size_t>(iters) * pose_bytes : 0;
   int rc = pgo_host(pg, head + trace_bytes);
   if (rc != MH_OK) return rc;
-  if (trace_bytes > pg->d_trace_bytes) {
-    AllocCache::free(pg->d_trace);
-    pg->d_trace = nullptr;
-    pg->d_trace_bytes = 0;
-    void * p = nullptr;
-    MH_HIP(ctx, AllocCache::alloc(&p, trace_bytes));
-    pg->d_trace = static_cast<double *>(p);
-    pg->d_trace_bytes = trace_bytes;
-  }
+  if (trace_bytes > pg->mem.trace.cap) MH_HIP(ctx, pg->mem.trace.alloc(trace_bytes));
+  double * const d_trace = pg->mem.trace.as<double>();
   const mh::PgoGraph g = pgo_graph(pg);
   const mh::PgoParams p{cfg->damping, cfg->eps_rot, cfg->eps_trans};
   unsigned int seq[mh::kPgoMaxIters];
@@ -240,7 +215,7 @@ int pgo_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_g
   while (e == hipSuccess && queued < iters && !(flags & 1)) {
     const int upto = std::min(queued + chunk, iters);
     for (; e == hipSuccess && queued < upto; ++queued)
-      e = mh::launch_pgo_iteration(g, p, queued, trace_poses ? pg->d_trace + static_cast<size_t>(queued) * 12 * N : nullptr, pg->d_words + queued,
+      e = mh::launch_pgo_iteration(g, p, queued, trace_poses ? d_trace + static_cast<size_t>(queued) * 12 * N : nullptr, pg->d_words + queued,
                                    seq[queued], ctx->stream);
     if (e != hipSuccess || queued == iters) break;
     // the last queued iteration's word: the value itself, then the stream behind it
@@ -251,18 +226,18 @@ int pgo_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_g
       }
     }
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out, g.st, sizeof(mh::PgoState), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out + sizeof(mh::PgoState), g.rows, mh::kPgoMaxIters * sizeof(mh::PgoRow), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out(), g.st, sizeof(mh::PgoState), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out() + sizeof(mh::PgoState), g.rows, mh::kPgoMaxIters * sizeof(mh::PgoRow), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && trace_poses)
-    e = hipMemcpyAsync(pg->h_out + head, pg->d_trace, static_cast<size_t>(queued) * pose_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(pg->h_out() + head, d_trace, static_cast<size_t>(queued) * pose_bytes, hipMemcpyDeviceToHost, ctx->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(ctx->stream);
     return hip_fail(ctx, e, "mh_pose_graph_optimise");
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   mh::PgoState st;
-  std::memcpy(&st, pg->h_out, sizeof(st));
-  const mh::PgoRow * rows = reinterpret_cast<const mh::PgoRow *>(pg->h_out + sizeof(mh::PgoState));
+  std::memcpy(&st, pg->h_out(), sizeof(st));
+  const mh::PgoRow * rows = reinterpret_cast<const mh::PgoRow *>(pg->h_out() + sizeof(mh::PgoState));
   if (st.iters < 1 || st.iters > queued) return fail(ctx, MH_ERR_HIP, "mh_pose_graph_optimise: the chain left no result");
   std::memset(out, 0, sizeof(*out));
   out->iters = st.iters;
@@ -277,7 +252,7 @@ int pgo_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_g
   }
   out->f_first = rows[0].f;
   out->f_last = rows[st.iters - 1].f;
-  if (trace_poses) std::memcpy(trace_poses, pg->h_out + head, static_cast<size_t>(st.iters) * pose_bytes);
+  if (trace_poses) std::memcpy(trace_poses, pg->h_out() + head, static_cast<size_t>(st.iters) * pose_bytes);
   return MH_OK;
 }
 
@@ -293,17 +268,17 @@ int pgo_residuals(mh_pose_graph * pg, double * r, double * chi2, double * f)
   hipError_t e = hipMemsetAsync(g.st, 0, sizeof(mh::PgoState), ctx->stream);
   if (e == hipSuccess) e = mh::launch_pgo_edges(g, true, ctx->stream);
   if (e == hipSuccess) e = mh::launch_pgo_cost(g, true, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out, &g.rows[0].f, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && E) e = hipMemcpyAsync(pg->h_out + 16, g.res, 6 * E * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && E) e = hipMemcpyAsync(pg->h_out + 16 + 6 * E * sizeof(double), g.cz, E * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out(), &g.rows[0].f, sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && E) e = hipMemcpyAsync(pg->h_out() + 16, g.res, 6 * E * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && E) e = hipMemcpyAsync(pg->h_out() + 16 + 6 * E * sizeof(double), g.cz, E * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(ctx->stream);
     return hip_fail(ctx, e, "mh_pose_graph_residuals");
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (f) std::memcpy(f, pg->h_out, sizeof(double));
-  if (r && E) std::memcpy(r, pg->h_out + 16, 6 * E * sizeof(double));
-  if (chi2 && E) std::memcpy(chi2, pg->h_out + 16 + 6 * E * sizeof(double), E * sizeof(double));
+  if (f) std::memcpy(f, pg->h_out(), sizeof(double));
+  if (r && E) std::memcpy(r, pg->h_out() + 16, 6 * E * sizeof(double));
+  if (chi2 && E) std::memcpy(chi2, pg->h_out() + 16 + 6 * E * sizeof(double), E * sizeof(double));
   return MH_OK;
 }
 
@@ -418,11 +393,11 @@ int pgo_evaluate(mh_pose_graph * pg, const char * who, double * d, double * chi2
   const int rc = pgo_host(pg, 16 + (E + 8 * P) * D);
   if (rc != MH_OK) return rc;
   const mh::PgoGraph g = pgo_graph(pg);
-  char * const h_w = pg->h_out + 16, * const h_pw = h_w + E * D, * const h_d = h_pw + P * D, * const h_c = h_d + 6 * P * D;
+  char * const h_w = pg->h_out() + 16, * const h_pw = h_w + E * D, * const h_d = h_pw + P * D, * const h_c = h_d + 6 * P * D;
   hipError_t e = hipMemsetAsync(g.st, 0, sizeof(mh::PgoState), ctx->stream);
   if (e == hipSuccess) e = mh::launch_pgo_edges(g, false, ctx->stream);
   if (e == hipSuccess) e = mh::launch_pgo_cost(g, false, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out, &g.rows[0].f, D, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out(), &g.rows[0].f, D, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && E) e = hipMemcpyAsync(h_w, g.w, E * D, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && P) e = hipMemcpyAsync(h_pw, g.pw, P * D, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && P) e = hipMemcpyAsync(h_d, g.pres, 6 * P * D, hipMemcpyDeviceToHost, ctx->stream);
@@ -432,7 +407,7 @@ int pgo_evaluate(mh_pose_graph * pg, const char * who, double * d, double * chi2
     return hip_fail(ctx, e, who);
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (f) std::memcpy(f, pg->h_out, D);
+  if (f) std::memcpy(f, pg->h_out(), D);
   if (w_edges && E) std::memcpy(w_edges, h_w, E * D);
   if (w_priors && P) std::memcpy(w_priors, h_pw, P * D);
   if (d && P) std::memcpy(d, h_d, 6 * P * D);
@@ -440,22 +415,6 @@ int pgo_evaluate(mh_pose_graph * pg, const char * who, double * d, double * chi2
   return MH_OK;
 }
 }  // namespace
-
-namespace mhi
-{
-void pose_graph_ctx_gone(mh_ctx * ctx)
-{
-  if (ctx->pose_graphs.empty()) return;
-  (void)mh_enter(ctx);
-  (void)hipStreamSynchronize(ctx->stream);
-  for (mh_pose_graph * pg : ctx->pose_graphs) {
-    pgo_release_device(pg);
-    pg->n = pg->n_edges = pg->n_far = pg->n_priors = 0;
-    pg->ctx = nullptr;
-  }
-  ctx->pose_graphs.clear();
-}
-}  // namespace mhi
 
 extern "C" {
 
@@ -478,9 +437,7 @@ void mh_pose_graph_destroy(mh_pose_graph * pg)
   if (mh_ctx * ctx = pg->ctx) {
     (void)mh_enter(ctx);
     (void)hipStreamSynchronize(ctx->stream);  // the pinned blocks go back: nothing may still be copying into them
-    pgo_release_device(pg);
-    auto & v = ctx->pose_graphs;
-    v.erase(std::remove(v.begin(), v.end(), pg), v.end());
+    ctx_unregister(pg);
   }
   delete pg;
 }
@@ -612,11 +569,11 @@ int mh_pose_graph_get_poses(mh_pose_graph * pg, double * R, double * t, size_t c
     if (n == 0) return MH_OK;
     MH_HIP(ctx, mh_enter(ctx));
     if ((rc = pgo_host(pg, 12 * n * sizeof(double))) != MH_OK) return rc;
-    MH_HIP(ctx, hipMemcpyAsync(pg->h_out, pg->g.R, 9 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    MH_HIP(ctx, hipMemcpyAsync(pg->h_out + 9 * n * sizeof(double), pg->g.t, 3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(pg->h_out(), pg->g.R, 9 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(pg->h_out() + 9 * n * sizeof(double), pg->g.t, 3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (R) std::memcpy(R, pg->h_out, 9 * n * sizeof(double));
-    if (t) std::memcpy(t, pg->h_out + 9 * n * sizeof(double), 3 * n * sizeof(double));
+    if (R) std::memcpy(R, pg->h_out(), 9 * n * sizeof(double));
+    if (t) std::memcpy(t, pg->h_out() + 9 * n * sizeof(double), 3 * n * sizeof(double));
     return MH_OK;
   });
 }

@@ -21,7 +21,7 @@ struct mh_radar_scan
 {
   mh_ctx * ctx = nullptr;
   DevBuf d_raw, d_targets, d_bd, d_count;
-  uint32_t * h_count = nullptr;  // pinned landing word of the kept count
+  PinnedBuf h_count;  // pinned landing word of the kept count (a uint32_t)
   size_t n_in = 0, n_valid = 0;
   bool prepared = false;
 };
@@ -34,7 +34,7 @@ struct mh_radar_factor
   DevBuf d_args;  // the RadarLinArgs of the call in flight / the last call
   double R_B_S[9], t_B_S[3], omega[3], sigma = 0;
   // pinned, mapped: the argument block the kernel's argument copy reads, then the kernel's 55 sums (written by the kernel)
-  void * h_io = nullptr;
+  PinnedBuf h_io;
   void * d_io = nullptr;
   mh::RadarLinArgs last{};  // state of the last linearize (mh_radar_factor_get_residuals)
   bool linearized = false, pending = false, pending_timed = false;
@@ -146,8 +146,8 @@ int factor_new(mh_ctx * ctx, size_t n, const double R_B_S[9], const double t_B_S
   std::memcpy(f->t_B_S, t_B_S, sizeof(f->t_B_S));
   std::memcpy(f->omega, omega, sizeof(f->omega));
   f->sigma = sigma;
-  hipError_t e = AllocCache::alloc_pinned(&f->h_io, kIoBytes);
-  if (e == hipSuccess) e = hipHostGetDevicePointer(&f->d_io, f->h_io, 0);
+  hipError_t e = f->h_io.reserve(kIoBytes, kIoBytes);
+  if (e == hipSuccess) e = hipHostGetDevicePointer(&f->d_io, f->h_io.p, 0);
   if (e == hipSuccess) e = f->d_bd.reserve(n * sizeof(double4), ctx->stream, false);
   if (e == hipSuccess) e = f->d_args.reserve(sizeof(mh::RadarLinArgs), ctx->stream, false);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&f->done, hipEventDisableTiming);
@@ -174,14 +174,14 @@ int radar_enqueue(mh_radar_factor * f, const double * R_W_B, const double * v_W,
   MH_HIP(ctx, mh_enter(ctx));
   const bool timed = ctx->profiling > 0;
   const mh::RadarLinArgs a = make_args(f, R_W_B, v_W, bias_gyro);
-  std::memcpy(f->h_io, &a, sizeof(a));
+  std::memcpy(f->h_io.p, &a, sizeof(a));
   double * d_out = reinterpret_cast<double *>(static_cast<char *>(f->d_io) + kIoOut);
   if (timed && !f->ev[0]) {
     MH_HIP(ctx, hipEventCreate(&f->ev[0]));
     MH_HIP(ctx, hipEventCreate(&f->ev[1]));
   }
   if (f->n > 0) {  // (no kernel for a factor without targets: the sums are zero)
-    MH_HIP(ctx, hipMemcpyAsync(f->d_args.p, f->h_io, sizeof(a), hipMemcpyHostToDevice, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(f->d_args.p, f->h_io.p, sizeof(a), hipMemcpyHostToDevice, ctx->stream));
     if (timed) MH_HIP(ctx, hipEventRecord(f->ev[0], ctx->stream));
     MH_HIP(ctx, mh::launch_radar_linearize(static_cast<const mh::RadarLinArgs *>(f->d_args.p), 1, d_out, ctx->stream));
     if (timed) MH_HIP(ctx, hipEventRecord(f->ev[1], ctx->stream));
@@ -201,7 +201,7 @@ int radar_finish(mh_radar_factor * f, mh_radar_result * out)
   MH_HIP(ctx, mh_enter(ctx));
   MH_HIP(ctx, hipEventSynchronize(f->done));  // the end of the kernel makes its host writes visible
   static const double zeros[mh::kRadarOutStride] = {};
-  const double * s = f->n > 0 ? reinterpret_cast<const double *>(static_cast<const char *>(f->h_io) + kIoOut) : zeros;
+  const double * s = f->n > 0 ? reinterpret_cast<const double *>(f->h_io.as<const char>() + kIoOut) : zeros;
   expand(s, f->n, out);
   if (f->pending_timed) (void)hipEventElapsedTime(&out->gpu_ms, f->ev[0], f->ev[1]);
   return MH_OK;
@@ -218,10 +218,8 @@ int mh_radar_scan_create(mh_ctx * ctx, mh_radar_scan ** out)
     MH_HIP(ctx, mh_enter(ctx));
     mh_radar_scan * s = new mh_radar_scan;
     s->ctx = ctx;
-    void * p = nullptr;
-    hipError_t e = AllocCache::alloc_pinned(&p, 4096);
+    hipError_t e = s->h_count.reserve(4096, 4096);
     if (e == hipSuccess) e = s->d_count.reserve(64, ctx->stream, false);
-    s->h_count = static_cast<uint32_t *>(p);
     if (e != hipSuccess) {
       mh_radar_scan_destroy(s);
       return hip_fail(ctx, e, "mh_radar_scan_create");
@@ -236,8 +234,7 @@ void mh_radar_scan_destroy(mh_radar_scan * s)
   if (!s) return;
   (void)mh_enter(s->ctx);
   (void)hipStreamSynchronize(s->ctx->stream);
-  for (DevBuf * b : {&s->d_raw, &s->d_targets, &s->d_bd, &s->d_count}) b->release(true);
-  if (s->h_count) AllocCache::free_pinned(s->h_count, 4096);
+  const DrainedScope drained;
   delete s;
 }
 
@@ -278,10 +275,10 @@ int mh_radar_prepare_input(mh_radar_scan * s, const void * raw, size_t n, const 
     fl.filter_min_db = cfg->filter_min_db;
     MH_HIP(ctx, mh::launch_radar_prepare(s->d_raw.p, static_cast<uint32_t>(n), fl, static_cast<mh_radar_target *>(s->d_targets.p),
                                          static_cast<double4 *>(s->d_bd.p), static_cast<uint32_t *>(s->d_count.p), ctx->stream));
-    MH_HIP(ctx, hipMemcpyAsync(s->h_count, s->d_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(s->h_count.p, s->d_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s->n_in = n;
-    s->n_valid = *s->h_count;
+    s->n_valid = *s->h_count.as<uint32_t>();
     s->prepared = true;
     if (info) {
       info->n_points_in = n;
@@ -390,10 +387,9 @@ void mh_radar_factor_destroy(mh_radar_factor * f)
   if (!f) return;
   (void)mh_enter(f->ctx);
   (void)hipStreamSynchronize(f->ctx->stream);  // a call in flight still reads the targets and writes h_io
-  for (DevBuf * b : {&f->d_bd, &f->d_args}) b->release(true);
-  if (f->h_io) AllocCache::free_pinned(f->h_io, kIoBytes);
   for (hipEvent_t e : {f->done, f->ev[0], f->ev[1]})
     if (e) (void)hipEventDestroy(e);
+  const DrainedScope drained;
   delete f;
 }
 
@@ -448,16 +444,11 @@ int mh_radar_factor_linearize_batch(mh_radar_factor * const * factors, size_t n_
     }
     MH_HIP(ctx, mh_enter(ctx));
     const bool timed = ctx->profiling > 0;
-    void * h = nullptr;
-    MH_HIP(ctx, AllocCache::alloc_pinned(&h, kBatchBytes));
-    struct PinnedBack  // the staging block goes back to the pool on every exit path (the call waits for its kernel)
-    {
-      void * p;
-      ~PinnedBack() { AllocCache::free_pinned(p, kBatchBytes); }
-    } back{h};
+    PinnedBuf h;  // the staging block goes back to the pool on every exit path (the call waits for its kernel)
+    MH_HIP(ctx, h.reserve(kBatchBytes, kBatchBytes));
     void * d_h = nullptr;
-    MH_HIP(ctx, hipHostGetDevicePointer(&d_h, h, 0));
-    mh::RadarLinArgs * args = static_cast<mh::RadarLinArgs *>(h);
+    MH_HIP(ctx, hipHostGetDevicePointer(&d_h, h.p, 0));
+    mh::RadarLinArgs * args = h.as<mh::RadarLinArgs>();
     for (size_t i = 0; i < n_factors; ++i) args[i] = make_args(factors[i], R_W_B + 9 * i, v_W + 3 * i, bias_gyro + 3 * i);
     DevTemp<mh::RadarLinArgs> d_args;
     MH_HIP(ctx, d_args.alloc(n_factors * sizeof(mh::RadarLinArgs)));
@@ -479,7 +470,7 @@ int mh_radar_factor_linearize_batch(mh_radar_factor * const * factors, size_t n_
       (void)hipEventDestroy(ev[0]);
       (void)hipEventDestroy(ev[1]);
     }
-    const double * s = reinterpret_cast<const double *>(static_cast<const char *>(h) + kBatchArgBytes);
+    const double * s = reinterpret_cast<const double *>(h.as<const char>() + kBatchArgBytes);
     for (size_t i = 0; i < n_factors; ++i) {
       expand(s + i * mh::kRadarOutStride, factors[i]->n, &out[i]);
       out[i].gpu_ms = ms;

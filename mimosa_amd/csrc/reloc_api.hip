@@ -45,15 +45,7 @@ static int score_begin(mh_icp * icp, const double * R, const double * t, size_t 
   // the pinned block
   const size_t h_scores_at = kRelocPosesAt + align256(n_poses * 12 * sizeof(double));
   const size_t h_bytes = h_scores_at + align256(n_poses * sizeof(mh_pose_score));
-  if (h_bytes > icp->h_reloc_cap) {
-    size_t cap = size_t(64) << 10;
-    while (cap < h_bytes) cap <<= 1;
-    if (icp->h_reloc) AllocCache::free_pinned(icp->h_reloc, icp->h_reloc_cap);  // (no call in flight: nothing reads it)
-    icp->h_reloc = nullptr;
-    icp->h_reloc_cap = 0;
-    MH_HIP(ctx, AllocCache::alloc_pinned(&icp->h_reloc, cap));
-    icp->h_reloc_cap = cap;
-  }
+  MH_HIP(ctx, icp->h_reloc.reserve(h_bytes));  // (no call in flight: nothing reads it)
   // the device block
   const size_t d_sub_at = align256(n_poses * 12 * sizeof(double));
   const size_t d_part_at = d_sub_at + align256(static_cast<size_t>(m) * sizeof(float4));
@@ -61,7 +53,7 @@ static int score_begin(mh_icp * icp, const double * R, const double * t, size_t 
   const size_t d_bytes = d_scores_at + align256(n_poses * sizeof(mh::RelocScore));
   MH_HIP(ctx, icp->d_reloc.reserve(d_bytes, ctx->stream, false));
 
-  char * h = static_cast<char *>(icp->h_reloc);
+  char * h = static_cast<char *>(icp->h_reloc.p);
   char * d = static_cast<char *>(icp->d_reloc.p);
   double * hp = reinterpret_cast<double *>(h + kRelocPosesAt);
   for (size_t p = 0; p < n_poses; ++p) {
@@ -69,7 +61,7 @@ static int score_begin(mh_icp * icp, const double * R, const double * t, size_t 
     std::memcpy(hp + 12 * p + 9, t + 3 * p, 3 * sizeof(double));
   }
   void * d_h = nullptr;  // the pinned block as the device sees it
-  MH_HIP(ctx, hipHostGetDevicePointer(&d_h, icp->h_reloc, 0));
+  MH_HIP(ctx, hipHostGetDevicePointer(&d_h, icp->h_reloc.p, 0));
   char * dh = static_cast<char *>(d_h);
   MH_HIP(ctx, mh::launch_copy16(dh + kRelocPosesAt, d, n_poses * 12 * sizeof(double), ctx->stream));
   MH_HIP(ctx, mh::launch_reloc_gather(static_cast<const float4 *>(icp->d_src.p), icp->ordered ? static_cast<const uint32_t *>(icp->d_perm.p) : nullptr, n,
@@ -107,7 +99,7 @@ int mhi::score_wait(mh_icp * icp)
   let_go(icp);
   MH_HIP(ctx, mh_enter(ctx));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const char * h = static_cast<const char *>(icp->h_reloc);
+  const char * h = static_cast<const char *>(icp->h_reloc.p);
   if (c.scores) std::memcpy(c.scores, h + kRelocPosesAt + align256(c.n_poses * 12 * sizeof(double)), c.n_poses * sizeof(mh_pose_score));
   if (c.best) std::memcpy(c.best, reinterpret_cast<const mh::RelocBest *>(h)->index, sizeof(int32_t) * MH_RELOC_MAX_REFINE);
   return MH_OK;
@@ -176,7 +168,7 @@ static int relocalise_impl(mh_icp * icp, const double * R, const double * t, siz
   int32_t best[MH_RELOC_MAX_REFINE];
   int rc = score_impl(icp, R, t, n_poses, &cfg->score, nullptr, best, true);
   if (rc != MH_OK) return rc;
-  const mh::RelocBest coarse = *static_cast<const mh::RelocBest *>(icp->h_reloc);
+  const mh::RelocBest coarse = *static_cast<const mh::RelocBest *>(icp->h_reloc.p);
   int nc = 0;
   while (nc < MH_RELOC_MAX_REFINE && best[nc] >= 0) ++nc;
   out->n_candidates = nc;

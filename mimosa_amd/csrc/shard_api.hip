@@ -191,7 +191,17 @@ struct ShardRound
 };
 }  // namespace
 
-struct mh_shard_comm
+// What a communicator holds on the context its rounds run on: the exchange buffers and the publish ring.  comm_release_ctx assigns
+// a fresh one.
+struct CommWorkspace
+{
+  DevBuf ws_send, ws_recv, ws_ar, ws_loc;
+  PinnedBuf h_ring;  // ShardPublish: kShardRing x ring_width entries
+  mh::ShardPublish * d_h_ring = nullptr;
+  size_t ring_width = 0;
+};
+
+struct mh_shard_comm : CommWorkspace
 {
   int world = 1, rank = 0;
   bool is_rccl = false;
@@ -204,10 +214,6 @@ struct mh_shard_comm
   // reused in stream order, the publish slots form a ring in mapped pinned memory (kShardRing x ring_width entries)
   mh_ctx * ws_ctx = nullptr;  // (set by comm_bind only: the context lists the communicator in shard_comms)
   std::deque<ShardRound> rounds;
-  DevBuf ws_send, ws_recv, ws_ar, ws_loc;
-  mh::ShardPublish * h_ring = nullptr;
-  mh::ShardPublish * d_h_ring = nullptr;
-  size_t ring_width = 0;
   int ring_pos = 0;
   unsigned int seq = 0;
   unsigned long long n_rounds = 0;   // rounds enqueued so far
@@ -273,16 +279,21 @@ struct mh_shard_comm
   }
 };
 
-struct mh_shard_icp
+// The device buffers of a sharded factor: shard_release_device assigns a fresh one.
+struct ShardDevice
+{
+  DevBuf d_state;  // a ShardState
+  DevBuf d_dest, d_hist, d_ar, d_flags, d_pos, d_temp;
+  mh::ShardState * state() const { return d_state.as<mh::ShardState>(); }
+};
+
+struct mh_shard_icp : ShardDevice
 {
   mh_ctx * ctx = nullptr;          // null: mh_shutdown of the context ran first (shard_ctx_gone), the handle can only be destroyed
   mh_shard_comm * comm = nullptr;  // set exactly while the factor is in comm->factors
   mh_icp * icp = nullptr;
   bool collective = false;
   int block_log2 = 3;
-  // device
-  mh::ShardState * d_state = nullptr;
-  DevBuf d_dest, d_hist, d_ar, d_flags, d_pos, d_temp;
   // host knowledge.  n_slots / n_live are exact as of the last COMPLETED call (the publish kernel reports the counters);
   // slots_bound is an upper bound of the slot count behind every call enqueued so far (what sizes grids while calls are in
   // flight); cur is the ping-pong entry the NEXT enqueued call reads
@@ -389,7 +400,7 @@ int shard_compact(mh_shard_icp * S)
   MH_HIP(ctx, S->d_pos.reserve(k * sizeof(uint32_t), ctx->stream, false));
   MH_HIP(ctx, S->d_temp.reserve(mh::shard_temp_bytes(k), ctx->stream, false));
   // (only ever called on an idle factor: the host knows n_slots / n_live exactly)
-  MH_HIP(ctx, mh::launch_shard_compact(arrays_of(icp, false), arrays_of(icp, true), S->d_state, S->cur, S->n_slots, static_cast<uint32_t *>(S->d_flags.p),
+  MH_HIP(ctx, mh::launch_shard_compact(arrays_of(icp, false), arrays_of(icp, true), S->state(), S->cur, S->n_slots, static_cast<uint32_t *>(S->d_flags.p),
                                        static_cast<uint32_t *>(S->d_pos.p), S->d_temp.p, S->d_temp.cap, ctx->stream));
   if (S->n_slots) {
     std::swap(icp->d_src, icp->x_src);
@@ -446,10 +457,10 @@ static void comm_release_ctx(mh_shard_comm * comm)
   (void)hipStreamSynchronize(comm->ws_ctx->stream);
   fail_rounds(comm, MH_OK);
   comm->cap_updates.clear();
-  for (DevBuf * b : {&comm->ws_send, &comm->ws_recv, &comm->ws_ar, &comm->ws_loc}) b->release(true);
-  if (comm->h_ring) AllocCache::free_pinned(comm->h_ring, sizeof(mh::ShardPublish) * comm->ring_width * kShardRing);
-  comm->h_ring = comm->d_h_ring = nullptr;
-  comm->ring_width = 0;
+  {
+    const DrainedScope drained;
+    static_cast<CommWorkspace &>(*comm) = CommWorkspace{};
+  }
   comm_bind(comm, nullptr);
 }
 
@@ -473,9 +484,10 @@ static void comm_detach(mh_shard_icp * S)
 // Everything of a factor that lives on its context: device buffers, the inner plain factor.  The context must still be alive.
 static void shard_release_device(mh_shard_icp * S)
 {
-  for (DevBuf * b : {&S->d_dest, &S->d_hist, &S->d_ar, &S->d_flags, &S->d_pos, &S->d_temp}) b->release(true);
-  if (S->d_state) AllocCache::free(S->d_state, true);
-  S->d_state = nullptr;
+  {
+    const DrainedScope drained;
+    static_cast<ShardDevice &>(*S) = ShardDevice{};
+  }
   if (S->icp) {
     S->last_linearize_count = S->icp->linearize_count;
     mh_icp_destroy(S->icp);
@@ -696,10 +708,8 @@ static int shard_icp_create_impl(mh_ctx * ctx, mh_shard_comm * comm, mh_map * ma
   icp->cold = false;  // the state arrays are explicit (zeroed at creation): tombstones and migrated state live in them
   MH_HIP(ctx, icp->d_origin.reserve(static_cast<size_t>(S->slot_capacity) * sizeof(unsigned long long), ctx->stream, false));
   MH_HIP(ctx, mh::launch_shard_origin(static_cast<unsigned long long *>(icp->d_origin.p), static_cast<uint32_t>(n_local), static_cast<uint32_t>(comm->rank), ctx->stream));
-  void * st = nullptr;
-  MH_HIP(ctx, AllocCache::alloc(&st, sizeof(mh::ShardState)));
-  S->d_state = static_cast<mh::ShardState *>(st);
-  MH_HIP(ctx, mh::launch_shard_state_init(S->d_state, static_cast<uint32_t>(n_local), ctx->stream));
+  MH_HIP(ctx, S->d_state.alloc(sizeof(mh::ShardState)));
+  MH_HIP(ctx, mh::launch_shard_state_init(S->state(), static_cast<uint32_t>(n_local), ctx->stream));
   if (!comm->rounds.empty() && comm->ws_ctx != ctx) return bail(fail(ctx, MH_ERR_INVALID_ARG, "mh_shard_icp_create: the communicator has rounds in flight on another context"));
   if (comm->rounds.empty()) {
     comm_bind(comm, ctx);
@@ -756,14 +766,15 @@ int fail_rounds(mh_shard_comm * comm, int rc)
 int ensure_ring(mh_ctx * ctx, mh_shard_comm * comm, size_t width)  // only with no round in flight
 {
   if (width <= comm->ring_width) return MH_OK;
-  if (comm->h_ring) AllocCache::free_pinned(comm->h_ring, sizeof(mh::ShardPublish) * comm->ring_width * kShardRing);
-  comm->h_ring = comm->d_h_ring = nullptr;
+  comm->h_ring.release();
+  comm->d_h_ring = nullptr;
   comm->ring_width = 0;
   size_t w = 1;
   while (w < width) w *= 2;
-  MH_HIP(ctx, AllocCache::alloc_pinned(reinterpret_cast<void **>(&comm->h_ring), sizeof(mh::ShardPublish) * w * kShardRing));
-  std::memset(comm->h_ring, 0, sizeof(mh::ShardPublish) * w * kShardRing);
-  MH_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&comm->d_h_ring), comm->h_ring, 0));
+  const size_t ring_bytes = sizeof(mh::ShardPublish) * w * kShardRing;
+  MH_HIP(ctx, comm->h_ring.reserve(ring_bytes, ring_bytes));
+  std::memset(comm->h_ring.p, 0, ring_bytes);  // (a recycled block holds another ring's words)
+  MH_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&comm->d_h_ring), comm->h_ring.p, 0));
   comm->ring_width = w;
   comm->ring_pos = 0;
   return MH_OK;
@@ -1064,7 +1075,7 @@ int enqueue_round(const RoundSpec * spec, size_t B)
     mh::ShardFactorArgs & a = fa[f];
     mhi::pose_delta(c.R_src, c.t_src, c.has_tgt ? c.R_tgt : nullptr, c.has_tgt ? c.t_tgt : nullptr, a.P.R, a.P.t);
     a.a = arrays_of(icp, false);
-    a.st = S->d_state;
+    a.st = S->state();
     a.inv_leaf = 1.0 / icp->map->cfg.leaf_size;
     a.dest = static_cast<uint8_t *>(S->d_dest.p);
     a.hist = static_cast<uint32_t *>(S->d_hist.p);
@@ -1117,7 +1128,7 @@ int enqueue_round(const RoundSpec * spec, size_t B)
     icp->n_pending = 0;  // the pending slot is not used: the call lives in the round
     mh::IcpArgs & a = ia[f];
     mh::LocArgs & l = la[f];
-    a.n_dev = l.n_dev = &S->d_state->n_slots[S->cur ^ 1];
+    a.n_dev = l.n_dev = &S->state()->n_slots[S->cur ^ 1];
     a.cold = S->cold_pending ? 1 : 0;  // (K3 still reads the status words: tombstones and held-back movers are marked there)
     round.calls[f].cold = S->cold_pending;
     S->cold_pending = false;
@@ -1180,10 +1191,10 @@ int enqueue_round(const RoundSpec * spec, size_t B)
   round.seq = comm->seq;
   const size_t slot = static_cast<size_t>(comm->ring_pos) * comm->ring_width;
   comm->ring_pos = (comm->ring_pos + 1) % kShardRing;
-  round.h_pub = comm->h_ring + slot;
+  round.h_pub = comm->h_ring.as<mh::ShardPublish>() + slot;
   mh::ShardPublish * d_pub = comm->d_h_ring + slot;
   if (B == 1) {
-    const hipError_t e = mh::launch_shard_publish(ar, round.any_components ? loc : nullptr, spec[0].S->d_state, spec[0].S->cur ^ 1, d_pub, round.seq, ctx->stream);
+    const hipError_t e = mh::launch_shard_publish(ar, round.any_components ? loc : nullptr, spec[0].S->state(), spec[0].S->cur ^ 1, d_pub, round.seq, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "launch_shard_publish");
   } else {
     for (size_t f0 = 0; f0 < B; f0 += mh::kShardBatchMax) {
@@ -1191,7 +1202,7 @@ int enqueue_round(const RoundSpec * spec, size_t B)
       std::memset(static_cast<void *>(&pb), 0, sizeof(pb));
       pb.n = static_cast<int>(std::min<size_t>(mh::kShardBatchMax, B - f0));
       for (int i = 0; i < pb.n; ++i) {
-        pb.st[i] = spec[f0 + i].S->d_state;
+        pb.st[i] = spec[f0 + i].S->state();
         pb.next[i] = spec[f0 + i].S->cur ^ 1;
       }
       pb.host = d_pub + f0;

@@ -2,9 +2,10 @@
 """Device-memory growth over many create / use / destroy cycles of every handle type (hipMemGetInfo before and after; the
 allocation cache keeps blocks, so the figure to watch is growth BETWEEN two identical batches of cycles)."""
 import ctypes as C, os, sys
-import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mimosa_amd import capi, synth, synth_photo as sp, replay
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+from mimosa_amd import capi
+from handle_lifetime_worker import make_cycle  # the round tests/test_gpu_handle_lifetime.py::test_nothing_leaks runs
 
 hip = C.CDLL("libamdhip64.so")
 def rss_mb():
@@ -18,32 +19,9 @@ def free_mb():
     return f.value / 2**20
 
 ctx = capi.Context(0)
-m = synth.make_room(1234, 0, 0, room=np.array([8.0, 6.0, 3.0]))
-pts, aux = synth.make_scan(n_rows=32, seed=5, n_cols=256, room=np.array([8.0, 6.0, 3.0]), sensor_local=np.array([3.0, 3.0, 1.2]))
-rc = capi.make_reg_config(**synth.enwide_config())
-pcfg = sp.photo_config(rows=64, cols=512)
-fr = [sp.make_frame(pcfg, k) for k in range(2)]
-raw, _ = synth.make_raw_scan(32, n_cols=256)
-
-def cycle():
-    gm = capi.VoxelMap(ctx)
-    gm.insert(m)
-    g2 = gm.copy()
-    g2.insert(m[:5000] + np.float32(0.3))
-    f = capi.ICPFactor(ctx, g2, pts, rc)
-    f.linearize(aux["R_W_L"], aux["t_W_L"])
-    c = f.clone()
-    capi.linearize_batch([f, c], [aux["R_W_L"]] * 2, [aux["t_W_L"]] * 2)
-    sc = capi.Scan(ctx)
-    sc.prepare_input(raw, capi.make_input_config())
-    sc.destroy()
-    P = capi.Photo(ctx, pcfg)
-    P.preprocess(fr[0]["raw"], fr[0]["deskewed"], fr[0]["unique_ns"], fr[0]["T_Le_Lt"])
-    P.detect(30, fr[0]["R_W_Be"], fr[0]["t_W_Be"], sp.BIAS_DIRECTIONS)
-    P.preprocess(fr[1]["raw"], fr[1]["deskewed"], fr[1]["unique_ns"], fr[1]["T_Le_Lt"])
-    pf = P.make_factor()
-    pf.linearize(fr[1]["R_W_Be"], fr[1]["t_W_Be"])
-    pf.destroy(); P.destroy(); c.destroy(); f.destroy(); g2.release(); gm.release()
+# one of every handle type per cycle: map and its copy; factor and clone (linearize, batch, align, score_poses); scan with
+# prefetch and deskew; photometric model, frame and factor; radar scan and factor; place database; pose graph; keyframe store
+cycle = make_cycle(ctx)
 
 for _ in range(20):
     cycle()
