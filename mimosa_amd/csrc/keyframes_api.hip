@@ -26,14 +26,14 @@ int keyframes_add_check(const mh_keyframes * kf, const char * who, size_t n)
   return MH_OK;
 }
 
-// enqueue the new entry (n device points, `stride` floats apart) behind everything on the stream, and book it
-int keyframes_append(mh_keyframes * kf, const char * who, const float * d_src, size_t n, size_t stride, int64_t tag, int32_t * index)
+// enqueue the new entry behind everything on the stream, and book it
+int keyframes_append(mh_keyframes * kf, const char * who, const DeviceCloud & src, int64_t tag, int32_t * index)
 {
   mh_ctx * ctx = kf->ctx;
-  const size_t i = kf->tags.size();
+  const size_t i = kf->tags.size(), n = src.n;
   const uint64_t at = kf->offsets.back();
   // (a launch that fails leaves the books where they were: the slot is simply written again)
-  const hipError_t e = mh::launch_keyframes_pack(d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), kf->arena() + at, kf->mem.d_offsets.as<unsigned long long>() + i, at + n,
+  const hipError_t e = mh::launch_keyframes_pack(src.d, static_cast<uint32_t>(n), static_cast<uint32_t>(src.stride), kf->arena() + at, kf->mem.d_offsets.as<unsigned long long>() + i, at + n,
                                                  ctx->stream);
   if (e != hipSuccess) return hip_fail(ctx, e, who);
   if (index) *index = static_cast<int32_t>(i);
@@ -115,20 +115,14 @@ int mh_keyframes_add(mh_keyframes * kf, const float * xyz, size_t n, size_t stri
     int rc = keyframes_alive(kf, "mh_keyframes_add");
     if (rc != MH_OK) return rc;
     mh_ctx * ctx = kf->ctx;
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add: stride_floats must be >= 3");
+    if ((rc = check_stride(ctx, "mh_keyframes_add", stride_floats)) != MH_OK) return rc;
     if ((rc = keyframes_add_check(kf, "mh_keyframes_add", n)) != MH_OK) return rc;
-    if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_keyframes_add: batch too large");
+    if ((rc = check_cloud_size(ctx, "mh_keyframes_add", n)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    if (n) {  // packed xyz through the pinned block, then the pack kernel every add shares
-      const size_t bytes = n * 3 * sizeof(float);
-      MH_HIP(ctx, kf->mem.h_io.reserve(bytes));  // (every call that used it has waited)
-      MH_HIP(ctx, kf->mem.d_in.reserve(bytes, ctx->stream, false));
-      float * h = kf->mem.h_io.as<float>();
-      for (size_t i = 0; i < n; ++i) std::memcpy(h + 3 * i, xyz + i * stride_floats, 3 * sizeof(float));
-      MH_HIP(ctx, hipMemcpyAsync(kf->mem.d_in.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = keyframes_append(kf, "mh_keyframes_add", kf->mem.d_in.as<const float>(), n, 3, tag, index);
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the pinned block is the next call's too)
+    DeviceCloud cloud;  // packed xyz through the pinned block, then the pack kernel every add shares
+    if ((rc = kf->mem.in.upload(ctx, xyz, n, stride_floats, &cloud)) != MH_OK) return rc;
+    rc = keyframes_append(kf, "mh_keyframes_add", cloud, tag, index);
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the pinned block is the next call's too, and mh_keyframes_get's)
     return rc;
   });
 }
@@ -140,11 +134,11 @@ int mh_keyframes_add_device(mh_keyframes * kf, const void * d_points, size_t n, 
     int rc = keyframes_alive(kf, "mh_keyframes_add_device");
     if (rc != MH_OK) return rc;
     mh_ctx * ctx = kf->ctx;
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_device: stride_floats must be >= 3");
+    if ((rc = check_stride(ctx, "mh_keyframes_add_device", stride_floats)) != MH_OK) return rc;
     if ((rc = keyframes_add_check(kf, "mh_keyframes_add_device", n)) != MH_OK) return rc;
-    if (n > 0x3fffffffu || stride_floats > 0xffffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_keyframes_add_device: batch too large");
+    if (n > kCloudMax || stride_floats > 0xffffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_keyframes_add_device: batch too large");
     MH_HIP(ctx, mh_enter(ctx));
-    return keyframes_append(kf, "mh_keyframes_add_device", static_cast<const float *>(d_points), n, stride_floats, tag, index);
+    return keyframes_append(kf, "mh_keyframes_add_device", DeviceCloud{static_cast<const float *>(d_points), n, stride_floats}, tag, index);
   });
 }
 
@@ -155,17 +149,12 @@ int mh_keyframes_add_from_scan(mh_keyframes * kf, const mh_scan * scan, int whic
     int rc = keyframes_alive(kf, "mh_keyframes_add_from_scan");
     if (rc != MH_OK) return rc;
     mh_ctx * ctx = kf->ctx;
-    if (which < 0 || which > 1) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: which must be 0 (points_full_) or 1 (Be_cloud_)");
     // the entry is ordered behind the scan's stages by the stream they share: a scan of another context is refused
-    if (scan->ctx != ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: scan belongs to another context");
-    if (!scan->prepared || (which == 1 && !scan->preprocessed)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: that stage has not run");
-    const void * d = which == 0 ? scan->d_full.p : scan->d_body.p;
-    const size_t n = which == 0 ? static_cast<size_t>(scan->c.n_full) : scan->n_body;
-    if (n && !d) return fail(ctx, MH_ERR_INVALID_ARG, "mh_keyframes_add_from_scan: that stage has not run");
-    if ((rc = keyframes_add_check(kf, "mh_keyframes_add_from_scan", n)) != MH_OK) return rc;
-    if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_keyframes_add_from_scan: batch too large");
+    DeviceCloud cloud;
+    if ((rc = scan_cloud(ctx, "mh_keyframes_add_from_scan", scan, which, Residence::same_context, &cloud)) != MH_OK) return rc;
+    if ((rc = keyframes_add_check(kf, "mh_keyframes_add_from_scan", cloud.n)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    return keyframes_append(kf, "mh_keyframes_add_from_scan", static_cast<const float *>(d), n, sizeof(mh_point32) / sizeof(float), tag, index);
+    return keyframes_append(kf, "mh_keyframes_add_from_scan", cloud, tag, index);
   });
 }
 
@@ -181,10 +170,10 @@ int mh_keyframes_get(mh_keyframes * kf, int32_t index, float * xyz, size_t capac
     const size_t take = xyz ? static_cast<size_t>(std::min<uint64_t>(n, capacity_points)) : 0;
     if (take) {
       MH_HIP(ctx, mh_enter(ctx));
-      MH_HIP(ctx, kf->mem.h_io.reserve(take * sizeof(float4)));  // (every call that used it has waited)
-      MH_HIP(ctx, hipMemcpyAsync(kf->mem.h_io.p, kf->arena() + at, take * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+      MH_HIP(ctx, kf->mem.in.h.reserve(take * sizeof(float4)));  // (mh_keyframes_add, the other user of the block, has waited)
+      MH_HIP(ctx, hipMemcpyAsync(kf->mem.in.h.p, kf->arena() + at, take * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
       MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      const float * h = kf->mem.h_io.as<const float>();
+      const float * h = kf->mem.in.h.as<const float>();
       for (size_t i = 0; i < take; ++i) std::memcpy(xyz + 3 * i, h + 4 * i, 3 * sizeof(float));
     }
     if (n_out) *n_out = static_cast<size_t>(n);

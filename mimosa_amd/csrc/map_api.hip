@@ -267,12 +267,13 @@ int insert_grouped(mh_map * m, const char * who, size_t n, const ChunkStamps * s
   return MH_OK;
 }
 
-// iVox::insert on a batch already on the device: n points `stride` floats apart, optional f32 transform (12 floats on
-// the device).  Synchronous: the map is current when this returns.
-int insert_device(mh_map * m, const float * d_src, size_t n, size_t stride, const float * d_Rt12)
+// iVox::insert on a batch already on the device, optional f32 transform (12 floats on the device).  Synchronous: the map is
+// current when this returns.  (It speaks as mh_map_insert whoever calls it.)
+int insert_device(mh_map * m, const DeviceCloud & src, const float * d_Rt12)
 {
   mh_ctx * ctx = m->ctx;
-  if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_map_insert: batch too large");
+  const size_t n = src.n;
+  if (const int rc = check_cloud_size(ctx, "mh_map_insert", n); rc != MH_OK) return rc;
   if (m->poisoned) return fail(ctx, MH_ERR_HIP, "mh_map_insert: the map is inconsistent after a failed mutation");
   // Factors of other contexts (HIP streams) may be reading this map: the arrays are modified in place and may be
   // reallocated, so the streams of the contexts that hold factors on it are waited for first (none in the usual
@@ -281,7 +282,7 @@ int insert_device(mh_map * m, const float * d_src, size_t n, size_t stride, cons
   if (n) {
     int rc = ensure_scratch(m, n);
     if (rc != MH_OK) return rc;
-    MH_HIP(ctx, mh::launch_map_insert_assign(arrays_of(m), d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), d_Rt12, m->inv_leaf, scratch_of(m),
+    MH_HIP(ctx, mh::launch_map_insert_assign(arrays_of(m), src.d, static_cast<uint32_t>(n), static_cast<uint32_t>(src.stride), d_Rt12, m->inv_leaf, scratch_of(m),
                                              ctx->stream));
     rc = insert_grouped(m, "mh_map_insert", n, nullptr);
     if (rc != MH_OK) return rc;
@@ -302,7 +303,7 @@ int rebuild_fill(mh_map * m, const mh_keyframes * kf, const std::vector<uint64_t
   const size_t K = sizes.size();
   const std::vector<mh::RebuildChunk> plan = mh::rebuild_plan(sizes.data(), K, m->lru_counter, static_cast<uint64_t>(m->cfg.lru_clear_cycle), budget);
   for (const mh::RebuildChunk & c : plan)
-    if (c.points > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": batch too large");
+    if (const int rc = check_cloud_size(ctx, who, c.points); rc != MH_OK) return rc;
   // the whole plan goes to the device once: [RebuildKeyframe x K | prefix offsets: (k1 - k0 + 1) words per chunk]
   const size_t kf_bytes = K * sizeof(mh::RebuildKeyframe), rel_words = K + plan.size();
   DevTemp<char> d_plan;
@@ -368,12 +369,12 @@ int rebuild_fill(mh_map * m, const mh_keyframes * kf, const std::vector<uint64_t
 // What insert_device would do to this batch, without doing it: phase A as the insert runs it, then phase C's rule on buckets held
 // in registers (map_preview_points_kernel).  Nothing a reader of the map sees is written — only the insert scratch and the
 // per-insert words of the state block — so the streams of other contexts' factors are not waited for.  One wait for the device.
-int preview_device(mh_map * m, const char * who, const float * d_src, size_t n, size_t stride, const float * d_Rt12, mh_map_insert_preview * out,
-                   uint8_t * outcome)
+int preview_device(mh_map * m, const char * who, const DeviceCloud & src, const float * d_Rt12, mh_map_insert_preview * out, uint8_t * outcome)
 {
   mh_ctx * ctx = m->ctx;
+  const size_t n = src.n;
   std::memset(out, 0, sizeof(*out));
-  if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": batch too large");
+  if (const int rc = check_cloud_size(ctx, who, n); rc != MH_OK) return rc;
   if (m->poisoned) return fail(ctx, MH_ERR_HIP, std::string(who) + ": the map is inconsistent after a failed mutation");
   if (n == 0) return MH_OK;
   int rc = ensure_scratch(m, n);
@@ -384,7 +385,7 @@ int preview_device(mh_map * m, const char * who, const float * d_src, size_t n, 
   uint8_t * d_outcome = outcome ? reinterpret_cast<uint8_t *>(m->s_preview.p) + words : nullptr;
   const mh::InsertScratch s = scratch_of(m);
   const mh::MapArrays a = arrays_of(m);
-  MH_HIP(ctx, mh::launch_map_insert_prepare(a, d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), d_Rt12, m->inv_leaf, s, ctx->stream));
+  MH_HIP(ctx, mh::launch_map_insert_prepare(a, src.d, static_cast<uint32_t>(n), static_cast<uint32_t>(src.stride), d_Rt12, m->inv_leaf, s, ctx->stream));
   // a rejected batch (bad_coord) is grouped well-formed under voxel (0,0,0) and the kernel below only reads: it can run before the
   // flag has been looked at, which spares a second wait
   MH_HIP(ctx, mh::launch_map_preview_points(a, static_cast<uint32_t>(n), m->n_voxels, static_cast<uint32_t>(m->cfg.max_points_in_cell), m->min_sq, s,
@@ -417,7 +418,7 @@ int carve_check(const mh_ctx * ctx, const char * who, size_t stride, const doubl
                 const mh_map_carve_config & c)
 {
   const std::string w(who);
-  if (stride < 3) return fail(ctx, MH_ERR_INVALID_ARG, w + ": stride_floats must be >= 3");
+  if (const int rc = check_stride(ctx, who, stride); rc != MH_OK) return rc;
   if (c.grid < mh::kCarveGridMin || c.grid > mh::kCarveGridMax) return fail(ctx, MH_ERR_INVALID_ARG, w + ": grid must be in 4..512");
   if (c.ring < 0 || c.ring > mh::kCarveRingMax) return fail(ctx, MH_ERR_INVALID_ARG, w + ": ring must be in 0..2");
   if (c.apply != 0 && c.apply != 1) return fail(ctx, MH_ERR_INVALID_ARG, w + ": apply must be 0 or 1");
@@ -432,12 +433,13 @@ int carve_check(const mh_ctx * ctx, const char * who, size_t stride, const doubl
   return MH_OK;
 }
 
-int carve_device(mh_map * m, const char * who, const float * d_src, size_t n, size_t stride, const double * origin, const double * R, const double * t,
+int carve_device(mh_map * m, const char * who, const DeviceCloud & src, const double * origin, const double * R, const double * t,
                  const mh_map_carve_config & c, mh_map_carve_result * out)
 {
   mh_ctx * ctx = m->ctx;
+  const size_t n = src.n;
   std::memset(out, 0, sizeof(*out));
-  if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": batch too large");
+  if (const int rc = check_cloud_size(ctx, who, n); rc != MH_OK) return rc;
   if (m->poisoned) return fail(ctx, MH_ERR_HIP, std::string(who) + ": the map is inconsistent after a failed mutation");
   if (n == 0) return MH_OK;
   if (c.apply) MH_HIP(ctx, map_wait_readers(m));
@@ -462,7 +464,7 @@ int carve_device(mh_map * m, const char * who, const float * d_src, size_t n, si
     MH_HIP(ctx, m->s_pos.reserve(nvs * sizeof(uint32_t), ctx->stream, false));
     MH_HIP(ctx, m->s_temp.reserve(mh::map_temp_bytes(nv), ctx->stream, false));
   }
-  MH_HIP(ctx, mh::launch_carve_image(d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), P, m->s_carve_img.p, ctx->stream));
+  MH_HIP(ctx, mh::launch_carve_image(src.d, static_cast<uint32_t>(n), static_cast<uint32_t>(src.stride), P, m->s_carve_img.p, ctx->stream));
   MH_HIP(ctx, mh::launch_carve_test(arrays_of(m), nv, P, m->s_carve_img.p, m->cfg.leaf_size, sensor_W, c.range_max, c.apply != 0,
                                     static_cast<uint32_t *>(m->s_carve_vox.p), static_cast<uint32_t *>(m->s_flags.p), ctx->stream));
   int rc = fetch_state(m);
@@ -554,6 +556,53 @@ int map_create(mh_ctx * ctx, const char * who, const mh_map_config * cfg, int ca
   *out = m;
   return MH_OK;
 }
+
+// R (9) and t (3) as the 12 floats the kernels read, on the device in `buf`
+int upload_rt12(const mh_ctx * ctx, DevBuf & buf, const float * R, const float * t, const float ** d_rt)
+{
+  float rt[12];
+  std::memcpy(rt, R, 9 * sizeof(float));
+  std::memcpy(rt + 9, t, 3 * sizeof(float));
+  MH_HIP(ctx, buf.reserve(sizeof(rt), ctx->stream, false));
+  MH_HIP(ctx, hipMemcpyAsync(buf.p, rt, sizeof(rt), hipMemcpyHostToDevice, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // rt is a stack buffer
+  *d_rt = buf.as<const float>();
+  return MH_OK;
+}
+
+// the body cloud of a scan, for the entry points that take no `which`: they name the call that is missing
+int body_cloud(const mh_ctx * ctx, const char * who, const mh_scan * scan, DeviceCloud * out)
+{
+  if (!scan->preprocessed) return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": no mh_scan_preprocess_geometric before");
+  return scan_cloud(ctx, who, scan, 1, Residence::same_device, out);
+}
+
+int check_shard(const mh_ctx * ctx, const char * who, int world, int rank, int block_log2)
+{
+  if (world < 1 || world > 64 || rank < 0 || rank >= world || block_log2 < 0 || block_log2 > 10)
+    return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": world in 1..64, 0 <= rank < world, block_log2 in 0..10");
+  return MH_OK;
+}
+
+// This rank's share of a batch (mh_map_insert_shard*): the points whose voxel lies in one of the rank's blocks or in their halo,
+// in their order, packed into s_shard.  One wait for the device (the count).
+int shard_keep(mh_map * map, const DeviceCloud & src, int world, int rank, int block_log2, DeviceCloud * kept)
+{
+  mh_ctx * ctx = map->ctx;
+  const size_t n = src.n;
+  *kept = DeviceCloud{map->s_shard.as<const float>(), 0, 3};
+  if (!n) return MH_OK;
+  MH_HIP(ctx, map->s_flags.reserve(n * sizeof(uint32_t), ctx->stream, false));
+  MH_HIP(ctx, map->s_pos.reserve(n * sizeof(uint32_t), ctx->stream, false));
+  MH_HIP(ctx, map->s_temp.reserve(std::max(mh::shard_temp_bytes(n), mh::map_temp_bytes(n)), ctx->stream, false));
+  MH_HIP(ctx, map->s_shard.reserve(n * 3 * sizeof(float), ctx->stream, false));
+  MH_HIP(ctx, mh::launch_shard_filter(src.d, static_cast<uint32_t>(n), static_cast<uint32_t>(src.stride), map->inv_leaf, static_cast<uint32_t>(world),
+                                      static_cast<uint32_t>(rank), block_log2, static_cast<uint32_t *>(map->s_flags.p), static_cast<uint32_t *>(map->s_pos.p),
+                                      static_cast<float *>(map->s_shard.p), &map->d_state.as<mh::MapState>()->n_keep, map->s_temp.p, map->s_temp.cap, ctx->stream));
+  const int rc = fetch_state(map);
+  if (rc == MH_OK) *kept = DeviceCloud{map->s_shard.as<const float>(), map->h_state->n_keep, 3};
+  return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -614,41 +663,19 @@ int mh_map_rebuild_from_keyframes(mh_keyframes * kf, const mh_map_config * cfg, 
   });
 }
 
-// the batch goes to the device through pinned staging as packed xyz (a pageable strided source would copy at a few GB/s)
-static int stage_batch(mh_map * map, const float * xyz, size_t n, size_t stride_floats, bool count_upload = true)
-{
-  mh_ctx * ctx = map->ctx;
-  if (n > (size_t(1) << 40) / 12) return fail(ctx, MH_ERR_OOM, "mh_map_insert: batch too large");
-  const size_t bytes = n * 3 * sizeof(float);
-  MH_HIP(ctx, map->h_in.reserve(bytes));
-  float * st = map->h_in.as<float>();
-  if (stride_floats == 3) {
-    std::memcpy(st, xyz, bytes);
-  } else {
-    for (size_t i = 0; i < n; ++i) {
-      st[3 * i] = xyz[i * stride_floats];
-      st[3 * i + 1] = xyz[i * stride_floats + 1];
-      st[3 * i + 2] = xyz[i * stride_floats + 2];
-    }
-  }
-  MH_HIP(ctx, map->s_in.reserve(bytes, ctx->stream, false));
-  MH_HIP(ctx, hipMemcpyAsync(map->s_in.p, st, bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (count_upload) map->upload_bytes += static_cast<int64_t>(bytes);  // a preview is no upload of the map's (mh_map_get_stats)
-  return MH_OK;
-}
-
 int mh_map_insert(mh_map * map, const float * xyz, size_t n, size_t stride_floats)
 {
   if (!map || (!xyz && n)) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_insert: NULL argument");
   mh_ctx * ctx = map->ctx;
   return guarded(ctx, "mh_map_insert", [&]() -> int {
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_insert: stride_floats must be >= 3");
+    int rc = check_stride(ctx, "mh_map_insert", stride_floats);
+    if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    if (n) {
-      const int rc = stage_batch(map, xyz, n, stride_floats);
-      if (rc != MH_OK) return rc;
-    }
-    return insert_device(map, static_cast<const float *>(map->s_in.p), n, 3, nullptr);
+    if (n > (size_t(1) << 40) / 12) return fail(ctx, MH_ERR_OOM, "mh_map_insert: batch too large");
+    DeviceCloud cloud;
+    if ((rc = map->in.upload(ctx, xyz, n, stride_floats, &cloud)) != MH_OK) return rc;  // (the insert waits for the stream: fetch_state)
+    map->upload_bytes += static_cast<int64_t>(n * 3 * sizeof(float));
+    return insert_device(map, cloud, nullptr);
   });
 }
 
@@ -660,28 +687,18 @@ int mh_map_insert_shard(mh_map * map, const float * xyz, size_t n, size_t stride
   if (!map || (!xyz && n)) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_insert_shard: NULL argument");
   mh_ctx * ctx = map->ctx;
   return guarded(ctx, "mh_map_insert_shard", [&]() -> int {
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_insert_shard: stride_floats must be >= 3");
-    if (world < 1 || world > 64 || rank < 0 || rank >= world || block_log2 < 0 || block_log2 > 10)
-      return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_insert_shard: world in 1..64, 0 <= rank < world, block_log2 in 0..10");
+    int rc = check_stride(ctx, "mh_map_insert_shard", stride_floats);
+    if (rc == MH_OK) rc = check_shard(ctx, "mh_map_insert_shard", world, rank, block_log2);
+    if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    size_t kept = 0;
+    DeviceCloud cloud, kept;
     if (n) {
-      if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_map_insert_shard: batch too large");
-      int rc = stage_batch(map, xyz, n, stride_floats);
-      if (rc != MH_OK) return rc;
-      MH_HIP(ctx, map->s_flags.reserve(n * sizeof(uint32_t), ctx->stream, false));
-      MH_HIP(ctx, map->s_pos.reserve(n * sizeof(uint32_t), ctx->stream, false));
-      MH_HIP(ctx, map->s_temp.reserve(mh::shard_temp_bytes(n) > mh::map_temp_bytes(n) ? mh::shard_temp_bytes(n) : mh::map_temp_bytes(n), ctx->stream, false));
-      MH_HIP(ctx, map->s_shard.reserve(n * 3 * sizeof(float), ctx->stream, false));
-      MH_HIP(ctx, mh::launch_shard_filter(static_cast<const float *>(map->s_in.p), static_cast<uint32_t>(n), 3, map->inv_leaf, static_cast<uint32_t>(world),
-                                          static_cast<uint32_t>(rank), block_log2, static_cast<uint32_t *>(map->s_flags.p),
-                                          static_cast<uint32_t *>(map->s_pos.p), static_cast<float *>(map->s_shard.p), &map->d_state.as<mh::MapState>()->n_keep, map->s_temp.p,
-                                          map->s_temp.cap, ctx->stream));
-      rc = fetch_state(map);
-      if (rc != MH_OK) return rc;
-      kept = map->h_state->n_keep;
+      if ((rc = check_cloud_size(ctx, "mh_map_insert_shard", n)) != MH_OK) return rc;
+      if ((rc = map->in.upload(ctx, xyz, n, stride_floats, &cloud)) != MH_OK) return rc;  // (shard_keep waits for the stream)
+      map->upload_bytes += static_cast<int64_t>(n * 3 * sizeof(float));
     }
-    return insert_device(map, static_cast<const float *>(map->s_shard.p), kept, 3, nullptr);
+    if ((rc = shard_keep(map, cloud, world, rank, block_log2, &kept)) != MH_OK) return rc;
+    return insert_device(map, kept, nullptr);
   });
 }
 
@@ -690,41 +707,26 @@ int mh_map_insert_shard(mh_map * map, const float * xyz, size_t n, size_t stride
 // device — what mh_scan_get_points + mh_transform_f32 + mh_map_insert_shard do through the host, without the three copies.
 int mh_map_insert_shard_from_scan(mh_map * map, const mh_scan * scan, const float R_W_Be[9], const float t_W_Be[3], int world, int rank, int block_log2)
 {
-  if (!map || !scan || !R_W_Be || !t_W_Be) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_insert_shard_from_scan: NULL argument");
+  const char * who = "mh_map_insert_shard_from_scan";
+  if (!map || !scan || !R_W_Be || !t_W_Be) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
   mh_ctx * ctx = map->ctx;
-  return guarded(ctx, "mh_map_insert_shard_from_scan", [&]() -> int {
-    if (!scan->preprocessed) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_insert_shard_from_scan: no mh_scan_preprocess_geometric before");
-    if (scan->ctx->device != ctx->device) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_insert_shard_from_scan: scan lives on another device");
-    if (world < 1 || world > 64 || rank < 0 || rank >= world || block_log2 < 0 || block_log2 > 10)
-      return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_insert_shard_from_scan: world in 1..64, 0 <= rank < world, block_log2 in 0..10");
+  return guarded(ctx, who, [&]() -> int {
+    DeviceCloud body, kept;
+    int rc = body_cloud(ctx, who, scan, &body);
+    if (rc == MH_OK) rc = check_shard(ctx, who, world, rank, block_log2);
+    if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    const size_t n = scan->n_body;
-    size_t kept = 0;
-    if (n) {
-      if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_map_insert_shard_from_scan: batch too large");
-      float rt[12];
-      std::memcpy(rt, R_W_Be, 9 * sizeof(float));
-      std::memcpy(rt + 9, t_W_Be, 3 * sizeof(float));
-      MH_HIP(ctx, map->s_rt.reserve(sizeof(rt), ctx->stream, false));
-      MH_HIP(ctx, hipMemcpyAsync(map->s_rt.p, rt, sizeof(rt), hipMemcpyHostToDevice, ctx->stream));
-      MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // rt is a stack buffer
+    if (body.n) {
+      const float * d_rt = nullptr;
+      if ((rc = upload_rt12(ctx, map->s_rt, R_W_Be, t_W_Be, &d_rt)) != MH_OK) return rc;
       // a copy of the body cloud (the scan keeps its own), transformed in place; the filter reads xyz at the records' stride
-      MH_HIP(ctx, map->s_in.reserve(n * sizeof(mh_point32), ctx->stream, false));
-      MH_HIP(ctx, hipMemcpyAsync(map->s_in.p, scan->d_body.p, n * sizeof(mh_point32), hipMemcpyDeviceToDevice, ctx->stream));
-      MH_HIP(ctx, mh::launch_transform(static_cast<mh_point32 *>(map->s_in.p), static_cast<int>(n), static_cast<const float *>(map->s_rt.p), ctx->stream));
-      MH_HIP(ctx, map->s_flags.reserve(n * sizeof(uint32_t), ctx->stream, false));
-      MH_HIP(ctx, map->s_pos.reserve(n * sizeof(uint32_t), ctx->stream, false));
-      MH_HIP(ctx, map->s_temp.reserve(mh::shard_temp_bytes(n) > mh::map_temp_bytes(n) ? mh::shard_temp_bytes(n) : mh::map_temp_bytes(n), ctx->stream, false));
-      MH_HIP(ctx, map->s_shard.reserve(n * 3 * sizeof(float), ctx->stream, false));
-      MH_HIP(ctx, mh::launch_shard_filter(static_cast<const float *>(map->s_in.p), static_cast<uint32_t>(n), static_cast<uint32_t>(sizeof(mh_point32) / sizeof(float)),
-                                          map->inv_leaf, static_cast<uint32_t>(world), static_cast<uint32_t>(rank), block_log2,
-                                          static_cast<uint32_t *>(map->s_flags.p), static_cast<uint32_t *>(map->s_pos.p), static_cast<float *>(map->s_shard.p),
-                                          &map->d_state.as<mh::MapState>()->n_keep, map->s_temp.p, map->s_temp.cap, ctx->stream));
-      const int rc = fetch_state(map);
-      if (rc != MH_OK) return rc;
-      kept = map->h_state->n_keep;
+      MH_HIP(ctx, map->in.d.reserve(body.n * sizeof(mh_point32), ctx->stream, false));
+      MH_HIP(ctx, hipMemcpyAsync(map->in.d.p, body.d, body.n * sizeof(mh_point32), hipMemcpyDeviceToDevice, ctx->stream));
+      MH_HIP(ctx, mh::launch_transform(static_cast<mh_point32 *>(map->in.d.p), static_cast<int>(body.n), d_rt, ctx->stream));
+      body.d = map->in.d.as<const float>();
     }
-    return insert_device(map, static_cast<const float *>(map->s_shard.p), kept, 3, nullptr);
+    if ((rc = shard_keep(map, body, world, rank, block_log2, &kept)) != MH_OK) return rc;
+    return insert_device(map, kept, nullptr);
   });
 }
 
@@ -733,29 +735,22 @@ int mh_map_insert_device(mh_map * map, const void * d_points, size_t n, size_t s
   if (!map || (!d_points && n)) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_insert_device: NULL argument");
   mh_ctx * ctx = map->ctx;
   return guarded(ctx, "mh_map_insert_device", [&]() -> int {
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_insert_device: stride_floats must be >= 3");
-    if ((R == nullptr) != (t == nullptr)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_insert_device: R and t go together");
+    int rc = check_stride(ctx, "mh_map_insert_device", stride_floats);
+    if (rc == MH_OK) rc = check_rt_pair(ctx, "mh_map_insert_device", R, t);
+    if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
     const float * d_rt = nullptr;
-    if (R) {
-      float rt[12];
-      std::memcpy(rt, R, 9 * sizeof(float));
-      std::memcpy(rt + 9, t, 3 * sizeof(float));
-      MH_HIP(ctx, map->s_rt.reserve(sizeof(rt), ctx->stream, false));
-      MH_HIP(ctx, hipMemcpyAsync(map->s_rt.p, rt, sizeof(rt), hipMemcpyHostToDevice, ctx->stream));
-      MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // rt is a stack buffer
-      d_rt = static_cast<const float *>(map->s_rt.p);
-    }
-    return insert_device(map, static_cast<const float *>(d_points), n, stride_floats, d_rt);
+    if (R && (rc = upload_rt12(ctx, map->s_rt, R, t, &d_rt)) != MH_OK) return rc;
+    return insert_device(map, DeviceCloud{static_cast<const float *>(d_points), n, stride_floats}, d_rt);
   });
 }
 
 int mh_map_insert_from_scan(mh_map * map, const mh_scan * scan, const float R_W_Be[9], const float t_W_Be[3])
 {
   if (!map || !scan) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_insert_from_scan: NULL argument");
-  if (!scan->preprocessed) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_insert_from_scan: no mh_scan_preprocess_geometric before");
-  if (scan->ctx->device != map->ctx->device) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_insert_from_scan: scan lives on another device");
-  return mh_map_insert_device(map, scan->d_body.p, scan->n_body, sizeof(mh_point32) / sizeof(float), R_W_Be, t_W_Be);
+  DeviceCloud body;
+  const int rc = body_cloud(map->ctx, "mh_map_insert_from_scan", scan, &body);
+  return rc != MH_OK ? rc : mh_map_insert_device(map, body.d, body.n, body.stride, R_W_Be, t_W_Be);
 }
 
 int mh_map_preview_insert(mh_map * map, const float * xyz, size_t n, size_t stride_floats, mh_map_insert_preview * out, uint8_t * outcome)
@@ -763,13 +758,13 @@ int mh_map_preview_insert(mh_map * map, const float * xyz, size_t n, size_t stri
   if (!map || !out || (!xyz && n)) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_preview_insert: NULL argument");
   mh_ctx * ctx = map->ctx;
   return guarded(ctx, "mh_map_preview_insert", [&]() -> int {
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert: stride_floats must be >= 3");
+    int rc = check_stride(ctx, "mh_map_preview_insert", stride_floats);
+    if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    if (n && n <= 0x3fffffffu && !map->poisoned) {
-      const int rc = stage_batch(map, xyz, n, stride_floats, false);
-      if (rc != MH_OK) return rc;
-    }
-    return preview_device(map, "mh_map_preview_insert", static_cast<const float *>(map->s_in.p), n, 3, nullptr, out, outcome);
+    DeviceCloud cloud{nullptr, n, 3};  // (a batch that will be refused is not staged)
+    // a preview is no upload of the map's: upload_bytes does not move.  (The preview waits for the stream: fetch_state.)
+    if (n <= kCloudMax && !map->poisoned && (rc = map->in.upload(ctx, xyz, n, stride_floats, &cloud)) != MH_OK) return rc;
+    return preview_device(map, "mh_map_preview_insert", cloud, nullptr, out, outcome);
   });
 }
 
@@ -779,20 +774,13 @@ int mh_map_preview_insert_device(mh_map * map, const void * d_points, size_t n, 
   if (!map || !out || (!d_points && n)) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_preview_insert_device: NULL argument");
   mh_ctx * ctx = map->ctx;
   return guarded(ctx, "mh_map_preview_insert_device", [&]() -> int {
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_device: stride_floats must be >= 3");
-    if ((R == nullptr) != (t == nullptr)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_device: R and t go together");
+    int rc = check_stride(ctx, "mh_map_preview_insert_device", stride_floats);
+    if (rc == MH_OK) rc = check_rt_pair(ctx, "mh_map_preview_insert_device", R, t);
+    if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
     const float * d_rt = nullptr;
-    if (R) {
-      float rt[12];
-      std::memcpy(rt, R, 9 * sizeof(float));
-      std::memcpy(rt + 9, t, 3 * sizeof(float));
-      MH_HIP(ctx, map->s_rt.reserve(sizeof(rt), ctx->stream, false));
-      MH_HIP(ctx, hipMemcpyAsync(map->s_rt.p, rt, sizeof(rt), hipMemcpyHostToDevice, ctx->stream));
-      MH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // rt is a stack buffer
-      d_rt = static_cast<const float *>(map->s_rt.p);
-    }
-    return preview_device(map, "mh_map_preview_insert_device", static_cast<const float *>(d_points), n, stride_floats, d_rt, out, outcome);
+    if (R && (rc = upload_rt12(ctx, map->s_rt, R, t, &d_rt)) != MH_OK) return rc;
+    return preview_device(map, "mh_map_preview_insert_device", DeviceCloud{static_cast<const float *>(d_points), n, stride_floats}, d_rt, out, outcome);
   });
 }
 
@@ -800,9 +788,9 @@ int mh_map_preview_insert_from_scan(mh_map * map, const mh_scan * scan, const fl
                                     uint8_t * outcome)
 {
   if (!map || !scan || !out) return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_preview_insert_from_scan: NULL argument");
-  if (!scan->preprocessed) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_from_scan: no mh_scan_preprocess_geometric before");
-  if (scan->ctx->device != map->ctx->device) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_preview_insert_from_scan: scan lives on another device");
-  return mh_map_preview_insert_device(map, scan->d_body.p, scan->n_body, sizeof(mh_point32) / sizeof(float), R_W_Be, t_W_Be, out, outcome);
+  DeviceCloud body;
+  const int rc = body_cloud(map->ctx, "mh_map_preview_insert_from_scan", scan, &body);
+  return rc != MH_OK ? rc : mh_map_preview_insert_device(map, body.d, body.n, body.stride, R_W_Be, t_W_Be, out, outcome);
 }
 
 int mh_map_carve(mh_map * map, const float * xyz, size_t n, size_t stride_floats, const double origin_F[3], const double R_W_F[9], const double t_W_F[3],
@@ -815,11 +803,10 @@ int mh_map_carve(mh_map * map, const float * xyz, size_t n, size_t stride_floats
     int rc = carve_check(ctx, "mh_map_carve", stride_floats, origin_F, R_W_F, t_W_F, *cfg);
     if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    if (n && n <= 0x3fffffffu && !map->poisoned) {
-      rc = stage_batch(map, xyz, n, stride_floats, false);  // no upload of the map's: upload_bytes does not move
-      if (rc != MH_OK) return rc;
-    }
-    return carve_device(map, "mh_map_carve", static_cast<const float *>(map->s_in.p), n, 3, origin_F, R_W_F, t_W_F, *cfg, out);
+    DeviceCloud cloud{nullptr, n, 3};  // (a batch that will be refused is not staged)
+    // no upload of the map's: upload_bytes does not move.  (The carve waits for the stream: fetch_state.)
+    if (n <= kCloudMax && !map->poisoned && (rc = map->in.upload(ctx, xyz, n, stride_floats, &cloud)) != MH_OK) return rc;
+    return carve_device(map, "mh_map_carve", cloud, origin_F, R_W_F, t_W_F, *cfg, out);
   });
 }
 
@@ -833,7 +820,7 @@ int mh_map_carve_device(mh_map * map, const void * d_points, size_t n, size_t st
     const int rc = carve_check(ctx, "mh_map_carve_device", stride_floats, origin_F, R_W_F, t_W_F, *cfg);
     if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    return carve_device(map, "mh_map_carve_device", static_cast<const float *>(d_points), n, stride_floats, origin_F, R_W_F, t_W_F, *cfg, out);
+    return carve_device(map, "mh_map_carve_device", DeviceCloud{static_cast<const float *>(d_points), n, stride_floats}, origin_F, R_W_F, t_W_F, *cfg, out);
   });
 }
 
@@ -842,13 +829,9 @@ int mh_map_carve_from_scan(mh_map * map, const mh_scan * scan, int which, const 
 {
   if (!map || !scan || !out || !cfg || !origin_F || !R_W_F || !t_W_F)
     return fail(map ? map->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: NULL argument");
-  if (which < 0 || which > 1) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: which must be 0 (points_full_) or 1 (Be_cloud_)");
-  if (!scan->prepared || (which == 1 && !scan->preprocessed)) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: that stage has not run");
-  if (scan->ctx->device != map->ctx->device) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: scan lives on another device");
-  const void * d = which == 0 ? scan->d_full.p : scan->d_body.p;
-  const size_t n = which == 0 ? static_cast<size_t>(scan->c.n_full) : scan->n_body;
-  if (n && !d) return fail(map->ctx, MH_ERR_INVALID_ARG, "mh_map_carve_from_scan: that stage has not run");
-  return mh_map_carve_device(map, d, n, sizeof(mh_point32) / sizeof(float), origin_F, R_W_F, t_W_F, cfg, out);
+  DeviceCloud cloud;
+  const int rc = scan_cloud(map->ctx, "mh_map_carve_from_scan", scan, which, Residence::same_device, &cloud);
+  return rc != MH_OK ? rc : mh_map_carve_device(map, cloud.d, cloud.n, cloud.stride, origin_F, R_W_F, t_W_F, cfg, out);
 }
 
 int mh_map_copy(const mh_map * src, mh_map ** out)
@@ -940,11 +923,11 @@ int mh_map_get_cloud(const mh_map * cmap, float * xyz, size_t capacity_points, s
     MH_HIP(ctx, map->s_flags.reserve(nv * sizeof(uint32_t), ctx->stream, false));
     MH_HIP(ctx, map->s_pos.reserve(nv * sizeof(uint32_t), ctx->stream, false));
     MH_HIP(ctx, map->s_temp.reserve(mh::map_temp_bytes(nv), ctx->stream, false));
-    MH_HIP(ctx, map->s_in.reserve(np * 3 * sizeof(float), ctx->stream, false));
+    MH_HIP(ctx, map->in.d.reserve(np * 3 * sizeof(float), ctx->stream, false));
     MH_HIP(ctx, mh::launch_map_cloud(arrays_of(map), nv, static_cast<uint32_t *>(map->s_flags.p), static_cast<uint32_t *>(map->s_pos.p),
-                                     static_cast<float *>(map->s_in.p), np, map->s_temp.p, map->s_temp.cap, ctx->stream));
+                                     static_cast<float *>(map->in.d.p), np, map->s_temp.p, map->s_temp.cap, ctx->stream));
     const size_t take = np < capacity_points ? np : capacity_points;
-    MH_HIP(ctx, hipMemcpyAsync(xyz, map->s_in.p, take * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(xyz, map->in.d.p, take * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MH_OK;
   });

@@ -1640,14 +1640,13 @@ static int mh_scan_get_points_impl(const mh_scan * s, int which, mh_point32 * ou
 {
   if (!s || !n_out) return fail(s ? s->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_scan_get_points: NULL argument");
   mh_ctx * ctx = s->ctx;
-  if (!s->prepared || (which != 0 && !s->preprocessed) || which < 0 || which > 2)
-    return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_get_points: that stage has not run");
-  const DevBuf & b = which == 0 ? s->d_full : (which == 1 ? s->d_body : s->d_ds);
-  *n_out = which == 0 ? s->c.n_full : (which == 1 ? s->n_body : s->c.n_downsampled);
+  DeviceCloud stage;
+  if (!scan_stage(s, which, &stage)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_get_points: that stage has not run");
+  *n_out = stage.n;
   if (!out) return MH_OK;
   if (capacity < *n_out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_scan_get_points: buffer too small");
   MH_HIP(ctx, mh_enter(ctx));
-  if (*n_out) MH_HIP(ctx, hipMemcpyAsync(out, b.p, *n_out * sizeof(mh_point32), hipMemcpyDeviceToHost, ctx->stream));
+  if (*n_out) MH_HIP(ctx, hipMemcpyAsync(out, stage.d, *n_out * sizeof(mh_point32), hipMemcpyDeviceToHost, ctx->stream));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return scan_imu_error(s, ctx, "mh_scan_get_points");
 }
@@ -1659,11 +1658,10 @@ int mh_scan_get_points(const mh_scan * s, int which, mh_point32 * out, size_t ca
 int mh_scan_device_points(const mh_scan * s, int which, const mh_point32 ** d_points, size_t * n_out)
 {
   if (!s || !d_points || !n_out) return fail(s ? s->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_scan_device_points: NULL argument");
-  if (!s->prepared || (which != 0 && !s->preprocessed) || which < 0 || which > 2)
-    return fail(s->ctx, MH_ERR_INVALID_ARG, "mh_scan_device_points: that stage has not run");
-  const DevBuf & b = which == 0 ? s->d_full : (which == 1 ? s->d_body : s->d_ds);
-  *d_points = static_cast<const mh_point32 *>(b.p);
-  *n_out = which == 0 ? s->c.n_full : (which == 1 ? s->n_body : s->c.n_downsampled);
+  DeviceCloud stage;
+  if (!scan_stage(s, which, &stage)) return fail(s->ctx, MH_ERR_INVALID_ARG, "mh_scan_device_points: that stage has not run");
+  *d_points = reinterpret_cast<const mh_point32 *>(stage.d);
+  *n_out = stage.n;
   return MH_OK;
 }
 

@@ -688,6 +688,41 @@ struct PinnedBuf
   }
 };
 
+// ---- cloud sources: what the entry points that take a point cloud share ("Cloud sources") -----------------------------
+// A cloud on the device: n points `stride` floats apart, xyz first.  What every consumer of a cloud reads.
+struct DeviceCloud
+{
+  const float * d = nullptr;
+  size_t n = 0, stride = 3;
+};
+constexpr size_t kCloudMax = 0x3fffffffu;  // points per batch: what the 32-bit indices of the kernels leave room for
+inline int check_stride(const mh_ctx * ctx, const char * who, size_t stride) { return stride >= 3 ? MH_OK : fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": stride_floats must be >= 3"); }
+inline int check_rt_pair(const mh_ctx * ctx, const char * who, const void * R, const void * t) { return !R == !t ? MH_OK : fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + ": R and t go together"); }
+inline int check_cloud_size(const mh_ctx * ctx, const char * who, size_t n) { return n <= kCloudMax ? MH_OK : fail(ctx, MH_ERR_UNSUPPORTED, std::string(who) + ": batch too large"); }
+// A host cloud on its way to the device: packed xyz in a pinned block (a pageable strided source would copy at a few GB/s), uploaded
+// behind everything on the context's stream.  A member of its handle's buffers.  The next upload rewrites the pinned block, so
+// whoever uploads waits for the stream before it returns (each caller says where).
+struct HostStage
+{
+  PinnedBuf h;
+  DevBuf d;
+  int upload(const mh_ctx * ctx, const float * xyz, size_t n, size_t stride, DeviceCloud * out)
+  {
+    const size_t bytes = n * 3 * sizeof(float);
+    if (n) {
+      MH_HIP(ctx, h.reserve(bytes));
+      MH_HIP(ctx, d.reserve(bytes, ctx->stream, false));
+      if (stride == 3)
+        std::memcpy(h.p, xyz, bytes);
+      else
+        for (size_t i = 0; i < n; ++i) std::memcpy(h.as<float>() + 3 * i, xyz + i * stride, 3 * sizeof(float));
+      MH_HIP(ctx, hipMemcpyAsync(d.p, h.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    *out = DeviceCloud{d.as<const float>(), n, 3};
+    return MH_OK;
+  }
+};
+
 // device-resident scan front end (mh_scan_*): state of one scan
 struct mh_scan
 {
@@ -733,6 +768,29 @@ inline int scan_imu_error(const mh_scan * s, const mh_ctx * ctx, const char * wh
   return MH_OK;
 }
 
+// The stage `which` of a scan — 0 points_full_, 1 Be_cloud_, 2 the downsampled cloud — as mh_point32 records; false: it has not run
+inline bool scan_stage(const mh_scan * s, int which, DeviceCloud * c)
+{
+  if (which < 0 || which > 2 || !s->prepared || (which != 0 && !s->preprocessed)) return false;
+  const void * d = which == 0 ? s->d_full.p : (which == 1 ? s->d_body.p : s->d_ds.p);
+  *c = DeviceCloud{static_cast<const float *>(d), which == 0 ? s->c.n_full : (which == 1 ? s->n_body : s->c.n_downsampled), sizeof(mh_point32) / sizeof(float)};
+  return true;
+}
+// The one way from (scan, which in 0..1) to the cloud a consumer reads.  The checks, in this order: which, the stage has run,
+// residence, a buffer behind a count, the size.  Residence: the same device will do for a consumer that reads the scan's buffers
+// after the scan's calls have returned; one that is ordered behind them by the stream alone asks for its own context.
+enum class Residence { same_device, same_context };
+inline int scan_cloud(const mh_ctx * ctx, const char * who, const mh_scan * scan, int which, Residence residence, DeviceCloud * out)
+{
+  const auto refuse = [&](const char * why) { return fail(ctx, MH_ERR_INVALID_ARG, std::string(who) + why); };  // (no string unless it fails)
+  if (which < 0 || which > 1) return refuse(": which must be 0 (points_full_) or 1 (Be_cloud_)");
+  if (!scan_stage(scan, which, out)) return refuse(": that stage has not run");
+  if (residence == Residence::same_context && scan->ctx != ctx) return refuse(": scan belongs to another context");
+  if (scan->ctx->device != ctx->device) return refuse(": scan lives on another device");
+  if (out->n && !out->d) return refuse(": that stage has not run");
+  return check_cloud_size(ctx, who, out->n);
+}
+
 // IncrementalVoxelMapPCL counterpart: the device-resident voxel map (map_device.hpp / map_kernels.hip).  The device
 // arrays ARE the map; the host keeps counters only (refreshed from the mapped state after every mutation).
 struct mh_map
@@ -748,10 +806,10 @@ struct mh_map
   uint32_t n_voxels = 0, n_blocks = 0;
   uint64_t n_points = 0, lru_counter = 0;
   // insert scratch (grown on demand, reused)
-  DevBuf s_in, s_pts, s_group, s_seg_vid, s_seg_added, s_blk_new, s_flags, s_pos, s_temp, s_rt, s_shard;
+  DevBuf s_pts, s_group, s_seg_vid, s_seg_added, s_blk_new, s_flags, s_pos, s_temp, s_rt, s_shard;
   DevBuf s_preview;  // mh_map_preview_insert*: [too close | voxel full] per segment (n words each), then n outcome bytes
   DevBuf s_carve_img, s_carve_vox;  // mh_map_carve*: the observation image (+ its counter); removed / tested / emptied per voxel
-  PinnedBuf h_in;  // pinned staging of a host batch
+  HostStage in;    // a host batch on its way in; in.d is also where the other calls keep a cloud of their own (shard copy, get_cloud)
   int64_t inserts = 0, upload_bytes = 0, purges = 0;
   int n_off = 0;
   int8_t off[27][3];
@@ -773,8 +831,7 @@ struct mh_keyframes final : CtxOwned
   {
     DevBuf d_arena;    // float4: capacity_points entries
     DevBuf d_offsets;  // unsigned long long: capacity_keyframes + 1, entry i is points [d_offsets[i], d_offsets[i + 1]) of the arena
-    DevBuf d_in;       // a host batch, packed float4
-    PinnedBuf h_io;    // pinned staging of a host batch / of a read-back
+    HostStage in;      // a host batch on its way in; in.h is also the landing block of a read-back
   } mem;
   float4 * arena() const { return mem.d_arena.as<float4>(); }
   void ctx_gone() override

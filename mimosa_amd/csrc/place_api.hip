@@ -31,9 +31,8 @@ struct mh_place_db final : CtxOwned
     DevBuf norms;    // double: capacity x 60
     DevBuf scores;   // PlaceScore: capacity
     DevBuf query;    // [a descriptor, 4 864 B | its norms, 512 B | hits, 256 B]
-    DevBuf d_in;     // a host batch, packed xyz
     PinnedBuf h;     // the pinned block
-    PinnedBuf h_in;  // pinned staging of a host batch
+    HostStage in;    // a host batch on its way in
   } mem;
   float * d_desc() const { return mem.desc.as<float>(); }
   double * d_norms() const { return mem.norms.as<double>(); }
@@ -69,47 +68,20 @@ int place_check_desc(const mh_ctx * ctx, const char * who, const float * desc)
   return MH_OK;
 }
 
-// the stage `which` of a scan as a device batch
-int place_scan_points(const mh_place_db * db, const char * who, const mh_scan * scan, int which, const void ** d, size_t * n)
-{
-  const std::string w(who);
-  if (which < 0 || which > 1) return fail(db->ctx, MH_ERR_INVALID_ARG, w + ": which must be 0 (points_full_) or 1 (Be_cloud_)");
-  if (!scan->prepared || (which == 1 && !scan->preprocessed)) return fail(db->ctx, MH_ERR_INVALID_ARG, w + ": that stage has not run");
-  if (scan->ctx->device != db->ctx->device) return fail(db->ctx, MH_ERR_INVALID_ARG, w + ": scan lives on another device");
-  *d = which == 0 ? scan->d_full.p : scan->d_body.p;
-  *n = which == 0 ? static_cast<size_t>(scan->c.n_full) : scan->n_body;
-  if (*n && !*d) return fail(db->ctx, MH_ERR_INVALID_ARG, w + ": that stage has not run");
-  if (*n > 0x3fffffffu) return fail(db->ctx, MH_ERR_UNSUPPORTED, w + ": batch too large");
-  return MH_OK;
-}
-
 // enqueue: d_desc (device, 1 200 floats) = the descriptor of the batch
-int place_describe_to(mh_place_db * db, const char * who, const float * d_src, size_t n, size_t stride, const double * R, float * d_desc)
+int place_describe_to(mh_place_db * db, const char * who, const DeviceCloud & src, const double * R, float * d_desc)
 {
   mh::PlaceParams P = db->P;
   std::memcpy(P.R, R, sizeof(P.R));
-  const hipError_t e = mh::launch_place_describe(d_src, static_cast<uint32_t>(n), static_cast<uint32_t>(stride), P, d_desc, db->ctx->stream);
+  const hipError_t e = mh::launch_place_describe(src.d, static_cast<uint32_t>(src.n), static_cast<uint32_t>(src.stride), P, d_desc, db->ctx->stream);
   return e == hipSuccess ? MH_OK : hip_fail(db->ctx, e, who);
 }
 
-// a host batch, packed to xyz in the pinned staging block and uploaded behind everything on the stream
-int place_stage(mh_place_db * db, const float * xyz, size_t n, size_t stride)
-{
-  mh_ctx * ctx = db->ctx;
-  const size_t bytes = n * 3 * sizeof(float);
-  MH_HIP(ctx, db->mem.h_in.reserve(bytes));  // (every call that used it has waited)
-  MH_HIP(ctx, db->mem.d_in.reserve(bytes, ctx->stream, false));
-  float * h = db->mem.h_in.as<float>();
-  for (size_t i = 0; i < n; ++i) std::memcpy(h + 3 * i, xyz + i * stride, 3 * sizeof(float));
-  MH_HIP(ctx, hipMemcpyAsync(db->mem.d_in.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return MH_OK;
-}
-
 // describe into the query block, bring the descriptor to the caller: one wait
-int place_describe_out(mh_place_db * db, const char * who, const float * d_src, size_t n, size_t stride, const double * R, float * desc)
+int place_describe_out(mh_place_db * db, const char * who, const DeviceCloud & src, const double * R, float * desc)
 {
   mh_ctx * ctx = db->ctx;
-  const int rc = place_describe_to(db, who, d_src, n, stride, R, reinterpret_cast<float *>(db->d_query()));
+  const int rc = place_describe_to(db, who, src, R, reinterpret_cast<float *>(db->d_query()));
   if (rc != MH_OK) return rc;
   MH_HIP(ctx, hipMemcpyAsync(db->h() + kPlaceHostDescAt, db->d_query(), kPlaceDescBytes, hipMemcpyDeviceToHost, ctx->stream));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -241,12 +213,13 @@ int mh_place_describe(mh_place_db * db, const float * xyz, size_t n, size_t stri
     int rc = place_alive(db, "mh_place_describe");
     if (rc != MH_OK) return rc;
     mh_ctx * ctx = db->ctx;
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_place_describe: stride_floats must be >= 3");
+    if ((rc = check_stride(ctx, "mh_place_describe", stride_floats)) != MH_OK) return rc;
     if ((rc = place_check_R(ctx, "mh_place_describe", R_G_F)) != MH_OK) return rc;
-    if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_place_describe: batch too large");
+    if ((rc = check_cloud_size(ctx, "mh_place_describe", n)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    if (n && (rc = place_stage(db, xyz, n, stride_floats)) != MH_OK) return rc;
-    return place_describe_out(db, "mh_place_describe", static_cast<const float *>(db->mem.d_in.p), n, 3, R_G_F, desc);
+    DeviceCloud cloud;
+    if ((rc = db->mem.in.upload(ctx, xyz, n, stride_floats, &cloud)) != MH_OK) return rc;  // (place_describe_out waits for the stream)
+    return place_describe_out(db, "mh_place_describe", cloud, R_G_F, desc);
   });
 }
 
@@ -257,11 +230,11 @@ int mh_place_describe_device(mh_place_db * db, const void * d_points, size_t n, 
     int rc = place_alive(db, "mh_place_describe_device");
     if (rc != MH_OK) return rc;
     mh_ctx * ctx = db->ctx;
-    if (stride_floats < 3) return fail(ctx, MH_ERR_INVALID_ARG, "mh_place_describe_device: stride_floats must be >= 3");
+    if ((rc = check_stride(ctx, "mh_place_describe_device", stride_floats)) != MH_OK) return rc;
     if ((rc = place_check_R(ctx, "mh_place_describe_device", R_G_F)) != MH_OK) return rc;
-    if (n > 0x3fffffffu) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_place_describe_device: batch too large");
+    if ((rc = check_cloud_size(ctx, "mh_place_describe_device", n)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    return place_describe_out(db, "mh_place_describe_device", static_cast<const float *>(d_points), n, stride_floats, R_G_F, desc);
+    return place_describe_out(db, "mh_place_describe_device", DeviceCloud{static_cast<const float *>(d_points), n, stride_floats}, R_G_F, desc);
   });
 }
 
@@ -272,12 +245,11 @@ int mh_place_describe_from_scan(mh_place_db * db, const mh_scan * scan, int whic
     int rc = place_alive(db, "mh_place_describe_from_scan");
     if (rc != MH_OK) return rc;
     mh_ctx * ctx = db->ctx;
-    const void * d = nullptr;
-    size_t n = 0;
-    if ((rc = place_scan_points(db, "mh_place_describe_from_scan", scan, which, &d, &n)) != MH_OK) return rc;
+    DeviceCloud cloud;
+    if ((rc = scan_cloud(ctx, "mh_place_describe_from_scan", scan, which, Residence::same_device, &cloud)) != MH_OK) return rc;
     if ((rc = place_check_R(ctx, "mh_place_describe_from_scan", R_G_F)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    return place_describe_out(db, "mh_place_describe_from_scan", static_cast<const float *>(d), n, sizeof(mh_point32) / sizeof(float), R_G_F, desc);
+    return place_describe_out(db, "mh_place_describe_from_scan", cloud, R_G_F, desc);
   });
 }
 
@@ -311,15 +283,14 @@ int mh_place_db_add_from_scan(mh_place_db * db, const mh_scan * scan, int which,
     if (rc != MH_OK) return rc;
     mh_ctx * ctx = db->ctx;
     if ((rc = place_add_check(db, "mh_place_db_add_from_scan")) != MH_OK) return rc;
-    const void * d = nullptr;
-    size_t n = 0;
-    if ((rc = place_scan_points(db, "mh_place_db_add_from_scan", scan, which, &d, &n)) != MH_OK) return rc;
+    DeviceCloud cloud;
+    if ((rc = scan_cloud(ctx, "mh_place_db_add_from_scan", scan, which, Residence::same_device, &cloud)) != MH_OK) return rc;
     if ((rc = place_check_R(ctx, "mh_place_db_add_from_scan", R_G_F)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
     // on the device from end to end, and nothing waits: the entry is behind this call on the context's stream, where every
     // reader of it is enqueued.  (A launch that fails leaves the size where it was: the slot is simply written again.)
     float * slot = db->d_desc() + db->size * mh::kPlaceCells;
-    rc = place_describe_to(db, "mh_place_db_add_from_scan", static_cast<const float *>(d), n, sizeof(mh_point32) / sizeof(float), R_G_F, slot);
+    rc = place_describe_to(db, "mh_place_db_add_from_scan", cloud, R_G_F, slot);
     if (rc != MH_OK) return rc;
     MH_HIP(ctx, mh::launch_place_norms(slot, db->d_norms() + db->size * mh::kPlaceSectors, ctx->stream));
     if (index) *index = static_cast<int32_t>(db->size);
@@ -374,13 +345,11 @@ int mh_place_db_query_from_scan(mh_place_db * db, const mh_scan * scan, int whic
     if (rc != MH_OK) return rc;
     mh_ctx * ctx = db->ctx;
     if ((rc = place_check_query(db, "mh_place_db_query_from_scan", n_search, top_k)) != MH_OK) return rc;
-    const void * d = nullptr;
-    size_t n = 0;
-    if ((rc = place_scan_points(db, "mh_place_db_query_from_scan", scan, which, &d, &n)) != MH_OK) return rc;
+    DeviceCloud cloud;
+    if ((rc = scan_cloud(ctx, "mh_place_db_query_from_scan", scan, which, Residence::same_device, &cloud)) != MH_OK) return rc;
     if ((rc = place_check_R(ctx, "mh_place_db_query_from_scan", R_G_F)) != MH_OK) return rc;
     MH_HIP(ctx, mh_enter(ctx));
-    rc = place_describe_to(db, "mh_place_db_query_from_scan", static_cast<const float *>(d), n, sizeof(mh_point32) / sizeof(float), R_G_F,
-                           reinterpret_cast<float *>(db->d_query()));
+    rc = place_describe_to(db, "mh_place_db_query_from_scan", cloud, R_G_F, reinterpret_cast<float *>(db->d_query()));
     if (rc != MH_OK) return rc;
     return place_query_chain(db, "mh_place_db_query_from_scan", n_search, top_k, hits, all);
   });
