@@ -222,6 +222,7 @@ HOST_TESTS = {
     "place_device_check": ("place_device_check.cpp", ["place_device.hpp", "math3.hpp"]),
     "pose_graph_step": ("pose_graph_step.cpp", ["pose_graph_device.hpp", "window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "pose_graph_robust_step": ("pose_graph_robust_step.cpp", ["pose_graph_device.hpp", "window_device.hpp", "align_device.hpp", "math3.hpp"]),
+    "pose_graph_cov_step": ("pose_graph_cov_step.cpp", ["pose_graph_device.hpp", "window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "rebuild_plan_check": ("rebuild_plan_check.cpp", ["rebuild_plan.hpp"]),
     "window_request_check": ("window_request_check.cpp", ["window_request.hpp", "rebuild_plan.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]),
 }

@@ -32,6 +32,7 @@ EXPORTS = [
     "mh_pose_graph_create", "mh_pose_graph_destroy", "mh_pose_graph_set_poses", "mh_pose_graph_set_fixed", "mh_pose_graph_set_edges",
     "mh_pose_graph_get_poses", "mh_pose_graph_residuals", "mh_pose_graph_optimise",
     "mh_pose_graph_set_priors", "mh_pose_graph_set_loss", "mh_pose_graph_prior_residuals", "mh_pose_graph_weights",
+    "mh_pose_graph_covariances",
     "mh_keyframes_create", "mh_keyframes_destroy", "mh_keyframes_size", "mh_keyframes_get_info", "mh_keyframes_add", "mh_keyframes_add_device",
     "mh_keyframes_add_from_scan", "mh_keyframes_get", "mh_keyframes_device_points", "mh_map_rebuild_from_keyframes",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
@@ -773,6 +774,7 @@ def load(build_if_missing: bool = True):
     L.mh_pose_graph_set_loss.argtypes = [vp, C.POINTER(PoseGraphLoss), C.POINTER(PoseGraphLoss)]
     L.mh_pose_graph_prior_residuals.argtypes = [vp, vp, vp]
     L.mh_pose_graph_weights.argtypes = [vp, vp, vp, vp]
+    L.mh_pose_graph_covariances.argtypes = [vp, C.c_double, vp, vp, sz, vp, C.POINTER(PoseGraphCovInfo)]
     L.mh_keyframes_create.argtypes = [vp, C.POINTER(KeyframesConfig), pvp]
     L.mh_keyframes_destroy.argtypes = [vp]
     L.mh_keyframes_destroy.restype = None
@@ -2301,6 +2303,29 @@ class PoseGraphLoss(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("param", C.c_double)]
 
 
+MH_PGO_COV_PAIRS_MAX = 64
+
+
+class PoseGraphCovInfo(C.Structure):
+    """mh_pose_graph_cov_info (16 bytes)."""
+    _fields_ = [("n_poses", C.c_int32), ("n_far", C.c_int32), ("n_pairs", C.c_int32), ("flags", C.c_int32)]
+
+
+def _gate_edge_terms(Ra, ta, Rb, tb, ZR, Zt):
+    """an edge's residual [Log(Z.R^T R_ab), Z.R^T (t_ab - Z.t)] and J_a = -Ad(T_ab^-1) (J_b = I): rule 1 of the pose graph"""
+    hat = lambda v: np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    abR, abt = Ra.T @ Rb, Ra.T @ (tb - ta)
+    Re = ZR.T @ abR
+    th = np.arccos(min(1.0, max(-1.0, (np.trace(Re) - 1.0) / 2.0)))
+    k = 0.5 if th < 1e-9 else th / (2.0 * np.sin(th))
+    r = np.concatenate([np.array([Re[2, 1] - Re[1, 2], Re[0, 2] - Re[2, 0], Re[1, 0] - Re[0, 1]]) * k, ZR.T @ (abt - Zt)])
+    Ri, ti = abR.T, -(abR.T @ abt)
+    Ad = np.zeros((6, 6))
+    Ad[:3, :3] = Ad[3:, 3:] = Ri
+    Ad[3:, :3] = hat(ti) @ Ri
+    return r, -Ad
+
+
 def make_pose_prior(priors):
     """an array of mh_pose_prior from dicts {"pose": i, "Z": (R, t) the measured pose (world from keyframe), "info": 6 x 6}"""
     arr = (PosePrior * max(len(priors), 1))()
@@ -2398,6 +2423,35 @@ class PoseGraph:
         r, chi2, f = np.empty((self.n_edges, 6)), np.empty(self.n_edges), C.c_double(0.0)
         self.ctx.check(self.L.mh_pose_graph_residuals(self.h, _p(r) if self.n_edges else None, _p(chi2) if self.n_edges else None, C.byref(f)))
         return r, chi2, float(f.value)
+
+    def covariances(self, damping=0.0, pairs=None):
+        """mh_pose_graph_covariances: (cov n x 6 x 6, joint p x 12 x 12, info {"n_poses", "n_far", "n_pairs", "flags"}) at the stored
+        poses; nothing moves.  pairs: up to 64 (i, j) with i < j.  With flags == 4 (a pivot was not positive) the library writes
+        nothing, and both arrays come back filled with NaN."""
+        pr = np.ascontiguousarray(np.asarray(pairs if pairs is not None else [], np.int32).reshape(-1, 2))
+        cov, joint, info = np.full((self.n, 6, 6), np.nan), np.full((len(pr), 12, 12), np.nan), PoseGraphCovInfo()
+        self.ctx.check(self.L.mh_pose_graph_covariances(self.h, float(damping), _p(cov), _p(pr) if len(pr) else None, len(pr), _p(joint) if len(pr) else None,
+                                                        C.byref(info)))
+        return cov, joint, {"n_poses": int(info.n_poses), "n_far": int(info.n_far), "n_pairs": int(info.n_pairs), "flags": int(info.flags)}
+
+    def gate(self, candidates, damping=0.0):
+        """Up to 64 candidate edges that are NOT in the graph (dicts as make_window_edge takes them), each tested against the
+        joint marginal of its two poses: {"r": c x 6 the residual at the stored poses, "chi2": r^T Om r as mh_pose_graph_residuals
+        would report it, "d2": r^T (J S J^T + Om^-1)^-1 r with J = [J_a | I] and S the pair's 12 x 12 joint covariance, "flags"}.
+        d2 is chi^2 with 6 degrees of freedom for a true loop, whatever the drift between the two poses.  Host arithmetic on
+        covariances()."""
+        R, t = self.poses()
+        pairs = [(int(e["a"]), int(e["b"])) for e in candidates]
+        _, joint, info = self.covariances(damping, pairs)
+        r, chi2, d2 = np.zeros((len(pairs), 6)), np.zeros(len(pairs)), np.full(len(pairs), np.nan)
+        for k, ((a, b), e) in enumerate(zip(pairs, candidates)):
+            Om = np.asarray(e["info"], np.float64).reshape(6, 6)
+            r[k], Ja = _gate_edge_terms(R[a], t[a], R[b], t[b], np.asarray(e["Z"][0], np.float64).reshape(3, 3), np.asarray(e["Z"][1], np.float64).reshape(3))
+            chi2[k] = r[k] @ Om @ r[k]
+            if info["flags"] == 0:
+                J = np.hstack([Ja, np.eye(6)])
+                d2[k] = r[k] @ np.linalg.solve(J @ joint[k] @ J.T + np.linalg.inv(Om), r[k])
+        return {"r": r, "chi2": chi2, "d2": d2, "flags": info["flags"]}
 
     def optimise(self, cfg: PoseGraphConfig = None, trace_poses=False, **kw):
         """mh_pose_graph_optimise: {"iters", "converged", "n_poses", "n_far", "f_first", "f_last", "trace": [{"f", "step_rot",

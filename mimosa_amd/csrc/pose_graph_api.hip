@@ -17,6 +17,7 @@ static_assert(sizeof(mh_pose_prior) == 392 && sizeof(mh_pose_graph_loss) == 16, 
 static_assert(MH_PGO_LOSS_NONE == mh::kPgoLossNone && MH_PGO_LOSS_HUBER == mh::kPgoLossHuber && MH_PGO_LOSS_CAUCHY == mh::kPgoLossCauchy &&
                 MH_PGO_LOSS_DCS == mh::kPgoLossDcs,
               "MH_PGO_LOSS_*");
+static_assert(sizeof(mh_pose_graph_cov_info) == 16 && MH_PGO_COV_PAIRS_MAX == mh::kPgoCovPairsMax, "mh_pose_graph_cov_info layout");
 static_assert(MH_PGO_MAX_POSES == mh::kPgoMaxPoses && MH_PGO_MAX_EDGES == mh::kPgoMaxEdges && MH_PGO_FAR_MAX == mh::kPgoFarMax && mh::kPgoMaxIters == 64,
               "mh_pose_graph_* constants");
 
@@ -25,6 +26,7 @@ namespace mh
 hipError_t launch_pgo_edges(const PgoGraph & g, bool want_res, hipStream_t stream);
 hipError_t launch_pgo_cost(const PgoGraph & g, bool chi2, hipStream_t stream);
 hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream);
+hipError_t launch_pgo_covariances(const PgoGraph & g, const PgoParams & p, const PgoCov & cov, hipStream_t stream);
 }  // namespace mh
 
 struct mh_pose_graph final : CtxOwned
@@ -38,6 +40,8 @@ struct mh_pose_graph final : CtxOwned
   {
     DevBuf block;     // every array of mh::PgoGraph (pgo_layout)
     DevBuf trace;     // double, iters x n x 12: the poses behind every step (grown on demand)
+    DevBuf cov;       // mh_pose_graph_covariances (allocated at its first call): P and Sigma_ii (36 max_poses each), joint, pairs
+    DevBuf cov_cols;  // ... the pairs' columns X, Z (6 n x 6 n_pairs each) and U (6 F x 6 n_pairs), grown on demand
     PinnedBuf h_out;  // pinned staging of whatever a call hands to the host (grown on demand)
   } mem;
   uint4 * h_words = nullptr;  // one flagged word per iteration (mapped pinned, zeroed at create) and its device-side address
@@ -279,6 +283,59 @@ int pgo_residuals(mh_pose_graph * pg, double * r, double * chi2, double * f)
   if (f) std::memcpy(f, pg->h_out(), sizeof(double));
   if (r && E) std::memcpy(r, pg->h_out() + 16, 6 * E * sizeof(double));
   if (chi2 && E) std::memcpy(chi2, pg->h_out() + 16 + 6 * E * sizeof(double), E * sizeof(double));
+  return MH_OK;
+}
+
+// rule 10: the system as an iteration assembles it, up to C's factor; the chain, the correction, the pairs' columns; one wait
+int pgo_covariances(mh_pose_graph * pg, double damping, double * cov, const int32_t * pairs, size_t n_pairs, double * joint, mh_pose_graph_cov_info * info)
+{
+  mh_ctx * ctx = pg->ctx;
+  const size_t N = pg->n, D = sizeof(double), ncols = 6 * n_pairs;
+  MH_HIP(ctx, mh_enter(ctx));
+  const size_t at_pairs = 16, at_cov = at_pairs + 2 * mh::kPgoCovPairsMax * sizeof(int), at_joint = at_cov + 36 * N * D;
+  const int rc = pgo_host(pg, at_joint + 144 * n_pairs * D);
+  if (rc != MH_OK) return rc;
+  // the fixed part: P, Sigma_ii, joint, pairs
+  const size_t off_S = 36 * pg->max_poses * D, off_joint = 2 * off_S, off_pairs = off_joint + 144 * mh::kPgoCovPairsMax * D;
+  if (!pg->mem.cov.p) MH_HIP(ctx, pg->mem.cov.alloc(off_pairs + 2 * mh::kPgoCovPairsMax * sizeof(int)));
+  const size_t col = 6 * N * ncols * D, ucol = 6 * pg->n_far * ncols * D;
+  if (n_pairs) MH_HIP(ctx, pg->mem.cov_cols.reserve(2 * col + ucol, ctx->stream, false));
+  const mh::PgoGraph g = pgo_graph(pg);
+  const mh::PgoParams p{damping, 0.0, 0.0};
+  char * const base = pg->mem.cov.as<char>();
+  mh::PgoCov c{};
+  c.n_pairs = static_cast<int>(n_pairs);
+  c.ncols = static_cast<int>(ncols);
+  c.P = reinterpret_cast<double *>(base);
+  c.S = reinterpret_cast<double *>(base + off_S);
+  c.joint = reinterpret_cast<double *>(base + off_joint);
+  c.pairs = reinterpret_cast<int *>(base + off_pairs);
+  if (n_pairs) {
+    c.X = pg->mem.cov_cols.as<double>();
+    c.Z = c.X + 6 * N * ncols;
+    c.U = c.Z + 6 * N * ncols;
+  }
+  hipError_t e = hipMemsetAsync(g.st, 0, sizeof(mh::PgoState), ctx->stream);
+  size_t at = at_pairs;
+  if (e == hipSuccess && n_pairs) e = pgo_up(pg, at, c.pairs, pairs, 2 * n_pairs);
+  if (e == hipSuccess) e = mh::launch_pgo_covariances(g, p, c, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out(), g.st, sizeof(mh::PgoState), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(pg->h_out() + at_cov, c.S, 36 * N * D, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && n_pairs) e = hipMemcpyAsync(pg->h_out() + at_joint, c.joint, 144 * n_pairs * D, hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return hip_fail(ctx, e, "mh_pose_graph_covariances");
+  }
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  mh::PgoState st;
+  std::memcpy(&st, pg->h_out(), sizeof(st));
+  info->n_poses = static_cast<int32_t>(N);
+  info->n_far = static_cast<int32_t>(pg->n_far);
+  info->n_pairs = static_cast<int32_t>(n_pairs);
+  info->flags = st.ok ? 0 : 4;
+  if (!st.ok) return MH_OK;  // (what the kernels behind the failed pivot left on the device is not a result: nothing is handed out)
+  if (cov) std::memcpy(cov, pg->h_out() + at_cov, 36 * N * D);
+  if (joint && n_pairs) std::memcpy(joint, pg->h_out() + at_joint, 144 * n_pairs * D);
   return MH_OK;
 }
 
@@ -586,6 +643,26 @@ int mh_pose_graph_residuals(mh_pose_graph * pg, double * r, double * chi2, doubl
     if (rc != MH_OK) return rc;
     if (pg->n == 0) return fail(pg->ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_residuals: no poses have been set");
     return pgo_residuals(pg, r, chi2, f);
+  });
+}
+
+int mh_pose_graph_covariances(mh_pose_graph * pg, double damping, double * cov, const int32_t * pairs, size_t n_pairs, double * joint,
+                              mh_pose_graph_cov_info * info)
+{
+  if (!pg || !info) return fail(pg ? pg->ctx : nullptr, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: NULL argument");
+  return guarded(pg->ctx, "mh_pose_graph_covariances", [&]() -> int {
+    const int rc = pgo_alive(pg, "mh_pose_graph_covariances");
+    if (rc != MH_OK) return rc;
+    const mh_ctx * ctx = pg->ctx;
+    if (!cov && !joint) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: cov and joint are both NULL");
+    if (n_pairs > MH_PGO_COV_PAIRS_MAX) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: n_pairs must be in 0..64");
+    if (n_pairs && (!pairs || !joint)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: pairs and joint must be given with n_pairs > 0");
+    if (!(damping >= 0.0) || !std::isfinite(damping)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: damping must be >= 0 and finite");
+    if (pg->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: no poses have been set");
+    for (size_t p = 0; p < n_pairs; ++p)
+      if (pairs[2 * p] < 0 || pairs[2 * p] >= pairs[2 * p + 1] || static_cast<size_t>(pairs[2 * p + 1]) >= pg->n)
+        return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: pair " + std::to_string(p) + " needs 0 <= i < j < n");
+    return pgo_covariances(pg, damping, cov, pairs, n_pairs, joint, info);
   });
 }
 

@@ -387,13 +387,14 @@ MH_HD bool pgo_factor(const PgoGraph & g, double * sm, Par & par)
 }
 
 // ---- T out = v for one column: window_sweep over N blocks -----------------------------------------------------------------------
-// col < 6 F: column col of W^T; col == 6 F: the right-hand side; src != nullptr: that vector instead.  out has `stride` doubles
-// between rows.  One lane per column; L_i, D_i, G_i are the same for every column.
-MH_HD void pgo_sweep_col(const PgoGraph & g, int col, const double * src, double * out, int stride)
+// col < 6 F: column col of W^T; col == 6 F: the right-hand side; src != nullptr: that vector instead (`src_stride` doubles
+// between its rows; it may be `out` itself); unit >= 0: the unit vector of that row instead.  out has `stride` doubles between
+// rows.  One lane per column; L_i, D_i, G_i are the same for every column.
+MH_HD void pgo_sweep_col(const PgoGraph & g, int col, const double * src, double * out, int stride, int src_stride = 1, int unit = -1)
 {
   const int N = g.N;
   int fa = -1, fb = -1, f = 0, c = 0;
-  if (!src && col < 6 * g.F) {
+  if (!src && unit < 0 && col < 6 * g.F) {
     f = col / 6, c = col % 6;
     const int e = g.far[f];
     fa = g.fixed[g.ea[e]] ? -1 : g.ea[e];
@@ -404,8 +405,10 @@ MH_HD void pgo_sweep_col(const PgoGraph & g, int col, const double * src, double
     double v[6];
     for (int r = 0; r < 6; ++r) {
       double s;
-      if (src)
-        s = src[6 * i + r];
+      if (unit >= 0)
+        s = 6 * i + r == unit ? 1.0 : 0.0;
+      else if (src)
+        s = src[static_cast<size_t>(6 * i + r) * src_stride];
       else if (col == 6 * g.F)
         s = g.rhs[6 * i + r];
       else
@@ -494,25 +497,30 @@ MH_HD void pgo_solve_C(const PgoGraph & g, const double * y, int stride, Par & p
   for (int j = n - 1; j >= 1; --j) par.each(j, [&](int i) { g.u[i] -= g.C[j * n + i] * g.u[j]; });
 }
 
+// entry `row` of y - Y u for the entry y of one column and its u (`ustride` doubles between entries)
+MH_HD double pgo_apply_value(const PgoGraph & g, double y, const double * u, int ustride, int row)
+{
+  const int n = 6 * g.F;
+  double s = y;
+  for (int c = 0; c < n; ++c) s -= g.Y[static_cast<size_t>(row) * g.K + c] * u[static_cast<size_t>(c) * ustride];
+  return s;
+}
 // entry `row` of y - Y u: into x (first) or added to it (a refinement step)
 MH_HD void pgo_apply_row(const PgoGraph & g, const double * y, int stride, bool first, int row)
 {
-  const int n = 6 * g.F;
-  double s = y[static_cast<size_t>(row) * stride];
-  for (int c = 0; c < n; ++c) s -= g.Y[static_cast<size_t>(row) * g.K + c] * g.u[c];
+  const double s = pgo_apply_value(g, y[static_cast<size_t>(row) * stride], g.u, 1, row);
   g.x[row] = first ? s : g.x[row] + s;
 }
 
 // entry `row` of g.r = rhs - A x against the system as assembled (T's blocks, then the pose's far edges in list order, each
 // entry times the edge's weight), in twice the working precision as the window chains take it.  The row of a fixed pose is zero.
-MH_HD void pgo_residual_row(const PgoGraph & g, int row)
+// pgo_residual_value: the same for any column: its right-hand side entry and its x (`xs` doubles between entries).
+MH_HD double pgo_residual_value(const PgoGraph & g, int row, double rhs, const double * x, int xs)
 {
   const int i = row / 6, r = row % 6;
-  if (g.fixed[i]) {
-    g.r[row] = 0.0;
-    return;
-  }
-  double hi = g.rhs[row], lo = 0.0;
+  if (g.fixed[i]) return 0.0;
+  auto X = [&](int k) { return x[static_cast<size_t>(k) * xs]; };
+  double hi = rhs, lo = 0.0;
   auto term = [&](double a, double xj) {
     const double pr = a * xj, pe = fma(a, xj, -pr);  // a x = pr + pe exactly
     const double s = hi - pr, bv = s - hi;
@@ -520,10 +528,10 @@ MH_HD void pgo_residual_row(const PgoGraph & g, int row)
     hi = s;
   };
   if (i > 0)
-    for (int m = 0; m < 6; ++m) term(g.Eb[36 * i + 6 * r + m], g.x[6 * (i - 1) + m]);
-  for (int m = 0; m < 6; ++m) term(g.A[36 * i + 6 * r + m], g.x[6 * i + m]);
+    for (int m = 0; m < 6; ++m) term(g.Eb[36 * i + 6 * r + m], X(6 * (i - 1) + m));
+  for (int m = 0; m < 6; ++m) term(g.A[36 * i + 6 * r + m], X(6 * i + m));
   if (i + 1 < g.N)
-    for (int m = 0; m < 6; ++m) term(g.Eb[36 * (i + 1) + 6 * m + r], g.x[6 * (i + 1) + m]);
+    for (int m = 0; m < 6; ++m) term(g.Eb[36 * (i + 1) + 6 * m + r], X(6 * (i + 1) + m));
   const int * inc = g.inc + g.inc_off[i];
   const int n = g.inc_off[i + 1] - g.inc_off[i];
   for (int k = 0; k < n; ++k) {
@@ -533,16 +541,17 @@ MH_HD void pgo_residual_row(const PgoGraph & g, int row)
     const double we = g.w[e];
     if (inc[k] & 1) {
       if (!g.fixed[a])
-        for (int m = 0; m < 6; ++m) term(we * g.Eba[36 * e + 6 * r + m], g.x[6 * a + m]);
-      for (int m = 0; m < 6; ++m) term(we * g.Om[36 * e + 6 * r + m], g.x[6 * b + m]);
+        for (int m = 0; m < 6; ++m) term(we * g.Eba[36 * e + 6 * r + m], X(6 * a + m));
+      for (int m = 0; m < 6; ++m) term(we * g.Om[36 * e + 6 * r + m], X(6 * b + m));
     } else {
-      for (int m = 0; m < 6; ++m) term(we * g.Baa[36 * e + 6 * r + m], g.x[6 * a + m]);
+      for (int m = 0; m < 6; ++m) term(we * g.Baa[36 * e + 6 * r + m], X(6 * a + m));
       if (!g.fixed[b])
-        for (int m = 0; m < 6; ++m) term(we * g.Eba[36 * e + 6 * m + r], g.x[6 * b + m]);
+        for (int m = 0; m < 6; ++m) term(we * g.Eba[36 * e + 6 * m + r], X(6 * b + m));
     }
   }
-  g.r[row] = hi + lo;
+  return hi + lo;
 }
+MH_HD void pgo_residual_row(const PgoGraph & g, int row) { g.r[row] = pgo_residual_value(g, row, g.rhs[row], g.x, 1); }
 
 // ---- the phases of one iteration that one workgroup runs ------------------------------------------------------------------------
 // stage 0, behind the sweep of all K columns: C and its factors, u for y = Y[:, 6F]; stage 1, 2, behind the sweep of g.r into
@@ -654,6 +663,207 @@ inline int pgo_iterate_host(const PgoGraph & g, const PgoParams & p, int it, dou
   }
   pgo_finish(g, p, it, trace, par);
   return g.rows[it].flags;
+}
+
+// ---- marginal covariances (mh_pose_graph_covariances) ---------------------------------------------------------------------------
+// Sigma = A^-1 at the stored poses, from what an iteration leaves behind its stage-0 pgo_small: T = L D L^T (g.L, g.Dv, g.G),
+// Y = T^-1 W^T and C = L_C D_C L_C^T.  By the Woodbury identity A^-1 = T^-1 - Y C^-1 Y^T:
+//   P_i = (T^-1)_ii     the backward recursion P_{N-1} = S_{N-1}^-1, P_i = S_i^-1 + G_{i+1} P_{i+1} G_{i+1}^T (pgo_cov_chain)
+//   Sigma_ii            P_i - U_i^T D_C^-1 U_i, U_i = L_C^-1 Y_i^T (pgo_cov_correct: six right-hand sides side by side)
+//   Sigma_ij, i < j     block row i of the six columns X = A^-1 E_j: Z = T^-1 E_j (pgo_sweep_col, unit source), X = Z - Y C^-1 W Z,
+//                       then the chains' two refinement steps against A (pgo_residual_value, pgo_apply_value)
+// The arrays are a block of their own (PgoCov), not pgo_layout's: a graph that never asks for covariances does not pay for them.
+// A column lives at stride `ncols` (6 per pair): entry `row` of column q is at [row * ncols + q], one lane per column.
+constexpr int kPgoCovPairsMax = 64;
+constexpr int kPgoCovPanel = 8;     // rows of C's factor staged at a time by pgo_cov_correct
+constexpr int kPgoCovChainSm = 108; // doubles pgo_cov_chain shares: S_i^-1, M = G P, the current P
+struct PgoCov
+{
+  int n_pairs, ncols;  // ncols = 6 n_pairs
+  double *P, *S;       // 36 N each: (T^-1)_ii; Sigma_ii (symmetric to the bit, zero for a fixed pose)
+  double *X, *Z;       // 6 N x ncols each: the columns; T^-1 of the unit source, then of each residual
+  double * U;          // 6 F x ncols: C^-1 W z per column
+  double * joint;      // 144 n_pairs
+  int * pairs;         // 2 n_pairs: i < j
+};
+// doubles pgo_cov_correct shares for a graph of F far edges: U (6F x 6), then a panel of kPgoCovPanel rows of C
+MH_HD int pgo_cov_correct_sm(int F) { return 6 * F * (6 + kPgoCovPanel); }
+
+// One step of the recursion at block i, two phases.  Lb, Db: L_i, D_i; Gn: G_{i+1}; Pn: P_{i+1} (`last`: i == N - 1, neither is read).
+// phase 1, index l < 42: column l of S_i^-1 by window_solve6 (l < 6), else entry l - 6 of M = G_{i+1} P_{i+1}
+MH_HD void pgo_cov_step1(const double * Lb, const double * Db, const double * Gn, const double * Pn, bool last, double * Si, double * M, int l)
+{
+  if (l < 6) {
+    double e[6] = {0, 0, 0, 0, 0, 0}, col[6];
+    e[l] = 1.0;
+    window_solve6(Lb, Db, e, col);
+    for (int m = 0; m < 6; ++m) Si[6 * m + l] = col[m];
+  } else if (!last) {
+    const int a = (l - 6) / 6, m = (l - 6) % 6;
+    double s = 0.0;
+    for (int k = 0; k < 6; ++k) s += Gn[6 * a + k] * Pn[6 * k + m];
+    M[l - 6] = s;
+  }
+}
+// phase 2, index l < 36: entry (a, b), a >= b, of P_i = S_i^-1 + M G_{i+1}^T, written to both triangles of Pc (the next step's
+// P_{i+1}) and of out
+MH_HD void pgo_cov_step2(const double * Gn, const double * Si, const double * M, bool last, double * Pc, double * out, int l)
+{
+  const int a = l / 6, b = l % 6;
+  if (b > a) return;
+  double s = Si[6 * a + b];
+  if (!last)
+    for (int m = 0; m < 6; ++m) s += M[6 * a + m] * Gn[6 * b + m];
+  Pc[6 * a + b] = Pc[6 * b + a] = s;
+  out[6 * a + b] = out[6 * b + a] = s;
+}
+// the recursion over all blocks as the host runs it (the kernel walks the same two phases with block i - 1 prefetched)
+template <typename Par>
+MH_HD void pgo_cov_chain(const PgoGraph & g, const PgoCov & cov, double * sm, Par & par)
+{
+  double *Si = sm, *M = sm + 36, *Pc = sm + 72;
+  for (int i = g.N - 1; i >= 0; --i) {
+    const bool last = i == g.N - 1;
+    const double * Gn = last ? g.G : g.G + 36 * (i + 1);
+    par.each(42, [&](int l) { pgo_cov_step1(g.L + 36 * i, g.Dv + 6 * i, Gn, Pc, last, Si, M, l); });
+    par.each(36, [&](int l) { pgo_cov_step2(Gn, Si, M, last, Pc, cov.P + 36 * i, l); });
+  }
+}
+
+// Sigma_ii of pose i by one workgroup.  U = Y_i^T (6F x 6) is forward-substituted through L_C in place: row k takes
+// U[k] -= L_C[k][j] U[j] for j ascending, every product rounded and subtracted by itself; C's factor is staged kPgoCovPanel rows
+// at a time (the part left of the panel first, then the panel's own triangle row by row).  Then entry (a, b), a >= b:
+// P_i[a][b] - sum_k (U[k][a] U[k][b]) / D_C[k], k ascending, mirrored.  A fixed pose: zeros.  F == 0: P_i's lower triangle, mirrored.
+template <typename Par>
+MH_HD void pgo_cov_correct(const PgoGraph & g, const PgoCov & cov, int i, double * sm, Par & par)
+{
+  const int n = 6 * g.F, K = g.K;
+  double * S = cov.S + 36 * i;
+  const double * P = cov.P + 36 * i;
+  if (g.fixed[i]) {
+    par.each(36, [&](int l) { S[l] = 0.0; });
+    return;
+  }
+  double *U = sm, *Lp = sm + 6 * n;
+  par.each(6 * n, [&](int l) { U[l] = g.Y[static_cast<size_t>(6 * i + l % 6) * K + l / 6]; });
+  for (int r0 = 0; r0 < n; r0 += kPgoCovPanel) {
+    const int nb = n - r0 < kPgoCovPanel ? n - r0 : kPgoCovPanel, wd = r0 + nb;
+    par.each(nb * wd, [&](int l) { Lp[(l / wd) * n + l % wd] = g.C[(r0 + l / wd) * n + l % wd]; });
+    par.each(nb * 6, [&](int l) {
+      const int il = l / 6, c = l % 6;
+      double s = U[6 * (r0 + il) + c];
+      for (int j = 0; j < r0; ++j) s -= Lp[il * n + j] * U[6 * j + c];
+      U[6 * (r0 + il) + c] = s;
+    });
+    for (int jl = 0; jl + 1 < nb; ++jl)
+      par.each((nb - jl - 1) * 6, [&](int l) {
+        const int il = jl + 1 + l / 6, c = l % 6;
+        U[6 * (r0 + il) + c] -= Lp[il * n + r0 + jl] * U[6 * (r0 + jl) + c];
+      });
+  }
+  par.each(36, [&](int l) {
+    const int a = l / 6, b = l % 6;
+    if (b > a) return;
+    double s = P[6 * a + b];
+    for (int k = 0; k < n; ++k) s -= (U[6 * k + a] * U[6 * k + b]) / g.C[k * n + k];
+    S[6 * a + b] = S[6 * b + a] = s;
+  });
+}
+
+// ---- a pair's columns, one lane per column q (pair q / 6, column q % 6 of E_j) ---------------------------------------------------
+MH_HD int pgo_cov_unit(const PgoCov & cov, int q) { return 6 * cov.pairs[2 * (q / 6) + 1] + q % 6; }
+// Z = T^-1 E_j (first), or Z = T^-1 Z in place for a residual
+MH_HD void pgo_cov_sweep(const PgoGraph & g, const PgoCov & cov, int q, bool first)
+{
+  pgo_sweep_col(g, 0, cov.Z + q, cov.Z + q, cov.ncols, cov.ncols, first ? pgo_cov_unit(cov, q) : -1);
+}
+// u = C^-1 W z for column q: pgo_solve_C's sums in its order (forward j ascending, backward j descending), one lane running them
+MH_HD void pgo_cov_solve(const PgoGraph & g, const PgoCov & cov, int q)
+{
+  const int n = 6 * g.F;
+  const size_t us = static_cast<size_t>(cov.ncols);
+  double * u = cov.U + q;
+  for (int row = 0; row < n; ++row) u[row * us] = pgo_W_row(g, row, cov.Z + q, cov.ncols);
+  for (int i = 1; i < n; ++i) {
+    double s = u[i * us];
+    for (int j = 0; j < i; ++j) s -= g.C[i * n + j] * u[j * us];
+    u[i * us] = s;
+  }
+  for (int j = 0; j < n; ++j) u[j * us] = u[j * us] / g.C[j * n + j];
+  for (int i = n - 2; i >= 0; --i) {
+    double s = u[i * us];
+    for (int j = n - 1; j > i; --j) s -= g.C[j * n + i] * u[j * us];
+    u[i * us] = s;
+  }
+}
+// entry l = row * ncols + q: X = Z - Y u (first) or X += Z - Y u; with F == 0 there is no u and X = Z or X += Z
+MH_HD void pgo_cov_apply(const PgoGraph & g, const PgoCov & cov, bool first, size_t l)
+{
+  const int row = static_cast<int>(l / cov.ncols), q = static_cast<int>(l % cov.ncols);
+  const double s = pgo_apply_value(g, cov.Z[l], cov.U + q, cov.ncols, row);
+  cov.X[l] = first ? s : cov.X[l] + s;
+}
+// entry l of the residual E_j - A X into Z
+MH_HD void pgo_cov_residual(const PgoGraph & g, const PgoCov & cov, size_t l)
+{
+  const int row = static_cast<int>(l / cov.ncols), q = static_cast<int>(l % cov.ncols);
+  cov.Z[l] = pgo_residual_value(g, row, row == pgo_cov_unit(cov, q) ? 1.0 : 0.0, cov.X + q, cov.ncols);
+}
+// entry l < 144 n_pairs of joint: [[S_ii, S_ij], [S_ij^T, S_jj]], the diagonal blocks cov's bits, S_ij block row i of the pair's
+// columns (zero when either pose is fixed)
+MH_HD void pgo_cov_joint(const PgoGraph & g, const PgoCov & cov, int l)
+{
+  const int p = l / 144, r = (l % 144) / 12, c = l % 12, i = cov.pairs[2 * p], j = cov.pairs[2 * p + 1];
+  double v;
+  if (r < 6 && c < 6)
+    v = cov.S[36 * i + 6 * r + c];
+  else if (r >= 6 && c >= 6)
+    v = cov.S[36 * j + 6 * (r - 6) + c - 6];
+  else if (g.fixed[i] || g.fixed[j])
+    v = 0.0;
+  else if (r < 6)
+    v = cov.X[static_cast<size_t>(6 * i + r) * cov.ncols + 6 * p + c - 6];
+  else
+    v = cov.X[static_cast<size_t>(6 * i + c) * cov.ncols + 6 * p + r - 6];
+  cov.joint[l] = v;
+}
+// the columns of every pair as the host runs them (the kernels: one launch per line)
+inline void pgo_cov_column(const PgoGraph & g, const PgoCov & cov)
+{
+  const size_t entries = static_cast<size_t>(6 * g.N) * cov.ncols;
+  for (int step = 0; step < 3; ++step) {
+    if (step > 0)
+      for (size_t l = 0; l < entries; ++l) pgo_cov_residual(g, cov, l);
+    for (int q = 0; q < cov.ncols; ++q) pgo_cov_sweep(g, cov, q, step == 0);
+    if (g.F > 0)
+      for (int q = 0; q < cov.ncols; ++q) pgo_cov_solve(g, cov, q);
+    for (size_t l = 0; l < entries; ++l) pgo_cov_apply(g, cov, step == 0, l);
+  }
+}
+
+// ---- the host's whole covariance call (tests/cpp/pose_graph_cov_step.cpp): the kernels' launches as loops -------------------------
+// The system as pgo_iterate_host assembles it, up to C's factor; then the chain, the correction, the pairs.  sm: the larger of
+// 114, kPgoCovChainSm and pgo_cov_correct_sm(F) doubles.  Returns 0, or 4: a pivot was not positive (cov's arrays are not written).
+inline int pgo_cov_host(const PgoGraph & g, const PgoParams & p, const PgoCov & cov, double * sm)
+{
+  WindowSerial par;
+  g.st->stopped = 0;
+  for (int j = 0; j < g.E + g.P; ++j) pgo_term(g, j, false);
+  for (int l = 0; l < kPgoGather * g.N; ++l) pgo_gather(g, p, l);
+  g.st->ok = 1;
+  for (int f = 0; f < g.F; ++f)
+    if (!pgo_far_info(g, f)) g.st->ok = 0;
+  if (!g.st->ok || !pgo_factor(g, sm, par)) return 4;
+  for (int c = 0; c < g.K; ++c) pgo_sweep_col(g, c, nullptr, g.Y + c, g.K);
+  if (g.F > 0) pgo_small(g, 0, par);
+  if (!g.st->ok) return 4;
+  pgo_cov_chain(g, cov, sm, par);
+  for (int i = 0; i < g.N; ++i) pgo_cov_correct(g, cov, i, sm, par);
+  if (cov.n_pairs > 0) {
+    pgo_cov_column(g, cov);
+    for (int l = 0; l < 144 * cov.n_pairs; ++l) pgo_cov_joint(g, cov, l);
+  }
+  return 0;
 }
 
 }  // namespace mh

@@ -167,4 +167,121 @@ hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it,
   return hipGetLastError();
 }
 
+// ---- mh_pose_graph_covariances -------------------------------------------------------------------------------------------------------
+// Behind an iteration's launches up to the stage-0 pgo_small_kernel (T's factors, Y, C's factor):
+//   pgo_cov_chain_kernel    one wave: P_i = (T^-1)_ii, N dependent 6 x 6 steps backwards.  Block i - 1's L, D and G_i (78 doubles)
+//                           are loaded into registers before the arithmetic of block i and put into LDS behind it, so that no
+//                           step waits for global memory; P_{i+1} stays in LDS.
+//   pgo_cov_correct_kernel  one wave per pose: Sigma_ii = P_i - U^T D_C^-1 U; U and a panel of C's factor in LDS
+//   per pair column (one lane per column, or per entry of the columns):
+//     pgo_cov_sweep_kernel, pgo_cov_solve_kernel (F > 0), pgo_cov_apply_kernel, then twice pgo_cov_residual_kernel and the three again
+//   pgo_cov_joint_kernel    one lane per entry of joint
+// Every kernel returns at once when a pivot was not positive (PgoState::ok == 0).
+__global__ __launch_bounds__(64) void pgo_cov_chain_kernel(const PgoGraph g, const PgoCov cov)
+{
+  __shared__ double s_m[kPgoCovChainSm];
+  __shared__ double s_blk[2][78];  // L_i (36), D_i (6), G_{i+1} (36) of the current block and of the next one
+  if (!g.st->ok) return;
+  const int lane = static_cast<int>(threadIdx.x), N = g.N;
+  double *Si = s_m, *M = s_m + 36, *Pc = s_m + 72;
+  // entry k < 78 of block i: L_i, D_i, G_{i+1} (behind the last block: G_{N-1}, which pgo_cov_step1/2 do not read).  ONE load from
+  // a selected address per lane: three loads under three lane masks into one register would each wait for the one before.
+  auto load = [&](int i, int k) -> double {
+    const double * p = k < 36 ? g.L + 36 * i + k : (k < 42 ? g.Dv + 6 * i + (k - 36) : g.G + 36 * (i + 1 < N ? i + 1 : i) + (k - 42));
+    return *p;
+  };
+  s_blk[0][lane] = load(N - 1, lane);
+  if (lane < 14) s_blk[0][64 + lane] = load(N - 1, 64 + lane);
+  __syncthreads();
+  int cur = 0;
+  for (int i = N - 1; i >= 0; --i) {
+    const bool last = i == N - 1;
+    double n0 = 0.0, n1 = 0.0;
+    if (i > 0) {
+      n0 = load(i - 1, lane);
+      if (lane < 14) n1 = load(i - 1, 64 + lane);
+    }
+    const double *Lb = s_blk[cur], *Db = s_blk[cur] + 36, *Gn = s_blk[cur] + 42;
+    if (lane < 42) pgo_cov_step1(Lb, Db, Gn, Pc, last, Si, M, lane);
+    __syncthreads();
+    // (before phase 2: the wait for the prefetch then stands in front of phase 2's stores of P_i, not behind them)
+    s_blk[cur ^ 1][lane] = n0;
+    if (lane < 14) s_blk[cur ^ 1][64 + lane] = n1;
+    if (lane < 36) pgo_cov_step2(Gn, Si, M, last, Pc, cov.P + 36 * i, lane);
+    __syncthreads();
+    cur ^= 1;
+  }
+}
+
+__global__ __launch_bounds__(64) void pgo_cov_correct_kernel(const PgoGraph g, const PgoCov cov)
+{
+  __shared__ double s_m[6 * kPgoFarMax * (6 + kPgoCovPanel)];
+  if (!g.st->ok) return;
+  PgoGroup<64> par{static_cast<int>(threadIdx.x)};
+  pgo_cov_correct(g, cov, static_cast<int>(blockIdx.x), s_m, par);
+}
+
+__global__ __launch_bounds__(64) void pgo_cov_sweep_kernel(const PgoGraph g, const PgoCov cov, const int first)
+{
+  if (!g.st->ok) return;
+  const int q = static_cast<int>(blockIdx.x) * 64 + static_cast<int>(threadIdx.x);
+  if (q < cov.ncols) pgo_cov_sweep(g, cov, q, first != 0);
+}
+
+__global__ __launch_bounds__(64) void pgo_cov_solve_kernel(const PgoGraph g, const PgoCov cov)
+{
+  if (!g.st->ok) return;
+  const int q = static_cast<int>(blockIdx.x) * 64 + static_cast<int>(threadIdx.x);
+  if (q < cov.ncols) pgo_cov_solve(g, cov, q);
+}
+
+__global__ __launch_bounds__(kPgoLanes) void pgo_cov_apply_kernel(const PgoGraph g, const PgoCov cov, const int first)
+{
+  if (!g.st->ok) return;
+  const size_t l = static_cast<size_t>(blockIdx.x) * kPgoLanes + threadIdx.x;
+  if (l < static_cast<size_t>(6 * g.N) * cov.ncols) pgo_cov_apply(g, cov, first != 0, l);
+}
+
+__global__ __launch_bounds__(kPgoLanes) void pgo_cov_residual_kernel(const PgoGraph g, const PgoCov cov)
+{
+  if (!g.st->ok) return;
+  const size_t l = static_cast<size_t>(blockIdx.x) * kPgoLanes + threadIdx.x;
+  if (l < static_cast<size_t>(6 * g.N) * cov.ncols) pgo_cov_residual(g, cov, l);
+}
+
+__global__ __launch_bounds__(kPgoLanes) void pgo_cov_joint_kernel(const PgoGraph g, const PgoCov cov)
+{
+  if (!g.st->ok) return;
+  const int l = static_cast<int>(blockIdx.x) * kPgoLanes + static_cast<int>(threadIdx.x);
+  if (l < 144 * cov.n_pairs) pgo_cov_joint(g, cov, l);
+}
+
+// the whole chain of a covariance call behind whatever is on the stream (g.st zeroed by the caller)
+hipError_t launch_pgo_covariances(const PgoGraph & g, const PgoParams & p, const PgoCov & cov, hipStream_t stream)
+{
+  if (g.N < 1 || g.N > kPgoMaxPoses || g.E < 0 || g.E > kPgoMaxEdges || g.P < 0 || g.P > kPgoMaxPoses || g.F < 0 || g.F > kPgoFarMax || g.K != 6 * g.F + 1 ||
+      cov.n_pairs < 0 || cov.n_pairs > kPgoCovPairsMax || cov.ncols != 6 * cov.n_pairs)
+    return hipErrorInvalidValue;
+  hipError_t e = launch_pgo_edges(g, false, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(pgo_gather_kernel, dim3((kPgoGather * g.N + kPgoLanes - 1) / kPgoLanes), dim3(kPgoLanes), 0, stream, g, p);
+  hipLaunchKernelGGL(pgo_factor_kernel, dim3(1), dim3(64), 0, stream, g);
+  hipLaunchKernelGGL(pgo_sweep_kernel, dim3((g.K + 63) / 64), dim3(64), 0, stream, g, 0);
+  if (g.F > 0) hipLaunchKernelGGL(pgo_small_kernel, dim3(1), dim3(kPgoLanes), 0, stream, g, 0);
+  hipLaunchKernelGGL(pgo_cov_chain_kernel, dim3(1), dim3(64), 0, stream, g, cov);
+  hipLaunchKernelGGL(pgo_cov_correct_kernel, dim3(g.N), dim3(64), 0, stream, g, cov);
+  if (cov.n_pairs > 0) {
+    const dim3 cols((cov.ncols + 63) / 64);
+    const dim3 entries(static_cast<unsigned>((static_cast<size_t>(6 * g.N) * cov.ncols + kPgoLanes - 1) / kPgoLanes));
+    for (int step = 0; step < 3; ++step) {
+      if (step > 0) hipLaunchKernelGGL(pgo_cov_residual_kernel, entries, dim3(kPgoLanes), 0, stream, g, cov);
+      hipLaunchKernelGGL(pgo_cov_sweep_kernel, cols, dim3(64), 0, stream, g, cov, step == 0 ? 1 : 0);
+      if (g.F > 0) hipLaunchKernelGGL(pgo_cov_solve_kernel, cols, dim3(64), 0, stream, g, cov);
+      hipLaunchKernelGGL(pgo_cov_apply_kernel, entries, dim3(kPgoLanes), 0, stream, g, cov, step == 0 ? 1 : 0);
+    }
+    hipLaunchKernelGGL(pgo_cov_joint_kernel, dim3((144 * cov.n_pairs + kPgoLanes - 1) / kPgoLanes), dim3(kPgoLanes), 0, stream, g, cov);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace mh

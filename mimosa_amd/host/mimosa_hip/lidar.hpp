@@ -838,10 +838,136 @@ public:
     ctx_->check(mh_pose_graph_optimise(pg_, &cfg, &out, trace_poses ? trace_poses->data() : nullptr), "mh_pose_graph_optimise");
     return out;
   }
+  // Sigma = A^-1 at the stored poses (rule 10 of the header): cov takes 36 doubles per pose, block (i, i) row-major in
+  // (rotation, translation) order.  flags == 4 in the result: a pivot was not positive and the library wrote nothing into cov (it
+  // has been resized to 36 n; what it holds is not a result).  Nothing moves.
+  mh_pose_graph_cov_info covariances(double damping, std::vector<double> * cov)
+  {
+    mh_pose_graph_cov_info info{};
+    cov->resize(36 * n_);
+    ctx_->check(mh_pose_graph_covariances(pg_, damping, cov->data(), nullptr, 0, nullptr, &info), "mh_pose_graph_covariances");
+    return info;
+  }
+  // the 12 x 12 joint [[S_ii, S_ij], [S_ij^T, S_jj]] of up to MH_PGO_COV_PAIRS_MAX pairs i < j, 144 doubles each; cov optional
+  mh_pose_graph_cov_info jointCovariances(double damping, const std::vector<std::pair<int32_t, int32_t>> & pairs, std::vector<double> * joint,
+                                          std::vector<double> * cov = nullptr)
+  {
+    mh_pose_graph_cov_info info{};
+    std::vector<int32_t> ij;
+    for (const auto & p : pairs) {
+      ij.push_back(p.first);
+      ij.push_back(p.second);
+    }
+    joint->resize(144 * pairs.size());
+    if (cov) cov->resize(36 * n_);
+    if (pairs.empty()) return cov ? covariances(damping, cov) : info;
+    ctx_->check(mh_pose_graph_covariances(pg_, damping, cov ? cov->data() : nullptr, ij.data(), pairs.size(), joint->data(), &info), "mh_pose_graph_covariances");
+    return info;
+  }
+  // One candidate loop against the joint marginal of its two poses: the residual r of rule 1 at the stored poses, the plain
+  // chi2 = r^T Om r, and d2 = r^T (J S J^T + Om^-1)^-1 r with J = [J_a | I] — chi^2 with 6 degrees of freedom for a true loop,
+  // whatever the drift between the two poses.  valid == false: a pivot was not positive (d2 is not computed).
+  struct Gate
+  {
+    std::array<double, 6> r{};
+    double chi2 = 0.0, d2 = 0.0;
+    bool valid = false;
+  };
+  // up to MH_PGO_COV_PAIRS_MAX candidates that are NOT in the graph.  Small host arithmetic on jointCovariances.
+  std::vector<Gate> gate(const std::vector<mh_window_edge> & candidates, double damping = 0.0)
+  {
+    std::vector<std::pair<int32_t, int32_t>> pairs;
+    for (const auto & e : candidates) pairs.emplace_back(e.pose_a, e.pose_b);
+    std::vector<double> joint;
+    const mh_pose_graph_cov_info info = jointCovariances(damping, pairs, &joint);
+    const std::vector<PoseRM> T = poses();
+    std::vector<Gate> out(candidates.size());
+    for (size_t k = 0; k < candidates.size(); ++k) {
+      const mh_window_edge & e = candidates[k];
+      const PoseRM &A = T[static_cast<size_t>(e.pose_a)], &B = T[static_cast<size_t>(e.pose_b)];
+      double abR[9], abt[3], J[6][12] = {}, M[6][6], x[6];
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) abR[3 * r + c] = A.R[r] * B.R[c] + A.R[3 + r] * B.R[3 + c] + A.R[6 + r] * B.R[6 + c];
+        abt[r] = A.R[r] * (B.t[0] - A.t[0]) + A.R[3 + r] * (B.t[1] - A.t[1]) + A.R[6 + r] * (B.t[2] - A.t[2]);
+      }
+      // r = [Log(Z.R^T R_ab), Z.R^T (t_ab - Z.t)]
+      double Re[9];
+      Gate & g = out[k];
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Re[3 * r + c] = e.Z_R[r] * abR[c] + e.Z_R[3 + r] * abR[3 + c] + e.Z_R[6 + r] * abR[6 + c];
+        g.r[static_cast<size_t>(3 + r)] = e.Z_R[r] * (abt[0] - e.Z_t[0]) + e.Z_R[3 + r] * (abt[1] - e.Z_t[1]) + e.Z_R[6 + r] * (abt[2] - e.Z_t[2]);
+      }
+      const double cs = std::min(1.0, std::max(-1.0, (Re[0] + Re[4] + Re[8] - 1.0) / 2.0)), th = std::acos(cs), s = th < 1e-9 ? 0.5 : th / (2.0 * std::sin(th));
+      g.r[0] = (Re[7] - Re[5]) * s;
+      g.r[1] = (Re[2] - Re[6]) * s;
+      g.r[2] = (Re[3] - Re[1]) * s;
+      // J_a = -Ad(T_ab^-1): R_i = R_ab^T, t_i = -R_ab^T t_ab; Ad = [[R_i, 0], [hat(t_i) R_i, R_i]];  J_b = I
+      double Ri[9], ti[3];
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Ri[3 * r + c] = abR[3 * c + r];
+        ti[r] = -(abR[r] * abt[0] + abR[3 + r] * abt[1] + abR[6 + r] * abt[2]);
+      }
+      const double hat[9] = {0.0, -ti[2], ti[1], ti[2], 0.0, -ti[0], -ti[1], ti[0], 0.0};
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+          J[r][c] = J[3 + r][3 + c] = -Ri[3 * r + c];
+          J[3 + r][c] = -(hat[3 * r] * Ri[c] + hat[3 * r + 1] * Ri[3 + c] + hat[3 * r + 2] * Ri[6 + c]);
+        }
+      for (int r = 0; r < 6; ++r) J[r][6 + r] = 1.0;
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) g.chi2 += g.r[static_cast<size_t>(r)] * e.info[6 * r + c] * g.r[static_cast<size_t>(c)];
+      if (info.flags != 0) continue;
+      // M = J S J^T + Om^-1, then M x = r: both by Gauss-Jordan with partial pivoting on 6 x 6
+      const double * S = &joint[144 * k];
+      double JS[6][12] = {}, W[6][12];
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 12; ++c)
+          for (int m = 0; m < 12; ++m) JS[r][c] += J[r][m] * S[12 * m + c];
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) {
+          W[r][c] = e.info[6 * r + c];
+          W[r][6 + c] = r == c ? 1.0 : 0.0;
+        }
+      if (!eliminate6(W, 12)) continue;
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) {
+          M[r][c] = W[r][6 + c];
+          for (int m = 0; m < 12; ++m) M[r][c] += JS[r][m] * J[c][m];
+        }
+      for (int r = 0; r < 6; ++r) {
+        for (int c = 0; c < 6; ++c) W[r][c] = M[r][c];
+        W[r][6] = g.r[static_cast<size_t>(r)];
+      }
+      if (!eliminate6(W, 7)) continue;
+      for (int r = 0; r < 6; ++r) x[r] = W[r][6];
+      for (int r = 0; r < 6; ++r) g.d2 += g.r[static_cast<size_t>(r)] * x[r];
+      g.valid = true;
+    }
+    return out;
+  }
   size_t size() const { return n_; }
   mh_pose_graph * underlying() { return pg_; }
 
 private:
+  // [A | B] (6 rows, `cols` columns) -> [I | A^-1 B] by Gauss-Jordan with partial pivoting; false: A is singular
+  static bool eliminate6(double W[6][12], int cols)
+  {
+    for (int j = 0; j < 6; ++j) {
+      int piv = j;
+      for (int r = j + 1; r < 6; ++r)
+        if (std::fabs(W[r][j]) > std::fabs(W[piv][j])) piv = r;
+      if (!(std::fabs(W[piv][j]) > 0.0)) return false;
+      for (int c = 0; c < cols; ++c) std::swap(W[j][c], W[piv][c]);
+      const double d = W[j][j];
+      for (int c = 0; c < cols; ++c) W[j][c] /= d;
+      for (int r = 0; r < 6; ++r) {
+        if (r == j) continue;
+        const double f = W[r][j];
+        for (int c = 0; c < cols; ++c) W[r][c] -= f * W[j][c];
+      }
+    }
+    return true;
+  }
   std::shared_ptr<Context> ctx_;  // (declared first: the graph goes before its context)
   mh_pose_graph * pg_ = nullptr;
   size_t n_ = 0, n_edges_ = 0, n_priors_ = 0;
