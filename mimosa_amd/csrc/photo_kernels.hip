@@ -966,8 +966,10 @@ __device__ __forceinline__ void photo_linearize_feature(const PhotoLinLaunch & W
       } else if (fabs(static_cast<double>(fr.range[static_cast<size_t>(ry) * m.cols + rx]) - rng) >
                  static_cast<double>(m.occlusion_range_diff_threshold)) {
         st = PS_RANGE_DIFF;
-      } else if (ux > m.cols - 2 || uy > m.rows - 2) {
-        st = PS_PROJECT_UNDISTORTED;  // bilinear footprint outside the image: the reference's getSubPixelValue reads out of bounds
+      } else if (ux >= m.cols - 1 || uy >= m.rows - 1) {
+        // bilinear footprint (floor + 1) outside the image: the reference's getSubPixelValue reads out of bounds.  Between the last
+        // two rows / columns it is inside and the reference samples it (reachable with margin_size < 2).
+        st = PS_PROJECT_UNDISTORTED;
       } else {
         Ib = bilinear(fr.intensity, m.cols, ux, uy);
       }
