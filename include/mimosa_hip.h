@@ -941,7 +941,8 @@ int mh_icp_window_marginalise_joint_async(mh_icp * const * icps, size_t W, const
  *    on their other end.  `damping` is added to every diagonal entry of the free poses.  The system is A xi = -g.
  * 3. Every sum of a pose's block row is taken over the pose's edges in edge-list order; nothing is added by atomics.
  *    f = sum_{l < 256} (sum_k c[l + 256 k]), c[e] = r^T Om r of edge e, k and l ascending: the same bits whatever the launch.
- * 4. The edges are split into near ones (pose_b - pose_a == 1) and far ones (>= 2; at most MH_PGO_FAR_MAX of them, else
+ * 4. The edges are split into near ones (pose_b - pose_a == 1) and far ones (>= 2; at most MH_PGO_FAR_MAX of them on a graph of
+ *    mh_pose_graph_create, at most max_far (1 .. MH_PGO_FAR_LIMIT) on a graph of mh_pose_graph_create_wide, else
  *    MH_ERR_UNSUPPORTED).  A = T + sum_f W_f^T Om_f W_f: T block-tridiagonal (near edges, damping, the identity rows), W_f the
  *    6 x 6n matrix with J_a in block column a and I in block column b of far edge f (the block column of a fixed pose
  *    zeroed).  With Y = T^-1 [W^T | -g] and C = blockdiag(Om_f^-1) + W Y (6F x 6F) the step is xi = y - Y C^-1 W y, followed by
@@ -999,6 +1000,19 @@ int mh_icp_window_marginalise_joint_async(mh_icp * const * icps, size_t W, const
  *    relative error is about cond(A) x 1e-16 — 2e-7 on an open chain of 4 096 poses whose largest variance is 3e3 m^2, where
  *    the joint of two neighbours far from the anchor is no longer positive semi-definite to rounding.  One chain of launches
  *    on the context's stream and one wait.
+ * 11. A wide graph (mh_pose_graph_create_wide) is a graph like any other: every call takes it.  Whenever it holds a far edge it
+ *    builds, factorises and solves C in blocks over many workgroups, with the same arithmetic.  Build: entry (i, k), i >= k, of C
+ *    starts as the plain graph forms it: the row of W times column k of Y in the row's order, with the Om_f^-1 entry added in
+ *    front on the diagonal blocks.  Factor: for j ascending, D_j = C[j][j], under the pivot test d > 0 && d < 1e300;
+ *    U[j][i] = C[i][j] and L[i][j] = C[i][j] / D_j for i > j; C[i][k] -= L[i][j] * U[j][k] for i >= k > j, the product rounded
+ *    first, then subtracted.  Solve: u[i] -= L[i][j] * u[j], j ascending; u[j] /= D_j; u[i] -= L[j][i] * u[j], j descending.
+ *    Apply: s -= Y[row][c] * u[c], c ascending.  Every entry's operations therefore come in an order of their own, and any
+ *    schedule that keeps that order per entry gives the same bits, whether blocked, tiled or spread over any number of
+ *    workgroups.  A wide graph's result has the bits the unblocked phases give; on a graph of at most MH_PGO_FAR_MAX far edges
+ *    it therefore has the bits of a plain graph.  No FMA contraction, no MFMA, no floating-point atomics, no sums across lanes.
+ *    mh_pose_graph_covariances on a graph that holds more than MH_PGO_FAR_MAX far edges: MH_ERR_UNSUPPORTED, nothing written;
+ *    on a wide graph that holds at most that many it gives the plain graph's bits.  An allocation that fails is an error of
+ *    mh_pose_graph_create_wide with nothing kept: Y of a 4 096 x 512 graph is 604 MB, its C 75 MB.
  *
  * mh_pose_graph_set_poses copies n poses (1 .. max_poses); with an n other than the last one it also drops the edges, the
  * fixed flags, the priors and the losses.  mh_pose_graph_set_fixed: n flags (NULL: none fixed).  mh_pose_graph_set_edges replaces the edge list (n_edges
@@ -1023,12 +1037,14 @@ int mh_icp_window_marginalise_joint_async(mh_icp * const * icps, size_t W, const
  * not finite or an asymmetric info; more priors than max_poses; a loss kind outside 0 .. 3; a kind 1 .. 3 whose param is not
  * finite and positive; edge losses given before edges were set; mh_pose_graph_covariances with a NULL info, with cov and
  * joint both NULL, with n_pairs > 0 and pairs or joint NULL, n_pairs above MH_PGO_COV_PAIRS_MAX, a pair with i < 0, i >= j or
- * j >= n.  MH_ERR_UNSUPPORTED: more than MH_PGO_FAR_MAX far edges.  A graph belongs to its
+ * j >= n; max_far outside 1 .. MH_PGO_FAR_LIMIT.  MH_ERR_UNSUPPORTED: more than MH_PGO_FAR_MAX far edges (a wide graph: more
+ * than its max_far, the message names max_far); covariances of a graph that holds more than MH_PGO_FAR_MAX.  A graph belongs to its
  * context; after mh_shutdown of the context every call but mh_pose_graph_destroy refuses it.
  * Not here: an asynchronous form, the sharded path. */
 #define MH_PGO_MAX_POSES 4096
 #define MH_PGO_MAX_EDGES 32768
 #define MH_PGO_FAR_MAX 32 /* edges with pose_b - pose_a >= 2 */
+#define MH_PGO_FAR_LIMIT 512 /* ... on a graph of mh_pose_graph_create_wide */
 
 typedef struct mh_pose_graph mh_pose_graph;
 
@@ -1054,6 +1070,8 @@ typedef struct mh_pose_graph_result {
 } mh_pose_graph_result;
 
 int mh_pose_graph_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_pose_graph ** out);
+/* rule 11 */
+int mh_pose_graph_create_wide(mh_ctx * ctx, size_t max_poses, size_t max_edges, size_t max_far /* 1 .. MH_PGO_FAR_LIMIT */, mh_pose_graph ** out);
 void mh_pose_graph_destroy(mh_pose_graph * pg);
 int mh_pose_graph_set_poses(mh_pose_graph * pg, const double * R /* 9 n */, const double * t /* 3 n */, size_t n);
 int mh_pose_graph_set_fixed(mh_pose_graph * pg, const uint8_t * fixed /* n, NULL = none */);
@@ -1093,7 +1111,7 @@ typedef struct mh_pose_graph_cov_info {
   int32_t flags;   /* 0, or 4: a pivot of T, of an Om_f or of C was not positive (no output written) */
 } mh_pose_graph_cov_info; /* 16 bytes */
 
-/* rule 10.  The graph's far edges are within MH_PGO_FAR_MAX: mh_pose_graph_set_edges refuses a list with more (MH_ERR_UNSUPPORTED). */
+/* rule 10.  The graph's far edges are within MH_PGO_FAR_MAX: a wide graph that holds more is refused (MH_ERR_UNSUPPORTED, rule 11). */
 int mh_pose_graph_covariances(mh_pose_graph * pg, double damping, double * cov /* 36 n, or NULL */,
                               const int32_t * pairs /* 2 n_pairs: i, j with i < j; or NULL */, size_t n_pairs /* 0 .. MH_PGO_COV_PAIRS_MAX */,
                               double * joint /* 144 n_pairs, or NULL */, mh_pose_graph_cov_info * info);

@@ -47,7 +47,7 @@ SOURCES = [
     ("reloc_api.hip", []),
     ("place_kernels.hip", ["-ffp-contract=off"]),  # likewise place_device.hpp (tests/cpp/place_device_check.cpp)
     ("place_api.hip", []),
-    ("pose_graph_kernels.hip", ["-ffp-contract=off"]),  # likewise pose_graph_device.hpp (tests/cpp/pose_graph_step.cpp)
+    ("pose_graph_kernels.hip", ["-ffp-contract=off"]),  # likewise pose_graph_device.hpp (tests/cpp/pose_graph_step.cpp, pose_graph_wide_step.cpp)
     ("pose_graph_api.hip", []),
 ]
 HEADERS = ["icp_device.hpp", "flagged_word.hpp", "align_device.hpp", "window_device.hpp", "wave_dpp.hpp", "scan_device.hpp", "math3.hpp", "voxel_map.hpp", "voxel_group.hpp", "mh_internal.hpp", "photo_device.hpp", "map_device.hpp", "shard_device.hpp", "exact_sort.hpp", "radar_device.hpp", "reloc_device.hpp", "carve_device.hpp", "place_device.hpp", "pose_graph_device.hpp", "window_request.hpp", "rebuild_plan.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]
@@ -222,6 +222,7 @@ HOST_TESTS = {
     "place_device_check": ("place_device_check.cpp", ["place_device.hpp", "math3.hpp"]),
     "pose_graph_step": ("pose_graph_step.cpp", ["pose_graph_device.hpp", "window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "pose_graph_robust_step": ("pose_graph_robust_step.cpp", ["pose_graph_device.hpp", "window_device.hpp", "align_device.hpp", "math3.hpp"]),
+    "pose_graph_wide_step": ("pose_graph_wide_step.cpp", ["pose_graph_device.hpp", "window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "pose_graph_cov_step": ("pose_graph_cov_step.cpp", ["pose_graph_device.hpp", "window_device.hpp", "align_device.hpp", "math3.hpp"]),
     "rebuild_plan_check": ("rebuild_plan_check.cpp", ["rebuild_plan.hpp"]),
     "window_request_check": ("window_request_check.cpp", ["window_request.hpp", "rebuild_plan.hpp", os.path.join("..", "..", "include", "mimosa_hip.h")]),

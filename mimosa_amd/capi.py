@@ -32,7 +32,7 @@ EXPORTS = [
     "mh_pose_graph_create", "mh_pose_graph_destroy", "mh_pose_graph_set_poses", "mh_pose_graph_set_fixed", "mh_pose_graph_set_edges",
     "mh_pose_graph_get_poses", "mh_pose_graph_residuals", "mh_pose_graph_optimise",
     "mh_pose_graph_set_priors", "mh_pose_graph_set_loss", "mh_pose_graph_prior_residuals", "mh_pose_graph_weights",
-    "mh_pose_graph_covariances",
+    "mh_pose_graph_covariances", "mh_pose_graph_create_wide",
     "mh_keyframes_create", "mh_keyframes_destroy", "mh_keyframes_size", "mh_keyframes_get_info", "mh_keyframes_add", "mh_keyframes_add_device",
     "mh_keyframes_add_from_scan", "mh_keyframes_get", "mh_keyframes_device_points", "mh_map_rebuild_from_keyframes",
     "mh_icp_window_optimise", "mh_icp_window_optimise_async", "mh_icp_window_wait",
@@ -762,6 +762,7 @@ def load(build_if_missing: bool = True):
     L.mh_place_db_query.argtypes = [vp, vp, sz, C.c_int32, vp, vp]
     L.mh_place_db_query_from_scan.argtypes = [vp, vp, i32, vp, sz, C.c_int32, vp, vp]
     L.mh_pose_graph_create.argtypes = [vp, sz, sz, pvp]
+    L.mh_pose_graph_create_wide.argtypes = [vp, sz, sz, sz, pvp]
     L.mh_pose_graph_destroy.argtypes = [vp]
     L.mh_pose_graph_destroy.restype = None
     L.mh_pose_graph_set_poses.argtypes = [vp, vp, vp, sz]
@@ -2271,6 +2272,7 @@ def place_relocalise(factor, hits, keyframe_poses, cfg: RelocConfig = None, R_G_
 
 # ---- pose graph over all keyframes (mh_pose_graph_*) ----------------------------------------------------------------------------
 MH_PGO_MAX_POSES, MH_PGO_MAX_EDGES, MH_PGO_FAR_MAX = 4096, 32768, 32
+MH_PGO_FAR_LIMIT = 512
 
 
 class PoseGraphConfig(C.Structure):
@@ -2352,12 +2354,16 @@ def make_pose_graph_config(iters=16, check_every=0, damping=0.0, eps_rot=1e-9, e
 
 class PoseGraph:
     """A pose graph over all keyframes, optimised on the device (mh_pose_graph_*): poses (world from keyframe), relative-pose
-    edges in the shape the window chains take them, a fixed flag per pose."""
+    edges in the shape the window chains take them, a fixed flag per pose.  max_far (1 .. MH_PGO_FAR_LIMIT): a wide graph
+    (mh_pose_graph_create_wide), which takes that many far edges; None: at most MH_PGO_FAR_MAX."""
 
-    def __init__(self, ctx: Context, max_poses, max_edges):
+    def __init__(self, ctx: Context, max_poses, max_edges, max_far=None):
         self.ctx, self.L = ctx, ctx.L
         h = C.c_void_p()
-        ctx.check(self.L.mh_pose_graph_create(ctx.h, int(max_poses), int(max_edges), C.byref(h)))
+        if max_far is None:
+            ctx.check(self.L.mh_pose_graph_create(ctx.h, int(max_poses), int(max_edges), C.byref(h)))
+        else:
+            ctx.check(self.L.mh_pose_graph_create_wide(ctx.h, int(max_poses), int(max_edges), int(max_far), C.byref(h)))
         self.h = h
         self.n = self.n_edges = self.n_priors = 0
         ctx._children += 1

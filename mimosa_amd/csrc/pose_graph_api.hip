@@ -18,20 +18,24 @@ static_assert(MH_PGO_LOSS_NONE == mh::kPgoLossNone && MH_PGO_LOSS_HUBER == mh::k
                 MH_PGO_LOSS_DCS == mh::kPgoLossDcs,
               "MH_PGO_LOSS_*");
 static_assert(sizeof(mh_pose_graph_cov_info) == 16 && MH_PGO_COV_PAIRS_MAX == mh::kPgoCovPairsMax, "mh_pose_graph_cov_info layout");
-static_assert(MH_PGO_MAX_POSES == mh::kPgoMaxPoses && MH_PGO_MAX_EDGES == mh::kPgoMaxEdges && MH_PGO_FAR_MAX == mh::kPgoFarMax && mh::kPgoMaxIters == 64,
+static_assert(MH_PGO_MAX_POSES == mh::kPgoMaxPoses && MH_PGO_MAX_EDGES == mh::kPgoMaxEdges && MH_PGO_FAR_MAX == mh::kPgoFarMax && MH_PGO_FAR_LIMIT == mh::kPgoFarLimit &&
+                mh::kPgoMaxIters == 64,
               "mh_pose_graph_* constants");
 
 namespace mh
 {
 hipError_t launch_pgo_edges(const PgoGraph & g, bool want_res, hipStream_t stream);
 hipError_t launch_pgo_cost(const PgoGraph & g, bool chi2, hipStream_t stream);
-hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream);
+hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream, int far_cap,
+                                bool wide);
 hipError_t launch_pgo_covariances(const PgoGraph & g, const PgoParams & p, const PgoCov & cov, hipStream_t stream);
 }  // namespace mh
 
 struct mh_pose_graph final : CtxOwned
 {
   size_t max_poses = 0, max_edges = 0;
+  size_t max_far = MH_PGO_FAR_MAX;  // far edges the arrays are laid out for
+  bool wide = false;                // mh_pose_graph_create_wide: C in blocks (launch_pgo_iteration)
   size_t n = 0, n_edges = 0, n_far = 0, n_priors = 0;
   size_t off[mh::kPgArrays] = {};
   mh::PgoGraph g{};          // device pointers into mem.block
@@ -81,13 +85,15 @@ hipError_t pgo_up(mh_pose_graph * pg, size_t & at, T * dst, const T * src, size_
   return e;
 }
 
-int pgo_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_pose_graph ** out)
+int pgo_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, size_t max_far, bool wide, mh_pose_graph ** out)
 {
   MH_HIP(ctx, mh_enter(ctx));
   mh_pose_graph * pg = new mh_pose_graph;
   pg->max_poses = max_poses;
   pg->max_edges = max_edges;
-  const size_t bytes = mh::pgo_layout(max_poses, std::max<size_t>(max_edges, 1), pg->off);
+  pg->max_far = max_far;
+  pg->wide = wide;
+  const size_t bytes = mh::pgo_layout(max_poses, std::max<size_t>(max_edges, 1), pg->off, max_far);
   hipError_t e = pg->mem.block.alloc(bytes);
   if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&pg->h_words), mh::kPgoMaxIters * sizeof(uint4), hipHostMallocMapped);
   if (e == hipSuccess) {
@@ -101,7 +107,7 @@ int pgo_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_pose_graph *
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) {
     delete pg;
-    return hip_fail(ctx, e, "mh_pose_graph_create");
+    return hip_fail(ctx, e, wide ? "mh_pose_graph_create_wide" : "mh_pose_graph_create");
   }
   ctx_register(pg, ctx);
   *out = pg;
@@ -129,7 +135,10 @@ int pgo_check_edges(const mh_pose_graph * pg, const mh_window_edge * edges, size
     if (!exactly_symmetric(q.info, 6, 6)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_set_edges: an edge's info is not symmetric");
     if (q.pose_b - q.pose_a >= 2) ++n_far;
   }
-  if (n_far > MH_PGO_FAR_MAX) return fail(ctx, MH_ERR_UNSUPPORTED, "mh_pose_graph_set_edges: more than MH_PGO_FAR_MAX edges with pose_b - pose_a >= 2");
+  if (!pg->wide && n_far > MH_PGO_FAR_MAX)
+    return fail(ctx, MH_ERR_UNSUPPORTED, "mh_pose_graph_set_edges: more than MH_PGO_FAR_MAX edges with pose_b - pose_a >= 2");
+  if (n_far > pg->max_far)
+    return fail(ctx, MH_ERR_UNSUPPORTED, "mh_pose_graph_set_edges: more than max_far (" + std::to_string(pg->max_far) + ") edges with pose_b - pose_a >= 2");
   return MH_OK;
 }
 
@@ -147,8 +156,9 @@ int pgo_set_edges(mh_pose_graph * pg, const mh_window_edge * edges, size_t E, si
     std::memcpy(&Zt[3 * e], q.Z_t, sizeof(q.Z_t));
     std::memcpy(&Om[36 * e], q.info, sizeof(q.info));
   }
-  far.resize(mh::kPgoFarMax);
-  (void)mh::pgo_index_edges(static_cast<int>(N), static_cast<int>(E), ea.data(), eb.data(), slot.data(), inc_off.data(), inc.data(), far.data());
+  far.resize(pg->max_far);
+  (void)mh::pgo_index_edges(static_cast<int>(N), static_cast<int>(E), ea.data(), eb.data(), slot.data(), inc_off.data(), inc.data(), far.data(),
+                            static_cast<int>(pg->max_far));
   MH_HIP(ctx, mh_enter(ctx));
   const int rc = pgo_host(pg, (48 * E + 5 * E + N + 1 + n_far) * 8 + 16 * 16);
   if (rc != MH_OK) return rc;
@@ -220,7 +230,7 @@ int pgo_optimise(mh_pose_graph * pg, const mh_pose_graph_config * cfg, mh_pose_g
     const int upto = std::min(queued + chunk, iters);
     for (; e == hipSuccess && queued < upto; ++queued)
       e = mh::launch_pgo_iteration(g, p, queued, trace_poses ? d_trace + static_cast<size_t>(queued) * 12 * N : nullptr, pg->d_words + queued,
-                                   seq[queued], ctx->stream);
+                                   seq[queued], ctx->stream, static_cast<int>(pg->max_far), pg->wide);
     if (e != hipSuccess || queued == iters) break;
     // the last queued iteration's word: the value itself, then the stream behind it
     if (!pgo_read_word(pg, queued - 1, seq[queued - 1], 50000000L, flags)) {
@@ -484,7 +494,20 @@ int mh_pose_graph_create(mh_ctx * ctx, size_t max_poses, size_t max_edges, mh_po
     if (max_poses < 1 || max_poses > MH_PGO_MAX_POSES) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create: max_poses must be in 1..4096");
     if (max_edges > MH_PGO_MAX_EDGES) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create: max_edges must be in 0..32768");
     if (!ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create: NULL argument");
-    return pgo_create(ctx, max_poses, max_edges, out);
+    return pgo_create(ctx, max_poses, max_edges, MH_PGO_FAR_MAX, false, out);
+  });
+}
+
+int mh_pose_graph_create_wide(mh_ctx * ctx, size_t max_poses, size_t max_edges, size_t max_far, mh_pose_graph ** out)
+{
+  if (out) *out = nullptr;
+  if (!out) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create_wide: NULL argument");
+  return guarded(ctx, "mh_pose_graph_create_wide", [&]() -> int {
+    if (max_poses < 1 || max_poses > MH_PGO_MAX_POSES) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create_wide: max_poses must be in 1..4096");
+    if (max_edges > MH_PGO_MAX_EDGES) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create_wide: max_edges must be in 0..32768");
+    if (max_far < 1 || max_far > MH_PGO_FAR_LIMIT) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create_wide: max_far must be in 1..512");
+    if (!ctx) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_create_wide: NULL argument");
+    return pgo_create(ctx, max_poses, max_edges, max_far, true, out);
   });
 }
 
@@ -659,6 +682,8 @@ int mh_pose_graph_covariances(mh_pose_graph * pg, double damping, double * cov, 
     if (n_pairs && (!pairs || !joint)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: pairs and joint must be given with n_pairs > 0");
     if (!(damping >= 0.0) || !std::isfinite(damping)) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: damping must be >= 0 and finite");
     if (pg->n == 0) return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: no poses have been set");
+    if (pg->n_far > MH_PGO_FAR_MAX)
+      return fail(ctx, MH_ERR_UNSUPPORTED, "mh_pose_graph_covariances: the graph holds more than MH_PGO_FAR_MAX edges with pose_b - pose_a >= 2");
     for (size_t p = 0; p < n_pairs; ++p)
       if (pairs[2 * p] < 0 || pairs[2 * p] >= pairs[2 * p + 1] || static_cast<size_t>(pairs[2 * p + 1]) >= pg->n)
         return fail(ctx, MH_ERR_INVALID_ARG, "mh_pose_graph_covariances: pair " + std::to_string(p) + " needs 0 <= i < j < n");

@@ -3,7 +3,8 @@
 // the retraction are the window chains' (window_device.hpp: window_between_dense, window_so3log, window_adjoint,
 // window_solve6, align_retract), used here and not restated.
 //
-// The edges are split into near ones (pose_b - pose_a == 1) and far ones (>= 2; at most kPgoFarMax).  The system is
+// The edges are split into near ones (pose_b - pose_a == 1) and far ones (>= 2; at most kPgoFarMax, on a
+// graph created wide at most its max_far <= kPgoFarLimit: the section "a wide graph" below).  The system is
 //   A = T + sum_f W_f^T Om_f W_f,
 // T block-tridiagonal (near edges, damping, identity rows of the fixed poses), W_f the 6 x 6N matrix with J_a in block column
 // a and I in block column b of far edge f (a block column of a fixed pose zeroed).  It is solved as
@@ -38,6 +39,10 @@ namespace mh
 constexpr int kPgoMaxPoses = 4096;
 constexpr int kPgoMaxEdges = 32768;
 constexpr int kPgoFarMax = 32;
+constexpr int kPgoFarLimit = 512;  // far edges of a graph created wide (mh_pose_graph_create_wide)
+constexpr int kPgoWideNB = 64;     // panel width of the blocked phases of C: diagonal blocks, strips and tiles are NB x NB
+constexpr int kPgoWideLd = 65;     // row stride of a block that is read down a column (one block in a workgroup's LDS)
+constexpr int kPgoWideSm = 2 * kPgoWideNB * kPgoWideNB;  // doubles a blocked phase shares (the host's buffer, the kernel's LDS: 64 KiB)
 constexpr int kPgoFold = 256;   // partial sums of the cost fold (a constant of the rule, not of a launch)
 constexpr int kPgoMaxIters = 64;
 constexpr int kPgoGather = 78;  // outputs per pose of pgo_gather: 36 of A_ii, 36 of E_i, 6 of the right-hand side
@@ -67,6 +72,7 @@ struct PgoGraph
   double *L, *Dv, *G;                      // S_i = L D L^T, G_i = S_{i-1}^-1 E_i^T
   double *Y;                               // 6 N x K, row-major
   double *C, *u;                           // 6 F x 6 F (lower: L, diagonal: D, upper: L D), 6 F
+  double * v;                              // 6 F: the blocked solve's second vector (pgo_wide_forward / _backward)
   double *x, *r, *y1, *d;                  // 6 N each (d: the step norms of pgo_finish)
   double *fold;                            // 3 x kPgoFold
   PgoRow * rows;                           // kPgoMaxIters
@@ -97,19 +103,19 @@ enum PgoArray
   kPgR, kPgT, kPgZR, kPgZt, kPgOm, kPgBaa, kPgEba, kPgGa, kPgGb, kPgCz, kPgRes, kPgJa, kPgOmL, kPgOmD, kPgOmInv, kPgA, kPgEb, kPgRhs, kPgL,
   kPgDv, kPgG, kPgY, kPgC, kPgU, kPgX, kPgRr, kPgY1, kPgD, kPgFold, kPgRows, kPgEa, kPgEbI, kPgSlot, kPgIncOff, kPgInc, kPgFar, kPgFixed, kPgSt,
   kPgW, kPgRho, kPgLParam, kPgLKind, kPgPZR, kPgPZt, kPgPOm, kPgPH, kPgPG, kPgPRes, kPgPCz, kPgPW, kPgPRho, kPgPLParam, kPgPLKind, kPgPPose,
-  kPgPIncOff, kPgPInc,
+  kPgPIncOff, kPgPInc, kPgV,
   kPgArrays
 };
-inline size_t pgo_layout(size_t maxN, size_t maxE, size_t off[kPgArrays])
+inline size_t pgo_layout(size_t maxN, size_t maxE, size_t off[kPgArrays], size_t maxF = kPgoFarMax)
 {
-  const size_t F = kPgoFarMax, K = 6 * F + 1, D = sizeof(double), I = sizeof(int);
+  const size_t F = maxF, K = 6 * F + 1, D = sizeof(double), I = sizeof(int);
   const size_t bytes[kPgArrays] = {9 * maxN * D, 3 * maxN * D, 9 * maxE * D, 3 * maxE * D, 36 * maxE * D, 36 * maxE * D, 36 * maxE * D, 6 * maxE * D,
                                    6 * maxE * D, maxE * D, 6 * maxE * D, 36 * F * D, 36 * F * D, 6 * F * D, 36 * F * D, 36 * maxN * D, 36 * maxN * D,
                                    6 * maxN * D, 36 * maxN * D, 6 * maxN * D, 36 * maxN * D, 6 * maxN * K * D, 36 * F * F * D, 6 * F * D, 6 * maxN * D,
                                    6 * maxN * D, 6 * maxN * D, 6 * maxN * D, 3 * kPgoFold * D, kPgoMaxIters * sizeof(PgoRow), maxE * I, maxE * I, maxE * I,
                                    (maxN + 1) * I, 2 * maxE * I, F * I, maxN, sizeof(PgoState),
                                    maxE * D, maxE * D, maxE * D, maxE * I, 9 * maxN * D, 3 * maxN * D, 36 * maxN * D, 36 * maxN * D, 6 * maxN * D,
-                                   6 * maxN * D, maxN * D, maxN * D, maxN * D, maxN * D, maxN * I, maxN * I, (maxN + 1) * I, maxN * I};
+                                   6 * maxN * D, maxN * D, maxN * D, maxN * D, maxN * D, maxN * I, maxN * I, (maxN + 1) * I, maxN * I, 6 * F * D};
   size_t at = 0;
   for (int k = 0; k < kPgArrays; ++k) {
     off[k] = at;
@@ -134,19 +140,20 @@ inline void pgo_bind(PgoGraph & g, char * base, const size_t off[kPgArrays])
   g.pZR = dp(kPgPZR), g.pZt = dp(kPgPZt), g.pOm = dp(kPgPOm), g.pH = dp(kPgPH), g.pg = dp(kPgPG), g.pres = dp(kPgPRes), g.pcz = dp(kPgPCz);
   g.pw = dp(kPgPW), g.prho = dp(kPgPRho), g.plparam = dp(kPgPLParam), g.plkind = ip(kPgPLKind), g.ppose = ip(kPgPPose);
   g.pinc_off = ip(kPgPIncOff), g.pinc = ip(kPgPInc);
+  g.v = dp(kPgV);
 }
 
 // host: the index arrays of an edge list (ea, eb: E entries, 0 <= ea < eb < N) — every edge's far slot (-1: near), the far
 // edges in list order, and per pose its incidence list in edge-list order.  Returns the number of far edges; `far` takes
-// kPgoFarMax entries at most (the caller refuses a list with more before it gets here).
-inline int pgo_index_edges(int N, int E, const int * ea, const int * eb, int * eslot, int * inc_off, int * inc, int * far)
+// far_cap entries at most (the caller refuses a list with more before it gets here).
+inline int pgo_index_edges(int N, int E, const int * ea, const int * eb, int * eslot, int * inc_off, int * inc, int * far, int far_cap = kPgoFarMax)
 {
   int F = 0;
   for (int i = 0; i <= N; ++i) inc_off[i] = 0;
   for (int e = 0; e < E; ++e) {
     eslot[e] = -1;
     if (eb[e] - ea[e] >= 2) {
-      if (F < kPgoFarMax) far[F] = e;
+      if (F < far_cap) far[F] = e;
       eslot[e] = F++;
     }
     ++inc_off[ea[e] + 1];
@@ -655,6 +662,219 @@ inline int pgo_iterate_host(const PgoGraph & g, const PgoParams & p, int it, dou
     for (int stage = 0; stage < 3 && g.st->ok; ++stage) {
       if (stage > 0) pgo_sweep_col(g, 0, g.r, g.y1, 1);
       pgo_small(g, stage, par);
+      if (!g.st->ok) break;
+      for (int row = 0; row < 6 * g.N; ++row) pgo_apply_row(g, stage ? g.y1 : g.Y + 6 * g.F, stage ? 1 : g.K, stage == 0, row);
+      if (stage < 2)
+        for (int row = 0; row < 6 * g.N; ++row) pgo_residual_row(g, row);
+    }
+  }
+  pgo_finish(g, p, it, trace, par);
+  return g.rows[it].flags;
+}
+
+// ---- a wide graph (mh_pose_graph_create_wide): C built, factorised and solved in blocks ------------------------------------------
+// The arithmetic is pgo_factor_C's and pgo_solve_C's, entry by entry: entry (i, k), i >= k, of C starts as pgo_factor_C forms it
+// (pgo_W_row in its order, the OmInv entry added in front on the diagonal blocks); for j ascending D_j = C[j][j] under the pivot
+// test, U[j][i] = C[i][j] and L[i][j] = C[i][j] / D_j for i > j, and C[i][k] -= L[i][j] * U[j][k] for i >= k > j, the product
+// rounded, then subtracted; the solve is u[i] -= L[i][j] * u[j] with j ascending, u[j] /= D_j, u[i] -= L[j][i] * u[j] with j
+// descending.  Every entry's operations come in an order of their own, and a schedule that keeps that order per entry gives
+// the same bits.  The schedule here: panels of NB = kPgoWideNB columns.  Panel p takes its diagonal block (pgo_wide_diag: the
+// steps j of the panel on the block itself), then the strip of rows under it (pgo_wide_strip: the same steps on those rows, which
+// leaves their U and L), then every tile behind it (pgo_wide_trail: the panel's NB products of an entry, j ascending).  An entry
+// has then seen every j of panels 0 .. p in ascending order when panel p + 1 begins.  Each of the three is a function of a block,
+// strip or tile index; a phase that needs ALL of the phase before it is a launch of its own.  sm: kPgoWideSm doubles.
+MH_HD int pgo_wide_blocks(int n) { return (n + kPgoWideNB - 1) / kPgoWideNB; }
+
+// tile (ti, tk), tk <= ti, of C's lower triangle as pgo_factor_C forms it (the upper triangle is not read before U is written)
+template <typename Par>
+MH_HD void pgo_wide_build(const PgoGraph & g, int ti, int tk, Par & par)
+{
+  constexpr int NB = kPgoWideNB;
+  const int n = 6 * g.F, K = g.K;
+  par.each(NB * NB, [&](int l) {
+    const int row = ti * NB + l / NB, col = tk * NB + l % NB;
+    if (row >= n || col > row) return;
+    double s = pgo_W_row(g, row, g.Y + col, K);
+    if (row / 6 == col / 6) s = g.OmInv[36 * (row / 6) + 6 * (row % 6) + col % 6] + s;
+    g.C[row * n + col] = s;
+  });
+}
+
+// diagonal block p, one workgroup: pgo_factor_C's steps j = NB p .. on the block itself.  false (g.st->ok == 0): a pivot is not positive.
+template <typename Par>
+MH_HD bool pgo_wide_diag(const PgoGraph & g, int p, double * sm, Par & par)
+{
+  constexpr int NB = kPgoWideNB, LD = kPgoWideLd;
+  const int n = 6 * g.F, j0 = p * NB, nb = n - j0 < NB ? n - j0 : NB;
+  par.each(nb * nb, [&](int l) {
+    const int r = l / nb, c = l % nb;
+    if (c <= r) sm[r * LD + c] = g.C[(j0 + r) * n + j0 + c];
+  });
+  for (int j = 0; j < nb; ++j) {
+    par.each(1, [&](int) {
+      const double d = sm[j * LD + j];
+      if (!(d > 0.0) || !(d < 1e300)) g.st->ok = 0;
+    });
+    if (!g.st->ok) return false;
+    par.each(nb - j - 1, [&](int l) {
+      const int i = j + 1 + l;
+      const double t = sm[i * LD + j];
+      sm[j * LD + i] = t;
+      sm[i * LD + j] = t / sm[j * LD + j];
+    });
+    const int m = nb - j - 1;
+    par.each(m * m, [&](int l) {
+      const int i = j + 1 + l / m, k = j + 1 + l % m;
+      if (k > i) return;
+      sm[i * LD + k] -= sm[i * LD + j] * sm[j * LD + k];
+    });
+  }
+  par.each(nb * nb, [&](int l) { g.C[(j0 + l / nb) * n + j0 + l % nb] = sm[(l / nb) * LD + l % nb]; });
+  return true;
+}
+
+// strip s of the rows under diagonal block p (rows NB (p + 1 + s) ..): the panel's steps on those rows.  The strip lives in sm by
+// columns (entry (r, c) at [c NB + r]: a step reads and writes down a column), the diagonal block's U and D by rows.
+template <typename Par>
+MH_HD void pgo_wide_strip(const PgoGraph & g, int p, int s, double * sm, Par & par)
+{
+  constexpr int NB = kPgoWideNB;
+  const int n = 6 * g.F, j0 = p * NB, i0 = j0 + NB * (1 + s), nr = n - i0 < NB ? n - i0 : NB;
+  if (nr <= 0) return;
+  double *Bd = sm, *St = sm + NB * NB;
+  par.each(NB * NB, [&](int l) {
+    const int r = l / NB, c = l % NB;
+    if (c >= r) Bd[l] = g.C[(j0 + r) * n + j0 + c];
+  });
+  par.each(nr * NB, [&](int l) { St[(l % NB) * NB + l / NB] = g.C[(i0 + l / NB) * n + j0 + l % NB]; });
+  for (int j = 0; j < NB; ++j) {
+    par.each(nr, [&](int r) {
+      const double t = St[j * NB + r];
+      g.C[(j0 + j) * n + i0 + r] = t;
+      St[j * NB + r] = t / Bd[j * NB + j];
+    });
+    par.each(nr * (NB - j - 1), [&](int l) {
+      const int r = l % nr, k = j + 1 + l / nr;
+      St[k * NB + r] -= St[j * NB + r] * Bd[j * NB + k];
+    });
+  }
+  par.each(nr * NB, [&](int l) { g.C[(i0 + l / NB) * n + j0 + l % NB] = St[(l % NB) * NB + l / NB]; });
+}
+
+// tile (ti, tk), tk <= ti, of the blocks behind panel p: every entry takes the panel's NB products, j ascending
+template <typename Par>
+MH_HD void pgo_wide_trail(const PgoGraph & g, int p, int ti, int tk, double * sm, Par & par)
+{
+  constexpr int NB = kPgoWideNB;
+  const int n = 6 * g.F, j0 = p * NB, i0 = j0 + NB * (1 + ti), k0 = j0 + NB * (1 + tk);
+  const int nr = n - i0 < NB ? n - i0 : NB, nc = n - k0 < NB ? n - k0 : NB;
+  if (nr <= 0 || nc <= 0 || tk > ti) return;
+  double *Lp = sm, *Up = sm + NB * NB;
+  par.each(nr * NB, [&](int l) { Lp[l] = g.C[(i0 + l / NB) * n + j0 + l % NB]; });
+  par.each(NB * nc, [&](int l) { Up[(l / nc) * NB + l % nc] = g.C[(j0 + l / nc) * n + k0 + l % nc]; });
+  par.each(nr * nc, [&](int l) {
+    const int r = l / nc, c = l % nc, i = i0 + r, k = k0 + c;
+    if (k > i) return;
+    double t = g.C[i * n + k];
+    for (int j = 0; j < NB; ++j) t -= Lp[r * NB + j] * Up[j * NB + c];
+    g.C[i * n + k] = t;
+  });
+}
+
+// u = C^-1 W y in blocks, pgo_solve_C's sums in its order.  Forward step of panel p: block p's entries have taken every j in front
+// of the block; they take the block's own j (every workgroup for itself, in LDS), then strip s of the rows behind the block takes
+// the panel's NB products, j ascending.  p == 0 starts from pgo_W_row.  Strip 0 also leaves the block's entries, divided by D_j, in
+// g.v: g.u's block is read by every strip of this launch and written by none.
+template <typename Par>
+MH_HD void pgo_wide_forward(const PgoGraph & g, const double * y, int stride, int p, int s, double * sm, Par & par)
+{
+  constexpr int NB = kPgoWideNB, LD = kPgoWideLd;
+  const int n = 6 * g.F, j0 = p * NB, nb = n - j0 < NB ? n - j0 : NB;
+  double *ub = sm, *Ld = sm + NB;
+  par.each(nb, [&](int i) { ub[i] = p == 0 ? pgo_W_row(g, j0 + i, y, stride) : g.u[j0 + i]; });
+  par.each(nb * nb, [&](int l) {
+    const int r = l / nb, c = l % nb;
+    if (c <= r) Ld[r * LD + c] = g.C[(j0 + r) * n + j0 + c];
+  });
+  for (int j = 0; j + 1 < nb; ++j) par.each(nb - j - 1, [&](int l) { ub[j + 1 + l] -= Ld[(j + 1 + l) * LD + j] * ub[j]; });
+  if (s == 0) par.each(nb, [&](int i) { g.v[j0 + i] = ub[i] / Ld[i * LD + i]; });
+  const int i0 = j0 + NB * (1 + s), nr = n - i0 < NB ? n - i0 : NB;
+  if (nr <= 0) return;
+  par.each(nr * NB, [&](int l) { Ld[(l / NB) * LD + l % NB] = g.C[(i0 + l / NB) * n + j0 + l % NB]; });
+  par.each(nr, [&](int r) {
+    double t = p == 0 ? pgo_W_row(g, i0 + r, y, stride) : g.u[i0 + r];
+    for (int j = 0; j < NB; ++j) t -= Ld[r * LD + j] * ub[j];
+    g.u[i0 + r] = t;
+  });
+}
+// Backward step of panel p (p descending): block p's entries of g.v have taken every j behind the block; they take the block's own
+// j, descending, then strip s of the rows in front of the block (rows NB s ..) takes the panel's products, j descending.  Strip
+// 0 leaves the block's entries, now final, in g.u.
+template <typename Par>
+MH_HD void pgo_wide_backward(const PgoGraph & g, int p, int s, double * sm, Par & par)
+{
+  constexpr int NB = kPgoWideNB, LD = kPgoWideLd;
+  const int n = 6 * g.F, j0 = p * NB, nb = n - j0 < NB ? n - j0 : NB;
+  double *vb = sm, *Ld = sm + NB;
+  par.each(nb, [&](int i) { vb[i] = g.v[j0 + i]; });
+  par.each(nb * nb, [&](int l) {
+    const int r = l / nb, c = l % nb;
+    if (c < r) Ld[r * LD + c] = g.C[(j0 + r) * n + j0 + c];
+  });
+  for (int j = nb - 1; j >= 1; --j) par.each(j, [&](int i) { vb[i] -= Ld[j * LD + i] * vb[j]; });
+  if (s == 0) par.each(nb, [&](int i) { g.u[j0 + i] = vb[i]; });
+  const int i0 = NB * s;
+  if (i0 >= j0) return;
+  par.each(NB, [&](int r) {
+    double t = g.v[i0 + r];
+    for (int j = nb - 1; j >= 0; --j) t -= g.C[(j0 + j) * n + i0 + r] * vb[j];
+    g.v[i0 + r] = t;
+  });
+}
+
+// the phases of pgo_small on a wide graph as the host runs them (the kernels: one launch per line of a loop over blocks)
+inline void pgo_small_wide_host(const PgoGraph & g, int stage, double * sm)
+{
+  WindowSerial par;
+  const int nt = pgo_wide_blocks(6 * g.F);
+  if (stage == 0) {
+    for (int ti = 0; ti < nt; ++ti)
+      for (int tk = 0; tk <= ti; ++tk) pgo_wide_build(g, ti, tk, par);
+    for (int p = 0; p < nt; ++p) {
+      if (!pgo_wide_diag(g, p, sm, par)) return;
+      for (int s = 0; s < nt - p - 1; ++s) pgo_wide_strip(g, p, s, sm, par);
+      for (int ti = 0; ti < nt - p - 1; ++ti)
+        for (int tk = 0; tk <= ti; ++tk) pgo_wide_trail(g, p, ti, tk, sm, par);
+    }
+  }
+  const double * y = stage == 0 ? g.Y + 6 * g.F : g.y1;
+  const int stride = stage == 0 ? g.K : 1;
+  for (int p = 0; p < nt; ++p)
+    for (int s = 0; s < (nt - p - 1 > 1 ? nt - p - 1 : 1); ++s) pgo_wide_forward(g, y, stride, p, s, sm, par);
+  for (int p = nt - 1; p >= 0; --p)
+    for (int s = 0; s < (p > 1 ? p : 1); ++s) pgo_wide_backward(g, p, s, sm, par);
+}
+
+// the host's whole iteration of a wide graph (tests/cpp/pose_graph_wide_step.cpp): pgo_iterate_host with the blocked phases in
+// pgo_small's place whenever the graph holds a far edge; `blocked` false runs pgo_small itself on the same arrays (the parity
+// test's other side).  sm: kPgoWideSm doubles.
+inline int pgo_iterate_wide_host(const PgoGraph & g, const PgoParams & p, int it, double * trace, double * sm, bool blocked)
+{
+  WindowSerial par;
+  if (g.st->stopped) return 1;
+  for (int j = 0; j < g.E + g.P; ++j) pgo_term(g, j, false);
+  for (int l = 0; l < kPgoGather * g.N; ++l) pgo_gather(g, p, l);
+  g.st->ok = 1;
+  for (int f = 0; f < g.F; ++f)
+    if (!pgo_far_info(g, f)) g.st->ok = 0;
+  if (g.st->ok && pgo_factor(g, sm, par)) {
+    for (int c = 0; c < g.K; ++c) pgo_sweep_col(g, c, nullptr, g.Y + c, g.K);
+    for (int stage = 0; stage < 3 && g.st->ok; ++stage) {
+      if (stage > 0) pgo_sweep_col(g, 0, g.r, g.y1, 1);
+      if (blocked && g.F > 0)
+        pgo_small_wide_host(g, stage, sm);
+      else
+        pgo_small(g, stage, par);
       if (!g.st->ok) break;
       for (int row = 0; row < 6 * g.N; ++row) pgo_apply_row(g, stage ? g.y1 : g.Y + 6 * g.F, stage ? 1 : g.K, stage == 0, row);
       if (stage < 2)

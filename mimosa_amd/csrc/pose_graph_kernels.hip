@@ -4,14 +4,14 @@
 //   pgo_edge_kernel      one lane per term: an edge (window_between_dense into per-edge rows; J_a of a far edge) or, behind the
 //                        edges, a prior (window_local, window_transport into per-prior rows); its weight and cost (pgo_loss)
 //   pgo_gather_kernel    one lane per output of a pose (78): T's blocks and the right-hand side from the incidence list
-//   pgo_factor_kernel    one wave: Om_f = L D L^T and Om_f^-1 per far edge, then T's block L D L^T, N dependent 6 x 6 steps
+//   pgo_factor_kernel    one wave: Om_f = L D L^T and Om_f^-1 per far edge (lane l: f = l, l + 64, ...), then T's block L D L^T, N dependent 6 x 6 steps
 //   pgo_sweep_kernel     one lane per column of [W^T | rhs] (6 F + 1), forward and back over the N blocks
 //   then three times (stage 0, and the two refinement steps; from the second on behind a pgo_sweep_kernel of the residual's one column):
 //     pgo_small_kernel     one workgroup: (stage 0: C and its L D L^T,) u = C^-1 W y
 //     pgo_apply_kernel     one lane per row: x = y - Y u, or x += y - Y u
 //     pgo_residual_kernel  one lane per row: rhs - A x (not behind the last step)
 //   pgo_finish_kernel    one workgroup: retraction, the cost, the trace row, the stop test
-// 15 launches.  Every kernel returns at once when the chain has stopped (PgoState::stopped) and, behind the factor kernel, when
+// 15 launches; a graph created wide runs pgo_small_kernel's work in blocks over many workgroups (below: pgo_wide_*).  Every kernel returns at once when the chain has stopped (PgoState::stopped) and, behind the factor kernel, when
 // a pivot was not positive (PgoState::ok == 0): only pgo_finish_kernel then runs, to write the row.  Everything fp64, compiled
 // without floating-point contraction so that the host build of the header gives the same digits.
 #include <hip/hip_runtime.h>
@@ -61,7 +61,8 @@ __global__ __launch_bounds__(64) void pgo_factor_kernel(const PgoGraph g)
   PgoGroup<64> par{lane};
   if (lane == 0) g.st->ok = 1;
   __syncthreads();
-  if (lane < g.F && !pgo_far_info(g, lane)) g.st->ok = 0;
+  for (int f = lane; f < g.F; f += 64)
+    if (!pgo_far_info(g, f)) g.st->ok = 0;
   __syncthreads();
   if (!g.st->ok) return;
   pgo_factor(g, s_m, par);
@@ -146,10 +147,89 @@ hipError_t launch_pgo_cost(const PgoGraph & g, bool chi2, hipStream_t stream)
   return hipGetLastError();
 }
 
-// one iteration behind whatever is on the stream
-hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream)
+// ---- a wide graph: pgo_small_kernel's work in blocks (pose_graph_device.hpp: pgo_wide_*) ------------------------------------------
+// In pgo_small_kernel's place, with nt = ceil(6 F / NB) panels:
+//   stage 0:  pgo_wide_build_kernel   a workgroup per NB x NB tile of C's lower triangle, a lane per entry (adjacent lanes adjacent in col)
+//             per panel p:  pgo_wide_diag_kernel   one workgroup: the diagonal block in LDS, the pivot test
+//                           pgo_wide_strip_kernel  a workgroup per NB rows under the block: their U and L, the block's factors in LDS
+//                           pgo_wide_trail_kernel  a workgroup per tile behind the panel, the panel's L and U operands in LDS
+//   every stage:  per panel p ascending  pgo_wide_forward_kernel   a wave per NB rows behind the block (one at least), u's block in LDS
+//                 per panel p descending pgo_wide_backward_kernel  a wave per NB rows in front of the block (one at least)
+// 1 + 3 nt - 2 launches for the factor (the last panel has neither strip nor tile), 2 nt per solve.  The work of a launch is at most
+// NB^2 steps in one workgroup, whatever F is.
+__global__ __launch_bounds__(kPgoLanes) void pgo_wide_build_kernel(const PgoGraph g)
 {
-  if (g.N < 1 || g.N > kPgoMaxPoses || g.E < 0 || g.E > kPgoMaxEdges || g.P < 0 || g.P > kPgoMaxPoses || g.F < 0 || g.F > kPgoFarMax || g.K != 6 * g.F + 1 || it < 0 || it >= kPgoMaxIters)
+  if (g.st->stopped || !g.st->ok || blockIdx.x > blockIdx.y) return;
+  PgoGroup<kPgoLanes> par{static_cast<int>(threadIdx.x)};
+  pgo_wide_build(g, static_cast<int>(blockIdx.y), static_cast<int>(blockIdx.x), par);
+}
+
+__global__ __launch_bounds__(kPgoLanes) void pgo_wide_diag_kernel(const PgoGraph g, const int p)
+{
+  __shared__ double s_m[kPgoWideNB * kPgoWideLd];
+  if (g.st->stopped || !g.st->ok) return;
+  PgoGroup<kPgoLanes> par{static_cast<int>(threadIdx.x)};
+  pgo_wide_diag(g, p, s_m, par);
+}
+
+__global__ __launch_bounds__(kPgoLanes) void pgo_wide_strip_kernel(const PgoGraph g, const int p)
+{
+  __shared__ double s_m[kPgoWideSm];
+  if (g.st->stopped || !g.st->ok) return;
+  PgoGroup<kPgoLanes> par{static_cast<int>(threadIdx.x)};
+  pgo_wide_strip(g, p, static_cast<int>(blockIdx.x), s_m, par);
+}
+
+__global__ __launch_bounds__(kPgoLanes) void pgo_wide_trail_kernel(const PgoGraph g, const int p)
+{
+  __shared__ double s_m[kPgoWideSm];
+  if (g.st->stopped || !g.st->ok || blockIdx.x > blockIdx.y) return;
+  PgoGroup<kPgoLanes> par{static_cast<int>(threadIdx.x)};
+  pgo_wide_trail(g, p, static_cast<int>(blockIdx.y), static_cast<int>(blockIdx.x), s_m, par);
+}
+
+__global__ __launch_bounds__(64) void pgo_wide_forward_kernel(const PgoGraph g, const int stage, const int p)
+{
+  __shared__ double s_m[kPgoWideNB + kPgoWideNB * kPgoWideLd];
+  if (g.st->stopped || !g.st->ok) return;
+  PgoGroup<64> par{static_cast<int>(threadIdx.x)};
+  pgo_wide_forward(g, stage ? g.y1 : g.Y + 6 * g.F, stage ? 1 : g.K, p, static_cast<int>(blockIdx.x), s_m, par);
+}
+
+__global__ __launch_bounds__(64) void pgo_wide_backward_kernel(const PgoGraph g, const int p)
+{
+  __shared__ double s_m[kPgoWideNB + kPgoWideNB * kPgoWideLd];
+  if (g.st->stopped || !g.st->ok) return;
+  PgoGroup<64> par{static_cast<int>(threadIdx.x)};
+  pgo_wide_backward(g, p, static_cast<int>(blockIdx.x), s_m, par);
+}
+
+// pgo_small_kernel's stage on a wide graph that holds a far edge
+static void launch_pgo_small_wide(const PgoGraph & g, int stage, hipStream_t stream)
+{
+  const int nt = pgo_wide_blocks(6 * g.F);
+  if (stage == 0) {
+    hipLaunchKernelGGL(pgo_wide_build_kernel, dim3(nt, nt), dim3(kPgoLanes), 0, stream, g);
+    for (int p = 0; p < nt; ++p) {
+      const int behind = nt - p - 1;
+      hipLaunchKernelGGL(pgo_wide_diag_kernel, dim3(1), dim3(kPgoLanes), 0, stream, g, p);
+      if (behind > 0) {
+        hipLaunchKernelGGL(pgo_wide_strip_kernel, dim3(behind), dim3(kPgoLanes), 0, stream, g, p);
+        hipLaunchKernelGGL(pgo_wide_trail_kernel, dim3(behind, behind), dim3(kPgoLanes), 0, stream, g, p);
+      }
+    }
+  }
+  for (int p = 0; p < nt; ++p) hipLaunchKernelGGL(pgo_wide_forward_kernel, dim3(nt - p - 1 > 1 ? nt - p - 1 : 1), dim3(64), 0, stream, g, stage, p);
+  for (int p = nt - 1; p >= 0; --p) hipLaunchKernelGGL(pgo_wide_backward_kernel, dim3(p > 1 ? p : 1), dim3(64), 0, stream, g, p);
+}
+
+// one iteration behind whatever is on the stream.  far_cap: the far edges the graph's arrays were laid out for; wide: a graph created
+// wide, which runs the blocked launches in pgo_small_kernel's place whenever it holds a far edge
+hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it, double * trace, uint4 * word, unsigned int seq, hipStream_t stream, int far_cap,
+                                bool wide)
+{
+  if (g.N < 1 || g.N > kPgoMaxPoses || g.E < 0 || g.E > kPgoMaxEdges || g.P < 0 || g.P > kPgoMaxPoses || g.F < 0 || g.F > far_cap ||
+      far_cap > (wide ? kPgoFarLimit : kPgoFarMax) || g.K != 6 * g.F + 1 || it < 0 || it >= kPgoMaxIters)
     return hipErrorInvalidValue;
   hipError_t e = launch_pgo_edges(g, false, stream);
   if (e != hipSuccess) return e;
@@ -159,7 +239,10 @@ hipError_t launch_pgo_iteration(const PgoGraph & g, const PgoParams & p, int it,
   const dim3 rows((6 * g.N + kPgoLanes - 1) / kPgoLanes);
   for (int stage = 0; stage < 3; ++stage) {
     if (stage > 0) hipLaunchKernelGGL(pgo_sweep_kernel, dim3(1), dim3(64), 0, stream, g, 1);
-    hipLaunchKernelGGL(pgo_small_kernel, dim3(1), dim3(kPgoLanes), 0, stream, g, stage);
+    if (wide && g.F > 0)
+      launch_pgo_small_wide(g, stage, stream);
+    else
+      hipLaunchKernelGGL(pgo_small_kernel, dim3(1), dim3(kPgoLanes), 0, stream, g, stage);
     hipLaunchKernelGGL(pgo_apply_kernel, rows, dim3(kPgoLanes), 0, stream, g, stage);
     if (stage < 2) hipLaunchKernelGGL(pgo_residual_kernel, rows, dim3(kPgoLanes), 0, stream, g);
   }

@@ -746,9 +746,13 @@ inline mh_pose_graph_loss poseGraphLoss(int32_t kind, double param)
 class PoseGraph
 {
 public:
-  PoseGraph(const std::shared_ptr<Context> & ctx, size_t max_poses, size_t max_edges) : ctx_(ctx)
+  // max_far 0: a plain graph (at most MH_PGO_FAR_MAX far edges); 1 .. MH_PGO_FAR_LIMIT: a wide one
+  PoseGraph(const std::shared_ptr<Context> & ctx, size_t max_poses, size_t max_edges, size_t max_far = 0) : ctx_(ctx)
   {
-    ctx_->check(mh_pose_graph_create(ctx_->get(), max_poses, max_edges, &pg_), "mh_pose_graph_create");
+    if (max_far == 0)
+      ctx_->check(mh_pose_graph_create(ctx_->get(), max_poses, max_edges, &pg_), "mh_pose_graph_create");
+    else
+      ctx_->check(mh_pose_graph_create_wide(ctx_->get(), max_poses, max_edges, max_far, &pg_), "mh_pose_graph_create_wide");
   }
   ~PoseGraph() { mh_pose_graph_destroy(pg_); }
   PoseGraph(const PoseGraph &) = delete;
